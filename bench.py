@@ -18,6 +18,9 @@ for N > 1, one rank per GPU) prints ONE JSON line on rank 0.
               instrumented pass of the same K steps; peak = 157.3 TFLOP/s dense fp32 MFMA.
 * cpu_baseline : the oracle (oracle/aether_oracle.py, PyTorch CPU restatement pinned to the
               reference) on the same batch on this host's cores, bounded to ~15 s.
+* outputs   : ``--dump-outputs DIR`` writes what the last timed step returned (``output.npy``: the
+              forward's [B*N, D] positions; with --seq2seq the fused step's five tensors) so that two
+              builds can be compared on identical inputs (the batch and the weights are seeded).
 """
 from __future__ import annotations
 
@@ -394,6 +397,33 @@ def _other_configs(dev, budget_s=10.0):
     return {"budget_s": budget_s, "block_seconds": round(time.perf_counter() - t_block, 2), "legs": out}
 
 
+DUMP_BYTES = 64 * 1000 * 1000      # --dump-outputs: at most this much in all, .npy headers included
+
+
+def _dump_outputs(path, arrays, limit=DUMP_BYTES):
+    """--dump-outputs: {name: tensor} -> path/<name>.npy, float32 (float64 stays float64).  If the arrays hold more than
+    `limit` bytes, each keeps a fixed sample of its flattened elements in proportion to its size (numpy seed 0, drawn without
+    replacement, in index order).  Returns what was written, for the result line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: (v.detach() if v.dtype == torch.float64 else v.detach().float()) for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    budget = limit - 4096 * len(arrays)
+    info = {}
+    for name, t in arrays.items():
+        n = t.numel()
+        keep = n if total <= budget else n * budget // total
+        if keep < n:
+            idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+            arr = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+        else:
+            arr = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), arr)
+        info[name] = {"shape": list(t.shape), "dtype": str(arr.dtype), "elements": int(arr.size),
+                      "sample": None if keep == n else "numpy default_rng(0).choice(numel, elements, replace=False), sorted"}
+    return info
+
+
 def _seq2seq_traffic(workload):
     """HBM bytes per launch of the filter GEMM from the committed PMC passes (profiles/traffic.json), or None."""
     try:
@@ -441,15 +471,20 @@ def _seq2seq_line(args):
         step_modules()
     torch.cuda.synchronize()
     modules_ms = (time.perf_counter() - t0) / 10 * 1e3
-    for _ in range(max(1, min(args.warmup, 5))):
+    for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    steps = max(1, min(args.steps, 50))
+    steps = args.steps
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        res = step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
+    dumped = None
+    if args.dump_outputs:
+        out, dh, (h1, c1), edges = res
+        dumped = _dump_outputs(args.dump_outputs, {"predictions": out, "decoder_hidden": dh, "prior_hidden_h": h1,
+                                                   "prior_hidden_c": c1, "edges": edges})
     # dominant kernel: the anisotropic-filter GEMM of the prior step, timed with events on the launch stream
     f, _ = m.predict_field(x)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -465,7 +500,7 @@ def _seq2seq_line(args):
     r_feat = 2 * nrf + 3 * D
     filt_flop = float(B * E) * r_feat * H * H * 2
     line = {"metric": "seq2seq autoregressive edge-steps/sec (field + prior + sample + decoder step, h=512)",
-            "value": B * E / dt, "unit": "edge-steps/s", "n_gpus": 1, "steps": steps, "warmup": min(args.warmup, 5),
+            "value": B * E / dt, "unit": "edge-steps/s", "n_gpus": 1, "steps": steps, "warmup": args.warmup,
             "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic",
             "config": {"workload": f"seq2seq-{D}d-N{N}-B{B}-h{H}", "num_dims": D, "nodes_per_graph": N,
@@ -483,6 +518,8 @@ def _seq2seq_line(args):
                                  "bf16 MFMA terms on 3-way split operands (fp32-equivalent): a fraction above 1 of the fp32-MFMA "
                                  "peak quoted here is possible; of the bf16 pipe's 2,500 TFLOP/s it is 6 x achieved / 2500"},
             "cpu_baseline": None}
+    if dumped is not None:
+        line["dump_outputs"] = dumped
     if not args.no_cpu_baseline:
         # the oracle's step on the host cores (bounded sample), which also checks the HIP step on this batch
         from oracle import seq2seq_oracle as SO
@@ -531,8 +568,12 @@ def _seq2seq_line(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default 200; 20 with --config cfg5shard / cfg5, 50 with --seq2seq)")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="warm-up steps before them (default 20; 3 with --config cfg5shard / cfg5, 5 with --seq2seq)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of hipGraph replay")
     ap.add_argument("--prewarm-ms", type=float, default=300.0,
                     help="untimed device warm-up (forward steps) before the W warm-up steps, in milliseconds; 0 = none")
@@ -578,8 +619,16 @@ def main():
             args.chunks = (hi - lo) // 32
         if args.config in ("cfg5shard", "cfg5"):      # 33.5 M edges: a step is 25 ms, the CPU legs would take minutes
             args.no_cpu_baseline, args.no_rollout = True, True
-            args.steps, args.warmup = min(args.steps, 20), min(args.warmup, 3)
+            args.steps = 20 if args.steps is None else args.steps
+            args.warmup = 3 if args.warmup is None else args.warmup
             args.big = True                           # training figure from 3 eager steps (a backward is ~0.1 s here)
+    if args.seq2seq:
+        args.steps = 50 if args.steps is None else args.steps
+        args.warmup = 5 if args.warmup is None else args.warmup
+    args.steps = 200 if args.steps is None else args.steps
+    args.warmup = 20 if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.seq2seq:
         return _seq2seq_line(args)
 
@@ -663,6 +712,7 @@ def main():
             with torch.cuda.graph(g):
                 out = call()
             step = g.replay
+            out_one = out                              # what a replay of `g` rewrites in place
             # `graph_steps` consecutive steps per hipGraph (as a rollout would be captured): the
             # launch gap between two graph replays is paid once per group instead of once per step
             S = max(1, min(args.graph_steps, args.steps))
@@ -672,6 +722,7 @@ def main():
                     for _ in range(S):
                         out = call()
                 group = gs.replay
+                out_group = out                        # the last of its S steps
             if world > 1:
                 # Guard for ranks that share one GPU (rehearsals with --share-gpu): hipGraph replays from two
                 # processes on the same device serialise pathologically (71 ms per step measured, against 0.1 ms for
@@ -696,12 +747,18 @@ def main():
             S = 1
 
         def run_steps(k):
+            """k steps; returns the output of the last one (graph replays rewrite their captured outputs)"""
+            last = None
             if S > 1:
                 for _ in range(k // S):
                     group()
+                last = out_group
                 k = k % S
             for _ in range(k):
-                step()
+                last = step()
+            if use_graph and k:
+                last = out_one
+            return last
 
         # device warm-up before the W warm-up steps of the contract: an idle MI355X takes tens of milliseconds of load to
         # reach its sustained clocks (the first 10 ms region after 20 warm-up steps ran 5-6 % slower than the regions
@@ -719,7 +776,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run_steps(args.steps)
+        last = run_steps(args.steps)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -727,6 +784,11 @@ def main():
         dt = time.perf_counter() - t0
         # graph replays never pass through a C entry point: ask for asynchronous kernel errors of the timed region here
         _lib.check(_lib.load().aether_check_async_error(), "asynchronous kernel error in the timed region")
+        dumped = None
+        if args.dump_outputs:                          # before the repeats below rewrite the same buffers
+            dumped = _dump_outputs(args.dump_outputs, {"output" if world == 1 else f"output_rank{rank}": last},
+                                   limit=DUMP_BYTES // world)
+        del last
         if world > 1:
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1064,6 +1126,8 @@ def main():
             "step_algorithmic_tflops": step_flops * world / (dt / args.steps) / 1e12,
             "roofline": roof, "roofline_other": other, "kernels": kernels, "rollout": roll, "train": train, "ranks_seen": ranks_seen,
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if world == 1 and (B, N, D) == (128, 20, 2) and not args.no_other_configs and not args.streamed:
             del out                                    # the headline's buffers are no longer needed
             line["other_configs"] = _other_configs(dev)

@@ -302,6 +302,8 @@ def dynfield_future_fixture(out_dir):
         out = {"in.inputs": inputs.numpy(), "in.uniform": U.numpy(), "ref.predictions": preds.numpy(),
                "ref.edges": edges.numpy(), "ref.summary": summary.numpy(), "ref.field": field0.numpy(),
                "ref64.summary": summary64.numpy(), "ref64.field": field64.numpy(),
+               # the fp32 sin / cos table ref64.summary was computed with: hosts round it differently by an ulp
+               "ref.pe": sd["graph_pooler.pe.pe"].numpy(),
                "seed": np.int64(DYN_SEED), "steps": np.int64(steps), "hidden_size": np.int64(H),
                "rnn_hidden": np.int64(R), "num_vars": np.int64(N), "graph_hidden": np.int64(GH),
                "mlp_hidden": np.int64(MH)}

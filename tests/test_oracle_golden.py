@@ -248,7 +248,7 @@ def test_seq2seq_predict_future():
     assert scale_rel_err(preds, t("ref.predictions")) <= 2e-6
 
 
-def test_seq2seq_dynamic_field_variant():
+def test_seq2seq_dynamic_field_variant(monkeypatch):
     """SURVEY 8f N3, seq2seq half: GraphSummary, the FiLM field query and predict_future of the imported
     reference nn.seq2seq.dynamic_field_aether.DynamicFieldAether (3-D)."""
     from conftest import load_s2s_dynfield
@@ -260,7 +260,13 @@ def test_seq2seq_dynamic_field_variant():
     gp = {k[len("graph_pooler."):]: v for k, v in sd.items() if k.startswith("graph_pooler.")}
     summary = S.graph_summary(gp, x)
     assert scale_rel_err(summary, t("ref.summary")) <= 2e-6
-    assert scale_rel_err(S.graph_summary({k: v.double() for k, v in gp.items()}, x.double()), t("ref64.summary")) <= 1e-12
+    # The reference's fp64 summary adds its fp32 sin / cos table, whose last bit depends on the host's math library
+    # (one ulp moves the fp64 result by 2e-11): this host's table is within an ulp of it, and the fp64 check uses it.
+    pe = t("ref.pe")
+    assert (S.positional_encoding(pe.shape[-1], pe.shape[1]) - pe[0]).abs().max() <= 2.0 ** -24
+    with monkeypatch.context() as m:
+        m.setattr(S, "positional_encoding", lambda d_model, length, dtype=torch.float32: pe[0, :length, :d_model].to(dtype))
+        assert scale_rel_err(S.graph_summary({k: v.double() for k, v in gp.items()}, x.double()), t("ref64.summary")) <= 1e-12
     field = S.film_field(sd, x, t("ref.summary"), 3)
     assert field.shape == x.shape[:-1] + (3,) and scale_rel_err(field, t("ref.field")) <= 2e-6
     preds, edges = S.predict_future_dynamic_field(sd, t("in.inputs"), int(d["steps"]), t("in.uniform"), 0.5, True,
