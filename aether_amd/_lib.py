@@ -105,6 +105,16 @@ SIGNATURES = {
                         [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6),
     "aether_s2s_rollout": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_float, C.c_int64, C.c_int64] + [C.c_void_p] * 4 +
                            [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3),
+    "aether_s2s_markov_decoder_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64, C.c_int64]),
+    "aether_s2s_markov_decoder_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64] +
+                                       [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p, C.c_void_p]),
+    "aether_s2s_markov_plan_bytes": (C.c_size_t, [C.c_int] * 8),
+    "aether_s2s_markov_plan_build": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "aether_s2s_markov_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_float, C.c_int64, C.c_int64] +
+                               [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5),
+    "aether_s2s_markov_rollout": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_float, C.c_int64, C.c_int64] +
+                                  [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 +
+                                  [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3),
     "aether_s2s_filter_image_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "aether_s2s_filter_prepare": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "aether_s2s_prior_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),

@@ -38,6 +38,7 @@
 #include "seq2seq.h"
 #include "s2s_filter.h"
 #include "s2s_step.h"
+#include "s2s_markov.h"
 #include "dynfield.h"
 #include "s2s_dynfield.h"
 #include "knn.h"
@@ -961,6 +962,7 @@ const char* aether_last_error(void) { return g_err; }
 
 #include "host_seq2seq.inc"
 #include "host_s2s_step.inc"
+#include "host_s2s_markov.inc"
 #include "host_dynamicvars.inc"
 #include "host_dyn_step.inc"
 #include "host_sim.inc"

@@ -17,30 +17,43 @@ struct S2SPlanLayout {
     size_t i_mlp4e, i_mlp4_3, i_ih, i_hh, i_prior[4], i_msg2[4], i_pmsg1[4], i_pmsg2[4];       // fp16 x 2 images (0: none)
     size_t i_f0, i_f2, i_mlp3_0, i_mlp3_3, i_ps, i_pr, i_a[4], i_s[4], i_wr, i_wi, i_wn, i_hh2, i_out0, i_out3;   // node-level layers
     int ldg;
+    // Markov decoder (markov_ku >= 0 used edge types; the recurrent decoder's tensors are then not in the plan): padded lin1 /
+    // res1, lin2's bias permuted from c Ku + k to k h + c, and the images of lin1 and of lin2's per-type h x h blocks
+    size_t m_l1p = 0, m_r1p = 0, m_b2 = 0, m_i_l1 = 0, m_i_l2[4] = {0, 0, 0, 0};
     static bool splittable(int M, int Kk) { return M % 128 == 0 && Kk % 32 == 0; }
-    S2SPlanLayout(int D, int he, int hd, int K, int R, int prior_layers = 1, int ph = 0) {
+    S2SPlanLayout(int D, int he, int hd, int K, int R, int prior_layers = 1, int ph = 0, int markov_ku = -1) {
         const S2SDims d(D);
+        const bool rec = markov_ku < 0;
+        const int Kr = rec ? K : 0;
+        const int64_t hr = rec ? hd : 0;
         ldg = S2S_RFG + 2 * hd;
         size_t off = 0;
         auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
         fimg = take(filt_image_bytes(d.EA, he));
         res1p = take((size_t)he * d.RFp * 4);
         bn = take((size_t)4 * he * 4);
-        for (int k = 0; k < 4; ++k) p1p[k] = take(k < K ? (size_t)hd * d.EAp * 4 : 0);
-        wr = take((size_t)hd * ldg * 4); wi = take((size_t)hd * ldg * 4); wn = take((size_t)hd * ldg * 4);
-        br = take((size_t)hd * 4); bi = take((size_t)hd * 4); bn_ = take((size_t)hd * 4);
+        for (int k = 0; k < 4; ++k) p1p[k] = take(k < Kr ? (size_t)hd * d.EAp * 4 : 0);
+        wr = take((size_t)hr * ldg * 4); wi = take((size_t)hr * ldg * 4); wn = take((size_t)hr * ldg * 4);
+        br = take((size_t)hr * 4); bi = take((size_t)hr * 4); bn_ = take((size_t)hr * 4);
         lb = take((size_t)4 * R * 4);
         lbp = take((size_t)4 * R * 4);          // the same, gates interleaved by unit (the fused LSTM cell of the split GEMM)
         auto image = [&](int M, int Kk) { return splittable(M, Kk) ? take((size_t)M * Kk * 4) : (size_t)0; };
         i_mlp4e = image(he, he); i_mlp4_3 = image(he, he); i_ih = image(4 * R, he); i_hh = image(4 * R, R);
         for (int l = 0; l < 4; ++l) i_prior[l] = l + 1 < prior_layers ? image(ph, l == 0 ? R : ph) : 0;
         for (int k = 0; k < 4; ++k) {
-            i_msg2[k] = k < K ? image(hd, hd) : 0; i_pmsg1[k] = k < K ? image(hd, d.EAp) : 0; i_pmsg2[k] = k < K ? image(hd, hd) : 0;
-            i_a[k] = k < K ? image(hd, hd) : 0; i_s[k] = k < K ? image(hd, hd) : 0;
+            i_msg2[k] = k < Kr ? image(hd, hd) : 0; i_pmsg1[k] = k < Kr ? image(hd, d.EAp) : 0; i_pmsg2[k] = k < Kr ? image(hd, hd) : 0;
+            i_a[k] = k < Kr ? image(hd, hd) : 0; i_s[k] = k < Kr ? image(hd, hd) : 0;
         }
         i_f0 = image(he, he); i_f2 = image(he, he); i_mlp3_0 = image(he, he); i_mlp3_3 = image(he, he); i_ps = image(he, he);
-        i_pr = image(he, he); i_wr = image(hd, ldg); i_wi = image(hd, ldg); i_wn = image(hd, S2S_RFG + hd); i_hh2 = image(hd, hd);
+        i_pr = image(he, he);
+        if (rec) { i_wr = image(hd, ldg); i_wi = image(hd, ldg); i_wn = image(hd, S2S_RFG + hd); i_hh2 = image(hd, hd); }
+        else i_wr = i_wi = i_wn = i_hh2 = 0;
         i_out0 = image(hd, hd); i_out3 = image(hd, hd);
+        if (!rec) {
+            m_l1p = take((size_t)hd * d.EAp * 4); m_r1p = take((size_t)hd * d.RFp * 4); m_b2 = take((size_t)markov_ku * hd * 4);
+            m_i_l1 = image(hd, d.EAp);
+            for (int k = 0; k < markov_ku && k < 4; ++k) m_i_l2[k] = image(hd, hd);
+        }
         total = off;
     }
 };
@@ -197,26 +210,28 @@ struct S2SStepArgs {
     bool field_images;         // the plan was built with the field net's parameters (images of its two hidden layers)
 };
 
-// x_in [Nn][2D], dh_in [Nn][hd], h0 / c0 [E][R], uniform [E][K] -> x_out, dh_out, h1, c1 (+ edges_out [E][K] when not null)
-int s2s_step_impl(const S2SStepArgs& a, const S2SStepLayout& L, char* ws, const float* x_in, const float* ext_field,
-                  const float* dh_in, const float* h0, const float* c0, const float* uniform, float* x_out, float* dh_out,
-                  float* h1, float* c1, float* edges_out, hipStream_t st) {
-    const int D = a.D, he = a.he, hd = a.hd, R = a.R, K = a.K, k0 = a.skip_first ? 1 : 0;
+// The half of the step both decoders share -- field query -> local frames -> prior step -> hard Gumbel sample
+// (aether.py:86-90, :384-410, :92-98) -- up to the per-type edge lists.  x_in [Nn][2D], h0 / c0 [E][R], uniform [E][K] ->
+// h1, c1, and, when `edges` is not null, the sample [E][K] with its lists / counts in the workspace (edges == nullptr: no
+// sample, the burn-in of the Markov rollout).  The decoder rides along in two launches: first_jobs(T) adds its jobs to the
+// field query's first layer (flushing T itself when it fills up), res1_jobs(T) to the prior's res1 layer, whose launch
+// holds only that job otherwise.  P: the plan's layout (recurrent or Markov, S2SPlanLayout).
+extern "C++" {                 // (a template: the including block has C linkage)
+template <class FirstJobs, class Res1Jobs>
+int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLayout& P, char* ws, const float* x_in,
+                   const float* ext_field, const float* h0, const float* c0, const float* uniform, float* h1, float* c1,
+                   float* edges, FirstJobs&& first_jobs, Res1Jobs&& res1_jobs, hipStream_t st) {
+    const int D = a.D, he = a.he, R = a.R, K = a.K, k0 = a.skip_first ? 1 : 0;
     const int64_t Nn = a.Nn, E = a.E;
     const S2SDims d(D);
-    const S2SPlanLayout P(D, he, hd, K, R, a.prior_layers, a.ph);
     auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto pl = [&](size_t off) { return reinterpret_cast<const float*>(a.plan + off); };
     auto im = [&](size_t off) { return off ? reinterpret_cast<const void*>(a.plan + off) : nullptr; };
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     const AetherS2SPriorParams* p = a.pp;
-    const AetherS2SDecoderParams* q = a.dp;
     S2SJobs T;
     const int ldg = P.ldg;
-    float* A = wp(L.A);
-    float* S = wp(L.S);
-    // ---- field query (aether.py:86-90); its first layer shares a launch with the decoder's four first-layer products of
-    // the hidden state (aether.py:596-601, receiver | sender halves of msg_fc1)
+    // ---- field query (aether.py:86-90); its first layer shares a launch with first_jobs
     T.n = 0;
     if (!ext_field) {
         const int half = he / 2;
@@ -226,14 +241,7 @@ int s2s_step_impl(const S2SStepArgs& a, const S2SStepLayout& L, char* ws, const 
         T.j[T.n++] = s2s_job(1, a.fp->w0, he, a.fp->b0, wp(L.gamma), he, wp(L.fh1), he, he, he, Nn);
         T.j[T.n - 1].Wimg = a.field_images ? im(P.i_f0) : nullptr;
     }
-    if (E > 0)
-        for (int k = k0; k < K; ++k) {
-            T.j[T.n++] = s2s_job(0, q->msg_fc1_w[k], 2 * hd, q->msg_fc1_b[k], dh_in, hd, A + (size_t)k * Nn * hd, hd, hd, hd, Nn);
-            T.j[T.n - 1].Wimg = im(P.i_a[k]);
-            T.j[T.n++] = s2s_job(0, q->msg_fc1_w[k] + hd, 2 * hd, nullptr, dh_in, hd, S + (size_t)k * Nn * hd, hd, hd, hd, Nn);
-            T.j[T.n - 1].Wimg = im(P.i_s[k]);
-            if (T.n > S2S_MAX_JOBS - 2) { if (int rc = s2s_launch_jobs(T, st)) return rc; T.n = 0; }
-        }
+    if (int rc = first_jobs(T)) return rc;
     if (int rc = s2s_launch_jobs(T, st)) return rc;
     if (!ext_field) {
         T.n = 0; T.j[T.n++] = s2s_job(1, a.fp->w2, he, a.fp->b2, wp(L.fh1), he, wp(L.fh2), he, he, he, Nn);
@@ -286,7 +294,9 @@ int s2s_step_impl(const S2SStepArgs& a, const S2SStepLayout& L, char* ws, const 
     auto one = [&](S2SJob J) { T.n = 0; T.j[T.n++] = J; return s2s_launch_jobs(T, st); };
     // + res1(rel_feat) (:395), mlp3 (RefNRIMLP, eval)
     { S2SJob J = s2s_job(0, pl(P.res1p), d.RFp, p->res1_b, wp(L.relp), d.RFp, wp(L.X0), he, he, d.RFp, Nn); J.accumulate = 1;
-      if (int rc = one(J)) return rc; }
+      T.n = 0; T.j[T.n++] = J;
+      if (int rc = res1_jobs(T)) return rc;
+      if (int rc = s2s_launch_jobs(T, st)) return rc; }
     { S2SJob J = s2s_job(4, p->mlp3_w0, he, p->mlp3_b0, wp(L.X0), he, wp(L.X1), he, he, he, Nn); J.Wimg = im(P.i_mlp3_0);
       if (int rc = one(J)) return rc; }
     { S2SJob J = s2s_job(4, p->mlp3_w3, he, p->mlp3_b3, wp(L.X1), he, wp(L.X3), he, he, he, Nn); J.post_scale = bn3s; J.post_shift = bn3b;
@@ -335,8 +345,48 @@ int s2s_step_impl(const S2SStepArgs& a, const S2SStepLayout& L, char* ws, const 
         }
     }
     // ---- hard Gumbel sample (:92-98) and the per-type edge lists of the decoder
+    if (edges != nullptr)
+        k_s2s_gumbel_select<<<blocks(E), dim3(256), 0, st>>>(wp(L.logits), uniform, a.tau, K, k0, edges, lists, counts, E);
+    return AETHER_OK;
+}
+}  // extern "C++"
+
+// x_in [Nn][2D], dh_in [Nn][hd], h0 / c0 [E][R], uniform [E][K] -> x_out, dh_out, h1, c1 (+ edges_out [E][K] when not null)
+int s2s_step_impl(const S2SStepArgs& a, const S2SStepLayout& L, char* ws, const float* x_in, const float* ext_field,
+                  const float* dh_in, const float* h0, const float* c0, const float* uniform, float* x_out, float* dh_out,
+                  float* h1, float* c1, float* edges_out, hipStream_t st) {
+    const int D = a.D, he = a.he, hd = a.hd, R = a.R, K = a.K, k0 = a.skip_first ? 1 : 0;
+    const int64_t Nn = a.Nn, E = a.E;
+    const S2SDims d(D);
+    const S2SPlanLayout P(D, he, hd, K, R, a.prior_layers, a.ph);
+    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto pl = [&](size_t off) { return reinterpret_cast<const float*>(a.plan + off); };
+    auto im = [&](size_t off) { return off ? reinterpret_cast<const void*>(a.plan + off) : nullptr; };
+    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    const AetherS2SDecoderParams* q = a.dp;
+    S2SJobs T;
+    const int ldg = P.ldg;
+    float* A = wp(L.A);
+    float* S = wp(L.S);
+    int* counts = reinterpret_cast<int*>(ws + L.counts);
+    int64_t* lists = reinterpret_cast<int64_t*>(ws + L.lists);
     float* edges = edges_out ? edges_out : wp(L.edges);
-    k_s2s_gumbel_select<<<blocks(E), dim3(256), 0, st>>>(wp(L.logits), uniform, a.tau, K, k0, edges, lists, counts, E);
+    // ---- field query, prior step, sample; the field query's first layer shares a launch with the decoder's four
+    // first-layer products of the hidden state (aether.py:596-601, receiver | sender halves of msg_fc1)
+    auto first_jobs = [&](S2SJobs& F) {
+        if (E > 0)
+            for (int k = k0; k < K; ++k) {
+                F.j[F.n++] = s2s_job(0, q->msg_fc1_w[k], 2 * hd, q->msg_fc1_b[k], dh_in, hd, A + (size_t)k * Nn * hd, hd, hd, hd, Nn);
+                F.j[F.n - 1].Wimg = im(P.i_a[k]);
+                F.j[F.n++] = s2s_job(0, q->msg_fc1_w[k] + hd, 2 * hd, nullptr, dh_in, hd, S + (size_t)k * Nn * hd, hd, hd, hd, Nn);
+                F.j[F.n - 1].Wimg = im(P.i_s[k]);
+                if (F.n > S2S_MAX_JOBS - 2) { if (int rc = s2s_launch_jobs(F, st)) return rc; F.n = 0; }
+            }
+        return (int)AETHER_OK;
+    };
+    auto no_jobs = [](S2SJobs&) { return (int)AETHER_OK; };
+    if (int rc = s2s_front_impl(a, L, P, ws, x_in, ext_field, h0, c0, uniform, h1, c1, edges, first_jobs, no_jobs, st)) return rc;
+    auto one = [&](S2SJob J) { T.n = 0; T.j[T.n++] = J; return s2s_launch_jobs(T, st); };
     // ---- decoder (:590-654): messages from the hidden states
     // (hard samples: an edge sits in at most one type's list, so the second-layer jobs below WRITE their rows of M1 / M2;
     // the rows of edges sampled as a skipped type are cleared here)
@@ -421,20 +471,11 @@ size_t aether_s2s_plan_bytes(int num_dims, int encoder_hidden, int decoder_hidde
     return S2SPlanLayout(num_dims, encoder_hidden, decoder_hidden, num_edge_types, rnn_hidden, prior_layers, prior_hidden).total;
 }
 
-int aether_s2s_plan_build(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp, const AetherS2SDecoderParams* dp, int num_dims,
-                          int encoder_hidden,
-                          int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, void* plan,
-                          size_t plan_bytes, void* stream) {
-    if (!pp || !dp || !plan) return fail(AETHER_EINVAL, "s2s_plan_build: null pointer");
-    const size_t need = aether_s2s_plan_bytes(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden,
-                                              num_edge_types);
-    if (need == 0) return fail(AETHER_EINVAL, "s2s_plan_build: bad sizes");
-    if (plan_bytes < need || ((size_t)plan & 255)) return fail(AETHER_ESPACE, "s2s_plan_build: plan buffer too small or not 256-byte aligned");
-    const int D = num_dims, he = encoder_hidden, hd = decoder_hidden, K = num_edge_types;
+namespace {
+// The prepared weights of the shared half of the step (field query, prior) into a plan of either layout.
+void s2s_plan_build_front(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp, int D, int he, int rnn_hidden,
+                          int prior_layers, int prior_hidden, const S2SPlanLayout& P, char* base, hipStream_t st) {
     const S2SDims d(D);
-    const S2SPlanLayout P(D, he, hd, K, rnn_hidden, prior_layers, prior_hidden);
-    hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)plan;
     auto fl = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     filter_images_launch(pp->filt_w2, d.EA, he, base + P.fimg, st);
@@ -443,18 +484,6 @@ int aether_s2s_plan_build(const AetherS2SFieldParams* fp, const AetherS2SPriorPa
                                                      fl(P.bn) + he, he);
     k_s2s_bn_affine<<<blocks(he), dim3(256), 0, st>>>(pp->mlp4_bn_w, pp->mlp4_bn_b, pp->mlp4_bn_mean, pp->mlp4_bn_var,
                                                      fl(P.bn) + 2 * he, fl(P.bn) + 3 * he, he);
-    for (int k = 0; k < K; ++k)
-        k_s2s_pad_rows<<<blocks((int64_t)hd * d.EAp), dim3(256), 0, st>>>(dp->pmsg_fc1_w[k], d.EA, d.EA, fl(P.p1p[k]), d.EAp, hd);
-    const int64_t gitems = (int64_t)hd * P.ldg;
-    k_s2s_concat_rows<<<blocks(gitems), dim3(256), 0, st>>>(dp->input_r_w, d.RF, S2S_RFG, dp->present_r_w, hd, dp->hidden_r_w, hd,
-                                                           fl(P.wr), P.ldg, hd);
-    k_s2s_concat_rows<<<blocks(gitems), dim3(256), 0, st>>>(dp->input_i_w, d.RF, S2S_RFG, dp->present_i_w, hd, dp->hidden_i_w, hd,
-                                                           fl(P.wi), P.ldg, hd);
-    k_s2s_concat_rows<<<blocks(gitems), dim3(256), 0, st>>>(dp->input_n_w, d.RF, S2S_RFG, dp->present_n_w, hd, nullptr, hd, fl(P.wn),
-                                                           P.ldg, hd);
-    k_s2s_add_vec<<<blocks(hd), dim3(256), 0, st>>>(dp->input_r_b, dp->present_r_b, fl(P.br), hd);
-    k_s2s_add_vec<<<blocks(hd), dim3(256), 0, st>>>(dp->input_i_b, dp->present_i_b, fl(P.bi), hd);
-    k_s2s_add_vec<<<blocks(hd), dim3(256), 0, st>>>(dp->input_n_b, dp->present_n_b, fl(P.bn_), hd);
     k_s2s_add_vec<<<blocks(4 * rnn_hidden), dim3(256), 0, st>>>(pp->lstm_b_ih, pp->lstm_b_hh, fl(P.lb), 4 * rnn_hidden);
     k_s2s_lstm_bias_interleave<<<blocks(4 * rnn_hidden), dim3(256), 0, st>>>(pp->lstm_b_ih, pp->lstm_b_hh, fl(P.lbp), rnn_hidden);
     auto image = [&](size_t off, const float* W, int M, int Kk, int ldw, int gate_units = 0) {
@@ -472,6 +501,41 @@ int aether_s2s_plan_build(const AetherS2SFieldParams* fp, const AetherS2SPriorPa
     image(P.i_mlp3_3, pp->mlp3_w3, he, he, he);
     image(P.i_ps, pp->mlp4_w0, he, he, 3 * he);
     image(P.i_pr, pp->mlp4_w0 + he, he, he, 3 * he);
+}
+}  // namespace
+
+int aether_s2s_plan_build(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp, const AetherS2SDecoderParams* dp, int num_dims,
+                          int encoder_hidden,
+                          int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, void* plan,
+                          size_t plan_bytes, void* stream) {
+    if (!pp || !dp || !plan) return fail(AETHER_EINVAL, "s2s_plan_build: null pointer");
+    const size_t need = aether_s2s_plan_bytes(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden,
+                                              num_edge_types);
+    if (need == 0) return fail(AETHER_EINVAL, "s2s_plan_build: bad sizes");
+    if (plan_bytes < need || ((size_t)plan & 255)) return fail(AETHER_ESPACE, "s2s_plan_build: plan buffer too small or not 256-byte aligned");
+    const int D = num_dims, he = encoder_hidden, hd = decoder_hidden, K = num_edge_types;
+    const S2SDims d(D);
+    const S2SPlanLayout P(D, he, hd, K, rnn_hidden, prior_layers, prior_hidden);
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)plan;
+    auto fl = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
+    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    s2s_plan_build_front(fp, pp, D, he, rnn_hidden, prior_layers, prior_hidden, P, base, st);
+    for (int k = 0; k < K; ++k)
+        k_s2s_pad_rows<<<blocks((int64_t)hd * d.EAp), dim3(256), 0, st>>>(dp->pmsg_fc1_w[k], d.EA, d.EA, fl(P.p1p[k]), d.EAp, hd);
+    const int64_t gitems = (int64_t)hd * P.ldg;
+    k_s2s_concat_rows<<<blocks(gitems), dim3(256), 0, st>>>(dp->input_r_w, d.RF, S2S_RFG, dp->present_r_w, hd, dp->hidden_r_w, hd,
+                                                           fl(P.wr), P.ldg, hd);
+    k_s2s_concat_rows<<<blocks(gitems), dim3(256), 0, st>>>(dp->input_i_w, d.RF, S2S_RFG, dp->present_i_w, hd, dp->hidden_i_w, hd,
+                                                           fl(P.wi), P.ldg, hd);
+    k_s2s_concat_rows<<<blocks(gitems), dim3(256), 0, st>>>(dp->input_n_w, d.RF, S2S_RFG, dp->present_n_w, hd, nullptr, hd, fl(P.wn),
+                                                           P.ldg, hd);
+    k_s2s_add_vec<<<blocks(hd), dim3(256), 0, st>>>(dp->input_r_b, dp->present_r_b, fl(P.br), hd);
+    k_s2s_add_vec<<<blocks(hd), dim3(256), 0, st>>>(dp->input_i_b, dp->present_i_b, fl(P.bi), hd);
+    k_s2s_add_vec<<<blocks(hd), dim3(256), 0, st>>>(dp->input_n_b, dp->present_n_b, fl(P.bn_), hd);
+    auto image = [&](size_t off, const float* W, int M, int Kk, int ldw) {
+        if (off) k_s2s_gemm_image<<<blocks((int64_t)M * (Kk / 8)), dim3(256), 0, st>>>(W, M, Kk, ldw, reinterpret_cast<f16x8*>(base + off), 0);
+    };
     image(P.i_wr, fl(P.wr), hd, P.ldg, P.ldg);
     image(P.i_wi, fl(P.wi), hd, P.ldg, P.ldg);
     image(P.i_wn, fl(P.wn), hd, S2S_RFG + hd, P.ldg);

@@ -20,6 +20,7 @@ from ... import _lib
 from .decoder import RecurrentDecoder
 from .encoder import Encoder, gumbel_softmax_hard
 from .field import FieldQuery
+from .markov import MarkovDecoder
 
 
 def _tensors_key(module):
@@ -105,12 +106,14 @@ class _RolloutRunner:
     def __call__(self, burn_in, x_last, decoder_hidden, prior_hidden, uniform):
         if self.burn is not None:
             self.burn.copy_(burn_in)
-        self.x.copy_(x_last); self.dh.copy_(decoder_hidden)
+        self.x.copy_(x_last)
+        if decoder_hidden is not None:                             # (None: the Markov decoder has no state)
+            self.dh.copy_(decoder_hidden)
         self.ph.copy_(prior_hidden[0]); self.pc.copy_(prior_hidden[1])
         self.u.copy_(uniform.reshape(self.u.shape))
         self.graph.replay()
         preds, edges, (dh, (h, c)) = self.out
-        return preds.clone(), edges.clone(), (dh.clone(), (h.clone(), c.clone()))
+        return preds.clone(), edges.clone(), (None if dh is None else dh.clone(), (h.clone(), c.clone()))
 
 
 class _StepLoop:
@@ -415,9 +418,8 @@ class Aether(_StepLoop, _EvalLoss, nn.Module):
         super().__init__()
         self.num_vars = params["num_vars"]
         self.encoder = Encoder(params, device=None)                       # creation order of aether.py:19-24,71-84
-        if params.get("decoder_type", None) == "ref_mlp":
-            raise ValueError("decoder_type 'ref_mlp' (MarkovDecoder) is not part of this path")
-        self.decoder = RecurrentDecoder(params, device=None)
+        self._markov = params.get("decoder_type", None) == "ref_mlp"
+        self.decoder = (MarkovDecoder if self._markov else RecurrentDecoder)(params, device=None)
         self.num_edge_types = params.get("num_edge_types")
         self.gumbel_temp = params.get("gumbel_temp")
         self.kl_coef = params.get("kl_coef", 1.)                      # read by the training scripts
@@ -429,6 +431,141 @@ class Aether(_StepLoop, _EvalLoss, nn.Module):
         self._fq = [fq]                                                    # not a registered sub-module: no duplicate keys
         if device is not None:
             self.to(device)
+
+    # -- the Markov decoder (decoder_type 'ref_mlp'): the fused step / rollout on the aether_s2s_markov_* entries ----------
+    def _plan(self, device):
+        if not self._markov:
+            return super()._plan(device)
+        enc, dec = self.encoder, self.decoder
+        tensors = list(enc.parameters()) + list(enc.buffers()) + list(dec.parameters()) + \
+            list(self._fq[0].field_net.parameters())
+        key = (str(device),) + tuple((t.data_ptr(), t._version) for t in tensors)
+        hit = self.__dict__.get("_plan_cache")
+        if hit is None or hit[0] != key:
+            lib = _lib.load()
+            D, he, hd, R, K = self._step_sizes()
+            skip = 1 if dec.skip_first_edge_type else 0
+            pe, n_layers, prior_hidden = enc._param_struct(with_image=False)
+            nbytes = lib.aether_s2s_markov_plan_bytes(D, he, hd, R, n_layers, prior_hidden, K, skip)
+            if nbytes == 0:
+                raise _lib.AetherHipError("fused seq2seq step: encoder_hidden must be a multiple of 128, decoder_hidden of 32")
+            buf = hit[1] if hit is not None and hit[1].numel() == nbytes and hit[1].device == torch.device(device) else \
+                torch.empty(nbytes, dtype=torch.uint8, device=device)
+            pd, pf = dec._param_struct(), self._field_struct()
+            _lib.check(lib.aether_s2s_markov_plan_build(C.byref(pf), C.byref(pe), C.byref(pd), D, he, hd, R, n_layers,
+                                                        prior_hidden, K, skip, buf.data_ptr(), nbytes,
+                                                        torch.cuda.current_stream(device).cuda_stream),
+                       "aether_s2s_markov_plan_build")
+            hit = self.__dict__["_plan_cache"] = (key, buf)
+        return hit[1]
+
+    @torch.no_grad()
+    def _fused_step(self, x, decoder_hidden, prior_hidden, uniform, field=None):
+        """As _StepLoop._fused_step; with the Markov decoder ``decoder_hidden`` is ignored and comes back as None."""
+        if not self._markov:
+            return super()._fused_step(x, decoder_hidden, prior_hidden, uniform, field)
+        if not x.is_cuda:
+            raise _lib.AetherHipError("aether_amd seq2seq models run on an MI355X only; got a CPU tensor (there is no CPU fallback)")
+        B, N, _ = x.shape
+        dev = x.device
+        lib, plan, ws, (send, recv, order, rowptr), (pf, pe, pd), scal = self._step_common(B, N, dev)
+        D, he, hd, R, K = self._step_sizes()
+        E1 = self.encoder.recv_edges.shape[0]
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+        xf, h0, c0, uf = f32(x), f32(prior_hidden[0]), f32(prior_hidden[1]), f32(uniform)
+        if xf.shape != (B, N, 2 * D) or h0.shape != (B, E1, R) or c0.shape != h0.shape or uf.numel() != B * E1 * K:
+            raise ValueError("fused step: input shapes do not match the model")
+        ff = None if field is None else f32(field)
+        out = torch.empty_like(xf)
+        h1, c1 = torch.empty_like(h0), torch.empty_like(c0)
+        edges = torch.empty(B, E1, K, dtype=torch.float32, device=dev)
+        st = lib.aether_s2s_markov_step(C.byref(pf), C.byref(pe), C.byref(pd), plan.data_ptr(), *scal, send.data_ptr(),
+                                        recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), xf.data_ptr(),
+                                        None if ff is None else ff.data_ptr(), h0.data_ptr(), c0.data_ptr(), uf.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), out.data_ptr(), h1.data_ptr(), c1.data_ptr(),
+                                        edges.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(st, "aether_s2s_markov_step")
+        return out, None, (h1, c1), edges
+
+    @torch.no_grad()
+    def _fused_rollout(self, burn_in, x_last, decoder_hidden, prior_hidden, steps, uniform, return_edges):
+        """As _StepLoop._fused_rollout; with the Markov decoder the burn-in steps run the prior only and the final decoder
+        state is None."""
+        if not self._markov:
+            return super()._fused_rollout(burn_in, x_last, decoder_hidden, prior_hidden, steps, uniform, return_edges)
+        B, N, _ = x_last.shape
+        dev = x_last.device
+        lib, plan, ws, (send, recv, order, rowptr), (pf, pe, pd), scal = self._step_common(B, N, dev)
+        D, he, hd, R, K = self._step_sizes()
+        E1 = self.encoder.recv_edges.shape[0]
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+        T0 = 0 if burn_in is None else burn_in.shape[1]
+        bi = None if T0 == 0 else f32(burn_in.transpose(0, 1))                       # [T0, B, N, 2D]
+        xl = f32(x_last)
+        h, c = f32(prior_hidden[0]).clone(), f32(prior_hidden[1]).clone()
+        if uniform is None:
+            uniform = torch.rand(T0 + steps, B, E1, K, device=dev)
+        uf = f32(uniform.reshape(T0 + steps, B, E1, K))
+        preds = torch.empty(steps, B, N, 2 * D, dtype=torch.float32, device=dev)
+        edges = torch.empty(steps, B, E1, K, dtype=torch.float32, device=dev) if return_edges else None
+        st = lib.aether_s2s_markov_rollout(C.byref(pf), C.byref(pe), C.byref(pd), plan.data_ptr(), *scal, send.data_ptr(),
+                                           recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), T0,
+                                           None if bi is None else bi.data_ptr(), int(steps), xl.data_ptr(), h.data_ptr(),
+                                           c.data_ptr(), uf.data_ptr(), ws.data_ptr(), ws.numel(), preds.data_ptr(),
+                                           None if edges is None else edges.data_ptr(),
+                                           torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(st, "aether_s2s_markov_rollout")
+        return (preds.transpose(0, 1).contiguous(), None if edges is None else edges.transpose(0, 1).contiguous(),
+                (None, (h, c)))
+
+    def _calculate_loss_eval(self, inputs, teacher_forcing, return_edges, return_logits, use_prior_logits, uniform):
+        """With the Markov decoder the teacher-forced steps do not depend on each other (no decoder state): they run as
+        ONE decoder call over (steps x B) graphs, the rest step by step as the reference's loop does (aether.py:118-140)."""
+        if not self._markov:
+            return super()._calculate_loss_eval(inputs, teacher_forcing, return_edges, return_logits, use_prior_logits,
+                                                uniform)
+        B, T, N, _ = inputs.shape
+        E, K = N * (N - 1), self.num_edge_types
+        predicted_field, field_fn = self._sequence_field(inputs)                     # [B, N, T - 1, D]
+        prior_logits, posterior_logits, _ = self.encoder(inputs[:, :-1], predicted_field)
+        logits_all = prior_logits if use_prior_logits else posterior_logits         # [B, T - 1, E, K]
+        tf_steps = self.val_teacher_forcing_steps
+        forced = T - 1 if teacher_forcing and tf_steps == -1 else \
+            max(1, min(tf_steps, T - 1)) if teacher_forcing else 1                  # step 0 is always teacher-forced
+        if uniform is None:
+            uniform = torch.rand(T - 1, B, E, K, device=inputs.device)
+        flat = lambda t: t.reshape(forced * B, *t.shape[2:])
+        x_f = flat(inputs[:, :forced].transpose(0, 1))
+        field_f = flat(predicted_field[:, :, :forced].permute(2, 0, 1, 3))
+        edges = gumbel_softmax_hard(flat(logits_all[:, :forced].transpose(0, 1)), flat(uniform[:forced]), self.gumbel_temp)
+        preds, _ = self.decoder(x_f, None, edges, field_f)
+        preds = preds.view(forced, B, N, -1).transpose(0, 1)
+        edges = edges.view(forced, B, E, K)[-1]
+        all_predictions = [preds]
+        predictions = preds[:, -1]
+        for step in range(forced, T - 1):
+            predictions, _, edges = self.single_step_forward(predictions, None, logits_all[:, step].contiguous(), True,
+                                                             field_fn(predictions), uniform=uniform[step])
+            all_predictions.append(predictions.unsqueeze(1))
+        all_predictions = torch.cat(all_predictions, dim=1)
+        target = inputs[:, 1:].to(torch.float32)
+        loss_nll = self.nll(all_predictions, target)
+        prob = torch.softmax(posterior_logits, dim=-1)
+        loss_kl = self.kl_categorical_learned(prob, prior_logits)
+        if self.add_uniform_prior:
+            loss_kl = 0.5 * loss_kl + 0.5 * self.kl_categorical_avg(prob)
+        loss = (loss_nll + self.kl_coef * loss_kl).mean()
+        if return_edges:
+            return loss, loss_nll, loss_kl, edges
+        if return_logits:
+            return loss, loss_nll, loss_kl, posterior_logits, all_predictions
+        return loss, loss_nll, loss_kl
+
+    def _calculate_loss_stepwise(self, inputs, teacher_forcing=True, uniform=None):
+        """The evaluation loss through the per-step loop of _EvalLoss (one decoder call per time step): the cross-check of
+        the batched teacher-forced evaluation above."""
+        with torch.no_grad():
+            return _EvalLoss._calculate_loss_eval(self, inputs, teacher_forcing, False, False, False, uniform)
 
     def save(self, path):
         torch.save(self.state_dict(), path)                       # as the reference's save / load

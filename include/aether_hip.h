@@ -503,6 +503,68 @@ int aether_s2s_rollout(const AetherS2SFieldParams* field, const AetherS2SPriorPa
                        float* edges_out, void* stream);
 
 /*
+ * seq2seq Aether with decoder_type 'ref_mlp': one step of the Markov decoder (MarkovDecoder, nn/seq2seq/aether.py:413-503,
+ * with MLPEdgeFilter of nn/nn/anisotropic_filter.py:43-71) on a flattened batch -- local frames of [inputs | field]
+ * (AugmentedLocalizer, polar), edge MLP relu(lin2(relu(lin1(edge_attr)))) whose output column c Ku + k is channel c of used
+ * type k (Ku = K - skip_first), messages sum_k out[e][c Ku + k] edge_w[e][k0 + k], receiver mean, + res1(rel_feat), output MLP,
+ * rotate back, residual.  There is no hidden state (get_initial_hidden returns None, :456-457).
+ *   params    : the reference module's tensors (nn.Linear layout weight[out][in])
+ *   inputs    : float[n_nodes][2D]   edge_w : float[n_edges][K] (one-hot or soft)   field : float[n_nodes][D]
+ *   send, recv, order, rowptr : as for aether_s2s_decoder_step
+ *   outputs   : float[n_nodes][2D]
+ *   workspace : aether_s2s_markov_decoder_workspace_bytes(D, h, n_nodes, n_edges) bytes
+ * Each type's second layer runs on the edges whose weight for it is not zero; the [n_edges][h Ku] output is never formed.
+ * Dropout is 0 (inference).  Stream-ordered.
+ */
+typedef struct AetherS2SMarkovParams {
+    const float* lin1_w; const float* lin1_b;    /* edge_filter.lin1: [h][2(4D+O)+3D], [h] */
+    const float* lin2_w; const float* lin2_b;    /* edge_filter.lin2: [h Ku][h], [h Ku] (row c Ku + k: channel c of type k) */
+    const float* res1_w; const float* res1_b;    /* res1: [h][7D+O], [h] */
+    const float* out0_w; const float* out0_b; const float* out3_w; const float* out3_b;   /* out_mlp.0 / .3: [h][h], [h] */
+    const float* out6_w; const float* out6_b;    /* out_mlp.6: [2D][h], [2D] */
+} AetherS2SMarkovParams;
+size_t aether_s2s_markov_decoder_workspace_bytes(int num_dims, int hidden, int64_t n_nodes, int64_t n_edges);
+int aether_s2s_markov_decoder_step(const AetherS2SMarkovParams* params, int num_dims, int hidden, int num_edge_types,
+                                   int skip_first, int64_t n_nodes, int64_t n_edges, const float* inputs,
+                                   const float* edge_w, const float* field, const int64_t* send, const int64_t* recv,
+                                   const int64_t* order, const int64_t* rowptr, void* workspace, size_t workspace_bytes,
+                                   float* outputs, void* stream);
+/*
+ * The whole autoregressive step with the Markov decoder, as aether_s2s_plan_* / aether_s2s_step / aether_s2s_rollout for the
+ * recurrent one (aether.py:176-185 with MarkovDecoder.forward :459-503): the same field query -> prior step -> hard Gumbel
+ * sample (one shared implementation), then the Markov decoder on the sample's per-type edge lists -- each edge costs one
+ * h x h product of its own type, scaled by its actual weight ((1 - y) + y) -- and no decoder state.  lin1 and res1 share the
+ * launch of the prior's res1 layer.  The plan holds the prior's prepared weights and the Markov ones (padded lin1 / res1,
+ * lin2's bias per type, fp16 x 2 images of lin2's per-type blocks and of out_mlp's hidden layers).
+ *   workspace : aether_s2s_step_workspace_bytes(D, he, hd, R, prior_hidden, K, n_nodes, n_edges) bytes
+ *   aether_s2s_markov_rollout: burn_in_steps steps on burn_in run the prior only (their predictions are discarded, so the
+ *   decoder is skipped; their uniform rows are consumed all the same), then `steps` autoregressive steps; h, c as for
+ *   aether_s2s_rollout.
+ */
+size_t aether_s2s_markov_plan_bytes(int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
+                                    int prior_hidden, int num_edge_types, int skip_first);
+int aether_s2s_markov_plan_build(const AetherS2SFieldParams* field, const AetherS2SPriorParams* prior,
+                                 const AetherS2SMarkovParams* decoder, int num_dims, int encoder_hidden, int decoder_hidden,
+                                 int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, int skip_first,
+                                 void* plan, size_t plan_bytes, void* stream);
+int aether_s2s_markov_step(const AetherS2SFieldParams* field, const AetherS2SPriorParams* prior,
+                           const AetherS2SMarkovParams* decoder, const void* plan, int num_dims, int encoder_hidden,
+                           int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types,
+                           int skip_first, int polar, int num_vars, float tau, int64_t n_nodes, int64_t n_edges,
+                           const int64_t* send, const int64_t* recv, const int64_t* order, const int64_t* rowptr,
+                           const float* inputs, const float* ext_field, const float* h0, const float* c0,
+                           const float* uniform, void* workspace, size_t workspace_bytes, float* outputs, float* h1,
+                           float* c1, float* edges_out, void* stream);
+int aether_s2s_markov_rollout(const AetherS2SFieldParams* field, const AetherS2SPriorParams* prior,
+                              const AetherS2SMarkovParams* decoder, const void* plan, int num_dims, int encoder_hidden,
+                              int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types,
+                              int skip_first, int polar, int num_vars, float tau, int64_t n_nodes, int64_t n_edges,
+                              const int64_t* send, const int64_t* recv, const int64_t* order, const int64_t* rowptr,
+                              int burn_in_steps, const float* burn_in, int steps, const float* inputs, float* h, float* c,
+                              const float* uniform, void* workspace, size_t workspace_bytes, float* predictions,
+                              float* edges_out, void* stream);
+
+/*
  * seq2seq dynamic-field variant: nn/seq2seq/dynamic_field_aether.py, the model
  * scripts/gravitational_field_3d_aether.sh trains (use_charges is never set by a runner: False).
  *
