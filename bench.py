@@ -2,7 +2,10 @@
 """Benchmark of the Aether state2state hot path on MI355X.
 
 Contract: ``python bench.py --gpus N --steps K --warmup W`` (under torch.distributed.run
-for N > 1, one rank per GPU) prints ONE JSON line on rank 0.
+for N > 1, one rank per GPU) prints ONE JSON line on rank 0.  Such a plain run sets up, warms up,
+times the K steps, writes --dump-outputs and prints the line; everything else the line can carry
+(the repeats of the K steps, the per-kernel pass and roofline, the device rollout, the training
+step, the other configurations, the CPU baseline and its parity checks) runs with ``--full`` only.
 
 * workload  : BASELINE.json configs[1] -- electrostatic 2-D, N=20 fully connected,
               batch=128 graphs per GPU (2,560 nodes, 48,640 edges), synthetic inputs
@@ -12,11 +15,11 @@ for N > 1, one rank per GPU) prints ONE JSON line on rank 0.
               one GNNLayer.message_fn evaluation on one edge; a forward does 4E of them).
 * scaling   : weak -- every rank processes its own 128 graphs; the forward has no exchange
               step, so there is no data-path collective (graphs are independent).
-* roofline  : dominant kernel k_edge_layer (layers 2-4): ALGORITHMIC flops per launch
+* roofline  : (--full) dominant kernel k_edge_layer (layers 2-4): ALGORITHMIC flops per launch
               (reference formulation: E * 2*(192*64 + 64*64) = E * 32,768) / its average launch
               duration, measured with HIP events on the launch stream in a separate
               instrumented pass of the same K steps; peak = 157.3 TFLOP/s dense fp32 MFMA.
-* cpu_baseline : the oracle (oracle/aether_oracle.py, PyTorch CPU restatement pinned to the
+* cpu_baseline : (--full) the oracle (oracle/aether_oracle.py, PyTorch CPU restatement pinned to the
               reference) on the same batch on this host's cores, bounded to ~15 s.
 * outputs   : ``--dump-outputs DIR`` writes what the last timed step returned (``output.npy``: the
               forward's [B*N, D] positions; with --seq2seq the fused step's five tensors) so that two
@@ -463,14 +466,16 @@ def _seq2seq_line(args):
     def step():                                           # the product path of predict_future: one C call (aether_s2s_step)
         return m._fused_step(x, hid, ps, U)
 
-    for _ in range(3):
-        step_modules()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(10):
-        step_modules()
-    torch.cuda.synchronize()
-    modules_ms = (time.perf_counter() - t0) / 10 * 1e3
+    modules_ms = None
+    if args.full:
+        for _ in range(3):
+            step_modules()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(10):
+            step_modules()
+        torch.cuda.synchronize()
+        modules_ms = (time.perf_counter() - t0) / 10 * 1e3
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -485,38 +490,41 @@ def _seq2seq_line(args):
         out, dh, (h1, c1), edges = res
         dumped = _dump_outputs(args.dump_outputs, {"predictions": out, "decoder_hidden": dh, "prior_hidden_h": h1,
                                                    "prior_hidden_c": c1, "edges": edges})
-    # dominant kernel: the anisotropic-filter GEMM of the prior step, timed with events on the launch stream
-    f, _ = m.predict_field(x)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    reps = 10
-    torch.cuda.synchronize()
-    ev[0].record()
-    for _ in range(reps):
-        m.encoder.single_step_forward(x, ps, f)
-    ev[1].record()
-    torch.cuda.synchronize()
-    prior_ms = ev[0].elapsed_time(ev[1]) / reps
-    nrf = 4 * D + D * (D - 1) // 2
-    r_feat = 2 * nrf + 3 * D
-    filt_flop = float(B * E) * r_feat * H * H * 2
+    roof = None
+    if args.full:
+        # dominant kernel: the anisotropic-filter GEMM of the prior step, timed with events on the launch stream
+        f, _ = m.predict_field(x)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        reps = 10
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(reps):
+            m.encoder.single_step_forward(x, ps, f)
+        ev[1].record()
+        torch.cuda.synchronize()
+        prior_ms = ev[0].elapsed_time(ev[1]) / reps
+        nrf = 4 * D + D * (D - 1) // 2
+        r_feat = 2 * nrf + 3 * D
+        filt_flop = float(B * E) * r_feat * H * H * 2
+        roof = {"bound": "mfma", "kernel": "prior step (k_s2s_filter dominates)", "unit": "TFLOP/s",
+                "achieved": filt_flop / (prior_ms * 1e-3) / 1e12, "peak": PEAK_FP32_MFMA_TFLOPS,
+                "frac": filt_flop / (prior_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS,
+                "traffic": _seq2seq_traffic(f"seq2seq-{D}d-N{N}-B{B}-h{H}"),
+                "avg_launch_us": prior_ms * 1e3,
+                "algorithmic_flop_per_launch": filt_flop,
+                "note": "algorithmic = the filter contraction alone (R h^2 MACs per edge); the time is the "
+                        "whole prior step, so the fraction is a lower bound for the filter GEMM.  The GEMM runs as six "
+                        "bf16 MFMA terms on 3-way split operands (fp32-equivalent): a fraction above 1 of the fp32-MFMA "
+                        "peak quoted here is possible; of the bf16 pipe's 2,500 TFLOP/s it is 6 x achieved / 2500"}
     line = {"metric": "seq2seq autoregressive edge-steps/sec (field + prior + sample + decoder step, h=512)",
             "value": B * E / dt, "unit": "edge-steps/s", "n_gpus": 1, "steps": steps, "warmup": args.warmup,
             "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             "config": {"workload": f"seq2seq-{D}d-N{N}-B{B}-h{H}", "num_dims": D, "nodes_per_graph": N,
                        "graphs_per_gpu": B, "edges_per_gpu": B * E, "hidden": H,
                        "launch": "eager, one C call per step (aether_s2s_step: 31 launches on a plan of prepared weights)"},
             "four_entry_points_ms_per_step": modules_ms,
-            "roofline": {"bound": "mfma", "kernel": "prior step (k_s2s_filter dominates)", "unit": "TFLOP/s",
-                         "achieved": filt_flop / (prior_ms * 1e-3) / 1e12, "peak": PEAK_FP32_MFMA_TFLOPS,
-                         "frac": filt_flop / (prior_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS,
-                         "traffic": _seq2seq_traffic(f"seq2seq-{D}d-N{N}-B{B}-h{H}"),
-                         "avg_launch_us": prior_ms * 1e3,
-                         "algorithmic_flop_per_launch": filt_flop,
-                         "note": "algorithmic = the filter contraction alone (R h^2 MACs per edge); the time is the "
-                                 "whole prior step, so the fraction is a lower bound for the filter GEMM.  The GEMM runs as six "
-                                 "bf16 MFMA terms on 3-way split operands (fp32-equivalent): a fraction above 1 of the fp32-MFMA "
-                                 "peak quoted here is possible; of the bf16 pipe's 2,500 TFLOP/s it is 6 x achieved / 2500"},
+            "roofline": roof,
             "cpu_baseline": None}
     if dumped is not None:
         line["dump_outputs"] = dumped
@@ -574,19 +582,23 @@ def main():
                     help="warm-up steps before them (default 20; 3 with --config cfg5shard / cfg5, 5 with --seq2seq)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the repeats of the timed steps, "
+                         "the per-kernel pass and roofline, the rollout, the training step, the other configurations, the "
+                         "CPU baseline with its parity checks (without it those fields of the line are null)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of hipGraph replay")
     ap.add_argument("--prewarm-ms", type=float, default=300.0,
                     help="untimed device warm-up (forward steps) before the W warm-up steps, in milliseconds; 0 = none")
-    ap.add_argument("--no-rollout", action="store_true", help="skip the 20-step device rollout timing")
+    ap.add_argument("--no-rollout", action="store_true", help="with --full: skip the 20-step device rollout timing")
     ap.add_argument("--graph-steps", type=int, default=10,
                     help="consecutive forward steps captured per hipGraph (1: one replay per step)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="testing only: all ranks use cuda:0 (with --backend gloo) to rehearse the N > 1 path on one GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the training-step (fwd+bwd+opt) figure")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity checks")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the training-step (fwd+bwd+opt) figure")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the bounded block of non-headline configurations (cfg3, wide hidden, cfg5 shard, variable-N step)")
+                    help="with --full: skip the bounded block of non-headline configurations (cfg3, wide hidden, cfg5 shard, variable-N step)")
     ap.add_argument("--streamed", action="store_true", help="force the layer-by-layer kernels")
     ap.add_argument("--opt", action="append", default=[], help="name=value passed to aether_set_option")
     ap.add_argument("--dims", type=int, default=WORKLOAD["D"], help="2 (headline) or 3 (cfg3)")
@@ -629,6 +641,8 @@ def main():
     args.warmup = 20 if args.warmup is None else args.warmup
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:                                 # a plain run: the headline figure alone
+        args.no_cpu_baseline = args.no_rollout = args.no_train = args.no_other_configs = True
     if args.seq2seq:
         return _seq2seq_line(args)
 
@@ -654,7 +668,7 @@ def main():
             dist.init_process_group(args.backend, rank=rank, world_size=world)
 
     ranks_seen = None
-    if world > 1:
+    if world > 1 and args.full:
         # which device does every rank sit on?  (uuid / PCI bus id: a SCALE line should show N distinct GPUs.)  Plain
         # tensor all_gather of a fixed-size byte string -- nothing but the collective the backend certainly has.
         pr = torch.cuda.get_device_properties(dev)
@@ -796,7 +810,7 @@ def main():
         # the same K steps a few more times: `value` stays the contract's single timed region, the spread goes next to it
         # (with the driver's --steps 20 that region is ~1 ms; VERDICT r1 asked for a robust companion)
         rep_ms = []
-        if not args.big:
+        if args.full and not args.big:
             for _ in range(5):
                 torch.cuda.synchronize()
                 if world > 1:
@@ -809,7 +823,7 @@ def main():
         # ---- instrumented pass: per-kernel HIP events on the launch stream (eager) --------
         roof = None
         kernels = {}
-        if rank == 0:
+        if rank == 0 and args.full:
             lib = _lib.load()
             nk = lib.aether_profile_kernels()
             lib.aether_profile_enable(1)
@@ -1075,7 +1089,7 @@ def main():
         value = 4.0 * E * args.chunks * world / (dt / args.steps)
         step_flops = (E * FLOP_PER_EDGE_STEP[D] + Nn * FLOP_PER_NODE_STEP[D]) * args.chunks
         other = None
-        if (B, N, D) == (32, 1024, 2):
+        if args.full and (B, N, D) == (32, 1024, 2):
             # HBM and pipe fractions of the OTHER heavy kernels of the config-5 shard, from the committed PMC
             # passes (profiles/traffic.json -> cfg5shard.r03_final) over the launch times measured in THIS run
             try:
@@ -1107,7 +1121,7 @@ def main():
             "metric": ("edge-messages/sec (forward, electrostatic N=20 batch=128 per GPU)" if (B, N, D) == (128, 20, 2)
                        else f"edge-messages/sec (forward, {D}-D N={N} batch={B} per GPU)"),
             "value": value, "unit": "edge-messages/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "pre_warm_ms": args.prewarm_ms, "ms_per_step": ms_step,
+            "warmup": args.warmup, "pre_warm_ms": args.prewarm_ms, "ms_per_step": ms_step, "full": args.full,
             "ms_per_step_repeats": ({"n": len(rep_ms), "median": sorted(rep_ms)[len(rep_ms) // 2], "min": min(rep_ms),
                                      "max": max(rep_ms), "note": "rank 0, the same K steps timed again after the contract's region"}
                                     if rep_ms else None),

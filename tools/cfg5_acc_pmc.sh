@@ -6,7 +6,7 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/cfg5acc$acc
 mkdir -p $out
 export TMPDIR=/tmp
-ARGS="--config cfg5shard --no-cpu-baseline --no-rollout --no-other-configs --no-graph --steps 2 --warmup 1 --opt edge_acc=$acc"
+ARGS="--full --config cfg5shard --no-cpu-baseline --no-rollout --no-other-configs --no-graph --steps 2 --warmup 1 --opt edge_acc=$acc"
 pass() {
     local n=$1; shift; local ctr=$1; shift
     echo "[pmc] $n: $ctr"

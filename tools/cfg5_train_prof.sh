@@ -5,7 +5,7 @@ acc=${1:-2}
 out=$root/gpurun_out/cfg5train_$acc
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- python3 $root/bench.py --config cfg5shard --no-cpu-baseline --no-rollout --no-other-configs --no-graph --steps 3 --warmup 1 --opt edge_acc=$acc > $out/bench.json 2> $out/err.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- python3 $root/bench.py --full --config cfg5shard --no-cpu-baseline --no-rollout --no-other-configs --no-graph --steps 3 --warmup 1 --opt edge_acc=$acc > $out/bench.json 2> $out/err.txt
 for f in $(find $out/trace -name "*kernel_stats.csv"); do cp $f $out/kernel_stats.csv; done
 rm -rf $out/trace
 python3 - <<PY

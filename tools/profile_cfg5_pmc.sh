@@ -7,7 +7,7 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-ARGS="--config cfg5shard --no-cpu-baseline --no-rollout --no-graph --steps 4 --warmup 1"
+ARGS="--full --config cfg5shard --no-cpu-baseline --no-rollout --no-graph --steps 4 --warmup 1"
 pass() {
     local n=$1; shift; local ctr=$1; shift
     echo "[pmc] $n: $ctr"

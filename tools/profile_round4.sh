@@ -18,22 +18,22 @@ pass() {   # name, counters, bench args...
     rm -rf $out/pmc_$n
 }
 cd $root
-if has bench; then echo "[1] default bench"; python3 bench.py > $out/default_bench.json 2> $out/bench.err || exit 1; fi
+if has bench; then echo "[1] default bench"; python3 bench.py --full > $out/default_bench.json 2> $out/bench.err || exit 1; fi
 if has stats; then
     echo "[2] rocprofv3 stats of the default command"
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- python3 $root/bench.py > $out/default_bench_under_rocprof.json 2> $out/trace.err || exit 1
+    rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- python3 $root/bench.py --full > $out/default_bench_under_rocprof.json 2> $out/trace.err || exit 1
     cp $(find $out/trace -name "*kernel_stats.csv" | head -1) $out/default_bench_kernel_stats.csv
     rm -rf $out/trace
     cd $root
 fi
 if has pmc; then
-    FW="--no-cpu-baseline --no-train --no-rollout --no-other-configs --no-graph --steps 100 --warmup 10"
+    FW="--full --no-cpu-baseline --no-train --no-rollout --no-other-configs --no-graph --steps 100 --warmup 10"
     pass fwd_fetch "FETCH_SIZE" $FW
     pass fwd_write "WRITE_SIZE" $FW
     pass fwd_mfma "SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_WAVE_CYCLES" $FW
     pass fwd_wait "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" $FW
-    TR="--no-cpu-baseline --no-rollout --no-other-configs --no-graph --steps 40 --warmup 5"
+    TR="--full --no-cpu-baseline --no-rollout --no-other-configs --no-graph --steps 40 --warmup 5"
     pass train_fetch "FETCH_SIZE" $TR
     pass train_write "WRITE_SIZE" $TR
     pass train_mfma "SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU" $TR
@@ -42,7 +42,7 @@ fi
 if has train; then
     echo "[3] training step kernel stats (eager + graph replays)"
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_t -o t -- python3 $root/bench.py --no-cpu-baseline --no-rollout --no-other-configs --no-graph --steps 40 --warmup 5 > $out/train_eager_bench.json 2> $out/trace_t.err
+    rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_t -o t -- python3 $root/bench.py --full --no-cpu-baseline --no-rollout --no-other-configs --no-graph --steps 40 --warmup 5 > $out/train_eager_bench.json 2> $out/trace_t.err
     cp $(find $out/trace_t -name "*kernel_stats.csv" | head -1) $out/train_step_kernel_stats.csv
     rm -rf $out/trace_t
     cd $root
@@ -60,6 +60,6 @@ if has dyn; then
 fi
 if has cfg5; then
     echo "[6] config-5 shard"
-    python3 bench.py --config cfg5shard > $out/cfg5shard_bench.json 2> $out/cfg5shard_bench.err
+    python3 bench.py --full --config cfg5shard > $out/cfg5shard_bench.json 2> $out/cfg5shard_bench.err
 fi
 echo done
