@@ -221,9 +221,9 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 constexpr int64_t FUSED_TABLE_MAX_EDGES = 4 << 20;
 int g_fused_split = 1;        // aether_set_option("fused_split", 0|1): two workgroups per group when CUs are idle
-int g_fused_pair_stride = 8;  // aether_set_option("fused_pair_stride", 1|8): distance of the two workgroups of a split group
-                              // (8: both on one XCD -- workgroup b runs on XCD b % 8 -- 47.25 -> 46.56 us per launch at cfg2; a
-                              // placement hint only: the hand-off protocol is the cross-XCD one either way)
+constexpr int FUSED_PAIR_STRIDE = 8;   // distance of the two workgroups of a split group (8: both on one XCD -- workgroup b
+                                       // runs on XCD b % 8 -- 47.25 -> 46.56 us per launch at cfg2; a placement hint only:
+                                       // the hand-off protocol is the cross-XCD one either way)
 
 struct GraphLayout {
     size_t perm, send_s, recv_s, rowptr, gsel, wgdesc, tdesc, tsel, tdst, lorder, ledge, nrange, hflags, sperm, srowptr, keys,
@@ -268,20 +268,17 @@ struct GraphLayout {
 };
 
 constexpr int OUTER_MAX_CHUNKS = 256;      // workgroups (= partials) per task
+constexpr int64_t EA8_MAX_WGS = 512;        // kb_edge_acc8 workgroups (= FB_PART-float partials) per layer: two per CU
+constexpr size_t EA8_PARTIAL_PIECES = (EA8_MAX_WGS * FB_PART + OUTER_PART - 1) / OUTER_PART;    // in OUTER_PART pieces: 490
 // Up to this many edges the backward keeps the operands of every layer's weight gradients alive and
 // multiplies all of them in one launch at the end (12 more [E, 64] buffers: 3 KiB per edge).
 int64_t g_outer_defer_max_edges = 1 << 20;      // aether_set_option("outer_defer_max_edges", n)
-int g_edge_acc = 3;                             // aether_set_option("edge_acc", 0..3; 3 = kb_edge_acc8<4 waves>, two workgroups per CU): above that threshold, the edge-level weight
-                                                // gradients are accumulated inside the edge kernel (edge_acc.h)
-int g_outer_tiles_per_wave = 0;                 // aether_set_option("outer_tiles_per_wave", n): 16-row tiles per wave of k_outer (0: by task size)
-int g_linear_small_wgs = 128;                   // aether_set_option("linear_small_wgs", n): below n workgroups, 16 x 32 blocks
+bool g_edge_acc = true;                         // aether_set_option("edge_acc", 0 | non-zero): above that threshold, the edge-level weight
+                                                // gradients are accumulated inside the edge kernel (edge_acc.h: kb_edge_acc8); 0: row tensors + k_outer
+constexpr int LINEAR_SMALL_WGS = 128;           // dense layers of the seq2seq steps: below this many workgroups, 16 x 32 blocks
 int g_linear_kwaves = 4;                        // aether_set_option("linear_kwaves", 1 | 4): waves of a workgroup that split a small layer's k-groups
-int g_filter_wg_target = 768;                   // aether_set_option("filter_wg_target", n): k-splits of the first-version filter kernel (variable-N steps)
 int g_gemm_split = 1;                           // aether_set_option("gemm_split", 0 | 1 | 2 | 3): fp16 x 2 GEMM for the >= 128-workgroup layers of the fused seq2seq step (2 / 3: force a kernel structure)
-int g_dyn_filter_v1 = 0;                        // aether_set_option("dyn_filter_v1", 0 auto | 1 always | 2 never): first-version filter kernel in the variable-N steps
-int g_dyn_filter_v1_edges = 0;                  // auto: below this many edges (measured: no size where the first version wins)
-int g_filter_rsplits = 0;                       // aether_set_option("filter_rsplits", 0 auto | 1 | 3 | 5 | 15): feature split of the 15-feature filter GEMM
-int g_filter_wgs = 256;                         // workgroups of k_s2s_filter_split: one per CU
+constexpr int FILTER_WGS = 256;                 // workgroups of k_s2s_filter_split: one per CU
 int g_filter_splits = 0;                        // aether_set_option("filter_splits", n): k-splits of the filter GEMM, 0 = by balance
 
 
@@ -346,6 +343,9 @@ struct WsLayout {
                 return c < 1 ? (size_t)1 : (c > (size_t)OUTER_MAX_CHUNKS ? (size_t)OUTER_MAX_CHUNKS : c);
             };
             partial_cap = 9 * chunks_of(ee) + 48 * chunks_of(nn);     // 64 x 64 pieces
+            // not deferred: kb_edge_acc8's partials (<= EA8_MAX_WGS of FB_PART floats) use the same buffer; this only adds
+            // to graphs forced out of deferral (beyond the default threshold the tasks above need 2,352 pieces)
+            if (!defer) partial_cap = std::max(partial_cap, EA8_PARTIAL_PIECES);
             partial = take(partial_cap * OUTER_PART);
         }
         // fused backward (fused_bwd.h): one partial per workgroup and layer; a workgroup owns >= 1 node, split
@@ -594,7 +594,7 @@ int run_outer(OuterList& L, float* partial, size_t partial_cap, hipStream_t st, 
         int64_t tiles = (t.rows + 15) / 16;
         // row tiles per wave: 1 for the edge-level products (measured), 4 for node-level ones, whose
         // 35 KB partial per workgroup otherwise outweighs their operands (29 -> 22 us per step at cfg2)
-        const int tpw = g_outer_tiles_per_wave > 0 ? g_outer_tiles_per_wave : (t.rows > 16384 ? 1 : 4);
+        const int tpw = t.rows > 16384 ? 1 : 4;
         int64_t chunks = (tiles + 4 * tpw - 1) / (4 * tpw);
         if (chunks < 1) chunks = 1;
         if (chunks > OUTER_MAX_CHUNKS) chunks = OUTER_MAX_CHUNKS;
@@ -646,9 +646,8 @@ int backward_impl(const AetherParams& P, const AetherParams& Gr, int64_t Nn, int
     const unsigned ngrid = (unsigned)ntile;
     const unsigned egrid = (unsigned)((etile + 3) / 4 < 512 ? (etile + 3) / 4 : 512);    // 2 workgroups per CU
     auto optin = [&](const void* k, size_t lds) -> int { return ensure_dynamic_lds(k, lds); };
-    // edge-level weight gradients inside the edge kernel (edge_acc.h): one 4-wave workgroup per CU, one partial each
-    const unsigned agrid = (unsigned)((etile + 3) / 4 < 256 ? (etile + 3) / 4 : 256);
-    const bool acc_path = g_edge_acc && !W.defer && E > 0 && (size_t)agrid * EA_PART <= W.partial_cap * (size_t)OUTER_PART;
+    // edge-level weight gradients inside the edge kernel (edge_acc.h; WsLayout sizes the partial buffer for it)
+    const bool acc_path = g_edge_acc && !W.defer && E > 0;
     // ---- transposed weight copies (one launch)
     TransposeBatch TB;
     const BwdWT WT = transposed_weights<D>(P, wp(W.wt), TB);     // written by the forward (prepare_weights)
@@ -688,59 +687,28 @@ int backward_impl(const AetherParams& P, const AetherParams& Gr, int64_t Nn, int
         if (E > 0) {
             const size_t lds = (size_t)(4 * H * LDW) * 4;
             ProfScope* pse = new ProfScope(KB_EDGE, st);
-            if (acc_path && g_edge_acc >= 2 && (size_t)512 * FB_PART <= W.partial_cap * (size_t)OUTER_PART) {       // (<= 512 partials)
-                // round 4: two waves per SIMD, transposed products from the forward's images, accumulators partitioned by
-                // output rows (edge_acc.h, kb_edge_acc8): 2 = one workgroup of eight waves per CU, 3 = two of four
-                EdgeAccOut O{};
-                O.w2 = gw2; O.b2 = gb2;
-                int n_parts = 0;
-                auto launch8 = [&](auto nw_tag) -> bool {
-                    constexpr int NW = decltype(nw_tag)::value;
-                    const size_t lds_8 = ea8_lds_bytes(NW);
-                    const int64_t want = (etile + NW - 1) / NW, cap = 256 * (8 / NW);
-                    const unsigned g8 = (unsigned)(want < cap ? want : cap);
-                    n_parts = (int)g8 * (NW / 4);
-                    if (l == 1) {
-                        if (optin(reinterpret_cast<const void*>(kb_edge_acc8<true, NW>), lds_8)) return false;
-                        kb_edge_acc8<true, NW><<<dim3(g8), dim3(64 * NW), lds_8, st>>>(
-                            P.l1_msg_b0, b2, nullptr, nullptr, nullptr, wp(W.feat), send_s, recv_s, rowptr, wp(W.DN), wp(W.DE), 1, bG,
-                            wp(W.DA), partial, wp(W.wimg) + fused_wimg_offset(1, 0), wp(W.wimg) + fused_wimg_offset(1, 1), E, (int)g8);
-                    } else {
-                        if (optin(reinterpret_cast<const void*>(kb_edge_acc8<false, NW>), lds_8)) return false;
-                        kb_edge_acc8<false, NW><<<dim3(g8), dim3(64 * NW), lds_8, st>>>(
-                            nullptr, b2, wp(W.ps[l - 2]), wp(W.pr[l - 2]), wp(W.e[l - 2]), nullptr, send_s, recv_s, rowptr, wp(W.DN),
-                            wp(W.DE), l < 4 ? 1 : 0, bG, nullptr, partial, wp(W.wimg) + fused_wimg_offset(l, 0),
-                            wp(W.wimg) + fused_wimg_offset(l, 1), E, (int)g8);
-                    }
-                    return true;
-                };
-                const bool ok8 = g_edge_acc == 2 ? launch8(std::integral_constant<int, 8>{}) : launch8(std::integral_constant<int, 4>{});
-                if (!ok8) return AETHER_EHIP;
-                if (l == 1) { O.we = Gr.l1_msg_w0; O.ldwe = F1; O.ncols = F1; O.b1 = Gr.l1_msg_b0; O.nb_e = 2; }
-                else { O.we = Gr.ln_msg_w0[l - 2] + 2 * H; O.ldwe = 3 * H; O.ncols = H; O.b1 = nullptr; O.nb_e = 4; }
-                k_edge_acc8_reduce<<<dim3((FB_PART + 63) / 64), dim3(1024), 0, st>>>(partial, n_parts, O);
-            } else if (acc_path) {
-                // large graphs: the two edge-level products of the layer accumulate inside the edge kernel (edge_acc.h)
-                const size_t lds_a = (size_t)(4 * SPLIT_WIMG + 4 * EA_STG) * 4;      // four split images + a staging pair per wave
+            if (acc_path) {
+                // the two edge-level products of the layer accumulate inside the edge kernel (edge_acc.h): two workgroups of
+                // four waves per CU, one partial each
+                const size_t lds_a = ea8_lds_bytes(4);
+                const unsigned agrid = (unsigned)((etile + 3) / 4 < EA8_MAX_WGS ? (etile + 3) / 4 : EA8_MAX_WGS);
                 EdgeAccOut O{};
                 O.w2 = gw2; O.b2 = gb2;
                 if (l == 1) {
-                    if (optin(reinterpret_cast<const void*>(kb_edge_acc<true>), lds_a)) return AETHER_EHIP;
-                    kb_edge_acc<true><<<dim3(agrid), dim3(256), lds_a, st>>>(
-                        P.l1_msg_w0, F1, P.l1_msg_b0, w2, b2, WT.msg_w0t[0], WT.msg_w2t[0], nullptr, nullptr, nullptr,
-                        wp(W.feat), send_s, recv_s, rowptr, wp(W.DN), wp(W.DE), 1, bG, wp(W.DA), partial,
-                        wp(W.wimg) + fused_wimg_offset(1, 0), wp(W.wimg) + fused_wimg_offset(1, 1), E);
+                    if (optin(reinterpret_cast<const void*>(kb_edge_acc8<true, 4>), lds_a)) return AETHER_EHIP;
+                    kb_edge_acc8<true, 4><<<dim3(agrid), dim3(256), lds_a, st>>>(
+                        P.l1_msg_b0, b2, nullptr, nullptr, nullptr, wp(W.feat), send_s, recv_s, rowptr, wp(W.DN), wp(W.DE), 1, bG,
+                        wp(W.DA), partial, wp(W.wimg) + fused_wimg_offset(1, 0), wp(W.wimg) + fused_wimg_offset(1, 1), E, (int)agrid);
                     O.we = Gr.l1_msg_w0; O.ldwe = F1; O.ncols = F1; O.b1 = Gr.l1_msg_b0; O.nb_e = 2;
                 } else {
-                    if (optin(reinterpret_cast<const void*>(kb_edge_acc<false>), lds_a)) return AETHER_EHIP;
-                    kb_edge_acc<false><<<dim3(agrid), dim3(256), lds_a, st>>>(
-                        P.ln_msg_w0[l - 2], 0, nullptr, w2, b2, WT.msg_w0t[l - 1] + 2 * H * H, WT.msg_w2t[l - 1],
-                        wp(W.ps[l - 2]), wp(W.pr[l - 2]), wp(W.e[l - 2]), nullptr, send_s, recv_s, rowptr, wp(W.DN),
+                    if (optin(reinterpret_cast<const void*>(kb_edge_acc8<false, 4>), lds_a)) return AETHER_EHIP;
+                    kb_edge_acc8<false, 4><<<dim3(agrid), dim3(256), lds_a, st>>>(
+                        nullptr, b2, wp(W.ps[l - 2]), wp(W.pr[l - 2]), wp(W.e[l - 2]), nullptr, send_s, recv_s, rowptr, wp(W.DN),
                         wp(W.DE), l < 4 ? 1 : 0, bG, nullptr, partial, wp(W.wimg) + fused_wimg_offset(l, 0),
-                        wp(W.wimg) + fused_wimg_offset(l, 1), E);
+                        wp(W.wimg) + fused_wimg_offset(l, 1), E, (int)agrid);
                     O.we = Gr.ln_msg_w0[l - 2] + 2 * H; O.ldwe = 3 * H; O.ncols = H; O.b1 = nullptr; O.nb_e = 4;
                 }
-                k_edge_acc_reduce<<<dim3(EA_PART / 64), dim3(1024), 0, st>>>(partial, (int)agrid, O);
+                k_edge_acc8_reduce<<<dim3((FB_PART + 63) / 64), dim3(1024), 0, st>>>(partial, (int)agrid, O);
             } else if (l == 1) {
                 if (optin(reinterpret_cast<const void*>(kb_edge<true>), lds)) return AETHER_EHIP;
                 kb_edge<true><<<dim3(egrid), dim3(256), lds, st>>>(
@@ -974,31 +942,17 @@ int aether_set_option(const char* name, int value) {
         g_fused_split = value != 0;
         return AETHER_OK;
     }
-    if (!strcmp(name, "fused_pair_stride")) {     // takes effect at the next aether_graph_build
-        if (value != 1 && value != 8) return fail(AETHER_EINVAL, "set_option: fused_pair_stride is 1 or 8");
-        g_fused_pair_stride = (int)value;
-        return AETHER_OK;
-    }
     if (!strcmp(name, "fused_backward")) {   // 0: layer-by-layer backward kernels even for small-graph groups
         g_fused_backward = value != 0;
         return AETHER_OK;
     }
     if (!strcmp(name, "edge_acc")) {                // changes aether_workspace_bytes(): set before sizing workspaces
-        g_edge_acc = value < 0 ? 0 : (value > 3 ? 3 : value);      // 0: row tensors + k_outer, 1: kb_edge_acc (round 3), 2 / 3: kb_edge_acc8<8 / 4 waves>
+        g_edge_acc = value != 0;                    // 0: row tensors + k_outer, non-zero: kb_edge_acc8<4 waves>
         return AETHER_OK;
     }
     if (!strcmp(name, "outer_defer_max_edges")) {   // changes aether_workspace_bytes(): set before sizing workspaces
         if (value < 0) return fail(AETHER_EINVAL, "set_option: outer_defer_max_edges must be >= 0");
         g_outer_defer_max_edges = value;
-        return AETHER_OK;
-    }
-    if (!strcmp(name, "outer_tiles_per_wave")) {
-        if (value < 0 || value > 64) return fail(AETHER_EINVAL, "set_option: outer_tiles_per_wave must be 0..64");
-        g_outer_tiles_per_wave = value;
-        return AETHER_OK;
-    }
-    if (!strcmp(name, "linear_small_wgs")) {
-        g_linear_small_wgs = value;
         return AETHER_OK;
     }
     if (!strcmp(name, "linear_kwaves")) {
@@ -1011,31 +965,10 @@ int aether_set_option(const char* name, int value) {
         g_gemm_split = value;
         return AETHER_OK;
     }
-    if (!strcmp(name, "dyn_filter_v1")) {
-        if (value < 0 || value > 2) return fail(AETHER_EINVAL, "set_option: dyn_filter_v1 must be 0, 1 or 2");
-        g_dyn_filter_v1 = value;
-        return AETHER_OK;
-    }
-    if (!strcmp(name, "dyn_filter_v1_edges")) { g_dyn_filter_v1_edges = value; return AETHER_OK; }
-    if (!strcmp(name, "filter_rsplits")) {
-        if (value != 0 && 15 % value != 0) return fail(AETHER_EINVAL, "set_option: filter_rsplits is 0 (auto), 1, 3, 5 or 15");
-        g_filter_rsplits = value;
-        return AETHER_OK;
-    }
-    if (!strcmp(name, "filter_wgs")) {
-        if (value < 8 || value % 8 != 0) return fail(AETHER_EINVAL, "set_option: filter_wgs must be a multiple of 8");
-        g_filter_wgs = value;
-        return AETHER_OK;
-    }
     if (!strcmp(name, "filter_splits")) {           // changes the seq2seq / variable-N prior workspace sizes
         if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
             return fail(AETHER_EINVAL, "set_option: filter_splits must be 0 (automatic), 1, 2, 4 or 8");
         g_filter_splits = value;
-        return AETHER_OK;
-    }
-    if (!strcmp(name, "filter_wg_target")) {        // changes the seq2seq / variable-N prior and decoder workspace sizes
-        if (value < 1) return fail(AETHER_EINVAL, "set_option: filter_wg_target must be >= 1");
-        g_filter_wg_target = value;
         return AETHER_OK;
     }
     return fail(AETHER_EINVAL, "set_option: unknown option");
@@ -1203,9 +1136,9 @@ int aether_graph_build(const int64_t* send, const int64_t* recv, int64_t n_edges
                 return nm;
             };
             // Workgroups are dispatched round-robin over the 8 XCDs (workgroup b runs on XCD b % 8: tools/micro/xcc_map.hip).
-            // With option "fused_pair_stride" = 8 the two halves of a group sit 8 apart (blocks of 16: the eight first
-            // halves, then the eight second halves), i.e. on the SAME XCD and behind the same L2; 1 = adjacent (different XCDs).
-            const int pstride = split ? g_fused_pair_stride : 1;
+            // The two halves of a group sit FUSED_PAIR_STRIDE = 8 apart (blocks of 16: the eight first halves, then the eight
+            // second halves), i.e. on the SAME XCD and behind the same L2.
+            const int pstride = split ? FUSED_PAIR_STRIDE : 1;
             for (int k0 = 0; k0 < n_grp; k0 += pstride) {
                 const int kn = std::min(pstride, n_grp - k0);
                 if (!split) { add_wg(grp[k0], grp[k0 + 1], grp[k0], grp[k0 + 1], -1); continue; }

@@ -6,24 +6,8 @@ namespace {
 // The variable-N models' anisotropic filter (aether_dynamicvars.py: 15 edge features, ReLU hyper-network): the split-fp16
 // filter GEMM of s2s_filter.h.  image: prepared (aether_s2s_filter_prepare) or NULL -> built into fimg for this call.
 int dyn_filter(const float* w0, const float* b0, const float* w2, const float* b2, const void* image, const float* ea15,
-               const float* epos, char* bimg_buf, char* fimg_buf, float* fpart, int splits, float* out, int h, int64_t E,
-               hipStream_t st) {
+               const float* epos, char* bimg_buf, char* fimg_buf, float* fpart, float* out, int h, int64_t E, hipStream_t st) {
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-    if (g_dyn_filter_v1 == 1 || (g_dyn_filter_v1 == 0 && E < g_dyn_filter_v1_edges)) {
-        // few edges: the first-version kernel (fp32 MFMA, operand formed on the fly) has the finer work split
-        float* hw = reinterpret_cast<float*>(bimg_buf);                      // E x h floats fit the image's 1.5 E h
-        k_s2s_pos_hidden<<<blocks(E * h), dim3(256), 0, st>>>(w0, b0, epos, 3, hw, h, E, 1);
-        constexpr int NB = 4;
-        const int s1 = S2SPriorLayout::filter_splits_v1(h, E);          // the layout holds max(v1, v2) planes
-        const dim3 grid((unsigned)((E + 32 * NB - 1) / (32 * NB)), (unsigned)(h / 128), (unsigned)s1);
-        if (s1 > 1) {
-            k_s2s_filter<15, NB, true><<<grid, dim3(256), 0, st>>>(w2, b2, ea15, hw, fpart, h, E);
-            k_s2s_sum_planes<<<blocks(E * h / 4), dim3(256), 0, st>>>(fpart, s1, E * (int64_t)h, out);
-        } else {
-            k_s2s_filter<15, NB, false><<<grid, dim3(256), 0, st>>>(w2, b2, ea15, hw, out, h, E);
-        }
-        return AETHER_OK;
-    }
     const f16x8* img = reinterpret_cast<const f16x8*>(image);
     if (!img) {
         f16x8* mine = reinterpret_cast<f16x8*>(fimg_buf);
@@ -32,10 +16,10 @@ int dyn_filter(const float* w0, const float* b0, const float* w2, const float* b
     }
     f16x8* bimg = reinterpret_cast<f16x8*>(bimg_buf);
     k_s2s_filter_bimg<3><<<filter_bimg_grid(E), dim3(256), 0, st>>>(epos, w0, b0, 1, h, E, bimg);
-    splits = S2SPriorLayout::filter_splits(h, E);
+    const int splits = S2SPriorLayout::filter_splits(h, E);
     const int rs = S2SPriorLayout::filter_rsplits15(h, E), planes = splits * rs;
     const int64_t units = ((E + 255) / 256) * (h / 64) * planes;
-    const dim3 grid((unsigned)(units < g_filter_wgs ? units : g_filter_wgs));
+    const dim3 grid((unsigned)(units < FILTER_WGS ? units : FILTER_WGS));
     float* dst = planes > 1 ? fpart : out;
     const size_t lds = filt_lds_bytes(15);
     if (ensure_dynamic_lds(reinterpret_cast<const void*>(k_s2s_filter_split<15>), lds)) return AETHER_EHIP;
@@ -60,8 +44,7 @@ struct DynDecLayout {
         ext = take(nn * 6); rel = take(nn * 15); Rinv = take(nn * 4);
         ea = take(ee * 24); ea15 = take(ee * 15); epos = take(ee * 3); bimg = take((ee + 15) / 16 * 16 * hh_ * 3 / 2);
         fimg = take((size_t)15 * hh_ * hh_ * 3 / 2); fout = take(ee * hh_);
-        splits = std::max(S2SPriorLayout::filter_splits(h, E) * S2SPriorLayout::filter_rsplits15(h, E),
-                          S2SPriorLayout::filter_splits_v1(h, E));
+        splits = S2SPriorLayout::filter_splits(h, E) * S2SPriorLayout::filter_rsplits15(h, E);     // planes of the filter GEMM
         fpart = take(splits > 1 ? ee * hh_ * splits : 0);
         ewn = take(ee * 4);
         rp = take(nn * hh_); ip = take(nn * hh_); np_ = take(nn * hh_); hh = take(nn * hh_);
@@ -69,9 +52,8 @@ struct DynDecLayout {
         for (auto& v : list) v = take(ee * 2);
         counts = take(64);
         // all edge types' filters in one launch (k_s2s_filter_split_types): a B-operand image and the planes per type
-        const int s2 = S2SPriorLayout::filter_splits(h, E) * S2SPriorLayout::filter_rsplits15(h, E);
         for (auto& v : bimg_t) v = take((ee + 15) / 16 * 16 * hh_ * 3 / 2);
-        for (auto& v : fpart_t) v = take(ee * hh_ * (size_t)(s2 > 1 ? s2 : 1));
+        for (auto& v : fpart_t) v = take(ee * hh_ * (size_t)(splits > 1 ? splits : 1));
         total = off;
     }
 };
@@ -178,7 +160,7 @@ static int dyn_decoder_impl(const AetherDynDecoderParams* p, int hidden, int num
         k_s2s_aug_edges<2><<<blocks(E), dim3(256), 0, st>>>(edge_state ? edge_state : n_ext, send, recv, n_rel, polar,
                                                            wp(L.ea15), wp(L.epos), E, state_send, state_recv, 15);
         // ---- messages from the present state: one anisotropic filter per edge type, ReLU (:827-835)
-        bool all_types_at_once = !(g_dyn_filter_v1 == 1 || (g_dyn_filter_v1 == 0 && E < g_dyn_filter_v1_edges));
+        bool all_types_at_once = true;
         for (int k = k0; k < K; ++k) all_types_at_once = all_types_at_once && p->filt_image[k] != nullptr;
         if (all_types_at_once) {
             // three launches for all edge types (was four per type): B-operand images, the filter GEMMs, and the
@@ -195,7 +177,7 @@ static int dyn_decoder_impl(const AetherDynDecoderParams* p, int hidden, int num
             k_s2s_filter_bimg_types<3><<<filter_bimg_grid(E, nT), dim3(256), 0, st>>>(
                 wp(L.epos), T, 1, h, E);
             const int64_t units = ((E + 255) / 256) * (h / 64) * splits * rs;
-            const dim3 grid((unsigned)(units < g_filter_wgs ? units : g_filter_wgs), (unsigned)nT);
+            const dim3 grid((unsigned)(units < FILTER_WGS ? units : FILTER_WGS), (unsigned)nT);
             const size_t lds = filt_lds_bytes(15);
             if (ensure_dynamic_lds(reinterpret_cast<const void*>(k_s2s_filter_split_types<15>), lds)) return AETHER_EHIP;
             // All types' filter GEMMs as ONE launch.  Round 3 launched them per type: with this kernel as a graph node, replays
@@ -209,7 +191,7 @@ static int dyn_decoder_impl(const AetherDynDecoderParams* p, int hidden, int num
         } else {
             for (int k = k0; k < K; ++k) {
                 if (int rc = dyn_filter(p->filt_w0[k], p->filt_b0[k], p->filt_w2[k], p->filt_b2[k], p->filt_image[k], wp(L.ea15),
-                                        wp(L.epos), ws + L.bimg, ws + L.fimg, wp(L.fpart), L.splits, wp(L.fout), h, E, st)) return rc;
+                                        wp(L.epos), ws + L.bimg, ws + L.fimg, wp(L.fpart), wp(L.fout), h, E, st)) return rc;
                 k_s2s_relu_scale_acc<<<blocks(E * (h / 4)), dim3(256), 0, st>>>(wp(L.fout), edge_w + k, K, wp(L.M2), h, E);
             }
         }
@@ -262,8 +244,7 @@ struct DynPriorLayout {
         ext = take(nn * 6); rel = take(nn * 15); Rinv = take(nn * 4);
         ea = take(ee * 24); ea15 = take(ee * 15); epos = take(ee * 3); bimg = take((ee + 15) / 16 * 16 * hh * 3 / 2);
         fimg = take((size_t)15 * hh * hh * 3 / 2); eaf = take(ee * hh);
-        splits = std::max(S2SPriorLayout::filter_splits(h, E) * S2SPriorLayout::filter_rsplits15(h, E),
-                          S2SPriorLayout::filter_splits_v1(h, E));
+        splits = S2SPriorLayout::filter_splits(h, E) * S2SPriorLayout::filter_rsplits15(h, E);     // planes of the filter GEMM
         fpart = take(splits > 1 ? ee * hh * splits : 0);
         X0 = take(nn * hh); X1 = take(nn * hh); X3 = take(nn * hh); Ps = take(nn * hh); Pr = take(nn * hh);
         T1 = take(ee * hh); X4 = take(ee * hh); G = take(ee * 4 * (size_t)R);
@@ -307,7 +288,7 @@ int aether_dyn_prior_step(const AetherDynPriorParams* p, int hidden, int rnn_hid
     k_s2s_aug_edges<2><<<blocks(E), dim3(256), 0, st>>>(wp(L.ext), send, recv, wp(L.rel), polar, wp(L.ea15), wp(L.epos), E, nullptr,
                                                        nullptr, 15);
     if (int rc = dyn_filter(p->filt_w0, p->filt_b0, p->filt_w2, p->filt_b2, p->filt_image, wp(L.ea15), wp(L.epos), ws + L.bimg,
-                            ws + L.fimg, wp(L.fpart), L.splits, wp(L.eaf), h, E, st)) return rc;
+                            ws + L.fimg, wp(L.fpart), wp(L.eaf), h, E, st)) return rc;
     // ---- x = sum over in-edges + mlp1(canonical state) (:541-542); RefNRIMLP (eval): Linear-ELU-Linear-ELU-BatchNorm
     float* bns[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
     const float* bnp[3][4] = {{p->mlp1_bn_w, p->mlp1_bn_b, p->mlp1_bn_mean, p->mlp1_bn_var},

@@ -102,7 +102,7 @@ bool s2s_jobs_take_split(const S2SJobs& T) {
         if (T.j[t].N * T.j[t].M > T.j[best].N * T.j[best].M) best = t;
     int64_t tiles_big = 0;
     for (int t = 0; t < T.n; ++t) tiles_big += ((T.j[t].N + 63) / 64) * ((T.j[t].M + 127) / 128);
-    if (!(T.j[best].M >= 128 && tiles_big >= g_linear_small_wgs)) return false;
+    if (!(T.j[best].M >= 128 && tiles_big >= LINEAR_SMALL_WGS)) return false;
     for (int t = 0; t < T.n; ++t) {
         const S2SJob& J = T.j[t];
         if (!(J.Wimg != nullptr && J.M % 128 == 0 && J.K % 32 == 0 && (J.W2 == nullptr || (J.W2img != nullptr && J.K2 % 32 == 0)) &&
@@ -124,7 +124,7 @@ int s2s_launch_jobs(S2SJobs& T, hipStream_t st) {
             tiles_big += ((T.j[t].N + 63) / 64) * ((T.j[t].M + 127) / 128);
             tiles_small += ((T.j[t].N + 63) / 64) * ((T.j[t].M + 31) / 32);
         }
-        big = B.M >= 128 && tiles_big >= g_linear_small_wgs;
+        big = B.M >= 128 && tiles_big >= LINEAR_SMALL_WGS;
         wide = big && B.N >= 16384;
         ksplit = !big && g_linear_kwaves == 4 && B.K >= 128 && tiles_small < 1024;
     }
@@ -276,7 +276,7 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
         if (D == 2) k_s2s_filter_bimg<3><<<filter_bimg_grid(E), dim3(256), 0, st>>>(wp(L.epos), p->filt_w0, p->filt_b0, 0, he, E, bimg);
         else k_s2s_filter_bimg<6><<<filter_bimg_grid(E), dim3(256), 0, st>>>(wp(L.epos), p->filt_w0, p->filt_b0, 0, he, E, bimg);
         const int64_t units = ((E + 255) / 256) * (he / 64) * L.splits;
-        const dim3 grid((unsigned)(units < g_filter_wgs ? units : g_filter_wgs));
+        const dim3 grid((unsigned)(units < FILTER_WGS ? units : FILTER_WGS));
         float* dst = L.splits > 1 ? wp(L.fpart) : wp(L.eaf);
 #define FILT_LAUNCH(RR)                                                                                                  \
     do {                                                                                                                 \

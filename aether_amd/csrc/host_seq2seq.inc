@@ -72,7 +72,7 @@ int s2s_linear(int act, const float* W, int ldw, const float* b, const float* X,
     // A wave's k-step costs (MT x NT) MFMAs x 32 cycles whatever the problem size: with few rows (the reference's
     // 5-object graphs: 640 nodes, 2,560 edges) 64 x 32 blocks per wave leave most SIMDs idle and every GEMM takes the
     // 32 k-steps x 0.43 us of one wave; 16 x 32 blocks give four times the waves.
-    const bool big = M >= 128 && ((N + 63) / 64) * ((M + 127) / 128) >= g_linear_small_wgs;
+    const bool big = M >= 128 && ((N + 63) / 64) * ((M + 127) / 128) >= LINEAR_SMALL_WGS;
     const bool wide = big && N >= 16384;             // 64 points per wave once there are enough workgroups
     const int nt = wide ? 4 : 2;
     // ... and when even those are few (a node-level layer of 640 rows), the waves of a workgroup split the k-groups
@@ -216,14 +216,6 @@ struct S2SPriorLayout {
     // k-splits of the filter GEMM (k_s2s_filter_split: persistent workgroups, 32 per XCD, an XCD walks (c block, split) pairs
     // xcd, xcd + 8, .. with one 256-edge tile per workgroup): the split count that minimises rounds x k range per unit on the
     // busiest XCD; ties go to fewer planes
-    // k-splits of the first-version filter kernel (k_s2s_filter, still used by the variable-N steps): with few edges its
-    // (E / 128) x (h / 128) workgroups do not fill 256 CUs
-    static int filter_splits_v1(int h, int64_t E) {
-        const int64_t base = ((E + 127) / 128) * (h / 128);
-        int s = 1;
-        while (s < 16 && base * s < g_filter_wg_target && (h / 16) % (2 * s) == 0) s *= 2;
-        return s;
-    }
     static int filter_splits(int h, int64_t E) {
         if (g_filter_splits > 0 && (h / 64) % g_filter_splits == 0) return g_filter_splits;
         const int64_t eb = (E + 255) / 256;
@@ -239,7 +231,6 @@ struct S2SPriorLayout {
     // Few edges (variable-N steps, 15 features): the features are divided over rs units as well (s2s_filter.h) until the
     // launch has ~a third of the CUs' worth of workgroups per filter; rs divides 15.
     static int filter_rsplits15(int h, int64_t E) {
-        if (g_filter_rsplits >= 1 && 15 % g_filter_rsplits == 0) return g_filter_rsplits;
         const int64_t units = ((E + 255) / 256) * (h / 64) * filter_splits(h, E);
         int rs = 1;
         for (int cand : {3, 5})
@@ -314,7 +305,7 @@ int s2s_prior_features(const AetherS2SPriorParams* p, int D, int h, int polar, i
         if (D == 2) k_s2s_filter_bimg<3><<<filter_bimg_grid(E), dim3(256), 0, st>>>(wp(L.epos), p->filt_w0, p->filt_b0, 0, h, E, bimg);
         else k_s2s_filter_bimg<6><<<filter_bimg_grid(E), dim3(256), 0, st>>>(wp(L.epos), p->filt_w0, p->filt_b0, 0, h, E, bimg);
         const int64_t units = ((E + 255) / 256) * (h / 64) * L.splits;
-        const dim3 grid((unsigned)(units < g_filter_wgs ? units : g_filter_wgs));
+        const dim3 grid((unsigned)(units < FILTER_WGS ? units : FILTER_WGS));
         float* dst = L.splits > 1 ? wp(L.fpart) : wp(L.eaf);
 #define FILT_LAUNCH(RR)                                                                                                  \
     do {                                                                                                                 \

@@ -13,7 +13,7 @@
 // within 2^-18 of its row's / tensor's maximum are normal fp16 numbers; the product of the inverse scales multiplies the
 // edge feature ea[e][r] before it weights Z_r (four multiplies per step).  Smaller values lose relative, not absolute,
 // precision (fp16 subnormals: 2^-24 of the scaled maximum).
-// The first version (seq2seq.h, k_s2s_filter) formed x[(r, k)] = ea[e][r] * hw[e][k] on the fly for the fp32 MFMA.
+// (The first version, removed since, formed x[(r, k)] = ea[e][r] * hw[e][k] on the fly for the fp32 MFMA.)
 //
 // Workgroup = 8 waves = 2 (c halves) x 4 (edge quarters) on a 64 (c) x 256 (edges) output tile, two waves per SIMD.  The
 // k range of a unit is walked in slabs of 64; a wave owns 32 c x 64 edges and holds the B fragments of its edges for BOTH

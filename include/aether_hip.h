@@ -900,21 +900,21 @@ int aether_adamw_step(const AetherAdamWTensor* tensors, int n_tensors, float* st
                       double beta1, double beta2, double eps, double weight_decay, double grad_scale, void* stream);
 
 /*
- * Tuning knobs (process-wide; not thread-safe): "fused_split" 0|1 (two workgroups per group when
- * there are fewer groups than half the CUs; read by aether_graph_build), "fused_pair_stride" 1|8 (index distance of the
- * two workgroups of a split group: 8, the default, puts both on one XCD; read by aether_graph_build),
- * "outer_defer_max_edges" n (aether_backward keeps every layer's weight-gradient operands and
- * multiplies them in one launch when n_edges <= n, default 2^20; changes aether_workspace_bytes),
- * "filter_wg_target" n (the anisotropic-filter GEMM of the seq2seq / variable-N steps splits its k-groups, up to
- * 16 ways, until it launches at least n workgroups; default 768, measured best at 2,560 edges; changes the prior /
- * decoder workspace sizes), "linear_small_wgs" n (dense layers of the seq2seq / variable-N steps whose 64 x 32-per-wave
- * tiling would launch fewer than n workgroups use 16 x 32 blocks per wave instead: four times the waves for the
- * 5-object graphs; default 128), "linear_kwaves" 1|4 (when even those blocks are few, the four waves of a workgroup
- * share one block and split its k-groups, partial sums added in wave order; default 4, 1 turns it off),
+ * Tuning knobs (process-wide; not thread-safe); any other name returns AETHER_EINVAL:
+ * "fused_split" 0|1 (two workgroups per group when there are fewer groups than half the CUs; default 1; read by
+ * aether_graph_build), "fused_backward" 0|1 (one-launch backward for small-graph groups; default 1, 0 sends them through
+ * the layer-by-layer kernels), "outer_defer_max_edges" n (aether_backward keeps every layer's weight-gradient operands
+ * and multiplies them in one launch when n_edges <= n, default 2^20; changes aether_workspace_bytes), "edge_acc"
+ * 0|non-zero (above outer_defer_max_edges, non-zero -- the default -- accumulates each layer's edge-level weight gradients
+ * inside the edge kernel, 0 writes the rows and multiplies them afterwards; changes aether_workspace_bytes),
+ * "linear_kwaves" 1|4 (dense layers of the seq2seq / variable-N steps with few 16 x 32 blocks: the four waves of a
+ * workgroup share one block and split its k-groups, partial sums added in wave order; default 4, 1 turns it off),
  * "gemm_split" 0|1|2|3 (dense layers of the fused seq2seq step from 128 workgroups on: 1, the default, multiplies
  * fp16 x 2 pieces on the 16-bit matrix pipe and picks the kernel structure per launch -- both operands through an
  * LDS-DMA ring up to 256 workgroups, X rows in registers above; 2 / 3 force the second / the first structure for
- * every launch; 0 sends these layers through the fp32-MFMA job kernel).
+ * every launch; 0 sends these layers through the fp32-MFMA job kernel), "filter_splits" 0|1|2|4|8 (k-splits of the
+ * anisotropic-filter GEMM of the seq2seq / variable-N prior steps; default 0, chosen by balance; changes the prior /
+ * decoder workspace sizes).
  */
 int aether_set_option(const char* name, int value);
 

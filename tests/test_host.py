@@ -132,6 +132,20 @@ def test_library_exports_every_declared_symbol():
     assert lib.aether_workspace_bytes(10, 10, 4, 0) == 0
 
 
+def test_set_option_knows_exactly_the_documented_options():
+    """Host-only: every option include/aether_hip.h documents accepts its default value; the names of the removed
+    superseded kernel paths and tuning knobs are unknown (AETHER_EINVAL = -1)."""
+    lib = _lib.load()
+    kept = {"fused_split": 1, "fused_backward": 1, "edge_acc": 3, "outer_defer_max_edges": 1 << 20,
+            "linear_kwaves": 4, "gemm_split": 1, "filter_splits": 0}
+    for name, default in kept.items():
+        assert lib.aether_set_option(name.encode(), default) == 0, name
+    removed = {"fused_pair_stride": 8, "outer_tiles_per_wave": 0, "filter_wgs": 256, "filter_rsplits": 0,
+               "linear_small_wgs": 128, "dyn_filter_v1": 0, "dyn_filter_v1_edges": 0, "filter_wg_target": 768}
+    for name, old_default in removed.items():
+        assert lib.aether_set_option(name.encode(), old_default) == -1, name
+
+
 def test_params_struct_layout_matches_header():
     hdr = open(os.path.join(REPO, "include", "aether_hip.h")).read()
     body = hdr[hdr.index("typedef struct AetherParams"):hdr.index("} AetherParams;")]

@@ -1,6 +1,6 @@
 #!/bin/bash
-# PMC passes of the config-5 shard's training step for one edge_acc option: where kb_edge_acc / kb_edge_acc8 spend their cycles.
-# usage: tools/cfg5_acc_pmc.sh <edge_acc option> -> gpurun_out/cfg5acc<opt>/pmc_*.txt
+# PMC passes of the config-5 shard's training step for one edge_acc option: where kb_edge_acc8 (non-zero) or kb_edge + k_outer
+# (0) spend their cycles.   usage: tools/cfg5_acc_pmc.sh <edge_acc option 0|3> -> pmc_*.txt in the cfg5acc<opt> output directory
 acc=${1:-3}
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/cfg5acc$acc

@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes of the config-5 shard (forward + training step) with the library as committed: HBM bytes and issue / wait
-# counters of k_edge_layer, k_edge_layer1, kb_edge_acc.  Each counter set in its own run, --kernel-trace only.
+# counters of k_edge_layer, k_edge_layer1, kb_edge_acc8.  Each counter set in its own run, --kernel-trace only.
 # usage: tools/profile_cfg5_pmc.sh <tag>  -> gpurun_out/<tag>/pmc_*.txt
 tag=$1
 root=${GRAFT_REPO_ROOT:-$(pwd)}
