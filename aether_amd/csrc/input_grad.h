@@ -41,14 +41,19 @@ __device__ __forceinline__ void edge_local_grad(const float* __restrict__ da, co
         }
     }
     if constexpr (D == 3) {   // polar angle acos(clamp(r_z / (|r| + eps), -1, 1))
+        // At r = 0 (coincident particles) c = 0 and the slope in r_z stays 1 / eps; only the d|r| part vanishes (torch's
+        // norm subgradient at 0).  At c = +-1 exactly (an exactly z-aligned r with |r| + eps rounding to |r|) the
+        // reference's slope is not finite; that point keeps zero here.
         const float rho = sqrtf(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
         const float c = r[2] / (rho + EPS_F);
-        if (rho > 0.f && c > -1.0f && c < 1.0f) {
+        if (c > -1.0f && c < 1.0f) {
             const float dc = -da[C_B + 1] / sqrtf(1.0f - c * c);
             dr[2] += dc / (rho + EPS_F);
-            const float k = -dc * r[2] / ((rho + EPS_F) * (rho + EPS_F) * rho);
+            if (rho > 0.f) {
+                const float k = -dc * r[2] / ((rho + EPS_F) * (rho + EPS_F) * rho);
 #pragma unroll
-            for (int a = 0; a < D; ++a) dr[a] += k * r[a];
+                for (int a = 0; a < D; ++a) dr[a] += k * r[a];
+            }
         }
     }
     float d2 = 0.f;
@@ -90,6 +95,7 @@ __device__ __forceinline__ void euler_grad(const float* __restrict__ da, const f
     }
     if constexpr (D == 3) {
         const float s2 = 1.0f - M[2][0] * M[2][0];
+        // an exact gimbal (|M20| = 1): asin' is infinite in the reference, zero here
         if (s2 > 0.f) dM[2][0] += -da[D + 1] * ipi / sqrtf(s2);
         const float den = M[2][1] * M[2][1] + M[2][2] * M[2][2];
         if (den > 0.f) {
@@ -135,6 +141,10 @@ kb_inputs(AetherParams P, const float* __restrict__ x, const float* __restrict__
 #pragma unroll
         for (int b = 0; b < D; ++b) rel[b] = nj[NI::P + b] - ni[NI::P + b];
         edge_local_grad<D>(da, rel, ni + NI::R, dr, drel);
+        if (send_s[k] == nc) {      // self loop: rel = p_i - p_i, its two ends cancel exactly (not through +-1/eps sums)
+#pragma unroll
+            for (int b = 0; b < D; ++b) drel[b] = 0.f;
+        }
         float dM[D][D];
         euler_grad<D>(da, ni + NI::R, nj + NI::R, dM);
 #pragma unroll
@@ -160,6 +170,10 @@ kb_inputs(AetherParams P, const float* __restrict__ x, const float* __restrict__
 #pragma unroll
         for (int b = 0; b < D; ++b) rel[b] = ni[NI::P + b] - nr[NI::P + b];
         edge_local_grad<D>(da, rel, nr + NI::R, dr, drel);
+        if (recv_s[k] == nc) {      // self loop (above)
+#pragma unroll
+            for (int b = 0; b < D; ++b) drel[b] = 0.f;
+        }
         float dM[D][D];
         euler_grad<D>(da, nr + NI::R, ni + NI::R, dM);
 #pragma unroll
@@ -232,11 +246,15 @@ kb_inputs(AetherParams P, const float* __restrict__ x, const float* __restrict__
             const float v2 = ni[NI::V + 2];
             const float rho = sqrtf(den + v2 * v2);
             const float cz = v2 / (rho + EPS_F);
-            if (rho > 0.f && cz > -1.0f && cz < 1.0f) {
+            // as in edge_local_grad: at v = 0 the slope in v_z is 1 / eps, only the d|v| part is guarded; cz = +-1
+            // exactly (|v| >= 2 along z) keeps zero where the reference's slope is not finite
+            if (cz > -1.0f && cz < 1.0f) {
                 const float dcz = -dph / sqrtf(1.0f - cz * cz);
                 gv[2] += dcz / (rho + EPS_F);
-                const float k = -dcz * v2 / ((rho + EPS_F) * (rho + EPS_F) * rho);
-                gv[0] += k * v0; gv[1] += k * v1; gv[2] += k * v2;
+                if (rho > 0.f) {
+                    const float k = -dcz * v2 / ((rho + EPS_F) * (rho + EPS_F) * rho);
+                    gv[0] += k * v0; gv[1] += k * v1; gv[2] += k * v2;
+                }
             }
         }
         if (den > 0.f) {

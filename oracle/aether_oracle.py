@@ -169,10 +169,13 @@ def out_mlp(sd, x, dropout_masks=None):
 
 
 # --------------------------------------------------------------------- whole
-def aether_forward(sd, x, vel, edges, edge_attr_orig, charges, return_all=False, field=None, dropout_masks=None):
+def aether_forward(sd, x, vel, edges, edge_attr_orig, charges, return_all=False, field=None, dropout_masks=None,
+                   edge_shift=None):
     """aether.py:169-186.  ``sd`` maps reference state_dict keys to tensors.  ``field``: a precomputed
     per-node field replaces the built-in field net (the dynamic-field variant, dynamic_field_aether.py:84-97,
-    is this function with ``dynamic_field`` below)."""
+    is this function with ``dynamic_field`` below).  ``edge_shift``: a constant [E, 7D + D(D-1)/2] added to the
+    local-frame edge features -- whole periods on the branch-cut columns (``cut_margin``), so that the evaluation
+    follows the side of a cut another implementation took; None (the default) is the reference's own map."""
     D = x.shape[-1]
     send, recv = edges
     inputs = torch.cat([x, vel], dim=-1)
@@ -182,6 +185,8 @@ def aether_forward(sd, x, vel, edges, edge_attr_orig, charges, return_all=False,
     rel_feat, R = canonical_nodes(ext, D)
     ea = edge_features(ext, send, recv, D)
     ea_local = torch.cat([ea, rel_feat[recv]], -1)                  # aether.py:99
+    if edge_shift is not None:
+        ea_local = ea_local + edge_shift.to(ea_local.dtype)
     ea_full = torch.cat([ea_local, edge_attr_orig], -1)             # aether.py:177
     res = {"field": field, "rel_feat": rel_feat, "R": R, "edge_attr_local": ea_local}
     h, e = rel_feat, ea_full
@@ -229,10 +234,12 @@ def dynamic_field(sd, x, vel, charges, num_nodes):
     return lin("wrapper.linear_3", y)
 
 
-def dynamic_field_aether_forward(sd, x, vel, edges, edge_attr_orig, charges, num_nodes, dropout_masks=None):
+def dynamic_field_aether_forward(sd, x, vel, edges, edge_attr_orig, charges, num_nodes, dropout_masks=None,
+                                 return_all=False, edge_shift=None):
     """DynamicFieldAether.forward (dynamic_field_aether.py:79-100)."""
-    return aether_forward(sd, x, vel, edges, edge_attr_orig, charges,
-                          field=dynamic_field(sd, x, vel, charges, num_nodes), dropout_masks=dropout_masks)
+    return aether_forward(sd, x, vel, edges, edge_attr_orig, charges, return_all=return_all,
+                          field=dynamic_field(sd, x, vel, charges, num_nodes), dropout_masks=dropout_masks,
+                          edge_shift=edge_shift)
 
 
 def cut_margin(edge_attr_local, D):

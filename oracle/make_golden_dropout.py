@@ -5,13 +5,16 @@
   on ``gnn.out_mlp[2]`` / ``[5]``, nn/state2state/locs/locs.py:160-168) together with the output and all gradients, so that
   the oracle's and the HIP path's mask placement and scaling are pinned to the reference and not to a restatement;
 * gradients with respect to the INPUTS (x, vel, edge_attr_orig) of the reference's differentiable forward
-  (nn/state2state/aether.py:169-186), with and without dropout.
+  (nn/state2state/aether.py:169-186), with and without dropout;
+* the same input and parameter gradients at the degenerate inputs of ``case_D{D}_edge_B2N5`` (tag ``edgegrad``: zero
+  velocity, coincident particles, anti-parallel headings, velocities along an axis), where the polar angle's 1/eps slope
+  gives d/dvel and d/dx entries four orders of magnitude above the rest.
 
 TEST INFRASTRUCTURE ONLY.  Runs in the build container (where /root/reference is mounted); never on the GPU box.  Inputs
 and expected outputs only; no reference source is copied.  Same import recipe as oracle/make_golden.py (its torch_scatter
 stand-in).
 
-Usage:  python oracle/make_golden_dropout.py [--out tests/golden]
+Usage:  python oracle/make_golden_dropout.py [--out tests/golden] [--tags dropout,inputgrad,edgegrad]
 """
 from __future__ import annotations
 
@@ -32,7 +35,9 @@ sys.path.insert(0, REPO)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
+    ap.add_argument("--tags", default="dropout,inputgrad,edgegrad")
     args = ap.parse_args()
+    tags = args.tags.split(",")
     os.makedirs(args.out, exist_ok=True)
     import make_golden as MG
     from aether_amd.synthetic import make_batch
@@ -40,12 +45,16 @@ def main():
     torch.set_num_threads(1)
     for D in (2, 3):
         sd = {k: torch.from_numpy(v) for k, v in np.load(os.path.join(REPO, "tests", "golden", f"state_dict_D{D}.npz")).items()}
-        for tag, p, B, N, seed in (("dropout", 0.25, 4, 9, 41), ("inputgrad", 0.0, 3, 12, 42)):
+        for tag, p, B, N, seed in (("dropout", 0.25, 4, 9, 41), ("inputgrad", 0.0, 3, 12, 42), ("edgegrad", 0.0, 2, 5, 4)):
+            if tag not in tags:
+                continue
             with contextlib.redirect_stdout(io.StringIO()):
                 model = Aether(2 * D, 64, p, D, device="cpu")
             model.load_state_dict(sd)
             model.train()
             inp = make_batch(B, N, D, seed=seed)
+            if tag == "edgegrad":        # the inputs of case_D{D}_edge_B2N5 (make_golden.py)
+                inp = MG._refresh_edge_attr(MG._edge_cases(inp, D, N))
             cap = {}
 
             def hook(name):

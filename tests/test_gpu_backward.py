@@ -267,7 +267,9 @@ def test_input_gradients_match_oracle_autograd(D):
 def test_input_gradients_on_random_multigraphs(D):
     """Self loops, duplicate edges, nodes without in- or out-edges, components of 1..40 nodes (the batch of
     test_gradients_on_random_multigraphs): d/dx, d/dvel, d/dedge_attr of both dispatch paths against the oracle's fp64
-    autograd.  (A self loop has rel = 0: distance and bearing sit at their clamps, where both sides give zero slope.)"""
+    autograd.  (A self loop has rel = 0: distance and bearing sit at their clamps, where both sides give zero slope; in 3-D
+    the polar angle keeps a 1/eps slope in r_z there, and d/dx gets zero only because the loop's two ends cancel -- the
+    kernel skips both instead of summing +-1e7-sized terms.)"""
     from test_gpu_configs import _random_multigraph_batch
     sd = load_state_dict(D)
     inp = _random_multigraph_batch(31, D)

@@ -82,6 +82,37 @@ def test_dropout_masks_and_input_gradients_match_reference(D, tag):
         assert scale_rel_err(v.grad, ref["grad_in." + k]) <= 2e-5, k
 
 @pytest.mark.parametrize("D", [2, 3])
+def test_input_gradients_at_degenerate_inputs_match_reference(D):
+    """case_D{D}_edgegrad.npz (oracle/make_golden_dropout.py): the reference's own d/dx, d/dvel, d/dedge_attr and parameter
+    gradients at the inputs of case_D{D}_edge_B2N5 -- zero velocity, coincident particles, anti-parallel headings, v along
+    an axis.  The oracle's fp32 autograd reproduces them, block by block (branch_align.node_blocks: the 3-D zero-velocity
+    slope of d/dvel, 1/eps through the polar angle, is four orders of magnitude above every other entry)."""
+    import branch_align as BA
+    torch.set_num_threads(1)
+    inp, ref, _, meta = load_case(f"case_D{D}_edgegrad.npz")
+    e_inp, e_ref, _, _ = load_case(f"case_D{D}_edge_B2N5.npz")
+    for k in ("x", "vel", "edge_attr", "target", "charges"):
+        assert torch.equal(inp[k], e_inp[k]), k
+    for k in e_ref:
+        if k.startswith("grad."):
+            assert torch.equal(ref[k], e_ref[k]), k
+    res, pg, ig = BA.run_oracle(load_state_dict(D), inp, torch.float32)
+    assert scale_rel_err(res["out"], ref["out"]) <= 1e-6
+    for k, g in pg.items():
+        assert scale_rel_err(g, ref["grad." + k]) <= 2e-5, k
+    graph_of = torch.arange(inp["x"].shape[0]) // meta["N"]
+    for k in ("x", "vel"):
+        for name, err, _ in BA.block_errors(ig[k], ref["grad_in." + k], ig[k], BA.node_blocks(inp["x"], inp["vel"], graph_of)):
+            assert err <= 2e-5, (k, name, err)
+    for name, err, _ in BA.block_errors(ig["edge_attr"], ref["grad_in.edge_attr"], ig["edge_attr"],
+                                        BA.edge_blocks(inp["edges"][1], graph_of)):
+        assert err <= 2e-5, ("edge_attr", name, err)
+    if D == 3:      # the 1/eps slopes are the reference's: zero velocity (node 0) and the coincident pair (nodes 1, 2)
+        assert float(ref["grad_in.vel"][0, 2]) < -1e4
+        assert float(ref["grad_in.x"][1:3, 2].abs().min()) > 10.0
+
+
+@pytest.mark.parametrize("D", [2, 3])
 def test_degenerate_inputs_finite_and_wrap_aware(D):
     """Zero velocity, coincident particles, anti-parallel headings, v || +-z.
 
