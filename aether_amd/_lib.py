@@ -68,6 +68,10 @@ FLAG_WEIGHTS_PREPARED = 16
 FLAG_BACKWARD_ONLY = 32
 FLAG_DROPOUT = 64
 
+EGNN_NORM_DIFF = 1            # aether_egnn_* flags
+EGNN_TANH = 2
+EGNN_KEEP = 4
+
 # name -> (restype, argtypes); every symbol include/aether_hip.h declares
 SIGNATURES = {
     "aether_version": (C.c_char_p, []),
@@ -221,6 +225,14 @@ SIGNATURES = {
                                     C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "aether_graph_matches": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "aether_check_async_error": (C.c_int, []),
+    "aether_egnn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int]),
+    "aether_egnn_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64] +
+                            [C.c_void_p] * 6 + [C.POINTER(AetherGraphInfo), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "aether_egnn_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64] +
+                             [C.c_void_p] * 6 + [C.POINTER(AetherGraphInfo), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                 C.c_int64, C.c_void_p]),
+    "aether_egnn_grad_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "aether_egnn_workspace_offset": (C.c_int64, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
     "aether_profile_enable": (C.c_int, [C.c_int]),
     "aether_profile_kernels": (C.c_int, []),
     "aether_profile_kernel_name": (C.c_char_p, [C.c_int]),

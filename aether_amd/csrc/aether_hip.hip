@@ -45,6 +45,7 @@
 #include "dyn_step.h"
 #include "sim.h"
 #include "train_step.h"
+#include "egnn.h"
 
 #include <mutex>
 #include <utility>
@@ -935,6 +936,7 @@ const char* aether_last_error(void) { return g_err; }
 #include "host_dyn_step.inc"
 #include "host_sim.inc"
 #include "host_train.inc"
+#include "host_egnn.inc"
 
 int aether_set_option(const char* name, int value) {
     if (!name) return fail(AETHER_EINVAL, "set_option: null name");

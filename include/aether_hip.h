@@ -919,6 +919,53 @@ int aether_adamw_step(const AetherAdamWTensor* tensors, int n_tensors, float* st
 int aether_set_option(const char* name, int value);
 
 /*
+ * EGNN-Aether: replaces EGNN_vel_Aether.forward (nn/state2state/egnn_aether.py:65-75) with its layers
+ * E_GCL_vel_field (nn/state2state/gcl.py:59-83 on nn/state2state/egnn/gcl.py:E_GCL) and the field net
+ * (nn/state2state/aether.py:108-134), the model experiments/lorentz/main.py:147 builds for --model egnn_aether.
+ *   params      : n_params = 2 + 15 n_layers + 7 fp32 device tensors in the reference's named_parameters() order:
+ *                 embedding.{weight,bias}; per layer gcl_l.edge_mlp.{0,2}.{weight,bias}, node_mlp.{0,2}.{weight,bias},
+ *                 coord_mlp.0.{weight,bias}, coord_mlp.2.weight, coord_mlp_vel.{0,2}.{weight,bias};
+ *                 field_net.net.{0,2,4}.{weight,bias}, field_net.class_embedding.weight (host array of device pointers)
+ *   hidden      : hidden_nf, 64 or 128;  in_node_nf : width of h;  edge_attr : float[E][2] (in_edge_nf = 2 + 6 field)
+ *   h           : float[n_nodes][in_node_nf];  x, vel : float[n_nodes][3];  charges : float[n_nodes] in {-1, 0, +1}
+ *   graph, info : aether_graph_build(edges[1], edges[0], ...) -- the index rows SWAPPED, so that the view groups the
+ *                 edges by edges[0] (row), over which every sum and mean of E_GCL runs (egnn/gcl.py:69-101)
+ *   out         : float[n_nodes][3], the returned x.  The caller's x is not written (the reference adds into it in
+ *                 place, gcl.py:81 / egnn/gcl.py:97; the runner never reads it again)
+ *   flags       : AETHER_EGNN_NORM_DIFF (norm_diff), AETHER_EGNN_TANH (tanh), AETHER_EGNN_KEEP (keep-for-backward form:
+ *                 every layer's h, x and row sums of m stay in the workspace for aether_egnn_backward)
+ * Per layer one launch (edge MLP, phi, clamp and both row sums in the edge loop of a node's workgroup; psi, the x update,
+ * node_mlp and the residual after it).  Deterministic: no float atomics.  fp32 throughout (csrc/egnn.h).
+ */
+#define AETHER_EGNN_NORM_DIFF 1
+#define AETHER_EGNN_TANH 2
+#define AETHER_EGNN_KEEP 4
+size_t aether_egnn_workspace_bytes(int hidden, int n_layers, int in_node_nf, int64_t n_nodes, int64_t n_edges,
+                                   int keep_for_backward);
+int aether_egnn_forward(const float* const* params, int n_params, int hidden, int n_layers, int in_node_nf, int flags,
+                        int64_t n_nodes, int64_t n_edges, const float* h, const float* x, const float* vel,
+                        const float* edge_attr, const float* charges, const void* graph, const AetherGraphInfo* info,
+                        void* workspace, size_t workspace_bytes, float* out, void* stream);
+/*
+ * Parameter gradients of a loss given dL/d(out) (grad_out, float[n_nodes][3]): replaces loss.backward() through
+ * EGNN_vel_Aether (experiments/lorentz/main.py:254-292; the runner detaches every input, so no input gradient).
+ * Reads the workspace of an aether_egnn_forward(... AETHER_EGNN_KEEP) with the same arguments.  OVERWRITES `grad`:
+ * one flat fp32 buffer, every parameter at the next multiple of 4 floats in named_parameters() order (the drop-in's
+ * _grad_buffers layout), aether_egnn_grad_floats() floats.  Where the +-100 clamp of the translation is active the
+ * gradient is zero, as in torch.  Weight gradients: row chunks summed in a fixed order (no atomics).
+ */
+int aether_egnn_backward(const float* const* params, int n_params, int hidden, int n_layers, int in_node_nf, int flags,
+                         int64_t n_nodes, int64_t n_edges, const float* h, const float* x, const float* vel,
+                         const float* edge_attr, const float* charges, const void* graph, const AetherGraphInfo* info,
+                         void* workspace, size_t workspace_bytes, const float* grad_out, float* grad, int64_t grad_floats,
+                         void* stream);
+int64_t aether_egnn_grad_floats(int hidden, int n_layers, int in_node_nf);
+/* Byte offset, in a keep-for-backward workspace, of "field" (float[n_nodes][3]) or of layer `layer`'s input "h"
+ * (float[n_nodes][hidden]) / "x" (float[n_nodes][3]); layer n_layers is the model's last h / output x.  Tests. */
+int64_t aether_egnn_workspace_offset(const char* name, int layer, int hidden, int n_layers, int in_node_nf, int64_t n_nodes,
+                                     int64_t n_edges);
+
+/*
  * A kernel cannot return a status.  The one bounded wait in the library -- a split-mode workgroup of the fused
  * kernel polling for its partner's rows -- sets a word in host-mapped memory when it gives up (partner not
  * resident within ~seconds); the results of that launch are then invalid.  Every launching entry point checks and
