@@ -5,6 +5,7 @@ with the host helpers ``aether_amd.edges`` / ``aether_amd.synthetic`` / ``aether
 Widened rows of SURVEY.md 8f (each mirrors the reference module of the same name):
 
 * ``aether_amd.nn.state2state.dynamic_field_aether.DynamicFieldAether``
+* ``aether_amd.nn.state2state.locs.LoCS`` (the no-field baseline, on the same kernels with a zero field)
 * ``aether_amd.nn.seq2seq.{aether.Aether, dynamic_field_aether.DynamicFieldAether}`` (+ ``encoder``, ``decoder``, ``field``,
   ``localizer``)
 * ``aether_amd.nn.dynamicvars.{aether_dynamicvars.AetherDynamicVars, encoder.Encoder, decoder.Decoder}``

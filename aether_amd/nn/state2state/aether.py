@@ -79,6 +79,55 @@ class _WsToken:
     __slots__ = ("__weakref__",)
 
 
+def _train_workspace(module, ws_bytes, device):
+    """The workspace of a training forward and the token its autograd node holds (None under capture).
+
+    The backward reads this forward's intermediates: one workspace per forward that is still waiting for its backward.
+    The usual loop (forward, backward, step) gets the module's cached buffer back every time -- a fresh torch.empty per
+    call kept TWO of them alive across steps (this one and the previous step's, still referenced), which at the 33.5 M-edge
+    shard of config 5 (~120 GB each) pushed the caching allocator into freeing and re-allocating device memory every step
+    (0.44 s of a 0.55 s step).  Under hipGraph capture the buffer comes from the graph's pool as before.
+    "Still waiting": the autograd node that saved the buffer is alive (a token it holds; after backward() without
+    retain_graph the node and the token are gone).  The module keeps ``_train_ws`` and ``_train_ws_token``."""
+    tw, tok = module._train_ws, module._train_ws_token
+    busy = tok is not None and tok() is not None
+    capturing = torch.cuda.is_current_stream_capturing()
+    if tw is not None and not busy and tw.numel() >= ws_bytes and tw.device == device and not capturing:
+        ws = tw
+    else:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        if not capturing:
+            module._train_ws = ws
+    token = _WsToken() if not capturing else None
+    if token is not None:
+        module._train_ws_token = weakref.ref(token)
+    return ws, token
+
+
+def _hand_over_grads(module, plist, views, dst_flat, dst_views, aliased, need):
+    """After a backward wrote its parameter gradients into ``dst_flat`` (``dst_views``): the data-parallel mean, then what
+    autograd returns for the parameters.  A parameter whose .grad is unset gets the view of the flat buffer itself (like
+    DDP's gradient_as_bucket_view); a .grad that already is that view is accumulated into in place (``aliased``: the
+    backward wrote into the second buffer); any other existing .grad is accumulated by autograd."""
+    if module.dp_group is not None:            # one fused all-reduce of the flat buffer (RCCL)
+        import torch.distributed as dist
+        dist.all_reduce(dst_flat, group=module.dp_group)
+        dst_flat.div_(dist.get_world_size(module.dp_group))
+    out = []
+    for p, v, dv, n in zip(plist, views, dst_views, need):
+        if not n:
+            out.append(None)
+        elif module.grad_as_view and p.grad is None and not aliased:
+            p.grad = v
+            out.append(None)
+        elif module.grad_as_view and p.grad is not None and p.grad.data_ptr() == v.data_ptr():
+            v.add_(dv)
+            out.append(None)
+        else:
+            out.append(dv.clone())
+    return out
+
+
 class _AetherStep(torch.autograd.Function):
     """aether_forward / aether_backward behind torch.autograd (parameters only get gradients:
     the runner detaches positions and edge attributes, experiments/lorentz/main.py:243-247)."""
@@ -103,26 +152,7 @@ class _AetherStep(torch.autograd.Function):
         ws_bytes = module._workspace_bytes(n_nodes, n_edges, keep)
         ws_key = None
         if train:
-            # The backward reads this forward's intermediates: one workspace per forward that is still waiting for its
-            # backward.  The usual loop (forward, backward, step) gets the module's cached buffer back every time -- a
-            # fresh torch.empty per call kept TWO of them alive across steps (this one and the previous step's, still
-            # referenced), which at the 33.5 M-edge shard of config 5 (~120 GB each) pushed the caching allocator into
-            # freeing and re-allocating device memory every step (0.44 s of a 0.55 s step).  Under hipGraph capture the
-            # buffer comes from the graph's pool as before.
-            # "Still waiting": the autograd node that saved the buffer is alive (a token it holds; after backward() without
-            # retain_graph the node and the token are gone).
-            tw, tok = module._train_ws, module._train_ws_token
-            busy = tok is not None and tok() is not None
-            capturing = torch.cuda.is_current_stream_capturing()
-            if tw is not None and not busy and tw.numel() >= ws_bytes and tw.device == x.device and not capturing:
-                ws = tw
-            else:
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-                if not capturing:
-                    module._train_ws = ws
-            token = _WsToken() if not capturing else None
-            if token is not None:
-                module._train_ws_token = weakref.ref(token)
+            ws, token = _train_workspace(module, ws_bytes, x.device)
             # An optimizer step follows a training forward, and not every optimizer bumps the parameters' version
             # counters (torch's fused AdamW does not): the inference workspace's weight images are stale from here on.
             module._wimg_key = None
@@ -234,26 +264,8 @@ class _AetherStep(torch.autograd.Function):
                 gx = None
             if not ctx.needs_input_grad[2]:
                 gv = None
-        if module.dp_group is not None:            # one fused all-reduce of the flat buffer (RCCL)
-            import torch.distributed as dist
-            dist.all_reduce(dst_flat, group=module.dp_group)
-            dst_flat.div_(dist.get_world_size(module.dp_group))
-        # Hand the gradients over as views of the flat buffer (no 47 small copies): a parameter whose
-        # .grad is unset gets the view itself (like DDP's gradient_as_bucket_view); a .grad that already is
-        # that view is accumulated into in place; any other existing .grad is accumulated by autograd.
-        need = ctx.needs_input_grad[_AetherStep.N_FIXED:]
-        out = []
-        for p, v, dv, n in zip(plist, views, dst_views, need):
-            if not n:
-                out.append(None)
-            elif module.grad_as_view and p.grad is None and not aliased:
-                p.grad = v
-                out.append(None)
-            elif module.grad_as_view and p.grad is not None and p.grad.data_ptr() == v.data_ptr():
-                v.add_(dv)
-                out.append(None)
-            else:
-                out.append(dv.clone())
+        # hand the gradients over as views of the flat buffer (no 47 small copies)
+        out = _hand_over_grads(module, plist, views, dst_flat, dst_views, aliased, ctx.needs_input_grad[_AetherStep.N_FIXED:])
         return (None, gx, gv, gea, None, None, None) + tuple(out)
 
 
