@@ -6,6 +6,7 @@ Widened rows of SURVEY.md 8f (each mirrors the reference module of the same name
 
 * ``aether_amd.nn.state2state.dynamic_field_aether.DynamicFieldAether``
 * ``aether_amd.nn.state2state.locs.LoCS`` (the no-field baseline, on the same kernels with a zero field)
+* ``aether_amd.nn.state2state.clof.{ClofNet, ClofNet_vel, ClofNet_vel_gbf}`` (the Lorentz runner's ClofNet baseline)
 * ``aether_amd.nn.seq2seq.{aether.Aether, dynamic_field_aether.DynamicFieldAether}`` (+ ``encoder``, ``decoder``, ``field``,
   ``localizer``)
 * ``aether_amd.nn.dynamicvars.{aether_dynamicvars.AetherDynamicVars, encoder.Encoder, decoder.Decoder}``

@@ -72,6 +72,11 @@ EGNN_NORM_DIFF = 1            # aether_egnn_* flags
 EGNN_TANH = 2
 EGNN_KEEP = 4
 
+CLOF_NORM_DIFF = 1          # aether_clof_* flags
+CLOF_TANH = 2
+CLOF_KEEP = 4
+CLOF_RECURRENT = 8
+
 # name -> (restype, argtypes); every symbol include/aether_hip.h declares
 SIGNATURES = {
     "aether_version": (C.c_char_p, []),
@@ -233,6 +238,17 @@ SIGNATURES = {
                                                  C.c_int64, C.c_void_p]),
     "aether_egnn_grad_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "aether_egnn_workspace_offset": (C.c_int64, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
+    "aether_clof_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int]),
+    "aether_clof_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                      C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 +
+                            [C.POINTER(AetherGraphInfo), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "aether_clof_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                       C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 +
+                             [C.POINTER(AetherGraphInfo), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int64,
+                              C.c_void_p]),
+    "aether_clof_grad_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "aether_clof_workspace_offset": (C.c_int64, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                                 C.c_int64]),
     "aether_profile_enable": (C.c_int, [C.c_int]),
     "aether_profile_kernels": (C.c_int, []),
     "aether_profile_kernel_name": (C.c_char_p, [C.c_int]),

@@ -46,6 +46,7 @@
 #include "sim.h"
 #include "train_step.h"
 #include "egnn.h"
+#include "clof.h"
 
 #include <mutex>
 #include <utility>
@@ -937,6 +938,7 @@ const char* aether_last_error(void) { return g_err; }
 #include "host_sim.inc"
 #include "host_train.inc"
 #include "host_egnn.inc"
+#include "host_clof.inc"
 
 int aether_set_option(const char* name, int value) {
     if (!name) return fail(AETHER_EINVAL, "set_option: null name");

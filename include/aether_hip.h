@@ -966,6 +966,62 @@ int64_t aether_egnn_workspace_offset(const char* name, int layer, int hidden, in
                                      int64_t n_edges);
 
 /*
+ * ClofNet: replaces the forward of ClofNet / ClofNet_vel / ClofNet_vel_gbf (nn/state2state/clof/clof.py:86-101, 187-202,
+ * 285-302) with their layers Clof_GCL (nn/state2state/clof/gcl.py:54-66 on nn/state2state/egnn/gcl.py:E_GCL), the models
+ * experiments/lorentz/main.py:152-157 builds for --model clof, clof_vel and clof_vel_gbf.
+ *   variant     : 0 ClofNet, 1 ClofNet_vel, 2 ClofNet_vel_gbf
+ *   params      : n_params = head + 19 n_layers fp32 device tensors in the reference's named_parameters() order:
+ *                 embedding_node.{weight,bias}; then ClofNet embedding_edge.0.{weight,bias} (never used, clof.py:93),
+ *                 fuse_edge.{0,2}.{weight,bias} (head 8); ClofNet_vel fuse_edge.{0,2}.{weight,bias} (head 6);
+ *                 ClofNet_vel_gbf gbf.{means,stds,mul,bias}.weight, fuse_edge.{0,2}.{weight,bias} (head 10); per layer
+ *                 gcl_l.edge_mlp.{0,2,4}.{weight,bias}, node_mlp.{0,2}.{weight,bias}, coord_mlp.0.{weight,bias},
+ *                 coord_mlp.2.weight, coord_mlp_vel.{0,2}.{weight,bias}, layer_norm.{weight,bias}
+ *   hidden      : hidden_nf, 64 or 128;  in_node_nf : width of h;  edge_attr : float[E][2] ([q_row q_col, |x_row - x_col|^2])
+ *   h           : float[n_nodes][in_node_nf];  x, vel : float[n_nodes][3]
+ *   n_per_graph : the forward's n_nodes argument: x is centred per block of n_per_graph rows (clof.py:88-90)
+ *   graph, info : aether_graph_build(edges[1], edges[0], ...) -- the index rows SWAPPED, so that the view groups the
+ *                 edges by edges[0] (row), over which every sum and mean of Clof_GCL runs
+ *   out         : float[n_nodes][3], the returned x.  The caller's x is not written.
+ *   flags       : AETHER_CLOF_NORM_DIFF (the layers' norm_diff; ClofNet also scalarizes with it, the _vel variants always
+ *                 normalise there, clof.py:113,190), AETHER_CLOF_TANH, AETHER_CLOF_RECURRENT, AETHER_CLOF_KEEP
+ *                 (keep-for-backward form: every layer's h, x and pre-activations stay in the workspace)
+ * The cross products are per edge.  torch.cross without dim (gcl.py:29, clof.py:69) takes the first axis of size 3,
+ * which is the edge axis when there are exactly 3 edges; this entry always takes the per-edge product.  The Gaussian
+ * layer's edge type (edge_attr[:, 0] * 0.5 + 0.5, truncated) is clamped to [0, 7] (the reference raises an index error
+ * outside it).  Deterministic: no float atomics.  fp32 throughout, edge MLPs on fp32 MFMA (csrc/clof.h).
+ */
+#define AETHER_CLOF_NORM_DIFF 1
+#define AETHER_CLOF_TANH 2
+#define AETHER_CLOF_KEEP 4
+#define AETHER_CLOF_RECURRENT 8
+size_t aether_clof_workspace_bytes(int variant, int hidden, int n_layers, int in_node_nf, int64_t n_nodes, int64_t n_edges,
+                                   int keep_for_backward);
+int aether_clof_forward(const float* const* params, int n_params, int variant, int hidden, int n_layers, int in_node_nf,
+                        int flags, float coords_weight, int n_per_graph, int64_t n_nodes, int64_t n_edges, const float* h,
+                        const float* x, const float* vel, const float* edge_attr, const void* graph,
+                        const AetherGraphInfo* info, void* workspace, size_t workspace_bytes, float* out, void* stream);
+/*
+ * Parameter gradients of a loss given dL/d(out) (grad_out, float[n_nodes][3]): replaces loss.backward() through the
+ * ClofNet models (experiments/lorentz/main.py:266-292; the runner detaches every input, so no input gradient).  Reads the
+ * workspace of an aether_clof_forward(... AETHER_CLOF_KEEP) with the same arguments.  Writes `grad`: one flat fp32
+ * buffer, every parameter at the next multiple of 4 floats in named_parameters() order (the drop-in's _grad_buffers
+ * layout), aether_clof_grad_floats() floats.  Parameters that do not reach the output -- the last layer's node_mlp and
+ * layer_norm, ClofNet's embedding_edge -- are not written.  Where the +-100 clamp of the translation is active the
+ * gradient is zero, as in torch.  Weight gradients: fp32 MFMA over row chunks summed in a fixed order (no atomics).
+ */
+int aether_clof_backward(const float* const* params, int n_params, int variant, int hidden, int n_layers, int in_node_nf,
+                         int flags, float coords_weight, int n_per_graph, int64_t n_nodes, int64_t n_edges, const float* h,
+                         const float* x, const float* vel, const float* edge_attr, const void* graph,
+                         const AetherGraphInfo* info, void* workspace, size_t workspace_bytes, const float* grad_out,
+                         float* grad, int64_t grad_floats, void* stream);
+int64_t aether_clof_grad_floats(int variant, int hidden, int n_layers, int in_node_nf);
+/* Byte offset, in a keep-for-backward workspace, of "edge_feat" (float[n_edges][hidden / 2], row-sorted order) or of
+ * layer `layer`'s input "h" (float[n_nodes][hidden]) / centred "x" (float[n_nodes][3]); layer n_layers is the last
+ * layer's output.  Tests. */
+int64_t aether_clof_workspace_offset(const char* name, int layer, int variant, int hidden, int n_layers, int in_node_nf,
+                                     int64_t n_nodes, int64_t n_edges);
+
+/*
  * A kernel cannot return a status.  The one bounded wait in the library -- a split-mode workgroup of the fused
  * kernel polling for its partner's rows -- sets a word in host-mapped memory when it gives up (partner not
  * resident within ~seconds); the results of that launch are then invalid.  Every launching entry point checks and
