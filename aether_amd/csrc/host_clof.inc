@@ -331,7 +331,7 @@ int clof_backward_impl(const ClofCall& c, const float* const* params, const Clof
         BG.ga1 = wp(Lo.ga1); BG.ghp = wp(Lo.ghp); BG.gx = gx_out; BG.gxr = wp(Lo.gxr); BG.gxc = wp(Lo.gxc);
         BG.srow = wp(Lo.srow); BG.scol = wp(Lo.scol); BG.gh = ghb(s); BG.gxo = gxb(s);
         clof::kb_clof_gather<H><<<dim3(nb), dim3(H), 0, st>>>(W, BG, KIN, Nn, c.rowptr, c.sperm, c.srowptr,
-                                                              (first || E == 0) ? 1 : 0);
+                                                              first ? 1 : 0);
         // weight gradients of layer l (parameters p0 ...); the last layer's node_mlp and layer_norm are dead
         const int p0 = clof_head(v) + CLOF_PER_LAYER * l, SILU = 1;
         ClofJobs J;

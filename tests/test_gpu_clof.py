@@ -80,8 +80,17 @@ def test_gradients_against_the_fixture_and_the_restatement(case):
             continue
         assert gv is not None, k
         gc = gv.cpu()
-        assert rel(gc, d["ref.grad." + k]) < GRAD_TOL, (k, rel(gc, d["ref.grad." + k]))
         assert rel(gc, g64[k]) < GRAD_TOL, (k, rel(gc, g64[k]))
+        if "ref.grad." + k not in d.files:
+            # a slim case (width 128, four layers): the fixture holds sum, sum of |.| and max of |.| of every gradient.
+            # max|a - b| < GRAD_TOL max|b| bounds each checksum's difference by numel GRAD_TOL max|b|
+            for tag in ("ref", "ref64"):
+                bound = gc.numel() * GRAD_TOL * float(d[f"{tag}.gmax.{k}"])
+                assert abs(float(gc.double().sum()) - float(d[f"{tag}.gsum.{k}"])) <= bound, (tag, k)
+                assert abs(float(gc.double().abs().sum()) - float(d[f"{tag}.gabs.{k}"])) <= bound, (tag, k)
+                assert abs(float(gc.abs().max()) - float(d[f"{tag}.gmax.{k}"])) < GRAD_TOL * float(d[f"{tag}.gmax.{k}"])
+            continue
+        assert rel(gc, d["ref.grad." + k]) < GRAD_TOL, (k, rel(gc, d["ref.grad." + k]))
         if "ref64.grad." + k in d.files:
             assert rel(gc, d["ref64.grad." + k]) < GRAD_TOL, k
 

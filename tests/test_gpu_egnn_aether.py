@@ -78,8 +78,18 @@ def test_parameter_gradients_match_reference(case):
                        cfg["L"], cfg["norm_diff"], cfg["tanh"])
     for k, gk in grads.items():
         assert torch.isfinite(gk).all(), k
-        assert scale_rel_err(gk, torch.from_numpy(d["ref.grad." + k])) <= GTOL, (k, "fp32 reference")
         assert scale_rel_err(gk, g64[k]) <= GTOL, (k, "restatement")
+        if "ref.grad." + k not in d.files:
+            # the slim case (width 128, four layers): the fixture holds sum, sum of |.| and max of |.| of every gradient.
+            # max|a - b| <= GTOL max|b| bounds each checksum's difference by numel GTOL max|b|
+            for tag in ("ref", "ref64"):
+                gmax = float(d[f"{tag}.gmax.{k}"])
+                bound = gk.numel() * GTOL * gmax
+                assert abs(float(gk.double().sum()) - float(d[f"{tag}.gsum.{k}"])) <= bound, (tag, k)
+                assert abs(float(gk.double().abs().sum()) - float(d[f"{tag}.gabs.{k}"])) <= bound, (tag, k)
+                assert abs(float(gk.abs().max()) - gmax) <= GTOL * gmax, (tag, k)
+            continue
+        assert scale_rel_err(gk, torch.from_numpy(d["ref.grad." + k])) <= GTOL, (k, "fp32 reference")
         if "ref64.grad." + k in d.files:
             assert scale_rel_err(gk, torch.from_numpy(d["ref64.grad." + k])) <= GTOL, (k, "fp64 reference")
 

@@ -19,6 +19,13 @@ experiments/lorentz/main.py:266-271 builds them (tests/egnn_restatement.py::runn
                               parameters whose .grad torch leaves None
   ref64.*                     the same after .double(); full fp64 gradients in the one-layer cases, sums (gsum / gabs)
                               in every case
+  in_node_nf, graph           only in the cases that leave the runner's inputs: the width of h (h = [|vel|, q, |x|]) and
+                              "multi" (tests/graph_cases.py::random_multigraph: duplicate edges, a self loop, a node
+                              without edges, rows in random order) or "empty" (no edge at all)
+
+The cases of width 128 with four layers are "slim": their fp32 gradient tensors alone would exceed the 1 MiB file limit,
+so they hold no ref.grad.* and no param.*, and instead ref.gsum.* / ref.gabs.* / ref.gmax.* (sum, sum of |.|, max of |.|
+of every fp32 gradient, as fp64 numbers) next to ref64.gsum.* / ref64.gabs.* / ref64.gmax.*.
 
 No case has exactly 3 edges (torch.cross without dim would cross along the edge axis there).  Reruns reproduce the files
 byte for byte (np.savez of deterministic CPU results; no timestamps).
@@ -43,6 +50,7 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 
 import make_golden as MG                      # noqa: E402  (torch_scatter stand-in)
 import egnn_restatement as R                  # noqa: E402  (runner_batch)
+import graph_cases as GC                      # noqa: E402  (inputs off the runner's graphs)
 
 CLASSES = {"clof": "ClofNet", "clof_vel": "ClofNet_vel", "clof_vel_gbf": "ClofNet_vel_gbf"}
 
@@ -61,6 +69,17 @@ CASES = [
     # |translation| > 100 on some edges: coord_mlp.2's weight x 4e6 (zero gradient there).  With norm_diff the frame
     # vectors are bounded by 1, so the translation is the coefficients themselves: no cancellation amplifies fp32 rounding
     ("clof_vel_B2N5_H64_L1_clamp", "clof_vel", 6110, 2, 5, 64, 1, True, False, True, 1.0, 1.0, 4e6),
+    # width 128 at depth: the not-last node kernel and LayerNorm at 128 (slim files, see above)
+    ("clof_vel_B2N5_H128_L4", "clof_vel", 6111, 2, 5, 128, 4, True, False, True, 1.0, 1.0, 1.0),
+    ("clof_B2N5_H128_L4", "clof", 6112, 2, 5, 128, 4, True, False, True, 1.0, 1.0, 1.0),
+    ("clof_vel_gbf_B2N5_H128_L4", "clof_vel_gbf", 6113, 2, 5, 128, 4, True, False, True, 1.0, 1.0, 1.0),
+    ("clof_vel_B2N5_H64_L4_norec_cw_tanh", "clof_vel", 6114, 2, 5, 64, 4, True, True, False, 0.5, 1.0, 1.0),
+    ("clof_vel_B2N5_H64_L2_innf3", "clof_vel", 6115, 2, 5, 64, 2, True, False, True, 1.0, 1.0, 1.0, dict(in_nf=3)),
+    # a self loop: norm_diff off in the layers (sqrt at 0 has a NaN gradient in the reference)
+    ("clof_vel_B2N6_H64_L2_multigraph", "clof_vel", 6116, 2, 6, 64, 2, False, False, True, 1.0, 1.0, 1.0,
+     dict(graph="multi")),
+    ("clof_vel_B2N5_H64_L2_noedges", "clof_vel", 6117, 2, 5, 64, 2, True, False, True, 1.0, 1.0, 1.0,
+     dict(graph="empty")),
 ]
 
 
@@ -74,10 +93,10 @@ def reference():
     yield A
 
 
-def build_model(A, model, seed, H, L, norm_diff, tanh, recurrent, cw, coord_scale):
+def build_model(A, model, seed, H, L, norm_diff, tanh, recurrent, cw, coord_scale, in_nf=1):
     torch.manual_seed(seed)
     with contextlib.redirect_stdout(io.StringIO()):
-        m = getattr(A, CLASSES[model])(in_node_nf=1, in_edge_nf=2, hidden_nf=H, device="cpu", n_layers=L,
+        m = getattr(A, CLASSES[model])(in_node_nf=in_nf, in_edge_nf=2, hidden_nf=H, device="cpu", n_layers=L,
                                        coords_weight=cw, recurrent=recurrent, norm_diff=norm_diff, tanh=tanh)
     if coord_scale != 1.0:
         with torch.no_grad():
@@ -111,15 +130,36 @@ def run(m, inp, L, N):
     return ref_out, hs, xs
 
 
-def case_fixture(A, name, model, seed, B, N, H, L, norm_diff, tanh, recurrent, cw, pos_scale, coord_scale):
-    m = build_model(A, model, seed, H, L, norm_diff, tanh, recurrent, cw, coord_scale)
+def case_inputs(B, N, seed, pos_scale, in_nf, graph):
+    if graph == "multi":
+        inp = GC.random_multigraph(B, N, seed + 1, self_loop=True, dtype=torch.float32)
+        row, col = inp["edges"]
+        deg_r, deg_c = (torch.bincount(t, minlength=B * N) for t in (row, col))
+        assert int((row == col).sum()) == 1 and int(((deg_r == 0) & (deg_c == 0)).sum()) >= B
+        assert torch.unique(torch.stack([row, col]), dim=1).shape[1] < row.numel()           # duplicate edges
+    else:
+        inp = R.runner_batch(B, N, seed + 1, pos_scale=pos_scale)
+        if graph == "empty":
+            inp = GC.without_edges(inp)
+    if in_nf != 1:
+        inp = GC.with_wide_h(inp, in_nf)
+    return inp
+
+
+def case_fixture(A, name, model, seed, B, N, H, L, norm_diff, tanh, recurrent, cw, pos_scale, coord_scale, extra=None):
+    extra = extra or {}
+    in_nf, graph = extra.get("in_nf", 1), extra.get("graph", "runner")
+    m = build_model(A, model, seed, H, L, norm_diff, tanh, recurrent, cw, coord_scale, in_nf)
     sd = m.state_dict()
     full = L == 1 and H == 64
-    inp = R.runner_batch(B, N, seed + 1, pos_scale=pos_scale)
+    slim = L > 1 and H == 128
+    inp = case_inputs(B, N, seed, pos_scale, in_nf, graph)
     assert inp["edges"][0].numel() != 3
     o = {"seed": np.int64(seed), "variant": np.array(model),
          "config": np.array([B, N, H, L, int(norm_diff), int(tanh), int(recurrent)], dtype=np.int64),
          "coords_weight": np.float64(cw), "coord_scale": np.float64(coord_scale), "keys": np.array(list(sd.keys()))}
+    if extra:
+        o["in_node_nf"], o["graph"] = np.int64(in_nf), np.array(graph)
     for k, v in sd.items():
         o["sum." + k] = np.float64(v.double().sum().item())
         o["abs." + k] = np.float64(v.double().abs().sum().item())
@@ -128,7 +168,7 @@ def case_fixture(A, name, model, seed, B, N, H, L, norm_diff, tanh, recurrent, c
     for k in ("h", "x", "vel", "edge_attr", "target"):
         o["in." + k] = inp[k].numpy()
     o["in.row"], o["in.col"] = inp["edges"][0].numpy(), inp["edges"][1].numpy()
-    if model == "clof_vel_gbf":                  # both edge types occur
+    if model == "clof_vel_gbf" and graph != "empty":                  # both edge types occur
         assert set((inp["edge_attr"][:, 0] * 0.5 + 0.5).long().tolist()) == {0, 1}
     for tag in ("ref", "ref64"):
         model_t = m if tag == "ref" else m.double()
@@ -149,11 +189,13 @@ def case_fixture(A, name, model, seed, B, N, H, L, norm_diff, tanh, recurrent, c
                 dead.append(k)
                 continue
             g = p.grad.detach()
-            if tag == "ref" or full:
+            if (tag == "ref" and not slim) or full:
                 o[f"{tag}.grad.{k}"] = g.numpy().copy()
-            if tag == "ref64":
-                o["ref64.gsum." + k] = np.float64(g.sum().item())
-                o["ref64.gabs." + k] = np.float64(g.abs().sum().item())
+            if tag == "ref64" or slim:
+                o[f"{tag}.gsum.{k}"] = np.float64(g.double().sum().item())
+                o[f"{tag}.gabs.{k}"] = np.float64(g.double().abs().sum().item())
+            if slim:
+                o[f"{tag}.gmax.{k}"] = np.float64(g.double().abs().max().item())
         o[tag + ".dead"] = np.array(dead)
     if coord_scale != 1.0:         # the clamp must be active on some edges and inactive on others, in the first layer
         m32 = build_model(A, model, seed, H, L, norm_diff, tanh, recurrent, cw, coord_scale)

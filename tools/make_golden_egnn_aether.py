@@ -17,6 +17,13 @@ experiments/lorentz/main.py:204-259 builds them (tests/egnn_restatement.py::runn
   ref64.out / ref64.h<l> / ref64.x<l>   the same after .double()
   ref64.grad.*                fp64 gradients in the same cases; ref64.gsum.* / ref64.gabs.* (sum, sum of |.|) for every
                               case -- full fp64 gradients of the larger models would exceed the file size limit
+  in_node_nf, graph           only in the cases that leave the runner's inputs: the width of h (h = [|vel|, q, |x|]) and
+                              "multi" (tests/graph_cases.py::random_multigraph: duplicate edges, a self loop, a node
+                              without edges, rows in random order) or "empty" (no edge at all)
+
+The case of width 128 with four layers is "slim": its fp32 gradient tensors alone would exceed the 1 MiB file limit, so
+it holds no ref.grad.* and instead ref.gsum.* / ref.gabs.* / ref.gmax.* (sum, sum of |.|, max of |.| of every fp32
+gradient, as fp64 numbers) next to ref64.gsum.* / ref64.gabs.* / ref64.gmax.*.
 
 Reruns reproduce the files byte for byte (np.savez of deterministic CPU results; no timestamps).
 
@@ -40,6 +47,7 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 
 import make_golden as MG                      # noqa: E402  (torch_scatter stand-in)
 import egnn_restatement as R                  # noqa: E402  (runner_batch)
+import graph_cases as GC                      # noqa: E402  (inputs off the runner's graphs)
 
 # name, seed, B, N, hidden_nf, n_layers, norm_diff, tanh, pos_scale, phi_scale
 CASES = [
@@ -51,6 +59,14 @@ CASES = [
     ("B1N2_H128_L1", 5106, 1, 2, 128, 1, False, False, 1.0, 1.0),
     # |d * phi| > 100 on some edges: positions x 30 and phi's last weight x 3000 (the clamp's gradient is zero there)
     ("B2N5_H64_L1_clamp", 5107, 2, 5, 64, 1, False, False, 30.0, 3000.0),
+    ("B2N5_H128_L4_norm", 5108, 2, 5, 128, 4, True, False, 1.0, 1.0),                  # slim, see above
+    # four layers: positions x 3 and phi x 30000.  At positions x 30 the fp32 reference's own gradients are 1.1e-4 from
+    # the fp64 ones (max|a - b| / max|b|), past the 5e-5 bar of the GPU tests; here they are 1e-5 away
+    ("B2N5_H64_L4_clamp", 5109, 2, 5, 64, 4, False, False, 3.0, 30000.0),
+    ("B2N5_H64_L2_innf3", 5110, 2, 5, 64, 2, False, True, 1.0, 1.0, dict(in_nf=3)),
+    # a self loop: norm_diff off (sqrt at 0 has a NaN gradient in the reference)
+    ("B2N6_H64_L2_multigraph", 5111, 2, 6, 64, 2, False, False, 1.0, 1.0, dict(graph="multi")),
+    ("B2N5_H64_L2_noedges", 5112, 2, 5, 64, 2, True, False, 1.0, 1.0, dict(graph="empty")),
 ]
 
 
@@ -64,10 +80,10 @@ def reference():
     yield A
 
 
-def build_model(A, seed, H, L, norm_diff, tanh, phi_scale):
+def build_model(A, seed, H, L, norm_diff, tanh, phi_scale, in_nf=1):
     torch.manual_seed(seed)
     with contextlib.redirect_stdout(io.StringIO()):
-        m = A.EGNN_vel_Aether(in_node_nf=1, in_edge_nf=8, hidden_nf=H, num_dims=3, device="cpu", n_layers=L,
+        m = A.EGNN_vel_Aether(in_node_nf=in_nf, in_edge_nf=8, hidden_nf=H, num_dims=3, device="cpu", n_layers=L,
                               recurrent=True, norm_diff=norm_diff, tanh=tanh)
     if phi_scale != 1.0:
         with torch.no_grad():
@@ -93,13 +109,35 @@ def run(m, inp, L):
     return out, hs, xs
 
 
-def case_fixture(A, name, seed, B, N, H, L, norm_diff, tanh, pos_scale, phi_scale):
-    m = build_model(A, seed, H, L, norm_diff, tanh, phi_scale)
+def case_inputs(B, N, seed, pos_scale, in_nf, graph):
+    if graph == "multi":
+        inp = GC.random_multigraph(B, N, seed + 1, self_loop=True, dtype=torch.float32)
+        row, col = inp["edges"]
+        deg_r, deg_c = (torch.bincount(t, minlength=B * N) for t in (row, col))
+        assert int((row == col).sum()) == 1 and int(((deg_r == 0) & (deg_c == 0)).sum()) >= B
+        assert torch.unique(torch.stack([row, col]), dim=1).shape[1] < row.numel()           # duplicate edges
+        assert row.numel() != 3
+    else:
+        inp = R.runner_batch(B, N, seed + 1, pos_scale=pos_scale)
+        if graph == "empty":
+            inp = GC.without_edges(inp)
+    if in_nf != 1:
+        inp = GC.with_wide_h(inp, in_nf)
+    return inp
+
+
+def case_fixture(A, name, seed, B, N, H, L, norm_diff, tanh, pos_scale, phi_scale, extra=None):
+    extra = extra or {}
+    in_nf, graph = extra.get("in_nf", 1), extra.get("graph", "runner")
+    m = build_model(A, seed, H, L, norm_diff, tanh, phi_scale, in_nf)
     sd = m.state_dict()
     full = L == 1 and H == 64            # parameters and fp64 gradients in full (the others: size limit)
-    inp = R.runner_batch(B, N, seed + 1, pos_scale=pos_scale)
+    slim = L > 1 and H == 128
+    inp = case_inputs(B, N, seed, pos_scale, in_nf, graph)
     o = {"seed": np.int64(seed), "config": np.array([B, N, H, L, int(norm_diff), int(tanh)], dtype=np.int64),
          "keys": np.array(list(sd.keys())), "phi_scale": np.float64(phi_scale)}
+    if extra:
+        o["in_node_nf"], o["graph"] = np.int64(in_nf), np.array(graph)
     for k, v in sd.items():
         o["sum." + k] = np.float64(v.double().sum().item())
         o["abs." + k] = np.float64(v.double().abs().sum().item())
@@ -124,13 +162,15 @@ def case_fixture(A, name, seed, B, N, H, L, norm_diff, tanh, pos_scale, phi_scal
         for k, p in model.named_parameters():
             # the last layer's node_mlp does not reach the output x: torch leaves its .grad None, stored as zeros
             g = p.grad.detach() if p.grad is not None else torch.zeros_like(p)
-            if tag == "ref" or full:
+            if (tag == "ref" and not slim) or full:
                 o[f"{tag}.grad.{k}"] = g.numpy().copy()
-            if tag == "ref64":
-                o["ref64.gsum." + k] = np.float64(g.sum().item())
-                o["ref64.gabs." + k] = np.float64(g.abs().sum().item())
+            if tag == "ref64" or slim:
+                o[f"{tag}.gsum.{k}"] = np.float64(g.double().sum().item())
+                o[f"{tag}.gabs.{k}"] = np.float64(g.double().abs().sum().item())
+            if slim:
+                o[f"{tag}.gmax.{k}"] = np.float64(g.double().abs().max().item())
     if phi_scale != 1.0:           # the clamp must be active on some edges and inactive on others, in the first layer
-        m32 = build_model(A, seed, H, L, norm_diff, tanh, phi_scale)
+        m32 = build_model(A, seed, H, L, norm_diff, tanh, phi_scale, in_nf)
         raw = _first_layer_translation(m32, inp)
         n_clamped = int((raw.abs() > 100).sum())
         assert 0 < n_clamped < raw.numel(), n_clamped
