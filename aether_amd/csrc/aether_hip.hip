@@ -49,6 +49,7 @@
 #include "clof.h"
 
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -937,6 +938,7 @@ const char* aether_last_error(void) { return g_err; }
 #include "host_dyn_step.inc"
 #include "host_sim.inc"
 #include "host_train.inc"
+#include "host_gnn_common.inc"
 #include "host_egnn.inc"
 #include "host_clof.inc"
 

@@ -16,9 +16,11 @@
 // coord_mlp_vel, LayerNorm) are per-node vector loops, thread j = channel j.
 //
 // Weight gradients: fp32 MFMA with the rows (edges or nodes) as K, per job a 32 x 32 output tile per wave and a row chunk
-// per workgroup; chunk partials are summed in chunk order by a second launch.
+// per workgroup; chunk partials are summed in chunk order by a second launch (gnn_common.h).
 
 #pragma once
+
+#include "gnn_common.h"
 
 namespace clof {
 
@@ -30,11 +32,12 @@ constexpr int FMAX = 16;         // fuse_edge input width (ClofNet 10, ClofNet_v
 constexpr int NTYPES = 8;        // GaussianLayer edge_types (clof.py:196)
 constexpr int WG_CH_MAX = 64;    // row chunks of a weight-gradient reduction
 constexpr int PACK_MAX = 16;     // jobs of one k_clof_pack launch
-constexpr int WGJ_MAX = 24;      // jobs of one weight-gradient launch
 
-__device__ __forceinline__ float sig(float a) { return 1.0f / (1.0f + expf(-a)); }
-__device__ __forceinline__ float silu(float a) { return a * sig(a); }
-__device__ __forceinline__ float dsilu(float a) { const float s = sig(a); return s * (1.0f + a * (1.0f - s)); }
+using gnn::dsilu;
+using gnn::sig;
+using gnn::silu;
+using gnn::WgJob;
+using gnn::WgJobs;
 // torch.clamp(t, -100, 100): NaN passes through (fminf / fmaxf would drop it)
 __device__ __forceinline__ float clamp100(float t) { return t < -100.0f ? -100.0f : (t > 100.0f ? 100.0f : t); }
 __device__ __forceinline__ bool in100(float t) { return t >= -100.0f && t <= 100.0f; }   // clamp's gradient mask
@@ -824,16 +827,7 @@ __global__ __launch_bounds__(64) void kb_clof_prologue(ProW W, BProBufs B, int F
 }
 
 // ------------------------------------------------------------------ weight gradients
-// out[j][k] (row stride ldo) = sum_i G[i][j] act(A[i][k]); A null: a column of ones (bias); act: 1 = SiLU
-struct WgJob {
-    const float *G, *A;
-    float* out;
-    int ldg, lda, ldo, J, K, act;
-    int64_t rows;
-    int tile0, poff;
-};
-struct WgJobs { WgJob j[WGJ_MAX]; int n, n_tiles, n_out, n_ch; };
-
+// First stage of gnn_common.h's weight-gradient reduction:
 // one wave per (32 x 32 output tile, row chunk); rows are the MFMA's k
 __global__ __launch_bounds__(64) void k_clof_wgrad_part(WgJobs T, float* __restrict__ part) {
     const int t = blockIdx.x, ch = blockIdx.y;
@@ -877,18 +871,6 @@ __global__ __launch_bounds__(64) void k_clof_wgrad_part(WgJobs T, float* __restr
                 const int jj = j0 + 16 * u + 4 * kq + i, kk = k0 + 16 * w + n;
                 if (jj < J.J && kk < J.K) P[(int64_t)jj * J.K + kk] = acc[u][w][i];
             }
-}
-
-__global__ __launch_bounds__(256) void k_clof_wgrad_sum(WgJobs T, const float* __restrict__ part) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= T.n_out) return;
-    int q = 0;
-    while (q + 1 < T.n && T.j[q + 1].poff <= idx) ++q;
-    const WgJob& J = T.j[q];
-    const int o = idx - J.poff, jj = o / J.K, kk = o % J.K;
-    float s = 0.0f;
-    for (int c = 0; c < T.n_ch; ++c) s += part[(int64_t)c * T.n_out + idx];
-    J.out[(int64_t)jj * J.ldo + kk] = s;
 }
 
 }  // namespace clof

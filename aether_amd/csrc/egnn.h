@@ -16,6 +16,8 @@
 
 #pragma once
 
+#include "gnn_common.h"
+
 namespace egnn {
 
 constexpr int EB = 4;            // edges of one node processed side by side (each weight load feeds EB products)
@@ -23,9 +25,11 @@ constexpr int FIN = 22;          // field net input: x (3), vel (3), class embed
 constexpr int FH = 32;           // field net hidden width
 constexpr int WG_CH_MAX = 256;   // row chunks of a weight-gradient reduction (partials summed in chunk order)
 
-__device__ __forceinline__ float sig(float a) { return 1.0f / (1.0f + expf(-a)); }
-__device__ __forceinline__ float silu(float a) { return a * sig(a); }
-__device__ __forceinline__ float dsilu(float a) { const float s = sig(a); return s * (1.0f + a * (1.0f - s)); }
+using gnn::dsilu;
+using gnn::sig;
+using gnn::silu;
+using gnn::WgJob;
+using gnn::WgJobs;
 
 // one layer's parameters: transposed images (t suffix, [in][H]) for the forward products, torch layout for W^T g
 struct LayerW {
@@ -576,18 +580,8 @@ __global__ __launch_bounds__(64) void kb_egnn_field(FieldW fw, FieldBufs Fb, con
 }
 
 // ------------------------------------------------------------------ weight gradients
-// out[j * ldo + k] = sum_i G[i * ldg + j] * A[i * lda + k]  (A null: 1, a bias), i over `rows`, in two deterministic
-// stages: row chunk c of every 64 x 64 output tile -> part[c][...] (a 4 x 4 block per thread), then the chunks in order.
-struct WgJob {
-    const float *G, *A;
-    float* out;
-    int ldg, lda, ldo, J, K;
-    int64_t rows;
-    int tile0, poff;            // first tile of the job; offset of its J * K partials
-};
-constexpr int WG_MAX_JOBS = 20;
-struct WgJobs { WgJob j[WG_MAX_JOBS]; int n, n_tiles, n_out, n_ch; };
-
+// First stage of gnn_common.h's weight-gradient reduction: row chunk c of every 64 x 64 output tile -> part[c][...], a
+// 4 x 4 block per thread.  No job here has an activation (WgJob::act is 0 and is not read).
 __global__ __launch_bounds__(256) void k_egnn_wgrad_part(WgJobs T, float* __restrict__ part) {
     const int t = blockIdx.x, c = blockIdx.y;
     int q = 0;
@@ -617,18 +611,6 @@ __global__ __launch_bounds__(256) void k_egnn_wgrad_part(WgJobs T, float* __rest
 #pragma unroll
         for (int w = 0; w < 4; ++w)
             if (j0 + u < J.J && k0 + w < J.K) P[(j0 + u) * J.K + k0 + w] = acc[u][w];
-}
-
-__global__ __launch_bounds__(256) void k_egnn_wgrad_sum(WgJobs T, const float* __restrict__ part) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= T.n_out) return;
-    int q = 0;
-    while (q + 1 < T.n && T.j[q + 1].poff <= idx) ++q;
-    const WgJob& J = T.j[q];
-    const int o = idx - J.poff, jj = o / J.K, kk = o % J.K;
-    float s = 0.0f;
-    for (int c = 0; c < T.n_ch; ++c) s += part[(int64_t)c * T.n_out + idx];
-    J.out[jj * J.ldo + kk] = s;
 }
 
 }  // namespace egnn

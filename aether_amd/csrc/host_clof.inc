@@ -1,10 +1,11 @@
 // Host side of the C ABI: ClofNet (ClofNet / ClofNet_vel / ClofNet_vel_gbf, nn/state2state/clof/clof.py), forward and
 // parameter backward.  Included by aether_hip.hip inside its extern "C" block; not a stand-alone source file.
-// Kernels: csrc/clof.h.
+// Kernels: csrc/clof.h; shared plumbing: csrc/host_gnn_common.inc.
 
 extern "C++" {
 namespace {
 
+constexpr int CLOF_FLAGS = AETHER_CLOF_NORM_DIFF | AETHER_CLOF_TANH | AETHER_CLOF_KEEP | AETHER_CLOF_RECURRENT;
 constexpr int CLOF_PER_LAYER = 19;   // edge_mlp.{0,2,4} w b, node_mlp.{0,2} w b, coord_mlp.0 w b, coord_mlp.2 w,
                                      // coord_mlp_vel.{0,2} w b, layer_norm w b
 // head tensors before gcl_0: embedding_node w b, then ClofNet: embedding_edge.0 w b, fuse_edge.{0,2} w b;
@@ -34,20 +35,16 @@ int64_t clof_numel(int p, int variant, int H, int L, int in_nf) {
 }
 
 int64_t clof_grad_offset(int p, int variant, int H, int L, int in_nf) {
-    int64_t off = 0;
-    for (int q = 0; q < p; ++q) off += (clof_numel(q, variant, H, L, in_nf) + 3) / 4 * 4;
-    return off;
+    return gnn_grad_offset(p, [&](int q) { return clof_numel(q, variant, H, L, in_nf); });
 }
 
-struct ClofLayout {
+struct ClofLayout : FloatArena {
     size_t wimg, cen, hs, xs, P, ef, m, trans;
     size_t fin, af1, af2, a1, a2, a3, ac1, rad, av, an1, agg, xhat, rstd;
     size_t gx, gh, gtr, gav, gpsi, gu, gn1, glnw, gagg, ghp, ga1, ga2, ga3, gac1, gc, gef, gxr, gxc, srow, scol;
     size_t gaf1, gaf2, gmean, gstd, gmul, gbias, part, total;
     int64_t img_layer, n_slots, n_out, n_ch;
     ClofLayout(int variant, int H, int L, int in_nf, int64_t Nn, int64_t E, bool keep) {
-        size_t off = 0;
-        auto take = [&](size_t floats) { size_t o = off; off = align_up(off + floats * 4, 256); return o; };
         const size_t n = (size_t)Nn, e = (size_t)(E > 0 ? E : 1), h = (size_t)H, h2 = h / 2, l = (size_t)L;
         img_layer = (int64_t)(13 * h * h + h);
         n_slots = keep ? L + 1 : 2;
@@ -89,12 +86,11 @@ struct ClofLayout {
     }
 };
 
-struct ClofCall {
+struct ClofCall : GraphView {
     int variant, H, L, in_nf, n_per, recurrent;
     bool norm, tanh_;
     float cw;
     int64_t Nn, E;
-    const int32_t *perm, *row_s, *col_s, *rowptr, *sperm, *srowptr;
 };
 
 bool clof_sizes_ok(int variant, int H, int L, int in_nf) {
@@ -103,35 +99,17 @@ bool clof_sizes_ok(int variant, int H, int L, int in_nf) {
 
 int clof_check(const float* const* params, int n_params, int variant, int H, int L, int in_nf, int n_per, int64_t Nn,
                int64_t E, const void* graph, const AetherGraphInfo* info, const char* what) {
-    char msg[160];
-    auto bad = [&](const char* why) { snprintf(msg, sizeof(msg), "%s: %s", what, why); return fail(AETHER_EINVAL, msg); };
     if (!clof_sizes_ok(variant, H, L, in_nf))
-        return bad("variant must be 0..2, hidden 64 or 128, n_layers in [1, 64], in_node_nf in [1, 4096]");
-    if (!params || n_params != clof_n_params(variant, L)) return bad("parameter list does not match variant / n_layers");
-    for (int p = 0; p < n_params; ++p)
-        if (!params[p]) return bad("null parameter pointer");
-    if (Nn <= 0 || E < 0 || Nn >= ((int64_t)1 << 31) || E >= ((int64_t)1 << 31)) return bad("bad sizes");
-    if (n_per < 1 || Nn % n_per != 0) return bad("n_nodes must be a multiple of the nodes per graph");
-    if (!graph || !info || info->n_nodes != Nn || info->n_edges != E)
-        return bad("graph view missing or built for another (n_nodes, n_edges)");
-    return AETHER_OK;
+        return gnn_fail(AETHER_EINVAL, what,
+                        "variant must be 0..2, hidden 64 or 128, n_layers in [1, 64], in_node_nf in [1, 4096]");
+    return gnn_check(params, n_params, clof_n_params(variant, L), "parameter list does not match variant / n_layers", n_per,
+                     Nn, E, graph, info, what);
 }
 
 ClofCall clof_call(int variant, int H, int L, int in_nf, int flags, float cw, int n_per, int64_t Nn, int64_t E,
                    const void* graph) {
-    const GraphLayout G(E, Nn, false);
-    const char* g = (const char*)graph;
-    auto gp = [&](size_t off) { return reinterpret_cast<const int32_t*>(g + off); };
-    ClofCall c;
-    c.variant = variant; c.H = H; c.L = L; c.in_nf = in_nf; c.n_per = n_per;
-    c.norm = (flags & AETHER_CLOF_NORM_DIFF) != 0;
-    c.tanh_ = (flags & AETHER_CLOF_TANH) != 0;
-    c.recurrent = (flags & AETHER_CLOF_RECURRENT) != 0 ? 1 : 0;
-    c.cw = cw;
-    c.Nn = Nn; c.E = E;
-    c.perm = gp(G.perm); c.row_s = gp(G.recv_s); c.col_s = gp(G.send_s); c.rowptr = gp(G.rowptr);
-    c.sperm = gp(G.sperm); c.srowptr = gp(G.srowptr);
-    return c;
+    return ClofCall{GraphView(graph, Nn, E), variant, H, L, in_nf, n_per, (flags & AETHER_CLOF_RECURRENT) != 0 ? 1 : 0,
+                    (flags & AETHER_CLOF_NORM_DIFF) != 0, (flags & AETHER_CLOF_TANH) != 0, cw, Nn, E};
 }
 
 // layer l's packed images (offsets inside its image block) and tensors
@@ -191,29 +169,24 @@ int clof_forward_impl(const ClofCall& c, const float* const* params, const ClofL
     const int L = c.L, v = c.variant;
     const int64_t Nn = c.Nn, E = c.E;
     const size_t h = H;
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto hslot = [&](int s) { return wp(Lo.hs) + (size_t)s * Nn * h; };
-    auto xslot = [&](int s) { return wp(Lo.xs) + (size_t)s * Nn * 3; };
+    const WsFloats wp{ws, Nn, H, Lo.hs, Lo.xs, Lo.gh, Lo.gx};
     for (int l = 0; l < L; ++l) clof_pack_layer(params, v, l, Lo, ws, H, st);
     const unsigned nb = (unsigned)((Nn + clof::NB - 1) / clof::NB);
     clof::k_clof_prep<H><<<dim3(nb), dim3(H), 0, st>>>(clof_layer_w(params, v, 0, Lo, ws, H), params[0], params[1], c.in_nf,
-                                                        c.n_per, Nn, hin, x, xslot(0), wp(Lo.cen), hslot(0), wp(Lo.P));
+                                                        c.n_per, Nn, hin, x, wp.x(0), wp(Lo.cen), wp.h(0), wp(Lo.P));
     if (E > 0) {
         const clof::ProW pw = clof_pro_w(params, v);
         const dim3 eg((unsigned)((E + 63) / 64));
-#define CLOF_PRO(VAR, NORM)                                                                                                   \
-    (keep ? clof::k_clof_prologue<H, VAR, NORM, true><<<eg, dim3(64), 0, st>>>(pw, E, c.perm, c.row_s, c.col_s, xslot(0),     \
-                                                                              vel, ea, wp(Lo.ef), wp(Lo.fin), wp(Lo.af1),    \
-                                                                              wp(Lo.af2))                                   \
-          : clof::k_clof_prologue<H, VAR, NORM, false><<<eg, dim3(64), 0, st>>>(pw, E, c.perm, c.row_s, c.col_s, xslot(0),  \
-                                                                               vel, ea, wp(Lo.ef), nullptr, nullptr,       \
-                                                                               nullptr))
+        float *fin = keep ? wp(Lo.fin) : nullptr, *af1 = keep ? wp(Lo.af1) : nullptr, *af2 = keep ? wp(Lo.af2) : nullptr;
+        auto pro = [&](auto VAR, auto NORM, auto KEEP) {
+            clof::k_clof_prologue<H, decltype(VAR)::value, decltype(NORM)::value, decltype(KEEP)::value>
+                <<<eg, dim3(64), 0, st>>>(pw, E, c.perm, c.row_s, c.col_s, wp.x(0), vel, ea, wp(Lo.ef), fin, af1, af2);
+        };
         // ClofNet_vel / _gbf scalarize with norm_diff = True whatever the argument (clof.py:113,190); ClofNet uses it
-        if (v == 0 && c.norm) CLOF_PRO(0, true);
-        else if (v == 0) CLOF_PRO(0, false);
-        else if (v == 1) CLOF_PRO(1, true);
-        else CLOF_PRO(2, true);
-#undef CLOF_PRO
+        using std::integral_constant;
+        if (v == 0) dispatch_bools([&](auto NORM, auto KEEP) { pro(integral_constant<int, 0>{}, NORM, KEEP); }, c.norm, keep);
+        else if (v == 1) dispatch_bools([&](auto KEEP) { pro(integral_constant<int, 1>{}, std::true_type{}, KEEP); }, keep);
+        else dispatch_bools([&](auto KEEP) { pro(integral_constant<int, 2>{}, std::true_type{}, KEEP); }, keep);
     }
     const dim3 eb((unsigned)((E + clof::ET - 1) / clof::ET)), et(64 * clof::EW);
     for (int l = 0; l < L; ++l) {
@@ -222,67 +195,37 @@ int clof_forward_impl(const ClofCall& c, const float* const* params, const ClofL
         const clof::LayerW Wn = clof_layer_w(params, v, l + 1 < L ? l + 1 : l, Lo, ws, H);
         if (E > 0) {
             clof::EdgeBufs B;
-            B.x = xslot(si); B.P = wp(Lo.P); B.ef = wp(Lo.ef); B.m = wp(Lo.m); B.trans = wp(Lo.trans);
+            B.x = wp.x(si); B.P = wp(Lo.P); B.ef = wp(Lo.ef); B.m = wp(Lo.m); B.trans = wp(Lo.trans);
             const size_t eo = (size_t)l * E * h;
             B.a1 = keep ? wp(Lo.a1) + eo : nullptr; B.a2 = keep ? wp(Lo.a2) + eo : nullptr;
             B.a3 = keep ? wp(Lo.a3) + eo : nullptr; B.ac1 = keep ? wp(Lo.ac1) + eo : nullptr;
             B.rad = keep ? wp(Lo.rad) + (size_t)l * E : nullptr;
-#define CLOF_EDGE(NORM, TANH)                                                                                                 \
-    (keep ? clof::k_clof_edge<H, NORM, TANH, true><<<eb, et, 0, st>>>(W, B, E, c.row_s, c.col_s)                            \
-          : clof::k_clof_edge<H, NORM, TANH, false><<<eb, et, 0, st>>>(W, B, E, c.row_s, c.col_s))
-            if (c.norm && c.tanh_) CLOF_EDGE(true, true);
-            else if (c.norm) CLOF_EDGE(true, false);
-            else if (c.tanh_) CLOF_EDGE(false, true);
-            else CLOF_EDGE(false, false);
-#undef CLOF_EDGE
+            dispatch_bools([&](auto NORM, auto TANH, auto KEEP) {
+                clof::k_clof_edge<H, decltype(NORM)::value, decltype(TANH)::value, decltype(KEEP)::value>
+                    <<<eb, et, 0, st>>>(W, B, E, c.row_s, c.col_s);
+            }, c.norm, c.tanh_, keep);
         }
         clof::NodeBufs N;
-        N.h = hslot(si); N.x = xslot(si); N.vel = vel; N.m = wp(Lo.m); N.trans = wp(Lo.trans); N.cen = wp(Lo.cen);
-        N.h2 = hslot(so); N.x2 = xslot(so); N.out = out; N.P = wp(Lo.P);
+        N.h = wp.h(si); N.x = wp.x(si); N.vel = vel; N.m = wp(Lo.m); N.trans = wp(Lo.trans); N.cen = wp(Lo.cen);
+        N.h2 = wp.h(so); N.x2 = wp.x(so); N.out = out; N.P = wp(Lo.P);
         const size_t no = (size_t)l * Nn * h;
         N.av = keep ? wp(Lo.av) + no : nullptr; N.an1 = keep ? wp(Lo.an1) + no : nullptr;
         N.agg = keep ? wp(Lo.agg) + no : nullptr; N.xhat = keep ? wp(Lo.xhat) + no : nullptr;
         N.rstd = keep ? wp(Lo.rstd) + (size_t)l * Nn : nullptr;
         const bool last = l == L - 1;
-#define CLOF_NODE(LAST, KEEP) clof::k_clof_node<H, LAST, KEEP><<<dim3(nb), dim3(H), 0, st>>>(W, Wn, N, c.cw, c.recurrent, Nn, c.rowptr)
-        if (last && keep) CLOF_NODE(true, true);
-        else if (last) CLOF_NODE(true, false);
-        else if (keep) CLOF_NODE(false, true);
-        else CLOF_NODE(false, false);
-#undef CLOF_NODE
+        dispatch_bools([&](auto LAST, auto KEEP) {
+            clof::k_clof_node<H, decltype(LAST)::value, decltype(KEEP)::value><<<dim3(nb), dim3(H), 0, st>>>(
+                W, Wn, N, c.cw, c.recurrent, Nn, c.rowptr);
+        }, last, keep);
     }
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }
 
-int clof_wgrad(clof::WgJobs& T, const ClofLayout& Lo, char* ws, hipStream_t st) {
-    int tiles = 0, outs = 0;
-    for (int q = 0; q < T.n; ++q) {
-        clof::WgJob& J = T.j[q];
-        J.tile0 = tiles;
-        J.poff = outs;
-        tiles += ((J.J + 31) / 32) * ((J.K + 31) / 32);
-        outs += J.J * J.K;
-    }
-    if (outs > Lo.n_out) return fail(AETHER_EINVAL, "clof: weight-gradient partials exceed their region");
-    T.n_tiles = tiles;
-    T.n_out = outs;
-    T.n_ch = (int)Lo.n_ch;
-    float* part = reinterpret_cast<float*>(ws + Lo.part);
-    clof::k_clof_wgrad_part<<<dim3((unsigned)tiles, (unsigned)T.n_ch), dim3(64), 0, st>>>(T, part);
-    clof::k_clof_wgrad_sum<<<dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, st>>>(T, part);
-    return AETHER_OK;
+int clof_wgrad(gnn::WgJobs& T, const ClofLayout& Lo, char* ws, hipStream_t st) {
+    return gnn_wgrad(T, 32, 64, clof::k_clof_wgrad_part, reinterpret_cast<float*>(ws + Lo.part), Lo.n_out, Lo.n_ch,
+                     "clof: weight-gradient partials exceed their region", st);
 }
-
-struct ClofJobs {
-    clof::WgJobs T;
-    ClofJobs() { T.n = 0; }
-    void add(const float* G, int ldg, const float* A, int lda, int act, float* out, int ldo, int J, int K, int64_t rows) {
-        clof::WgJob& j = T.j[T.n++];
-        j.G = G; j.A = A; j.out = out; j.ldg = ldg; j.lda = lda; j.ldo = ldo; j.J = J; j.K = K; j.act = act; j.rows = rows;
-        j.tile0 = j.poff = 0;
-    }
-};
 
 template <int H>
 int clof_backward_impl(const ClofCall& c, const float* const* params, const ClofLayout& Lo, const float* hin,
@@ -290,12 +233,8 @@ int clof_backward_impl(const ClofCall& c, const float* const* params, const Clof
     const int L = c.L, v = c.variant, KIN = (int)clof_kin(H), H2 = H / 2;
     const int64_t Nn = c.Nn, E = c.E;
     const size_t h = H;
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    const WsFloats wp{ws, Nn, H, Lo.hs, Lo.xs, Lo.gh, Lo.gx};
     auto gdst = [&](int p) { return grad + clof_grad_offset(p, v, H, L, c.in_nf); };
-    auto hslot = [&](int s) { return wp(Lo.hs) + (size_t)s * Nn * h; };
-    auto xslot = [&](int s) { return wp(Lo.xs) + (size_t)s * Nn * 3; };
-    auto ghb = [&](int s) { return wp(Lo.gh) + (size_t)s * Nn * h; };
-    auto gxb = [&](int s) { return wp(Lo.gx) + (size_t)s * Nn * 3; };
     const unsigned nb = (unsigned)((Nn + clof::NB - 1) / clof::NB);
     const dim3 eb((unsigned)((E + clof::ET - 1) / clof::ET)), et(64 * clof::EW);
     const float* gx_out = grad_out;
@@ -305,36 +244,35 @@ int clof_backward_impl(const ClofCall& c, const float* const* params, const Clof
         const bool last = l == L - 1, first = l == 0;
         const clof::LayerW W = clof_layer_w(params, v, l, Lo, ws, H);
         const size_t eo = (size_t)l * E * h, no = (size_t)l * Nn * h;
-        const float* hl = hslot(l);
+        const float* hl = wp.h(l);
         clof::BNodeBufs BN;
         BN.gx = gx_out; BN.gh = gh_out; BN.h = hl; BN.vel = vel; BN.av = wp(Lo.av) + no; BN.an1 = wp(Lo.an1) + no;
         BN.xhat = wp(Lo.xhat) + no; BN.rstd = wp(Lo.rstd) + (size_t)l * Nn;
         BN.gtr = wp(Lo.gtr); BN.gav = wp(Lo.gav); BN.gpsi = wp(Lo.gpsi); BN.gu = wp(Lo.gu); BN.gn1 = wp(Lo.gn1);
         BN.glnw = wp(Lo.glnw); BN.gagg = wp(Lo.gagg); BN.ghp = wp(Lo.ghp);
-        if (last) clof::kb_clof_node<H, true><<<dim3(nb), dim3(H), 0, st>>>(W, BN, c.cw, c.recurrent, Nn, c.rowptr);
-        else clof::kb_clof_node<H, false><<<dim3(nb), dim3(H), 0, st>>>(W, BN, c.cw, c.recurrent, Nn, c.rowptr);
+        dispatch_bools([&](auto LAST) {
+            clof::kb_clof_node<H, decltype(LAST)::value><<<dim3(nb), dim3(H), 0, st>>>(W, BN, c.cw, c.recurrent, Nn, c.rowptr);
+        }, last);
         if (E > 0) {
             clof::BEdgeBufs BE;
-            BE.x = xslot(l); BE.a1 = wp(Lo.a1) + eo; BE.a2 = wp(Lo.a2) + eo; BE.a3 = wp(Lo.a3) + eo; BE.ac1 = wp(Lo.ac1) + eo;
+            BE.x = wp.x(l); BE.a1 = wp(Lo.a1) + eo; BE.a2 = wp(Lo.a2) + eo; BE.a3 = wp(Lo.a3) + eo; BE.ac1 = wp(Lo.ac1) + eo;
             BE.gtr = wp(Lo.gtr); BE.gagg = wp(Lo.gagg);
             BE.ga1 = wp(Lo.ga1); BE.ga2 = wp(Lo.ga2); BE.ga3 = wp(Lo.ga3); BE.gac1 = wp(Lo.gac1); BE.gc = wp(Lo.gc);
             BE.gef = wp(Lo.gef); BE.gxr = wp(Lo.gxr); BE.gxc = wp(Lo.gxc);
             const int top = last ? 1 : 0, fst = first ? 1 : 0;
-#define CLOF_BEDGE(NORM, TANH) clof::kb_clof_edge<H, NORM, TANH><<<eb, et, 0, st>>>(W, BE, E, c.row_s, c.col_s, top, fst)
-            if (c.norm && c.tanh_) CLOF_BEDGE(true, true);
-            else if (c.norm) CLOF_BEDGE(true, false);
-            else if (c.tanh_) CLOF_BEDGE(false, true);
-            else CLOF_BEDGE(false, false);
-#undef CLOF_BEDGE
+            dispatch_bools([&](auto NORM, auto TANH) {
+                clof::kb_clof_edge<H, decltype(NORM)::value, decltype(TANH)::value><<<eb, et, 0, st>>>(
+                    W, BE, E, c.row_s, c.col_s, top, fst);
+            }, c.norm, c.tanh_);
         }
         clof::BGatherBufs BG;
         BG.ga1 = wp(Lo.ga1); BG.ghp = wp(Lo.ghp); BG.gx = gx_out; BG.gxr = wp(Lo.gxr); BG.gxc = wp(Lo.gxc);
-        BG.srow = wp(Lo.srow); BG.scol = wp(Lo.scol); BG.gh = ghb(s); BG.gxo = gxb(s);
+        BG.srow = wp(Lo.srow); BG.scol = wp(Lo.scol); BG.gh = wp.gh(s); BG.gxo = wp.gx(s);
         clof::kb_clof_gather<H><<<dim3(nb), dim3(H), 0, st>>>(W, BG, KIN, Nn, c.rowptr, c.sperm, c.srowptr,
                                                               first ? 1 : 0);
         // weight gradients of layer l (parameters p0 ...); the last layer's node_mlp and layer_norm are dead
         const int p0 = clof_head(v) + CLOF_PER_LAYER * l, SILU = 1;
-        ClofJobs J;
+        WgTable J;
         J.add(wp(Lo.srow), H, hl, H, 0, gdst(p0), KIN, H, H, Nn);                           // edge_mlp.0: h_row, h_col
         J.add(wp(Lo.scol), H, hl, H, 0, gdst(p0) + H, KIN, H, H, Nn);
         J.add(wp(Lo.ga1), H, wp(Lo.rad) + (size_t)l * E, 1, 0, gdst(p0) + 2 * H, KIN, H, 1, E);   // radial
@@ -363,8 +301,8 @@ int clof_backward_impl(const ClofCall& c, const float* const* params, const Clof
             J.add(gh_out, H, nullptr, 0, 0, gdst(p0 + 18), 1, H, 1, Nn);
         }
         if (int rc = clof_wgrad(J.T, Lo, ws, st)) return rc;
-        gx_out = gxb(s);
-        gh_out = ghb(s);
+        gx_out = wp.gx(s);
+        gh_out = wp.gh(s);
     }
     // the prologue: edge_feat's gradient (summed over the layers) through fuse_edge and the Gaussian layer
     const int F = clof_fuse_in(v), f0 = clof_fuse0(v), SILU = 1;
@@ -378,7 +316,7 @@ int clof_backward_impl(const ClofCall& c, const float* const* params, const Clof
         if (v == 2) clof::kb_clof_prologue<H, 2><<<eg, dim3(64), 0, st>>>(pw, BP, F, E, c.perm);
         else clof::kb_clof_prologue<H, 0><<<eg, dim3(64), 0, st>>>(pw, BP, F, E, c.perm);
     }
-    ClofJobs J;
+    WgTable J;
     J.add(gh_out, H, hin, c.in_nf, 0, gdst(0), c.in_nf, H, c.in_nf, Nn);                   // embedding_node
     J.add(gh_out, H, nullptr, 0, 0, gdst(1), 1, H, 1, Nn);
     const int64_t re = E > 0 ? E : 0;
@@ -417,10 +355,7 @@ int64_t aether_clof_workspace_offset(const char* name, int layer, int variant, i
         return fail(AETHER_EINVAL, "clof_workspace_offset: bad arguments");
     const ClofLayout Lo(variant, hidden, n_layers, in_node_nf, n_nodes, n_edges, true);
     if (!strcmp(name, "edge_feat")) return (int64_t)Lo.ef;
-    if (layer < 0 || layer > n_layers) return fail(AETHER_EINVAL, "clof_workspace_offset: layer outside [0, n_layers]");
-    if (!strcmp(name, "h")) return (int64_t)(Lo.hs + (size_t)layer * n_nodes * hidden * 4);
-    if (!strcmp(name, "x")) return (int64_t)(Lo.xs + (size_t)layer * n_nodes * 3 * 4);
-    return fail(AETHER_EINVAL, "clof_workspace_offset: unknown name (edge_feat, h, x)");
+    return gnn_slot_offset("clof_workspace_offset", "edge_feat, h, x", name, layer, n_layers, Lo.hs, Lo.xs, n_nodes, hidden);
 }
 
 int aether_clof_forward(const float* const* params, int n_params, int variant, int hidden, int n_layers, int in_node_nf,
@@ -430,13 +365,11 @@ int aether_clof_forward(const float* const* params, int n_params, int variant, i
     if (int rc = clof_check(params, n_params, variant, hidden, n_layers, in_node_nf, n_per_graph, n_nodes, n_edges, graph,
                             info, "clof_forward"))
         return rc;
-    if (!h || !x || !vel || !workspace || !out || (n_edges > 0 && !edge_attr))
-        return fail(AETHER_EINVAL, "clof_forward: null pointer");
-    if (flags & ~(AETHER_CLOF_NORM_DIFF | AETHER_CLOF_TANH | AETHER_CLOF_KEEP | AETHER_CLOF_RECURRENT))
-        return fail(AETHER_EINVAL, "clof_forward: unknown flag");
     const bool keep = (flags & AETHER_CLOF_KEEP) != 0;
     const ClofLayout Lo(variant, hidden, n_layers, in_node_nf, n_nodes, n_edges, keep);
-    if (workspace_bytes < Lo.total) return fail(AETHER_ESPACE, "clof_forward: workspace too small");
+    if (int rc = gnn_entry_check("clof_forward", !h || !x || !vel || !workspace || !out || (n_edges > 0 && !edge_attr),
+                                 flags & ~CLOF_FLAGS, workspace_bytes, Lo.total))
+        return rc;
     const ClofCall c = clof_call(variant, hidden, n_layers, in_node_nf, flags, coords_weight, n_per_graph, n_nodes, n_edges,
                                  graph);
     hipStream_t st = (hipStream_t)stream;
@@ -452,14 +385,12 @@ int aether_clof_backward(const float* const* params, int n_params, int variant, 
     if (int rc = clof_check(params, n_params, variant, hidden, n_layers, in_node_nf, n_per_graph, n_nodes, n_edges, graph,
                             info, "clof_backward"))
         return rc;
-    if (!h || !x || !vel || !workspace || !grad_out || !grad || (n_edges > 0 && !edge_attr))
-        return fail(AETHER_EINVAL, "clof_backward: null pointer");
-    if (flags & ~(AETHER_CLOF_NORM_DIFF | AETHER_CLOF_TANH | AETHER_CLOF_KEEP | AETHER_CLOF_RECURRENT))
-        return fail(AETHER_EINVAL, "clof_backward: unknown flag");
-    if (grad_floats < clof_grad_offset(clof_n_params(variant, n_layers), variant, hidden, n_layers, in_node_nf))
-        return fail(AETHER_ESPACE, "clof_backward: gradient buffer too small");
     const ClofLayout Lo(variant, hidden, n_layers, in_node_nf, n_nodes, n_edges, true);
-    if (workspace_bytes < Lo.total) return fail(AETHER_ESPACE, "clof_backward: workspace too small (keep-for-backward size)");
+    if (int rc = gnn_entry_check("clof_backward",
+                                 !h || !x || !vel || !workspace || !grad_out || !grad || (n_edges > 0 && !edge_attr),
+                                 flags & ~CLOF_FLAGS, workspace_bytes, Lo.total, grad_floats,
+                                 clof_grad_offset(clof_n_params(variant, n_layers), variant, hidden, n_layers, in_node_nf)))
+        return rc;
     const ClofCall c = clof_call(variant, hidden, n_layers, in_node_nf, flags, coords_weight, n_per_graph, n_nodes, n_edges,
                                  graph);
     hipStream_t st = (hipStream_t)stream;

@@ -1,15 +1,18 @@
 // Host side of the C ABI: EGNN-Aether (EGNN_vel_Aether, nn/state2state/egnn_aether.py), forward and parameter backward.
-// Included by aether_hip.hip inside its extern "C" block; not a stand-alone source file.  Kernels: csrc/egnn.h.
+// Included by aether_hip.hip inside its extern "C" block; not a stand-alone source file.  Kernels: csrc/egnn.h; shared
+// plumbing: csrc/host_gnn_common.inc.
 
 extern "C++" {
 namespace {
 
 // Parameter tensors in the reference's named_parameters() order (= state_dict order)
+constexpr int EGNN_FLAGS = AETHER_EGNN_NORM_DIFF | AETHER_EGNN_TANH | AETHER_EGNN_KEEP;
 constexpr int EGNN_PER_LAYER = 15;        // edge_mlp.0 w b, .2 w b, node_mlp.0 w b, .2 w b, coord_mlp.0 w b, .2 w,
                                           // coord_mlp_vel.0 w b, .2 w b
 constexpr int EGNN_FIELD = 7;             // field_net.net.0 w b, .2 w b, .4 w b, class_embedding
 
 int egnn_n_params(int L) { return 2 + EGNN_PER_LAYER * L + EGNN_FIELD; }
+bool egnn_sizes_ok(int H, int L, int in_nf) { return (H == 64 || H == 128) && L >= 1 && L <= 64 && in_nf >= 1; }
 
 // numel of parameter p (named_parameters order)
 int64_t egnn_numel(int p, int H, int L, int in_nf) {
@@ -25,23 +28,17 @@ int64_t egnn_numel(int p, int H, int L, int in_nf) {
     return fs[p - 2 - EGNN_PER_LAYER * L];
 }
 
-// float offset of parameter p in the flat gradient buffer: every tensor padded to 4 floats (16 bytes), in order --
-// the layout of the drop-in's _grad_buffers
 int64_t egnn_grad_offset(int p, int H, int L, int in_nf) {
-    int64_t off = 0;
-    for (int q = 0; q < p; ++q) off += (egnn_numel(q, H, L, in_nf) + 3) / 4 * 4;
-    return off;
+    return gnn_grad_offset(p, [&](int q) { return egnn_numel(q, H, L, in_nf); });
 }
 
-struct EgnnLayout {
+struct EgnnLayout : FloatArena {
     size_t wt, F, hs, xs, agg, total_fwd;
     size_t gh, gx, gf, ghn, gagg, zn, gn1, zp, gp1, gpsi, gxm, gfn, ghe, gxe, gfe;
     size_t in, z1, m, z3, ga1, ga2, gc1, gphi, ghc, gd, gfc;
     size_t fin, fz1, fz2, fga1, fga2, onehot, gemb, part, total;
     int64_t wt_layer, n_slots, n_out, n_ch;
     EgnnLayout(int H, int L, int in_nf, int64_t Nn, int64_t E, bool keep) {
-        size_t off = 0;
-        auto take = [&](size_t floats) { size_t o = off; off = align_up(off + floats * 4, 256); return o; };
         const size_t n = (size_t)Nn, e = (size_t)(E > 0 ? E : 1), h = (size_t)H, KIN = 2 * h + 9;
         wt_layer = (int64_t)(h * (8 * h + 12));
         n_slots = keep ? L + 1 : 2;
@@ -80,41 +77,24 @@ struct EgnnLayout {
     }
 };
 
-struct EgnnCall {
+struct EgnnCall : GraphView {
     int H, L, in_nf;
     bool norm, tanh_;
     int64_t Nn, E;
-    const int32_t *perm, *col_s, *rowptr, *sperm, *srowptr;
 };
 
 int egnn_check(const float* const* params, int n_params, int H, int L, int in_nf, int64_t Nn, int64_t E,
                const void* graph, const AetherGraphInfo* info, const char* what) {
-    char msg[160];
-    auto bad = [&](const char* why) { snprintf(msg, sizeof(msg), "%s: %s", what, why); return fail(AETHER_EINVAL, msg); };
-    if (H != 64 && H != 128) return bad("hidden must be 64 or 128");
-    if (L < 1 || L > 64) return bad("n_layers must lie in [1, 64]");
-    if (in_nf < 1 || in_nf > 4096) return bad("in_node_nf must lie in [1, 4096]");
-    if (!params || n_params != egnn_n_params(L)) return bad("parameter list does not match n_layers");
-    for (int p = 0; p < n_params; ++p)
-        if (!params[p]) return bad("null parameter pointer");
-    if (Nn <= 0 || E < 0 || Nn >= ((int64_t)1 << 31) || E >= ((int64_t)1 << 31)) return bad("bad sizes");
-    if (!graph || !info || info->n_nodes != Nn || info->n_edges != E)
-        return bad("graph view missing or built for another (n_nodes, n_edges)");
-    return AETHER_OK;
+    if (H != 64 && H != 128) return gnn_fail(AETHER_EINVAL, what, "hidden must be 64 or 128");
+    if (L < 1 || L > 64) return gnn_fail(AETHER_EINVAL, what, "n_layers must lie in [1, 64]");
+    if (in_nf < 1 || in_nf > 4096) return gnn_fail(AETHER_EINVAL, what, "in_node_nf must lie in [1, 4096]");
+    return gnn_check(params, n_params, egnn_n_params(L), "parameter list does not match n_layers", 1, Nn, E, graph, info,
+                     what);
 }
 
 EgnnCall egnn_call(int H, int L, int in_nf, int flags, int64_t Nn, int64_t E, const void* graph) {
-    const GraphLayout G(E, Nn, false);
-    const char* g = (const char*)graph;
-    auto gp = [&](size_t off) { return reinterpret_cast<const int32_t*>(g + off); };
-    EgnnCall c;
-    c.H = H; c.L = L; c.in_nf = in_nf;
-    c.norm = (flags & AETHER_EGNN_NORM_DIFF) != 0;
-    c.tanh_ = (flags & AETHER_EGNN_TANH) != 0;
-    c.Nn = Nn; c.E = E;
-    c.perm = gp(G.perm); c.col_s = gp(G.send_s); c.rowptr = gp(G.rowptr);
-    c.sperm = gp(G.sperm); c.srowptr = gp(G.srowptr);
-    return c;
+    return EgnnCall{GraphView(graph, Nn, E), H, L, in_nf, (flags & AETHER_EGNN_NORM_DIFF) != 0,
+                    (flags & AETHER_EGNN_TANH) != 0, Nn, E};
 }
 
 egnn::LayerW egnn_layer_w(const float* const* params, int l, const EgnnLayout& Lo, char* ws, int H) {
@@ -144,10 +124,8 @@ int egnn_forward_impl(const EgnnCall& c, const float* const* params, const EgnnL
     const int L = c.L;
     const int64_t Nn = c.Nn;
     const size_t h = H;
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    const WsFloats wp{ws, Nn, H, Lo.hs, Lo.xs, Lo.gh, Lo.gx};
     float* F = wp(Lo.F);
-    auto hslot = [&](int s) { return wp(Lo.hs) + (size_t)s * Nn * h; };
-    auto xslot = [&](int s) { return wp(Lo.xs) + (size_t)s * Nn * 3; };
     // transposed weight images, one launch per layer
     for (int l = 0; l < L; ++l) {
         const egnn::LayerW W = egnn_layer_w(params, l, Lo, ws, H);
@@ -160,51 +138,25 @@ int egnn_forward_impl(const EgnnCall& c, const float* const* params, const EgnnL
         egnn::k_egnn_wt<H><<<dim3((unsigned)(((2 * H + 9) * H + 255) / 256), 6), dim3(256), 0, st>>>(J);
     }
     egnn::k_egnn_prep<H><<<dim3((unsigned)Nn), dim3(H), 0, st>>>(egnn_field_w(params, L), params[0], params[1], c.in_nf, hin,
-                                                                 x, vel, charges, F, hslot(0));
-    HIP_OK(hipMemcpyAsync(xslot(0), x, (size_t)Nn * 3 * 4, hipMemcpyDeviceToDevice, st));
+                                                                 x, vel, charges, F, wp.h(0));
+    HIP_OK(hipMemcpyAsync(wp.x(0), x, (size_t)Nn * 3 * 4, hipMemcpyDeviceToDevice, st));
     for (int l = 0; l < L; ++l) {
         const int si = keep ? l : l % 2, so = keep ? l + 1 : (l + 1) % 2;
         const egnn::LayerW W = egnn_layer_w(params, l, Lo, ws, H);
         float* agg = keep ? wp(Lo.agg) + (size_t)l * Nn * h : nullptr;
         float* x2 = l == L - 1 ? out : nullptr;
-#define EGNN_LAYER(NORM, TANH)                                                                                               \
-    egnn::k_egnn_layer<H, NORM, TANH><<<dim3((unsigned)Nn), dim3(H), 0, st>>>(W, hslot(si), xslot(si), vel, F, ea, c.perm,  \
-                                                                             c.col_s, c.rowptr, hslot(so), xslot(so), x2,  \
-                                                                             agg)
-        if (c.norm && c.tanh_) EGNN_LAYER(true, true);
-        else if (c.norm) EGNN_LAYER(true, false);
-        else if (c.tanh_) EGNN_LAYER(false, true);
-        else EGNN_LAYER(false, false);
-#undef EGNN_LAYER
+        dispatch_bools([&](auto NORM, auto TANH) {
+            egnn::k_egnn_layer<H, decltype(NORM)::value, decltype(TANH)::value><<<dim3((unsigned)Nn), dim3(H), 0, st>>>(
+                W, wp.h(si), wp.x(si), vel, F, ea, c.perm, c.col_s, c.rowptr, wp.h(so), wp.x(so), x2, agg);
+        }, c.norm, c.tanh_);
     }
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }
 
-int egnn_wgrad(egnn::WgJobs& T, const EgnnLayout& Lo, char* ws, hipStream_t st) {
-    int tiles = 0, outs = 0;
-    for (int q = 0; q < T.n; ++q) {
-        egnn::WgJob& J = T.j[q];
-        J.tile0 = tiles;
-        J.poff = outs;
-        tiles += ((J.J + 63) / 64) * ((J.K + 63) / 64);
-        outs += J.J * J.K;
-    }
-    if (outs > Lo.n_out) return fail(AETHER_EINVAL, "egnn: weight-gradient partials exceed their region");
-    T.n_tiles = tiles;
-    T.n_out = outs;
-    T.n_ch = (int)Lo.n_ch;
-    float* part = reinterpret_cast<float*>(ws + Lo.part);
-    egnn::k_egnn_wgrad_part<<<dim3((unsigned)tiles, (unsigned)T.n_ch), dim3(256), 0, st>>>(T, part);
-    egnn::k_egnn_wgrad_sum<<<dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, st>>>(T, part);
-    return AETHER_OK;
-}
-
-egnn::WgJob wg(const float* G, int ldg, const float* A, int lda, float* out, int ldo, int J, int K, int64_t rows) {
-    egnn::WgJob j;
-    j.G = G; j.A = A; j.out = out; j.ldg = ldg; j.lda = lda; j.ldo = ldo; j.J = J; j.K = K; j.rows = rows;
-    j.tile0 = j.poff = 0;
-    return j;
+int egnn_wgrad(gnn::WgJobs& T, const EgnnLayout& Lo, char* ws, hipStream_t st) {
+    return gnn_wgrad(T, 64, 256, egnn::k_egnn_wgrad_part, reinterpret_cast<float*>(ws + Lo.part), Lo.n_out, Lo.n_ch,
+                     "egnn: weight-gradient partials exceed their region", st);
 }
 
 template <int H>
@@ -214,83 +166,75 @@ int egnn_backward_impl(const EgnnCall& c, const float* const* params, const Egnn
     const int L = c.L, KIN = 2 * H + 9;
     const int64_t Nn = c.Nn, E = c.E;
     const size_t h = H;
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    const WsFloats wp{ws, Nn, H, Lo.hs, Lo.xs, Lo.gh, Lo.gx};
     auto gdst = [&](int p) { return grad + egnn_grad_offset(p, H, L, c.in_nf); };
     float* F = wp(Lo.F);
-    auto hslot = [&](int s) { return wp(Lo.hs) + (size_t)s * Nn * h; };
-    auto xslot = [&](int s) { return wp(Lo.xs) + (size_t)s * Nn * 3; };
     egnn::BwdBufs B;
     B.gf = wp(Lo.gf);
     B.ghn = wp(Lo.ghn); B.gagg = wp(Lo.gagg); B.zn = wp(Lo.zn); B.gn1 = wp(Lo.gn1); B.zp = wp(Lo.zp); B.gp1 = wp(Lo.gp1);
     B.gpsi = wp(Lo.gpsi); B.gxm = wp(Lo.gxm); B.gfn = wp(Lo.gfn); B.ghe = wp(Lo.ghe); B.gxe = wp(Lo.gxe); B.gfe = wp(Lo.gfe);
     B.in = wp(Lo.in); B.z1 = wp(Lo.z1); B.m = wp(Lo.m); B.z3 = wp(Lo.z3); B.ga1 = wp(Lo.ga1); B.ga2 = wp(Lo.ga2);
     B.gc1 = wp(Lo.gc1); B.gphi = wp(Lo.gphi); B.ghc = wp(Lo.ghc); B.gd = wp(Lo.gd); B.gfc = wp(Lo.gfc);
-    auto ghb = [&](int s) { return wp(Lo.gh) + (size_t)s * Nn * h; };
-    auto gxb = [&](int s) { return wp(Lo.gx) + (size_t)s * Nn * 3; };
     HIP_OK(hipMemsetAsync(B.gf, 0, (size_t)Nn * 3 * 4, st));
-    HIP_OK(hipMemsetAsync(ghb(0), 0, (size_t)Nn * h * 4, st));                 // the output x does not depend on h_L
+    HIP_OK(hipMemsetAsync(wp.gh(0), 0, (size_t)Nn * h * 4, st));                 // the output x does not depend on h_L
     const dim3 nb((unsigned)Nn), tb(H);
     const float* gx_out = grad_out;
     for (int l = L - 1; l >= 0; --l) {
         const int cur = (L - 1 - l) % 2, nxt = 1 - cur;
-        const float* gh_out = ghb(cur);
-        B.gh_in = ghb(nxt);
-        B.gx_in = gxb(nxt);
+        const float* gh_out = wp.gh(cur);
+        B.gh_in = wp.gh(nxt);
+        B.gx_in = wp.gx(nxt);
         const egnn::LayerW W = egnn_layer_w(params, l, Lo, ws, H);
-        const float* hl = hslot(l);
-        const float* xl = xslot(l);
+        const float* hl = wp.h(l);
+        const float* xl = wp.x(l);
         const float* aggl = wp(Lo.agg) + (size_t)l * Nn * h;
         egnn::kb_egnn_node<H><<<nb, tb, 0, st>>>(W, B, hl, aggl, vel, F, c.rowptr, gh_out, gx_out);
-#define EGNN_BEDGE(NORM, TANH) egnn::kb_egnn_edge<H, NORM, TANH><<<nb, tb, 0, st>>>(W, B, hl, xl, F, ea, c.perm, c.col_s, c.rowptr)
-        if (c.norm && c.tanh_) EGNN_BEDGE(true, true);
-        else if (c.norm) EGNN_BEDGE(true, false);
-        else if (c.tanh_) EGNN_BEDGE(false, true);
-        else EGNN_BEDGE(false, false);
-#undef EGNN_BEDGE
+        dispatch_bools([&](auto NORM, auto TANH) {
+            egnn::kb_egnn_edge<H, decltype(NORM)::value, decltype(TANH)::value><<<nb, tb, 0, st>>>(
+                W, B, hl, xl, F, ea, c.perm, c.col_s, c.rowptr);
+        }, c.norm, c.tanh_);
         egnn::kb_egnn_gather<H><<<nb, tb, 0, st>>>(B, gx_out, c.sperm, c.srowptr);
         // weight gradients of the layer (parameters 2 + 15 l ...)
         const int p0 = 2 + EGNN_PER_LAYER * l;
-        egnn::WgJobs T;
-        T.n = 0;
-        T.j[T.n++] = wg(B.ga1, H, B.in, KIN, gdst(p0 + 0), KIN, H, KIN, E);            // edge_mlp.0
-        T.j[T.n++] = wg(B.ga1, H, nullptr, 0, gdst(p0 + 1), 1, H, 1, E);
-        T.j[T.n++] = wg(B.ga2, H, B.z1, H, gdst(p0 + 2), H, H, H, E);                  // edge_mlp.2
-        T.j[T.n++] = wg(B.ga2, H, nullptr, 0, gdst(p0 + 3), 1, H, 1, E);
-        T.j[T.n++] = wg(B.gn1, H, hl, H, gdst(p0 + 4), 2 * H, H, H, Nn);               // node_mlp.0: [h | agg]
-        T.j[T.n++] = wg(B.gn1, H, aggl, H, gdst(p0 + 4) + H, 2 * H, H, H, Nn);
-        T.j[T.n++] = wg(B.gn1, H, nullptr, 0, gdst(p0 + 5), 1, H, 1, Nn);
-        T.j[T.n++] = wg(gh_out, H, B.zn, H, gdst(p0 + 6), H, H, H, Nn);                // node_mlp.2
-        T.j[T.n++] = wg(gh_out, H, nullptr, 0, gdst(p0 + 7), 1, H, 1, Nn);
-        T.j[T.n++] = wg(B.gc1, H, B.m, H, gdst(p0 + 8), H, H, H, E);                   // coord_mlp.0
-        T.j[T.n++] = wg(B.gc1, H, nullptr, 0, gdst(p0 + 9), 1, H, 1, E);
-        T.j[T.n++] = wg(B.gphi, 1, B.z3, H, gdst(p0 + 10), H, 1, H, E);                // coord_mlp.2 (no bias)
-        T.j[T.n++] = wg(B.gp1, H, hl, H, gdst(p0 + 11), H + 3, H, H, Nn);              // coord_mlp_vel.0: [h | f]
-        T.j[T.n++] = wg(B.gp1, H, F, 3, gdst(p0 + 11) + H, H + 3, H, 3, Nn);
-        T.j[T.n++] = wg(B.gp1, H, nullptr, 0, gdst(p0 + 12), 1, H, 1, Nn);
-        T.j[T.n++] = wg(B.gpsi, 1, B.zp, H, gdst(p0 + 13), H, 1, H, Nn);               // coord_mlp_vel.2
-        T.j[T.n++] = wg(B.gpsi, 1, nullptr, 0, gdst(p0 + 14), 1, 1, 1, Nn);
-        if (int rc = egnn_wgrad(T, Lo, ws, st)) return rc;
+        WgTable J;
+        J.add(B.ga1, H, B.in, KIN, 0, gdst(p0 + 0), KIN, H, KIN, E);            // edge_mlp.0
+        J.add(B.ga1, H, nullptr, 0, 0, gdst(p0 + 1), 1, H, 1, E);
+        J.add(B.ga2, H, B.z1, H, 0, gdst(p0 + 2), H, H, H, E);                  // edge_mlp.2
+        J.add(B.ga2, H, nullptr, 0, 0, gdst(p0 + 3), 1, H, 1, E);
+        J.add(B.gn1, H, hl, H, 0, gdst(p0 + 4), 2 * H, H, H, Nn);               // node_mlp.0: [h | agg]
+        J.add(B.gn1, H, aggl, H, 0, gdst(p0 + 4) + H, 2 * H, H, H, Nn);
+        J.add(B.gn1, H, nullptr, 0, 0, gdst(p0 + 5), 1, H, 1, Nn);
+        J.add(gh_out, H, B.zn, H, 0, gdst(p0 + 6), H, H, H, Nn);                // node_mlp.2
+        J.add(gh_out, H, nullptr, 0, 0, gdst(p0 + 7), 1, H, 1, Nn);
+        J.add(B.gc1, H, B.m, H, 0, gdst(p0 + 8), H, H, H, E);                   // coord_mlp.0
+        J.add(B.gc1, H, nullptr, 0, 0, gdst(p0 + 9), 1, H, 1, E);
+        J.add(B.gphi, 1, B.z3, H, 0, gdst(p0 + 10), H, 1, H, E);                // coord_mlp.2 (no bias)
+        J.add(B.gp1, H, hl, H, 0, gdst(p0 + 11), H + 3, H, H, Nn);              // coord_mlp_vel.0: [h | f]
+        J.add(B.gp1, H, F, 3, 0, gdst(p0 + 11) + H, H + 3, H, 3, Nn);
+        J.add(B.gp1, H, nullptr, 0, 0, gdst(p0 + 12), 1, H, 1, Nn);
+        J.add(B.gpsi, 1, B.zp, H, 0, gdst(p0 + 13), H, 1, H, Nn);               // coord_mlp_vel.2
+        J.add(B.gpsi, 1, nullptr, 0, 0, gdst(p0 + 14), 1, 1, 1, Nn);
+        if (int rc = egnn_wgrad(J.T, Lo, ws, st)) return rc;
         gx_out = B.gx_in;
     }
     // field net (d/dF summed over the layers) and embedding (d/dh_0)
-    const float* gh0 = ghb(L % 2);
+    const float* gh0 = wp.gh(L % 2);
     egnn::FieldBufs Fb;
     Fb.fin = wp(Lo.fin); Fb.z1 = wp(Lo.fz1); Fb.z2 = wp(Lo.fz2); Fb.ga1 = wp(Lo.fga1); Fb.ga2 = wp(Lo.fga2);
     Fb.onehot = wp(Lo.onehot); Fb.gemb = wp(Lo.gemb);
     egnn::kb_egnn_field<<<nb, dim3(64), 0, st>>>(egnn_field_w(params, L), Fb, x, vel, charges, B.gf);
     const int f0 = 2 + EGNN_PER_LAYER * L, FH = egnn::FH, FIN = egnn::FIN;
-    egnn::WgJobs T;
-    T.n = 0;
-    T.j[T.n++] = wg(gh0, H, hin, c.in_nf, gdst(0), c.in_nf, H, c.in_nf, Nn);          // embedding
-    T.j[T.n++] = wg(gh0, H, nullptr, 0, gdst(1), 1, H, 1, Nn);
-    T.j[T.n++] = wg(Fb.ga1, FH, Fb.fin, FIN, gdst(f0 + 0), FIN, FH, FIN, Nn);          // field_net.net.0
-    T.j[T.n++] = wg(Fb.ga1, FH, nullptr, 0, gdst(f0 + 1), 1, FH, 1, Nn);
-    T.j[T.n++] = wg(Fb.ga2, FH, Fb.z1, FH, gdst(f0 + 2), FH, FH, FH, Nn);              // field_net.net.2
-    T.j[T.n++] = wg(Fb.ga2, FH, nullptr, 0, gdst(f0 + 3), 1, FH, 1, Nn);
-    T.j[T.n++] = wg(B.gf, 3, Fb.z2, FH, gdst(f0 + 4), FH, 3, FH, Nn);                  // field_net.net.4
-    T.j[T.n++] = wg(B.gf, 3, nullptr, 0, gdst(f0 + 5), 1, 3, 1, Nn);
-    T.j[T.n++] = wg(Fb.onehot, 3, Fb.gemb, 16, gdst(f0 + 6), 16, 3, 16, Nn);          // class_embedding
-    if (int rc = egnn_wgrad(T, Lo, ws, st)) return rc;
+    WgTable J;
+    J.add(gh0, H, hin, c.in_nf, 0, gdst(0), c.in_nf, H, c.in_nf, Nn);          // embedding
+    J.add(gh0, H, nullptr, 0, 0, gdst(1), 1, H, 1, Nn);
+    J.add(Fb.ga1, FH, Fb.fin, FIN, 0, gdst(f0 + 0), FIN, FH, FIN, Nn);          // field_net.net.0
+    J.add(Fb.ga1, FH, nullptr, 0, 0, gdst(f0 + 1), 1, FH, 1, Nn);
+    J.add(Fb.ga2, FH, Fb.z1, FH, 0, gdst(f0 + 2), FH, FH, FH, Nn);              // field_net.net.2
+    J.add(Fb.ga2, FH, nullptr, 0, 0, gdst(f0 + 3), 1, FH, 1, Nn);
+    J.add(B.gf, 3, Fb.z2, FH, 0, gdst(f0 + 4), FH, 3, FH, Nn);                  // field_net.net.4
+    J.add(B.gf, 3, nullptr, 0, 0, gdst(f0 + 5), 1, 3, 1, Nn);
+    J.add(Fb.onehot, 3, Fb.gemb, 16, 0, gdst(f0 + 6), 16, 3, 16, Nn);          // class_embedding
+    if (int rc = egnn_wgrad(J.T, Lo, ws, st)) return rc;
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }
@@ -300,27 +244,22 @@ int egnn_backward_impl(const EgnnCall& c, const float* const* params, const Egnn
 
 size_t aether_egnn_workspace_bytes(int hidden, int n_layers, int in_node_nf, int64_t n_nodes, int64_t n_edges,
                                    int keep_for_backward) {
-    if ((hidden != 64 && hidden != 128) || n_layers < 1 || n_layers > 64 || in_node_nf < 1 || n_nodes <= 0 || n_edges < 0)
-        return 0;
+    if (!egnn_sizes_ok(hidden, n_layers, in_node_nf) || n_nodes <= 0 || n_edges < 0) return 0;
     return EgnnLayout(hidden, n_layers, in_node_nf, n_nodes, n_edges, keep_for_backward != 0).total;
 }
 
 int64_t aether_egnn_grad_floats(int hidden, int n_layers, int in_node_nf) {
-    if ((hidden != 64 && hidden != 128) || n_layers < 1 || n_layers > 64 || in_node_nf < 1) return AETHER_EINVAL;
+    if (!egnn_sizes_ok(hidden, n_layers, in_node_nf)) return AETHER_EINVAL;
     return egnn_grad_offset(egnn_n_params(n_layers), hidden, n_layers, in_node_nf);
 }
 
 int64_t aether_egnn_workspace_offset(const char* name, int layer, int hidden, int n_layers, int in_node_nf, int64_t n_nodes,
                                      int64_t n_edges) {
-    if (!name || (hidden != 64 && hidden != 128) || n_layers < 1 || n_layers > 64 || in_node_nf < 1 || n_nodes <= 0 ||
-        n_edges < 0)
+    if (!name || !egnn_sizes_ok(hidden, n_layers, in_node_nf) || n_nodes <= 0 || n_edges < 0)
         return fail(AETHER_EINVAL, "egnn_workspace_offset: bad arguments");
     const EgnnLayout Lo(hidden, n_layers, in_node_nf, n_nodes, n_edges, true);
     if (!strcmp(name, "field")) return (int64_t)Lo.F;
-    if (layer < 0 || layer > n_layers) return fail(AETHER_EINVAL, "egnn_workspace_offset: layer outside [0, n_layers]");
-    if (!strcmp(name, "h")) return (int64_t)(Lo.hs + (size_t)layer * n_nodes * hidden * 4);
-    if (!strcmp(name, "x")) return (int64_t)(Lo.xs + (size_t)layer * n_nodes * 3 * 4);
-    return fail(AETHER_EINVAL, "egnn_workspace_offset: unknown name (field, h, x)");
+    return gnn_slot_offset("egnn_workspace_offset", "field, h, x", name, layer, n_layers, Lo.hs, Lo.xs, n_nodes, hidden);
 }
 
 int aether_egnn_forward(const float* const* params, int n_params, int hidden, int n_layers, int in_node_nf, int flags,
@@ -329,13 +268,13 @@ int aether_egnn_forward(const float* const* params, int n_params, int hidden, in
                         void* workspace, size_t workspace_bytes, float* out, void* stream) {
     if (int rc = egnn_check(params, n_params, hidden, n_layers, in_node_nf, n_nodes, n_edges, graph, info, "egnn_forward"))
         return rc;
-    if (!h || !x || !vel || !charges || !workspace || !out || (n_edges > 0 && !edge_attr))
-        return fail(AETHER_EINVAL, "egnn_forward: null pointer");
-    if (flags & ~(AETHER_EGNN_NORM_DIFF | AETHER_EGNN_TANH | AETHER_EGNN_KEEP))
-        return fail(AETHER_EINVAL, "egnn_forward: unknown flag");
     const bool keep = (flags & AETHER_EGNN_KEEP) != 0;
     const EgnnLayout Lo(hidden, n_layers, in_node_nf, n_nodes, n_edges, keep);
-    if (workspace_bytes < Lo.total) return fail(AETHER_ESPACE, "egnn_forward: workspace too small");
+    if (int rc = gnn_entry_check("egnn_forward",
+                                 !h || !x || !vel || !charges || !workspace || !out || (n_edges > 0 && !edge_attr),
+                                 flags & ~EGNN_FLAGS, workspace_bytes,
+                                 Lo.total))
+        return rc;
     const EgnnCall c = egnn_call(hidden, n_layers, in_node_nf, flags, n_nodes, n_edges, graph);
     hipStream_t st = (hipStream_t)stream;
     if (hidden == 64) return egnn_forward_impl<64>(c, params, Lo, keep, h, x, vel, edge_attr, charges, (char*)workspace, out, st);
@@ -349,14 +288,13 @@ int aether_egnn_backward(const float* const* params, int n_params, int hidden, i
                          void* stream) {
     if (int rc = egnn_check(params, n_params, hidden, n_layers, in_node_nf, n_nodes, n_edges, graph, info, "egnn_backward"))
         return rc;
-    if (!h || !x || !vel || !charges || !workspace || !grad_out || !grad || (n_edges > 0 && !edge_attr))
-        return fail(AETHER_EINVAL, "egnn_backward: null pointer");
-    if (flags & ~(AETHER_EGNN_NORM_DIFF | AETHER_EGNN_TANH | AETHER_EGNN_KEEP))
-        return fail(AETHER_EINVAL, "egnn_backward: unknown flag");
-    if (grad_floats < egnn_grad_offset(egnn_n_params(n_layers), hidden, n_layers, in_node_nf))
-        return fail(AETHER_ESPACE, "egnn_backward: gradient buffer too small");
     const EgnnLayout Lo(hidden, n_layers, in_node_nf, n_nodes, n_edges, true);
-    if (workspace_bytes < Lo.total) return fail(AETHER_ESPACE, "egnn_backward: workspace too small (keep-for-backward size)");
+    if (int rc = gnn_entry_check("egnn_backward", !h || !x || !vel || !charges || !workspace || !grad_out || !grad ||
+                                                      (n_edges > 0 && !edge_attr),
+                                 flags & ~EGNN_FLAGS, workspace_bytes,
+                                 Lo.total, grad_floats,
+                                 egnn_grad_offset(egnn_n_params(n_layers), hidden, n_layers, in_node_nf)))
+        return rc;
     const EgnnCall c = egnn_call(hidden, n_layers, in_node_nf, flags, n_nodes, n_edges, graph);
     hipStream_t st = (hipStream_t)stream;
     if (hidden == 64)

@@ -104,18 +104,19 @@ def _train_workspace(module, ws_bytes, device):
     return ws, token
 
 
-def _hand_over_grads(module, plist, views, dst_flat, dst_views, aliased, need):
+def _hand_over_grads(module, plist, views, dst_flat, dst_views, aliased, need, skip=()):
     """After a backward wrote its parameter gradients into ``dst_flat`` (``dst_views``): the data-parallel mean, then what
     autograd returns for the parameters.  A parameter whose .grad is unset gets the view of the flat buffer itself (like
     DDP's gradient_as_bucket_view); a .grad that already is that view is accumulated into in place (``aliased``: the
-    backward wrote into the second buffer); any other existing .grad is accumulated by autograd."""
+    backward wrote into the second buffer); any other existing .grad is accumulated by autograd.  ``skip``: indices of
+    parameters that never get a gradient (they do not reach the output): None, .grad left as it is."""
     if module.dp_group is not None:            # one fused all-reduce of the flat buffer (RCCL)
         import torch.distributed as dist
         dist.all_reduce(dst_flat, group=module.dp_group)
         dst_flat.div_(dist.get_world_size(module.dp_group))
     out = []
-    for p, v, dv, n in zip(plist, views, dst_views, need):
-        if not n:
+    for i, (p, v, dv, n) in enumerate(zip(plist, views, dst_views, need)):
+        if not n or i in skip:
             out.append(None)
         elif module.grad_as_view and p.grad is None and not aliased:
             p.grad = v

@@ -4,9 +4,10 @@ experiments/lorentz/main.py:152-157 builds for ``--model clof``, ``clof_vel`` an
 Same constructors, ``forward(h, x, edges, vel, edge_attr, node_attr=None, n_nodes=5)`` signature and ``state_dict`` keys /
 shapes / order (clof.py, clof/gcl.py, clof/layers.py, egnn/gcl.py:17-51), and the same default initialisation under a
 torch seed.  The computation runs in ``libaether_hip.so`` (``aether_clof_forward`` / ``aether_clof_backward``,
-csrc/clof.h); there is no PyTorch or CPU fallback.  With gradients enabled the step goes through ``_ClofStep``: parameter
-gradients only, written into one flat buffer (the runner detaches every input, main.py:266-271), so ``GraphedTrainStep``,
-``FusedAdamW`` and ``attach_data_parallel`` work as they do for ``Aether``.  Parameters that do not reach the output --
+csrc/clof.h); there is no PyTorch or CPU fallback.  With gradients enabled the step goes through
+``_paramgrad._ParamGradStep``: parameter gradients only, written into one flat buffer (the runner detaches every input,
+main.py:266-271), so ``GraphedTrainStep``, ``FusedAdamW`` and ``attach_data_parallel`` work as they do for ``Aether``.  The
+plumbing around the library calls is ``_paramgrad.ParamGradModule``'s.  Parameters that do not reach the output --
 the last layer's ``node_mlp`` and ``layer_norm``, ClofNet's ``embedding_edge`` -- keep ``.grad`` None, as in the
 reference, so no optimizer touches them.
 
@@ -16,15 +17,11 @@ exactly 3 edges); the Gaussian layer's edge type is clamped to [0, 7] (the refer
 """
 from __future__ import annotations
 
-import ctypes as C
-import weakref
-
-import numpy as np
 import torch
 import torch.nn as nn
 
 from ... import _lib
-from .aether import GraphCache, _WsToken
+from ._paramgrad import ParamGradModule
 
 SUPPORTED_HIDDEN = (64, 128)
 _HEAD = {0: 8, 1: 6, 2: 10}           # tensors before gcl_0 (include/aether_hip.h)
@@ -71,62 +68,10 @@ class GaussianLayer(nn.Module):
         nn.init.constant_(self.mul.weight, 1)
 
 
-class _ClofStep(torch.autograd.Function):
-    """aether_clof_forward (keep-for-backward form) / aether_clof_backward behind torch.autograd; parameters only."""
-
-    N_FIXED = 7          # module, h, x, vel, edge_attr, n_nodes, graph precede the parameters
-
-    @staticmethod
-    def forward(ctx, module, h, x, vel, ea, n_per, graph, *params):
-        out, ws, token = module._launch(h, x, vel, ea, n_per, graph, train=True)
-        ctx.module = module
-        ctx.saved = (h, x, vel, ea, n_per, graph, ws, token)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        lib = _lib.load()
-        module = ctx.module
-        h, x, vel, ea, n_per, (graph, ginfo), ws, _token = ctx.saved
-        flat, views = module._grad_buffers()
-        plist = module._param_list()
-        # aether_clof_backward OVERWRITES its destination: when a .grad already is a view of the flat buffer (a second
-        # backward without zero_grad), the kernels write into a second buffer and the result is added
-        aliased = module.grad_as_view and any(p.grad is not None and p.grad.data_ptr() == v.data_ptr()
-                                              for p, v in zip(plist, views))
-        dst_flat, dst_views = module._grad_buffers(second=True) if aliased else (flat, views)
-        g = grad_out.to(torch.float32).contiguous()
-        st = lib.aether_clof_backward(module._ptrs(), len(plist), module._variant, module.hidden_nf, module.n_layers,
-                                      module.in_node_nf, module._flags | _lib.CLOF_KEEP, module.coords_weight, n_per,
-                                      x.shape[0], ginfo.n_edges, h.data_ptr(), x.data_ptr(), vel.data_ptr(),
-                                      ea.data_ptr(), graph.data_ptr(), C.byref(ginfo), ws.data_ptr(), ws.numel(),
-                                      g.data_ptr(), dst_flat.data_ptr(), dst_flat.numel(),
-                                      torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(st, "aether_clof_backward")
-        if module.dp_group is not None:            # one fused all-reduce of the flat buffer (RCCL)
-            import torch.distributed as dist
-            dist.all_reduce(dst_flat, group=module.dp_group)
-            dst_flat.div_(dist.get_world_size(module.dp_group))
-        need = ctx.needs_input_grad[_ClofStep.N_FIXED:]
-        dead = module._dead()
-        out = []
-        for i, (p, v, dv, n) in enumerate(zip(plist, views, dst_views, need)):
-            if not n or i in dead:
-                out.append(None)
-            elif module.grad_as_view and p.grad is None and not aliased:
-                p.grad = v
-                out.append(None)
-            elif module.grad_as_view and p.grad is not None and p.grad.data_ptr() == v.data_ptr():
-                v.add_(dv)
-                out.append(None)
-            else:
-                out.append(dv.clone())
-        return (None,) * _ClofStep.N_FIXED + tuple(out)
-
-
-class _ClofBase(nn.Module):
+class _ClofBase(ParamGradModule):
     VARIANT = None
-    NAME = None
+    ENTRY = "aether_clof"
+    KEEP = _lib.CLOF_KEEP
 
     def __init__(self, in_node_nf, in_edge_nf, hidden_nf, device="cpu", act_fn=nn.SiLU(), n_layers=4, coords_weight=1.0,
                  recurrent=True, norm_diff=True, tanh=False):
@@ -166,41 +111,10 @@ class _ClofBase(nn.Module):
             self.add_module("gcl_%d" % i, Clof_GCL(H, H2, self.tanh))
         self._flags = ((_lib.CLOF_NORM_DIFF if self._layer_norm_diff else 0) | (_lib.CLOF_TANH if self.tanh else 0) |
                        (_lib.CLOF_RECURRENT if self.recurrent else 0))
-        self._graphs = GraphCache()
-        self.dp_group = None              # set by aether_amd.parallel.attach_data_parallel
-        self.grad_as_view = True          # .grad tensors alias one flat buffer (see _ClofStep.backward)
-        self._plist = None
-        self._ptr_cache = None
-        self._gbuf = None
-        self._gbuf2 = None
-        self._ws = None
-        self._train_ws, self._train_ws_token = None, None
-        self._last_ws = None
-        self.to(self.device)
-        self.params = self.__str__()
+        self._finish_init()
 
-    def __str__(self):
-        params = sum(int(np.prod(p.size())) for p in self.parameters() if p.requires_grad)
-        print("Network Size", params)
-        return str(params)
-
-    # -- plumbing ------------------------------------------------------------------
-    def _apply(self, fn, *a, **k):
-        self._plist = None                # parameter storage may move (.to / .cuda / .float)
-        self._ptr_cache = None
-        self._gbuf = None
-        self._gbuf2 = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._plist = None
-        self._ptr_cache = None
-        return super().load_state_dict(*a, **k)
-
-    def _param_list(self):
-        if self._plist is None:
-            self._plist = [p for _, p in self.named_parameters()]
-        return self._plist
+    def _sizes(self):
+        return self._variant, self.hidden_nf, self.n_layers, self.in_node_nf
 
     def _dead(self):
         """Indices (named_parameters order) of the tensors that do not reach the output: the last layer's node_mlp and
@@ -210,85 +124,6 @@ class _ClofBase(nn.Module):
         if self._variant == 0:
             dead |= {2, 3}
         return dead
-
-    def _ptrs(self):
-        """Host array of the parameters' device pointers, named_parameters() order (include/aether_hip.h)."""
-        plist = self._param_list()
-        key = tuple(p.data_ptr() for p in plist)
-        if self._ptr_cache is None or self._ptr_cache[0] != key:
-            for p in plist:
-                if not (p.dtype == torch.float32 and p.is_contiguous()):
-                    raise _lib.AetherHipError(f"{self.NAME}: parameters must be contiguous fp32")
-            self._ptr_cache = (key, (C.c_void_p * len(plist))(*key))
-        return self._ptr_cache[1]
-
-    def _grad_buffers(self, second=False):
-        """Flat fp32 gradient buffer and per-parameter views into it: every tensor at the next multiple of 4 floats, in
-        named_parameters() order (the layout aether_clof_backward writes)."""
-        slot = "_gbuf2" if second else "_gbuf"
-        cur = getattr(self, slot, None)
-        plist = self._param_list()
-        if cur is not None and cur[0].device == plist[0].device:
-            return cur
-        offs, off = [], 0
-        for p in plist:
-            offs.append(off)
-            off += (p.numel() + 3) // 4 * 4
-        want = _lib.load().aether_clof_grad_floats(self._variant, self.hidden_nf, self.n_layers, self.in_node_nf)
-        if want != off:
-            raise _lib.AetherHipError(f"{self.NAME}: gradient layout mismatch ({off} floats, library {want})")
-        flat = torch.zeros(off, dtype=torch.float32, device=plist[0].device)
-        views = [flat[o:o + p.numel()].view_as(p) for o, p in zip(offs, plist)]
-        cur = (flat, views)
-        setattr(self, slot, cur)
-        return cur
-
-    def _workspace_bytes(self, n_nodes, n_edges, keep):
-        return _lib.load().aether_clof_workspace_bytes(self._variant, self.hidden_nf, self.n_layers, self.in_node_nf,
-                                                       n_nodes, n_edges, 1 if keep else 0)
-
-    def prepare_graph(self, edges, n_nodes):
-        """Row-sorted view of ``edges = [row, col]``: aether_graph_build with the index rows swapped, so that the view
-        groups the edges by edges[0], over which Clof_GCL sums and averages."""
-        row, col = edges
-        return self._graphs.get(col.contiguous(), row.contiguous(), n_nodes)
-
-    def _launch(self, h, x, vel, ea, n_per, graph, train, keep=False):
-        lib = _lib.load()
-        graph, ginfo = graph
-        n_nodes, n_edges = x.shape[0], ginfo.n_edges
-        keep = keep or train
-        nbytes = max(self._workspace_bytes(n_nodes, n_edges, keep), 256)
-        token = None
-        if train:
-            # one workspace per forward still waiting for its backward (the token its autograd node holds); under
-            # hipGraph capture the buffer comes from the graph's pool
-            tw, tok = self._train_ws, self._train_ws_token
-            busy = tok is not None and tok() is not None
-            capturing = torch.cuda.is_current_stream_capturing()
-            if tw is not None and not busy and tw.numel() >= nbytes and tw.device == x.device and not capturing:
-                ws = tw
-            else:
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-                if not capturing:
-                    self._train_ws = ws
-            if not capturing:
-                token = _WsToken()
-                self._train_ws_token = weakref.ref(token)
-        else:
-            if self._ws is None or self._ws.numel() < nbytes or self._ws.device != x.device:
-                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            ws = self._ws
-        out = torch.empty_like(x)
-        flags = self._flags | (_lib.CLOF_KEEP if keep else 0)
-        st = lib.aether_clof_forward(self._ptrs(), len(self._param_list()), self._variant, self.hidden_nf, self.n_layers,
-                                     self.in_node_nf, flags, self.coords_weight, n_per, n_nodes, n_edges, h.data_ptr(),
-                                     x.data_ptr(), vel.data_ptr(), ea.data_ptr(), graph.data_ptr(), C.byref(ginfo),
-                                     ws.data_ptr(), ws.numel(), out.data_ptr(),
-                                     torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(st, "aether_clof_forward")
-        self._last_ws = ws
-        return out, ws, token
 
     def _inputs(self, h, x, edges, vel, edge_attr, node_attr, n_nodes):
         if node_attr is not None:
@@ -313,36 +148,18 @@ class _ClofBase(nn.Module):
             raise ValueError("h / edge index / edge_attr shapes do not match")
         f32 = lambda t: t.detach().to(torch.float32).contiguous()
         graph = self.prepare_graph((row, col), N)
-        return f32(h), f32(x), f32(vel), f32(edge_attr), n_per, graph
+        return f32(h), f32(x), f32(vel), (f32(edge_attr),), (self.coords_weight, n_per), graph
 
     # -- reference surface -----------------------------------------------------------
     def forward(self, h, x, edges, vel, edge_attr, node_attr=None, n_nodes=5):
-        h, x, vel, ea, n_per, graph = self._inputs(h, x, edges, vel, edge_attr, node_attr, n_nodes)
-        plist = self._param_list()
-        if torch.is_grad_enabled() and any(p.requires_grad for p in plist):
-            return _ClofStep.apply(self, h, x, vel, ea, n_per, graph, *plist)
-        return self._launch(h, x, vel, ea, n_per, graph, train=False)[0]
+        return self._run(*self._inputs(h, x, edges, vel, edge_attr, node_attr, n_nodes))
 
     # -- test hook -------------------------------------------------------------------
     @torch.no_grad()
     def forward_layers(self, h, x, edges, vel, edge_attr, node_attr=None, n_nodes=5):
         """(out, [h_0 .. h_L], [x_0 .. x_L]): every layer's input h and centred x (the embedding's output and the
         centred input, then each layer's output), from a keep-for-backward forward."""
-        h, x, vel, ea, n_per, graph = self._inputs(h, x, edges, vel, edge_attr, node_attr, n_nodes)
-        out, ws, _ = self._launch(h, x, vel, ea, n_per, graph, train=False, keep=True)
-        lib = _lib.load()
-        n, H, L = x.shape[0], self.hidden_nf, self.n_layers
-        E = graph[1].n_edges
-        f = ws[: ws.numel() // 4 * 4].view(torch.float32)
-
-        def at(name, layer, cols):
-            off = lib.aether_clof_workspace_offset(name.encode(), layer, self._variant, H, L, self.in_node_nf, n, E)
-            _lib.check(off, "aether_clof_workspace_offset")
-            return f[off // 4: off // 4 + n * cols].view(n, cols).clone()
-
-        hs = [at("h", l, H) for l in range(L + 1)]
-        xs = [at("x", l, 3) for l in range(L + 1)]
-        return out, hs, xs
+        return self._run_layers(*self._inputs(h, x, edges, vel, edge_attr, node_attr, n_nodes))
 
 
 class ClofNet(_ClofBase):

@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from ... import _lib
+from ._paramgrad import _flat_grad_buffers
 from .aether import GraphCache, _GNN, _hand_over_grads, _kernel_width, _pad_blocks, _train_workspace
 
 
@@ -290,19 +291,7 @@ class LoCS(nn.Module):
         named_parameters() order (Aether._grad_buffers' layout; GraphedTrainStep, FusedAdamW and data parallelism use it).
         ``second``: a scratch buffer of the same layout, the destination of a backward whose result is ADDED to
         gradients that already live in the first one."""
-        slot = "_gbuf2" if second else "_gbuf"
-        cur = getattr(self, slot)
-        plist = self._param_list()
-        if cur is not None and cur[0].device == plist[0].device:
-            return cur
-        offs, off = [], 0
-        for p in plist:
-            offs.append(off)
-            off += (p.numel() + 3) // 4 * 4
-        flat = torch.zeros(off, dtype=torch.float32, device=plist[0].device)
-        cur = (flat, [flat[o:o + p.numel()].view_as(p) for o, p in zip(offs, plist)])
-        setattr(self, slot, cur)
-        return cur
+        return _flat_grad_buffers(self, second)
 
     def _grad_struct(self, dst_views):
         """AetherParams of gradient destinations: the views themselves where the shapes agree, engine-shaped scratch for
