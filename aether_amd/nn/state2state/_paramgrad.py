@@ -15,12 +15,11 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
 import torch
 import torch.nn as nn
 
 from ... import _lib
-from .aether import GraphCache, _hand_over_grads, _train_workspace
+from ._frame import GraphCache, _grads_alias_flat, _hand_over_grads, _train_workspace, network_size
 
 
 def _flat_grad_buffers(module, second=False, check=None):
@@ -63,10 +62,7 @@ class _ParamGradStep(torch.autograd.Function):
         h, x, vel, extra, call, (graph, ginfo), ws, _token = ctx.saved
         flat, views = module._grad_buffers()
         plist = module._param_list()
-        # ENTRY_backward OVERWRITES its destination: when a .grad already is a view of the flat buffer (a second backward
-        # without zero_grad), the kernels write into a second buffer and the result is added
-        aliased = module.grad_as_view and any(p.grad is not None and p.grad.data_ptr() == v.data_ptr()
-                                              for p, v in zip(plist, views))
+        aliased = _grads_alias_flat(module, plist, views)        # ENTRY_backward OVERWRITES its destination
         dst_flat, dst_views = module._grad_buffers(second=True) if aliased else (flat, views)
         g = grad_out.to(torch.float32).contiguous()
         st = module._entry("backward")(module._ptrs(), len(plist), *module._sizes(), module._flags | module.KEEP, *call,
@@ -100,10 +96,7 @@ class ParamGradModule(nn.Module):
         self.to(self.device)
         self.params = self.__str__()
 
-    def __str__(self):
-        params = sum(int(np.prod(p.size())) for p in self.parameters() if p.requires_grad)
-        print("Network Size", params)
-        return str(params)
+    __str__ = network_size
 
     # -- what a subclass supplies ----------------------------------------------------
     def _sizes(self):

@@ -5,128 +5,18 @@ Same constructor, ``forward(h, x, edges, vel, edge_attr_orig, charges)`` signatu
 checkpoint saved by either loads into the other.  The computation runs in
 ``libaether_hip.so`` (hand-written gfx950 kernels, include/aether_hip.h); there is no
 PyTorch or CPU fallback -- on a machine without the library or a GPU tensor the call
-raises.
+raises.  The plumbing shared with ``DynamicFieldAether`` and ``LoCS`` is ``_frame.FrameModule``.
 """
 from __future__ import annotations
 
 import ctypes as C
-import weakref
-from collections import OrderedDict
 
-import numpy as np
 import torch
 import torch.nn as nn
 
 from ... import _lib
-
-
-class GraphCache:
-    """Receiver-sorted view of an edge index, built once per distinct edge tensor pair.
-
-    The reference re-creates the same edge index every batch
-    (experiments/lorentz/main.py:211-212); reusing the tensors (or calling
-    ``Aether.prepare_graph``) makes this a dictionary lookup."""
-
-    def __init__(self, max_entries=8):
-        self.max_entries = max_entries
-        self._d = OrderedDict()
-
-    @staticmethod
-    def _key(send, recv, n_nodes):
-        return (send.data_ptr(), recv.data_ptr(), send.numel(), int(n_nodes), send._version,
-                recv._version, send.device.index)
-
-    def get(self, send, recv, n_nodes):
-        key = self._key(send, recv, n_nodes)
-        hit = self._d.get(key)
-        if hit is not None:
-            self._d.move_to_end(key)
-            return hit[0]
-        # Same index in new tensors (the runner rebuilds it every batch, main.py:211-212): one comparison kernel against
-        # the view's own sorted copy + a 4-byte flag (aether_graph_matches, ~20 us) instead of sorting again (two
-        # torch.equal calls cost 0.19 ms: several reductions and a blocking .item() each).
-        lib = _lib.load()
-        for k2, (val, s2, r2) in reversed(list(self._d.items())):
-            if (k2[2], k2[3], k2[6]) == (key[2], key[3], key[6]):
-                stream = torch.cuda.current_stream(send.device).cuda_stream
-                same = lib.aether_graph_matches(send.data_ptr(), recv.data_ptr(), send.numel(), n_nodes, val[0].data_ptr(), stream)
-                if same < 0:
-                    _lib.check(same, "aether_graph_matches")
-                if same == 1:
-                    self._d[key] = (val, send, recv)
-                    self._trim()
-                    return val
-        E = send.numel()
-        nbytes = lib.aether_graph_bytes(E, n_nodes)
-        buf = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=send.device)
-        info = _lib.AetherGraphInfo()
-        stream = torch.cuda.current_stream(send.device).cuda_stream
-        _lib.check(lib.aether_graph_build(send.data_ptr(), recv.data_ptr(), E, n_nodes,
-                                          buf.data_ptr(), buf.numel(), C.byref(info), stream),
-                   "aether_graph_build")
-        # keep the index tensors alive so the key (their addresses) stays unique
-        self._d[key] = ((buf, info), send, recv)
-        self._trim()
-        return buf, info
-
-    def _trim(self):
-        while len(self._d) > self.max_entries:
-            self._d.popitem(last=False)
-
-
-class _WsToken:
-    """Held by the autograd node of a training forward: while it is alive that forward's workspace is still needed."""
-    __slots__ = ("__weakref__",)
-
-
-def _train_workspace(module, ws_bytes, device):
-    """The workspace of a training forward and the token its autograd node holds (None under capture).
-
-    The backward reads this forward's intermediates: one workspace per forward that is still waiting for its backward.
-    The usual loop (forward, backward, step) gets the module's cached buffer back every time -- a fresh torch.empty per
-    call kept TWO of them alive across steps (this one and the previous step's, still referenced), which at the 33.5 M-edge
-    shard of config 5 (~120 GB each) pushed the caching allocator into freeing and re-allocating device memory every step
-    (0.44 s of a 0.55 s step).  Under hipGraph capture the buffer comes from the graph's pool as before.
-    "Still waiting": the autograd node that saved the buffer is alive (a token it holds; after backward() without
-    retain_graph the node and the token are gone).  The module keeps ``_train_ws`` and ``_train_ws_token``."""
-    tw, tok = module._train_ws, module._train_ws_token
-    busy = tok is not None and tok() is not None
-    capturing = torch.cuda.is_current_stream_capturing()
-    if tw is not None and not busy and tw.numel() >= ws_bytes and tw.device == device and not capturing:
-        ws = tw
-    else:
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-        if not capturing:
-            module._train_ws = ws
-    token = _WsToken() if not capturing else None
-    if token is not None:
-        module._train_ws_token = weakref.ref(token)
-    return ws, token
-
-
-def _hand_over_grads(module, plist, views, dst_flat, dst_views, aliased, need, skip=()):
-    """After a backward wrote its parameter gradients into ``dst_flat`` (``dst_views``): the data-parallel mean, then what
-    autograd returns for the parameters.  A parameter whose .grad is unset gets the view of the flat buffer itself (like
-    DDP's gradient_as_bucket_view); a .grad that already is that view is accumulated into in place (``aliased``: the
-    backward wrote into the second buffer); any other existing .grad is accumulated by autograd.  ``skip``: indices of
-    parameters that never get a gradient (they do not reach the output): None, .grad left as it is."""
-    if module.dp_group is not None:            # one fused all-reduce of the flat buffer (RCCL)
-        import torch.distributed as dist
-        dist.all_reduce(dst_flat, group=module.dp_group)
-        dst_flat.div_(dist.get_world_size(module.dp_group))
-    out = []
-    for i, (p, v, dv, n) in enumerate(zip(plist, views, dst_views, need)):
-        if not n or i in skip:
-            out.append(None)
-        elif module.grad_as_view and p.grad is None and not aliased:
-            p.grad = v
-            out.append(None)
-        elif module.grad_as_view and p.grad is not None and p.grad.data_ptr() == v.data_ptr():
-            v.add_(dv)
-            out.append(None)
-        else:
-            out.append(dv.clone())
-    return out
+from ._frame import (FrameModule, GraphCache, _GNN, _f32, _f32g, _grads_alias_flat, _hand_over_grads,  # noqa: F401
+                     _kernel_width, _pad_blocks, _train_workspace, cut, place)
 
 
 class _AetherStep(torch.autograd.Function):
@@ -136,159 +26,40 @@ class _AetherStep(torch.autograd.Function):
     N_FIXED = 7          # module, x, vel, edge_attr, charges, graph, n_edges precede the parameters
 
     @staticmethod
-    def launch(module, train, x, vel, edge_attr, charges, graph, n_edges):
-        """One aether_forward call; returns (out, saved-for-backward or None)."""
-        lib = _lib.load()
-        graph, ginfo = graph
-        D = module.num_dims
-        n_nodes = x.shape[0]
-        flags = module.flags
-        if train and not (flags & _lib.FLAG_KEEP_INTERMEDIATES):
-            # training: keep what the backward reads, not the last layer's messages (only aether_debug_fetch reads them)
-            flags |= _lib.FLAG_KEEP_INTERMEDIATES | _lib.FLAG_BACKWARD_ONLY
-        keep = bool(flags & _lib.FLAG_KEEP_INTERMEDIATES)
-        dropout = train and module.dropout_prob > 0.0 and module.training
-        if dropout:
-            flags |= _lib.FLAG_DROPOUT
-        ws_bytes = module._workspace_bytes(n_nodes, n_edges, keep)
-        ws_key = None
-        if train:
-            ws, token = _train_workspace(module, ws_bytes, x.device)
-            # An optimizer step follows a training forward, and not every optimizer bumps the parameters' version
-            # counters (torch's fused AdamW does not): the inference workspace's weight images are stale from here on.
-            module._wimg_key = None
-        else:
-            ws = module._workspace(ws_bytes, x.device)
-            # same buffer, same layout as the last completed inference call: the fused kernel left its
-            # hand-off words re-armed, the library need not zero them again (AETHER_FLAG_WORKSPACE_REUSED)
-            fused = ginfo.n_groups > 0 and n_edges > 0 and not (flags & _lib.FLAG_FORCE_STREAMED)
-            ws_key = (ws.data_ptr(), n_nodes, n_edges, D, keep, graph.data_ptr()) if fused else None
-            if ws_key is not None and module._ws_key == ws_key:
-                flags |= _lib.FLAG_WORKSPACE_REUSED
-            module._ws_key = None
-            wkey = module._weights_key(ws, n_nodes, n_edges)
-            if fused and module._wimg_key == wkey and module._may_reuse_weight_images():
-                flags |= _lib.FLAG_WEIGHTS_PREPARED
-            module._wimg_key = None
-        if dropout:
-            # nn.Dropout after the two SiLUs of the out MLP (locs.py:163,166): scale masks drawn by torch, written straight
-            # into their place in the training workspace (same distribution as nn.Dropout, not its random stream)
-            kw = module._kw
-            off = (lib.aether_dropout_mask_offset(n_nodes, n_edges, D) if kw == 64 else
-                   lib.aether_dropout_mask_offset_h(n_nodes, n_edges, D, kw))
-            masks = ws[off:off + 2 * n_nodes * kw * 4].view(torch.float32).view(2, n_nodes, kw)
-            given = module.__dict__.get("_dropout_masks")          # tests: explicit masks [2, n_nodes, width]
-            if given is not None:
-                masks.copy_(given.to(device=x.device, dtype=torch.float32))
-            else:
-                keep_p = 1.0 - module.dropout_prob
-                masks.bernoulli_(keep_p).mul_(1.0 / keep_p)
-        out = torch.empty_like(x)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        if module._kw == 64:
-            st = lib.aether_forward(module._param_struct_ref(), D, n_nodes, n_edges,
-                                    x.data_ptr(), vel.data_ptr(), charges.data_ptr(),
-                                    edge_attr.data_ptr(), graph.data_ptr(), C.byref(ginfo), ws.data_ptr(),
-                                    ws.numel(), out.data_ptr(), flags, stream)
-        else:       # hidden_size > 64: the layer-by-layer GEMM path (csrc/wide.h), width as an argument
-            st = lib.aether_forward_h(module._param_struct_ref(), D, module._kw, n_nodes, n_edges,
-                                      x.data_ptr(), vel.data_ptr(), charges.data_ptr(), None,
-                                      edge_attr.data_ptr(), graph.data_ptr(), C.byref(ginfo), ws.data_ptr(),
-                                      ws.numel(), out.data_ptr(), flags & ~_lib.FLAG_FORCE_STREAMED, stream)
-        _lib.check(st, "aether_forward")
-        module._ws_key = ws_key
-        if not train:
-            module._wimg_key = wkey
-        module._last_ws = ws
-        return out, ((x, vel, charges, graph, ginfo, ws, n_edges, token) if train else None)
-
-    @staticmethod
     def forward(ctx, module, x, vel, edge_attr, charges, graph, n_edges, *params):
         # only the training path comes through here (inside Function.forward grad mode is always off and
         # needs_input_grad reflects requires_grad even under torch.no_grad(): the caller decides)
-        out, saved = _AetherStep.launch(module, True, x, vel, edge_attr, charges, graph, n_edges)
+        out, ws, token = module._step("aether_forward", module._param_struct_ref(), x, vel, charges, None, edge_attr,
+                                      graph, n_edges, True)
         ctx.module = module
-        ctx.saved = saved
+        ctx.saved = (x, vel, charges, graph, ws, n_edges, token)
         if any(ctx.needs_input_grad[1:4]):       # x / vel / edge_attr: aether_backward_inputs recovers y = R^T (out - x)
             ctx.save_for_backward(out)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         module = ctx.module
-        x, vel, charges, graph, ginfo, ws, n_edges, _token = ctx.saved
-        D = module.num_dims
+        x, vel, charges, graph, ws, n_edges, _token = ctx.saved
         flat, gstruct, views = module._grad_buffers()
-        plist = module._plist if module._plist is not None else [p for _, p in module.named_parameters()]
-        # aether_backward OVERWRITES its destination.  When some .grad already IS a view of the flat buffer (a
-        # second backward without zero_grad, micro-batch accumulation, the module applied twice in one autograd
-        # graph), the kernels write into a second buffer and the result is added, as torch.autograd would.
-        aliased = module.grad_as_view and any(p.grad is not None and p.grad.data_ptr() == v.data_ptr()
-                                              for p, v in zip(plist, views))
+        plist = module._param_list()
+        aliased = _grads_alias_flat(module, plist, views)
         if aliased:
             dst_flat, dst_struct, dst_views = module._grad_buffers(second=True)
         else:
             dst_flat, dst_struct, dst_views = flat, gstruct, views
         g = grad_out.to(torch.float32).contiguous()
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        kw = module._kw
-        if kw == 64:
-            st = lib.aether_backward(C.byref(module._param_struct()), C.byref(dst_struct), D, x.shape[0], n_edges,
-                                     x.data_ptr(), vel.data_ptr(), charges.data_ptr(), graph.data_ptr(),
-                                     C.byref(ginfo), ws.data_ptr(), ws.numel(), g.data_ptr(), stream)
-        else:
-            st = lib.aether_backward_h(C.byref(module._param_struct()), C.byref(dst_struct), D, kw, x.shape[0], n_edges,
-                                       x.data_ptr(), vel.data_ptr(), charges.data_ptr(), graph.data_ptr(),
-                                       C.byref(ginfo), ws.data_ptr(), ws.numel(), g.data_ptr(), None, stream)
-        _lib.check(st, "aether_backward")
+        ps = module._param_struct_ref()
+        module._backward("aether_backward", ps, C.byref(dst_struct), x, vel, charges, graph, ws, n_edges, g)
         gx = gv = gea = None
         if any(ctx.needs_input_grad[1:4]):
             # gradients w.r.t. the inputs (the reference's forward is differentiable in them, aether.py:169-186): one more
             # kernel over what aether_backward left in the workspace
-            (out_saved,) = ctx.saved_tensors
-            gx, gv = torch.empty_like(x), torch.empty_like(x)
-            if ctx.needs_input_grad[3]:
-                gea = torch.empty(n_edges, 2, dtype=torch.float32, device=x.device)
-            if kw == 64:
-                st = lib.aether_backward_inputs(C.byref(module._param_struct()), D, x.shape[0], n_edges, x.data_ptr(),
-                                                vel.data_ptr(), charges.data_ptr(), graph.data_ptr(), C.byref(ginfo),
-                                                ws.data_ptr(), ws.numel(), out_saved.data_ptr(), g.data_ptr(), gx.data_ptr(),
-                                                gv.data_ptr(), gea.data_ptr() if gea is not None else None, None, stream)
-            else:
-                st = lib.aether_backward_inputs_h(C.byref(module._param_struct()), D, kw, x.shape[0], n_edges, x.data_ptr(),
-                                                  vel.data_ptr(), charges.data_ptr(), graph.data_ptr(), C.byref(ginfo),
-                                                  ws.data_ptr(), ws.numel(), out_saved.data_ptr(), g.data_ptr(), gx.data_ptr(),
-                                                  gv.data_ptr(), gea.data_ptr() if gea is not None else None, None, stream)
-            _lib.check(st, "aether_backward_inputs")
-            if not ctx.needs_input_grad[1]:
-                gx = None
-            if not ctx.needs_input_grad[2]:
-                gv = None
+            gx, gv, gea = module._input_grads(ctx.needs_input_grad[1:4], ps, x, vel, charges, graph, ws, n_edges,
+                                              ctx.saved_tensors[0], g)
         # hand the gradients over as views of the flat buffer (no 47 small copies)
         out = _hand_over_grads(module, plist, views, dst_flat, dst_views, aliased, ctx.needs_input_grad[_AetherStep.N_FIXED:])
         return (None, gx, gv, gea, None, None, None) + tuple(out)
-
-
-def _kernel_width(hidden_size):
-    """Width the kernels compute a model of this hidden_size at: 64 (fused / streamed kernels) up to 64, the next multiple
-    of 64 above (csrc/wide.h)."""
-    return 64 if hidden_size <= 64 else -(-hidden_size // 64) * 64
-
-
-def _pad_blocks(name, shape, H, kw=64):
-    """Where a parameter of a model with hidden_size H lives inside the same-named parameter of the kw-wide model the
-    kernels are built for (kw = 64, or the next multiple of 64 above H): a list of (source slices, destination slices).
-    Hidden vectors sit at the start of their kw-wide (update MLP: 2 kw-wide) counterparts; the first message layer of
-    layers 2-4 reads [x_send | x_recv | e], three H-wide column blocks that go to the starts of the three kw-wide blocks.
-    Everything else in the wide parameters stays zero, which makes the padded channels exactly zero through SiLU, the mean
-    and the residuals: the wide model computes the narrow one."""
-    full = tuple(slice(0, n) for n in shape)
-    if name.startswith("field_net."):
-        return [(full, full)]
-    if name.endswith("message_fn.0.weight") and not name.startswith("gnn.layer_1."):
-        return [((slice(0, H), slice(b * H, (b + 1) * H)), (slice(0, H), slice(kw * b, kw * b + H))) for b in range(3)]
-    return [(full, full)]                  # top / top-left aligned
 
 
 class _PaddedStep(torch.autograd.Function):
@@ -321,15 +92,8 @@ class _PaddedStep(torch.autograd.Function):
         need_in = (ctx.needs_input_grad[1], ctx.needs_input_grad[4], ctx.needs_input_grad[5])
         gx, gv, gea = (gin.pop(0) if n else None for n in need_in)
         need = ctx.needs_input_grad[_PaddedStep.N_FIXED:]
-        out = []
-        for (name, p), g, n in zip(outer.named_parameters(), grads, need):
-            if not n or g is None:
-                out.append(None)
-                continue
-            d = torch.empty_like(p)
-            for ss, ds in _pad_blocks(name, p.shape, outer.hidden_size, outer._kw):
-                d[ss] = g[ds]
-            out.append(d)
+        out = [cut(torch.empty_like(p), g, _pad_blocks(name, p.shape, outer.hidden_size, outer._kw))
+               if n and g is not None else None for (name, p), g, n in zip(outer.named_parameters(), grads, need)]
         if outer.dp_group is not None:             # data-parallel: one all-reduce of the narrow gradients, flat
             import torch.distributed as dist
             have = [g for g in out if g is not None]
@@ -353,83 +117,26 @@ class _FieldNetwork(nn.Module):
         self.class_embedding = nn.Embedding(3, class_embedding_dim)
 
 
-class _GNNLayer(nn.Module):
-    """Parameter holder, locs.py:197-225."""
-
-    def __init__(self, input_size, hidden_size, only_edge_attr=False, num_edge_features=0):
-        super().__init__()
-        self.only_edge_attr = only_edge_attr
-        num_edge_features = num_edge_features if only_edge_attr else 3 * hidden_size
-        self.message_fn = nn.Sequential(
-            nn.Linear(num_edge_features, hidden_size), nn.SiLU(),
-            nn.Linear(hidden_size, hidden_size), nn.SiLU())
-        self.res = nn.Linear(input_size, hidden_size) if input_size != hidden_size else nn.Identity()
-        self.update_fn = nn.Sequential(
-            nn.Linear(hidden_size, 2 * hidden_size), nn.SiLU(),
-            nn.Linear(2 * hidden_size, hidden_size))
-
-
-class _GNN(nn.Module):
-    """Parameter holder, locs.py:142-181 (construction order kept so that the default
-    initialisation under a given torch seed equals the reference's)."""
-
-    def __init__(self, input_size, hidden_size, dropout_prob, num_dims, additional_features=0):
-        super().__init__()
-        out_size = input_size // 2
-        num_orientations = num_dims * (num_dims - 1) // 2
-        num_relative_features = input_size + num_dims + num_orientations
-        self.out_mlp = nn.Sequential(
-            nn.Linear(hidden_size, hidden_size), nn.SiLU(), nn.Dropout(p=dropout_prob),
-            nn.Linear(hidden_size, hidden_size), nn.SiLU(), nn.Dropout(p=dropout_prob),
-            nn.Linear(hidden_size, out_size))
-        self.layer_1 = _GNNLayer(
-            input_size + additional_features, hidden_size, only_edge_attr=True,
-            num_edge_features=num_relative_features + input_size + 2 + 2 * additional_features)
-        self.layer_2 = _GNNLayer(hidden_size, hidden_size)
-        self.layer_3 = _GNNLayer(hidden_size, hidden_size)
-        self.layer_4 = _GNNLayer(hidden_size, hidden_size)
-
-
-class Aether(nn.Module):
+class Aether(FrameModule):
     """Drop-in for nn/state2state/aether.py:142-186."""
+
+    # forcing the 64-wide fused kernel on a wider model stays the library's error
+    WIDE_FORWARD_STRIP = _lib.FLAG_FORCE_STREAMED
+    EVAL_KEEP = True
+    DROP_ON_APPLY = ("_pstruct", "_plist", "_gbuf", "_gbuf2")
+    DROP_ON_LOAD = ("_pstruct", "_plist")
 
     def __init__(self, input_size, hidden_size, dropout_prob, num_dims, device="cuda"):
         super().__init__()
-        if not (1 <= hidden_size <= 4096):
-            raise ValueError("hidden_size must lie in [1, 4096] (experiments/lorentz/main.py:42-43)")
-        if num_dims not in (2, 3) or input_size != 2 * num_dims:
-            raise ValueError("num_dims must be 2 or 3 and input_size == 2*num_dims")
-        if hidden_size == 3 * num_dims:
-            raise ValueError("hidden_size == 3 * num_dims is not supported (the reference then builds layer_1 without its "
-                             "res Linear, locs.py:214-218)")
-        if not (0.0 <= float(dropout_prob) < 1.0):
-            raise ValueError("dropout_prob must lie in [0, 1)")
-        # nn.Dropout sits between the layers of out_mlp (locs.py:160-168).  In eval() it is the identity, which is what
-        # the kernels compute for any p; a train()-mode forward with p > 0 applies the two scale masks (_AetherStep.launch:
-        # drawn with bernoulli_, same distribution as nn.Dropout, not its random stream).  rollout() is an inference path:
-        # it raises in train() mode with p > 0 instead of silently skipping the masks.
-        self.dropout_prob = float(dropout_prob)
+        self._frame_init("Aether", 3 * num_dims, input_size, hidden_size, dropout_prob, num_dims)
         self.gnn = _GNN(input_size, hidden_size, dropout_prob, num_dims,
                         additional_features=num_dims)
-        self.num_dims = num_dims
-        self.hidden_size = hidden_size
-        # width the kernels run this model at: 64 (fused / streamed), or the next multiple of 64 above (csrc/wide.h)
-        self._kw = _kernel_width(hidden_size)
         self.field_net = _FieldNetwork(num_dims, 32, 16)
-        self._graphs = GraphCache()
-        self.flags = 0                    # _lib.FLAG_* bits passed to aether_forward
-        self.dp_group = None              # set by aether_amd.parallel.attach_data_parallel
         self.grad_as_view = True          # .grad tensors alias one flat buffer (see _AetherStep.backward)
-        self._last_ws = None
         self._train_ws, self._train_ws_token = None, None
-        self._wimg_key = None             # (workspace, parameter versions) whose split weight images the workspace holds
-        self._ws_key = None               # (workspace, shape, graph) of the last completed inference call
         self._gbuf = None
         self._gbuf2 = None
-        self._ws = None
         self._pstruct = None
-        self._plist = None
-        self._ws_bytes = {}
         self.to(device)
         if hidden_size != self._kw:
             # the engine of kernel width: same class, its parameters are the zero-padded images of this model's (kept out of
@@ -446,17 +153,8 @@ class Aether(nn.Module):
             self.__dict__["_engine_key"] = None
         self.params = self.__str__()
 
-    def __str__(self):
-        params = sum(int(np.prod(p.size())) for p in self.parameters() if p.requires_grad)
-        print("Network Size", params)
-        return str(params)
-
     # -- plumbing ------------------------------------------------------------------
     def _apply(self, fn, *a, **k):
-        self._pstruct = None              # parameter storage may move (.to / .cuda / .float)
-        self._plist = None
-        self._gbuf = None
-        self._gbuf2 = None
         eng = self.__dict__.get("_engine")
         if eng is not None:
             eng._apply(fn, *a, **k)
@@ -466,32 +164,23 @@ class Aether(nn.Module):
     def _sync_engine(self):
         """Copy this model's parameters into their places in the padded engine when any of them changed."""
         eng = self._engine
-        if self._plist is None:
-            self._plist = [p for _, p in self.named_parameters()]
-        key = tuple((p.data_ptr(), p._version) for p in self._plist)
+        plist = self._param_list()
+        key = tuple((p.data_ptr(), p._version) for p in plist)
         # Training: always (an optimizer step lies between two training forwards and torch's fused AdamW leaves the version
         # counters alone; inside a captured training step the copies have to be part of the graph), and the call after a
         # training forward as well.
-        train = torch.is_grad_enabled() and any(p.requires_grad for p in self._plist)
+        train = torch.is_grad_enabled() and any(p.requires_grad for p in plist)
         if self._engine_key != key or train:
             with torch.no_grad():
                 for (name, p), (_, ep) in zip(self.named_parameters(), eng.named_parameters()):
-                    for ss, ds in _pad_blocks(name, p.shape, self.hidden_size, self._kw):
-                        ep[ds].copy_(p[ss])
+                    place(ep, p, _pad_blocks(name, p.shape, self.hidden_size, self._kw))
             self.__dict__["_engine_key"] = None if train else key
         eng.flags = self.flags
         eng.train(self.training)
         return eng
 
-    def load_state_dict(self, *a, **k):
-        self._pstruct = None
-        self._plist = None
-        return super().load_state_dict(*a, **k)
-
     def _param_struct(self):
-        if self._plist is None:
-            self._plist = [p for _, p in self.named_parameters()]
-        key = tuple([p.data_ptr() for p in self._plist])
+        key = tuple([p.data_ptr() for p in self._param_list()])
         if self._pstruct is None or self._pstruct[0] != key:
             struct = _lib.params_struct(dict(self.named_parameters()))
             self._pstruct = (key, struct, C.byref(struct))
@@ -501,19 +190,8 @@ class Aether(nn.Module):
         self._param_struct()
         return self._pstruct[2]
 
-    def _workspace_bytes(self, n_nodes, n_edges, keep):
-        if self._kw != 64:
-            return _lib.load().aether_workspace_bytes_h(n_nodes, n_edges, self.num_dims, self._kw, 1 if keep else 0)
-        if keep:         # the training layout depends on a library option (outer_defer_max_edges): always ask
-            return _lib.load().aether_workspace_bytes(n_nodes, n_edges, self.num_dims, 1)
-        key = (n_nodes, n_edges)
-        nbytes = self._ws_bytes.get(key)
-        if nbytes is None:
-            nbytes = _lib.load().aether_workspace_bytes(n_nodes, n_edges, self.num_dims, 0)
-            if len(self._ws_bytes) > 64:
-                self._ws_bytes.clear()
-            self._ws_bytes[key] = nbytes
-        return nbytes
+    def _rollout_params(self, device):
+        return self._param_struct_ref(), None
 
     def _grad_buffers(self, second=False):
         """Flat fp32 gradient buffer + an AetherParams struct and per-parameter views into it.  ``second``: a
@@ -539,151 +217,36 @@ class Aether(nn.Module):
             setattr(self, slot, cur)
         return cur
 
-    def _workspace(self, nbytes, device):
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        return self._ws
-
-    def _weights_key(self, ws, n_nodes, n_edges):
-        """Identity of the split weight images a call leaves in `ws` (AETHER_FLAG_WEIGHTS_PREPARED): the buffer and the
-        version counters / addresses of all parameters (in-place updates bump the version, re-assignment the address)."""
-        if self._plist is None:
-            self._plist = [p for _, p in self.named_parameters()]
-        return (ws.data_ptr(), int(n_nodes), int(n_edges), tuple(p._version for p in self._plist),
-                tuple(p.data_ptr() for p in self._plist))
-
-    def _may_reuse_weight_images(self):
-        """Eagerly, the version check above is exact.  While a hipGraph is being captured the decision is baked into
-        the graph, so the conversion kernel is only left out in eval mode -- a captured INFERENCE graph, which has to
-        be re-captured when the weights change (as any graph whose kernels read prepared data)."""
-        return not (self.training and torch.cuda.is_current_stream_capturing())
-
-    def prepare_graph(self, edges, n_nodes):
-        """Build (or fetch) the receiver-sorted view for ``edges = [send, recv]``."""
-        send, recv = edges
-        return self._graphs.get(send.contiguous(), recv.contiguous(), n_nodes)
-
     # -- reference surface -----------------------------------------------------------
     def forward(self, h, x, edges, vel, edge_attr_orig, charges):
         """``h`` is ignored, as in the reference (aether.py:169-186)."""
-        if not x.is_cuda:
-            raise _lib.AetherHipError("aether_amd.Aether runs on an MI355X only; got a CPU tensor "
-                                      "(there is no CPU fallback)")
-        send, recv = edges
-        if send.dtype != torch.int64 or recv.dtype != torch.int64:
-            raise TypeError("edges must be int64 (torch.LongTensor), as in the reference")
-        n_nodes, D = x.shape
-        if D != self.num_dims or vel.shape != x.shape:
-            raise ValueError(f"x/vel must be [n_nodes, {self.num_dims}]")
-        E = send.numel()
-        if recv.numel() != E or edge_attr_orig.shape != (E, 2) or charges.numel() != n_nodes:
-            raise ValueError("edge index / edge_attr / charges shapes do not match")
+        send, recv, n_nodes, E = self._validate_forward(x, vel, edges, edge_attr_orig, charges)
         # the reference's forward is differentiable in x / vel / edge_attr_orig (aether.py:169-186): so is this one
         # (aether_backward_inputs); charges are an embedding index, no gradient flows to them there either
         wants_in = torch.is_grad_enabled() and (x.requires_grad or vel.requires_grad or edge_attr_orig.requires_grad)
         # nn.Dropout keys on the module's mode, not on autograd's: a train()-mode forward applies it even under no_grad
         drops = self.dropout_prob > 0.0 and self.training
-        f32 = lambda t: t.detach().to(torch.float32).contiguous()
-        f32g = (lambda t: t.to(torch.float32).contiguous() if t.requires_grad else f32(t)) if wants_in else f32
-        if self.hidden_size != self._kw:      # not a kernel width: the zero-padded engine computes it (same kernels)
-            eng = self._sync_engine()
-            if not (drops or wants_in or (torch.is_grad_enabled() and any(p.requires_grad for p in self._plist))):
+        f32g = _f32g if wants_in else _f32
+        narrow = self.hidden_size != self._kw      # not a kernel width: the zero-padded engine computes it (same kernels)
+        eng = self._sync_engine() if narrow else None
+        plist = self._param_list()
+        train = drops or wants_in or (torch.is_grad_enabled() and any(p.requires_grad for p in plist))
+        if narrow:
+            if not train:
                 with torch.no_grad():
                     return eng(h, x, edges, vel, edge_attr_orig, charges)
-            return _PaddedStep.apply(self, f32g(x), send, recv, f32g(vel), f32g(edge_attr_orig), f32(charges), *self._plist)
+            return _PaddedStep.apply(self, f32g(x), send, recv, f32g(vel), f32g(edge_attr_orig), _f32(charges), *plist)
         graph = self.prepare_graph((send, recv), n_nodes)
-        if self._plist is None:         # nn.Module.parameters() walks the module tree: 0.15 ms per call
-            self._plist = [p for _, p in self.named_parameters()]
-        train = drops or wants_in or (torch.is_grad_enabled() and any(p.requires_grad for p in self._plist))
         if not train:           # inference: no autograd node, no parameter list to marshal
-            return _AetherStep.launch(self, False, f32(x), f32(vel), f32(edge_attr_orig), f32(charges), graph, E)[0]
-        return _AetherStep.apply(self, f32g(x), f32g(vel), f32g(edge_attr_orig), f32(charges), graph, E,
-                                 *self._plist)
+            return self._step("aether_forward", self._param_struct_ref(), _f32(x), _f32(vel), _f32(charges), None,
+                              _f32(edge_attr_orig), graph, E, False)[0]
+        return _AetherStep.apply(self, f32g(x), f32g(vel), f32g(edge_attr_orig), _f32(charges), graph, E, *plist)
 
-    # -- device rollout ---------------------------------------------------------------
     @torch.no_grad()
     def rollout(self, x, vel, edges, charges, steps, dt=1.0):
-        """``steps`` autoregressive steps on the device (``aether_rollout``): positions
-        ``[steps, n_nodes, D]``.  x_{t+1} = self(x_t, v_t), v_{t+1} = (x_{t+1} - x_t) / dt, with
-        ``edge_attr = [q_i q_j, |x_i - x_j|]`` rebuilt inside the kernels every step
-        (experiments/lorentz/main.py:243-246); one kernel launch per step, no host-side gathers."""
-        if not x.is_cuda:
-            raise _lib.AetherHipError("aether_amd.Aether runs on an MI355X only; got a CPU tensor "
-                                      "(there is no CPU fallback)")
-        if self.dropout_prob > 0.0 and self.training:
-            raise RuntimeError("Aether.rollout is an inference path (no dropout masks): call .eval() first")
+        """``steps`` autoregressive steps on the device (``aether_rollout``): positions ``[steps, n_nodes, D]``, one
+        kernel launch per step, no host-side gathers (``FrameModule._rollout``)."""
         if self.hidden_size != self._kw:
+            self._require_gpu(x)
             return self._sync_engine().rollout(x, vel, edges, charges, steps, dt)
-        lib = _lib.load()
-        send, recv = edges
-        if send.dtype != torch.int64 or recv.dtype != torch.int64:
-            raise TypeError("edges must be int64 (torch.LongTensor), as in the reference")
-        n_nodes, D = x.shape
-        if D != self.num_dims or vel.shape != x.shape or charges.numel() != n_nodes:
-            raise ValueError(f"x/vel must be [n_nodes, {self.num_dims}], charges [n_nodes, 1]")
-        E = send.numel()
-        f32 = lambda t: t.detach().to(torch.float32).contiguous()
-        x, vel, charges = f32(x), f32(vel), f32(charges)
-        graph, ginfo = self.prepare_graph((send, recv), n_nodes)
-        ws_bytes = self._workspace_bytes(n_nodes, E, False)
-        ws = self._workspace(ws_bytes, x.device)
-        flags = self.flags & ~_lib.FLAG_KEEP_INTERMEDIATES
-        if self._kw != 64:
-            traj = torch.empty(int(steps), n_nodes, D, dtype=torch.float32, device=x.device)
-            if int(steps) > 0:
-                st = lib.aether_rollout_h(C.byref(self._param_struct()), D, self._kw, n_nodes, E, x.data_ptr(), vel.data_ptr(),
-                                          charges.data_ptr(), graph.data_ptr(), C.byref(ginfo), ws.data_ptr(), ws.numel(),
-                                          traj.data_ptr(), int(steps), float(dt), 0,
-                                          torch.cuda.current_stream(x.device).cuda_stream)
-                _lib.check(st, "aether_rollout_h")
-                self._last_ws = ws
-            return traj
-        fused = ginfo.n_groups > 0 and E > 0 and not (flags & _lib.FLAG_FORCE_STREAMED)
-        ws_key = (ws.data_ptr(), n_nodes, E, D, False, graph.data_ptr()) if fused else None
-        if ws_key is not None and self._ws_key == ws_key:
-            flags |= _lib.FLAG_WORKSPACE_REUSED
-        self._ws_key = None
-        wkey = self._weights_key(ws, n_nodes, E)
-        if fused and self._wimg_key == wkey and self._may_reuse_weight_images():
-            flags |= _lib.FLAG_WEIGHTS_PREPARED
-        self._wimg_key = None
-        traj = torch.empty(int(steps), n_nodes, D, dtype=torch.float32, device=x.device)
-        if int(steps) <= 0:
-            return traj
-        st = lib.aether_rollout(C.byref(self._param_struct()), D, n_nodes, E, x.data_ptr(), vel.data_ptr(),
-                                charges.data_ptr(), graph.data_ptr(), C.byref(ginfo), ws.data_ptr(), ws.numel(),
-                                traj.data_ptr(), int(steps), float(dt), flags,
-                                torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(st, "aether_rollout")
-        self._ws_key = ws_key
-        self._wimg_key = wkey
-        self._last_ws = ws
-        return traj
-
-    # -- test hook -------------------------------------------------------------------
-    def debug_fetch(self, name, n_nodes, n_edges, cols):
-        lib = _lib.load()
-        dev = next(self.parameters()).device
-        rows = n_edges if name.startswith("e") else n_nodes
-        dst = torch.empty(rows, cols, dtype=torch.float32, device=dev)
-        if self._kw == 64:
-            n = lib.aether_debug_fetch(name.encode(), self.num_dims, n_nodes, n_edges,
-                                       self._last_ws.data_ptr(), dst.data_ptr(),
-                                       torch.cuda.current_stream(dev).cuda_stream)
-        else:
-            n = lib.aether_debug_fetch_h(name.encode(), self.num_dims, self._kw, n_nodes, n_edges,
-                                         self._last_ws.data_ptr(), dst.data_ptr(),
-                                         torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(n, "aether_debug_fetch")
-        assert n == rows * cols, (n, rows, cols)
-        return dst
-
-    def graph_perm(self, edges, n_nodes):
-        lib = _lib.load()
-        g, _ = self.prepare_graph(edges, n_nodes)
-        E = edges[0].numel()
-        perm = torch.empty(E, dtype=torch.int32, device=edges[0].device)
-        _lib.check(lib.aether_graph_perm(g.data_ptr(), E, n_nodes, perm.data_ptr(),
-                                         torch.cuda.current_stream(perm.device).cuda_stream),
-                   "aether_graph_perm")
-        return perm.long()
+        return self._rollout(x, vel, edges, charges, steps, dt, reuse=True)

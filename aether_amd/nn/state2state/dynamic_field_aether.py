@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from ... import _lib
-from .aether import GraphCache, _GNN, _kernel_width, _pad_blocks
+from ._frame import FrameModule, _GNN, _f32, _f32g, _pad_blocks, cut, engine_shapes, field_slot_shapes, place
 
 
 class _AttentionalAggregation(nn.Module):
@@ -88,9 +88,10 @@ class _DynStep(torch.autograd.Function):
     def backward(ctx, grad_out):
         lib = _lib.load()
         module = ctx.module
-        x, vel, charges, (graph, ginfo), ws, n_edges, num_nodes = ctx.saved
+        x, vel, charges, graph, ws, n_edges, num_nodes = ctx.saved
         D, n_nodes = module.num_dims, x.shape[0]
         ps, fps = module._structs(x.device)
+        ps = C.byref(ps)
         names, offsets, total = module._grad_layout()
         flat = torch.zeros(total, dtype=torch.float32, device=x.device)        # one buffer, one memset
         kshapes = module._kernel_shapes()
@@ -102,17 +103,7 @@ class _DynStep(torch.autograd.Function):
         gfs = module._dyn_struct(kgrads)
         g = grad_out.to(torch.float32).contiguous()
         grad_field = torch.empty(n_nodes, D, dtype=torch.float32, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        kw = module._kw
-        if kw == 64:
-            st = lib.aether_backward_field(C.byref(ps), C.byref(gs), D, n_nodes, n_edges, x.data_ptr(), vel.data_ptr(),
-                                           charges.data_ptr(), graph.data_ptr(), C.byref(ginfo), ws.data_ptr(),
-                                           ws.numel(), g.data_ptr(), grad_field.data_ptr(), stream)
-        else:
-            st = lib.aether_backward_h(C.byref(ps), C.byref(gs), D, kw, n_nodes, n_edges, x.data_ptr(), vel.data_ptr(),
-                                       charges.data_ptr(), graph.data_ptr(), C.byref(ginfo), ws.data_ptr(),
-                                       ws.numel(), g.data_ptr(), grad_field.data_ptr(), stream)
-        _lib.check(st, "aether_backward_field")
+        module._backward("aether_backward_field", ps, C.byref(gs), x, vel, charges, graph, ws, n_edges, g, grad_field)
         n_graphs = n_nodes // num_nodes
         need = lib.aether_dynamic_field_backward_workspace_bytes(D, n_graphs)
         dws = torch.empty(need, dtype=torch.uint8, device=x.device)
@@ -121,26 +112,16 @@ class _DynStep(torch.autograd.Function):
         _lib.check(lib.aether_dynamic_field_backward_inputs(C.byref(fps), C.byref(gfs), D, n_graphs, num_nodes, x.data_ptr(),
                                                             vel.data_ptr(), charges.data_ptr(), grad_field.data_ptr(),
                                                             dws.data_ptr(), dws.numel(),
-                                                            gz.data_ptr() if gz is not None else None, stream),
+                                                            gz.data_ptr() if gz is not None else None,
+                                                            torch.cuda.current_stream(x.device).cuda_stream),
                    "aether_dynamic_field_backward_inputs")
         module.last_grad_field = grad_field
         gx = gv = gea = None
         if want_in:
             # gradients w.r.t. the inputs (dynamic_field_aether.py:79-100 is differentiable in them): the GNN / frame part
             # from what aether_backward_field left in the workspace, the part through the latent field from gz
-            (out_saved,) = ctx.saved_tensors
-            gx, gv = torch.empty_like(x), torch.empty_like(x)
-            if ctx.needs_input_grad[3]:
-                gea = torch.empty(n_edges, 2, dtype=torch.float32, device=x.device)
-            _lib.check(lib.aether_backward_inputs_h(C.byref(ps), D, kw, n_nodes, n_edges, x.data_ptr(), vel.data_ptr(),
-                                                    charges.data_ptr(), graph.data_ptr(), C.byref(ginfo), ws.data_ptr(),
-                                                    ws.numel(), out_saved.data_ptr(), g.data_ptr(), gx.data_ptr(), gv.data_ptr(),
-                                                    gea.data_ptr() if gea is not None else None, gz.data_ptr(), stream),
-                       "aether_backward_inputs")
-            if not ctx.needs_input_grad[1]:
-                gx = None
-            if not ctx.needs_input_grad[2]:
-                gv = None
+            gx, gv, gea = module._input_grads(ctx.needs_input_grad[1:4], ps, x, vel, charges, graph, ws, n_edges,
+                                              ctx.saved_tensors[0], g, gz)
         if module.dp_group is not None:            # one all-reduce of the flat gradient buffer (RCCL), then the mean
             import torch.distributed as dist
             dist.all_reduce(flat, group=module.dp_group)
@@ -150,62 +131,32 @@ class _DynStep(torch.autograd.Function):
         return (None, gx, gv, gea, None, None, None, None) + tuple(grads[n] if k else None for n, k in zip(names, need_g))
 
 
-class DynamicFieldAether(nn.Module):
+class DynamicFieldAether(FrameModule):
     """Drop-in for nn/state2state/dynamic_field_aether.py:51-100."""
+
+    WEIGHTS_PREPARED = False     # the padded copies of the GNN parameters are refreshed every call (_padded_gnn)
+    TRAIN_WS_PER_CALL = True     # (moving it to the cached training workspace changes its memory behaviour: DESIGN 4.15)
+    DROP_ON_APPLY = ("_glayout", "_plist", "_struct_cache")
+    DROP_ON_LOAD = ("_plist", "_struct_cache")
 
     def __init__(self, input_size, hidden_size, dropout_prob, num_dims, device="cuda"):
         super().__init__()
-        if not (1 <= hidden_size <= 4096):
-            raise ValueError("hidden_size must lie in [1, 4096] (experiments/lorentz/main.py:42-43)")
-        if num_dims not in (2, 3) or input_size != 2 * num_dims:
-            raise ValueError("num_dims must be 2 or 3 and input_size == 2*num_dims")
-        if hidden_size == 3 * num_dims:
-            raise ValueError("hidden_size == 3 * num_dims is not supported (the reference then builds layer_1 without its "
-                             "res Linear, locs.py:214-218)")
-        if not (0.0 <= float(dropout_prob) < 1.0):
-            raise ValueError("dropout_prob must lie in [0, 1)")
-        # (the runner passes 0.0, main.py:149; > 0: identity in eval(), the out MLP's two masks in train() -- as Aether)
-        self.dropout_prob = float(dropout_prob)
+        # (the runner passes dropout 0.0, main.py:149; > 0: identity in eval(), the out MLP's two masks in train() -- as Aether)
+        self._frame_init("DynamicFieldAether", 3 * num_dims, input_size, hidden_size, dropout_prob, num_dims)
         self.gnn = _GNN(input_size, hidden_size, dropout_prob, num_dims, additional_features=num_dims)
-        self.num_dims = num_dims
-        self.hidden_size = hidden_size
-        # width the kernels run the GNN at: 64 (fused / streamed), or the next multiple of 64 above (csrc/wide.h); a model of
-        # another width runs on zero-padded copies of its GNN parameters (exact: padded channels stay zero), as Aether does
-        self._kw = _kernel_width(hidden_size)
+        # a model whose width is not a kernel width runs on zero-padded copies of its GNN parameters (exact: padded
+        # channels stay zero), as Aether does
         self._kshapes = None
         self._padded = None
         self.field_net = _LatentFieldNetwork(num_dims, 32, 16)
-        self._graphs = GraphCache()
-        self.flags = 0
-        self.dp_group = None               # set by aether_amd.parallel.attach_data_parallel
-        self._ws = None
-        self._ws_key = None
-        self._plist = None
         self._struct_cache = None
         self._dummy = None
+        self._glayout = None
         self.to(device)
         self.params = self.__str__()
 
-    def __str__(self):
-        params = sum(int(np.prod(p.size())) for p in self.parameters() if p.requires_grad)
-        print("Network Size", params)
-        return str(params)
-
-    def _apply(self, fn, *a, **k):
-        self._glayout = None
-        self._plist = None                # parameter storage may move (.to / .cuda / .float)
-        self._struct_cache = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._plist = None
-        self._struct_cache = None
-        return super().load_state_dict(*a, **k)
-
     def _structs(self, device):
-        if self._plist is None:
-            self._plist = [p for _, p in self.named_parameters()]
-        key = (str(device),) + tuple([p.data_ptr() for p in self._plist])
+        key = (str(device),) + tuple([p.data_ptr() for p in self._param_list()])
         if self._struct_cache is not None and self._struct_cache[0] == key:
             return self._struct_cache[1], self._struct_cache[2]
         ps, fps = self._build_structs(device)
@@ -216,8 +167,8 @@ class DynamicFieldAether(nn.Module):
         sd = dict(self.named_parameters())
         D = self.num_dims
         # the built-in field net is bypassed; its slots of AetherParams point at readable scratch of the right size
-        dummy = {"field_net.net.0.weight": (32, 2 * D + 16), "field_net.net.0.bias": (32,), "field_net.net.2.weight": (32, 32),
-                 "field_net.net.2.bias": (32,), "field_net.net.4.weight": (D, 32), "field_net.net.4.bias": (D,)}
+        # (the class embedding's slot is the model's own)
+        dummy = {k: shape for k, shape in field_slot_shapes(D).items() if k.startswith("field_net.net.")}
         if self._dummy is None or next(iter(self._dummy.values())).device != device:
             self._dummy = {k: torch.zeros(*shape, device=device) for k, shape in dummy.items()}
         tensors = {k: v for k, v in sd.items()}
@@ -232,9 +183,7 @@ class DynamicFieldAether(nn.Module):
         if self._kshapes is None:
             shapes = {n: tuple(p.shape) for n, p in self.named_parameters()}
             if self.hidden_size != self._kw:
-                with torch.device("meta"):
-                    wide = _GNN(2 * self.num_dims, self._kw, 0.0, self.num_dims, additional_features=self.num_dims)
-                shapes.update({"gnn." + n: tuple(p.shape) for n, p in wide.named_parameters()})
+                shapes.update(engine_shapes(self.num_dims, self._kw))
             self._kshapes = shapes
         return self._kshapes
 
@@ -249,24 +198,15 @@ class DynamicFieldAether(nn.Module):
         with torch.no_grad():
             for n, p in self.named_parameters():
                 if n.startswith("gnn."):
-                    for ss, ds in _pad_blocks(n, p.shape, self.hidden_size, self._kw):
-                        self._padded[n][ds].copy_(p[ss])
+                    place(self._padded[n], p, _pad_blocks(n, p.shape, self.hidden_size, self._kw))
         return self._padded
 
     def _narrow_grads(self, kgrads):
         """Kernel-side gradients cut back to the parameters' shapes."""
         if self.hidden_size == self._kw:
             return kgrads
-        out = {}
-        for n, p in self.named_parameters():
-            g = kgrads[n]
-            if n.startswith("gnn."):
-                d = torch.empty_like(p)
-                for ss, ds in _pad_blocks(n, p.shape, self.hidden_size, self._kw):
-                    d[ss] = g[ds]
-                g = d
-            out[n] = g
-        return out
+        return {n: cut(torch.empty_like(p), kgrads[n], _pad_blocks(n, p.shape, self.hidden_size, self._kw))
+                if n.startswith("gnn.") else kgrads[n] for n, p in self.named_parameters()}
 
     _DYN_NAMES = ["summary_net.summary_net.gate_nn.0", "summary_net.summary_net.gate_nn.2", "summary_net.summary_net.nn.0",
                   "summary_net.summary_net.nn.2", "wrapper.linear_1", "wrapper.linear_2", "wrapper.linear_3",
@@ -275,7 +215,7 @@ class DynamicFieldAether(nn.Module):
 
     def _grad_layout(self):
         """(parameter names, offsets into one flat gradient buffer (64-float aligned), total floats)."""
-        if getattr(self, "_glayout", None) is None:
+        if self._glayout is None:
             names, offsets, total = [], [], 0
             ks = self._kernel_shapes()
             for n, p in self.named_parameters():
@@ -293,125 +233,45 @@ class DynamicFieldAether(nn.Module):
         ptrs.append(tensors["field_net.class_embedding.weight"].data_ptr())
         return _DynFieldParams(*ptrs)
 
-    def _launch(self, x, vel, ea, charges, graph, n_edges, num_nodes, train):
-        lib = _lib.load()
-        graph, ginfo = graph
-        n_nodes, D, E = x.shape[0], self.num_dims, n_edges
+    def _current_structs(self, device):
         if self.hidden_size != self._kw:
-            self._padded_gnn(x.device)      # refresh the kernel-width copies of the GNN parameters
-        kw = self._kw
-        ps, fps = self._structs(x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
+            self._padded_gnn(device)        # refresh the kernel-width copies of the GNN parameters
+        return self._structs(device)
+
+    def _rollout_params(self, device):
+        ps, fps = self._current_structs(device)
+        return C.byref(ps), C.byref(fps)
+
+    def _launch(self, x, vel, ea, charges, graph, n_edges, num_nodes, train):
+        n_nodes, D = x.shape[0], self.num_dims
+        ps, fps = self._current_structs(x.device)
         field = torch.empty(n_nodes, D, dtype=torch.float32, device=x.device)
-        _lib.check(lib.aether_dynamic_field(C.byref(fps), D, n_nodes // int(num_nodes), int(num_nodes), x.data_ptr(),
-                                            vel.data_ptr(), charges.data_ptr(), field.data_ptr(), stream),
+        _lib.check(_lib.load().aether_dynamic_field(C.byref(fps), D, n_nodes // int(num_nodes), int(num_nodes), x.data_ptr(),
+                                                    vel.data_ptr(), charges.data_ptr(), field.data_ptr(),
+                                                    torch.cuda.current_stream(x.device).cuda_stream),
                    "aether_dynamic_field")
-        ws_bytes = lib.aether_workspace_bytes_h(n_nodes, E, D, kw, 1 if train else 0)
-        flags = self.flags & ~_lib.FLAG_KEEP_INTERMEDIATES
-        if kw != 64:
-            flags &= ~(_lib.FLAG_FORCE_FUSED | _lib.FLAG_FORCE_STREAMED)
-        ws_key = None
-        if train:                           # the backward reads this forward's intermediates: one workspace per call
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-            flags |= _lib.FLAG_KEEP_INTERMEDIATES | (0 if self.flags & _lib.FLAG_KEEP_INTERMEDIATES else _lib.FLAG_BACKWARD_ONLY)
-            if self.dropout_prob > 0.0 and self.training:
-                # nn.Dropout after the two SiLUs of the out MLP (locs.py:163,166): scale masks into the training workspace
-                off = lib.aether_dropout_mask_offset_h(n_nodes, E, D, kw)
-                masks = ws[off:off + 2 * n_nodes * kw * 4].view(torch.float32).view(2, n_nodes, kw)
-                given = self.__dict__.get("_dropout_masks")          # tests: explicit masks [2, n_nodes, width]
-                if given is not None and given.shape[-1] != kw:      # a narrow model's masks: padded channels are zero anyway
-                    given = torch.nn.functional.pad(given, (0, kw - given.shape[-1]), value=1.0)
-                if given is not None:
-                    masks.copy_(given.to(device=x.device, dtype=torch.float32))
-                else:
-                    masks.bernoulli_(1.0 - self.dropout_prob).mul_(1.0 / (1.0 - self.dropout_prob))
-                flags |= _lib.FLAG_DROPOUT
-        else:
-            if self._ws is None or self._ws.numel() < ws_bytes or self._ws.device != x.device:
-                self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-            ws = self._ws
-            fused = ginfo.n_groups > 0 and E > 0 and not (flags & _lib.FLAG_FORCE_STREAMED)
-            ws_key = (ws.data_ptr(), n_nodes, E, D, graph.data_ptr()) if fused else None
-            if ws_key is not None and self._ws_key == ws_key:
-                flags |= _lib.FLAG_WORKSPACE_REUSED
-        self._ws_key = None
-        out = torch.empty_like(x)
-        if kw == 64:
-            st = lib.aether_forward_field(C.byref(ps), D, n_nodes, E, x.data_ptr(), vel.data_ptr(), charges.data_ptr(),
-                                          field.data_ptr(), ea.data_ptr(), graph.data_ptr(), C.byref(ginfo),
-                                          ws.data_ptr(), ws.numel(), out.data_ptr(), flags, stream)
-        else:       # hidden_size > 64: csrc/wide.h with the external field
-            st = lib.aether_forward_h(C.byref(ps), D, kw, n_nodes, E, x.data_ptr(), vel.data_ptr(), charges.data_ptr(),
-                                      field.data_ptr(), ea.data_ptr(), graph.data_ptr(), C.byref(ginfo),
-                                      ws.data_ptr(), ws.numel(), out.data_ptr(), flags, stream)
-        _lib.check(st, "aether_forward_field")
-        self._ws_key = ws_key
+        out, ws, _ = self._step("aether_forward_field", C.byref(ps), x, vel, charges, field, ea, graph, n_edges, train)
         self.last_field = field
         return out, field, ws
 
     @torch.no_grad()
     def rollout(self, x, vel, edges, charges, steps, dt=1.0, num_nodes=None):
         """``steps`` autoregressive steps on the device (``aether_rollout_dynamic_field``), the protocol of
-        ``aether_amd.rollout``: x_{t+1} = self(x_t, v_t), v_{t+1} = (x_{t+1} - x_t) / dt, edge attributes rebuilt in the
-        kernels, the latent field recomputed from the current state every step.  -> [steps, n_nodes, D]."""
-        if not x.is_cuda:
-            raise _lib.AetherHipError("aether_amd.DynamicFieldAether runs on an MI355X only; got a CPU tensor "
-                                      "(there is no CPU fallback)")
+        ``aether_amd.rollout`` (``FrameModule._rollout``); the latent field is recomputed from the current state every
+        step.  -> [steps, n_nodes, D]."""
+        self._require_gpu(x)
         if num_nodes is None:
             raise ValueError("num_nodes (objects per graph) is required, as in forward")
-        lib = _lib.load()
-        send, recv = edges
-        n_nodes, D = x.shape
-        E = send.numel()
-        if D != self.num_dims or vel.shape != x.shape or charges.numel() != n_nodes or n_nodes % int(num_nodes) != 0:
-            raise ValueError("x/vel must be [B * num_nodes, num_dims], charges [B * num_nodes, 1]")
-        f32 = lambda t: t.detach().to(torch.float32).contiguous()
-        x, vel, charges = f32(x), f32(vel), f32(charges)
-        graph, ginfo = self._graphs.get(send.contiguous(), recv.contiguous(), n_nodes)
-        if self.dropout_prob > 0.0 and self.training:
-            raise RuntimeError("DynamicFieldAether.rollout is an inference path (no dropout masks): call .eval() first")
-        if self.hidden_size != self._kw:
-            self._padded_gnn(x.device)
-        ps, fps = self._structs(x.device)
-        ws_bytes = lib.aether_workspace_bytes_h(n_nodes, E, D, self._kw, 0)
-        if self._ws is None or self._ws.numel() < ws_bytes or self._ws.device != x.device:
-            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-        self._ws_key = None
-        traj = torch.empty(int(steps), n_nodes, D, dtype=torch.float32, device=x.device)
-        if int(steps) <= 0:
-            return traj
-        field = torch.empty(n_nodes, D, dtype=torch.float32, device=x.device)
-        flags = self.flags & ~_lib.FLAG_KEEP_INTERMEDIATES
-        if self._kw != 64:
-            flags &= ~(_lib.FLAG_FORCE_FUSED | _lib.FLAG_FORCE_STREAMED)
-        st = lib.aether_rollout_dynamic_field_h(C.byref(ps), C.byref(fps), D, self._kw, n_nodes, E, int(num_nodes), x.data_ptr(),
-                                                vel.data_ptr(), charges.data_ptr(), graph.data_ptr(), C.byref(ginfo),
-                                                self._ws.data_ptr(), self._ws.numel(), field.data_ptr(), traj.data_ptr(),
-                                                int(steps), float(dt), flags,
-                                                torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(st, "aether_rollout_dynamic_field")
-        return traj
+        return self._rollout(x, vel, edges, charges, steps, dt, num_nodes=num_nodes)
 
     def forward(self, h, x, edges, vel, edge_attr_orig, charges, num_nodes):
         """``h`` is ignored, as in the reference (dynamic_field_aether.py:79-100)."""
-        if not x.is_cuda:
-            raise _lib.AetherHipError("aether_amd.DynamicFieldAether runs on an MI355X only; got a CPU tensor "
-                                      "(there is no CPU fallback)")
-        send, recv = edges
-        if send.dtype != torch.int64 or recv.dtype != torch.int64:
-            raise TypeError("edges must be int64 (torch.LongTensor), as in the reference")
-        n_nodes, D = x.shape
-        E = send.numel()
-        if D != self.num_dims or vel.shape != x.shape or n_nodes % int(num_nodes) != 0:
-            raise ValueError("x/vel must be [B * num_nodes, num_dims]")
-        if recv.numel() != E or edge_attr_orig.shape != (E, 2) or charges.numel() != n_nodes:
-            raise ValueError("edge index / edge_attr / charges shapes do not match")
+        send, recv, n_nodes, E = self._validate_forward(x, vel, edges, edge_attr_orig, charges, num_nodes)
         # differentiable in x / vel / edge_attr_orig, as the reference's forward (dynamic_field_aether.py:79-100)
         wants_in = torch.is_grad_enabled() and (x.requires_grad or vel.requires_grad or edge_attr_orig.requires_grad)
-        f32 = lambda t: t.detach().to(torch.float32).contiguous()
-        f32g = (lambda t: t.to(torch.float32).contiguous() if t.requires_grad else f32(t)) if wants_in else f32
-        x, vel, ea, charges = f32g(x), f32g(vel), f32g(edge_attr_orig), f32(charges)
-        graph = self._graphs.get(send.contiguous(), recv.contiguous(), n_nodes)
+        f32g = _f32g if wants_in else _f32
+        x, vel, ea, charges = f32g(x), f32g(vel), f32g(edge_attr_orig), _f32(charges)
+        graph = self.prepare_graph((send, recv), n_nodes)
         if wants_in or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             return _DynStep.apply(self, x, vel, ea, charges, graph, E, int(num_nodes), *self.parameters())
         with torch.no_grad():
