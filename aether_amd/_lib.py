@@ -238,6 +238,10 @@ SIGNATURES = {
                                                  C.c_int64, C.c_void_p]),
     "aether_egnn_grad_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "aether_egnn_workspace_offset": (C.c_int64, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
+    "aether_egnn_rollout_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
+    "aether_egnn_rollout": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64] +
+                            [C.c_void_p] * 6 + [C.POINTER(AetherGraphInfo), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
+                                                C.c_float, C.c_void_p]),
     "aether_clof_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int]),
     "aether_clof_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                       C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 +
@@ -249,6 +253,11 @@ SIGNATURES = {
     "aether_clof_grad_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "aether_clof_workspace_offset": (C.c_int64, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
                                                  C.c_int64]),
+    "aether_clof_rollout_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
+    "aether_clof_rollout": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                      C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 6 +
+                            [C.POINTER(AetherGraphInfo), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_float,
+                             C.c_void_p]),
     "aether_profile_enable": (C.c_int, [C.c_int]),
     "aether_profile_kernels": (C.c_int, []),
     "aether_profile_kernel_name": (C.c_char_p, [C.c_int]),

@@ -165,12 +165,14 @@ clof::ProW clof_pro_w(const float* const* params, int variant) {
 
 template <int H>
 int clof_forward_impl(const ClofCall& c, const float* const* params, const ClofLayout& Lo, bool keep, const float* hin,
-                      const float* x, const float* vel, const float* ea, char* ws, float* out, hipStream_t st) {
+                      const float* x, const float* vel, const float* ea, char* ws, float* out, hipStream_t st,
+                      bool images = true) {
     const int L = c.L, v = c.variant;
     const int64_t Nn = c.Nn, E = c.E;
     const size_t h = H;
     const WsFloats wp{ws, Nn, H, Lo.hs, Lo.xs, Lo.gh, Lo.gx};
-    for (int l = 0; l < L; ++l) clof_pack_layer(params, v, l, Lo, ws, H, st);
+    if (images)                       // a rollout packs them once, in front of its first step
+        for (int l = 0; l < L; ++l) clof_pack_layer(params, v, l, Lo, ws, H, st);
     const unsigned nb = (unsigned)((Nn + clof::NB - 1) / clof::NB);
     clof::k_clof_prep<H><<<dim3(nb), dim3(H), 0, st>>>(clof_layer_w(params, v, 0, Lo, ws, H), params[0], params[1], c.in_nf,
                                                         c.n_per, Nn, hin, x, wp.x(0), wp(Lo.cen), wp.h(0), wp(Lo.P));
@@ -397,4 +399,52 @@ int aether_clof_backward(const float* const* params, int n_params, int variant, 
     if (hidden == 64)
         return clof_backward_impl<64>(c, params, Lo, h, vel, edge_attr, (char*)workspace, grad_out, grad, st);
     return clof_backward_impl<128>(c, params, Lo, h, vel, edge_attr, (char*)workspace, grad_out, grad, st);
+}
+
+size_t aether_clof_rollout_workspace_bytes(int variant, int hidden, int n_layers, int in_node_nf, int64_t n_nodes,
+                                           int64_t n_edges) {
+    if (!clof_sizes_ok(variant, hidden, n_layers, in_node_nf) || n_nodes <= 0 || n_edges < 0) return 0;
+    return RolloutState(ClofLayout(variant, hidden, n_layers, in_node_nf, n_nodes, n_edges, false).total, n_nodes, n_edges)
+        .total;
+}
+
+extern "C++" {
+namespace {
+
+template <int H>
+int clof_rollout_impl(const ClofCall& c, const float* const* params, const ClofLayout& Lo, const RolloutState& R,
+                      const float* x0, const float* vel0, const float* charges, const int64_t* send,
+                      const int64_t* recv, char* ws, float* traj, int steps, float dt, hipStream_t st) {
+    for (int l = 0; l < c.L; ++l) clof_pack_layer(params, c.variant, l, Lo, ws, H, st);
+    return gnn_rollout(ws, R, c.Nn, c.E, x0, vel0, charges, send, recv, traj, steps, dt, st,
+                       [&](const float* h, const float* x, const float* vel, const float* ea, float* out) {
+                           return clof_forward_impl<H>(c, params, Lo, false, h, x, vel, ea, ws, out, st, false);
+                       });
+}
+
+}  // namespace
+}  // extern "C++"
+
+int aether_clof_rollout(const float* const* params, int n_params, int variant, int hidden, int n_layers, int in_node_nf,
+                        int flags, float coords_weight, int n_per_graph, int64_t n_nodes, int64_t n_edges, const float* x0,
+                        const float* vel0, const float* charges, const int64_t* send, const int64_t* recv,
+                        const void* graph, const AetherGraphInfo* info, void* workspace, size_t workspace_bytes,
+                        float* trajectory, int steps, float dt, void* stream) {
+    if (int rc = clof_check(params, n_params, variant, hidden, n_layers, in_node_nf, n_per_graph, n_nodes, n_edges, graph,
+                            info, "clof_rollout"))
+        return rc;
+    const ClofLayout Lo(variant, hidden, n_layers, in_node_nf, n_nodes, n_edges, false);
+    const RolloutState R(Lo.total, n_nodes, n_edges);
+    if (int rc = gnn_rollout_check("clof_rollout", in_node_nf, flags & AETHER_CLOF_KEEP,
+                                   !x0 || !vel0 || !charges || !workspace || (steps > 0 && !trajectory) ||
+                                       (n_edges > 0 && (!send || !recv)),
+                                   flags & ~CLOF_FLAGS, workspace_bytes, R.total))
+        return rc;
+    if (steps <= 0) return 0;
+    const ClofCall c = clof_call(variant, hidden, n_layers, in_node_nf, flags, coords_weight, n_per_graph, n_nodes, n_edges,
+                                 graph);
+    hipStream_t st = (hipStream_t)stream;
+    if (hidden == 64)
+        return clof_rollout_impl<64>(c, params, Lo, R, x0, vel0, charges, send, recv, (char*)workspace, trajectory, steps, dt, st);
+    return clof_rollout_impl<128>(c, params, Lo, R, x0, vel0, charges, send, recv, (char*)workspace, trajectory, steps, dt, st);
 }

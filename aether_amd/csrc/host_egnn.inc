@@ -117,16 +117,9 @@ egnn::FieldW egnn_field_w(const float* const* params, int L) {
     return f;
 }
 
+// transposed weight images, one launch per layer
 template <int H>
-int egnn_forward_impl(const EgnnCall& c, const float* const* params, const EgnnLayout& Lo, bool keep, const float* hin,
-                      const float* x, const float* vel, const float* ea, const float* charges, char* ws, float* out,
-                      hipStream_t st) {
-    const int L = c.L;
-    const int64_t Nn = c.Nn;
-    const size_t h = H;
-    const WsFloats wp{ws, Nn, H, Lo.hs, Lo.xs, Lo.gh, Lo.gx};
-    float* F = wp(Lo.F);
-    // transposed weight images, one launch per layer
+void egnn_weight_images(const float* const* params, int L, const EgnnLayout& Lo, char* ws, hipStream_t st) {
     for (int l = 0; l < L; ++l) {
         const egnn::LayerW W = egnn_layer_w(params, l, Lo, ws, H);
         egnn::WtJob J;
@@ -137,6 +130,19 @@ int egnn_forward_impl(const EgnnCall& c, const float* const* params, const EgnnL
         for (int q = 0; q < 6; ++q) { J.src[q] = P[srcs[q]]; J.dst[q] = const_cast<float*>(dsts[q]); J.cols[q] = cols[q]; }
         egnn::k_egnn_wt<H><<<dim3((unsigned)(((2 * H + 9) * H + 255) / 256), 6), dim3(256), 0, st>>>(J);
     }
+}
+
+// images: prepare the weight images first (a rollout prepares them once, in front of its first step)
+template <int H>
+int egnn_forward_impl(const EgnnCall& c, const float* const* params, const EgnnLayout& Lo, bool keep, const float* hin,
+                      const float* x, const float* vel, const float* ea, const float* charges, char* ws, float* out,
+                      hipStream_t st, bool images = true) {
+    const int L = c.L;
+    const int64_t Nn = c.Nn;
+    const size_t h = H;
+    const WsFloats wp{ws, Nn, H, Lo.hs, Lo.xs, Lo.gh, Lo.gx};
+    float* F = wp(Lo.F);
+    if (images) egnn_weight_images<H>(params, L, Lo, ws, st);
     egnn::k_egnn_prep<H><<<dim3((unsigned)Nn), dim3(H), 0, st>>>(egnn_field_w(params, L), params[0], params[1], c.in_nf, hin,
                                                                  x, vel, charges, F, wp.h(0));
     HIP_OK(hipMemcpyAsync(wp.x(0), x, (size_t)Nn * 3 * 4, hipMemcpyDeviceToDevice, st));
@@ -300,4 +306,47 @@ int aether_egnn_backward(const float* const* params, int n_params, int hidden, i
     if (hidden == 64)
         return egnn_backward_impl<64>(c, params, Lo, h, x, vel, edge_attr, charges, (char*)workspace, grad_out, grad, st);
     return egnn_backward_impl<128>(c, params, Lo, h, x, vel, edge_attr, charges, (char*)workspace, grad_out, grad, st);
+}
+
+size_t aether_egnn_rollout_workspace_bytes(int hidden, int n_layers, int in_node_nf, int64_t n_nodes, int64_t n_edges) {
+    if (!egnn_sizes_ok(hidden, n_layers, in_node_nf) || n_nodes <= 0 || n_edges < 0) return 0;
+    return RolloutState(EgnnLayout(hidden, n_layers, in_node_nf, n_nodes, n_edges, false).total, n_nodes, n_edges).total;
+}
+
+extern "C++" {
+namespace {
+
+template <int H>
+int egnn_rollout_impl(const EgnnCall& c, const float* const* params, const EgnnLayout& Lo, const RolloutState& R,
+                      const float* x0, const float* vel0, const float* charges, const int64_t* send,
+                      const int64_t* recv, char* ws, float* traj, int steps, float dt, hipStream_t st) {
+    egnn_weight_images<H>(params, c.L, Lo, ws, st);
+    return gnn_rollout(ws, R, c.Nn, c.E, x0, vel0, charges, send, recv, traj, steps, dt, st,
+                       [&](const float* h, const float* x, const float* vel, const float* ea, float* out) {
+                           return egnn_forward_impl<H>(c, params, Lo, false, h, x, vel, ea, charges, ws, out, st, false);
+                       });
+}
+
+}  // namespace
+}  // extern "C++"
+
+int aether_egnn_rollout(const float* const* params, int n_params, int hidden, int n_layers, int in_node_nf, int flags,
+                        int64_t n_nodes, int64_t n_edges, const float* x0, const float* vel0, const float* charges,
+                        const int64_t* send, const int64_t* recv, const void* graph, const AetherGraphInfo* info,
+                        void* workspace, size_t workspace_bytes, float* trajectory, int steps, float dt, void* stream) {
+    if (int rc = egnn_check(params, n_params, hidden, n_layers, in_node_nf, n_nodes, n_edges, graph, info, "egnn_rollout"))
+        return rc;
+    const EgnnLayout Lo(hidden, n_layers, in_node_nf, n_nodes, n_edges, false);
+    const RolloutState R(Lo.total, n_nodes, n_edges);
+    if (int rc = gnn_rollout_check("egnn_rollout", in_node_nf, flags & AETHER_EGNN_KEEP,
+                                   !x0 || !vel0 || !charges || !workspace || (steps > 0 && !trajectory) ||
+                                       (n_edges > 0 && (!send || !recv)),
+                                   flags & ~EGNN_FLAGS, workspace_bytes, R.total))
+        return rc;
+    if (steps <= 0) return 0;
+    const EgnnCall c = egnn_call(hidden, n_layers, in_node_nf, flags, n_nodes, n_edges, graph);
+    hipStream_t st = (hipStream_t)stream;
+    if (hidden == 64)
+        return egnn_rollout_impl<64>(c, params, Lo, R, x0, vel0, charges, send, recv, (char*)workspace, trajectory, steps, dt, st);
+    return egnn_rollout_impl<128>(c, params, Lo, R, x0, vel0, charges, send, recv, (char*)workspace, trajectory, steps, dt, st);
 }

@@ -130,5 +130,50 @@ int gnn_wgrad(gnn::WgJobs& T, int edge, int block, void (*part_kernel)(gnn::WgJo
     return AETHER_OK;
 }
 
+// State of a device rollout, behind the model's inference workspace (`base` bytes): vel[Nn][3], h[Nn] and edge_attr[E][2]
+// of the step about to run.  Positions need no buffer of their own: step t reads x0 (t = 0) or row t - 1 of the
+// trajectory and writes row t.
+struct RolloutState : FloatArena {
+    size_t vel, h, ea, total;
+    RolloutState(size_t base, int64_t Nn, int64_t E) {
+        off = align_up(base, 256);
+        vel = take((size_t)Nn * 3);
+        h = take((size_t)Nn);
+        ea = take((size_t)(E > 0 ? E : 1) * 2);
+        total = off;
+    }
+};
+
+// What a rollout entry checks beyond gnn_check: widths and flags a rollout cannot serve, pointers, workspace
+int gnn_rollout_check(const char* what, int in_nf, int keep_flag, bool any_null, int unknown_flags, size_t ws_bytes,
+                      size_t ws_need) {
+    if (in_nf != 1) return gnn_fail(AETHER_EINVAL, what, "in_node_nf must be 1 (h = |vel| is rebuilt every step)");
+    if (keep_flag) return gnn_fail(AETHER_EINVAL, what, "the keep-for-backward flag has no meaning in a rollout");
+    return gnn_entry_check(what, any_null, unknown_flags, ws_bytes, ws_need);
+}
+
+// The loop of aether_egnn_rollout / aether_clof_rollout: x_{t+1} = model(x_t, v_t), v_{t+1} = (x_{t+1} - x_t) / dt, the
+// step's h and edge_attr from k_gnn_rollout_state.  step(h, x, vel, edge_attr, out) launches the model's layers (weight
+// images already prepared by the caller).  Launches only: no allocation, no synchronisation, nothing read back.
+template <class Step>
+int gnn_rollout(char* ws, const RolloutState& R, int64_t Nn, int64_t E, const float* x0, const float* vel0,
+                const float* charges, const int64_t* send, const int64_t* recv, float* traj, int steps, float dt,
+                hipStream_t st, Step step) {
+    float *vel = reinterpret_cast<float*>(ws + R.vel), *h = reinterpret_cast<float*>(ws + R.h),
+          *ea = reinterpret_cast<float*>(ws + R.ea);
+    const dim3 grid((unsigned)(((E > Nn ? E : Nn) + 255) / 256)), block(256);
+    const size_t row = (size_t)Nn * 3;
+    for (int t = 0; t < steps; ++t) {
+        const float* x = t == 0 ? x0 : traj + (size_t)(t - 1) * row;
+        if (t == 0)
+            gnn::k_gnn_rollout_state<true><<<grid, block, 0, st>>>(Nn, E, x, nullptr, vel0, dt, charges, recv, send, vel, h, ea);
+        else
+            gnn::k_gnn_rollout_state<false><<<grid, block, 0, st>>>(Nn, E, x, t == 1 ? x0 : traj + (size_t)(t - 2) * row,
+                                                                     nullptr, dt, charges, recv, send, vel, h, ea);
+        if (int rc = step(h, x, vel, ea, traj + (size_t)t * row)) return rc;
+    }
+    return AETHER_OK;
+}
+
 }  // namespace
 }  // extern "C++"

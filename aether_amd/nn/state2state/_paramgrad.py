@@ -4,12 +4,13 @@ autograd function around them.
 
 A subclass supplies its constructor (argument checks and parameter holders, then ``_finish_init``), ``_inputs`` (validation;
 returns what ``_run`` takes), ``NAME`` / ``ENTRY`` / ``KEEP``, ``_sizes`` and, where some parameters do not reach the
-output, ``_dead``.  Its five library entries are ``ENTRY_forward``, ``_backward``, ``_workspace_bytes``, ``_grad_floats``
-and ``_workspace_offset`` (include/aether_hip.h); forward and backward take
+output, ``_dead``.  Its library entries are ``ENTRY_forward``, ``_backward``, ``_workspace_bytes``, ``_grad_floats``,
+``_workspace_offset``, ``_rollout`` and ``_rollout_workspace_bytes`` (include/aether_hip.h); forward and backward take
 
     params, n_params, *_sizes(), flags, *call, n_nodes, n_edges, h, x, vel, *extra, graph, info, workspace, ...
 
-where ``call`` (scalars of this call) and ``extra`` (tensors between vel and the graph) come from ``_inputs``.
+where ``call`` (scalars of this call) and ``extra`` (tensors between vel and the graph) come from ``_inputs``.  ``rollout``
+(the device rollout of metric 2) is shared: a subclass whose entry takes scalars of the call supplies ``_rollout_call``.
 """
 from __future__ import annotations
 
@@ -91,6 +92,7 @@ class ParamGradModule(nn.Module):
         self._gbuf = None
         self._gbuf2 = None
         self._ws = None
+        self._rollout_ws = None           # aether_*_rollout's workspace (inference workspace + the rollout's state)
         self._train_ws, self._train_ws_token = None, None
         self._last_ws = None
         self.to(self.device)
@@ -185,6 +187,49 @@ class ParamGradModule(nn.Module):
         if torch.is_grad_enabled() and any(p.requires_grad for p in plist):
             return _ParamGradStep.apply(self, h, x, vel, extra, call, graph, *plist)
         return self._launch(h, x, vel, extra, call, graph, train=False)[0]
+
+    def _rollout_call(self, n_total):
+        """Scalars of a rollout between the flags and n_nodes (``call`` of a forward), from ``rollout``'s further keyword
+        arguments."""
+        return ()
+
+    @torch.no_grad()
+    def rollout(self, x, vel, edges, charges, steps, dt=1.0, **call_kw):
+        """``steps`` autoregressive steps on the device -> positions [steps, n_nodes, 3]: x_{t+1} = self(|v_t|, x_t, v_t,
+        edge_attr_t), v_{t+1} = (x_{t+1} - x_t) / dt, ``edge_attr_t = [q_row q_col, |x_row - x_col|^2]`` rebuilt by the
+        library every step (experiments/lorentz/main.py:254-271); one call of ENTRY_rollout, weight images prepared once.
+        ``x`` and ``vel`` are not written."""
+        if self.in_node_nf != 1:
+            raise ValueError(f"{self.NAME}.rollout: in_node_nf must be 1 (h = |vel| is rebuilt every step)")
+        row, col = edges
+        n_nodes, E = x.shape[0], row.numel()
+        call = self._rollout_call(n_nodes, **call_kw)
+        if x.shape != (n_nodes, 3) or vel.shape != x.shape or n_nodes == 0:
+            raise ValueError("x / vel must be [n_nodes, 3]")
+        if col.numel() != E or charges.numel() != n_nodes:
+            raise ValueError("edge index / charges shapes do not match")
+        if row.dtype != torch.int64 or col.dtype != torch.int64:
+            raise TypeError("edges must be int64 (torch.LongTensor), as in the reference")
+        if not x.is_cuda:
+            raise _lib.AetherHipError(f"aether_amd {self.NAME} runs on an MI355X only; got a CPU tensor "
+                                      "(there is no CPU fallback)")
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+        x, vel, charges, row, col = f32(x), f32(vel), f32(charges), row.contiguous(), col.contiguous()
+        graph, ginfo = self.prepare_graph((row, col), n_nodes)
+        steps = int(steps)
+        traj = torch.empty(max(steps, 0), n_nodes, 3, dtype=torch.float32, device=x.device)
+        if steps <= 0:
+            return traj
+        nbytes = max(self._entry("rollout_workspace_bytes")(*self._sizes(), n_nodes, E), 256)
+        if self._rollout_ws is None or self._rollout_ws.numel() < nbytes or self._rollout_ws.device != x.device:
+            self._rollout_ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        ws = self._rollout_ws
+        st = self._entry("rollout")(self._ptrs(), len(self._param_list()), *self._sizes(), self._flags, *call, n_nodes, E,
+                                    x.data_ptr(), vel.data_ptr(), charges.data_ptr(), col.data_ptr(), row.data_ptr(),
+                                    graph.data_ptr(), C.byref(ginfo), ws.data_ptr(), ws.numel(), traj.data_ptr(), steps,
+                                    float(dt), torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(st, self.ENTRY + "_rollout")
+        return traj
 
     def _run_layers(self, h, x, vel, extra, call, graph):
         """The body of ``forward_layers`` (under torch.no_grad()): (out, [h_0 .. h_L], [x_0 .. x_L]) from a

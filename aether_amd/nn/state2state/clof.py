@@ -150,6 +150,14 @@ class _ClofBase(ParamGradModule):
         graph = self.prepare_graph((row, col), N)
         return f32(h), f32(x), f32(vel), (f32(edge_attr),), (self.coords_weight, n_per), graph
 
+    def _rollout_call(self, n_total, n_nodes=5):
+        """``rollout(x, vel, edges, charges, steps, dt=1.0, n_nodes=5)``: the forward's n_nodes.  The charges only form
+        the charge product the runner puts in edge_attr[:, 0] (the forward takes none)."""
+        n_per = int(n_nodes)
+        if n_per < 1 or n_total % n_per != 0:
+            raise ValueError(f"{self.NAME}: the node count {n_total} is not a multiple of n_nodes={n_nodes}")
+        return self.coords_weight, n_per
+
     # -- reference surface -----------------------------------------------------------
     def forward(self, h, x, edges, vel, edge_attr, node_attr=None, n_nodes=5):
         return self._run(*self._inputs(h, x, edges, vel, edge_attr, node_attr, n_nodes))

@@ -6,9 +6,13 @@ restates (oracle/aether_oracle.py::rollout): x_{t+1} = Aether(x_t, v_t), v_{t+1}
 with ``edge_attr = [q_i q_j, |x_i - x_j|]`` rebuilt from the current positions every step
 (experiments/lorentz/main.py:243-246).  Everything stays on the device; the edge index (and therefore
 the receiver-sorted graph view) is reused across steps.  ``rollout`` runs the loop inside the library
-(``aether_rollout``); ``rollout_stepwise`` is the loop of module calls it replaces.
+(``aether_rollout``); ``rollout_stepwise`` is the loop of module calls it replaces.  ``EGNN_vel_Aether`` and ``ClofNet*`` have
+the same ``rollout`` (``aether_egnn_rollout`` / ``aether_clof_rollout``) under the runner's preparation for them --
+``nodes = |vel|`` and the squared distance in ``edge_attr``; their loop of module calls is ``rollout_stepwise_gnn``.
 """
 from __future__ import annotations
+
+import inspect
 
 import torch
 
@@ -35,6 +39,28 @@ def rollout_stepwise(model, x, vel, edges, charges, steps: int, dt: float = 1.0)
         x = xn
         traj.append(x)
     return torch.stack(traj)
+
+
+@torch.no_grad()
+def rollout_stepwise_gnn(model, x, vel, edges, charges, steps: int, dt: float = 1.0, **fwd_kwargs):
+    """``rollout_stepwise`` for the drop-ins the Lorentz runner feeds ``nodes = |vel|`` and the SQUARED distance
+    (``EGNN_vel_Aether``, ``ClofNet*``; experiments/lorentz/main.py:254-271): the loop of module calls that their
+    ``rollout`` replaces, kept as its cross-check.  ``fwd_kwargs`` go to every forward (ClofNet's ``n_nodes``)."""
+    rows, cols = edges
+    q = charges.reshape(-1, 1)
+    qprod = q[rows] * q[cols]
+    takes_charges = "charges" in inspect.signature(model.forward).parameters       # ClofNet's forward takes none
+    traj = []
+    for _ in range(int(steps)):
+        dist2 = torch.sum((x[rows] - x[cols]) ** 2, 1).unsqueeze(1)
+        ea = torch.cat([qprod, dist2], 1)
+        h = torch.sqrt(torch.sum(vel ** 2, dim=1)).unsqueeze(1)
+        args = (h, x, edges, vel, ea) + ((charges,) if takes_charges else ())
+        xn = model(*args, **fwd_kwargs)
+        vel = (xn - x) / dt
+        x = xn
+        traj.append(x)
+    return torch.stack(traj) if traj else x.new_empty(0, *x.shape)
 
 
 def rollout_mse(pred, truth):

@@ -964,6 +964,29 @@ int64_t aether_egnn_grad_floats(int hidden, int n_layers, int in_node_nf);
  * (float[n_nodes][hidden]) / "x" (float[n_nodes][3]); layer n_layers is the model's last h / output x.  Tests. */
 int64_t aether_egnn_workspace_offset(const char* name, int layer, int hidden, int n_layers, int in_node_nf, int64_t n_nodes,
                                      int64_t n_edges);
+/*
+ * Autoregressive rollout of EGNN-Aether, all on the device: `steps` forward steps back to back,
+ *   x_{t+1} = EGNN_vel_Aether(|v_t|, x_t, v_t, edge_attr_t),  v_{t+1} = (x_{t+1} - x_t) / dt,
+ * with h = |v_t| (the runner's `nodes`, in_node_nf = 1) and edge_attr_t = [q_row q_col, |x_row - x_col|^2] rebuilt from
+ * the current positions by one state kernel per step (csrc/gnn_common.h: k_gnn_rollout_state) -- the runner's per-batch
+ * preparation, experiments/lorentz/main.py:254-259, under the protocol of the "20-step rollout MSE" metric (SURVEY.md
+ * 8d).  Replaces a Python loop of model calls with a gather, a norm and a concatenation per step; the transposed weight
+ * images, which aether_egnn_forward writes per call, are written once per rollout.  The charge product is written at
+ * step 0 only.
+ *   x0, vel0   : float[n_nodes][3], state at t = 0 (not modified);  charges : float[n_nodes]
+ *   send, recv : int64[n_edges], the index arrays graph was built from (send = edges[1], recv = edges[0])
+ *   trajectory : float[steps][n_nodes][3], positions x_1 .. x_steps (step t reads row t - 1 and writes row t)
+ *   workspace  : aether_egnn_rollout_workspace_bytes() bytes: the inference workspace of aether_egnn_forward, then vel,
+ *                h and edge_attr of the step about to run
+ *   flags      : AETHER_EGNN_NORM_DIFF, AETHER_EGNN_TANH.  AETHER_EGNN_KEEP and in_node_nf != 1 are errors
+ * steps <= 0 returns 0 and writes nothing.  Launches only (no allocation, no synchronisation, nothing read back):
+ * stream-ordered, deterministic; capture it in a hipGraph to replay a whole rollout with one launch.
+ */
+size_t aether_egnn_rollout_workspace_bytes(int hidden, int n_layers, int in_node_nf, int64_t n_nodes, int64_t n_edges);
+int aether_egnn_rollout(const float* const* params, int n_params, int hidden, int n_layers, int in_node_nf, int flags,
+                        int64_t n_nodes, int64_t n_edges, const float* x0, const float* vel0, const float* charges,
+                        const int64_t* send, const int64_t* recv, const void* graph, const AetherGraphInfo* info,
+                        void* workspace, size_t workspace_bytes, float* trajectory, int steps, float dt, void* stream);
 
 /*
  * ClofNet: replaces the forward of ClofNet / ClofNet_vel / ClofNet_vel_gbf (nn/state2state/clof/clof.py:86-101, 187-202,
@@ -1020,6 +1043,21 @@ int64_t aether_clof_grad_floats(int variant, int hidden, int n_layers, int in_no
  * layer's output.  Tests. */
 int64_t aether_clof_workspace_offset(const char* name, int layer, int variant, int hidden, int n_layers, int in_node_nf,
                                      int64_t n_nodes, int64_t n_edges);
+/*
+ * aether_egnn_rollout for the ClofNet models: x_{t+1} = ClofNet*(|v_t|, x_t, v_t, edge_attr_t, n_nodes = n_per_graph),
+ * v_{t+1} = (x_{t+1} - x_t) / dt, the runner's preparation of experiments/lorentz/main.py:266-271 done by the same state
+ * kernel; the packed weight images of aether_clof_forward are written once per rollout.  ClofNet's forward takes no
+ * charges: they are read here only for the charge product in edge_attr[:, 0].  Arguments as aether_egnn_rollout and
+ * aether_clof_forward; workspace aether_clof_rollout_workspace_bytes() bytes; AETHER_CLOF_KEEP and in_node_nf != 1 are
+ * errors.
+ */
+size_t aether_clof_rollout_workspace_bytes(int variant, int hidden, int n_layers, int in_node_nf, int64_t n_nodes,
+                                           int64_t n_edges);
+int aether_clof_rollout(const float* const* params, int n_params, int variant, int hidden, int n_layers, int in_node_nf,
+                        int flags, float coords_weight, int n_per_graph, int64_t n_nodes, int64_t n_edges, const float* x0,
+                        const float* vel0, const float* charges, const int64_t* send, const int64_t* recv,
+                        const void* graph, const AetherGraphInfo* info, void* workspace, size_t workspace_bytes,
+                        float* trajectory, int steps, float dt, void* stream);
 
 /*
  * A kernel cannot return a status.  The one bounded wait in the library -- a split-mode workgroup of the fused
