@@ -27,8 +27,8 @@ constexpr int FUSED_MAX_EDGES = 384;         // 24 tiles (N=20 fully connected: 
 constexpr int FUSED_MAX_TILES = FUSED_MAX_EDGES / 16;
 constexpr int LDU = 2 * H + 8;               // padded LDS row for the 128-wide update hidden
 
-// The edge MLP's two 64 x 64 contractions run as six bf16 MFMA terms on split operands (common.h, gemm_split); the
-// weight images (3 x 8 KB each instead of 18 KB of padded fp32) fit every variant since the layer-1 features of the
+// The edge MLP's two 64 x 64 contractions run as three fp16 MFMA terms on operands split into two fp16 pieces (common.h,
+// gemm_split); the weight images (2 x 8 KB each instead of 18 KB of padded fp32) fit every variant since the layer-1 features of the
 // 17-24 tile one are built two rounds at a time.
 template <int ROUNDS> constexpr bool fused_split_gemm() { return true; }
 constexpr int FUSED_WIMG = SPLIT_WIMG;                   // floats of a split image of a 64 x 64 matrix (16 KB)
@@ -75,7 +75,7 @@ template <int NW, int ROUNDS> struct FusedLds {          // offsets in floats
     static_assert(TOTAL * 4 <= 160 * 1024, "LDS budget");
 };
 
-// Split (3 x bf16) images of the edge-MLP weights in global memory, in the exact order the kernel keeps them in LDS
+// Split (2 x fp16) images of the edge-MLP weights in global memory, in the exact order the kernel keeps them in LDS
 // (stage_split4): per layer l = 1..4 image A (layer 1: W1 padded to K = 32, FUSED_WIMG / 2 floats; layers 2-4: W_e)
 // and image B (W2).  k_prepare_weights (aether_hip.hip) writes them once per weight version; k_fused copies them with LDS-DMA.
 // Round 4: the node phase's weights as split images too (its GEMMs moved from the fp32 MFMA to the matrix pipe): per layer
@@ -716,9 +716,13 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         const int mb2 = wave & 7;                         // step 2: rows 16*mb2.. of the 128
         const int mb3 = wave & 3, tn3 = (wave >> 2) & 1;  // steps 3, 4: rows 16*mb3.. of node tile tn3
         const bool act3 = wave < 8;                       // steps 2 - 4 / out MLP: waves 0-7
-        // step 4 with one node tile (split mode): waves 0-3 compute P_s, waves 4-7 P_r, tile 0
+        // One node tile (split mode, small groups): step 3 runs on waves 4-7, which own at most one edge tile per layer,
+        // so a two-tile wave (0-3) never asks for the W4 fragments nor carries them through its last tile; in step 4 waves
+        // 0-3 compute P_s and waves 4-7 P_r, all on tile 0.  Two node tiles: wave -> (mb3, tn3) in steps 3 and 4.
         const bool one_tile = n <= 16;
         const int tn4 = one_tile ? 0 : tn3;
+        const int tn3s = tn4;
+        const bool do3 = act3 && (one_tile ? wave >= 4 : 16 * tn3 < n);
         const bool do_s = act3 && (one_tile ? wave < 4 : true);
         const bool do_r = act3 && (one_tile ? wave >= 4 : true);
         // Every L2 load of the node phase is issued BEFORE the wave's last edge tile, so that the
@@ -749,7 +753,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             }
             // (round 4: fragments of the prepared fp16 x 2 images, fused_nimg_offset -- same bytes per weight as fp32)
             if (part == 1 && act3) load_split_frags<8, 2>(dbg.wimg + fused_nimg_offset(layer, 0), mb2, lane, w3h, w3l);
-            if ((part == 2 || part == 3) && act3 && 16 * tn3 < n) {
+            if ((part == 2 || part == 3) && do3) {
                 const f16x8* w = reinterpret_cast<const f16x8*>(dbg.wimg + fused_nimg_offset(layer, 1)) +
                                  __builtin_amdgcn_readfirstlane(mb3) * (4 * 64);
 #pragma unroll
@@ -966,22 +970,22 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         lds_barrier();       // u complete
         FUSED_STAMP(4 + 8 * (layer - 1) + 4);
 
-        // step 3: x = n + W4 u + b4: rows 16*mb3.. of node tile tn3
-        if (act3 && 16 * tn3 < n) {
+        // step 3: x = n + W4 u + b4: rows 16*mb3.. of node tile tn3s (one node tile: on waves 4-7)
+        if (do3) {
             const float* ubuf = smem + L::UBUF;
             f32x4 acc = ld4(b4 + 16 * mb3 + 4 * q);
 #pragma unroll
             for (int hk = 0; hk < 2; ++hk) {                   // k halves of 64 (each with its own range check): fewer live registers
                 f32x4 uv[4];
 #pragma unroll
-                for (int a = 0; a < 4; ++a) uv[a] = ld4(ubuf + (16 * tn3 + i) * LDU + 16 * (4 * hk + a) + 4 * q);
+                for (int a = 0; a < 4; ++a) uv[a] = ld4(ubuf + (16 * tn3s + i) * LDU + 16 * (4 * hk + a) + 4 * q);
                 const f16x8 wh2[2] = {w4h[2 * hk], w4h[2 * hk + 1]}, wl2[2] = {w4l[2 * hk], w4l[2 * hk + 1]};
                 acc = gemm_split_regs<2>(wh2, wl2, uv, acc);
             }
-            acc += ld4(nbuf + (16 * tn3 + i) * LDW + 16 * mb3 + 4 * q);
-            st4(xbuf + (16 * tn3 + i) * LDW + 16 * mb3 + 4 * q, acc);
-            if (keep && 16 * tn3 + i < n)
-                st4(dbg.x[layer] + (int64_t)(nb + 16 * tn3 + i) * H + 16 * mb3 + 4 * q, acc);
+            acc += ld4(nbuf + (16 * tn3s + i) * LDW + 16 * mb3 + 4 * q);
+            st4(xbuf + (16 * tn3s + i) * LDW + 16 * mb3 + 4 * q, acc);
+            if (keep && 16 * tn3s + i < n)
+                st4(dbg.x[layer] + (int64_t)(nb + 16 * tn3s + i) * H + 16 * mb3 + 4 * q, acc);
         }
         lds_barrier();
         FUSED_STAMP(4 + 8 * (layer - 1) + 5);
