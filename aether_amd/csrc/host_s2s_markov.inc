@@ -31,13 +31,15 @@ int s2s_markov_check(const AetherS2SMarkovParams* mp, int D, int h, int K, int s
 
 // Hard samples of the fused step: the sample, its lists / counts and the local frames are in the step's workspace (S2SStepLayout).
 // decode = false: the prior only (burn-in).  x_in [Nn][2D], h0 / c0 [E][R], uniform [E][K] -> x_out, h1, c1 (+ edges_out).
-int s2s_markov_step_impl(const S2SStepArgs& a, const AetherS2SMarkovParams* mp, const S2SStepLayout& L, char* ws,
-                         const float* x_in, const float* ext_field, const float* h0, const float* c0, const float* uniform,
-                         float* x_out, float* h1, float* c1, float* edges_out, bool decode, hipStream_t st) {
-    const int D = a.D, he = a.he, hd = a.hd, R = a.R, K = a.K, k0 = a.skip_first ? 1 : 0, ku = K - k0;
+int s2s_markov_step_impl(const S2SStepArgs& a, char* ws, const float* x_in, const float* ext_field, const float* h0,
+                         const float* c0, const float* uniform, float* x_out, float* h1, float* c1, float* edges_out,
+                         bool decode, hipStream_t st) {
+    const int D = a.D, hd = a.hd, K = a.K, k0 = a.skip_first ? 1 : 0, ku = K - k0;
     const int64_t Nn = a.Nn, E = a.E;
     const S2SDims d(D);
-    const S2SPlanLayout P(D, he, hd, K, R, a.prior_layers, a.ph, ku);
+    const AetherS2SMarkovParams* mp = a.mp;
+    const S2SPlanLayout& P = a.P;
+    const S2SStepLayout& L = a.L;
     auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto pl = [&](size_t off) { return reinterpret_cast<const float*>(a.plan + off); };
     auto im = [&](size_t off) { return off ? reinterpret_cast<const void*>(a.plan + off) : nullptr; };
@@ -69,15 +71,7 @@ int s2s_markov_step_impl(const S2SStepArgs& a, const AetherS2SMarkovParams* mp, 
     }
     if (int rc = s2s_launch_jobs(T, st)) return rc;
     k_s2s_markov_agg<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(M, a.order, a.rowptr, edges, K, k0, aug, hd);
-    auto one = [&](S2SJob J) { T.n = 0; T.j[T.n++] = J; return s2s_launch_jobs(T, st); };
-    { S2SJob J = s2s_job(2, mp->out0_w, hd, mp->out0_b, aug, hd, wp(L.o1), hd, hd, hd, Nn); J.Wimg = im(P.i_out0);
-      if (int rc = one(J)) return rc; }
-    { S2SJob J = s2s_job(2, mp->out3_w, hd, mp->out3_b, wp(L.o1), hd, wp(L.o2), hd, hd, hd, Nn); J.Wimg = im(P.i_out3);
-      if (int rc = one(J)) return rc; }
-    const dim3 nb4((unsigned)((Nn + 3) / 4));
-    if (D == 2) k_s2s_out_globalize<2><<<nb4, dim3(256), 0, st>>>(wp(L.o2), mp->out6_w, mp->out6_b, hd, x_in, wp(L.Rinv), x_out, Nn);
-    else k_s2s_out_globalize<3><<<nb4, dim3(256), 0, st>>>(wp(L.o2), mp->out6_w, mp->out6_b, hd, x_in, wp(L.Rinv), x_out, Nn);
-    return AETHER_OK;
+    return s2s_out_tail(a, ws, mp, aug, x_in, x_out, st);
 }
 }  // namespace
 
@@ -110,13 +104,11 @@ int aether_s2s_markov_decoder_step(const AetherS2SMarkovParams* p, int num_dims,
     // the zero-padded rows the dense layers read.  (Every node's origin edge has an Euler angle on its branch cut, +-pi by one
     // rounding; these kernels land where the reference's fp32 evaluation does, tests/test_gpu_seq2seq.py localizer tests.)
     HIP_OK(hipMemsetAsync(counts, 0, 64 * sizeof(int), st));
-    if (D == 2) {
-        k_s2s_aug_nodes<2><<<blocks(Nn), dim3(256), 0, st>>>(nullptr, wp(L.rel), wp(L.Rinv), Nn, inputs, field, wp(L.ext));
-        if (E > 0) k_s2s_aug_edges<2><<<blocks(E), dim3(256), 0, st>>>(wp(L.ext), send, recv, wp(L.rel), 1, wp(L.ea), wp(L.epos), E);
-    } else {
-        k_s2s_aug_nodes<3><<<blocks(Nn), dim3(256), 0, st>>>(nullptr, wp(L.rel), wp(L.Rinv), Nn, inputs, field, wp(L.ext));
-        if (E > 0) k_s2s_aug_edges<3><<<blocks(E), dim3(256), 0, st>>>(wp(L.ext), send, recv, wp(L.rel), 1, wp(L.ea), wp(L.epos), E);
-    }
+    dispatch_dim(D, [&](auto DD) {
+        constexpr int Dc = decltype(DD)::value;
+        k_s2s_aug_nodes<Dc><<<blocks(Nn), dim3(256), 0, st>>>(nullptr, wp(L.rel), wp(L.Rinv), Nn, inputs, field, wp(L.ext));
+        if (E > 0) k_s2s_aug_edges<Dc><<<blocks(E), dim3(256), 0, st>>>(wp(L.ext), send, recv, wp(L.rel), 1, wp(L.ea), wp(L.epos), E);
+    });
     k_s2s_pad_rows<<<blocks(Nn * d.RFp), dim3(256), 0, st>>>(wp(L.rel), d.RF, d.RF, wp(L.relp), d.RFp, Nn);
     if (E > 0) k_s2s_pad_rows<<<blocks(E * d.EAp), dim3(256), 0, st>>>(wp(L.ea), d.EA, d.EA, wp(L.eap), d.EAp, E);
     // ---- padded lin1 / res1 and lin2's bias per type (the plan's preparation, per call here)
@@ -142,9 +134,10 @@ int aether_s2s_markov_decoder_step(const AetherS2SMarkovParams* p, int num_dims,
     k_s2s_markov_agg<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(wp(L.M), order, rowptr, nullptr, K, k0, wp(L.aug), h);
     if (s2s_linear(2, p->out0_w, h, p->out0_b, wp(L.aug), wp(L.o1), h, h, Nn, h, nullptr, 0, 0, st)) return AETHER_EINVAL;
     if (s2s_linear(2, p->out3_w, h, p->out3_b, wp(L.o1), wp(L.o2), h, h, Nn, h, nullptr, 0, 0, st)) return AETHER_EINVAL;
-    const dim3 nb4((unsigned)((Nn + 3) / 4));
-    if (D == 2) k_s2s_out_globalize<2><<<nb4, dim3(256), 0, st>>>(wp(L.o2), p->out6_w, p->out6_b, h, inputs, wp(L.Rinv), outputs, Nn);
-    else k_s2s_out_globalize<3><<<nb4, dim3(256), 0, st>>>(wp(L.o2), p->out6_w, p->out6_b, h, inputs, wp(L.Rinv), outputs, Nn);
+    dispatch_dim(D, [&](auto DD) {
+        k_s2s_out_globalize<decltype(DD)::value><<<dim3((unsigned)((Nn + 3) / 4)), dim3(256), 0, st>>>(
+            wp(L.o2), p->out6_w, p->out6_b, h, inputs, wp(L.Rinv), outputs, Nn);
+    });
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }
@@ -152,11 +145,8 @@ int aether_s2s_markov_decoder_step(const AetherS2SMarkovParams* p, int num_dims,
 size_t aether_s2s_markov_plan_bytes(int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
                                     int prior_hidden, int num_edge_types, int skip_first) {
     const int ku = num_edge_types - (skip_first ? 1 : 0);
-    if ((num_dims != 2 && num_dims != 3) || encoder_hidden < 128 || encoder_hidden % 128 != 0 || decoder_hidden < 32 ||
-        decoder_hidden % 32 != 0 || rnn_hidden < 16 || rnn_hidden % 16 != 0 || num_edge_types < 1 || num_edge_types > 4 ||
-        ku < 1 || prior_layers < 1 || prior_layers > 4)
-        return 0;
-    return S2SPlanLayout(num_dims, encoder_hidden, decoder_hidden, num_edge_types, rnn_hidden, prior_layers, prior_hidden, ku).total;
+    return ku < 1 ? 0 : s2s_plan_size(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden,
+                                      num_edge_types, ku);
 }
 
 int aether_s2s_markov_plan_build(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp,
@@ -165,12 +155,10 @@ int aether_s2s_markov_plan_build(const AetherS2SFieldParams* fp, const AetherS2S
                                  void* plan, size_t plan_bytes, void* stream) {
     if (!pp || !plan) return fail(AETHER_EINVAL, "s2s_markov_plan_build: null pointer");
     if (int rc = s2s_markov_check(mp, num_dims, decoder_hidden, num_edge_types, skip_first)) return rc;
-    const size_t need = aether_s2s_markov_plan_bytes(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers,
-                                                     prior_hidden, num_edge_types, skip_first);
-    if (need == 0) return fail(AETHER_EINVAL, "s2s_markov_plan_build: bad sizes");
-    if (plan_bytes < need || ((size_t)plan & 255))
-        return fail(AETHER_ESPACE, "s2s_markov_plan_build: plan buffer too small or not 256-byte aligned");
     const int D = num_dims, he = encoder_hidden, hd = decoder_hidden, K = num_edge_types, ku = K - (skip_first ? 1 : 0);
+    if (int rc = s2s_plan_buffer_check("s2s_markov_plan_build",
+                                       s2s_plan_size(D, he, hd, rnn_hidden, prior_layers, prior_hidden, K, ku), plan, plan_bytes))
+        return rc;
     const S2SDims d(D);
     const S2SPlanLayout P(D, he, hd, K, rnn_hidden, prior_layers, prior_hidden, ku);
     hipStream_t st = (hipStream_t)stream;
@@ -181,12 +169,8 @@ int aether_s2s_markov_plan_build(const AetherS2SFieldParams* fp, const AetherS2S
     k_s2s_pad_rows<<<blocks((int64_t)hd * d.EAp), dim3(256), 0, st>>>(mp->lin1_w, d.EA, d.EA, fl(P.m_l1p), d.EAp, hd);
     k_s2s_pad_rows<<<blocks((int64_t)hd * d.RFp), dim3(256), 0, st>>>(mp->res1_w, d.RF, d.RF, fl(P.m_r1p), d.RFp, hd);
     k_s2s_markov_bias<<<blocks((int64_t)ku * hd), dim3(256), 0, st>>>(mp->lin2_b, ku, hd, fl(P.m_b2));
-    auto image = [&](size_t off, const float* W, int M, int Kk, int ldw) {
-        if (off) k_s2s_gemm_image<<<blocks((int64_t)M * (Kk / 8)), dim3(256), 0, st>>>(W, M, Kk, ldw, reinterpret_cast<f16x8*>(base + off), 0);
-    };
-    image(P.i_out0, mp->out0_w, hd, hd, hd);
-    image(P.i_out3, mp->out3_w, hd, hd, hd);
-    for (int k = 0; k < ku; ++k) image(P.m_i_l2[k], mp->lin2_w + (size_t)k * hd, hd, hd, ku * hd);    // type k's rows c Ku + k
+    s2s_out_images(base, st, P, mp->out0_w, mp->out3_w, hd);
+    for (int k = 0; k < ku; ++k) s2s_image(base, st, P.m_i_l2[k], mp->lin2_w + (size_t)k * hd, hd, hd, ku * hd);    // type k's rows c Ku + k
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }
@@ -198,23 +182,14 @@ int aether_s2s_markov_step(const AetherS2SFieldParams* fp, const AetherS2SPriorP
                            const int64_t* order, const int64_t* rowptr, const float* inputs, const float* ext_field,
                            const float* h0, const float* c0, const float* uniform, void* workspace, size_t workspace_bytes,
                            float* outputs, float* h1, float* c1, float* edges_out, void* stream) {
-    if (int rc = s2s_markov_check(mp, num_dims, decoder_hidden, num_edge_types, skip_first)) return rc;
-    // (s2s_step_check only tests the decoder pointer for null; the Markov params were checked above)
-    if (int rc = s2s_step_check(fp, pp, reinterpret_cast<const AetherS2SDecoderParams*>(mp), plan, num_dims, encoder_hidden,
-                                decoder_hidden, rnn_hidden, prior_layers, prior_hidden, num_edge_types, num_vars, n_nodes,
-                                n_edges, ext_field == nullptr)) return rc;
-    if (!send || !recv || !order || !rowptr || !inputs || !h0 || !c0 || !uniform || !workspace || !outputs || !h1 || !c1)
-        return fail(AETHER_EINVAL, "s2s_markov_step: null pointer");
-    if (!(tau > 0.0f)) return fail(AETHER_EINVAL, "s2s_markov_step: tau must be positive");
-    const S2SStepLayout L(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_hidden, num_edge_types, n_nodes, n_edges);
-    if (workspace_bytes < L.total) return fail(AETHER_ESPACE, "s2s_markov_step: workspace too small");
-    const S2SStepArgs a{fp, pp, nullptr, (const char*)plan, num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers,
-                        prior_hidden, num_edge_types, skip_first, polar, num_vars, n_nodes, n_edges, send, recv, order, rowptr, tau,
-                        fp != nullptr};
-    if (int rc = s2s_markov_step_impl(a, mp, L, (char*)workspace, inputs, ext_field, h0, c0, uniform, outputs, h1, c1, edges_out,
-                                      true, (hipStream_t)stream)) return rc;
-    HIP_OK(hipGetLastError());
-    return AETHER_OK;
+    const S2SSizes z{num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden, num_edge_types, skip_first,
+                     polar, num_vars, tau, n_nodes, n_edges};
+    if (int rc = s2s_entry_check("s2s_markov_step", true, fp, pp, nullptr, mp, plan, z, ext_field == nullptr,
+                                 send && recv && order && rowptr && inputs && h0 && c0 && uniform && workspace && outputs && h1 && c1,
+                                 0, 1)) return rc;
+    return s2s_run_step("s2s_markov_step", s2s_step_args(fp, pp, nullptr, mp, plan, z, send, recv, order, rowptr), workspace,
+                        workspace_bytes, {inputs, nullptr, h0, c0}, ext_field, uniform, {outputs, nullptr, h1, c1}, edges_out,
+                        stream);
 }
 
 int aether_s2s_markov_rollout(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp, const AetherS2SMarkovParams* mp,
@@ -224,45 +199,13 @@ int aether_s2s_markov_rollout(const AetherS2SFieldParams* fp, const AetherS2SPri
                               const int64_t* order, const int64_t* rowptr, int burn_in_steps, const float* burn_in, int steps,
                               const float* inputs, float* h, float* c, const float* uniform, void* workspace,
                               size_t workspace_bytes, float* predictions, float* edges_out, void* stream) {
-    if (int rc = s2s_markov_check(mp, num_dims, decoder_hidden, num_edge_types, skip_first)) return rc;
-    if (int rc = s2s_step_check(fp, pp, reinterpret_cast<const AetherS2SDecoderParams*>(mp), plan, num_dims, encoder_hidden,
-                                decoder_hidden, rnn_hidden, prior_layers, prior_hidden, num_edge_types, num_vars, n_nodes,
-                                n_edges, true)) return rc;
-    if (!send || !recv || !order || !rowptr || !inputs || !h || !c || !uniform || !workspace || (steps > 0 && !predictions) ||
-        (burn_in_steps > 0 && !burn_in))
-        return fail(AETHER_EINVAL, "s2s_markov_rollout: null pointer");
-    if (steps < 0 || burn_in_steps < 0 || steps + burn_in_steps == 0) return fail(AETHER_EINVAL, "s2s_markov_rollout: no steps");
-    if (!(tau > 0.0f)) return fail(AETHER_EINVAL, "s2s_markov_rollout: tau must be positive");
-    const S2SStepLayout L(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_hidden, num_edge_types, n_nodes, n_edges);
-    if (workspace_bytes < L.total) return fail(AETHER_ESPACE, "s2s_markov_rollout: workspace too small");
-    const S2SStepArgs a{fp, pp, nullptr, (const char*)plan, num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers,
-                        prior_hidden, num_edge_types, skip_first, polar, num_vars, n_nodes, n_edges, send, recv, order, rowptr, tau,
-                        fp != nullptr};
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    const size_t rbytes = (size_t)n_edges * rnn_hidden * 4;
-    const size_t ustep = (size_t)n_edges * num_edge_types, xstep = (size_t)n_nodes * 2 * num_dims;
-    // prior state ping-pong inside the workspace; the caller's h / c are read first and written last
-    float* hcur = wp(L.ha); float* hnext = wp(L.hb);
-    float* ccur = wp(L.ca); float* cnext = wp(L.cb);
-    HIP_OK(hipMemcpyAsync(hcur, h, rbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(ccur, c, rbytes, hipMemcpyDeviceToDevice, st));
-    const int total = burn_in_steps + steps;
-    const float* xcur = burn_in_steps > 0 ? burn_in : inputs;
-    for (int t = 0; t < total; ++t) {
-        const bool teacher = t < burn_in_steps;                       // the prior only: the prediction would be discarded
-        float* xout = teacher ? nullptr : predictions + (size_t)(t - burn_in_steps) * xstep;
-        float* eout = (!teacher && edges_out) ? edges_out + (size_t)(t - burn_in_steps) * ustep : nullptr;
-        if (int rc = s2s_markov_step_impl(a, mp, L, ws, xcur, nullptr, hcur, ccur, uniform + (size_t)t * ustep, xout, hnext, cnext,
-                                          eout, !teacher, st)) return rc;
-        std::swap(hcur, hnext); std::swap(ccur, cnext);
-        if (t + 1 < burn_in_steps) xcur = burn_in + (size_t)(t + 1) * xstep;
-        else if (t + 1 == burn_in_steps) xcur = inputs;
-        else xcur = xout;
-    }
-    HIP_OK(hipMemcpyAsync(h, hcur, rbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(c, ccur, rbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipGetLastError());
-    return AETHER_OK;
+    const S2SSizes z{num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden, num_edge_types, skip_first,
+                     polar, num_vars, tau, n_nodes, n_edges};
+    if (int rc = s2s_entry_check("s2s_markov_rollout", true, fp, pp, nullptr, mp, plan, z, true,
+                                 send && recv && order && rowptr && inputs && h && c && uniform && workspace &&
+                                     (steps <= 0 || predictions) && (burn_in_steps <= 0 || burn_in),
+                                 burn_in_steps, steps)) return rc;
+    return s2s_run_rollout("s2s_markov_rollout", s2s_step_args(fp, pp, nullptr, mp, plan, z, send, recv, order, rowptr),
+                           workspace, workspace_bytes, burn_in_steps, burn_in, steps, inputs, nullptr, h, c, uniform,
+                           predictions, edges_out, stream);
 }

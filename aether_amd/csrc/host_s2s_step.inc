@@ -3,6 +3,12 @@
 
 namespace {
 
+int s2s_fail(int code, const char* what, const char* why) {
+    char msg[128];
+    snprintf(msg, sizeof(msg), "%s: %s", what, why);
+    return fail(code, msg);
+}
+
 struct S2SDims {
     int D, O, NF, RF, RFp, EA, EAp, EP;
     explicit S2SDims(int D_) : D(D_) {
@@ -200,15 +206,38 @@ S2SJob s2s_job(int act, const float* W, int ldw, const float* b, const float* X,
     return J;
 }
 
-struct S2SStepArgs {
-    const AetherS2SFieldParams* fp; const AetherS2SPriorParams* pp; const AetherS2SDecoderParams* dp;
-    const char* plan;
+// The model's sizes and scalar options, as the step / rollout entries receive them
+struct S2SSizes {
     int D, he, hd, R, prior_layers, ph, K, skip_first, polar, num_vars;
-    int64_t Nn, E;
-    const int64_t *send, *recv, *order, *rowptr;
     float tau;
-    bool field_images;         // the plan was built with the field net's parameters (images of its two hidden layers)
+    int64_t Nn, E;
 };
+
+// Everything a step reads besides its state: made once per entry call (s2s_step_args).  Exactly one of dp (recurrent
+// decoder) and mp (Markov decoder) is set; the plan's layout P is the one of that decoder.
+struct S2SStepArgs : S2SSizes {
+    const AetherS2SFieldParams* fp; const AetherS2SPriorParams* pp; const AetherS2SDecoderParams* dp;
+    const AetherS2SMarkovParams* mp;
+    const char* plan;
+    const int64_t *send, *recv, *order, *rowptr;
+    bool field_images;         // the plan was built with the field net's parameters (images of its two hidden layers)
+    S2SPlanLayout P;
+    S2SStepLayout L;
+};
+
+// The state a step reads and the one it writes: x [Nn][2D], dh [Nn][hd] (null with the Markov decoder, which has none),
+// h / c [E][R]
+struct S2SStateIn { const float *x, *dh, *h, *c; };
+struct S2SStateOut { float *x, *dh, *h, *c; };
+
+extern "C++" {                 // (templates: the including block has C linkage)
+// f(std::integral_constant<int, D>) for the run-time num_dims (2 or 3): picks a kernel's template argument, e.g.
+//   dispatch_dim(D, [&](auto DD) { k<decltype(DD)::value><<<...>>>(...); })      (as dispatch_bools, host_gnn_common.inc)
+template <class F>
+void dispatch_dim(int D, F&& f) {
+    if (D == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 3>{});
+}
 
 // The half of the step both decoders share -- field query -> local frames -> prior step -> hard Gumbel sample
 // (aether.py:86-90, :384-410, :92-98) -- up to the per-type edge lists.  x_in [Nn][2D], h0 / c0 [E][R], uniform [E][K] ->
@@ -216,7 +245,6 @@ struct S2SStepArgs {
 // sample, the burn-in of the Markov rollout).  The decoder rides along in two launches: first_jobs(T) adds its jobs to the
 // field query's first layer (flushing T itself when it fills up), res1_jobs(T) to the prior's res1 layer, whose launch
 // holds only that job otherwise.  P: the plan's layout (recurrent or Markov, S2SPlanLayout).
-extern "C++" {                 // (a template: the including block has C linkage)
 template <class FirstJobs, class Res1Jobs>
 int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLayout& P, char* ws, const float* x_in,
                    const float* ext_field, const float* h0, const float* c0, const float* uniform, float* h1, float* c1,
@@ -236,8 +264,9 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
     if (!ext_field) {
         const int half = he / 2;
         const unsigned rb = (unsigned)((Nn * half + 255) / 256);
-        if (D == 2) k_s2s_rff<2><<<dim3(rb), dim3(256), 0, st>>>(x_in, 2 * D, a.fp->B, half, wp(L.gamma), Nn);
-        else k_s2s_rff<3><<<dim3(rb), dim3(256), 0, st>>>(x_in, 2 * D, a.fp->B, half, wp(L.gamma), Nn);
+        dispatch_dim(D, [&](auto DD) {
+            k_s2s_rff<decltype(DD)::value><<<dim3(rb), dim3(256), 0, st>>>(x_in, 2 * D, a.fp->B, half, wp(L.gamma), Nn);
+        });
         T.j[T.n++] = s2s_job(1, a.fp->w0, he, a.fp->b0, wp(L.gamma), he, wp(L.fh1), he, he, he, Nn);
         T.j[T.n - 1].Wimg = a.field_images ? im(P.i_f0) : nullptr;
     }
@@ -257,24 +286,22 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
         const float* b4 = ext_field ? nullptr : a.fp->b4;
         float* fout = ext_field ? nullptr : wp(L.field);
         const dim3 nb4((unsigned)((Nn + 3) / 4));
-        if (D == 2) {
-            k_s2s_node_prep<2><<<nb4, dim3(256), 0, st>>>(x_in, ext_field, fh2, w4, b4, he, fout, wp(L.ext), wp(L.rel), wp(L.Rinv),
-                                                          wp(L.relp), d.RFp, wp(L.wide), ldg, counts, Nn);
-            k_s2s_edge_prep<2><<<blocks(E), dim3(256), 0, st>>>(wp(L.ext), a.send, a.recv, wp(L.rel), a.polar, wp(L.ea), wp(L.eap),
-                                                                wp(L.epos), E);
-        } else {
-            k_s2s_node_prep<3><<<nb4, dim3(256), 0, st>>>(x_in, ext_field, fh2, w4, b4, he, fout, wp(L.ext), wp(L.rel), wp(L.Rinv),
-                                                          wp(L.relp), d.RFp, wp(L.wide), ldg, counts, Nn);
-            k_s2s_edge_prep<3><<<blocks(E), dim3(256), 0, st>>>(wp(L.ext), a.send, a.recv, wp(L.rel), a.polar, wp(L.ea), wp(L.eap),
-                                                                wp(L.epos), E);
-        }
+        dispatch_dim(D, [&](auto DD) {
+            constexpr int Dc = decltype(DD)::value;
+            k_s2s_node_prep<Dc><<<nb4, dim3(256), 0, st>>>(x_in, ext_field, fh2, w4, b4, he, fout, wp(L.ext), wp(L.rel), wp(L.Rinv),
+                                                           wp(L.relp), d.RFp, wp(L.wide), ldg, counts, Nn);
+            k_s2s_edge_prep<Dc><<<blocks(E), dim3(256), 0, st>>>(wp(L.ext), a.send, a.recv, wp(L.rel), a.polar, wp(L.ea), wp(L.eap),
+                                                                 wp(L.epos), E);
+        });
     }
     // ---- anisotropic edge filter (:391)
     {
         const f16x8* image = reinterpret_cast<const f16x8*>(a.plan + P.fimg);
         f16x8* bimg = reinterpret_cast<f16x8*>(ws + L.bimg);
-        if (D == 2) k_s2s_filter_bimg<3><<<filter_bimg_grid(E), dim3(256), 0, st>>>(wp(L.epos), p->filt_w0, p->filt_b0, 0, he, E, bimg);
-        else k_s2s_filter_bimg<6><<<filter_bimg_grid(E), dim3(256), 0, st>>>(wp(L.epos), p->filt_w0, p->filt_b0, 0, he, E, bimg);
+        dispatch_dim(D, [&](auto DD) {
+            constexpr int EP = decltype(DD)::value * (decltype(DD)::value + 1) / 2;       // S2SDims::EP: 3 or 6
+            k_s2s_filter_bimg<EP><<<filter_bimg_grid(E), dim3(256), 0, st>>>(wp(L.epos), p->filt_w0, p->filt_b0, 0, he, E, bimg);
+        });
         const int64_t units = ((E + 255) / 256) * (he / 64) * L.splits;
         const dim3 grid((unsigned)(units < FILTER_WGS ? units : FILTER_WGS));
         float* dst = L.splits > 1 ? wp(L.fpart) : wp(L.eaf);
@@ -349,16 +376,40 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
         k_s2s_gumbel_select<<<blocks(E), dim3(256), 0, st>>>(wp(L.logits), uniform, a.tau, K, k0, edges, lists, counts, E);
     return AETHER_OK;
 }
+
+// The end of both decoders: the output MLP on `in` [Nn][hd], its last layer with globalise and residual (aether.py:649-654;
+// q: either decoder's parameters, both name the layers out0 / out3 / out6)
+template <class DecoderParams>
+int s2s_out_tail(const S2SStepArgs& a, char* ws, const DecoderParams* q, const float* in, const float* x_in, float* x_out,
+                 hipStream_t st) {
+    const int hd = a.hd;
+    const int64_t Nn = a.Nn;
+    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto one = [&](S2SJob J, size_t image) {
+        S2SJobs T;
+        T.n = 1; T.j[0] = J; T.j[0].Wimg = image ? a.plan + image : nullptr;
+        return s2s_launch_jobs(T, st);
+    };
+    if (int rc = one(s2s_job(2, q->out0_w, hd, q->out0_b, in, hd, wp(a.L.o1), hd, hd, hd, Nn), a.P.i_out0)) return rc;
+    if (int rc = one(s2s_job(2, q->out3_w, hd, q->out3_b, wp(a.L.o1), hd, wp(a.L.o2), hd, hd, hd, Nn), a.P.i_out3)) return rc;
+    dispatch_dim(a.D, [&](auto DD) {
+        k_s2s_out_globalize<decltype(DD)::value><<<dim3((unsigned)((Nn + 3) / 4)), dim3(256), 0, st>>>(
+            wp(a.L.o2), q->out6_w, q->out6_b, hd, x_in, wp(a.L.Rinv), x_out, Nn);
+    });
+    return AETHER_OK;
+}
 }  // extern "C++"
 
-// x_in [Nn][2D], dh_in [Nn][hd], h0 / c0 [E][R], uniform [E][K] -> x_out, dh_out, h1, c1 (+ edges_out [E][K] when not null)
-int s2s_step_impl(const S2SStepArgs& a, const S2SStepLayout& L, char* ws, const float* x_in, const float* ext_field,
-                  const float* dh_in, const float* h0, const float* c0, const float* uniform, float* x_out, float* dh_out,
-                  float* h1, float* c1, float* edges_out, hipStream_t st) {
-    const int D = a.D, he = a.he, hd = a.hd, R = a.R, K = a.K, k0 = a.skip_first ? 1 : 0;
+// The recurrent decoder's step.  x_in [Nn][2D], dh_in [Nn][hd], h0 / c0 [E][R], uniform [E][K] -> x_out, dh_out, h1, c1
+// (+ edges_out [E][K] when not null)
+int s2s_step_impl(const S2SStepArgs& a, char* ws, const float* x_in, const float* ext_field, const float* dh_in,
+                  const float* h0, const float* c0, const float* uniform, float* x_out, float* dh_out, float* h1, float* c1,
+                  float* edges_out, hipStream_t st) {
+    const int D = a.D, hd = a.hd, K = a.K, k0 = a.skip_first ? 1 : 0;
     const int64_t Nn = a.Nn, E = a.E;
     const S2SDims d(D);
-    const S2SPlanLayout P(D, he, hd, K, R, a.prior_layers, a.ph);
+    const S2SPlanLayout& P = a.P;
+    const S2SStepLayout& L = a.L;
     auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto pl = [&](size_t off) { return reinterpret_cast<const float*>(a.plan + off); };
     auto im = [&](size_t off) { return off ? reinterpret_cast<const void*>(a.plan + off) : nullptr; };
@@ -386,7 +437,6 @@ int s2s_step_impl(const S2SStepArgs& a, const S2SStepLayout& L, char* ws, const 
     };
     auto no_jobs = [](S2SJobs&) { return (int)AETHER_OK; };
     if (int rc = s2s_front_impl(a, L, P, ws, x_in, ext_field, h0, c0, uniform, h1, c1, edges, first_jobs, no_jobs, st)) return rc;
-    auto one = [&](S2SJob J) { T.n = 0; T.j[T.n++] = J; return s2s_launch_jobs(T, st); };
     // ---- decoder (:590-654): messages from the hidden states
     // (hard samples: an edge sits in at most one type's list, so the second-layer jobs below WRITE their rows of M1 / M2;
     // the rows of edges sampled as a skipped type are cleared here)
@@ -434,44 +484,133 @@ int s2s_step_impl(const S2SStepArgs& a, const S2SStepLayout& L, char* ws, const 
     T.j[T.n - 1].Wimg = im(P.i_hh2);
     if (int rc = s2s_launch_jobs(T, st)) return rc;
     k_s2s_gate<<<blocks(Nn * hd), dim3(256), 0, st>>>(wp(L.rp), wp(L.ip), wp(L.np_), wp(L.hh), dh_in, dh_out, Nn * hd);
-    // output MLP, globalise, residual (:649-654)
-    { S2SJob J = s2s_job(2, q->out0_w, hd, q->out0_b, dh_out, hd, wp(L.o1), hd, hd, hd, Nn); J.Wimg = im(P.i_out0);
-      if (int rc = one(J)) return rc; }
-    { S2SJob J = s2s_job(2, q->out3_w, hd, q->out3_b, wp(L.o1), hd, wp(L.o2), hd, hd, hd, Nn); J.Wimg = im(P.i_out3);
-      if (int rc = one(J)) return rc; }
-    {
-        const dim3 nb4((unsigned)((Nn + 3) / 4));
-        if (D == 2) k_s2s_out_globalize<2><<<nb4, dim3(256), 0, st>>>(wp(L.o2), q->out6_w, q->out6_b, hd, x_in, wp(L.Rinv), x_out, Nn);
-        else k_s2s_out_globalize<3><<<nb4, dim3(256), 0, st>>>(wp(L.o2), q->out6_w, q->out6_b, hd, x_in, wp(L.Rinv), x_out, Nn);
-    }
-    return AETHER_OK;
+    return s2s_out_tail(a, ws, q, dh_out, x_in, x_out, st);
 }
 
-int s2s_step_check(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp, const AetherS2SDecoderParams* dp,
-                   const void* plan, int D, int he, int hd, int R, int prior_layers, int ph, int K, int num_vars, int64_t Nn,
-                   int64_t E, bool need_field) {
-    if (!pp || !dp || !plan || (need_field && !fp)) return fail(AETHER_EINVAL, "s2s_step: null pointer");
-    if (D != 2 && D != 3) return fail(AETHER_EINVAL, "s2s_step: num_dims must be 2 or 3");
-    if (he < 128 || he % 128 != 0) return fail(AETHER_EINVAL, "s2s_step: encoder hidden must be a multiple of 128");
-    if (hd < 32 || hd % 32 != 0) return fail(AETHER_EINVAL, "s2s_step: decoder hidden must be a multiple of 32");
-    if (R < 16 || R % 16 != 0) return fail(AETHER_EINVAL, "s2s_step: rnn_hidden must be a multiple of 16");
-    if (prior_layers < 1 || prior_layers > 4 || (prior_layers > 1 && (ph < 16 || ph % 16 != 0)))
+int s2s_markov_step_impl(const S2SStepArgs& a, char* ws, const float* x_in, const float* ext_field, const float* h0,
+                         const float* c0, const float* uniform, float* x_out, float* h1, float* c1, float* edges_out,
+                         bool decode, hipStream_t st);                     // host_s2s_markov.inc
+int s2s_markov_check(const AetherS2SMarkovParams* mp, int D, int h, int K, int skip_first);
+
+// One step of whichever decoder the arguments name.  decode = false (Markov decoder only): the prior alone -- no sample, no
+// decoder, next.x not written.
+int s2s_step(const S2SStepArgs& a, char* ws, const S2SStateIn& cur, const float* ext_field, const float* uniform,
+             const S2SStateOut& next, float* edges_out, bool decode, hipStream_t st) {
+    if (a.mp) return s2s_markov_step_impl(a, ws, cur.x, ext_field, cur.h, cur.c, uniform, next.x, next.h, next.c, edges_out, decode, st);
+    return s2s_step_impl(a, ws, cur.x, ext_field, cur.dh, cur.h, cur.c, uniform, next.x, next.dh, next.h, next.c, edges_out, st);
+}
+
+// The checks of the four step / rollout entries (`what`: the entry's name in the messages) but the workspace's size, which
+// s2s_run_step / s2s_run_rollout compare with the layout of the arguments made afterwards.  markov: the entry's decoder is mp, not dp
+// (the other one is null); need_field: no field is handed in, so fp is needed; pointers: the entry's own buffers are all
+// there; burn_in_steps, steps: of a rollout (a single step: 0, 1).
+int s2s_entry_check(const char* what, bool markov, const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp,
+                    const AetherS2SDecoderParams* dp, const AetherS2SMarkovParams* mp, const void* plan, const S2SSizes& z,
+                    bool need_field, bool pointers, int burn_in_steps, int steps) {
+    if (markov)
+        if (int rc = s2s_markov_check(mp, z.D, z.hd, z.K, z.skip_first)) return rc;
+    if (!pp || !(markov ? mp != nullptr : dp != nullptr) || !plan || (need_field && !fp))
+        return fail(AETHER_EINVAL, "s2s_step: null pointer");
+    if (z.D != 2 && z.D != 3) return fail(AETHER_EINVAL, "s2s_step: num_dims must be 2 or 3");
+    if (z.he < 128 || z.he % 128 != 0) return fail(AETHER_EINVAL, "s2s_step: encoder hidden must be a multiple of 128");
+    if (z.hd < 32 || z.hd % 32 != 0) return fail(AETHER_EINVAL, "s2s_step: decoder hidden must be a multiple of 32");
+    if (z.R < 16 || z.R % 16 != 0) return fail(AETHER_EINVAL, "s2s_step: rnn_hidden must be a multiple of 16");
+    if (z.prior_layers < 1 || z.prior_layers > 4 || (z.prior_layers > 1 && (z.ph < 16 || z.ph % 16 != 0)))
         return fail(AETHER_EINVAL, "s2s_step: 1..4 prior layers, prior_hidden a multiple of 16");
-    if (K < 1 || K > 4 || num_vars < 2 || Nn <= 0 || E <= 0) return fail(AETHER_EINVAL, "s2s_step: bad sizes");
+    if (z.K < 1 || z.K > 4 || z.num_vars < 2 || z.Nn <= 0 || z.E <= 0) return fail(AETHER_EINVAL, "s2s_step: bad sizes");
+    if (!pointers) return s2s_fail(AETHER_EINVAL, what, "null pointer");
+    if (burn_in_steps < 0 || steps < 0 || burn_in_steps + steps == 0) return s2s_fail(AETHER_EINVAL, what, "no steps");
+    if (!(z.tau > 0.0f)) return s2s_fail(AETHER_EINVAL, what, "tau must be positive");
     return AETHER_OK;
 }
-}  // namespace
 
-size_t aether_s2s_plan_bytes(int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
-                             int prior_hidden, int num_edge_types) {
-    if ((num_dims != 2 && num_dims != 3) || encoder_hidden < 128 || encoder_hidden % 128 != 0 || decoder_hidden < 32 ||
-        decoder_hidden % 32 != 0 || rnn_hidden < 16 || rnn_hidden % 16 != 0 || num_edge_types < 1 || num_edge_types > 4 ||
-        prior_layers < 1 || prior_layers > 4)
-        return 0;
-    return S2SPlanLayout(num_dims, encoder_hidden, decoder_hidden, num_edge_types, rnn_hidden, prior_layers, prior_hidden).total;
+// (after s2s_entry_check: the layouts take the sizes as valid)
+extern "C++" S2SStepArgs s2s_step_args(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp,
+                                       const AetherS2SDecoderParams* dp, const AetherS2SMarkovParams* mp, const void* plan,
+                                       const S2SSizes& z, const int64_t* send, const int64_t* recv, const int64_t* order,
+                                       const int64_t* rowptr) {
+    return S2SStepArgs{z, fp, pp, dp, mp, (const char*)plan, send, recv, order, rowptr, fp != nullptr,
+                       S2SPlanLayout(z.D, z.he, z.hd, z.K, z.R, z.prior_layers, z.ph, dp ? -1 : z.K - (z.skip_first ? 1 : 0)),
+                       S2SStepLayout(z.D, z.he, z.hd, z.R, z.ph, z.K, z.Nn, z.E)};
 }
 
-namespace {
+// (`what`, workspace_bytes: the last of the entry's checks, on the one layout its call builds)
+int s2s_run_step(const char* what, const S2SStepArgs& a, void* workspace, size_t workspace_bytes, const S2SStateIn& cur,
+                 const float* ext_field, const float* uniform, const S2SStateOut& next, float* edges_out, void* stream) {
+    if (workspace_bytes < a.L.total) return s2s_fail(AETHER_ESPACE, what, "workspace too small");
+    if (int rc = s2s_step(a, (char*)workspace, cur, ext_field, uniform, next, edges_out, true, (hipStream_t)stream)) return rc;
+    HIP_OK(hipGetLastError());
+    return AETHER_OK;
+}
+
+// burn_in [T0][Nn][2D] teacher-forced, then `steps` steps from inputs; decoder_state (null: the Markov decoder), h, c are
+// read first and written last.
+int s2s_run_rollout(const char* what, const S2SStepArgs& a, void* workspace, size_t workspace_bytes, int burn_in_steps,
+                    const float* burn_in, int steps, const float* inputs, float* decoder_state, float* h, float* c,
+                    const float* uniform, float* predictions, float* edges_out, void* stream) {
+    if (workspace_bytes < a.L.total) return s2s_fail(AETHER_ESPACE, what, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const S2SStepLayout& L = a.L;
+    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    const size_t dbytes = (size_t)a.Nn * a.hd * 4, rbytes = (size_t)a.E * a.R * 4;
+    const size_t ustep = (size_t)a.E * a.K, xstep = (size_t)a.Nn * 2 * a.D;
+    // state ping-pong inside the workspace (the decoder's only when it has a state)
+    float *dcur = decoder_state ? wp(L.da) : nullptr, *dnext = decoder_state ? wp(L.db) : nullptr;
+    float *hcur = wp(L.ha), *hnext = wp(L.hb), *ccur = wp(L.ca), *cnext = wp(L.cb);
+    if (dcur) HIP_OK(hipMemcpyAsync(dcur, decoder_state, dbytes, hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipMemcpyAsync(hcur, h, rbytes, hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipMemcpyAsync(ccur, c, rbytes, hipMemcpyDeviceToDevice, st));
+    const int total = burn_in_steps + steps;
+    const float* xcur = burn_in_steps > 0 ? burn_in : inputs;
+    for (int t = 0; t < total; ++t) {
+        // A burn-in step's prediction is discarded.  The recurrent decoder still needs the step for its state: the whole
+        // step, its output into L.xa.  The Markov decoder has no state: the prior only -- no sample, no decoder, no output.
+        const bool teacher = t < burn_in_steps, decode = !teacher || !a.mp;
+        float* xout = !teacher ? predictions + (size_t)(t - burn_in_steps) * xstep : decode ? wp(L.xa) : nullptr;
+        float* eout = (!teacher && edges_out) ? edges_out + (size_t)(t - burn_in_steps) * ustep : nullptr;
+        if (int rc = s2s_step(a, ws, {xcur, dcur, hcur, ccur}, nullptr, uniform + (size_t)t * ustep, {xout, dnext, hnext, cnext},
+                              eout, decode, st)) return rc;
+        std::swap(dcur, dnext); std::swap(hcur, hnext); std::swap(ccur, cnext);
+        if (t + 1 < burn_in_steps) xcur = burn_in + (size_t)(t + 1) * xstep;
+        else if (t + 1 == burn_in_steps) xcur = inputs;
+        else xcur = xout;
+    }
+    if (dcur) HIP_OK(hipMemcpyAsync(decoder_state, dcur, dbytes, hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipMemcpyAsync(h, hcur, rbytes, hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipMemcpyAsync(c, ccur, rbytes, hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipGetLastError());
+    return AETHER_OK;
+}
+
+// Bytes of the plan of either decoder, 0 for sizes the fused step does not take.  markov_ku: the Markov decoder's count of
+// used edge types (at least one), -1 for the recurrent decoder.
+size_t s2s_plan_size(int D, int he, int hd, int R, int prior_layers, int ph, int K, int markov_ku) {
+    if ((D != 2 && D != 3) || he < 128 || he % 128 != 0 || hd < 32 || hd % 32 != 0 || R < 16 || R % 16 != 0 || K < 1 || K > 4 ||
+        prior_layers < 1 || prior_layers > 4 || markov_ku == 0 || markov_ku < -1)
+        return 0;
+    return S2SPlanLayout(D, he, hd, K, R, prior_layers, ph, markov_ku).total;
+}
+
+// need: s2s_plan_size of the model
+int s2s_plan_buffer_check(const char* what, size_t need, const void* plan, size_t plan_bytes) {
+    if (need == 0) return s2s_fail(AETHER_EINVAL, what, "bad sizes");
+    if (plan_bytes < need || ((size_t)plan & 255)) return s2s_fail(AETHER_ESPACE, what, "plan buffer too small or not 256-byte aligned");
+    return AETHER_OK;
+}
+
+// The fp16 x 2 image of W [M][Kk] (row stride ldw) at its place in the plan (off == 0: the layout has none)
+void s2s_image(char* base, hipStream_t st, size_t off, const float* W, int M, int Kk, int ldw, int gate_units = 0) {
+    if (off) k_s2s_gemm_image<<<dim3((unsigned)(((int64_t)M * (Kk / 8) + 255) / 256)), dim3(256), 0, st>>>(
+                 W, M, Kk, ldw, reinterpret_cast<f16x8*>(base + off), gate_units);
+}
+
+// The images of the output MLP's two hidden layers, which both decoders have
+void s2s_out_images(char* base, hipStream_t st, const S2SPlanLayout& P, const float* out0_w, const float* out3_w, int hd) {
+    s2s_image(base, st, P.i_out0, out0_w, hd, hd, hd);
+    s2s_image(base, st, P.i_out3, out3_w, hd, hd, hd);
+}
+
 // The prepared weights of the shared half of the step (field query, prior) into a plan of either layout.
 void s2s_plan_build_front(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp, int D, int he, int rnn_hidden,
                           int prior_layers, int prior_hidden, const S2SPlanLayout& P, char* base, hipStream_t st) {
@@ -486,34 +625,34 @@ void s2s_plan_build_front(const AetherS2SFieldParams* fp, const AetherS2SPriorPa
                                                      fl(P.bn) + 2 * he, fl(P.bn) + 3 * he, he);
     k_s2s_add_vec<<<blocks(4 * rnn_hidden), dim3(256), 0, st>>>(pp->lstm_b_ih, pp->lstm_b_hh, fl(P.lb), 4 * rnn_hidden);
     k_s2s_lstm_bias_interleave<<<blocks(4 * rnn_hidden), dim3(256), 0, st>>>(pp->lstm_b_ih, pp->lstm_b_hh, fl(P.lbp), rnn_hidden);
-    auto image = [&](size_t off, const float* W, int M, int Kk, int ldw, int gate_units = 0) {
-        if (off) k_s2s_gemm_image<<<blocks((int64_t)M * (Kk / 8)), dim3(256), 0, st>>>(W, M, Kk, ldw, reinterpret_cast<f16x8*>(base + off),
-                                                                                        gate_units);
-    };
-    image(P.i_mlp4e, pp->mlp4_w0 + 2 * he, he, he, 3 * he);
-    image(P.i_mlp4_3, pp->mlp4_w3, he, he, he);
-    image(P.i_ih, pp->lstm_w_ih, 4 * rnn_hidden, he, he, rnn_hidden);                 // gates interleaved by unit (S2SJob act 5)
-    image(P.i_hh, pp->lstm_w_hh, 4 * rnn_hidden, rnn_hidden, rnn_hidden, rnn_hidden);
-    for (int l = 0; l + 1 < prior_layers; ++l) image(P.i_prior[l], pp->prior_w[l], prior_hidden, l == 0 ? rnn_hidden : prior_hidden,
-                                                     l == 0 ? rnn_hidden : prior_hidden);
-    if (fp) { image(P.i_f0, fp->w0, he, he, he); image(P.i_f2, fp->w2, he, he, he); }
-    image(P.i_mlp3_0, pp->mlp3_w0, he, he, he);
-    image(P.i_mlp3_3, pp->mlp3_w3, he, he, he);
-    image(P.i_ps, pp->mlp4_w0, he, he, 3 * he);
-    image(P.i_pr, pp->mlp4_w0 + he, he, he, 3 * he);
+    s2s_image(base, st, P.i_mlp4e, pp->mlp4_w0 + 2 * he, he, he, 3 * he);
+    s2s_image(base, st, P.i_mlp4_3, pp->mlp4_w3, he, he, he);
+    s2s_image(base, st, P.i_ih, pp->lstm_w_ih, 4 * rnn_hidden, he, he, rnn_hidden);             // gates interleaved by unit (S2SJob act 5)
+    s2s_image(base, st, P.i_hh, pp->lstm_w_hh, 4 * rnn_hidden, rnn_hidden, rnn_hidden, rnn_hidden);
+    for (int l = 0; l + 1 < prior_layers; ++l)
+        s2s_image(base, st, P.i_prior[l], pp->prior_w[l], prior_hidden, l == 0 ? rnn_hidden : prior_hidden,
+                  l == 0 ? rnn_hidden : prior_hidden);
+    if (fp) { s2s_image(base, st, P.i_f0, fp->w0, he, he, he); s2s_image(base, st, P.i_f2, fp->w2, he, he, he); }
+    s2s_image(base, st, P.i_mlp3_0, pp->mlp3_w0, he, he, he);
+    s2s_image(base, st, P.i_mlp3_3, pp->mlp3_w3, he, he, he);
+    s2s_image(base, st, P.i_ps, pp->mlp4_w0, he, he, 3 * he);
+    s2s_image(base, st, P.i_pr, pp->mlp4_w0 + he, he, he, 3 * he);
 }
 }  // namespace
+
+size_t aether_s2s_plan_bytes(int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
+                             int prior_hidden, int num_edge_types) {
+    return s2s_plan_size(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden, num_edge_types, -1);
+}
 
 int aether_s2s_plan_build(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp, const AetherS2SDecoderParams* dp, int num_dims,
                           int encoder_hidden,
                           int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, void* plan,
                           size_t plan_bytes, void* stream) {
     if (!pp || !dp || !plan) return fail(AETHER_EINVAL, "s2s_plan_build: null pointer");
-    const size_t need = aether_s2s_plan_bytes(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden,
-                                              num_edge_types);
-    if (need == 0) return fail(AETHER_EINVAL, "s2s_plan_build: bad sizes");
-    if (plan_bytes < need || ((size_t)plan & 255)) return fail(AETHER_ESPACE, "s2s_plan_build: plan buffer too small or not 256-byte aligned");
     const int D = num_dims, he = encoder_hidden, hd = decoder_hidden, K = num_edge_types;
+    if (int rc = s2s_plan_buffer_check("s2s_plan_build", s2s_plan_size(D, he, hd, rnn_hidden, prior_layers, prior_hidden, K, -1),
+                                       plan, plan_bytes)) return rc;
     const S2SDims d(D);
     const S2SPlanLayout P(D, he, hd, K, rnn_hidden, prior_layers, prior_hidden);
     hipStream_t st = (hipStream_t)stream;
@@ -533,21 +672,17 @@ int aether_s2s_plan_build(const AetherS2SFieldParams* fp, const AetherS2SPriorPa
     k_s2s_add_vec<<<blocks(hd), dim3(256), 0, st>>>(dp->input_r_b, dp->present_r_b, fl(P.br), hd);
     k_s2s_add_vec<<<blocks(hd), dim3(256), 0, st>>>(dp->input_i_b, dp->present_i_b, fl(P.bi), hd);
     k_s2s_add_vec<<<blocks(hd), dim3(256), 0, st>>>(dp->input_n_b, dp->present_n_b, fl(P.bn_), hd);
-    auto image = [&](size_t off, const float* W, int M, int Kk, int ldw) {
-        if (off) k_s2s_gemm_image<<<blocks((int64_t)M * (Kk / 8)), dim3(256), 0, st>>>(W, M, Kk, ldw, reinterpret_cast<f16x8*>(base + off), 0);
-    };
-    image(P.i_wr, fl(P.wr), hd, P.ldg, P.ldg);
-    image(P.i_wi, fl(P.wi), hd, P.ldg, P.ldg);
-    image(P.i_wn, fl(P.wn), hd, S2S_RFG + hd, P.ldg);
-    image(P.i_hh2, dp->hidden_h_w, hd, hd, hd);
-    image(P.i_out0, dp->out0_w, hd, hd, hd);
-    image(P.i_out3, dp->out3_w, hd, hd, hd);
+    s2s_image(base, st, P.i_wr, fl(P.wr), hd, P.ldg, P.ldg);
+    s2s_image(base, st, P.i_wi, fl(P.wi), hd, P.ldg, P.ldg);
+    s2s_image(base, st, P.i_wn, fl(P.wn), hd, S2S_RFG + hd, P.ldg);
+    s2s_image(base, st, P.i_hh2, dp->hidden_h_w, hd, hd, hd);
+    s2s_out_images(base, st, P, dp->out0_w, dp->out3_w, hd);
     for (int k = 0; k < K; ++k) {
-        image(P.i_a[k], dp->msg_fc1_w[k], hd, hd, 2 * hd);
-        image(P.i_s[k], dp->msg_fc1_w[k] + hd, hd, hd, 2 * hd);
-        image(P.i_msg2[k], dp->msg_fc2_w[k], hd, hd, hd);
-        image(P.i_pmsg1[k], fl(P.p1p[k]), hd, d.EAp, d.EAp);            // the zero-padded copy built above
-        image(P.i_pmsg2[k], dp->pmsg_fc2_w[k], hd, hd, hd);
+        s2s_image(base, st, P.i_a[k], dp->msg_fc1_w[k], hd, hd, 2 * hd);
+        s2s_image(base, st, P.i_s[k], dp->msg_fc1_w[k] + hd, hd, hd, 2 * hd);
+        s2s_image(base, st, P.i_msg2[k], dp->msg_fc2_w[k], hd, hd, hd);
+        s2s_image(base, st, P.i_pmsg1[k], fl(P.p1p[k]), hd, d.EAp, d.EAp);            // the zero-padded copy built above
+        s2s_image(base, st, P.i_pmsg2[k], dp->pmsg_fc2_w[k], hd, hd, hd);
     }
     HIP_OK(hipGetLastError());
     return AETHER_OK;
@@ -568,20 +703,15 @@ int aether_s2s_step(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* 
                     const float* inputs, const float* ext_field, const float* decoder_hidden_in, const float* h0, const float* c0,
                     const float* uniform, void* workspace, size_t workspace_bytes, float* outputs, float* decoder_hidden_out,
                     float* h1, float* c1, float* edges_out, void* stream) {
-    if (int rc = s2s_step_check(fp, pp, dp, plan, num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden,
-                                num_edge_types, num_vars, n_nodes, n_edges, ext_field == nullptr)) return rc;
-    if (!send || !recv || !order || !rowptr || !inputs || !decoder_hidden_in || !h0 || !c0 || !uniform || !workspace || !outputs ||
-        !decoder_hidden_out || !h1 || !c1)
-        return fail(AETHER_EINVAL, "s2s_step: null pointer");
-    if (!(tau > 0.0f)) return fail(AETHER_EINVAL, "s2s_step: tau must be positive");
-    const S2SStepLayout L(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_hidden, num_edge_types, n_nodes, n_edges);
-    if (workspace_bytes < L.total) return fail(AETHER_ESPACE, "s2s_step: workspace too small");
-    const S2SStepArgs a{fp, pp, dp, (const char*)plan, num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers,
-                        prior_hidden, num_edge_types, skip_first, polar, num_vars, n_nodes, n_edges, send, recv, order, rowptr, tau, fp != nullptr};
-    if (int rc = s2s_step_impl(a, L, (char*)workspace, inputs, ext_field, decoder_hidden_in, h0, c0, uniform, outputs,
-                               decoder_hidden_out, h1, c1, edges_out, (hipStream_t)stream)) return rc;
-    HIP_OK(hipGetLastError());
-    return AETHER_OK;
+    const S2SSizes z{num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden, num_edge_types, skip_first,
+                     polar, num_vars, tau, n_nodes, n_edges};
+    if (int rc = s2s_entry_check("s2s_step", false, fp, pp, dp, nullptr, plan, z, ext_field == nullptr,
+                                 send && recv && order && rowptr && inputs && decoder_hidden_in && h0 && c0 && uniform &&
+                                     workspace && outputs && decoder_hidden_out && h1 && c1,
+                                 0, 1)) return rc;
+    return s2s_run_step("s2s_step", s2s_step_args(fp, pp, dp, nullptr, plan, z, send, recv, order, rowptr), workspace,
+                        workspace_bytes, {inputs, decoder_hidden_in, h0, c0}, ext_field, uniform,
+                        {outputs, decoder_hidden_out, h1, c1}, edges_out, stream);
 }
 
 int aether_s2s_rollout(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp, const AetherS2SDecoderParams* dp,
@@ -591,47 +721,13 @@ int aether_s2s_rollout(const AetherS2SFieldParams* fp, const AetherS2SPriorParam
                        int burn_in_steps, const float* burn_in, int steps, const float* inputs, float* decoder_state, float* h,
                        float* c, const float* uniform, void* workspace, size_t workspace_bytes, float* predictions,
                        float* edges_out, void* stream) {
-    if (int rc = s2s_step_check(fp, pp, dp, plan, num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden,
-                                num_edge_types, num_vars, n_nodes, n_edges, true)) return rc;
-    if (!send || !recv || !order || !rowptr || !inputs || !decoder_state || !h || !c || !uniform || !workspace ||
-        (steps > 0 && !predictions) || (burn_in_steps > 0 && !burn_in))
-        return fail(AETHER_EINVAL, "s2s_rollout: null pointer");
-    if (steps < 0 || burn_in_steps < 0 || steps + burn_in_steps == 0) return fail(AETHER_EINVAL, "s2s_rollout: no steps");
-    if (!(tau > 0.0f)) return fail(AETHER_EINVAL, "s2s_rollout: tau must be positive");
-    const S2SStepLayout L(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_hidden, num_edge_types, n_nodes, n_edges);
-    if (workspace_bytes < L.total) return fail(AETHER_ESPACE, "s2s_rollout: workspace too small");
-    const S2SStepArgs a{fp, pp, dp, (const char*)plan, num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers,
-                        prior_hidden, num_edge_types, skip_first, polar, num_vars, n_nodes, n_edges, send, recv, order, rowptr, tau, fp != nullptr};
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    const size_t xbytes = (size_t)n_nodes * 2 * num_dims * 4, dbytes = (size_t)n_nodes * decoder_hidden * 4,
-                 rbytes = (size_t)n_edges * rnn_hidden * 4;
-    const size_t ustep = (size_t)n_edges * num_edge_types, xstep = (size_t)n_nodes * 2 * num_dims;
-    // state ping-pong inside the workspace; the caller's state buffers are read first and written last
-    float* dcur = wp(L.da); float* dnext = wp(L.db);
-    float* hcur = wp(L.ha); float* hnext = wp(L.hb);
-    float* ccur = wp(L.ca); float* cnext = wp(L.cb);
-    HIP_OK(hipMemcpyAsync(dcur, decoder_state, dbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(hcur, h, rbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(ccur, c, rbytes, hipMemcpyDeviceToDevice, st));
-    const int total = burn_in_steps + steps;
-    const float* xcur = burn_in_steps > 0 ? burn_in : inputs;
-    for (int t = 0; t < total; ++t) {
-        const bool teacher = t < burn_in_steps;                       // the step's prediction is discarded
-        float* xout = teacher ? wp(L.xa) : predictions + (size_t)(t - burn_in_steps) * xstep;
-        float* eout = (!teacher && edges_out) ? edges_out + (size_t)(t - burn_in_steps) * ustep : nullptr;
-        if (int rc = s2s_step_impl(a, L, ws, xcur, nullptr, dcur, hcur, ccur, uniform + (size_t)t * ustep, xout, dnext, hnext,
-                                   cnext, eout, st)) return rc;
-        std::swap(dcur, dnext); std::swap(hcur, hnext); std::swap(ccur, cnext);
-        if (t + 1 < burn_in_steps) xcur = burn_in + (size_t)(t + 1) * xstep;
-        else if (t + 1 == burn_in_steps) xcur = inputs;
-        else xcur = xout;
-    }
-    HIP_OK(hipMemcpyAsync(decoder_state, dcur, dbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(h, hcur, rbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(c, ccur, rbytes, hipMemcpyDeviceToDevice, st));
-    (void)xbytes;
-    HIP_OK(hipGetLastError());
-    return AETHER_OK;
+    const S2SSizes z{num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden, num_edge_types, skip_first,
+                     polar, num_vars, tau, n_nodes, n_edges};
+    if (int rc = s2s_entry_check("s2s_rollout", false, fp, pp, dp, nullptr, plan, z, true,
+                                 send && recv && order && rowptr && inputs && decoder_state && h && c && uniform && workspace &&
+                                     (steps <= 0 || predictions) && (burn_in_steps <= 0 || burn_in),
+                                 burn_in_steps, steps)) return rc;
+    return s2s_run_rollout("s2s_rollout", s2s_step_args(fp, pp, dp, nullptr, plan, z, send, recv, order, rowptr), workspace,
+                           workspace_bytes, burn_in_steps, burn_in, steps, inputs, decoder_state, h, c, uniform, predictions,
+                           edges_out, stream);
 }

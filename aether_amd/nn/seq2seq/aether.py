@@ -19,12 +19,27 @@ import torch.nn as nn
 from ... import _lib
 from .decoder import RecurrentDecoder
 from .encoder import Encoder, gumbel_softmax_hard
-from .field import FieldQuery
+from .field import FieldQuery, _S2SFieldParams
 from .markov import MarkovDecoder
 
 
 def _tensors_key(module):
     return tuple((t.data_ptr(), t._version) for t in list(module.parameters()) + list(module.buffers()))
+
+
+def _capture(device, run, warmups):
+    """``run`` ``warmups`` times on a side stream (lazy initialisation, plan, workspaces, caches), then once more under
+    capture -> (the hipGraph, what the captured call returned)."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        for _ in range(warmups):
+            run()
+    torch.cuda.current_stream(device).wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = run()
+    return graph, out
 
 
 class _StepRunner:
@@ -45,15 +60,7 @@ class _StepRunner:
         self.u = torch.full((B, E, K), 0.5, dtype=torch.float32, device=device)
         self.model, self.field_fn = model, field_fn
         self.edges = None
-        side = torch.cuda.Stream(device=device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):                              # warm-up: lazy initialisation, workspaces, caches
-            self._step()
-            self._step()
-        torch.cuda.current_stream(device).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self._step()
+        self.graph, _ = _capture(device, self._step, 2)
         self.field_fn = None                                       # only needed for the capture
         self.keep = model._graph_keepalive()                       # buffers whose addresses the graph holds
 
@@ -90,14 +97,7 @@ class _RolloutRunner:
         self.x, self.dh, self.ph, self.pc = z(B, N, 2 * D), z(B, N, h), z(B, E, R), z(B, E, R)
         self.u = torch.full((T0 + steps, B, E, K), 0.5, dtype=torch.float32, device=device)
         self.model, self.steps = model, steps
-        side = torch.cuda.Stream(device=device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):                              # warm-up: plan, workspaces, lazy initialisation
-            self._run()
-        torch.cuda.current_stream(device).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.out = self._run()
+        self.graph, self.out = _capture(device, self._run, 1)
         self.keep = model._graph_keepalive()
 
     def _run(self):
@@ -125,8 +125,8 @@ class _StepLoop:
         return (self.num_dims, enc.hidden_size, dec.msg_out_shape, enc.rnn_hidden_size, self.num_edge_types)
 
     def _plan(self, device):
-        """Prepared weights of the fused step (``aether_s2s_plan_build``), rebuilt -- into the same buffer, which captured
-        graphs point at -- whenever an encoder / decoder tensor moved or was written to."""
+        """Prepared weights of the fused step (``aether_s2s_plan_build`` / ``aether_s2s_markov_plan_build``), rebuilt --
+        into the same buffer, which captured graphs point at -- whenever an encoder / decoder tensor moved or was written to."""
         enc, dec = self.encoder, self.decoder
         fq = getattr(self, "_fq", None)
         tensors = list(enc.parameters()) + list(enc.buffers()) + list(dec.parameters())
@@ -136,18 +136,20 @@ class _StepLoop:
         hit = self.__dict__.get("_plan_cache")
         if hit is None or hit[0] != key:
             lib = _lib.load()
+            bytes_entry, build_entry = dec._fused_entries[:2]
+            extra = dec._plan_extra()
             D, he, hd, R, K = self._step_sizes()
             pe, n_layers, prior_hidden = enc._param_struct(with_image=False)
-            nbytes = lib.aether_s2s_plan_bytes(D, he, hd, R, n_layers, prior_hidden, K)
+            nbytes = getattr(lib, bytes_entry)(D, he, hd, R, n_layers, prior_hidden, K, *extra)
             if nbytes == 0:
                 raise _lib.AetherHipError("fused seq2seq step: encoder_hidden must be a multiple of 128, decoder_hidden of 32")
             buf = hit[1] if hit is not None and hit[1].numel() == nbytes and hit[1].device == torch.device(device) else \
                 torch.empty(nbytes, dtype=torch.uint8, device=device)
             pd = dec._param_struct()
             pf = self._field_struct()
-            _lib.check(lib.aether_s2s_plan_build(None if pf is None else C.byref(pf), C.byref(pe), C.byref(pd), D, he, hd, R, n_layers,
-                                                 prior_hidden, K, buf.data_ptr(), nbytes,
-                                                 torch.cuda.current_stream(device).cuda_stream), "aether_s2s_plan_build")
+            _lib.check(getattr(lib, build_entry)(None if pf is None else C.byref(pf), C.byref(pe), C.byref(pd), D, he, hd, R,
+                                                 n_layers, prior_hidden, K, *extra, buf.data_ptr(), nbytes,
+                                                 torch.cuda.current_stream(device).cuda_stream), build_entry)
             hit = self.__dict__["_plan_cache"] = (key, buf)
         return hit[1]
 
@@ -157,7 +159,6 @@ class _StepLoop:
         if fq is None:
             return None
         fn, ce = fq[0].field_net, fq[0].coordinate_embedding
-        from .field import _S2SFieldParams
         return _S2SFieldParams(*[t.data_ptr() for t in (ce.B, fn[0].weight, fn[0].bias, fn[2].weight, fn[2].bias,
                                                         fn[4].weight, fn[4].bias)])
 
@@ -184,7 +185,8 @@ class _StepLoop:
     @torch.no_grad()
     def _fused_step(self, x, decoder_hidden, prior_hidden, uniform, field=None):
         """One autoregressive step: x [B, N, 2D], decoder_hidden [B, N, hd], prior_hidden (h, c) [B, E, rnn], uniform
-        [B, E, K]; ``field`` [B, N, D] replaces the built-in field query -> (predictions, decoder_hidden, (h, c), edges)."""
+        [B, E, K]; ``field`` [B, N, D] replaces the built-in field query -> (predictions, decoder_hidden, (h, c), edges).
+        With the Markov decoder, which has no state, ``decoder_hidden`` is ignored and comes back as None."""
         if not x.is_cuda:
             raise _lib.AetherHipError("aether_amd seq2seq models run on an MI355X only; got a CPU tensor (there is no CPU fallback)")
         B, N, _ = x.shape
@@ -192,30 +194,35 @@ class _StepLoop:
         lib, plan, ws, (send, recv, order, rowptr), (pf, pe, pd), scal = self._step_common(B, N, dev)
         D, he, hd, R, K = self._step_sizes()
         E1 = self.encoder.recv_edges.shape[0]
+        entry = self.decoder._fused_entries[2]
         f32 = lambda t: t.detach().to(torch.float32).contiguous()
-        xf, dhf, h0, c0, uf = f32(x), f32(decoder_hidden), f32(prior_hidden[0]), f32(prior_hidden[1]), f32(uniform)
-        if xf.shape != (B, N, 2 * D) or dhf.shape != (B, N, hd) or h0.shape != (B, E1, R) or c0.shape != h0.shape or \
-                uf.numel() != B * E1 * K:
+        xf, h0, c0, uf = f32(x), f32(prior_hidden[0]), f32(prior_hidden[1]), f32(uniform)
+        dhf = f32(decoder_hidden) if self.decoder._has_state else None
+        if xf.shape != (B, N, 2 * D) or (dhf is not None and dhf.shape != (B, N, hd)) or h0.shape != (B, E1, R) or \
+                c0.shape != h0.shape or uf.numel() != B * E1 * K:
             raise ValueError("fused step: input shapes do not match the model")
         ff = None if field is None else f32(field)
         if ff is None and pf is None:
             raise _lib.AetherHipError("this model has no built-in field query: pass the field")
         out = torch.empty_like(xf)
-        dh_out = torch.empty_like(dhf)
+        dh_out = None if dhf is None else torch.empty_like(dhf)
         h1, c1 = torch.empty_like(h0), torch.empty_like(c0)
         edges = torch.empty(B, E1, K, dtype=torch.float32, device=dev)
-        st = lib.aether_s2s_step(None if pf is None else C.byref(pf), C.byref(pe), C.byref(pd), plan.data_ptr(), *scal,
+        ptr = lambda t: () if t is None else (t.data_ptr(),)              # the Markov entries take no decoder state
+        st = getattr(lib, entry)(None if pf is None else C.byref(pf), C.byref(pe), C.byref(pd), plan.data_ptr(), *scal,
                                  send.data_ptr(), recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), xf.data_ptr(),
-                                 None if ff is None else ff.data_ptr(), dhf.data_ptr(), h0.data_ptr(), c0.data_ptr(),
-                                 uf.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), dh_out.data_ptr(), h1.data_ptr(),
+                                 None if ff is None else ff.data_ptr(), *ptr(dhf), h0.data_ptr(), c0.data_ptr(),
+                                 uf.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), *ptr(dh_out), h1.data_ptr(),
                                  c1.data_ptr(), edges.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(st, "aether_s2s_step")
+        _lib.check(st, entry)
         return out, dh_out, (h1, c1), edges
 
     @torch.no_grad()
     def _fused_rollout(self, burn_in, x_last, decoder_hidden, prior_hidden, steps, uniform, return_edges):
-        """``aether_s2s_rollout``: burn_in [B, T0, N, 2D] (or None) teacher-forced, then ``steps`` autoregressive steps from
-        x_last [B, N, 2D]; uniform [T0 + steps, B, E, K] -> (predictions [B, steps, N, 2D], edges or None, final state)."""
+        """``aether_s2s_rollout`` / ``aether_s2s_markov_rollout``: burn_in [B, T0, N, 2D] (or None) teacher-forced, then
+        ``steps`` autoregressive steps from x_last [B, N, 2D]; uniform [T0 + steps, B, E, K] -> (predictions
+        [B, steps, N, 2D], edges or None, final state).  With the Markov decoder the burn-in steps run the prior only and the
+        final decoder state is None."""
         B, N, _ = x_last.shape
         dev = x_last.device
         lib, plan, ws, (send, recv, order, rowptr), (pf, pe, pd), scal = self._step_common(B, N, dev)
@@ -223,23 +230,25 @@ class _StepLoop:
             raise _lib.AetherHipError("this model has no built-in field query: step it with _fused_step")
         D, he, hd, R, K = self._step_sizes()
         E1 = self.encoder.recv_edges.shape[0]
+        entry = self.decoder._fused_entries[3]
         f32 = lambda t: t.detach().to(torch.float32).contiguous()
         T0 = 0 if burn_in is None else burn_in.shape[1]
         bi = None if T0 == 0 else f32(burn_in.transpose(0, 1))                       # [T0, B, N, 2D]
         xl = f32(x_last)
-        dh = f32(decoder_hidden).clone()
+        dh = f32(decoder_hidden).clone() if self.decoder._has_state else None
         h, c = f32(prior_hidden[0]).clone(), f32(prior_hidden[1]).clone()
         if uniform is None:
             uniform = torch.rand(T0 + steps, B, E1, K, device=dev)
         uf = f32(uniform.reshape(T0 + steps, B, E1, K))
         preds = torch.empty(steps, B, N, 2 * D, dtype=torch.float32, device=dev)
         edges = torch.empty(steps, B, E1, K, dtype=torch.float32, device=dev) if return_edges else None
-        st = lib.aether_s2s_rollout(C.byref(pf), C.byref(pe), C.byref(pd), plan.data_ptr(), *scal, send.data_ptr(),
-                                    recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), T0,
-                                    None if bi is None else bi.data_ptr(), int(steps), xl.data_ptr(), dh.data_ptr(),
-                                    h.data_ptr(), c.data_ptr(), uf.data_ptr(), ws.data_ptr(), ws.numel(), preds.data_ptr(),
-                                    None if edges is None else edges.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(st, "aether_s2s_rollout")
+        st = getattr(lib, entry)(C.byref(pf), C.byref(pe), C.byref(pd), plan.data_ptr(), *scal, send.data_ptr(),
+                                 recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), T0,
+                                 None if bi is None else bi.data_ptr(), int(steps), xl.data_ptr(),
+                                 *(() if dh is None else (dh.data_ptr(),)), h.data_ptr(), c.data_ptr(), uf.data_ptr(),
+                                 ws.data_ptr(), ws.numel(), preds.data_ptr(), None if edges is None else edges.data_ptr(),
+                                 torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(st, entry)
         return (preds.transpose(0, 1).contiguous(), None if edges is None else edges.transpose(0, 1).contiguous(),
                 (dh, (h, c)))
 
@@ -253,28 +262,30 @@ class _StepLoop:
             keep.append(fq[0]._ws)
         return keep
 
-    def _runner(self, field_fn, B, N, device, extra_key=()):
-        key = (B, N, str(device), _tensors_key(self)) + tuple(extra_key)
+    def _cached_runner(self, key, make):
+        """The captured runner of ``key``; one at a time (parameters moved or shapes changed: the old graphs are dropped)."""
         hit = self.__dict__.setdefault("_runners", {})
         if key not in hit:
-            hit.clear()                                            # parameters moved or shapes changed: drop old graphs
-            hit[key] = _StepRunner(self, field_fn, B, N, device)
+            hit.clear()
+            hit[key] = make()
         return hit[key]
+
+    def _uniform(self, uniform, T, B, N, device):
+        """The Gumbel draws of T steps as [T, B, E, K], drawn on the device when omitted."""
+        E, K = N * (N - 1), self.num_edge_types
+        if uniform is None:
+            uniform = torch.rand(T, B, E, K, device=device)
+        return uniform.reshape(T, B, E, K)
 
     def _graphed_rollout(self, burn_in, x_last, decoder_hidden, prior_hidden, steps, uniform, return_edges):
         """One hipGraph launch for the whole loop (``_RolloutRunner``); arguments as ``_fused_rollout``."""
         B, N = x_last.shape[0], x_last.shape[1]
         dev = x_last.device
         T0 = 0 if burn_in is None else burn_in.shape[1]
-        E, K = N * (N - 1), self.num_edge_types
-        if uniform is None:
-            uniform = torch.rand(T0 + steps, B, E, K, device=dev)
-        key = ("rollout", B, N, T0, int(steps), str(dev), _tensors_key(self))
-        hit = self.__dict__.setdefault("_runners", {})
-        if key not in hit:
-            hit.clear()                                            # parameters moved or shapes changed: drop old graphs
-            hit[key] = _RolloutRunner(self, B, N, T0, int(steps), dev)
-        preds, edges, state = hit[key](burn_in, x_last, decoder_hidden, prior_hidden, uniform)
+        uniform = self._uniform(uniform, T0 + steps, B, N, dev)
+        run = self._cached_runner(("rollout", B, N, T0, int(steps), str(dev), _tensors_key(self)),
+                                  lambda: _RolloutRunner(self, B, N, T0, int(steps), dev))
+        preds, edges, state = run(burn_in, x_last, decoder_hidden, prior_hidden, uniform)
         return preds, (edges if return_edges else None), state
 
     def _graphed(self, field_fn, burn_in, x_last, decoder_hidden, prior_hidden, steps, uniform, return_edges,
@@ -285,10 +296,9 @@ class _StepLoop:
         dev = x_last.device
         T0 = 0 if burn_in is None else burn_in.shape[1]
         E, K = N * (N - 1), self.num_edge_types
-        if uniform is None:
-            uniform = torch.rand(T0 + steps, B, E, K, device=dev)
-        uniform = uniform.reshape(T0 + steps, B, E, K)
-        run = self._runner(field_fn, B, N, dev, extra_key)
+        uniform = self._uniform(uniform, T0 + steps, B, N, dev)
+        run = self._cached_runner((B, N, str(dev), _tensors_key(self)) + tuple(extra_key),
+                                  lambda: _StepRunner(self, field_fn, B, N, dev))
         run.load(decoder_hidden=decoder_hidden, prior_hidden=prior_hidden)
         for t in range(T0):
             run.load(x=burn_in[:, t])
@@ -364,6 +374,11 @@ class _EvalLoss:
                 uniform=None if uniform is None else uniform[step])
             all_predictions.append(predictions)
         all_predictions = torch.stack(all_predictions, dim=1)
+        return self._loss_terms(inputs, all_predictions, prior_logits, posterior_logits, edges, return_edges, return_logits)
+
+    def _loss_terms(self, inputs, all_predictions, prior_logits, posterior_logits, edges, return_edges, return_logits):
+        """NLL of the predictions, KL of the posterior against the learned (and, if configured, the uniform) prior, and the
+        return shapes of aether.py:141-153."""
         target = inputs[:, 1:].to(torch.float32)
         loss_nll = self.nll(all_predictions, target)
         prob = torch.softmax(posterior_logits, dim=-1)
@@ -412,7 +427,6 @@ class _EvalLoss:
         return self._kl_reduce(kl_div, preds.size(0))
 
 
-
 class Aether(_StepLoop, _EvalLoss, nn.Module):
     def __init__(self, params, device="cuda"):
         super().__init__()
@@ -431,92 +445,6 @@ class Aether(_StepLoop, _EvalLoss, nn.Module):
         self._fq = [fq]                                                    # not a registered sub-module: no duplicate keys
         if device is not None:
             self.to(device)
-
-    # -- the Markov decoder (decoder_type 'ref_mlp'): the fused step / rollout on the aether_s2s_markov_* entries ----------
-    def _plan(self, device):
-        if not self._markov:
-            return super()._plan(device)
-        enc, dec = self.encoder, self.decoder
-        tensors = list(enc.parameters()) + list(enc.buffers()) + list(dec.parameters()) + \
-            list(self._fq[0].field_net.parameters())
-        key = (str(device),) + tuple((t.data_ptr(), t._version) for t in tensors)
-        hit = self.__dict__.get("_plan_cache")
-        if hit is None or hit[0] != key:
-            lib = _lib.load()
-            D, he, hd, R, K = self._step_sizes()
-            skip = 1 if dec.skip_first_edge_type else 0
-            pe, n_layers, prior_hidden = enc._param_struct(with_image=False)
-            nbytes = lib.aether_s2s_markov_plan_bytes(D, he, hd, R, n_layers, prior_hidden, K, skip)
-            if nbytes == 0:
-                raise _lib.AetherHipError("fused seq2seq step: encoder_hidden must be a multiple of 128, decoder_hidden of 32")
-            buf = hit[1] if hit is not None and hit[1].numel() == nbytes and hit[1].device == torch.device(device) else \
-                torch.empty(nbytes, dtype=torch.uint8, device=device)
-            pd, pf = dec._param_struct(), self._field_struct()
-            _lib.check(lib.aether_s2s_markov_plan_build(C.byref(pf), C.byref(pe), C.byref(pd), D, he, hd, R, n_layers,
-                                                        prior_hidden, K, skip, buf.data_ptr(), nbytes,
-                                                        torch.cuda.current_stream(device).cuda_stream),
-                       "aether_s2s_markov_plan_build")
-            hit = self.__dict__["_plan_cache"] = (key, buf)
-        return hit[1]
-
-    @torch.no_grad()
-    def _fused_step(self, x, decoder_hidden, prior_hidden, uniform, field=None):
-        """As _StepLoop._fused_step; with the Markov decoder ``decoder_hidden`` is ignored and comes back as None."""
-        if not self._markov:
-            return super()._fused_step(x, decoder_hidden, prior_hidden, uniform, field)
-        if not x.is_cuda:
-            raise _lib.AetherHipError("aether_amd seq2seq models run on an MI355X only; got a CPU tensor (there is no CPU fallback)")
-        B, N, _ = x.shape
-        dev = x.device
-        lib, plan, ws, (send, recv, order, rowptr), (pf, pe, pd), scal = self._step_common(B, N, dev)
-        D, he, hd, R, K = self._step_sizes()
-        E1 = self.encoder.recv_edges.shape[0]
-        f32 = lambda t: t.detach().to(torch.float32).contiguous()
-        xf, h0, c0, uf = f32(x), f32(prior_hidden[0]), f32(prior_hidden[1]), f32(uniform)
-        if xf.shape != (B, N, 2 * D) or h0.shape != (B, E1, R) or c0.shape != h0.shape or uf.numel() != B * E1 * K:
-            raise ValueError("fused step: input shapes do not match the model")
-        ff = None if field is None else f32(field)
-        out = torch.empty_like(xf)
-        h1, c1 = torch.empty_like(h0), torch.empty_like(c0)
-        edges = torch.empty(B, E1, K, dtype=torch.float32, device=dev)
-        st = lib.aether_s2s_markov_step(C.byref(pf), C.byref(pe), C.byref(pd), plan.data_ptr(), *scal, send.data_ptr(),
-                                        recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), xf.data_ptr(),
-                                        None if ff is None else ff.data_ptr(), h0.data_ptr(), c0.data_ptr(), uf.data_ptr(),
-                                        ws.data_ptr(), ws.numel(), out.data_ptr(), h1.data_ptr(), c1.data_ptr(),
-                                        edges.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(st, "aether_s2s_markov_step")
-        return out, None, (h1, c1), edges
-
-    @torch.no_grad()
-    def _fused_rollout(self, burn_in, x_last, decoder_hidden, prior_hidden, steps, uniform, return_edges):
-        """As _StepLoop._fused_rollout; with the Markov decoder the burn-in steps run the prior only and the final decoder
-        state is None."""
-        if not self._markov:
-            return super()._fused_rollout(burn_in, x_last, decoder_hidden, prior_hidden, steps, uniform, return_edges)
-        B, N, _ = x_last.shape
-        dev = x_last.device
-        lib, plan, ws, (send, recv, order, rowptr), (pf, pe, pd), scal = self._step_common(B, N, dev)
-        D, he, hd, R, K = self._step_sizes()
-        E1 = self.encoder.recv_edges.shape[0]
-        f32 = lambda t: t.detach().to(torch.float32).contiguous()
-        T0 = 0 if burn_in is None else burn_in.shape[1]
-        bi = None if T0 == 0 else f32(burn_in.transpose(0, 1))                       # [T0, B, N, 2D]
-        xl = f32(x_last)
-        h, c = f32(prior_hidden[0]).clone(), f32(prior_hidden[1]).clone()
-        if uniform is None:
-            uniform = torch.rand(T0 + steps, B, E1, K, device=dev)
-        uf = f32(uniform.reshape(T0 + steps, B, E1, K))
-        preds = torch.empty(steps, B, N, 2 * D, dtype=torch.float32, device=dev)
-        edges = torch.empty(steps, B, E1, K, dtype=torch.float32, device=dev) if return_edges else None
-        st = lib.aether_s2s_markov_rollout(C.byref(pf), C.byref(pe), C.byref(pd), plan.data_ptr(), *scal, send.data_ptr(),
-                                           recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), T0,
-                                           None if bi is None else bi.data_ptr(), int(steps), xl.data_ptr(), h.data_ptr(),
-                                           c.data_ptr(), uf.data_ptr(), ws.data_ptr(), ws.numel(), preds.data_ptr(),
-                                           None if edges is None else edges.data_ptr(),
-                                           torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(st, "aether_s2s_markov_rollout")
-        return (preds.transpose(0, 1).contiguous(), None if edges is None else edges.transpose(0, 1).contiguous(),
-                (None, (h, c)))
 
     def _calculate_loss_eval(self, inputs, teacher_forcing, return_edges, return_logits, use_prior_logits, uniform):
         """With the Markov decoder the teacher-forced steps do not depend on each other (no decoder state): they run as
@@ -548,18 +476,7 @@ class Aether(_StepLoop, _EvalLoss, nn.Module):
                                                              field_fn(predictions), uniform=uniform[step])
             all_predictions.append(predictions.unsqueeze(1))
         all_predictions = torch.cat(all_predictions, dim=1)
-        target = inputs[:, 1:].to(torch.float32)
-        loss_nll = self.nll(all_predictions, target)
-        prob = torch.softmax(posterior_logits, dim=-1)
-        loss_kl = self.kl_categorical_learned(prob, prior_logits)
-        if self.add_uniform_prior:
-            loss_kl = 0.5 * loss_kl + 0.5 * self.kl_categorical_avg(prob)
-        loss = (loss_nll + self.kl_coef * loss_kl).mean()
-        if return_edges:
-            return loss, loss_nll, loss_kl, edges
-        if return_logits:
-            return loss, loss_nll, loss_kl, posterior_logits, all_predictions
-        return loss, loss_nll, loss_kl
+        return self._loss_terms(inputs, all_predictions, prior_logits, posterior_logits, edges, return_edges, return_logits)
 
     def _calculate_loss_stepwise(self, inputs, teacher_forcing=True, uniform=None):
         """The evaluation loss through the per-step loop of _EvalLoss (one decoder call per time step): the cross-check of

@@ -74,6 +74,14 @@ class RecurrentDecoder(nn.Module):
         if device is not None:
             self.to(device)
 
+    # The model's fused step with this decoder (aether._StepLoop): the plan size / plan build / step / rollout entries, whether
+    # the step carries a decoder state, and what the two plan entries take after num_edge_types.
+    _fused_entries = ("aether_s2s_plan_bytes", "aether_s2s_plan_build", "aether_s2s_step", "aether_s2s_rollout")
+    _has_state = True
+
+    def _plan_extra(self):
+        return ()
+
     def get_initial_hidden(self, inputs):
         return torch.zeros(inputs.size(0), inputs.size(2), self.msg_out_shape, device=inputs.device)
 

@@ -298,11 +298,7 @@ class DynamicFieldAether(_StepLoop, _EvalLoss, nn.Module):
         # reference takes the burn-in's prior logits from the full-sequence encoder, :221-222: its prior path is causal, so
         # both give the same logits and state to rounding).
         all_predictions, all_edges = [], []
-        E1 = self.encoder.recv_edges.shape[0]
-        K = self.num_edge_types
-        if uniform is None:
-            uniform = torch.rand(T - 1 + int(prediction_steps), B, E1, K, device=inputs.device)
-        uniform = uniform.reshape(T - 1 + int(prediction_steps), B, E1, K)
+        uniform = self._uniform(uniform, T - 1 + int(prediction_steps), B, N, inputs.device)
         for step in range(T - 1):
             field = predicted_field[:, :, step].contiguous()
             predictions, decoder_hidden, prior_hidden, edges = self._fused_step(

@@ -74,6 +74,14 @@ class MarkovDecoder(nn.Module):
 
     _graph = RecurrentDecoder._graph
 
+    # (as RecurrentDecoder's)
+    _fused_entries = ("aether_s2s_markov_plan_bytes", "aether_s2s_markov_plan_build", "aether_s2s_markov_step",
+                      "aether_s2s_markov_rollout")
+    _has_state = False
+
+    def _plan_extra(self):
+        return (1 if self.skip_first_edge_type else 0,)
+
     def get_initial_hidden(self, inputs):
         return None
 
