@@ -139,6 +139,16 @@ SIGNATURES = {
     "aether_s2s_film_field": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
                                         C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.c_void_p]),
+    "aether_s2s_dynfield_plan_bytes": (C.c_size_t, [C.c_void_p] * 2 + [C.c_int] * 9),
+    "aether_s2s_dynfield_plan_build": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "aether_s2s_dynfield_step_workspace_bytes": (C.c_size_t, [C.c_int] * 7 + [C.c_int64, C.c_int64]),
+    "aether_s2s_dynfield_step": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 10 + [C.c_float, C.c_int64, C.c_int64] +
+                                 [C.c_int, C.c_void_p, C.c_size_t, C.c_int64, C.c_int] + [C.c_void_p] * 10 +
+                                 [C.c_void_p, C.c_size_t] + [C.c_void_p] * 7),
+    "aether_s2s_dynfield_rollout": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 10 + [C.c_float, C.c_int64, C.c_int64] +
+                                    [C.c_int, C.c_void_p, C.c_size_t, C.c_int64, C.c_int] + [C.c_void_p] * 4 +
+                                    [C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t] +
+                                    [C.c_void_p] * 3),
     "aether_knn_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "aether_knn_edges": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 6 +
                          [C.c_size_t, C.c_void_p]),

@@ -934,6 +934,7 @@ const char* aether_last_error(void) { return g_err; }
 #include "host_seq2seq.inc"
 #include "host_s2s_step.inc"
 #include "host_s2s_markov.inc"
+#include "host_s2s_dynfield.inc"
 #include "host_dynamicvars.inc"
 #include "host_dyn_step.inc"
 #include "host_sim.inc"

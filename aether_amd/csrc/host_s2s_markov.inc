@@ -73,6 +73,19 @@ int s2s_markov_step_impl(const S2SStepArgs& a, char* ws, const float* x_in, cons
     k_s2s_markov_agg<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(M, a.order, a.rowptr, edges, K, k0, aug, hd);
     return s2s_out_tail(a, ws, mp, aug, x_in, x_out, st);
 }
+
+// The Markov decoder's prepared weights (ku used edge types) into a plan of its layout.
+void s2s_plan_build_markov(const AetherS2SMarkovParams* mp, int D, int hd, int ku, const S2SPlanLayout& P, char* base,
+                           hipStream_t st) {
+    const S2SDims d(D);
+    auto fl = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
+    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    k_s2s_pad_rows<<<blocks((int64_t)hd * d.EAp), dim3(256), 0, st>>>(mp->lin1_w, d.EA, d.EA, fl(P.m_l1p), d.EAp, hd);
+    k_s2s_pad_rows<<<blocks((int64_t)hd * d.RFp), dim3(256), 0, st>>>(mp->res1_w, d.RF, d.RF, fl(P.m_r1p), d.RFp, hd);
+    k_s2s_markov_bias<<<blocks((int64_t)ku * hd), dim3(256), 0, st>>>(mp->lin2_b, ku, hd, fl(P.m_b2));
+    s2s_out_images(base, st, P, mp->out0_w, mp->out3_w, hd);
+    for (int k = 0; k < ku; ++k) s2s_image(base, st, P.m_i_l2[k], mp->lin2_w + (size_t)k * hd, hd, hd, ku * hd);    // type k's rows c Ku + k
+}
 }  // namespace
 
 size_t aether_s2s_markov_decoder_workspace_bytes(int num_dims, int hidden, int64_t n_nodes, int64_t n_edges) {
@@ -159,18 +172,11 @@ int aether_s2s_markov_plan_build(const AetherS2SFieldParams* fp, const AetherS2S
     if (int rc = s2s_plan_buffer_check("s2s_markov_plan_build",
                                        s2s_plan_size(D, he, hd, rnn_hidden, prior_layers, prior_hidden, K, ku), plan, plan_bytes))
         return rc;
-    const S2SDims d(D);
     const S2SPlanLayout P(D, he, hd, K, rnn_hidden, prior_layers, prior_hidden, ku);
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)plan;
-    auto fl = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
-    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     s2s_plan_build_front(fp, pp, D, he, rnn_hidden, prior_layers, prior_hidden, P, base, st);
-    k_s2s_pad_rows<<<blocks((int64_t)hd * d.EAp), dim3(256), 0, st>>>(mp->lin1_w, d.EA, d.EA, fl(P.m_l1p), d.EAp, hd);
-    k_s2s_pad_rows<<<blocks((int64_t)hd * d.RFp), dim3(256), 0, st>>>(mp->res1_w, d.RF, d.RF, fl(P.m_r1p), d.RFp, hd);
-    k_s2s_markov_bias<<<blocks((int64_t)ku * hd), dim3(256), 0, st>>>(mp->lin2_b, ku, hd, fl(P.m_b2));
-    s2s_out_images(base, st, P, mp->out0_w, mp->out3_w, hd);
-    for (int k = 0; k < ku; ++k) s2s_image(base, st, P.m_i_l2[k], mp->lin2_w + (size_t)k * hd, hd, hd, ku * hd);    // type k's rows c Ku + k
+    s2s_plan_build_markov(mp, D, hd, ku, P, base, st);
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }

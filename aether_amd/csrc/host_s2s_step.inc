@@ -22,12 +22,13 @@ struct S2SPlanLayout {
     size_t fimg, res1p, bn, p1p[4], wr, wi, wn, br, bi, bn_, lb, lbp, total;
     size_t i_mlp4e, i_mlp4_3, i_ih, i_hh, i_prior[4], i_msg2[4], i_pmsg1[4], i_pmsg2[4];       // fp16 x 2 images (0: none)
     size_t i_f0, i_f2, i_mlp3_0, i_mlp3_3, i_ps, i_pr, i_a[4], i_s[4], i_wr, i_wi, i_wn, i_hh2, i_out0, i_out3;   // node-level layers
+    size_t i_film1 = 0, i_film2 = 0;     // FiLM field net (mlp_hidden > 0): linear_1 [mh][he], linear_2 [mh][mh]; no i_f0 / i_f2 then
     int ldg;
     // Markov decoder (markov_ku >= 0 used edge types; the recurrent decoder's tensors are then not in the plan): padded lin1 /
     // res1, lin2's bias permuted from c Ku + k to k h + c, and the images of lin1 and of lin2's per-type h x h blocks
     size_t m_l1p = 0, m_r1p = 0, m_b2 = 0, m_i_l1 = 0, m_i_l2[4] = {0, 0, 0, 0};
     static bool splittable(int M, int Kk) { return M % 128 == 0 && Kk % 32 == 0; }
-    S2SPlanLayout(int D, int he, int hd, int K, int R, int prior_layers = 1, int ph = 0, int markov_ku = -1) {
+    S2SPlanLayout(int D, int he, int hd, int K, int R, int prior_layers = 1, int ph = 0, int markov_ku = -1, int mlp_hidden = 0) {
         const S2SDims d(D);
         const bool rec = markov_ku < 0;
         const int Kr = rec ? K : 0;
@@ -50,7 +51,9 @@ struct S2SPlanLayout {
             i_msg2[k] = k < Kr ? image(hd, hd) : 0; i_pmsg1[k] = k < Kr ? image(hd, d.EAp) : 0; i_pmsg2[k] = k < Kr ? image(hd, hd) : 0;
             i_a[k] = k < Kr ? image(hd, hd) : 0; i_s[k] = k < Kr ? image(hd, hd) : 0;
         }
-        i_f0 = image(he, he); i_f2 = image(he, he); i_mlp3_0 = image(he, he); i_mlp3_3 = image(he, he); i_ps = image(he, he);
+        if (mlp_hidden > 0) { i_f0 = i_f2 = 0; i_film1 = image(mlp_hidden, he); i_film2 = image(mlp_hidden, mlp_hidden); }
+        else { i_f0 = image(he, he); i_f2 = image(he, he); }
+        i_mlp3_0 = image(he, he); i_mlp3_3 = image(he, he); i_ps = image(he, he);
         i_pr = image(he, he);
         if (rec) { i_wr = image(hd, ldg); i_wi = image(hd, ldg); i_wn = image(hd, S2S_RFG + hd); i_hh2 = image(hd, hd); }
         else i_wr = i_wi = i_wn = i_hh2 = 0;
@@ -69,12 +72,14 @@ struct S2SStepLayout {
         logits, edges, lists, counts, A, S, Tm, T1p, M1, M2, wide, rp, ip, np_, hh, o1, o2, pred, xa, xb, da, db, ha, hb, ca, cb,
         total;
     int splits;
-    S2SStepLayout(int D, int he, int hd, int R, int ph, int K, int64_t Nn, int64_t E) {
+    // mlp_hidden > 0: the field query is the FiLM net, whose hidden rows (fh1, fh2) are mlp_hidden wide
+    S2SStepLayout(int D, int he, int hd, int R, int ph, int K, int64_t Nn, int64_t E, int mlp_hidden = 0) {
         const S2SDims d(D);
         size_t off = 0;
         auto take = [&](size_t floats) { size_t o = off; off = align_up(off + floats * 4, 256); return o; };
         const size_t nn = (size_t)Nn, ee = (size_t)E, h = (size_t)he, g = (size_t)hd;
-        gamma = take(nn * h); fh1 = take(nn * h); fh2 = take(nn * h); field = take(nn * D);
+        const size_t fw = (size_t)(mlp_hidden > he ? mlp_hidden : he);
+        gamma = take(nn * h); fh1 = take(nn * fw); fh2 = take(nn * fw); field = take(nn * D);
         ext = take(nn * 3 * D); rel = take(nn * d.RF); relp = take(nn * d.RFp); Rinv = take(nn * D * D);
         ea = take(ee * d.EA); eap = take(ee * d.EAp); epos = take(ee * d.EP);
         bimg = take((filt_bimg_bytes(E, (int)h) + 3) / 4);
@@ -119,6 +124,11 @@ bool s2s_jobs_take_split(const S2SJobs& T) {
 
 int s2s_launch_jobs(S2SJobs& T, hipStream_t st) {
     if (T.n <= 0) return AETHER_OK;
+    for (int t = 0; t < T.n; ++t) {
+        const S2SJob& J = T.j[t];
+        if (J.film_gamma != nullptr && (J.film_beta == nullptr || J.film_rows <= 0 || J.act == 5))
+            return fail(AETHER_EINVAL, "s2s_step: a FiLM job needs gamma, beta and rows per graph, and is never the LSTM cell job");
+    }
     bool big = false, wide = false, ksplit = false;
     {
         int best = 0;
@@ -223,6 +233,13 @@ struct S2SStepArgs : S2SSizes {
     bool field_images;         // the plan was built with the field net's parameters (images of its two hidden layers)
     S2SPlanLayout P;
     S2SStepLayout L;
+    // The FiLM field query of the dynamic-field model (film != nullptr; fp is null then): mod = gamma_1 | beta_1 | gamma_2 |
+    // beta_2, each [batch][mlp_hidden] (aether_s2s_film_modulation); node n belongs to graph n / num_objects
+    const AetherS2SFilmParams* film = nullptr;
+    int mlp_hidden = 0;
+    const float* mod = nullptr;
+    int64_t batch = 0;
+    int num_objects = 0;
 };
 
 // The state a step reads and the one it writes: x [Nn][2D], dh [Nn][hd] (null with the Markov decoder, which has none),
@@ -261,7 +278,20 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
     const int ldg = P.ldg;
     // ---- field query (aether.py:86-90); its first layer shares a launch with first_jobs
     T.n = 0;
-    if (!ext_field) {
+    const int mh = a.mlp_hidden;
+    const size_t mplane = (size_t)a.batch * mh;
+    if (!ext_field && a.film) {
+        // the FiLM net (dynamic_field_aether.py:117-134, nn/nn/filmed_network.py:27-35): linear_1 - FiLM - SiLU here, linear_2 -
+        // FiLM - SiLU below, linear_3 in k_s2s_node_prep
+        const int half = he / 2;
+        const unsigned rb = (unsigned)((Nn * half + 255) / 256);
+        dispatch_dim(D, [&](auto DD) {
+            k_s2s_rff<decltype(DD)::value><<<dim3(rb), dim3(256), 0, st>>>(x_in, 2 * D, a.film->B, half, wp(L.gamma), Nn);
+        });
+        S2SJob J = s2s_job(1, a.film->lin1_w, he, a.film->lin1_b, wp(L.gamma), he, wp(L.fh1), mh, mh, he, Nn);
+        J.film_gamma = a.mod; J.film_beta = a.mod + mplane; J.film_rows = a.num_objects; J.Wimg = im(P.i_film1);
+        T.j[T.n++] = J;
+    } else if (!ext_field) {
         const int half = he / 2;
         const unsigned rb = (unsigned)((Nn * half + 255) / 256);
         dispatch_dim(D, [&](auto DD) {
@@ -272,7 +302,12 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
     }
     if (int rc = first_jobs(T)) return rc;
     if (int rc = s2s_launch_jobs(T, st)) return rc;
-    if (!ext_field) {
+    if (!ext_field && a.film) {
+        S2SJob J = s2s_job(1, a.film->lin2_w, mh, a.film->lin2_b, wp(L.fh1), mh, wp(L.fh2), mh, mh, mh, Nn);
+        J.film_gamma = a.mod + 2 * mplane; J.film_beta = a.mod + 3 * mplane; J.film_rows = a.num_objects; J.Wimg = im(P.i_film2);
+        T.n = 0; T.j[T.n++] = J;
+        if (int rc = s2s_launch_jobs(T, st)) return rc;
+    } else if (!ext_field) {
         T.n = 0; T.j[T.n++] = s2s_job(1, a.fp->w2, he, a.fp->b2, wp(L.fh1), he, wp(L.fh2), he, he, he, Nn);
         T.j[T.n - 1].Wimg = a.field_images ? im(P.i_f2) : nullptr;
         if (int rc = s2s_launch_jobs(T, st)) return rc;
@@ -282,13 +317,14 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
     int64_t* lists = reinterpret_cast<int64_t*>(ws + L.lists);
     {
         const float* fh2 = ext_field ? nullptr : wp(L.fh2);
-        const float* w4 = ext_field ? nullptr : a.fp->w4;
-        const float* b4 = ext_field ? nullptr : a.fp->b4;
+        const float* w4 = ext_field ? nullptr : a.film ? a.film->lin3_w : a.fp->w4;
+        const float* b4 = ext_field ? nullptr : a.film ? a.film->lin3_b : a.fp->b4;
+        const int fk = a.film ? mh : he;                        // width of the last hidden layer of the field query
         float* fout = ext_field ? nullptr : wp(L.field);
         const dim3 nb4((unsigned)((Nn + 3) / 4));
         dispatch_dim(D, [&](auto DD) {
             constexpr int Dc = decltype(DD)::value;
-            k_s2s_node_prep<Dc><<<nb4, dim3(256), 0, st>>>(x_in, ext_field, fh2, w4, b4, he, fout, wp(L.ext), wp(L.rel), wp(L.Rinv),
+            k_s2s_node_prep<Dc><<<nb4, dim3(256), 0, st>>>(x_in, ext_field, fh2, w4, b4, fk, fout, wp(L.ext), wp(L.rel), wp(L.Rinv),
                                                            wp(L.relp), d.RFp, wp(L.wide), ldg, counts, Nn);
             k_s2s_edge_prep<Dc><<<blocks(E), dim3(256), 0, st>>>(wp(L.ext), a.send, a.recv, wp(L.rel), a.polar, wp(L.ea), wp(L.eap),
                                                                  wp(L.epos), E);
@@ -544,10 +580,12 @@ int s2s_run_step(const char* what, const S2SStepArgs& a, void* workspace, size_t
 }
 
 // burn_in [T0][Nn][2D] teacher-forced, then `steps` steps from inputs; decoder_state (null: the Markov decoder), h, c are
-// read first and written last.
+// read first and written last.  burn_in_field [T0][Nn][D] (or null): the field of the burn-in frames, known before the loop
+// starts (one batched query instead of one per step); the prediction steps always query theirs.
 int s2s_run_rollout(const char* what, const S2SStepArgs& a, void* workspace, size_t workspace_bytes, int burn_in_steps,
                     const float* burn_in, int steps, const float* inputs, float* decoder_state, float* h, float* c,
-                    const float* uniform, float* predictions, float* edges_out, void* stream) {
+                    const float* uniform, float* predictions, float* edges_out, void* stream,
+                    const float* burn_in_field = nullptr) {
     if (workspace_bytes < a.L.total) return s2s_fail(AETHER_ESPACE, what, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
@@ -569,7 +607,8 @@ int s2s_run_rollout(const char* what, const S2SStepArgs& a, void* workspace, siz
         const bool teacher = t < burn_in_steps, decode = !teacher || !a.mp;
         float* xout = !teacher ? predictions + (size_t)(t - burn_in_steps) * xstep : decode ? wp(L.xa) : nullptr;
         float* eout = (!teacher && edges_out) ? edges_out + (size_t)(t - burn_in_steps) * ustep : nullptr;
-        if (int rc = s2s_step(a, ws, {xcur, dcur, hcur, ccur}, nullptr, uniform + (size_t)t * ustep, {xout, dnext, hnext, cnext},
+        const float* ext = teacher && burn_in_field ? burn_in_field + (size_t)t * a.Nn * a.D : nullptr;
+        if (int rc = s2s_step(a, ws, {xcur, dcur, hcur, ccur}, ext, uniform + (size_t)t * ustep, {xout, dnext, hnext, cnext},
                               eout, decode, st)) return rc;
         std::swap(dcur, dnext); std::swap(hcur, hnext); std::swap(ccur, cnext);
         if (t + 1 < burn_in_steps) xcur = burn_in + (size_t)(t + 1) * xstep;
@@ -638,28 +677,13 @@ void s2s_plan_build_front(const AetherS2SFieldParams* fp, const AetherS2SPriorPa
     s2s_image(base, st, P.i_ps, pp->mlp4_w0, he, he, 3 * he);
     s2s_image(base, st, P.i_pr, pp->mlp4_w0 + he, he, he, 3 * he);
 }
-}  // namespace
 
-size_t aether_s2s_plan_bytes(int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
-                             int prior_hidden, int num_edge_types) {
-    return s2s_plan_size(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden, num_edge_types, -1);
-}
-
-int aether_s2s_plan_build(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp, const AetherS2SDecoderParams* dp, int num_dims,
-                          int encoder_hidden,
-                          int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, void* plan,
-                          size_t plan_bytes, void* stream) {
-    if (!pp || !dp || !plan) return fail(AETHER_EINVAL, "s2s_plan_build: null pointer");
-    const int D = num_dims, he = encoder_hidden, hd = decoder_hidden, K = num_edge_types;
-    if (int rc = s2s_plan_buffer_check("s2s_plan_build", s2s_plan_size(D, he, hd, rnn_hidden, prior_layers, prior_hidden, K, -1),
-                                       plan, plan_bytes)) return rc;
+// The recurrent decoder's prepared weights into a plan of its layout.
+void s2s_plan_build_recurrent(const AetherS2SDecoderParams* dp, int D, int hd, int K, const S2SPlanLayout& P, char* base,
+                              hipStream_t st) {
     const S2SDims d(D);
-    const S2SPlanLayout P(D, he, hd, K, rnn_hidden, prior_layers, prior_hidden);
-    hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)plan;
     auto fl = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-    s2s_plan_build_front(fp, pp, D, he, rnn_hidden, prior_layers, prior_hidden, P, base, st);
     for (int k = 0; k < K; ++k)
         k_s2s_pad_rows<<<blocks((int64_t)hd * d.EAp), dim3(256), 0, st>>>(dp->pmsg_fc1_w[k], d.EA, d.EA, fl(P.p1p[k]), d.EAp, hd);
     const int64_t gitems = (int64_t)hd * P.ldg;
@@ -684,6 +708,27 @@ int aether_s2s_plan_build(const AetherS2SFieldParams* fp, const AetherS2SPriorPa
         s2s_image(base, st, P.i_pmsg1[k], fl(P.p1p[k]), hd, d.EAp, d.EAp);            // the zero-padded copy built above
         s2s_image(base, st, P.i_pmsg2[k], dp->pmsg_fc2_w[k], hd, hd, hd);
     }
+}
+}  // namespace
+
+size_t aether_s2s_plan_bytes(int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
+                             int prior_hidden, int num_edge_types) {
+    return s2s_plan_size(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden, num_edge_types, -1);
+}
+
+int aether_s2s_plan_build(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp, const AetherS2SDecoderParams* dp, int num_dims,
+                          int encoder_hidden,
+                          int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, void* plan,
+                          size_t plan_bytes, void* stream) {
+    if (!pp || !dp || !plan) return fail(AETHER_EINVAL, "s2s_plan_build: null pointer");
+    const int D = num_dims, he = encoder_hidden, hd = decoder_hidden, K = num_edge_types;
+    if (int rc = s2s_plan_buffer_check("s2s_plan_build", s2s_plan_size(D, he, hd, rnn_hidden, prior_layers, prior_hidden, K, -1),
+                                       plan, plan_bytes)) return rc;
+    const S2SPlanLayout P(D, he, hd, K, rnn_hidden, prior_layers, prior_hidden);
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)plan;
+    s2s_plan_build_front(fp, pp, D, he, rnn_hidden, prior_layers, prior_hidden, P, base, st);
+    s2s_plan_build_recurrent(dp, D, hd, K, P, base, st);
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }

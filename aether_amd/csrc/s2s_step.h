@@ -34,6 +34,10 @@ struct S2SJob {
     // unit u: k_s2s_gemm_image with gate_units = R, bias permuted alike), so a lane's four accumulator rows are (i, f, g, o) of
     // ONE unit: the cell update runs in the epilogue -- c1 = sig(f) c0 + sig(i) tanh(g), h1 = sig(o) tanh(c1) -- and Y is not written
     const float* cell_c0; float* cell_h1; float* cell_c1;       // [N][M / 4]
+    // FiLM per graph (nn/nn/film.py:58-60), as k_s2s_linear's: v = (1 + film_gamma[g][m]) v + film_beta[g][m] with g = n / film_rows
+    // (n: the row of Y), after the bias and the gathers and before act; both [graphs][M].  Never with act == 5.
+    const float* film_gamma; const float* film_beta;
+    int film_rows;
 };
 struct S2SJobs { int n; S2SJob j[S2S_MAX_JOBS]; };
 
@@ -154,11 +158,17 @@ k_s2s_linear_jobs(const S2SJobs jobs) {
         if (J.yidx != nullptr) n = J.yidx[n];
         const float* g1 = J.g1 != nullptr ? J.g1 + (size_t)J.i1[nsrc] * M : nullptr;
         const float* g2 = J.g2 != nullptr ? J.g2 + (size_t)J.i2[nsrc] * M : nullptr;
+        const size_t film_off = J.film_gamma != nullptr ? (size_t)(n / J.film_rows) * M : 0;     // per row: a tile may hold rows of several graphs
 #pragma unroll
         for (int mb = 0; mb < MT; ++mb) {
             const int m = m0 + 16 * mb + 4 * q;
             f32x4 v = acc[mb][nb];
             if (g1 != nullptr && m + 3 < M) v += ld4(g1 + m) + ld4(g2 + m);
+            if (J.film_gamma != nullptr) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (m + r < M) v[r] = (1.0f + J.film_gamma[film_off + m + r]) * v[r] + J.film_beta[film_off + m + r];
+            }
             if (act == 1) v = silu4(v);
             else if (act == 2) {
 #pragma unroll
@@ -472,6 +482,7 @@ k_s2s_gemm_split(const S2SJobs jobs) {
         const float* g1 = J.g1 != nullptr ? J.g1 + (size_t)J.i1[nsrc] * M : nullptr;
         const float* g2 = J.g2 != nullptr ? J.g2 + (size_t)J.i2[nsrc] * M : nullptr;
         const float sc = J.scale != nullptr ? J.scale[(size_t)n * J.sstride] : 1.0f;
+        const size_t film_off = J.film_gamma != nullptr ? (size_t)(n / J.film_rows) * M : 0;     // per row: a tile may hold rows of several graphs
         if (act == 5) {                                       // LSTM cell on the gate pre-activations (rows interleaved by unit)
             const int Ru = M >> 2;
 #pragma unroll
@@ -491,6 +502,11 @@ k_s2s_gemm_split(const S2SJobs jobs) {
             const int m = m0 + 16 * mb + 4 * q;
             f32x4 v = acc[mb][nb] * inv_xs[nb];
             if (g1 != nullptr) v += ld4(g1 + m) + ld4(g2 + m);
+            if (J.film_gamma != nullptr) {
+                const f32x4 ga = ld4(J.film_gamma + film_off + m), be = ld4(J.film_beta + film_off + m);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = (1.0f + ga[r]) * v[r] + be[r];
+            }
             if (act == 1) v = silu4(v);
             else if (act == 2) {
 #pragma unroll
@@ -693,6 +709,7 @@ k_s2s_gemm_split_r1(const S2SJobs jobs) {
         const float* g1 = J.g1 != nullptr ? J.g1 + (size_t)J.i1[nsrc] * M : nullptr;
         const float* g2 = J.g2 != nullptr ? J.g2 + (size_t)J.i2[nsrc] * M : nullptr;
         const float sc = J.scale != nullptr ? J.scale[(size_t)n * J.sstride] : 1.0f;
+        const size_t film_off = J.film_gamma != nullptr ? (size_t)(n / J.film_rows) * M : 0;     // per row: a tile may hold rows of several graphs
         if (act == 5) {                                       // LSTM cell on the gate pre-activations (rows interleaved by unit)
             const int Ru = M >> 2;
 #pragma unroll
@@ -712,6 +729,11 @@ k_s2s_gemm_split_r1(const S2SJobs jobs) {
             const int m = m0 + 16 * mb + 4 * q;
             f32x4 v = acc[mb][nb] * inv_xs[nb];
             if (g1 != nullptr) v += ld4(g1 + m) + ld4(g2 + m);
+            if (J.film_gamma != nullptr) {
+                const f32x4 ga = ld4(J.film_gamma + film_off + m), be = ld4(J.film_beta + film_off + m);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = (1.0f + ga[r]) * v[r] + be[r];
+            }
             if (act == 1) v = silu4(v);
             else if (act == 2) {
 #pragma unroll
@@ -733,7 +755,8 @@ k_s2s_gemm_split_r1(const S2SJobs jobs) {
 
 // Node side of the local frames in one launch (last field layer + k_s2s_extend + k_s2s_aug_nodes + two k_s2s_pad_rows):
 // a wave per node.  With fh2 != nullptr the wave first finishes the field query, field[n] = W4 fh2[n] + b4 (D rows of he
-// weights: 64 lanes x he / 64 products each, butterfly sum); then lane 0 builds ext = [inputs | field], rel_feat (7D + O
+// weights -- he: the width of the field net's last hidden layer, encoder_hidden or the FiLM net's mlp_hidden, a multiple of
+// 4 -- 64 lanes x he / 64 products each, butterfly sum); then lane 0 builds ext = [inputs | field], rel_feat (7D + O
 // columns), Rinv and the zero-padded copies of rel_feat at the row strides the dense layers read (the prior's res1 and the
 // first columns of the decoder's wide gate row).  Also clears the per-type edge counters of the step.
 template <int D>

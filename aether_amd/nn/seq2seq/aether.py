@@ -116,85 +116,127 @@ class _RolloutRunner:
         return preds.clone(), edges.clone(), (None if dh is None else dh.clone(), (h.clone(), c.clone()))
 
 
+class _FieldHook:
+    """What the fused step needs to know of a model's built-in field query.  ``struct``: its parameter struct (None: the model
+    has none and hands the field in); ``tensors``: those whose change rebuilds the plan; ``entries``: (plan bytes, plan build,
+    workspace bytes, step, rollout) when the field query has library entries of its own -- they take both decoder structs, one
+    of them None, nullable decoder-state pointers and the step a ``field_out`` pointer -- else None: the decoder's;
+    ``plan_tail`` / ``ws_tail``: the scalars that follow num_edge_types in the plan / workspace size calls; ``call(B, N)``: the
+    arguments that follow n_edges in a step / rollout call; ``burn_field(burn_in [T0, B, N, 2D] or None)``: the arguments that
+    follow burn_in in a rollout call (the shared entries take the burn-in frames' field, queried in one batch)."""
+
+    def __init__(self, struct, tensors, entries=None, plan_tail=(), ws_tail=(), call=lambda B, N: (),
+                 burn_field=lambda burn_in: ()):
+        self.struct, self.tensors, self.entries = struct, tensors, entries
+        self.plan_tail, self.ws_tail, self.call, self.burn_field = plan_tail, ws_tail, call, burn_field
+
+    def decoders(self, dec, pd):
+        """The decoder argument(s) of an entry call."""
+        if self.entries is None:
+            return (C.byref(pd),)
+        return (C.byref(pd), None) if dec._has_state else (None, C.byref(pd))
+
+    def state(self, t):
+        """A decoder-state pointer argument: the Markov entries of a decoder take none, the shared ones a null pointer."""
+        if t is not None:
+            return (t.data_ptr(),)
+        return () if self.entries is None else (None,)
+
+
 class _StepLoop:
     """Mixin of the two seq2seq models: the fused autoregressive step (``aether_s2s_step`` / ``aether_s2s_rollout`` on a
     cached plan of prepared weights) and the burn-in / prediction loops on a cached ``_StepRunner``."""
+
+    def _field_hook(self):
+        """The built-in field query of the fused step (``_FieldHook``): the plain field net of ``Aether``."""
+        fq = getattr(self, "_fq", None)
+        dec = self.decoder
+        if fq is None:
+            return _FieldHook(None, [], plan_tail=dec._plan_extra())
+        fn, ce = fq[0].field_net, fq[0].coordinate_embedding
+        pf = _S2SFieldParams(*[t.data_ptr() for t in (ce.B, fn[0].weight, fn[0].bias, fn[2].weight, fn[2].bias,
+                                                      fn[4].weight, fn[4].bias)])
+        return _FieldHook(pf, list(fn.parameters()), plan_tail=dec._plan_extra())
+
+    def _entries(self, hook):
+        """Names of (plan bytes, plan build, workspace bytes, step, rollout)."""
+        if hook.entries is not None:
+            return hook.entries
+        e = self.decoder._fused_entries
+        return (e[0], e[1], "aether_s2s_step_workspace_bytes", e[2], e[3])
 
     def _step_sizes(self):
         enc, dec = self.encoder, self.decoder
         return (self.num_dims, enc.hidden_size, dec.msg_out_shape, enc.rnn_hidden_size, self.num_edge_types)
 
-    def _plan(self, device):
+    def _plan(self, device, hook=None):
         """Prepared weights of the fused step (``aether_s2s_plan_build`` / ``aether_s2s_markov_plan_build``), rebuilt --
         into the same buffer, which captured graphs point at -- whenever an encoder / decoder tensor moved or was written to."""
         enc, dec = self.encoder, self.decoder
-        fq = getattr(self, "_fq", None)
-        tensors = list(enc.parameters()) + list(enc.buffers()) + list(dec.parameters())
-        if fq is not None:
-            tensors += list(fq[0].field_net.parameters())
+        hook = hook or self._field_hook()
+        tensors = list(enc.parameters()) + list(enc.buffers()) + list(dec.parameters()) + hook.tensors
         key = (str(device),) + tuple((t.data_ptr(), t._version) for t in tensors)
         hit = self.__dict__.get("_plan_cache")
         if hit is None or hit[0] != key:
             lib = _lib.load()
-            bytes_entry, build_entry = dec._fused_entries[:2]
-            extra = dec._plan_extra()
+            bytes_entry, build_entry = self._entries(hook)[:2]
+            extra = hook.plan_tail
             D, he, hd, R, K = self._step_sizes()
             pe, n_layers, prior_hidden = enc._param_struct(with_image=False)
-            nbytes = getattr(lib, bytes_entry)(D, he, hd, R, n_layers, prior_hidden, K, *extra)
+            pd = dec._param_struct()
+            both = hook.decoders(dec, pd) if hook.entries is not None else ()     # (the shared entries size the plan by decoder)
+            nbytes = getattr(lib, bytes_entry)(*both, D, he, hd, R, n_layers, prior_hidden, K, *extra)
             if nbytes == 0:
                 raise _lib.AetherHipError("fused seq2seq step: encoder_hidden must be a multiple of 128, decoder_hidden of 32")
             buf = hit[1] if hit is not None and hit[1].numel() == nbytes and hit[1].device == torch.device(device) else \
                 torch.empty(nbytes, dtype=torch.uint8, device=device)
-            pd = dec._param_struct()
-            pf = self._field_struct()
-            _lib.check(getattr(lib, build_entry)(None if pf is None else C.byref(pf), C.byref(pe), C.byref(pd), D, he, hd, R,
-                                                 n_layers, prior_hidden, K, *extra, buf.data_ptr(), nbytes,
+            pf = hook.struct
+            _lib.check(getattr(lib, build_entry)(None if pf is None else C.byref(pf), C.byref(pe), *hook.decoders(dec, pd), D, he,
+                                                 hd, R, n_layers, prior_hidden, K, *extra, buf.data_ptr(), nbytes,
                                                  torch.cuda.current_stream(device).cuda_stream), build_entry)
             hit = self.__dict__["_plan_cache"] = (key, buf)
         return hit[1]
 
     def _field_struct(self):
-        """Parameter struct of the built-in field query, or None (the dynamic-field model hands its field in)."""
-        fq = getattr(self, "_fq", None)
-        if fq is None:
-            return None
-        fn, ce = fq[0].field_net, fq[0].coordinate_embedding
-        return _S2SFieldParams(*[t.data_ptr() for t in (ce.B, fn[0].weight, fn[0].bias, fn[2].weight, fn[2].bias,
-                                                        fn[4].weight, fn[4].bias)])
+        """Parameter struct of the built-in field query, or None (a model that hands its field in)."""
+        return self._field_hook().struct
 
     def _step_common(self, B, N, device):
-        """(plan, workspace, graph arrays, parameter structs, scalar arguments) of the fused step for B graphs of N objects."""
+        """(plan, workspace, graph arrays, parameter structs, scalar arguments, field hook) of the fused step for B graphs of N
+        objects; the scalar arguments end with the field hook's."""
         if self.encoder.training:
             raise _lib.AetherHipError("the prior step uses BatchNorm running statistics: call .eval() first")
         lib = _lib.load()
         enc, dec = self.encoder, self.decoder
         D, he, hd, R, K = self._step_sizes()
         E1 = enc.recv_edges.shape[0]
-        plan = self._plan(device)
+        hook = self._field_hook()                                    # once per call: it checks and packs the field's tensors
+        plan = self._plan(device, hook)
         pe, n_layers, prior_hidden = enc._param_struct(with_image=False)
         pd = dec._param_struct()
-        need = lib.aether_s2s_step_workspace_bytes(D, he, hd, R, prior_hidden, K, B * N, B * E1)
+        need = getattr(lib, self._entries(hook)[2])(D, he, hd, R, prior_hidden, K, *hook.ws_tail, B * N, B * E1)
         ws = self.__dict__.get("_step_ws")
         if ws is None or ws.numel() < need or ws.device != torch.device(device):
             ws = self.__dict__["_step_ws"] = torch.empty(need, dtype=torch.uint8, device=device)
-        pf = self._field_struct()
+        pf = hook.struct
         scal = (D, he, hd, R, n_layers, prior_hidden, K, 1 if dec.skip_first_edge_type else 0,
-                1 if enc.pos_representation == "polar" else 0, N, float(self.gumbel_temp), B * N, B * E1)
-        return lib, plan, ws, enc._graph(B, N, device), (pf, pe, pd), scal
+                1 if enc.pos_representation == "polar" else 0, N, float(self.gumbel_temp), B * N, B * E1) + tuple(hook.call(B, N))
+        return lib, plan, ws, enc._graph(B, N, device), (pf, pe, pd), scal, hook
 
     @torch.no_grad()
-    def _fused_step(self, x, decoder_hidden, prior_hidden, uniform, field=None):
+    def _fused_step(self, x, decoder_hidden, prior_hidden, uniform, field=None, return_field=False):
         """One autoregressive step: x [B, N, 2D], decoder_hidden [B, N, hd], prior_hidden (h, c) [B, E, rnn], uniform
         [B, E, K]; ``field`` [B, N, D] replaces the built-in field query -> (predictions, decoder_hidden, (h, c), edges).
-        With the Markov decoder, which has no state, ``decoder_hidden`` is ignored and comes back as None."""
+        With the Markov decoder, which has no state, ``decoder_hidden`` is ignored and comes back as None.
+        ``return_field`` (models whose step entry has a ``field_out``): also the field [B, N, D] the built-in query computed."""
         if not x.is_cuda:
             raise _lib.AetherHipError("aether_amd seq2seq models run on an MI355X only; got a CPU tensor (there is no CPU fallback)")
         B, N, _ = x.shape
         dev = x.device
-        lib, plan, ws, (send, recv, order, rowptr), (pf, pe, pd), scal = self._step_common(B, N, dev)
+        lib, plan, ws, (send, recv, order, rowptr), (pf, pe, pd), scal, hook = self._step_common(B, N, dev)
         D, he, hd, R, K = self._step_sizes()
         E1 = self.encoder.recv_edges.shape[0]
-        entry = self.decoder._fused_entries[2]
+        entry = self._entries(hook)[3]
         f32 = lambda t: t.detach().to(torch.float32).contiguous()
         xf, h0, c0, uf = f32(x), f32(prior_hidden[0]), f32(prior_hidden[1]), f32(uniform)
         dhf = f32(decoder_hidden) if self.decoder._has_state else None
@@ -208,29 +250,38 @@ class _StepLoop:
         dh_out = None if dhf is None else torch.empty_like(dhf)
         h1, c1 = torch.empty_like(h0), torch.empty_like(c0)
         edges = torch.empty(B, E1, K, dtype=torch.float32, device=dev)
-        ptr = lambda t: () if t is None else (t.data_ptr(),)              # the Markov entries take no decoder state
-        st = getattr(lib, entry)(None if pf is None else C.byref(pf), C.byref(pe), C.byref(pd), plan.data_ptr(), *scal,
+        if return_field and (hook.entries is None or ff is not None):
+            raise _lib.AetherHipError("return_field: only the field a FiLM step computes itself can be returned")
+        fout = torch.empty(B, N, D, dtype=torch.float32, device=dev) if return_field else None
+        field_out = () if hook.entries is None else (None if fout is None else fout.data_ptr(),)
+        ptr = hook.state
+        st = getattr(lib, entry)(None if pf is None else C.byref(pf), C.byref(pe), *hook.decoders(self.decoder, pd),
+                                 plan.data_ptr(), *scal,
                                  send.data_ptr(), recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), xf.data_ptr(),
                                  None if ff is None else ff.data_ptr(), *ptr(dhf), h0.data_ptr(), c0.data_ptr(),
                                  uf.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), *ptr(dh_out), h1.data_ptr(),
-                                 c1.data_ptr(), edges.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+                                 c1.data_ptr(), edges.data_ptr(), *field_out, torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(st, entry)
+        if return_field:
+            return out, dh_out, (h1, c1), edges, fout
         return out, dh_out, (h1, c1), edges
 
     @torch.no_grad()
-    def _fused_rollout(self, burn_in, x_last, decoder_hidden, prior_hidden, steps, uniform, return_edges):
+    def _fused_rollout(self, burn_in, x_last, decoder_hidden, prior_hidden, steps, uniform, return_edges,
+                       batched_burn_in=True):
         """``aether_s2s_rollout`` / ``aether_s2s_markov_rollout``: burn_in [B, T0, N, 2D] (or None) teacher-forced, then
         ``steps`` autoregressive steps from x_last [B, N, 2D]; uniform [T0 + steps, B, E, K] -> (predictions
         [B, steps, N, 2D], edges or None, final state).  With the Markov decoder the burn-in steps run the prior only and the
-        final decoder state is None."""
+        final decoder state is None.  ``batched_burn_in=False`` (a model whose rollout entry takes the burn-in frames' field):
+        hand none in, every burn-in step then queries its field itself -- what a caller of the C entry gets with NULL."""
         B, N, _ = x_last.shape
         dev = x_last.device
-        lib, plan, ws, (send, recv, order, rowptr), (pf, pe, pd), scal = self._step_common(B, N, dev)
+        lib, plan, ws, (send, recv, order, rowptr), (pf, pe, pd), scal, hook = self._step_common(B, N, dev)
         if pf is None:
             raise _lib.AetherHipError("this model has no built-in field query: step it with _fused_step")
         D, he, hd, R, K = self._step_sizes()
         E1 = self.encoder.recv_edges.shape[0]
-        entry = self.decoder._fused_entries[3]
+        entry = self._entries(hook)[4]
         f32 = lambda t: t.detach().to(torch.float32).contiguous()
         T0 = 0 if burn_in is None else burn_in.shape[1]
         bi = None if T0 == 0 else f32(burn_in.transpose(0, 1))                       # [T0, B, N, 2D]
@@ -242,10 +293,10 @@ class _StepLoop:
         uf = f32(uniform.reshape(T0 + steps, B, E1, K))
         preds = torch.empty(steps, B, N, 2 * D, dtype=torch.float32, device=dev)
         edges = torch.empty(steps, B, E1, K, dtype=torch.float32, device=dev) if return_edges else None
-        st = getattr(lib, entry)(C.byref(pf), C.byref(pe), C.byref(pd), plan.data_ptr(), *scal, send.data_ptr(),
-                                 recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), T0,
-                                 None if bi is None else bi.data_ptr(), int(steps), xl.data_ptr(),
-                                 *(() if dh is None else (dh.data_ptr(),)), h.data_ptr(), c.data_ptr(), uf.data_ptr(),
+        st = getattr(lib, entry)(C.byref(pf), C.byref(pe), *hook.decoders(self.decoder, pd), plan.data_ptr(), *scal,
+                                 send.data_ptr(), recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), T0,
+                                 None if bi is None else bi.data_ptr(), *hook.burn_field(bi if batched_burn_in else None), int(steps), xl.data_ptr(),
+                                 *hook.state(dh), h.data_ptr(), c.data_ptr(), uf.data_ptr(),
                                  ws.data_ptr(), ws.numel(), preds.data_ptr(), None if edges is None else edges.data_ptr(),
                                  torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(st, entry)
@@ -277,13 +328,14 @@ class _StepLoop:
             uniform = torch.rand(T, B, E, K, device=device)
         return uniform.reshape(T, B, E, K)
 
-    def _graphed_rollout(self, burn_in, x_last, decoder_hidden, prior_hidden, steps, uniform, return_edges):
-        """One hipGraph launch for the whole loop (``_RolloutRunner``); arguments as ``_fused_rollout``."""
+    def _graphed_rollout(self, burn_in, x_last, decoder_hidden, prior_hidden, steps, uniform, return_edges, extra_key=()):
+        """One hipGraph launch for the whole loop (``_RolloutRunner``); arguments as ``_fused_rollout``.  ``extra_key``: what else
+        the captured launches depend on (addresses of buffers that are rewritten in place between replays)."""
         B, N = x_last.shape[0], x_last.shape[1]
         dev = x_last.device
         T0 = 0 if burn_in is None else burn_in.shape[1]
         uniform = self._uniform(uniform, T0 + steps, B, N, dev)
-        run = self._cached_runner(("rollout", B, N, T0, int(steps), str(dev), _tensors_key(self)),
+        run = self._cached_runner(("rollout", B, N, T0, int(steps), str(dev), _tensors_key(self)) + tuple(extra_key),
                                   lambda: _RolloutRunner(self, B, N, T0, int(steps), dev))
         preds, edges, state = run(burn_in, x_last, decoder_hidden, prior_hidden, uniform)
         return preds, (edges if return_edges else None), state

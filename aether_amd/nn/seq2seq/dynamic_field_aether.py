@@ -6,9 +6,11 @@ It is the seq2seq ``Aether`` whose field query is conditioned on the burn-in tra
 ``film_net`` (``FilmedNetwork``, nn/nn/filmed_network.py:7-35) replaces ``field_net``.  Same constructor
 dictionary, sub-module names and ``state_dict`` keys as the reference (``load_state_dict`` of a reference
 checkpoint works); ``use_charges`` -- which no runner of the reference sets -- must be False.  The encoder prior
-step and the decoder step are the ones of ``aether_amd.nn.seq2seq.aether``.  Inference only; the computation
-runs in libaether_hip.so (``aether_s2s_graph_summary``, ``aether_s2s_film_modulation``,
-``aether_s2s_film_field``); there is no CPU fallback.
+step and the decoder step (recurrent, or the Markov decoder with ``decoder_type='ref_mlp'``) are the ones of
+``aether_amd.nn.seq2seq.aether``.  Inference only; the computation runs in libaether_hip.so: ``aether_s2s_graph_summary`` and
+``aether_s2s_film_modulation`` once per sequence, then ``predict_future`` is ONE ``aether_s2s_dynfield_rollout`` call whose
+prediction steps query the FiLM field themselves (``aether_s2s_film_field`` is the standalone ``predict_field``, also used for
+the one batched query of the burn-in frames); there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -21,9 +23,10 @@ import torch.nn as nn
 from ... import _lib
 from ..state2state.dynamic_field_aether import _AttentionalAggregation
 from .decoder import RecurrentDecoder
-from .aether import _EvalLoss, _StepLoop
+from .aether import _EvalLoss, _FieldHook, _StepLoop
 from .encoder import Encoder, gumbel_softmax_hard
 from .field import _CoordinateEmbedding
+from .markov import MarkovDecoder
 
 
 class _SummaryParams(C.Structure):
@@ -129,9 +132,8 @@ class DynamicFieldAether(_StepLoop, _EvalLoss, nn.Module):
             raise ValueError("use_charges=True is not part of this path (no runner of the reference sets it)")
         self.num_vars = params["num_vars"]
         self.encoder = Encoder(params, device=None)                       # creation order of dynamic_field_aether.py:20-87
-        if params.get("decoder_type", None) == "ref_mlp":
-            raise ValueError("decoder_type 'ref_mlp' (MarkovDecoder) is not part of this path")
-        self.decoder = RecurrentDecoder(params, device=None)
+        self._markov = params.get("decoder_type", None) == "ref_mlp"      # :22-27
+        self.decoder = (MarkovDecoder if self._markov else RecurrentDecoder)(params, device=None)
         self.num_edge_types = params.get("num_edge_types")
         self.gumbel_temp = params.get("gumbel_temp")
         self.kl_coef = params.get("kl_coef", 1.)                      # read by the training scripts
@@ -146,7 +148,7 @@ class DynamicFieldAether(_StepLoop, _EvalLoss, nn.Module):
         self.graph_pooler = GraphSummary(params["input_size"], self.graph_hidden)
         self.film_net = _FilmedNetwork(hidden_size, self.graph_hidden, self.mlp_hidden, self.num_dims)
         self.field = params.get("field")                                  # data-side grid helper (:88-95), unused here
-        self._mod, self._ws, self._mod_buf = None, None, {}
+        self._mod, self._ws, self._mod_buf, self._burn_field = None, None, {}, None
         if device is not None:
             self.to(device)
 
@@ -218,6 +220,45 @@ class DynamicFieldAether(_StepLoop, _EvalLoss, nn.Module):
         self._mod = (summary, summary._version, version, mod)
         return mod
 
+    def _set_summary(self, graph_summary):
+        """The modulation of this sequence's summary into the per-batch-size buffer the fused step reads (rewritten in
+        place: a captured rollout follows it) -> that buffer."""
+        if graph_summary.ndim != 2 or graph_summary.shape[1] != self.graph_hidden:
+            raise ValueError("graph_summary must be [batch, graph_hidden]")
+        if not (graph_summary.is_cuda and graph_summary.dtype == torch.float32 and graph_summary.is_contiguous()):
+            raise _lib.AetherHipError("graph_summary must be a contiguous fp32 CUDA tensor")
+        ps, version = self._film_struct()
+        return self._modulation(_lib.load(), ps, version, graph_summary)
+
+    _FILM_ENTRIES = ("aether_s2s_dynfield_plan_bytes", "aether_s2s_dynfield_plan_build",
+                     "aether_s2s_dynfield_step_workspace_bytes", "aether_s2s_dynfield_step", "aether_s2s_dynfield_rollout")
+
+    def _field_hook(self):
+        """The fused step's built-in field query is the FiLM net (``aether_s2s_dynfield_*``): its plan holds the images of
+        linear_1 / linear_2; the modulation of the current sequence (``_set_summary``) is an argument of every call."""
+        f, mh = self.film_net, self.mlp_hidden
+        ps, _ = self._film_struct()
+
+        def call(B, N):
+            mod = None if self._mod is None else self._mod[3]
+            if mod is None or self._mod[0].shape[0] != B:
+                raise _lib.AetherHipError("the fused step reads the FiLM modulation of the sequence: call _set_summary with "
+                                          "the graph summary of these graphs first")
+            return (mh, mod.data_ptr(), mod.numel() * 4, B, N)
+
+        def burn_field(burn_in):
+            """The field of the burn-in frames [T0, B, N, 2D] -> [T0, B, N, D] in one batched query (:219): they are known before
+            the loop starts; only the prediction steps query the field inside the step."""
+            if burn_in is None:
+                return (None,)
+            field, _ = self.predict_field(burn_in.permute(1, 2, 0, 3).contiguous(), self._mod[0])       # [B, N, T0, D]
+            self._burn_field = field = field.permute(2, 0, 1, 3).contiguous()      # (kept: the call that reads it comes next)
+            return (field.data_ptr(),)
+
+        return _FieldHook(ps, [self.coordinate_embedding.B, f.linear_1.weight, f.linear_2.weight], self._FILM_ENTRIES,
+                          plan_tail=(1 if self.decoder.skip_first_edge_type else 0, mh), ws_tail=(mh,), call=call,
+                          burn_field=burn_field)
+
     @torch.no_grad()
     def predict_field(self, x, graph_summary, charge_emb=None):
         """dynamic_field_aether.py:117-134: x [B, N, >=D] or [B, N, T, >=D], graph_summary [B, graph_hidden]
@@ -271,20 +312,62 @@ class DynamicFieldAether(_StepLoop, _EvalLoss, nn.Module):
     def _graph_keepalive(self):
         return super()._graph_keepalive() + [self._ws, list(self._mod_buf.values())]
 
+    def _start(self, inputs):
+        B, T, N, _ = inputs.shape
+        if T < 2:
+            raise ValueError("predict_future needs at least two frames: the graph summary is taken over inputs[:, :-1] "
+                             "(to continue from a single state with a known summary use predict_from_state)")
+        R, dev = self.encoder.rnn_hidden_size, inputs.device
+        return self.decoder.get_initial_hidden(inputs), (torch.zeros(B, N * (N - 1), R, device=dev),
+                                                         torch.zeros(B, N * (N - 1), R, device=dev))
+
     @torch.no_grad()
     def predict_future(self, inputs, prediction_steps, return_edges=False, return_everything=False, charges=None,
                        uniform=None, graph=False):
         """dynamic_field_aether.py:207-246.  inputs [B, T, N, 2D].  The summary of ``inputs[:, :-1]`` conditions every
-        field query; the burn-in half runs the (causal) prior step by step, as in ``Aether.predict_future``.
-        ``uniform`` [T - 1 + steps, B, E, K] fixes the Gumbel draws.  ``graph``: replay the step from a captured
-        hipGraph (not with ``return_everything``, which also collects the burn-in predictions)."""
+        field query: it, its FiLM modulation and the field of the burn-in frames are computed once, then the whole loop -- burn-in
+        (the causal prior chained step by step, as in ``Aether.predict_future``) and prediction steps, each querying the field
+        itself -- is ONE library call (``aether_s2s_dynfield_rollout``).  ``uniform`` [T - 1 + steps, B, E, K] fixes the Gumbel draws.  ``graph``: replay that
+        call from one captured hipGraph (``_RolloutRunner``: a single graph launch per rollout; identical results).
+        ``return_everything`` also collects the burn-in predictions: it takes the step-by-step loop."""
         if charges is not None:
             raise _lib.AetherHipError("charges (use_charges) are not part of this path")
+        if return_everything:
+            return self.predict_future_stepwise(inputs, prediction_steps, return_edges, True, uniform=uniform)
+        T = inputs.shape[1]
+        decoder_hidden, prior_hidden = self._start(inputs)
+        gr_summary = self.graph_pooler(inputs[:, :-1].transpose(2, 1).contiguous())      # :214-218
+        return self._rollout(inputs[:, :T - 1].float(), inputs[:, T - 1].float(), decoder_hidden,
+                             prior_hidden, gr_summary, prediction_steps, uniform, return_edges, graph)
+
+    def _rollout(self, burn_in, x_last, decoder_hidden, prior_hidden, graph_summary, steps, uniform, return_edges, graph):
+        mod = self._set_summary(graph_summary)
+        if graph:       # the captured launches read the modulation buffer, rewritten in place above: its address is in the key
+            preds, edges, _ = self._graphed_rollout(burn_in, x_last, decoder_hidden, prior_hidden, int(steps), uniform,
+                                                    return_edges, extra_key=(mod.data_ptr(),))
+        else:
+            preds, edges, _ = self._fused_rollout(burn_in, x_last, decoder_hidden, prior_hidden, int(steps), uniform,
+                                                  return_edges)
+        return (preds, edges) if return_edges else preds
+
+    @torch.no_grad()
+    def predict_from_state(self, predictions, decoder_hidden, prior_hidden, graph_summary, prediction_steps, uniform=None,
+                           return_edges=False, graph=False):
+        """The prediction loop of ``predict_future`` (dynamic_field_aether.py:232-243) from the state the burn-in leaves behind,
+        as ``Aether.predict_from_state``: last observed state ``predictions`` [B, N, 2D], ``decoder_hidden`` [B, N, h] (None
+        with the Markov decoder), ``prior_hidden`` = (h, c) each [B, E, rnn], ``graph_summary`` [B, graph_hidden] of the
+        sequence.  ``uniform`` [steps, B, E, K] fixes the Gumbel draws."""
+        return self._rollout(None, predictions.float(), decoder_hidden, prior_hidden, graph_summary, prediction_steps, uniform,
+                             return_edges, graph)
+
+    @torch.no_grad()
+    def predict_future_stepwise(self, inputs, prediction_steps, return_edges=False, return_everything=False, uniform=None,
+                                graph=False):
+        """``predict_future`` as a host loop -- one standalone ``predict_field`` call and one fused step with that field handed
+        in per time step (``graph``: the step replayed from a captured hipGraph; not with ``return_everything``) -- kept as the
+        cross-check of the device rollout, the counterpart of ``Aether.predict_from_state_stepwise``."""
         B, T, N, _ = inputs.shape
-        E = N * (N - 1)
-        decoder_hidden = self.decoder.get_initial_hidden(inputs)
-        R = self.encoder.rnn_hidden_size
-        prior_hidden = (torch.zeros(B, E, R, device=inputs.device), torch.zeros(B, E, R, device=inputs.device))
+        decoder_hidden, prior_hidden = self._start(inputs)
         x = inputs[:, :-1].transpose(2, 1).contiguous()                    # :214
         gr_summary = self.graph_pooler(x)                                  # :218
         predicted_field, _ = self.predict_field(x, gr_summary)             # :219, [B, N, T - 1, D]
@@ -292,11 +375,11 @@ class DynamicFieldAether(_StepLoop, _EvalLoss, nn.Module):
             mod = self._mod_buf[(B, str(inputs.device))]
             preds, edges, _ = self._graphed(lambda xx: self.predict_field(xx, gr_summary)[0], inputs[:, :T - 1].float(),
                                             inputs[:, T - 1].float(), decoder_hidden, prior_hidden,
-                                            int(prediction_steps), uniform, return_edges, extra_key=(mod.data_ptr(),))
+                                            int(prediction_steps), uniform, return_edges, extra_key=("step", mod.data_ptr()))
             return (preds, edges) if return_edges else preds
-        # The fused step (aether_s2s_step) with the FiLM field handed in; the burn-in chains it on the observations (the
-        # reference takes the burn-in's prior logits from the full-sequence encoder, :221-222: its prior path is causal, so
-        # both give the same logits and state to rounding).
+        # The fused step with the FiLM field handed in; the burn-in chains it on the observations (the reference takes the
+        # burn-in's prior logits from the full-sequence encoder, :221-222: its prior path is causal, so both give the same
+        # logits and state to rounding).
         all_predictions, all_edges = [], []
         uniform = self._uniform(uniform, T - 1 + int(prediction_steps), B, N, inputs.device)
         for step in range(T - 1):

@@ -615,6 +615,68 @@ int aether_s2s_film_field(const AetherS2SFilmParams* params, int num_dims, int h
                           float* field, void* stream);
 
 /*
+ * The fused step and the device rollout of the dynamic-field model: aether_s2s_plan_* / aether_s2s_step / aether_s2s_rollout
+ * (and their Markov counterparts) with the FiLM field query as the step's built-in field source.  They replace the per-step
+ * predict_field call (nn/seq2seq/dynamic_field_aether.py:117-134) and the loop of predict_future (:207-246): per step, the
+ * Fourier features, linear_1 and linear_2 as jobs of the step's dense-layer launches with FiLM and SiLU in their epilogues
+ * (linear_1 shares the launch of the decoder's first-layer products), linear_3 in the node kernel of the local frames.
+ * One set of entries serves both decoders: exactly one of `decoder` (RecurrentDecoder) and `markov` (MarkovDecoder) is not
+ * NULL.  Arguments are those of aether_s2s_step / aether_s2s_rollout, and:
+ *   film        : the FiLM net's tensors; the modulators (mod_*) are not read: they are not part of the step
+ *   mlp_hidden  : width of linear_1 / linear_2, a multiple of 16 (a multiple of 128: the plan holds their fp16 x 2 images)
+ *   mod         : gamma_1 | beta_1 | gamma_2 | beta_2, each [batch][mlp_hidden], as aether_s2s_film_modulation wrote it for
+ *                 this sequence's graph summary; mod_bytes >= aether_s2s_film_modulation_bytes(batch, mlp_hidden).  Not part
+ *                 of the plan: passed per call, so a captured graph follows a buffer that is rewritten in place.
+ *   batch, num_objects : node n belongs to graph n / num_objects; n_nodes must equal batch * num_objects
+ *   aether_s2s_dynfield_plan_bytes        : 0 for sizes the step does not take or unless exactly one decoder is given (only
+ *                                           whether `decoder` / `markov` are NULL is looked at); skip_first counts for the
+ *                                           Markov decoder only
+ *   aether_s2s_dynfield_plan_build        : as aether_s2s_plan_build / aether_s2s_markov_plan_build; rebuild after the weights
+ *                                           of the encoder, the decoder, linear_1 / linear_2 or coordinate_embedding change
+ *   aether_s2s_dynfield_step_workspace_bytes : aether_s2s_step_workspace_bytes with hidden rows of the field query
+ *                                           max(encoder_hidden, mlp_hidden) wide
+ *   aether_s2s_dynfield_step              : decoder_hidden_in / _out are NULL with the Markov decoder; ext_field != NULL replaces
+ *                                           the built-in query; field_out (NULL or [n_nodes][D]) receives the field the
+ *                                           built-in query computed
+ *   aether_s2s_dynfield_rollout           : decoder_state is NULL with the Markov decoder, whose burn-in steps run the prior only;
+ *                                           burn_in_field (NULL or [burn_in_steps][n_nodes][D]): the field of the burn-in
+ *                                           frames from ONE aether_s2s_film_field call over all of them (they are known
+ *                                           before the loop starts), instead of a query inside each burn-in step
+ * AETHER_EINVAL: a NULL mod, n_nodes != batch * num_objects, mlp_hidden not a multiple of 16, both or neither decoder;
+ * AETHER_ESPACE: mod_bytes or workspace_bytes too small.  Stream-ordered, no host synchronisation (capturable).
+ */
+size_t aether_s2s_dynfield_plan_bytes(const AetherS2SDecoderParams* decoder, const AetherS2SMarkovParams* markov, int num_dims,
+                                      int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
+                                      int prior_hidden, int num_edge_types, int skip_first, int mlp_hidden);
+int aether_s2s_dynfield_plan_build(const AetherS2SFilmParams* film, const AetherS2SPriorParams* prior,
+                                   const AetherS2SDecoderParams* decoder, const AetherS2SMarkovParams* markov, int num_dims,
+                                   int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden,
+                                   int num_edge_types, int skip_first, int mlp_hidden, void* plan, size_t plan_bytes,
+                                   void* stream);
+size_t aether_s2s_dynfield_step_workspace_bytes(int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden,
+                                                int prior_hidden, int num_edge_types, int mlp_hidden, int64_t n_nodes,
+                                                int64_t n_edges);
+int aether_s2s_dynfield_step(const AetherS2SFilmParams* film, const AetherS2SPriorParams* prior,
+                             const AetherS2SDecoderParams* decoder, const AetherS2SMarkovParams* markov, const void* plan,
+                             int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
+                             int prior_hidden, int num_edge_types, int skip_first, int polar, int num_vars, float tau,
+                             int64_t n_nodes, int64_t n_edges, int mlp_hidden, const float* mod, size_t mod_bytes, int64_t batch,
+                             int num_objects, const int64_t* send, const int64_t* recv, const int64_t* order,
+                             const int64_t* rowptr, const float* inputs, const float* ext_field, const float* decoder_hidden_in,
+                             const float* h0, const float* c0, const float* uniform, void* workspace, size_t workspace_bytes,
+                             float* outputs, float* decoder_hidden_out, float* h1, float* c1, float* edges_out, float* field_out,
+                             void* stream);
+int aether_s2s_dynfield_rollout(const AetherS2SFilmParams* film, const AetherS2SPriorParams* prior,
+                                const AetherS2SDecoderParams* decoder, const AetherS2SMarkovParams* markov, const void* plan,
+                                int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
+                                int prior_hidden, int num_edge_types, int skip_first, int polar, int num_vars, float tau,
+                                int64_t n_nodes, int64_t n_edges, int mlp_hidden, const float* mod, size_t mod_bytes,
+                                int64_t batch, int num_objects, const int64_t* send, const int64_t* recv, const int64_t* order,
+                                const int64_t* rowptr, int burn_in_steps, const float* burn_in, const float* burn_in_field,
+                                int steps, const float* inputs, float* decoder_state, float* h, float* c, const float* uniform,
+                                void* workspace, size_t workspace_bytes, float* predictions, float* edges_out, void* stream);
+
+/*
  * k-nearest-neighbour edge builder for variable-N scenes: replaces Encoder.knn_edges
  * (nn/dynamicvars/aether_dynamicvars.py:559-586; the same method in the other *_dynamicvars.py) and the send /
  * recv half of get_knn_graph_info (experiments/ind/single_ind_data.py:186-217).

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Time the seq2seq dynamic-field variant's pieces at the gravitational runner's sizes
 (scripts/gravitational_field_3d_aether.sh: 3-D, 5 objects, 49 burn-in steps, encoder_hidden = graph_hidden =
-mlp_hidden = 512): the once-per-sequence graph summary + FiLM modulation, and the per-step FiLM field query."""
+mlp_hidden = 512): the once-per-sequence graph summary + FiLM modulation, the per-step FiLM field query, and predict_future
+as a host loop, as a captured step graph, as the device rollout and as one graph launch per rollout."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -53,7 +54,19 @@ dt = timed(fresh_mod, 30)
 print("FiLM modulation + one-step query (cache miss)          : %.3f ms" % (dt * 1e3))
 U = torch.rand(T + 20, B, N * (N - 1), 2, device="cuda")
 inputs = torch.randn(B, T + 1, N, 2 * D, device="cuda")
-for name, graph in (("step by step", False), ("captured step graph", True)):
-    dt = timed(lambda: model.predict_future(inputs, 20, uniform=U, graph=graph), 3)
-    print("predict_future  %d burn-in + 20 prediction steps, %-20s: %.1f ms  (%.2f ms per step)" %
-          (T, name, dt * 1e3, dt * 1e3 / (T + 20)))
+def spread(fn, runs=5, reps=3):
+    """Median and (min, max) of `runs` timings of `reps` calls each, after warm-up."""
+    ts = sorted(timed(fn, reps) for _ in range(runs))
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+# the host loop (standalone field query + fused step with the field handed in, per time step) and the device rollout
+# (aether_s2s_dynfield_rollout: the field query inside the step), each eager and from a captured hipGraph
+stepwise = model.predict_future_stepwise
+for name, fn in (("step by step", lambda: stepwise(inputs, 20, uniform=U, graph=False)),
+                 ("captured step graph", lambda: stepwise(inputs, 20, uniform=U, graph=True)),
+                 ("device rollout", lambda: model.predict_future(inputs, 20, uniform=U, graph=False)),
+                 ("one graph launch per rollout", lambda: model.predict_future(inputs, 20, uniform=U, graph=True))):
+    med, lo, hi = spread(fn)
+    print("predict_future  %d burn-in + 20 prediction steps, %-28s: %.1f ms  (%.3f ms per step; min %.3f max %.3f over 5 runs)" %
+          (T, name, med * 1e3, med * 1e3 / (T + 20), lo * 1e3 / (T + 20), hi * 1e3 / (T + 20)))
