@@ -84,6 +84,8 @@ SIGNATURES = {
     "aether_graph_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "aether_graph_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                      C.c_size_t, C.POINTER(AetherGraphInfo), C.c_void_p]),
+    "aether_graph_build_counting": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                              C.c_size_t, C.POINTER(AetherGraphInfo), C.c_void_p]),
     "aether_graph_perm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "aether_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "aether_forward": (C.c_int, [C.POINTER(AetherParams), C.c_int, C.c_int64, C.c_int64,

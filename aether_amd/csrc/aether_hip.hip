@@ -47,6 +47,7 @@
 #include "train_step.h"
 #include "egnn.h"
 #include "clof.h"
+#include "graph_build.h"
 
 #include <mutex>
 #include <type_traits>
@@ -224,6 +225,7 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 constexpr int64_t FUSED_TABLE_MAX_EDGES = 4 << 20;
 int g_fused_split = 1;        // aether_set_option("fused_split", 0|1): two workgroups per group when CUs are idle
+int g_graph_build = 1;       // aether_set_option("graph_build", 0|1): 1 aether_graph_build_counting counts, 0 it forwards to aether_graph_build
 constexpr int FUSED_PAIR_STRIDE = 8;   // distance of the two workgroups of a split group (8: both on one XCD -- workgroup b
                                        // runs on XCD b % 8 -- 47.25 -> 46.56 us per launch at cfg2; a placement hint only:
                                        // the hand-off protocol is the cross-XCD one either way)
@@ -949,6 +951,11 @@ int aether_set_option(const char* name, int value) {
         g_fused_split = value != 0;
         return AETHER_OK;
     }
+    if (!strcmp(name, "graph_build")) {      // read by aether_graph_build_counting
+        if (value != 0 && value != 1) return fail(AETHER_EINVAL, "set_option: graph_build must be 0 or 1");
+        g_graph_build = value;
+        return AETHER_OK;
+    }
     if (!strcmp(name, "fused_backward")) {   // 0: layer-by-layer backward kernels even for small-graph groups
         g_fused_backward = value != 0;
         return AETHER_OK;
@@ -1014,6 +1021,9 @@ size_t aether_graph_bytes(int64_t n_edges, int64_t n_nodes) {
     return GraphLayout(n_edges, n_nodes).total;
 }
 
+static int graph_build_tables(const GraphLayout& G, char* g, int64_t n_edges, int64_t n_nodes, const int32_t* h_cross,
+                              const int32_t* h_rowptr, AetherGraphInfo* info, hipStream_t st);
+
 int aether_graph_build(const int64_t* send, const int64_t* recv, int64_t n_edges, int64_t n_nodes,
                        void* graph, size_t graph_bytes, AetherGraphInfo* info, void* stream) {
     if (n_nodes <= 0 || n_edges < 0 || !graph || !info) return fail(AETHER_EINVAL, "graph_build: bad sizes");
@@ -1074,6 +1084,16 @@ int aether_graph_build(const int64_t* send, const int64_t* recv, int64_t n_edges
     HIP_OK(hipMemcpyAsync(h_cross.data(), cross, (size_t)(n_nodes + 1) * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(h_rowptr.data(), rowptr, (size_t)(n_nodes + 1) * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
+    return graph_build_tables(G, g, n_edges, n_nodes, h_cross.data(), h_rowptr.data(), info, st);
+}
+
+// The host half of both graph builders: components from `cross`, packed into groups, the FusedWG / FusedTile tables
+// and the two kernels that read them.  h_cross, h_rowptr: host copies, n_nodes + 1 entries each.  Ends with a
+// synchronise (its host vectors must outlive the copies).
+static int graph_build_tables(const GraphLayout& G, char* g, int64_t n_edges, int64_t n_nodes, const int32_t* h_cross,
+                              const int32_t* h_rowptr, AetherGraphInfo* info, hipStream_t st) {
+    const int32_t* rowptr = (const int32_t*)(g + G.rowptr);
+    const int32_t* recv_s = (const int32_t*)(g + G.recv_s);
     // components = maximal ranges with no crossing edge at their boundaries
     const int cap_n = FUSED_MAX_NODES, cap_e = FUSED_MAX_EDGES;
     bool ok = true;
@@ -1186,6 +1206,8 @@ int aether_graph_build(const int64_t* send, const int64_t* recv, int64_t n_edges
     }
     return AETHER_OK;
 }
+
+#include "host_graph_build.inc"
 
 int aether_graph_matches(const int64_t* send, const int64_t* recv, int64_t n_edges, int64_t n_nodes, const void* graph,
                          void* stream) {

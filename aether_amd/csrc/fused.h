@@ -294,10 +294,10 @@ k_graph_tiles(const FusedTile* __restrict__ tdesc, const FusedWG* __restrict__ w
 // The same structure for the whole receiver-sorted edge list (tile t = sorted positions 16t..16t+15),
 // one word per lane, for the streamed edge kernels (streamed.h::tile_receiver_sums):
 // bits 0-3 segment-matrix column; per result register r4: first row of segment 4q+r4 (4 bits), valid (1 bit).
-__global__ void __launch_bounds__(64)
-k_graph_gtiles(const int32_t* __restrict__ recv_s, int64_t n_edges, uint32_t* __restrict__ gsel) {
-    const int lane = threadIdx.x, i = lane & 15, q = lane >> 4;
-    const int64_t k = (int64_t)blockIdx.x * 16 + i;
+__device__ inline void graph_gtile(const int32_t* __restrict__ recv_s, int64_t n_edges, uint32_t* __restrict__ gsel,
+                                   int64_t tile, int lane) {
+    const int i = lane & 15, q = lane >> 4;
+    const int64_t k = tile * 16 + i;
     const bool valid = k < n_edges;
     const int rcv = valid ? recv_s[k] : -1;
     const int prev = __shfl_up(rcv, 1, 16);
@@ -324,7 +324,12 @@ k_graph_gtiles(const int32_t* __restrict__ recv_s, int64_t n_edges, uint32_t* __
         const unsigned ok = (exists && ((vmask >> s0) & 1u)) ? 16u : 0u;
         w |= ((unsigned)s0 | ok) << (4 + 5 * r4);
     }
-    gsel[(size_t)blockIdx.x * 64 + lane] = w;
+    gsel[(size_t)tile * 64 + lane] = w;
+}
+
+__global__ void __launch_bounds__(64)
+k_graph_gtiles(const int32_t* __restrict__ recv_s, int64_t n_edges, uint32_t* __restrict__ gsel) {
+    graph_gtile(recv_s, n_edges, gsel, (int64_t)blockIdx.x, threadIdx.x);
 }
 
 #ifndef AETHER_R3_DEFER

@@ -62,9 +62,11 @@ class GraphCache:
         buf = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=send.device)
         info = _lib.AetherGraphInfo()
         stream = torch.cuda.current_stream(send.device).cuda_stream
-        _lib.check(lib.aether_graph_build(send.data_ptr(), recv.data_ptr(), E, n_nodes,
-                                          buf.data_ptr(), buf.numel(), C.byref(info), stream),
-                   "aether_graph_build")
+        # (the counting builder: the same view at a fraction of the sorting builder's time, so that a new topology on
+        # every call is an ordinary case; aether_set_option("graph_build", 0) sends it through aether_graph_build)
+        _lib.check(lib.aether_graph_build_counting(send.data_ptr(), recv.data_ptr(), E, n_nodes,
+                                                   buf.data_ptr(), buf.numel(), C.byref(info), stream),
+                   "aether_graph_build_counting")
         # keep the index tensors alive so the key (their addresses) stays unique
         self._d[key] = ((buf, info), send, recv)
         self._trim()

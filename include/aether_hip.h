@@ -8,8 +8,8 @@
  * each one names the reference interface it replaces.  Plain pointers and sizes only:
  * every pointer is a DEVICE pointer (HIP) unless it says "host"; `stream` is a
  * hipStream_t passed as void*.  No call allocates, frees or synchronises except
- * aether_graph_build (which synchronises `stream` to report bad indices and to size the
- * fused kernel's groups on the host).
+ * aether_graph_build / aether_graph_build_counting (which synchronise `stream` to report bad
+ * indices and to size the fused kernel's groups on the host).
  * All functions return 0 on success, a negative AETHER_E* code on error;
  * aether_last_error() returns a host string for the calling thread's last error.
  */
@@ -122,6 +122,19 @@ int aether_graph_matches(const int64_t* send, const int64_t* recv, int64_t n_edg
 int aether_graph_build(const int64_t* send, const int64_t* recv, int64_t n_edges,
                        int64_t n_nodes, void* graph, size_t graph_bytes, AetherGraphInfo* info,
                        void* stream);
+/*
+ * The same view -- same arguments, same buffer (aether_graph_bytes), same bytes in every region a kernel reads, same
+ * `info`, same error codes -- without sorting: for callers whose edge index is new on every call, as the runner's is
+ * (experiments/lorentz/main.py:211-212 rebuilds and re-uploads it every batch) and as every batch of kNN scenes is
+ * (nn/dynamicvars/aether_dynamicvars.py:559-586).  Receivers and senders are integers below n_nodes: one pass counts
+ * them (integer atomics), one workgroup scans the counters, every edge goes to its list, and each list is put into
+ * ascending order in LDS, which is the order of the stable sort whatever order the atomics arrived in (csrc/graph_build.h).
+ * Six launches in front of the host's group tables and two synchronisations of `stream`.  Falls back to aether_graph_build
+ * -- and returns what it returns -- for an empty edge list, for more than 2^20 - 1 nodes, when a node has more than
+ * 1,024 in- or out-edges, and under aether_set_option("graph_build", 0).
+ */
+int aether_graph_build_counting(const int64_t* send, const int64_t* recv, int64_t n_edges, int64_t n_nodes, void* graph,
+                                size_t graph_bytes, AetherGraphInfo* info, void* stream);
 /* Debug / test access: copies the sorted-position -> original-edge-id map (int32[E]). */
 int aether_graph_perm(const void* graph, int64_t n_edges, int64_t n_nodes, int32_t* perm_out,
                       void* stream);
@@ -964,7 +977,8 @@ int aether_adamw_step(const AetherAdamWTensor* tensors, int n_tensors, float* st
 /*
  * Tuning knobs (process-wide; not thread-safe); any other name returns AETHER_EINVAL:
  * "fused_split" 0|1 (two workgroups per group when there are fewer groups than half the CUs; default 1; read by
- * aether_graph_build), "fused_backward" 0|1 (one-launch backward for small-graph groups; default 1, 0 sends them through
+ * aether_graph_build), "graph_build" 0|1 (aether_graph_build_counting: 1, the default, builds by counting; 0 forwards
+ * every call to the sorting aether_graph_build), "fused_backward" 0|1 (one-launch backward for small-graph groups; default 1, 0 sends them through
  * the layer-by-layer kernels), "outer_defer_max_edges" n (aether_backward keeps every layer's weight-gradient operands
  * and multiplies them in one launch when n_edges <= n, default 2^20; changes aether_workspace_bytes), "edge_acc"
  * 0|non-zero (above outer_defer_max_edges, non-zero -- the default -- accumulates each layer's edge-level weight gradients
