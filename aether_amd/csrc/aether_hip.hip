@@ -316,7 +316,7 @@ struct WsLayout {
         stamps = take((size_t)4096 * FUSED_STAMPS);
         flags = take(2 * nn + 64);              // split-mode hand-off flags, one int per workgroup
         for (auto& v : velbuf) v = take(nn * 4);    // aether_rollout: velocities of the steps, ping-pong
-        wimg = take(FUSED_WIMG_SET);                // split (3 x bf16) images of the edge-MLP weights (k_split_weights)
+        wimg = take(FUSED_WIMG_SET);                // split weight images and constants blocks of the fused forward (k_prepare_weights)
         fwd_total = off;
         for (auto& v : n) v = take(nn * H);
         feat = take(ee * FPAD);
@@ -395,13 +395,14 @@ BwdWT transposed_weights(const AetherParams& P, float* base, TransposeBatch& TB)
     return WT;
 }
 
-// Everything derived from the weights alone, in ONE launch in front of the step: the split (3 x bf16) images of the
-// edge-MLP matrices the fused forward copies into LDS (blocks 0-7) and, when the intermediates are kept for a
-// backward, the transposed copies its kernels read (the remaining blocks).
+// Everything derived from the weights alone, in ONE launch in front of the step: the split images of the edge-MLP
+// matrices the fused forward copies into LDS (blocks 0-7), the node phase's (blocks 8-31), the per-layer constants
+// blocks (biases, out_w6: the last image block; fused.h CB_*) and, when the intermediates are kept for a backward, the
+// transposed copies its kernels read (the remaining blocks).
 __global__ void __launch_bounds__(512)
-k_prepare_weights(AetherParams P, int f1, float* __restrict__ wimg, TransposeBatch TB, int split_blocks) {
+k_prepare_weights(AetherParams P, int f1, int nd, float* __restrict__ wimg, TransposeBatch TB, int split_blocks) {
     if ((int)blockIdx.x < split_blocks) {
-        split_weights_block(P, f1, wimg, (int)blockIdx.x, threadIdx.x);
+        split_weights_block(P, f1, nd, wimg, (int)blockIdx.x, threadIdx.x);
         return;
     }
     const int b = (int)blockIdx.x - split_blocks;
@@ -422,7 +423,7 @@ int prepare_weights(const AetherParams& P, char* ws, bool split_images, bool tra
     TB.n_tasks = 0;
     if (transposes) (void)transposed_weights<D>(P, reinterpret_cast<float*>(ws + W.wt), TB);
     const int sb = split_images ? FUSED_SPLIT_BLOCKS : 0;
-    k_prepare_weights<<<dim3((unsigned)(sb + 2 * TB.n_tasks)), dim3(512), 0, st>>>(P, F1, reinterpret_cast<float*>(ws + W.wimg),
+    k_prepare_weights<<<dim3((unsigned)(sb + 2 * TB.n_tasks)), dim3(512), 0, st>>>(P, F1, D, reinterpret_cast<float*>(ws + W.wimg),
                                                                                     TB, sb);
     HIP_OK(hipGetLastError());
     return AETHER_OK;

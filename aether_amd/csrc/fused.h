@@ -30,14 +30,24 @@ constexpr int LDU = 2 * H + 8;               // padded LDS row for the 128-wide 
 // The edge MLP's two 64 x 64 contractions run as three fp16 MFMA terms on operands split into two fp16 pieces (common.h,
 // gemm_split); the weight images (2 x 8 KB each instead of 18 KB of padded fp32) fit every variant since the layer-1 features of the
 // 17-24 tile one are built two rounds at a time.
-template <int ROUNDS> constexpr bool fused_split_gemm() { return true; }
 constexpr int FUSED_WIMG = SPLIT_WIMG;                   // floats of a split image of a 64 x 64 matrix (16 KB)
+// Per-layer constants block (plain fp32, written by k_prepare_weights next to the images, copied into LDS with them): every
+// bias the kernel adds while layer l is in LDS, so that nothing between the node phase's barriers waits for global memory.
+constexpr int FUSED_CBLK = 768;                          // floats per layer (3 KiB = three LDS-DMA fragments)
+constexpr int CB_B1 = 0;                                 // [64]  bias of the tile's first Linear (layer 1: l1_msg_b0; layers 2-4: zeros)
+constexpr int CB_B2 = 64;                                // [64]  b2
+constexpr int CB_B3 = 128;                               // [128] b3
+constexpr int CB_B4 = 256;                               // [64]  b4
+constexpr int CB_B1N = 320;                              // [64]  layers 1-3: next layer's ln_msg_b0 (the P_r bias); layer 4: out_b0
+constexpr int CB_OB3 = 384;                              // [64]  layer 4: out_b3
+constexpr int CB_OB6 = 448;                              // [4]   layer 4: out_b6, zero padded
+constexpr int CB_OW6 = 512;                              // [3][64] layer 4: out_w6 rows 0..D-1; everything else in a block is zero
 template <int NW, int ROUNDS> struct FusedLds {          // offsets in floats
-    static constexpr int WSZ = fused_split_gemm<ROUNDS>() ? FUSED_WIMG : H * LDW;
-    static constexpr int WA = 0;                                   // W_e  (layer 1: W1): [64][LDW] fp32 (ld LDF) | split image
+    static constexpr int WSZ = FUSED_WIMG;
+    static constexpr int WA = 0;                                   // W_e  (layer 1: W1) split image
     static constexpr int WB = WA + WSZ;                            // W2
-    static constexpr int BIAS = WB + WSZ;                          // [128]      b1 | b2
-    static constexpr int XBUF = BIAS + 2 * H;                      // [32][LDW]  x_{l-1} / x_l
+    static constexpr int CBLK = WB + WSZ;                          // [2][FUSED_CBLK] constants of layer l in slot l & 1
+    static constexpr int XBUF = CBLK + 2 * FUSED_CBLK;             // [32][LDW]  x_{l-1} / x_l
     static constexpr int NBUF = XBUF + FUSED_MAX_NODES * LDW;      // [32][LDW]  n = x + mean
     static constexpr int PS = NBUF + FUSED_MAX_NODES * LDW;        // [32][LDW]  W_s x
     static constexpr int PR = PS + FUSED_MAX_NODES * LDW;          // [32][LDW]  W_r x + b1
@@ -82,16 +92,36 @@ template <int NW, int ROUNDS> struct FusedLds {          // offsets in floats
 // W3 [128][64] (stage_split4<8, 2>), W4 [64][128] (<4, 4>), and the NEXT layer's W_s, W_r (<4, 2> each; layer 4: out_w0, out_w3).
 constexpr int FUSED_NIMG_W3 = 2 * 8 * 2 * 64 * 4, FUSED_NIMG_W4 = 2 * 4 * 4 * 64 * 4, FUSED_NIMG_WS = 2 * 4 * 2 * 64 * 4;
 constexpr int FUSED_NIMG_LAYER = FUSED_NIMG_W3 + FUSED_NIMG_W4 + 2 * FUSED_NIMG_WS;
-constexpr int FUSED_WIMG_SET = 8 * FUSED_WIMG + 4 * FUSED_NIMG_LAYER;      // floats reserved (layer 1's image A uses half of its slot)
-constexpr int FUSED_SPLIT_BLOCKS = 8 + 4 * 6;            // blocks of k_prepare_weights that write images (512 threads each)
+constexpr int FUSED_WIMG_SET = 8 * FUSED_WIMG + 4 * FUSED_NIMG_LAYER + 4 * FUSED_CBLK;   // floats reserved (layer 1's image A uses half of its slot)
+constexpr int FUSED_SPLIT_BLOCKS = 8 + 4 * 6 + 1;        // blocks of k_prepare_weights that write images (512 threads each)
 __device__ __host__ constexpr int fused_wimg_offset(int layer, int which) { return ((layer - 1) * 2 + which) * FUSED_WIMG; }
 // which: 0 W3, 1 W4, 2 W_s (next layer / out_w0), 3 W_r (next layer / out_w3)
 __device__ __host__ constexpr int fused_nimg_offset(int layer, int which) {
     return 8 * FUSED_WIMG + (layer - 1) * FUSED_NIMG_LAYER +
            (which == 0 ? 0 : which == 1 ? FUSED_NIMG_W3 : which == 2 ? FUSED_NIMG_W3 + FUSED_NIMG_W4 : FUSED_NIMG_W3 + FUSED_NIMG_W4 + FUSED_NIMG_WS);
 }
+__device__ __host__ constexpr int fused_cblk_offset(int layer) { return 8 * FUSED_WIMG + 4 * FUSED_NIMG_LAYER + (layer - 1) * FUSED_CBLK; }
 
-__device__ __forceinline__ void split_weights_block(const AetherParams& P, int f1, float* __restrict__ wimg, int block, int tid) {
+// Float c of layer's constants block (layout: CB_* above).
+__device__ __forceinline__ float fused_cblk_value(const AetherParams& P, int nd, int layer, int c) {
+    if (c < CB_B2) return layer == 1 ? P.l1_msg_b0[c] : 0.0f;
+    if (c < CB_B3) return (layer == 1 ? P.l1_msg_b2 : P.ln_msg_b2[layer - 2])[c - CB_B2];
+    if (c < CB_B4) return (layer == 1 ? P.l1_upd_b0 : P.ln_upd_b0[layer - 2])[c - CB_B3];
+    if (c < CB_B1N) return (layer == 1 ? P.l1_upd_b2 : P.ln_upd_b2[layer - 2])[c - CB_B4];
+    if (c < CB_OB3) return (layer < 4 ? P.ln_msg_b0[layer - 1] : P.out_b0)[c - CB_B1N];
+    if (layer < 4) return 0.0f;
+    if (c < CB_OB6) return P.out_b3[c - CB_OB3];
+    if (c < CB_OB6 + 4) return c - CB_OB6 < nd ? P.out_b6[c - CB_OB6] : 0.0f;
+    if (c >= CB_OW6 && c < CB_OW6 + nd * H) return P.out_w6[c - CB_OW6];
+    return 0.0f;
+}
+
+__device__ __forceinline__ void split_weights_block(const AetherParams& P, int f1, int nd, float* __restrict__ wimg, int block, int tid) {
+    if (block == FUSED_SPLIT_BLOCKS - 1) {                // the four constants blocks
+        for (int idx = tid; idx < 4 * FUSED_CBLK; idx += 512)
+            wimg[fused_cblk_offset(1) + idx] = fused_cblk_value(P, nd, idx / FUSED_CBLK + 1, idx % FUSED_CBLK);
+        return;
+    }
     if (block >= 8) {                                     // node-phase images: six blocks per layer
         const int nbk = block - 8, layer = nbk / 6 + 1, part = nbk % 6;
         if (part < 2) {                                   // W3 rows 64 part ..: 1,024 float4
@@ -348,13 +378,12 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     using NI = NodeInfo<D>;
     using L = FusedLds<NW, ROUNDS>;
     constexpr int THREADS = NW * 64;
-    constexpr int F1 = 7 * D + D * (D - 1) / 2 + 2;
     constexpr int FIN = 2 * D + 16;
     static_assert(NW == 8, "waves 0-7 run the node phase (12 and 16 waves per workgroup were measured: DESIGN.md 4.1)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* wA = smem + L::WA;
     float* wB = smem + L::WB;
-    float* bias = smem + L::BIAS;
+    const float* cblk = smem + L::CBLK;
     float* xbuf = smem + L::XBUF;
     float* nbuf = smem + L::NBUF;
     float* psb = smem + L::PS;
@@ -379,43 +408,35 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
 #endif
     FUSED_STAMP(0);
 
-    // ---------------------------------------------------------------- P0: layer-1 weights, loads only
-    // (W1 [64][F1] zero padded to [64][LDF], W2, biases); they land in LDS after the prologue, so their
-    // latency hides behind the field net.
-    constexpr bool SPLITG = fused_split_gemm<ROUNDS>();
-    constexpr int P0A = SPLITG ? 1 : (H * LDF + THREADS - 1) / THREADS;
-    constexpr int P0B = SPLITG ? 1 : (H * H / 4 + THREADS - 1) / THREADS;
-    float p0a[P0A];
-    f32x4 p0b[P0B];
-    float p0bias = 0.0f;
-    // Split-GEMM variants: a layer's two weight images are copied global -> LDS by LDS-DMA, one 1 KiB fragment per wave
-    // instruction (images are lane-linear in both places), no registers, no VALU; `first` skips the unused half of
-    // layer 1's image A.  The caller waits (vmcnt) before the barrier that precedes the first read.
+    // ---------------------------------------------------------------- P0: layer-1 weights, requested only
+    // (images of W1 and W2, constants block 1); they land in LDS during the prologue, behind the field net.
+    // A layer's two weight images and its constants block are copied global -> LDS by LDS-DMA, one 1 KiB fragment per wave
+    // instruction (lane-linear in both places), no registers, no VALU; layer 1's image A is half a slot.  Block l goes to
+    // slot l & 1: the other slot holds the block that the running layer still reads.  The caller waits (vmcnt) before the
+    // barrier that precedes the first read.
     auto dma_images = [&](int layer_) {
-        const float* ga = dbg.wimg + fused_wimg_offset(layer_, 0);
-        const float* gb = dbg.wimg + fused_wimg_offset(layer_, 1);
-        const int na_frag = layer_ == 1 ? 8 : 16, total = na_frag + 16;       // 1 KiB fragments: 2 terms x 4 (x 2)
-        for (int f = wave; f < total; f += NW) {
-            const float* src = f < na_frag ? ga + f * 256 : gb + (f - na_frag) * 256;
-            float* dst = f < na_frag ? wA + f * 256 : wB + (f - na_frag) * 256;
-            __builtin_amdgcn_global_load_lds(src + lane * 4, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+        const int na_frag = layer_ == 1 ? 8 : 16, nw_frag = na_frag + 16;     // 1 KiB fragments: 2 terms x 4 (x 2)
+        const int total = nw_frag + FUSED_CBLK / 256;
+        // Fragment index and both offsets in scalar registers, selects instead of branches (with the wave index as a lane
+        // value this was a divergent loop of ~40 instructions and a dozen exec-mask branches per fragment, on every
+        // wave's critical path).  Image B follows image A in global memory as W2 follows W_e in LDS.
+        const int wv = __builtin_amdgcn_readfirstlane(wave);
+        __builtin_assume(wv >= 0 && wv < NW);
+        const int g_img = fused_wimg_offset(layer_, 0), g_cb = fused_cblk_offset(layer_);
+        const int l_cb = L::CBLK + (layer_ & 1) * FUSED_CBLK;
+        constexpr int MAXF = (32 + FUSED_CBLK / 256 + NW - 1) / NW;
+#pragma unroll
+        for (int j = 0; j < MAXF; ++j) {
+            const int f = wv + NW * j;
+            if (f < total) {
+                const int img = f < na_frag ? f * 256 : FUSED_WIMG + (f - na_frag) * 256;    // offset in [image A | image B]
+                const int soff = f < nw_frag ? g_img + img : g_cb + (f - nw_frag) * 256;
+                const int doff = f < nw_frag ? L::WA + img : l_cb + (f - nw_frag) * 256;
+                __builtin_amdgcn_global_load_lds(dbg.wimg + soff + lane * 4, (__attribute__((address_space(3))) void*)(smem + doff), 16, 0, 0);
+            }
         }
     };
-    if constexpr (SPLITG) {
-        dma_images(1);
-    } else {
-#pragma unroll
-        for (int j = 0; j < P0A; ++j) {
-            const int idx = tid + THREADS * j, r = idx / LDF, c = idx - r * LDF;
-            p0a[j] = (idx < H * LDF && c < F1) ? P.l1_msg_w0[r * F1 + c] : 0.0f;
-        }
-#pragma unroll
-        for (int j = 0; j < P0B; ++j) {
-            const int idx = tid + THREADS * j;
-            if (idx < H * H / 4) p0b[j] = ld4(P.l1_msg_w2 + (size_t)(idx >> 4) * H + (idx & 15) * 4);
-        }
-    }
-    if (tid < 2 * H) p0bias = tid < H ? P.l1_msg_b0[tid] : P.l1_msg_b2[tid - H];
+    dma_images(1);
     FUSED_STAMP(1);
 
     // ---------------------------------------------------------------- edge indices of P2, requested during P1
@@ -581,22 +602,8 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             for (int idx = tid - 64 * vtiles; idx < (FUSED_MAX_NODES - n) * (H / 4); idx += THREADS - 64 * vtiles)
                 st4(xbuf + (n + (idx >> 4)) * LDW + (idx & 15) * 4, f32x4{0.f, 0.f, 0.f, 0.f});
         }
-        // P0, second half: the layer-1 weights go to LDS
-        if constexpr (SPLITG) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's LDS-DMA fragments have landed
-        } else {
-#pragma unroll
-            for (int j = 0; j < P0A; ++j) {
-                const int idx = tid + THREADS * j;
-                if (idx < H * LDF) wA[idx] = p0a[j];
-            }
-#pragma unroll
-            for (int j = 0; j < P0B; ++j) {
-                const int idx = tid + THREADS * j;
-                if (idx < H * H / 4) st4(wB + (idx >> 4) * LDW + (idx & 15) * 4, p0b[j]);
-            }
-        }
-        if (tid < 2 * H) bias[tid] = p0bias;
+        // P0, second half: the layer-1 weights and constants are in LDS
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's LDS-DMA fragments have landed
         lds_barrier();
     }
     FUSED_STAMP(2);
@@ -713,10 +720,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         // No workgroup barrier in here.  A wave with K tiles runs them through one branch-free block
         // (front = first Linear + SiLU, back = second Linear + SiLU + per-receiver sums) so that the
         // compiler can overlap one tile's VALU / LDS tail with the next tile's MFMAs.
-        const float* w3 = layer == 1 ? P.l1_upd_w0 : P.ln_upd_w0[layer - 2];
-        const float* b3 = layer == 1 ? P.l1_upd_b0 : P.ln_upd_b0[layer - 2];
-        const float* w4 = layer == 1 ? P.l1_upd_w2 : P.ln_upd_w2[layer - 2];
-        const float* b4 = layer == 1 ? P.l1_upd_b2 : P.ln_upd_b2[layer - 2];
+        const float* cb = cblk + (layer & 1) * FUSED_CBLK;   // this layer's constants (CB_*)
         // work split: step 2 has 16 (row block, node tile) units, step 3 has 8, step 4 has 16
         const int mb2 = wave & 7;                         // step 2: rows 16*mb2.. of the 128
         const int mb3 = wave & 3, tn3 = (wave >> 2) & 1;  // steps 3, 4: rows 16*mb3.. of node tile tn3
@@ -730,32 +734,15 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         const bool do3 = act3 && (one_tile ? wave >= 4 : 16 * tn3 < n);
         const bool do_s = act3 && (one_tile ? wave < 4 : true);
         const bool do_r = act3 && (one_tile ? wave >= 4 : true);
-        // Every L2 load of the node phase is issued BEFORE the wave's last edge tile, so that the
-        // ~130 KB of weights a workgroup needs per layer (all 256 workgroups ask at the same moment)
-        // stream in under the tile's MFMAs: next layer's edge weights (W_e = W1[:, 128:192], W2: they
-        // go to LDS once every wave has left the edge tiles), then W3 / W4 / next-layer W_s, W_r fragments.
-        constexpr int STG = SPLITG ? 1 : (H * H / 4 + THREADS - 1) / THREADS;      // float4 per thread per staged matrix
+        // Every register load of the node phase is issued BEFORE the end of the wave's last edge tile, so that
+        // the weight fragments a workgroup needs per layer (all 256 workgroups ask at the same moment) stream in under
+        // the tile's MFMAs: W3 / W4 / next-layer W_s, W_r fragments.  Step 1 waits for them once; between that wait and
+        // the end of step 4 nothing waits for global memory (biases: the constants block in LDS).
         f16x8 w3h[2], w3l[2], w4h[4], w4l[4];              // the wave's row block of W3 (k = 64) and of W4 (k = 128), split pieces
-        f32x4 stA[STG], stB[STG];
-        float b2n = 0.0f;
         // layer 4 has no next edge layer: wsv / wrv carry the out-MLP fragments (out_w0, out_w3) instead
-        // part 0: staged matrices; 1: W3; 2, 3: W4 halves; 4: W_s / W_r.  A wave spreads the parts over
+        // part 1: W3; 2, 3: W4 halves; 4: W_s / W_r.  A wave spreads the parts over
         // its last tile (a burst of ~20 loads per wave blocks at issue until the L2 returns drain).
         auto issue_loads = [&](int part) {
-            if (part == 0 && layer < 4) {
-                if constexpr (!SPLITG) {
-                    const float* w1n = P.ln_msg_w0[layer - 1];
-#pragma unroll
-                    for (int j = 0; j < STG; ++j) {
-                        const int idx = tid + THREADS * j, rr = idx >> 4, cc = (idx & 15) * 4;
-                        if (idx < H * H / 4) {
-                            stA[j] = ld4(w1n + (size_t)rr * (3 * H) + 2 * H + cc);
-                            stB[j] = ld4(P.ln_msg_w2[layer - 1] + (size_t)rr * H + cc);
-                        }
-                    }
-                }
-                if (tid < H) b2n = P.ln_msg_b2[layer - 1][tid];
-            }
             // (round 4: fragments of the prepared fp16 x 2 images, fused_nimg_offset -- same bytes per weight as fp32)
             if (part == 1 && act3) load_split_frags<8, 2>(dbg.wimg + fused_nimg_offset(layer, 0), mb2, lane, w3h, w3l);
             if ((part == 2 || part == 3) && do3) {
@@ -780,19 +767,16 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         // workgroup barrier, and nobody waits while there is work that does not need the rows.
         const bool xch = wg.partner >= 0 && layer > 1;
         auto front_gemm = [&](int r, f32x4 (&acc)[4], bool last) {
-            if (last) issue_loads(0);
             if (layer == 1) {
 #pragma unroll
-                for (int mb = 0; mb < 4; ++mb) acc[mb] = ld4(bias + 16 * mb + 4 * q);
+                for (int mb = 0; mb < 4; ++mb) acc[mb] = ld4(cb + CB_B1 + 16 * mb + 4 * q);
                 f32x4 bop[2] = {e[r][0], e[r][1]};
-                if constexpr (SPLITG) gemm_split<4, 1>(wA, bop, acc, lane);
-                else gemm_tile<4, 2>(wA, LDF, bop, acc, i, q);
+                gemm_split<4, 1>(wA, bop, acc, lane);
             } else {
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb)
                     acc[mb] = ld4(prb + rl[r] * LDW + 16 * mb + 4 * q) + ld4(psb + sl[r] * LDW + 16 * mb + 4 * q);
-                if constexpr (SPLITG) gemm_split<4, 2>(wA, e[r], acc, lane);
-                else gemm_tile<4, 4>(wA, LDW, e[r], acc, i, q);
+                gemm_split<4, 2>(wA, e[r], acc, lane);
             }
         };
         auto receive_partner_rows = [&]() {
@@ -855,9 +839,8 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             f32x4 acc2[4];
             if (last && !(AETHER_R3_DEFER && ROUNDS >= 3)) issue_loads(2);
 #pragma unroll
-            for (int mb = 0; mb < 4; ++mb) acc2[mb] = ld4(bias + H + 16 * mb + 4 * q);
-            if constexpr (SPLITG) gemm_split<4, 2>(wB, h1, acc2, lane);
-            else gemm_tile<4, 4>(wB, LDW, h1, acc2, i, q);
+            for (int mb = 0; mb < 4; ++mb) acc2[mb] = ld4(cb + CB_B2 + 16 * mb + 4 * q);
+            gemm_split<4, 2>(wB, h1, acc2, lane);
             if (last && !(AETHER_R3_DEFER && ROUNDS >= 3)) issue_loads(3);
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) e[r][mb] = silu4(acc2[mb]);
@@ -901,7 +884,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             const int nvalid = n_tiles > wave ? (n_tiles - wave + NW - 1) / NW : 0;    // wave-uniform
             if (nvalid == 0) {
 #pragma unroll
-                for (int part = 0; part < 5; ++part) issue_loads(part);
+                for (int part = 1; part < 5; ++part) issue_loads(part);
             }
             if (xch && wave == NW - 1) receive_partner_rows();
             bool have_rows = !xch || wave == NW - 1;
@@ -940,27 +923,16 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             st4(nbuf + aslot * LDW + ac4, nv);
             if (keep && aslot < n) st4(dbg.n[layer - 1] + (int64_t)(nb + aslot) * H + ac4, nv);
         }
-        if (layer < 4) {       // next layer's edge weights -> LDS
-            if constexpr (SPLITG) {
-                dma_images(layer + 1);       // in flight under the node phase; waited for before its last barrier
-            } else {                         // (loads were issued above)
-#pragma unroll
-                for (int j = 0; j < STG; ++j) {
-                    const int idx = tid + THREADS * j, rr = idx >> 4, cc = (idx & 15) * 4;
-                    if (idx < H * H / 4) {
-                        st4(wA + rr * LDW + cc, stA[j]);
-                        st4(wB + rr * LDW + cc, stB[j]);
-                    }
-                }
-            }
-            if (tid < H) bias[H + tid] = b2n;
-        }
+        // The wave's W3 / W4 / W_s / W_r fragments have arrived: a wait the compiler's wait-count pass sees (simm16 of
+        // vmcnt(0) alone), so that it places none of its own in steps 2-4 -- in particular none behind the LDS-DMA below.
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        if (layer < 4) dma_images(layer + 1);    // next layer's images and constants: in flight under steps 2-4, waited for before step 4's barrier
         lds_barrier();       // n complete
         FUSED_STAMP(4 + 8 * (layer - 1) + 7);
         // step 2: u = SiLU(W3 n + b3): rows 16*mb2.. of u for both node tiles
         if (act3) {
             float* ubuf = smem + L::UBUF;
-            const f32x4 bv = ld4(b3 + 16 * mb2 + 4 * q);
+            const f32x4 bv = ld4(cb + CB_B3 + 16 * mb2 + 4 * q);
 #pragma unroll
             for (int tn = 0; tn < 2; ++tn) {
                 if (16 * tn < n) {
@@ -978,7 +950,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         // step 3: x = n + W4 u + b4: rows 16*mb3.. of node tile tn3s (one node tile: on waves 4-7)
         if (do3) {
             const float* ubuf = smem + L::UBUF;
-            f32x4 acc = ld4(b4 + 16 * mb3 + 4 * q);
+            f32x4 acc = ld4(cb + CB_B4 + 16 * mb3 + 4 * q);
 #pragma unroll
             for (int hk = 0; hk < 2; ++hk) {                   // k halves of 64 (each with its own range check): fewer live registers
                 f32x4 uv[4];
@@ -996,7 +968,6 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         FUSED_STAMP(4 + 8 * (layer - 1) + 5);
         // step 4: next layer's node terms P_s = W_s x, P_r = W_r x + b1 (locs.py:233 split)
         if (layer < 4) {
-            const float* b1n = P.ln_msg_b0[layer - 1];
             if (16 * tn4 < n) {
                 f32x4 xv[4];
 #pragma unroll
@@ -1022,7 +993,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                     }
                 }
                 if (do_r) {
-                    const f32x4 accr = gemm_split_regs<2>(wrh, wrl, xv, ld4(b1n + 16 * mb3 + 4 * q));
+                    const f32x4 accr = gemm_split_regs<2>(wrh, wrl, xv, ld4(cb + CB_B1N + 16 * mb3 + 4 * q));
                     st4(prb + (16 * tn4 + i) * LDW + 16 * mb3 + 4 * q, accr);
                     if (keep && 16 * tn4 + i < n)
                         st4(dbg.pr[layer - 1] + (int64_t)(nb + 16 * tn4 + i) * H + 16 * mb3 + 4 * q, accr);
@@ -1034,7 +1005,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             // before the barrier, then one lane raises the flag.  The partner picks the rows up after
             // the first GEMM of its next edge phase (receive_partner_rows), as this workgroup does with
             // the partner's: the flag's flight time hides behind those 64 MFMAs.
-            if (wg.partner >= 0 || SPLITG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // hand-off stores; LDS-DMA images
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // hand-off stores; LDS-DMA images and constants
             lds_barrier();   // P_s / P_r and the staged weights are visible to the next edge tiles
             if (wg.partner >= 0 && tid == 0)
                 __hip_atomic_store(dbg.flags + blockIdx.x, layer, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1051,16 +1022,12 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         float* o2 = smem + L::OBUF2;
         const int mb = wave & 3, tn = (wave >> 2) & 1;
         const bool act = wave < 8 && 16 * tn < n;
-        f32x4 w6v[4];                                    // last Linear: rows >= D of the block are discarded
-        if (wave < 2) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a) w6v[a] = ld4(P.out_w6 + (i < D ? i : D - 1) * H + 16 * a + 4 * q);
-        }
+        const float* cb = cblk;                          // slot 0: block 4 (out_b0, out_b3, out_b6, out_w6)
         if (act) {
             f32x4 xv[4];
 #pragma unroll
             for (int a = 0; a < 4; ++a) xv[a] = ld4(xbuf + (16 * tn + i) * LDW + 16 * a + 4 * q);
-            const f32x4 acc = gemm_split_regs<2>(wsh, wsl, xv, ld4(P.out_b0 + 16 * mb + 4 * q));
+            const f32x4 acc = gemm_split_regs<2>(wsh, wsl, xv, ld4(cb + CB_B1N + 16 * mb + 4 * q));
             f32x4 v = silu4(acc);
             if constexpr (KEEP) {
                 if (dbg.step.drop1 != nullptr && 16 * tn + i < n)
@@ -1076,7 +1043,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             f32x4 xv[4];
 #pragma unroll
             for (int a = 0; a < 4; ++a) xv[a] = ld4(o1 + (16 * tn + i) * LDW + 16 * a + 4 * q);
-            const f32x4 acc = gemm_split_regs<2>(wrh, wrl, xv, ld4(P.out_b3 + 16 * mb + 4 * q));
+            const f32x4 acc = gemm_split_regs<2>(wrh, wrl, xv, ld4(cb + CB_OB3 + 16 * mb + 4 * q));
             f32x4 v = silu4(acc);
             if constexpr (KEEP) {
                 if (dbg.step.drop2 != nullptr && 16 * tn + i < n)
@@ -1090,15 +1057,17 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             f32x4 y = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
+                // last Linear: rows >= D of the block are discarded
+                const f32x4 w6v = ld4(cb + CB_OW6 + (i < D ? i : D - 1) * H + 16 * a + 4 * q);
                 const f32x4 xv = ld4(o2 + (16 * tn2 + i) * LDW + 16 * a + 4 * q);
 #pragma unroll
-                for (int b = 0; b < 4; ++b) y = mfma16(w6v[a][b], xv[b], y);
+                for (int b = 0; b < 4; ++b) y = mfma16(w6v[b], xv[b], y);
             }
             const int node = 16 * tn2 + i;
             if (q == 0 && node < n) {
                 float yl[D];
 #pragma unroll
-                for (int d = 0; d < D; ++d) yl[d] = y[d] + P.out_b6[d];
+                for (int d = 0; d < D; ++d) yl[d] = y[d] + cb[CB_OB6 + d];
                 const float* ni = ninfo + (off + node) * 24;
 #pragma unroll
                 for (int a = 0; a < D; ++a) {
