@@ -34,6 +34,7 @@
 #include "fused_bwd.h"
 #include "edge_acc.h"
 #include "input_grad.h"
+#include "rollout_bwd.h"
 #include "wide.h"
 #include "seq2seq.h"
 #include "s2s_filter.h"
@@ -292,6 +293,7 @@ struct WsLayout {
     size_t nodeinfo, x[5], ps[3], pr[3], e[4], aggr, part, stamps, flags, velbuf[2], wimg, fwd_total;
     // saved by the forward under KEEP_INTERMEDIATES for the backward
     size_t n[4], feat, drop, dropword;      // drop: [2][n_nodes][64] dropout scale masks (caller-written), dropword: applied?
+    size_t saved_end;                       // end of what a forward leaves for its backward (but for `wt`); temporaries follow
     // backward temporaries
     // Operands of the weight-gradient outer products are per layer when `defer` (all of them are then
     // multiplied in ONE launch at the end of the backward); otherwise the layers share one set.
@@ -321,6 +323,7 @@ struct WsLayout {
         for (auto& v : n) v = take(nn * H);
         feat = take(ee * FPAD);
         drop = take(nn * 2 * H); dropword = take(64);
+        saved_end = off;
         defer = E <= g_outer_defer_max_edges;
         const int sets = defer ? 4 : 1;
         for (int k = 0; k < 5; ++k) DXl[k] = (defer || k < 2) ? take(nn * H) : DXl[k - 2];
@@ -414,19 +417,28 @@ k_prepare_weights(AetherParams P, int f1, int nd, float* __restrict__ wimg, Tran
     }
 }
 
+// Where the forward's split images (FUSED_WIMG_SET floats) and the backward's transposed copies (160 Ki floats) live when
+// that is not the step's own workspace: a training rollout prepares them once per call and every step reads them there.
+struct PreparedWeights { float* wimg; float* wt; };
+
 template <int D>
-int prepare_weights(const AetherParams& P, char* ws, bool split_images, bool transposes, int64_t Nn, int64_t E, hipStream_t st) {
+int prepare_weights_at(const AetherParams& P, float* wimg, float* wt, bool split_images, bool transposes, hipStream_t st) {
     if (!split_images && !transposes) return AETHER_OK;
     constexpr int F1 = 7 * D + D * (D - 1) / 2 + 2;
-    WsLayout W(Nn, E, D, transposes);
     TransposeBatch TB;
     TB.n_tasks = 0;
-    if (transposes) (void)transposed_weights<D>(P, reinterpret_cast<float*>(ws + W.wt), TB);
+    if (transposes) (void)transposed_weights<D>(P, wt, TB);
     const int sb = split_images ? FUSED_SPLIT_BLOCKS : 0;
-    k_prepare_weights<<<dim3((unsigned)(sb + 2 * TB.n_tasks)), dim3(512), 0, st>>>(P, F1, D, reinterpret_cast<float*>(ws + W.wimg),
-                                                                                    TB, sb);
+    k_prepare_weights<<<dim3((unsigned)(sb + 2 * TB.n_tasks)), dim3(512), 0, st>>>(P, F1, D, wimg, TB, sb);
     HIP_OK(hipGetLastError());
     return AETHER_OK;
+}
+
+template <int D>
+int prepare_weights(const AetherParams& P, char* ws, bool split_images, bool transposes, int64_t Nn, int64_t E, hipStream_t st) {
+    WsLayout W(Nn, E, D, transposes);
+    return prepare_weights_at<D>(P, reinterpret_cast<float*>(ws + W.wimg), reinterpret_cast<float*>(ws + W.wt), split_images,
+                                 transposes, st);
 }
 
 template <int D, int NW, int ROUNDS, bool KEEP>
@@ -447,7 +459,9 @@ int fused_launch(const AetherParams& P, const float* x, const float* vel, const 
 template <int D>
 int fused_impl(const AetherParams& P, int64_t Nn, int64_t E, const AetherGraphInfo& info, const float* x,
                const float* vel, const float* charges, const float* ea, const char* graph, char* ws,
-               float* out, bool keep, bool ws_reused, StepExtras step, hipStream_t st, bool weights_prepared = false) {
+               float* out, bool keep, bool ws_reused, StepExtras step, hipStream_t st, bool weights_prepared = false,
+               const PreparedWeights* pw = nullptr) {
+    // pw: everything derived from the weights is prepared already, elsewhere (a training rollout)
     GraphLayout G(E, Nn, false);
     WsLayout W(Nn, E, D, keep);
     auto gp = [&](size_t off) { return reinterpret_cast<const int32_t*>(graph + off); };
@@ -465,7 +479,7 @@ int fused_impl(const AetherParams& P, int64_t Nn, int64_t E, const AetherGraphIn
     // never touched by anything else -- no memset per call, whatever else the caller does with the workspace
     dbg.flags = reinterpret_cast<int*>(const_cast<char*>(graph) + G.hflags);
     dbg.errword = async_error_word();
-    dbg.wimg = wp(W.wimg);
+    dbg.wimg = pw ? pw->wimg : wp(W.wimg);
     dbg.step = step;
     const FusedWG* wgd = reinterpret_cast<const FusedWG*>(graph + G.wgdesc);
     const uint32_t* tsel = reinterpret_cast<const uint32_t*>(graph + G.tsel);
@@ -473,7 +487,7 @@ int fused_impl(const AetherParams& P, int64_t Nn, int64_t E, const AetherGraphIn
     (void)ws_reused;
     const int tiles = (info.max_group_edges + 15) / 16;
     // split-GEMM variants: 3 x bf16 images of the eight edge-MLP matrices; training: the backward's transposed copies
-    if (prepare_weights<D>(P, ws, !weights_prepared, keep, Nn, E, st)) return AETHER_EHIP;
+    if (!pw && prepare_weights<D>(P, ws, !weights_prepared, keep, Nn, E, st)) return AETHER_EHIP;
     int rc;
 #define AETHER_FUSED_CASE(NWV, R)                                                                     \
     rc = keep ? fused_launch<D, NWV, R, true>(P, x, vel, charges, ea, gp(G.perm), gp(G.send_s),       \
@@ -494,7 +508,7 @@ int fused_impl(const AetherParams& P, int64_t Nn, int64_t E, const AetherGraphIn
 template <int D>
 int streamed_impl(const AetherParams& P, int64_t Nn, int64_t E, const float* x, const float* vel,
                   const float* charges, const float* ea, const char* graph, char* ws, float* out,
-                  bool keep, StepExtras step, hipStream_t st) {
+                  bool keep, StepExtras step, hipStream_t st, const PreparedWeights* pw = nullptr) {
     GraphLayout G(E, Nn, false);
     WsLayout W(Nn, E, D, keep);
     auto gp = [&](size_t off) { return reinterpret_cast<const int32_t*>(graph + off); };
@@ -503,7 +517,8 @@ int streamed_impl(const AetherParams& P, int64_t Nn, int64_t E, const float* x, 
     float* nodeinfo = wp(W.nodeinfo);
     // the backward's transposed copies -- and the split images too: aether_backward picks the fused backward from the
     // graph alone (fused_backward_applies), whichever forward ran, and that kernel stages its recompute GEMMs from them
-    if (prepare_weights<D>(P, ws, keep, keep, Nn, E, st)) return AETHER_EHIP;
+    // (pw, as in fused_impl: prepared already, elsewhere)
+    if (!pw && prepare_weights<D>(P, ws, keep, keep, Nn, E, st)) return AETHER_EHIP;
 
     {
         ProfScope ps(K_NODE_PREP, st);
@@ -636,13 +651,16 @@ int run_outer(OuterList& L, float* partial, size_t partial_cap, hipStream_t st, 
 template <int D>
 int backward_impl(const AetherParams& P, const AetherParams& Gr, int64_t Nn, int64_t E, const float* x,
                   const float* vel, const float* charges, const char* graph, char* ws, const float* g_out,
-                  hipStream_t st, float* grad_field = nullptr) {
+                  hipStream_t st, float* grad_field = nullptr, const PreparedWeights* pw = nullptr) {
     constexpr int F1 = 7 * D + D * (D - 1) / 2 + 2;
     constexpr int FIN = 2 * D + 16;
     GraphLayout G(E, Nn, false);
     WsLayout W(Nn, E, D, true);
     auto gp = [&](size_t off) { return reinterpret_cast<const int32_t*>(graph + off); };
     auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    // what the forward derived from the weights: in this workspace, or where a training rollout prepared it
+    float* const wt_base = pw ? pw->wt : wp(W.wt);
+    float* const wimg = pw ? pw->wimg : wp(W.wimg);
     const int32_t *send_s = gp(G.send_s), *recv_s = gp(G.recv_s), *rowptr = gp(G.rowptr);
     const int32_t *sperm = gp(G.sperm), *srowptr = gp(G.srowptr);
     float* partial = wp(W.partial);
@@ -656,7 +674,7 @@ int backward_impl(const AetherParams& P, const AetherParams& Gr, int64_t Nn, int
     const bool acc_path = g_edge_acc && !W.defer && E > 0;
     // ---- transposed weight copies (one launch)
     TransposeBatch TB;
-    const BwdWT WT = transposed_weights<D>(P, wp(W.wt), TB);     // written by the forward (prepare_weights)
+    const BwdWT WT = transposed_weights<D>(P, wt_base, TB);     // written by the forward (prepare_weights)
     // ---- out MLP
     {
         { ProfScope ps(KB_OUT, st);
@@ -704,14 +722,14 @@ int backward_impl(const AetherParams& P, const AetherParams& Gr, int64_t Nn, int
                     if (optin(reinterpret_cast<const void*>(kb_edge_acc8<true, 4>), lds_a)) return AETHER_EHIP;
                     kb_edge_acc8<true, 4><<<dim3(agrid), dim3(256), lds_a, st>>>(
                         P.l1_msg_b0, b2, nullptr, nullptr, nullptr, wp(W.feat), send_s, recv_s, rowptr, wp(W.DN), wp(W.DE), 1, bG,
-                        wp(W.DA), partial, wp(W.wimg) + fused_wimg_offset(1, 0), wp(W.wimg) + fused_wimg_offset(1, 1), E, (int)agrid);
+                        wp(W.DA), partial, wimg + fused_wimg_offset(1, 0), wimg + fused_wimg_offset(1, 1), E, (int)agrid);
                     O.we = Gr.l1_msg_w0; O.ldwe = F1; O.ncols = F1; O.b1 = Gr.l1_msg_b0; O.nb_e = 2;
                 } else {
                     if (optin(reinterpret_cast<const void*>(kb_edge_acc8<false, 4>), lds_a)) return AETHER_EHIP;
                     kb_edge_acc8<false, 4><<<dim3(agrid), dim3(256), lds_a, st>>>(
                         nullptr, b2, wp(W.ps[l - 2]), wp(W.pr[l - 2]), wp(W.e[l - 2]), nullptr, send_s, recv_s, rowptr, wp(W.DN),
-                        wp(W.DE), l < 4 ? 1 : 0, bG, nullptr, partial, wp(W.wimg) + fused_wimg_offset(l, 0),
-                        wp(W.wimg) + fused_wimg_offset(l, 1), E, (int)agrid);
+                        wp(W.DE), l < 4 ? 1 : 0, bG, nullptr, partial, wimg + fused_wimg_offset(l, 0),
+                        wimg + fused_wimg_offset(l, 1), E, (int)agrid);
                     O.we = Gr.ln_msg_w0[l - 2] + 2 * H; O.ldwe = 3 * H; O.ncols = H; O.b1 = nullptr; O.nb_e = 4;
                 }
                 k_edge_acc8_reduce<<<dim3((FB_PART + 63) / 64), dim3(1024), 0, st>>>(partial, (int)agrid, O);
@@ -803,20 +821,22 @@ bool fused_backward_applies(const AetherGraphInfo& info, int64_t Nn, int64_t E) 
 template <int D>
 int backward_fused_impl(const AetherParams& P, const AetherParams& Gr, int64_t Nn, int64_t E, const AetherGraphInfo& info,
                         const float* x, const float* vel, const float* charges, const char* graph, char* ws,
-                        const float* g_out, hipStream_t st, float* grad_field = nullptr) {
+                        const float* g_out, hipStream_t st, float* grad_field = nullptr, const PreparedWeights* pw = nullptr) {
     constexpr int F1 = 7 * D + D * (D - 1) / 2 + 2;
     constexpr int FIN = 2 * D + 16;
     GraphLayout G(E, Nn, false);
     WsLayout W(Nn, E, D, true);
     auto gp = [&](size_t off) { return reinterpret_cast<const int32_t*>(graph + off); };
     auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    float* const wt_base = pw ? pw->wt : wp(W.wt);          // (backward_impl)
+    float* const wimg = pw ? pw->wimg : wp(W.wimg);
     const int32_t *recv_s = gp(G.recv_s), *rowptr = gp(G.rowptr);
     const int32_t *sperm = gp(G.sperm), *srowptr = gp(G.srowptr);
     OuterList L;
     const unsigned ngrid = (unsigned)((Nn + 15) / 16);
     // ---- transposed weight copies (one launch)
     TransposeBatch TB;
-    const BwdWT WT = transposed_weights<D>(P, wp(W.wt), TB);     // written by the forward (prepare_weights)
+    const BwdWT WT = transposed_weights<D>(P, wt_base, TB);     // written by the forward (prepare_weights)
     // ---- out MLP
     { ProfScope ps(KB_OUT, st);
     kb_out<D><<<dim3(ngrid), dim3(256), 0, st>>>(P, WT, wp(W.x[4]), wp(W.nodeinfo), g_out, wp(W.DXl[4]), wp(W.O1),
@@ -843,8 +863,8 @@ int backward_fused_impl(const AetherParams& P, const AetherParams& Gr, int64_t N
             Y.upd_w0 = k == 0 ? P.l1_upd_w0 : P.ln_upd_w0[k - 1];
             Y.upd_b0 = k == 0 ? P.l1_upd_b0 : P.ln_upd_b0[k - 1];
             Y.w4t = WT.upd_w2t[k]; Y.w3t = WT.upd_w0t[k]; Y.w2t = WT.msg_w2t[k]; Y.w0t = WT.msg_w0t[k];
-            Y.img_e = wp(W.wimg) + fused_wimg_offset(k + 1, 0);      // written by the forward of this step (prepare_weights)
-            Y.img_2 = wp(W.wimg) + fused_wimg_offset(k + 1, 1);
+            Y.img_e = wimg + fused_wimg_offset(k + 1, 0);      // written by the forward of this step (prepare_weights)
+            Y.img_2 = wimg + fused_wimg_offset(k + 1, 1);
             Y.U = wp(W.Ul[k]); Y.DPU = wp(W.DPUl[k]); Y.DPS = wp(W.DPSl[k]); Y.DPR = wp(W.DPRl[k]);
             Y.DXout = k == 0 ? nullptr : wp(W.DXl[k]);         // layer k + 1 produces dL/dx_k
         }
@@ -920,6 +940,27 @@ int backward_fused_impl(const AetherParams& P, const AetherParams& Gr, int64_t N
         R.f1 = F1;
         if (run_outer(L, wp(W.partial), W.partial_cap, st, &R)) return AETHER_EHIP;
     }
+    HIP_OK(hipGetLastError());
+    return AETHER_OK;
+}
+
+// Gradients with respect to the inputs from what a backward left in `ws` (aether_backward_inputs; every step of
+// aether_rollout_backward): kb_inputs, and kb_edge_attr_grad when grad_ea is wanted.
+template <int D>
+int backward_inputs_impl(const AetherParams& P, int64_t Nn, int64_t E, const float* x, const float* vel, const float* charges,
+                         const char* graph, char* ws, const float* out, const float* g_out, float* grad_x, float* grad_vel,
+                         float* grad_ea, const float* field_gz, hipStream_t st) {
+    GraphLayout G(E, Nn, false);
+    WsLayout W(Nn, E, D, true);
+    auto gp = [&](size_t off) { return reinterpret_cast<const int32_t*>(graph + off); };
+    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    kb_inputs<D><<<dim3((unsigned)((Nn + 7) / 8)), dim3(256), 0, st>>>(P, x, vel, charges, wp(W.nodeinfo), out, g_out, wp(W.DA),
+                                                                       wp(W.DN), wp(W.DF), gp(G.rowptr), gp(G.send_s),
+                                                                       gp(G.recv_s), gp(G.srowptr), gp(G.sperm), grad_x,
+                                                                       grad_vel, Nn, field_gz);
+    if (grad_ea && E > 0)
+        kb_edge_attr_grad<<<dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st>>>(wp(W.DA), gp(G.perm), 7 * D + D * (D - 1) / 2,
+                                                                                  grad_ea, E);
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }
@@ -1440,28 +1481,11 @@ int aether_backward_inputs(const AetherParams* params, int num_dims, int64_t n_n
         return fail(AETHER_ESPACE, "backward_inputs: workspace too small (the workspace of the forward / aether_backward pair)");
     hipStream_t st = (hipStream_t)stream;
     if (take_async_error()) return AETHER_EHIP;
-    GraphLayout G(n_edges, n_nodes, false);
-    WsLayout W(n_nodes, n_edges, num_dims, true);
-    const char* g = (const char*)graph;
-    char* ws = (char*)workspace;
-    auto gp = [&](size_t off) { return reinterpret_cast<const int32_t*>(g + off); };
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    const dim3 grid((unsigned)((n_nodes + 7) / 8));
     if (num_dims == 2)
-        kb_inputs<2><<<grid, dim3(256), 0, st>>>(*params, x, vel, charges, wp(W.nodeinfo), out, grad_out, wp(W.DA), wp(W.DN),
-                                               wp(W.DF), gp(G.rowptr), gp(G.send_s), gp(G.recv_s), gp(G.srowptr),
-                                               gp(G.sperm), grad_x, grad_vel, n_nodes, field_input_grad);
-    else
-        kb_inputs<3><<<grid, dim3(256), 0, st>>>(*params, x, vel, charges, wp(W.nodeinfo), out, grad_out, wp(W.DA), wp(W.DN),
-                                               wp(W.DF), gp(G.rowptr), gp(G.send_s), gp(G.recv_s), gp(G.srowptr),
-                                               gp(G.sperm), grad_x, grad_vel, n_nodes, field_input_grad);
-    if (grad_edge_attr && n_edges > 0) {
-        const int D = num_dims, col0 = 7 * D + D * (D - 1) / 2;
-        kb_edge_attr_grad<<<dim3((unsigned)((n_edges + 255) / 256)), dim3(256), 0, st>>>(wp(W.DA), gp(G.perm), col0, grad_edge_attr,
-                                                                                       n_edges);
-    }
-    HIP_OK(hipGetLastError());
-    return AETHER_OK;
+        return backward_inputs_impl<2>(*params, n_nodes, n_edges, x, vel, charges, (const char*)graph, (char*)workspace, out,
+                                       grad_out, grad_x, grad_vel, grad_edge_attr, field_input_grad, st);
+    return backward_inputs_impl<3>(*params, n_nodes, n_edges, x, vel, charges, (const char*)graph, (char*)workspace, out,
+                                   grad_out, grad_x, grad_vel, grad_edge_attr, field_input_grad, st);
 }
 
 int aether_backward_field(const AetherParams* params, const AetherParams* grads, int num_dims, int64_t n_nodes,
@@ -1567,5 +1591,6 @@ int64_t aether_debug_fetch(const char* name, int num_dims, int64_t n_nodes, int6
 }
 
 #include "host_wide.inc"
+#include "host_rollout_train.inc"
 
 }  // extern "C"

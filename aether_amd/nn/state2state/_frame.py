@@ -82,8 +82,9 @@ class _WsToken:
     __slots__ = ("__weakref__",)
 
 
-def _train_workspace(module, ws_bytes, device):
-    """The workspace of a training forward and the token its autograd node holds (None under capture).
+def _train_workspace(module, ws_bytes, device, slot="_train_ws"):
+    """The workspace of a training forward and the token its autograd node holds (None under capture).  ``slot``: the
+    module attribute that caches it (a training rollout keeps its own, many times a step's).
 
     The backward reads this forward's intermediates: one workspace per forward that is still waiting for its backward.
     The usual loop (forward, backward, step) gets the module's cached buffer back every time -- a fresh torch.empty per
@@ -91,8 +92,11 @@ def _train_workspace(module, ws_bytes, device):
     shard of config 5 (~120 GB each) pushed the caching allocator into freeing and re-allocating device memory every step
     (0.44 s of a 0.55 s step).  Under hipGraph capture the buffer comes from the graph's pool as before.
     "Still waiting": the autograd node that saved the buffer is alive (a token it holds; after backward() without
-    retain_graph the node and the token are gone).  The module keeps ``_train_ws`` and ``_train_ws_token``."""
-    tw, tok = module._train_ws, module._train_ws_token
+    retain_graph the node and the token are gone).  The module keeps ``_train_ws`` and ``_train_ws_token`` -- and, for a
+    training rollout (``slot``), ``_rollout_train_ws`` and its token: that buffer is the size of the longest rollout
+    trained so far (one training workspace + what a forward keeps per further step: 0.8 GB for 4 steps, 2.0 GB for 20 at
+    N=20, batch=128) and stays with the module until a larger one replaces it or the module goes."""
+    tw, tok = getattr(module, slot, None), getattr(module, slot + "_token", None)
     busy = tok is not None and tok() is not None
     capturing = torch.cuda.is_current_stream_capturing()
     if tw is not None and not busy and tw.numel() >= ws_bytes and tw.device == device and not capturing:
@@ -100,10 +104,10 @@ def _train_workspace(module, ws_bytes, device):
     else:
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
         if not capturing:
-            module._train_ws = ws
+            setattr(module, slot, ws)
     token = _WsToken() if not capturing else None
     if token is not None:
-        module._train_ws_token = weakref.ref(token)
+        setattr(module, slot + "_token", weakref.ref(token))
     return ws, token
 
 
@@ -154,6 +158,48 @@ def _f32(t):
 def _f32g(t):
     """As ``_f32``, but an input that requires a gradient stays attached."""
     return t.to(torch.float32).contiguous() if t.requires_grad else _f32(t)
+
+
+class _RolloutStep(torch.autograd.Function):
+    """aether_rollout_train_forward / aether_rollout_backward behind torch.autograd: the whole k-step rollout is ONE
+    autograd node (parameters, and x / vel where they require a gradient)."""
+
+    N_FIXED = 8          # module, x, vel, charges, graph, n_edges, steps, dt precede the parameters
+
+    @staticmethod
+    def forward(ctx, module, x, vel, charges, graph, n_edges, steps, dt, *params):
+        ps = module._rollout_train_params(x.device)
+        traj, ws, token = module._rollout_train_forward(ps, x, vel, charges, graph, n_edges, steps, dt)
+        ctx.module = module
+        ctx.saved = (x, vel, charges, graph, ws, n_edges, steps, dt, token)
+        ctx.consumed = False
+        ctx.save_for_backward(traj)
+        return traj
+
+    @staticmethod
+    def backward(ctx, grad_traj):
+        module = ctx.module
+        if ctx.consumed:        # (aether_rollout_backward: a step's temporaries land on the later steps' kept intermediates)
+            raise RuntimeError("trying to backward through a differentiable_rollout a second time: the first backward "
+                               "consumed its workspace (call differentiable_rollout again)")
+        ctx.consumed = True
+        x, vel, charges, (gbuf, ginfo), ws, n_edges, steps, dt, _token = ctx.saved
+        traj, = ctx.saved_tensors
+        plist, views, dst_flat, dst_views, aliased, gs, finish = module._grad_destination()
+        g = grad_traj.to(torch.float32).contiguous()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        gv = torch.empty_like(vel) if ctx.needs_input_grad[2] else None
+        ps = module._rollout_train_params(x.device, refresh=False)
+        st = _lib.load().aether_rollout_backward(ps, gs, module.num_dims, module._kw, x.shape[0], n_edges, x.data_ptr(),
+                                                 vel.data_ptr(), charges.data_ptr(), gbuf.data_ptr(), C.byref(ginfo),
+                                                 ws.data_ptr(), ws.numel(), traj.data_ptr(), g.data_ptr(),
+                                                 None if gx is None else gx.data_ptr(), None if gv is None else gv.data_ptr(),
+                                                 steps, dt, torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(st, "aether_rollout_backward")
+        if finish is not None:
+            finish()
+        out = _hand_over_grads(module, plist, views, dst_flat, dst_views, aliased, ctx.needs_input_grad[_RolloutStep.N_FIXED:])
+        return (None, gx, gv, None, None, None, None, None) + tuple(out)
 
 
 # -- a model inside its kernel-width engine --------------------------------------------------------------------------
@@ -314,6 +360,7 @@ class FrameModule(nn.Module):
         self._last_ws = None
         self._wimg_key = None             # (_ws_key, parameter versions) whose split weight images the workspace holds
         self._ws_key = None               # (workspace, shape, graph) of the last completed inference call
+        self._rollout_train_ws, self._rollout_train_ws_token = None, None     # differentiable_rollout (_train_workspace)
 
     # -- caches ------------------------------------------------------------------------
     def _drop(self, names):
@@ -548,6 +595,58 @@ class FrameModule(nn.Module):
         self._ws_key, self._wimg_key = pending
         self._last_ws = ws
         return traj
+
+    # -- training through the rollout ------------------------------------------------------
+    def _rollout_train_params(self, device, refresh=True):
+        """byref of the AetherParams a training rollout runs on; ``refresh``: bring copies of the parameters up to date
+        first (the forward does, the backward reads what the forward read)."""
+        raise NotImplementedError
+
+    def _grad_destination(self):
+        """Where a backward writes the parameter gradients -> (parameters, views of the flat gradient buffer, destination
+        flat buffer and its views, is that the second buffer, byref of the destinations' AetherParams, a callable that
+        finishes them (engine-shaped scratch cut to the model's shapes) or None)."""
+        raise NotImplementedError
+
+    def _rollout_train_forward(self, ps, x, vel, charges, graph, n_edges, steps, dt):
+        """``aether_rollout_train_forward`` -> (trajectory [steps, n_nodes, D], workspace, its token)."""
+        gbuf, ginfo = graph
+        n_nodes, D = x.shape
+        lib = _lib.load()
+        nbytes = lib.aether_rollout_train_workspace_bytes(n_nodes, n_edges, D, self._kw, steps)
+        ws, token = _train_workspace(self, max(nbytes, 256), x.device, slot="_rollout_train_ws")
+        # an optimizer step follows: the inference workspace's weight images are stale from here on (``_step``)
+        self._ws_key = self._wimg_key = None
+        traj = torch.empty(steps, n_nodes, D, dtype=torch.float32, device=x.device)
+        st = lib.aether_rollout_train_forward(ps, D, self._kw, n_nodes, n_edges, x.data_ptr(), vel.data_ptr(),
+                                              charges.data_ptr(), gbuf.data_ptr(), C.byref(ginfo), ws.data_ptr(), ws.numel(),
+                                              traj.data_ptr(), steps, dt, self.flags & _FORCED,
+                                              torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(st, "aether_rollout_train_forward")
+        return traj, ws, token
+
+    def _rollout_grad(self, x, vel, edges, charges, steps, dt, num_nodes=None):
+        """The rollout of ``_rollout`` attached to autograd (``_RolloutStep``): gradients for the parameters that require
+        one and, where they require one, ``x`` and ``vel``."""
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("differentiable_rollout: steps must be at least 1")
+        send, recv, n_nodes, E = self._validate_rollout(x, vel, edges, charges, num_nodes)
+        if self.dropout_prob > 0.0 and self.training:
+            raise RuntimeError(f"{self._name}.differentiable_rollout draws no dropout masks (one pair per step would be "
+                               "needed): call .eval() first or build the model with dropout_prob = 0")
+        if self._kw != 64:
+            raise _lib.AetherHipError("rollout training: 64-wide engine only")
+        graph = self.prepare_graph((send, recv), n_nodes)
+        return _RolloutStep.apply(self, _f32g(x), _f32g(vel), _f32(charges), graph, E, steps, float(dt), *self._param_list())
+
+    def differentiable_rollout(self, x, vel, edges, charges, steps, dt=1.0):
+        """``rollout`` for training: positions ``[steps, n_nodes, D]`` of the same protocol, attached to autograd for the
+        parameters and, where they require a gradient, ``x`` and ``vel`` -- a k-step loss on it trains through all steps
+        (``aether_rollout_train_forward`` / ``aether_rollout_backward``: the steps, the chain between them and the sum of
+        the parameter gradients over the steps all run on the device).  Works in train() and eval(); in train() with
+        dropout_prob > 0 it raises, as ``rollout`` does."""
+        return self._rollout_grad(x, vel, edges, charges, steps, dt)
 
     # -- test hooks -------------------------------------------------------------------
     def debug_fetch(self, name, n_nodes, n_edges, cols):

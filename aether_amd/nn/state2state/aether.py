@@ -193,6 +193,16 @@ class Aether(FrameModule):
     def _rollout_params(self, device):
         return self._param_struct_ref(), None
 
+    def _rollout_train_params(self, device, refresh=True):
+        return self._param_struct_ref()
+
+    def _grad_destination(self):
+        flat, gstruct, views = self._grad_buffers()
+        plist = self._param_list()
+        aliased = _grads_alias_flat(self, plist, views)
+        dst_flat, dst_struct, dst_views = self._grad_buffers(second=True) if aliased else (flat, gstruct, views)
+        return plist, views, dst_flat, dst_views, aliased, C.byref(dst_struct), None
+
     def _grad_buffers(self, second=False):
         """Flat fp32 gradient buffer + an AetherParams struct and per-parameter views into it.  ``second``: a
         scratch buffer of the same layout, the destination of a backward whose result has to be ADDED to gradients
@@ -250,3 +260,12 @@ class Aether(FrameModule):
             self._require_gpu(x)
             return self._sync_engine().rollout(x, vel, edges, charges, steps, dt)
         return self._rollout(x, vel, edges, charges, steps, dt, reuse=True)
+
+    def differentiable_rollout(self, x, vel, edges, charges, steps, dt=1.0):
+        if self.hidden_size != self._kw:
+            if int(steps) < 1:
+                raise ValueError("differentiable_rollout: steps must be at least 1")
+            self._require_gpu(x)
+            raise _lib.AetherHipError("rollout training: 64-wide engine only (hidden_size must be 64; a narrower Aether runs "
+                                      "on a zero-padded engine that has no rollout backward)")
+        return super().differentiable_rollout(x, vel, edges, charges, steps, dt)

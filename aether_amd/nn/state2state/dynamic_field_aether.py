@@ -264,6 +264,11 @@ class DynamicFieldAether(FrameModule):
             raise ValueError("num_nodes (objects per graph) is required, as in forward")
         return self._rollout(x, vel, edges, charges, steps, dt, num_nodes=num_nodes)
 
+    def differentiable_rollout(self, x, vel, edges, charges, steps, dt=1.0, num_nodes=None):
+        """Not built: the backward through a rollout exists for the built-in field net and the zero field only (the
+        latent field's own backward would have to join the chain between the steps)."""
+        raise _lib.AetherHipError("DynamicFieldAether.differentiable_rollout: not built")
+
     def forward(self, h, x, edges, vel, edge_attr_orig, charges, num_nodes):
         """``h`` is ignored, as in the reference (dynamic_field_aether.py:79-100)."""
         send, recv, n_nodes, E = self._validate_forward(x, vel, edges, edge_attr_orig, charges, num_nodes)

@@ -128,6 +128,7 @@ class LoCS(FrameModule):
         self._ws_key = None
         self._wimg_key = None
         self._train_ws, self._train_ws_token = None, None
+        self._rollout_train_ws, self._rollout_train_ws_token = None, None
 
     # Every device buffer above may be baked into a captured step (GraphedTrainStep): they are dropped only when the
     # parameters themselves moved, which invalidates such a graph anyway.
@@ -274,6 +275,24 @@ class LoCS(FrameModule):
     def _rollout_params(self, device):
         self._images(device, False)
         return C.byref(self._struct(device)), None
+
+    def _rollout_train_params(self, device, refresh=True):
+        # As ``rollout``, not as ``forward``: the rollout entries take no external field, so the engine's built-in field
+        # net runs on its all-zero weights (``_dummies``) -- a field of exactly 0 and, in the backward, zero input
+        # gradients through it; its parameter gradients go to ``_dummy_grad`` and are dropped.  The charges are the real
+        # ones (the edge attribute q_i q_j); they only index the zero embedding.
+        if refresh:
+            self._images(device, True)
+        return C.byref(self._struct(device))
+
+    def _grad_destination(self):
+        plist = self._param_list()
+        flat, views = self._grad_buffers()
+        aliased = _grads_alias_flat(self, plist, views)
+        dst_flat, dst_views = self._grad_buffers(second=True) if aliased else (flat, views)
+        # engine-shaped gradients (the mapped first-layer tensors; every GNN tensor of a narrow model) cut to LoCS's shapes
+        gs, kgrads = self._grad_struct(dst_views)
+        return plist, views, dst_flat, dst_views, aliased, C.byref(gs), lambda: self._cut(kgrads, dst_views)
 
     # -- reference surface -----------------------------------------------------------
     def forward(self, h, x, edges, vel, edge_attr_orig):

@@ -6,7 +6,8 @@ restates (oracle/aether_oracle.py::rollout): x_{t+1} = Aether(x_t, v_t), v_{t+1}
 with ``edge_attr = [q_i q_j, |x_i - x_j|]`` rebuilt from the current positions every step
 (experiments/lorentz/main.py:243-246).  Everything stays on the device; the edge index (and therefore
 the receiver-sorted graph view) is reused across steps.  ``rollout`` runs the loop inside the library
-(``aether_rollout``); ``rollout_stepwise`` is the loop of module calls it replaces.  ``EGNN_vel_Aether`` and ``ClofNet*`` have
+(``aether_rollout``); ``rollout_stepwise`` is the loop of module calls it replaces; ``rollout_loss`` trains through it (``differentiable_rollout``:
+the k-step loss and its backward through time on the device).  ``EGNN_vel_Aether`` and ``ClofNet*`` have
 the same ``rollout`` (``aether_egnn_rollout`` / ``aether_clof_rollout``) under the runner's preparation for them --
 ``nodes = |vel|`` and the squared distance in ``edge_attr``; their loop of module calls is ``rollout_stepwise_gnn``.
 """
@@ -66,3 +67,31 @@ def rollout_stepwise_gnn(model, x, vel, edges, charges, steps: int, dt: float = 
 def rollout_mse(pred, truth):
     """Per-step MSE over (sample, particle, feature), experiments/electrostatic/evaluate.py:61-70."""
     return ((pred - truth) ** 2).mean(dim=(1, 2))
+
+
+class _MseLoss(torch.autograd.Function):
+    """``aether_mse_loss_grad`` behind torch.autograd: loss and d(loss)/d(pred) in one launch."""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        from .optim import mse_loss_grad
+        loss, grad = mse_loss_grad(pred, target)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.saved_tensors[0] * g, None
+
+
+def rollout_loss(model, x, vel, edges, charges, targets, dt: float = 1.0):
+    """The k-step ("push-forward") training loss: mean over all steps and elements of the squared error between the
+    device rollout ``model.differentiable_rollout(x, vel, edges, charges, steps = targets.shape[0], dt)`` and
+    ``targets [steps, n_nodes, D]`` (the positions at t = 1 .. steps).  ``.backward()`` runs the backward through time
+    on the device; where a runner computes ``loss_mse(model(...), target)`` for one step, it calls this instead."""
+    if targets.dim() != 3:
+        raise ValueError("targets must be [steps, n_nodes, D]")
+    traj = model.differentiable_rollout(x, vel, edges, charges, targets.shape[0], dt)
+    if traj.shape != targets.shape:
+        raise ValueError(f"targets must be {tuple(traj.shape)}, got {tuple(targets.shape)}")
+    return _MseLoss.apply(traj.reshape(-1), targets.reshape(-1))

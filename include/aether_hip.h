@@ -324,6 +324,48 @@ int64_t aether_debug_fetch_h(const char* name, int num_dims, int hidden, int64_t
                              const void* workspace, float* dst, void* stream);
 
 /*
+ * Training through the device rollout: a k-step ("push-forward") loss and its backward through time.  Replaces a Python
+ * loop of differentiable module calls with the runner's tensor ops in between (the per-batch prep and the
+ * loss.backward() of experiments/lorentz/main.py:243-247,289-291, repeated per step and stitched together by autograd;
+ * oracle/aether_oracle.py::rollout restates the protocol) by two library calls:
+ *   x_{t+1} = Aether(x_t, v_t, ea_t),  ea_t = [q_i q_j, |x_i - x_j|] from x_t,  v_{t+1} = (x_{t+1} - x_t) / dt,  t = 0..steps-1.
+ * The 64-wide engine only, on both its paths (fused and streamed); hidden > 64 returns AETHER_EINVAL.
+ *
+ * aether_rollout_train_forward -- experiments/lorentz/main.py:243-247 per step, oracle rollout: the arguments of
+ *   aether_rollout_h; writes trajectory[steps][n_nodes][D] = x_1 .. x_steps and keeps, per step, what the backward reads
+ *   (the AETHER_FLAG_KEEP_INTERMEDIATES | AETHER_FLAG_BACKWARD_ONLY layout, edge attributes derived in the kernels) and the
+ *   step's input velocity in that step's own slice of `workspace`
+ *   (aether_rollout_train_workspace_bytes(n_nodes, n_edges, num_dims, hidden, steps) bytes; 0 for sizes it refuses).
+ *   flags: AETHER_FLAG_FORCE_STREAMED / AETHER_FLAG_FORCE_FUSED; no dropout masks.  Everything derived from the weights is
+ *   prepared once per call.
+ * aether_rollout_backward -- experiments/lorentz/main.py:289-291 through all steps, autograd through the oracle's rollout:
+ *   given grad_trajectory[steps][n_nodes][D] = dL/dx_1 .. dL/dx_steps of the caller's loss, on the workspace and trajectory
+ *   of the forward, writes
+ *     grads    : AetherParams of destinations, OVERWRITTEN with dL/dtheta summed over the steps (step steps-1 first, a fixed
+ *                order: the same bits on every run);
+ *     grad_x0  : dL/dx_0 [n_nodes][D], grad_vel0 : dL/dv_0 [n_nodes][D]; either may be NULL.
+ *   Per step: aether_backward, aether_backward_inputs and one chain launch that forms the next-earlier step's grad_out
+ *   from g, gx, gv of this and the later step and the distance term of ea (a fixed-order sum over each node's in- and
+ *   out-edge lists: no float atomics) and adds the step's parameter gradients (csrc/rollout_bwd.h).
+ *   The call CONSUMES the workspace (a step's temporaries are laid over the later steps' kept intermediates, which it
+ *   has finished with: the workspace grows per step by what a forward keeps, not by a whole training workspace): one
+ *   aether_rollout_backward per aether_rollout_train_forward.
+ *   Exactly coincident end points of an edge (distance 0, self loops included) are UNDEFINED: the distance has no
+ *   derivative there.
+ * Both are stream-ordered and capturable in a hipGraph: no synchronisation, no allocation.  Entry checks (null pointers,
+ * info mismatch, steps < 1, dt == 0, a short workspace -> AETHER_ESPACE) run before anything is queued.
+ */
+size_t aether_rollout_train_workspace_bytes(int64_t n_nodes, int64_t n_edges, int num_dims, int hidden, int steps);
+int aether_rollout_train_forward(const AetherParams* params, int num_dims, int hidden, int64_t n_nodes, int64_t n_edges,
+                                 const float* x0, const float* vel0, const float* charges, const void* graph,
+                                 const AetherGraphInfo* info, void* workspace, size_t workspace_bytes, float* trajectory,
+                                 int steps, float dt, int flags, void* stream);
+int aether_rollout_backward(const AetherParams* params, const AetherParams* grads, int num_dims, int hidden, int64_t n_nodes,
+                            int64_t n_edges, const float* x0, const float* vel0, const float* charges, const void* graph,
+                            const AetherGraphInfo* info, void* workspace, size_t workspace_bytes, const float* trajectory,
+                            const float* grad_trajectory, float* grad_x0, float* grad_vel0, int steps, float dt, void* stream);
+
+/*
  * seq2seq Aether, field query: replaces Aether.predict_field
  * (nn/seq2seq/aether.py:86-90) = FourierFeatureMapper (nn/nn/fourier_feature_mapper.py:7-21) followed by
  * field_net (aether.py:72-78).  Unlike the state2state field it sees positions only.
