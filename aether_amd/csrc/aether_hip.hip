@@ -232,7 +232,7 @@ constexpr int FUSED_PAIR_STRIDE = 8;   // distance of the two workgroups of a sp
                                        // the hand-off protocol is the cross-XCD one either way)
 
 struct GraphLayout {
-    size_t perm, send_s, recv_s, rowptr, gsel, wgdesc, tdesc, tsel, tdst, lorder, ledge, nrange, hflags, sperm, srowptr, keys,
+    size_t perm, send_s, recv_s, rowptr, gsel, wgdesc, tdesc, trec, lorder, ledge, nrange, hflags, sperm, srowptr, keys,
         vals, diff, cross, flag, cub, total, cub_bytes;
     int64_t max_wgs, max_tiles;
     GraphLayout(int64_t E, int64_t Nn, bool with_sort_scratch = true) {
@@ -248,8 +248,7 @@ struct GraphLayout {
         max_tiles = tables ? (E + 15) / 16 + 2 * Nn : 0;
         wgdesc = take((size_t)max_wgs * sizeof(FusedWG) + 4);
         tdesc = take((size_t)max_tiles * sizeof(FusedTile) + 4);
-        tsel = take((size_t)max_tiles * 64 * 4 + 4);
-        tdst = take((size_t)max_tiles * 64 * 4 + 4);
+        trec = take((size_t)max_tiles * FUSED_TREC * 4 + 4);          // per-tile segment records (k_graph_tiles)
         lorder = take(tables ? e4 : 4);         // local edge order of every fused workgroup (FusedWG)
         ledge = take(tables ? 4 * e4 : 16);     // ... and {sorted position, sender, receiver, original edge} in that order
         nrange = take(tables ? (size_t)Nn * 16 : 4);                 // per node: local index ranges of its two runs
@@ -444,7 +443,7 @@ int prepare_weights(const AetherParams& P, char* ws, bool split_images, bool tra
 template <int D, int NW, int ROUNDS, bool KEEP>
 int fused_launch(const AetherParams& P, const float* x, const float* vel, const float* charges,
                  const float* ea, const int32_t* perm, const int32_t* send_s, const int32_t* recv_s,
-                 const int32_t* rowptr, const FusedWG* wgdesc, const uint32_t* tsel, const uint32_t* tdst,
+                 const int32_t* rowptr, const FusedWG* wgdesc, const uint32_t* trec,
                  const int4* ledge, const int32_t* nrange, int n_groups, const FusedDebug& dbg, float* out,
                  hipStream_t st) {
     auto kern = k_fused<D, NW, ROUNDS, KEEP>;
@@ -452,7 +451,7 @@ int fused_launch(const AetherParams& P, const float* x, const float* vel, const 
     if (ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return AETHER_EHIP;
     ProfScope ps(K_FUSED, st);
     kern<<<dim3((unsigned)n_groups), dim3(NW * 64), lds, st>>>(P, x, vel, charges, ea, perm, send_s, recv_s,
-                                                              rowptr, wgdesc, tsel, tdst, ledge, nrange, dbg, out);
+                                                              rowptr, wgdesc, trec, ledge, nrange, dbg, out);
     return AETHER_OK;
 }
 
@@ -482,8 +481,7 @@ int fused_impl(const AetherParams& P, int64_t Nn, int64_t E, const AetherGraphIn
     dbg.wimg = pw ? pw->wimg : wp(W.wimg);
     dbg.step = step;
     const FusedWG* wgd = reinterpret_cast<const FusedWG*>(graph + G.wgdesc);
-    const uint32_t* tsel = reinterpret_cast<const uint32_t*>(graph + G.tsel);
-    const uint32_t* tdst = reinterpret_cast<const uint32_t*>(graph + G.tdst);
+    const uint32_t* trec = reinterpret_cast<const uint32_t*>(graph + G.trec);
     (void)ws_reused;
     const int tiles = (info.max_group_edges + 15) / 16;
     // split-GEMM variants: 3 x bf16 images of the eight edge-MLP matrices; training: the backward's transposed copies
@@ -491,10 +489,10 @@ int fused_impl(const AetherParams& P, int64_t Nn, int64_t E, const AetherGraphIn
     int rc;
 #define AETHER_FUSED_CASE(NWV, R)                                                                     \
     rc = keep ? fused_launch<D, NWV, R, true>(P, x, vel, charges, ea, gp(G.perm), gp(G.send_s),       \
-                                              gp(G.recv_s), gp(G.rowptr), wgd, tsel, tdst,            \
+                                              gp(G.recv_s), gp(G.rowptr), wgd, trec,                  \
                                               reinterpret_cast<const int4*>(graph + G.ledge), gp(G.nrange), info.n_groups, dbg, out, st) \
               : fused_launch<D, NWV, R, false>(P, x, vel, charges, ea, gp(G.perm), gp(G.send_s),      \
-                                               gp(G.recv_s), gp(G.rowptr), wgd, tsel, tdst,           \
+                                               gp(G.recv_s), gp(G.rowptr), wgd, trec,                 \
                                                reinterpret_cast<const int4*>(graph + G.ledge), gp(G.nrange), info.n_groups, dbg, out, st)
     if (tiles <= 8) { AETHER_FUSED_CASE(8, 1); }
     else if (tiles <= 16) { AETHER_FUSED_CASE(8, 2); }
@@ -1236,7 +1234,7 @@ static int graph_build_tables(const GraphLayout& G, char* g, int64_t n_edges, in
                                           hipMemcpyHostToDevice, st));
                     k_graph_tiles<<<dim3((unsigned)tiles.size()), dim3(64), 0, st>>>(
                         (const FusedTile*)(g + G.tdesc), (const FusedWG*)(g + G.wgdesc), recv_s, rowptr,
-                        (const int32_t*)(g + G.lorder), (uint32_t*)(g + G.tsel), (uint32_t*)(g + G.tdst));
+                        (const int32_t*)(g + G.lorder), (uint32_t*)(g + G.trec));
                 }
                 HIP_OK(hipStreamSynchronize(st));       // host vectors must outlive the copies
                 info->n_groups = (int32_t)wgs.size();

@@ -8,17 +8,25 @@
 //     layers (it is the next layer's MFMA B operand as it stands);
 //   * node state (x, n, P_s, P_r) and the per-layer edge weights live in LDS (padded rows);
 //   * the mean over in-edges needs no workgroup barrier inside a layer: the wave parks its tile in
-//     16 private LDS rows and multiplies it, transposed, by the tile's 0/1 receiver-segment matrix
-//     on the matrix core (16 extra MFMAs, built once per tile from the graph structure); one
-//     partial row per (receiver, tile) goes to LDS and the node phase adds a node's partial rows in
-//     tile order.  Fixed order everywhere: deterministic, no atomics.  (A masked DPP butterfly was
-//     measured 2-4x slower here: the kernel is VALU-issue-bound, not MFMA-bound.)
+//     16 private LDS rows and reads it back by columns -- lane L adds column L's 16 values in row
+//     order (16 vector adds per tile) and stores the running sum after the last row of each receiver
+//     segment; which rows end a segment, and where their sums go, is one record per tile built with
+//     the graph (k_graph_tiles), held in scalar registers: the tests and branches run on the scalar
+//     unit.  One partial row per (receiver, tile) goes to LDS and the node phase adds a node's
+//     partial rows in tile order.  Fixed order everywhere: deterministic, no atomics.  (Until round 8
+//     the sums were 16 fp32 MFMAs with the tile's 0/1 segment matrix: 512 cycles of vector-ALU time
+//     per tile, most of it multiplying zeros; a masked DPP butterfly on the accumulator layout was
+//     measured 2-4x slower than that in round 1, before the staging rows existed.)
 //   * node-level GEMMs are split along their output rows over the waves; their weights come from L2
 //     in MFMA fragment shape (each is used once per group and layer), all issued before the barrier
 //     that ends the edge phase.
 // References: see common.h / streamed.h; the arithmetic per stage is identical to the streamed path.
 #pragma once
 #include "common.h"
+
+#ifndef AETHER_SUMS_SELECT
+#define AETHER_SUMS_SELECT 0   // diagnostic: 1 = branch-free receiver sums (a store per row, rows that end no segment into a spare row)
+#endif
 
 namespace {
 
@@ -56,8 +64,9 @@ template <int NW, int ROUNDS> struct FusedLds {          // offsets in floats
     // then the partner's: see FusedWG), whose rows are kept apart by an offset of n: 2 * 32 + 16 rows for up to
     // 16 tiles; with 17-24 tiles (ROUNDS == 3) only unsplit workgroups are built: 32 + 24 rows.
     static constexpr int PART_ROWS = ROUNDS == 3 ? FUSED_MAX_NODES + FUSED_MAX_TILES : 2 * FUSED_MAX_NODES + 16;
+    static constexpr int PART_SPARE = AETHER_SUMS_SELECT ? 1 : 0;  // diagnostic build: one row nobody reads
     static constexpr int PART = NINFO + FUSED_MAX_NODES * 24;      // [PART_ROWS][LDW]  per-(receiver, tile) sums
-    static constexpr int ARRIVED = PART + PART_ROWS * LDW;         // [4] ints: split mode, layer whose partner rows are in LDS
+    static constexpr int ARRIVED = PART + (PART_ROWS + PART_SPARE) * LDW;   // [4] ints: split mode, layer whose partner rows are in LDS
     static constexpr int SCRATCH = ARRIVED + 4;                    // aliased by the regions below
     static constexpr int FEAT_ROWS = 16 * (ROUNDS < 2 ? ROUNDS : 2);           // per wave: two rounds of features at a time
     static constexpr int SCRATCH_SIZE =
@@ -274,14 +283,19 @@ k_graph_lorder(FusedWG* __restrict__ wgdesc, const int32_t* __restrict__ send_s,
     }
 }
 
-// Per-tile structure of a workgroup's edge list in LOCAL order, built once with the graph: for every lane of
-// the tile's wave the 0/1 column of the segment matrix it feeds to the matrix core (tsel) and the
-// partial rows its four result registers go to (tdst, one byte each, 0xFF = none).  A segment = consecutive
-// rows with one receiver inside one run; its partial row is receiver + tile (+ n in the second run).
+// Per-tile structure of a workgroup's edge list in LOCAL order, built once with the graph: one record of
+// FUSED_TREC dwords per tile, the same for all 64 lanes of the tile's wave (k_fused keeps it in scalar registers).
+// A segment = consecutive rows with one receiver inside one run; its partial row is receiver + tile (+ n in the
+// second run), at most 2 * 32 + 15 < 256.
+//   dword 0      bit k: row k is the last row of its segment (padding rows end nothing)
+//   dword 1      number of segments
+//   dwords 2-5   partial row of segment s in byte s (segment order = row order), 0xFF behind the last segment
+//   dwords 6, 7  zero
+constexpr int FUSED_TREC = 8;
 __global__ void __launch_bounds__(64)
 k_graph_tiles(const FusedTile* __restrict__ tdesc, const FusedWG* __restrict__ wgdesc,
               const int32_t* __restrict__ recv_s, const int32_t* __restrict__ rowptr,
-              const int32_t* __restrict__ lorder, uint32_t* __restrict__ tsel, uint32_t* __restrict__ tdst) {
+              const int32_t* __restrict__ lorder, uint32_t* __restrict__ trec) {
     const FusedTile T = tdesc[blockIdx.x];
     const FusedWG wg = wgdesc[T.wg];
     const int eb = rowptr[wg.nb], m = rowptr[wg.ne] - eb, n = wg.ne - wg.nb;
@@ -290,35 +304,29 @@ k_graph_tiles(const FusedTile* __restrict__ tdesc, const FusedWG* __restrict__ w
     const int local = 16 * T.t + i;
     const bool valid = local < m;
     const int rcv = valid ? recv_s[eb + lorder[eb + local]] - wg.nb : -1;
-    // smask bit j: row j starts a new segment; segment ids count up in row order; padding rows belong to no segment.
-    const int prev = __shfl_up(rcv, 1, 16);
-    const unsigned smask = (unsigned)__ballot(q == 0 && i > 0 && (rcv != prev || local == na)) & 0xFFFFu;
-    const unsigned vmask = (unsigned)__ballot(q == 0 && valid) & 0xFFFFu;
-    unsigned sb = 0, dp = 0;
+    // row i ends its segment when the next row is padding, has another receiver or opens the second run
+    const int next = __shfl_down(rcv, 1, 16);
+    const bool ends = valid && (i == 15 || next != rcv || local + 1 == na);
+    const unsigned emask = (unsigned)__ballot(q == 0 && ends) & 0xFFFFu;
+    const int second = (wg.partner >= 0 && local >= na) ? n : 0;
+    const int myrow = rcv + T.t + second;                 // (meaningful on rows that end a segment)
+    // lane j < FUSED_TREC assembles dword j; the row lookups run on all lanes (shuffles)
+    const int j = lane & (FUSED_TREC - 1);
+    unsigned w = 0;
 #pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) {
-        const int edge = 4 * s4 + q;
-        const int seg_of_edge = __popc(smask & ((2u << edge) - 1u));
-        if (((vmask >> edge) & 1u) && seg_of_edge == i) sb |= 1u << s4;
+    for (int b = 0; b < 4; ++b) {
+        const int seg = 4 * (j - 2) + b;                  // dwords 2-5: segments 0..15
+        unsigned mm = emask;
+        for (int t = 0; t < seg && mm != 0; ++t) mm &= mm - 1;
+        const bool exists = seg >= 0 && seg < 16 && mm != 0;
+        const int k = mm != 0 ? __ffs(mm) - 1 : 0;
+        const int row = __shfl(myrow, k);
+        w |= (exists ? (unsigned)row & 0xFFu : 0xFFu) << (8 * b);
     }
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-        const int seg = 4 * q + r4;
-        unsigned mm = smask;                 // first row of segment `seg`: its start bit (segment 0: row 0)
-        int s0 = 0;
-        bool exists = true;
-        for (int t = 0; t < seg; ++t) {
-            if (mm == 0) { exists = false; break; }
-            s0 = __ffs(mm) - 1;
-            mm &= mm - 1;
-        }
-        const int node = __shfl(rcv, (lane & 48) + s0);           // owner-local receiver of row s0
-        const int second = (wg.partner >= 0 && 16 * T.t + s0 >= na) ? n : 0;
-        const unsigned row = (exists && ((vmask >> s0) & 1u)) ? (unsigned)(node + T.t + second) : 0xFFu;
-        dp |= row << (8 * r4);
-    }
-    tsel[(size_t)blockIdx.x * 64 + lane] = sb;
-    tdst[(size_t)blockIdx.x * 64 + lane] = dp;
+    if (j == 0) w = emask;
+    if (j == 1) w = (unsigned)__popc(emask);
+    if (j >= 6) w = 0;
+    if (lane < FUSED_TREC) trec[(size_t)blockIdx.x * FUSED_TREC + lane] = w;
 }
 
 // The same structure for the whole receiver-sorted edge list (tile t = sorted positions 16t..16t+15),
@@ -371,8 +379,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         const float* __restrict__ charges, const float* __restrict__ edge_attr_orig,
         const int32_t* __restrict__ perm, const int32_t* __restrict__ send_s,
         const int32_t* __restrict__ recv_s, const int32_t* __restrict__ rowptr,
-        const FusedWG* __restrict__ wgdesc, const uint32_t* __restrict__ tsel,
-        const uint32_t* __restrict__ tdst, const int4* __restrict__ ledge,
+        const FusedWG* __restrict__ wgdesc, const uint32_t* __restrict__ trec, const int4* __restrict__ ledge,
         const int32_t* __restrict__ nrange, FusedDebug dbg, float* __restrict__ out) {
     constexpr bool keep = KEEP;      // inference build carries none of the save-for-backward stores
     using NI = NodeInfo<D>;
@@ -451,16 +458,28 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     int4 f_e = make_int4(0, 0, 0, 0);                        // {sorted position, sender, receiver, original edge}
     f32x2 f_ea = {0.0f, 0.0f};                               // its two edge attributes (q_i q_j: the first only)
     int4 t_e[ROUNDS];                                        // per (round, lane i): the tile's edge i
-    unsigned t_sel[ROUNDS], t_dst[ROUNDS];
+    // The segment records of the wave's tiles (k_graph_tiles) are the same for all lanes: tile index from the wave index in
+    // a scalar register (as dma_images), so they arrive by scalar loads and stay in scalar registers.  Requested here, in
+    // code every wave runs: behind a branch on the wave index the compiler would treat them as per-lane values.
+    unsigned seg_ends[ROUNDS];                               // bit k: row k is the last row of its segment
+    unsigned seg_rows[ROUNDS][4];                            // partial rows of the segments, one byte each, in segment order
+    {
+        const int wv = __builtin_amdgcn_readfirstlane(wave);
+#pragma unroll
+        for (int r = 0; r < ROUNDS; ++r) {
+            const int stile = NW * r + wv;
+            const uint32_t* rec = trec + (size_t)(wg.tile0 + (stile < n_tiles ? stile : 0)) * FUSED_TREC;   // (a wave without that tile reads record tile0: inside the table also for a workgroup without tiles -- GraphLayout::max_tiles counts two more per node than are ever built)
+            seg_ends[r] = stile < n_tiles ? __builtin_amdgcn_readfirstlane(rec[0]) : 0u;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) seg_rows[r][w] = __builtin_amdgcn_readfirstlane(rec[2 + w]);
+        }
+    }
     auto index_stage_a = [&]() {
         if (f_have) f_e = ledge[eb + f_local];
 #pragma unroll
         for (int r = 0; r < ROUNDS; ++r) {
             const int tile = NW * r + wave, local = 16 * tile + i;
             t_e[r] = m > 0 ? ledge[eb + (local < m ? local : 0)] : make_int4(0, vb, nb, 0);
-            const bool have = tile < n_tiles;
-            t_sel[r] = have ? tsel[(size_t)(wg.tile0 + tile) * 64 + lane] : 0u;
-            t_dst[r] = have ? tdst[(size_t)(wg.tile0 + tile) * 64 + lane] : 0xFFFFFFFFu;
         }
     };
     // (returns its result: written through the capture, the two floats were kept in scratch memory -- 8 bytes per thread
@@ -613,8 +632,6 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     // the wave's scratch rows; then every lane reads its B fragments back.  Per-tile constants of
     // the graph structure (sender / receiver slot, receiver-segment index) are computed once here.
     int sl[ROUNDS], rl[ROUNDS];              // sender slot (visible numbering), receiver slot (own numbering)
-    unsigned selbits[ROUNDS];                // bit s4: S[seg = i][edge = 4*s4 + q] of the tile
-    unsigned destpack[ROUNDS];               // byte r4: partial row of segment 4q + r4, 0xFF = none
     f32x4 e[ROUNDS][4];                      // message tiles, MFMA accumulator layout
     int ke[KEEP ? ROUNDS : 1];               // KEEP: receiver-sorted position of the lane's edge (row of the saved tensors)
     {
@@ -689,8 +706,6 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                     st4(dbg.feat + (int64_t)ke[r] * FPAD + 16 + 4 * q, e[r][1]);
                 }
             }
-            selbits[r] = t_sel[r];
-            destpack[r] = t_dst[r];
         }
         lds_barrier();       // feature scratch (aliases SCRATCH) is dead from here on
     }
@@ -851,30 +866,50 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                         st4(dbg.e[layer - 1] + (int64_t)ke[r] * H + 16 * mb + 4 * q, e[r][mb]);
                 }
             }
-            // Per-receiver sums of the tile on the matrix core: park the tile in 16 LDS rows (one set
-            // per round, private to the wave), read it back transposed and multiply by the 0/1 segment
-            // matrix, out[seg][h] = sum_edge S[seg][edge] * E[edge][h]  (k runs in edge order).
+            // Per-receiver sums of the tile: park the tile in 16 LDS rows (one set per wave, private to it) and read it
+            // back by columns -- lane L owns column L and adds its 16 values in row order, every segment from +0.0f, the
+            // order and the roundings of the fmaf chain that a product with the 0/1 segment matrix would run.  After the
+            // last row of a segment the sum goes to the segment's partial row.  Which rows end a segment and where the
+            // sums go is the same for all lanes (seg_ends / seg_rows in scalar registers): the test and the
+            // branch run on the scalar unit, and a restart is a move -- a non-finite message never reaches another
+            // receiver's sum.
             float* wst = smem + L::WSTAGE + wave * (16 * LDST);
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) st4(wst + i * LDST + 16 * mb + 4 * q, e[r][mb]);
+            FUSED_WSTAMP(layer, r, 4);
             __builtin_amdgcn_wave_barrier();
-            f32x4 red[4];
+            {
+                float cv[16];
 #pragma unroll
-            for (int nbk = 0; nbk < 4; ++nbk) red[nbk] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int k = 0; k < 16; ++k) cv[k] = wst[k * LDST + lane];
+                float* pcol = part + lane;
+                unsigned ends = seg_ends[r];
+                // (opaque here: the sixteen bit tests stay one scalar compare each in front of their branch -- hoisted out
+                // of the layer loop they become sixteen 64-bit lane masks per round, parked in vector-register lanes)
+                asm volatile("" : "+s"(ends));
+                unsigned long long lo = (unsigned long long)seg_rows[r][0] | ((unsigned long long)seg_rows[r][1] << 32);
+                unsigned long long hi = (unsigned long long)seg_rows[r][2] | ((unsigned long long)seg_rows[r][3] << 32);
+                float sum = 0.0f;
 #pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                const float sel = (selbits[r] >> s4) & 1u ? 1.0f : 0.0f;
-                const float* erow = wst + (4 * s4 + q) * LDST + i;
-#pragma unroll
-                for (int nbk = 0; nbk < 4; ++nbk) red[nbk] = mfma16(sel, erow[16 * nbk], red[nbk]);
-            }
-            // lane (h = 16 nbk + i, q) register r4 holds segment 4q + r4
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const unsigned row = (destpack[r] >> (8 * r4)) & 0xFFu;
-                if (row != 0xFFu) {
-                    float* dst = part + row * LDW + i;
-                    dst[0] = red[0][r4]; dst[16] = red[1][r4]; dst[32] = red[2][r4]; dst[48] = red[3][r4];
+                for (int k = 0; k < 16; ++k) {
+                    sum += cv[k];
+#if AETHER_SUMS_SELECT
+                    // branch-free form: every row stores, rows that end nothing into the spare row behind PART
+                    const bool end = (ends >> k) & 1u;
+                    const unsigned row = end ? (unsigned)lo & 0xFFu : (unsigned)L::PART_ROWS;
+                    pcol[row * LDW] = sum;
+                    sum = end ? 0.0f : sum;
+                    const unsigned long long nlo = (lo >> 8) | (hi << 56), nhi = hi >> 8;
+                    lo = end ? nlo : lo;
+                    hi = end ? nhi : hi;
+#else
+                    if ((ends >> k) & 1u) {
+                        pcol[((unsigned)lo & 0xFFu) * LDW] = sum;
+                        sum = 0.0f;
+                        lo = (lo >> 8) | (hi << 56);
+                        hi >>= 8;
+                    }
+#endif
                 }
             }
             __builtin_amdgcn_wave_barrier();

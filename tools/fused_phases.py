@@ -54,11 +54,16 @@ for k in order:
 clk = np.median(st[:, 41] / st[:, 40])
 print(f"  shader clock during the kernel: {clk:.0f} MHz (s_memtime cycles / wall us)")
 print("  layer-2 per-wave tile timeline, cycles since kernel entry (median over workgroups):")
-print("   wave round   start   gemm1   silu1   gemm2  silu2+stage  reduce   | total")
+print("   wave round   start  wait rows  gemm1+silu1  gemm2+silu2+stage  sums   | total")
+sums = []
 for w in range(8):
     for r in range(3):
         v = med[64 + w * 24 + r * 8: 64 + w * 24 + r * 8 + 6]
         if v[5] == 0: continue
-        d = np.diff(v)
-        print(f"   {w:4d} {r:5d} {v[0]:8.0f} " + " ".join(f"{x:7.0f}" for x in d) + f"    | {v[5]-v[0]:6.0f}")
+        d = [v[1] - v[0], v[2] - v[1], v[4] - v[2], v[5] - v[4]]      # stamps 0, 1, 2, 4 (tile parked, sums begin), 5
+        sums.append(d[3])
+        print(f"   {w:4d} {r:5d} {v[0]:8.0f} {d[0]:9.0f} {d[1]:12.0f} {d[2]:18.0f} {d[3]:6.0f}    | {v[5]-v[0]:6.0f}")
+if sums:
+    print(f"  receiver sums per tile (wait for the parked tile, column reads, adds, stores): median {np.median(sums):.0f}, "
+          f"min {min(sums):.0f}, max {max(sums):.0f} cycles over {len(sums)} tiles")
 print(f"  kernel span (max over WGs of last stamp): {st[:, 40].max():.2f} us; min start->end {st[:,40].min():.2f}")
