@@ -1,35 +1,11 @@
-// Host side of the C ABI: one prediction step of the variable-N model as ONE call (SURVEY 8f N2; dyn_step.h has the
-// kernels).  Included by aether_hip.hip inside its extern "C" block, after host_dynamicvars.inc.
+// Host side of the C ABI: one prediction step of the variable-N model, and the whole prediction loop, as ONE call for
+// 1 .. 256 scenes (SURVEY 8f N2; dyn_step.h has the kernels).  Included by aether_hip.hip inside its extern "C" block,
+// after host_dynamicvars.inc.  aether_dyn_step / aether_dyn_rollout (one scene) are the n_scenes = 1 case of the batched
+// entry points and forward to them (end of this file).
 
 namespace {
-struct DynStepLayout {
-    size_t idx, cidx, cur_in, cur_h, rowptr_dec, status, field_c, ext_full, ksend, krecv, kmeta, korder, krowptr, slot, h0, c0,
-        h1, c1, logits, ew, out_c, new_h, ws_field, ws_knn, ws_prior, ws_dec, total;
-    size_t b_field, b_knn, b_prior, b_dec;
-    int knn_k;
-    DynStepLayout(const AetherDynStepConfig& c, int n_max, int64_t n, int64_t E) {
-        size_t off = 0;
-        auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-        const size_t nn = (size_t)n, ee = (size_t)E, R = (size_t)c.rnn_hidden, K = (size_t)c.num_edge_types;
-        knn_k = std::min(c.knn_k, n_max - 1);
-        idx = take(nn * 8); cidx = take((size_t)n_max * 4); cur_in = take(nn * 16); cur_h = take(nn * c.decoder_hidden * 4);
-        rowptr_dec = take((nn + 1) * 8); status = take(256); field_c = take(nn * 8); ext_full = take((size_t)n_max * 24);
-        // (capacity of the kNN lists: whatever the mask holds, at most n_max objects x k neighbours are written)
-        const size_t kcap = std::max(ee, (size_t)n_max * (size_t)(knn_k > 0 ? knn_k : 1));
-        ksend = take(kcap * 8); krecv = take(kcap * 8); kmeta = take(64); korder = take(ee * 8); krowptr = take((nn + 1) * 8);
-        slot = take(ee * 8);
-        h0 = take(ee * R * 4); c0 = take(ee * R * 4); h1 = take(ee * R * 4); c1 = take(ee * R * 4);
-        logits = take(ee * K * 4); ew = take(ee * K * 4); out_c = take(nn * 16); new_h = take(nn * c.decoder_hidden * 4);
-        b_field = aether_dyn_field_workspace_bytes(n, c.field_hidden);
-        b_knn = aether_knn_workspace_bytes(1, n_max, knn_k > 0 ? knn_k : 1);
-        b_prior = aether_dyn_prior_workspace_bytes(c.encoder_hidden, c.rnn_hidden, c.prior_hidden, n, E);
-        b_dec = aether_dyn_decoder_workspace_bytes(c.decoder_hidden, n, E);
-        ws_field = take(b_field); ws_knn = take(b_knn); ws_prior = take(b_prior); ws_dec = take(b_dec);
-        total = off;
-    }
-};
-
-int dyn_step_check(const AetherDynStepConfig* c, int n_max, int64_t n, int64_t E, const char* who) {
+// One scene of a step: the configuration, and 2 <= n <= n_max present objects with the edge count of the encoder's kNN graph.
+int dyn_step_check(const AetherDynStepConfig* c, int n_max, int64_t n, int64_t E) {
     if (!c) return fail(AETHER_EINVAL, "dyn_step: null config");
     if (n_max < 2 || n_max > DYN_MAX_OBJECTS) return fail(AETHER_EINVAL, "dyn_step: 2..8192 object rows");
     if (n < 2 || n > n_max) return fail(AETHER_EINVAL, "dyn_step: a step needs 2..n_objects_max present objects");
@@ -42,166 +18,12 @@ int dyn_step_check(const AetherDynStepConfig* c, int n_max, int64_t n, int64_t E
     // the encoder's own kNN graph has n * min(k, n - 1) edges; the caller's graph must list as many (the module raises
     // "graph_info and the encoder's kNN graph list a different number of edges" for the same reason)
     const int64_t k = std::min<int64_t>(std::min(c->knn_k, n_max - 1), n - 1);
-    if (E != n * k) return fail(AETHER_EINVAL, "dyn_step: n_edges must be n_present * min(knn_k, n_present - 1)");
-    (void)who;
-    return AETHER_OK;
-}
-}  // namespace
-
-size_t aether_dyn_step_workspace_bytes(const AetherDynStepConfig* config, int n_objects_max, int64_t n_present,
-                                       int64_t n_edges) {
-    if (dyn_step_check(config, n_objects_max, n_present, n_edges, "workspace_bytes")) return 0;
-    return DynStepLayout(*config, n_objects_max, n_present, n_edges).total + 256;
-}
-
-int aether_dyn_step(const AetherDynFieldQueryParams* field_params, const AetherDynPriorParams* prior_params,
-                    const AetherDynDecoderParams* decoder_params, const AetherDynStepConfig* config, int n_objects_max,
-                    int64_t n_present, int64_t n_edges, const float* state, const float* mask, const int64_t* node_inds,
-                    const int64_t* graph_send, const int64_t* graph_recv, const int64_t* edge2node, int in_degree,
-                    float* prior_h, float* prior_c, float* decoder_hidden, const float* uniform, float* prediction,
-                    float* edge_types, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!field_params || !prior_params || !decoder_params || !state || !mask || !graph_send || !graph_recv || !edge2node ||
-        !prior_h || !prior_c || !decoder_hidden || !uniform || !prediction || !workspace)
-        return fail(AETHER_EINVAL, "dyn_step: null pointer");
-    if (int rc = dyn_step_check(config, n_objects_max, n_present, n_edges, "step")) return rc;
-    if (in_degree < 1 || (int64_t)in_degree * n_present > n_edges)
-        return fail(AETHER_EINVAL, "dyn_step: edge2node is [n_present][in_degree] edge ids");
-    const AetherDynStepConfig& c = *config;
-    const int n_max = n_objects_max, n = (int)n_present, R = c.rnn_hidden, K = c.num_edge_types, hd = c.decoder_hidden;
-    const int64_t E = n_edges;
-    DynStepLayout L(c, n_max, n_present, n_edges);
-    char* ws = reinterpret_cast<char*>(align_up((size_t)workspace, 256));
-    if (workspace_bytes < L.total + 256) return fail(AETHER_ESPACE, "dyn_step: workspace too small");
-    if (take_async_error()) return AETHER_EHIP;
-    hipStream_t st = (hipStream_t)stream;
-    auto fp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto ip = [&](size_t off) { return reinterpret_cast<int64_t*>(ws + off); };
-    auto blocks = [](int64_t cnt) { return dim3((unsigned)((cnt + 255) / 256)); };
-    int* cidx = reinterpret_cast<int*>(ws + L.cidx);
-    int* status = reinterpret_cast<int*>(ws + L.status);
-    // ---- the present objects (mask -> rows), their state and decoder hidden rows
-    {
-        const size_t lds = ((size_t)n_max + n + 257) * 4;
-        if (ensure_dynamic_lds(reinterpret_cast<const void*>(k_dyn_present), lds)) return AETHER_EHIP;
-        const DynDecLayout DL(hd, n, E);
-        k_dyn_present<<<dim3(1), dim3(256), lds, st>>>(state, mask, decoder_hidden, n_max, n, hd, in_degree, ip(L.idx), cidx,
-                                                      fp(L.cur_in), fp(L.cur_h), ip(L.rowptr_dec), status, async_error_word(),
-                                                      ip(L.kmeta), reinterpret_cast<int*>(ws + L.ws_dec + DL.counts));
-    }
-    const int64_t* ninds = node_inds ? node_inds : ip(L.idx);
-    // ---- field at the present objects (:64-79)
-    if (int rc = aether_dyn_field(field_params, c.field_hidden, n, fp(L.cur_in), ws + L.ws_field, L.b_field, fp(L.field_c), stream))
-        return rc;
-    // ---- the encoder's own kNN graph of the present objects (:528, :559-586), grouped by receiver
-    int64_t* kmeta = ip(L.kmeta);
-    if (int rc = knn_edges_impl(state, 4, mask, 1, n_max, L.knn_k, ip(L.ksend), ip(L.krecv), kmeta, kmeta + 1, kmeta + 2,
-                                ws + L.ws_knn, L.b_knn, stream, true)) return rc;
-    {
-        const size_t lds = ((size_t)n + 257 + 256) * 4;
-        if (ensure_dynamic_lds(reinterpret_cast<const void*>(k_dyn_csr), lds)) return AETHER_EHIP;
-        k_dyn_csr<<<dim3(1), dim3(256), lds, st>>>(ip(L.ksend), ip(L.krecv), E, n, status, ip(L.korder), ip(L.krowptr));
-    }
-    // ---- LSTM state rows of the caller's edges, prior step, state back into its slots (:680-694)
-    // (+ the un-compacted [state | field] rows the decoder's edge features read, :823)
-    const int64_t gwork = std::max<int64_t>(E * (R / 4), (int64_t)n_max * 6);
-    k_dyn_slots_gather<<<blocks(gwork), dim3(256), 0, st>>>(graph_send, graph_recv, ninds, n, n_max, E, R, prior_h, prior_c,
-                                                           ip(L.slot), fp(L.h0), fp(L.c0), state, fp(L.field_c), cidx,
-                                                           fp(L.ext_full));
-    if (int rc = aether_dyn_prior_step(prior_params, c.encoder_hidden, R, c.prior_layers, c.prior_hidden, K, c.encoder_polar, n, E,
-                                       fp(L.cur_in), fp(L.field_c), fp(L.h0), fp(L.c0), ip(L.ksend), ip(L.krecv), ip(L.korder),
-                                       ip(L.krowptr), ws + L.ws_prior, L.b_prior, fp(L.logits), fp(L.h1), fp(L.c1), stream))
-        return rc;
-    // ... and the hard Gumbel sample of the edge types (:137-141), same launch
-    float* ew = edge_types ? edge_types : fp(L.ew);
-    k_dyn_scatter_sample<<<blocks(E * (R / 4)), dim3(256), 0, st>>>(ip(L.slot), fp(L.h1), fp(L.c1), E, R, prior_h, prior_c,
-                                                                   fp(L.logits), uniform, c.gumbel_tau, K, ew, status, n);
-    // ---- decoder step on the caller's graph (:775-870), rows back to their objects
-    // (the prior step has just computed the canonical states / frames of these rows: the decoder takes them from its workspace)
-    const DynPriorLayout PL(c.encoder_hidden, R, c.prior_hidden, n, E);
-    const DynSharedNodes shared{reinterpret_cast<const float*>(ws + L.ws_prior + PL.ext),
-                                reinterpret_cast<const float*>(ws + L.ws_prior + PL.rel),
-                                reinterpret_cast<const float*>(ws + L.ws_prior + PL.Rinv), true};
-    if (int rc = dyn_decoder_impl(decoder_params, hd, K, c.skip_first, c.decoder_polar, n, E, fp(L.cur_in), fp(L.cur_h), ew,
-                                  fp(L.field_c), fp(L.ext_full), nullptr, nullptr, graph_send, graph_recv, edge2node,
-                                  ip(L.rowptr_dec), (float)(n - 1), nullptr, ws + L.ws_dec, L.b_dec, fp(L.out_c), fp(L.new_h), stream,
-                                  &shared)) return rc;
-    const int64_t work = std::max<int64_t>((int64_t)n_max * 4, (int64_t)n * (hd / 4));
-    k_dyn_finish<<<blocks(work), dim3(256), 0, st>>>(fp(L.out_c), fp(L.new_h), cidx, ip(L.idx), status, n_max, n, hd, prediction,
-                                                    decoder_hidden);
-    HIP_OK(hipGetLastError());
+    if (E != n * k)
+        return fail(AETHER_EINVAL, "dyn_step: n_edges must be n_present * min(knn_k, n_present - 1), the size of the encoder's "
+                                   "own kNN graph");
     return AETHER_OK;
 }
 
-// ------------------------------------------------------------------ the prediction loop (predict_future, :245-273)
-size_t aether_dyn_rollout_workspace_bytes(const AetherDynStepConfig* config, int n_objects_max, int n_steps,
-                                          const int64_t* n_present, const int64_t* n_edges) {
-    if (!config || !n_present || !n_edges || n_steps <= 0 || n_objects_max < 2) return 0;
-    size_t need = 0;
-    for (int t = 0; t < n_steps; ++t) {
-        if (n_present[t] < 2) continue;
-        const size_t b = aether_dyn_step_workspace_bytes(config, n_objects_max, n_present[t], n_edges[t]);
-        if (b == 0) return 0;       // (a graph with another edge count than the encoder's kNN graph: dyn_step_check)
-        need = std::max(need, b);
-    }
-    return need + align_up((size_t)n_objects_max * 16, 256) + 256;
-}
-
-int aether_dyn_rollout(const AetherDynFieldQueryParams* field_params, const AetherDynPriorParams* prior_params,
-                       const AetherDynDecoderParams* decoder_params, const AetherDynStepConfig* config, int n_objects_max,
-                       int n_steps, const float* inputs, const float* masks, const float* burn_in_masks,
-                       const int64_t* n_present, const int64_t* n_edges, const int64_t* const* node_inds,
-                       const int64_t* const* graph_send, const int64_t* const* graph_recv, const int64_t* const* edge2node,
-                       const int* in_degree, const float* const* uniform, float* prior_h, float* prior_c,
-                       float* decoder_hidden, float* predictions, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!config || !inputs || !masks || !burn_in_masks || !n_present || !n_edges || !graph_send || !graph_recv || !edge2node ||
-        !in_degree || !uniform || !predictions || !workspace || !field_params || !prior_params || !decoder_params || !prior_h ||
-        !prior_c || !decoder_hidden)
-        return fail(AETHER_EINVAL, "dyn_rollout: null pointer");
-    if (n_steps <= 0) return fail(AETHER_EINVAL, "dyn_rollout: n_steps must be positive");
-    // every step is validated on the host BEFORE anything is queued: a refused step t would otherwise leave steps 0 .. t-1
-    // queued with the caller's prior / decoder state already updated in place
-    for (int t = 0; t < n_steps; ++t) {
-        if (n_present[t] == 0) continue;
-        if (n_present[t] == 1)
-            return fail(AETHER_EINVAL, "dyn_rollout: a step with one present object (the reference fails there as well, "
-                                       "aether_dynamicvars.py:843-851)");
-        if (int rc = dyn_step_check(config, n_objects_max, n_present[t], n_edges[t], "rollout")) return rc;
-        if (!graph_send[t] || !graph_recv[t] || !edge2node[t] || !uniform[t])
-            return fail(AETHER_EINVAL, "dyn_rollout: a step's graph / uniform pointer is null");
-        if (in_degree[t] < 1 || (int64_t)in_degree[t] * n_present[t] > n_edges[t])
-            return fail(AETHER_EINVAL, "dyn_rollout: edge2node is [n_present][in_degree] edge ids");
-    }
-    const size_t need = aether_dyn_rollout_workspace_bytes(config, n_objects_max, n_steps, n_present, n_edges);
-    if (need == 0) return fail(AETHER_EINVAL, "dyn_rollout: bad sizes");
-    if (workspace_bytes < need) return fail(AETHER_ESPACE, "dyn_rollout: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(align_up((size_t)workspace, 256));
-    float* state = reinterpret_cast<float*>(ws);
-    char* step_ws = ws + align_up((size_t)n_objects_max * 16, 256);
-    const size_t step_bytes = workspace_bytes - (size_t)(step_ws - (char*)workspace);
-    const size_t row = (size_t)n_objects_max * 4;
-    for (int t = 0; t < n_steps; ++t) {
-        const float* last = t == 0 ? inputs : predictions + (size_t)(t - 1) * row;
-        float* pred = predictions + (size_t)t * row;
-        if (n_present[t] == 0) {                 // nobody there: zeros, states untouched (:841-843)
-            HIP_OK(hipMemsetAsync(pred, 0, row * 4, st));
-            continue;
-        }
-        k_dyn_mix<<<dim3((unsigned)((row + 255) / 256)), dim3(256), 0, st>>>(inputs + (size_t)t * row, last,
-                                                                            burn_in_masks + (size_t)t * n_objects_max,
-                                                                            n_objects_max, state);
-        const int64_t n = n_present[t];
-        const int64_t E = n_edges[t];
-        if (int rc = aether_dyn_step(field_params, prior_params, decoder_params, config, n_objects_max, n, E, state,
-                                     masks + (size_t)t * n_objects_max, node_inds ? node_inds[t] : nullptr, graph_send[t],
-                                     graph_recv[t], edge2node[t], in_degree[t], prior_h, prior_c, decoder_hidden, uniform[t], pred,
-                                     nullptr, step_ws, step_bytes, stream)) return rc;
-    }
-    return AETHER_OK;
-}
-
-// ------------------------------------------------------------------ B scenes per call (BASELINE config 4: batch = 64)
-namespace {
 struct DynBatchSizes { int64_t n_total, e_total, o_total; };
 struct DynBatchLayout {
     size_t idx, cidx, cur_in, cur_h, rowptr_dec, div_node, status, field_c, ext_full, ksend, krecv, ksums, ktot, korder, krowptr,
@@ -215,7 +37,7 @@ struct DynBatchLayout {
                      K = (size_t)c.num_edge_types, rows = (size_t)B * n_max;
         knn_k = std::min(c.knn_k, n_max - 1);
         idx = take(nn * 8); cidx = take(rows * 4); cur_in = take(nn * 16); cur_h = take(nn * c.decoder_hidden * 4);
-        rowptr_dec = take((nn + 1) * 8); div_node = take(nn * 4); status = take(256); field_c = take(nn * 8);
+        rowptr_dec = take((nn + 1) * 8); div_node = take(nn * 4); status = take((size_t)(1 + DYN_MAX_SCENES) * 4); field_c = take(nn * 8);
         ext_full = take(rows * 24);
         const size_t kcap = std::max(ee, rows * (size_t)(knn_k > 0 ? knn_k : 1));      // whatever the masks hold
         ksend = take(kcap * 8); krecv = take(kcap * 8); ksums = take((size_t)2 * B * 8); ktot = take(64);
@@ -233,7 +55,7 @@ struct DynBatchLayout {
     }
 };
 
-// Every scene is empty (n = 0) or a step aether_dyn_step would accept; fills the by-value scene table and the totals.
+// Every scene is empty (n = 0) or passes dyn_step_check; fills the by-value scene table and the totals.
 int dyn_batch_check(const AetherDynStepConfig* c, int B, int n_max, const int64_t* n_present, const int64_t* n_edges,
                     const int* in_degree, DynScenes* S, DynBatchSizes* Z) {
     if (!c || !n_present || !n_edges || !in_degree) return fail(AETHER_EINVAL, "dyn_step_batched: null size array");
@@ -252,7 +74,7 @@ int dyn_batch_check(const AetherDynStepConfig* c, int B, int n_max, const int64_
         if (n == 1)
             return fail(AETHER_EINVAL, "dyn_step_batched: a scene with one present object (the reference fails there as well, "
                                        "aether_dynamicvars.py:843-851)");
-        if (int rc = dyn_step_check(c, n_max, n, n_edges[b], "batched")) return rc;
+        if (int rc = dyn_step_check(c, n_max, n, n_edges[b])) return rc;
         checked = true;
         if (in_degree[b] < 1 || in_degree[b] > 255 || (int64_t)in_degree[b] * n > n_edges[b])
             return fail(AETHER_EINVAL, "dyn_step_batched: edge2node of a scene is [n_present][in_degree] edge ids, in_degree <= 255");
@@ -307,7 +129,6 @@ int aether_dyn_step_batched(const AetherDynFieldQueryParams* field_params, const
     auto blocks = [](int64_t cnt) { return dim3((unsigned)((cnt + 255) / 256)); };
     int* cidx = reinterpret_cast<int*>(ws + L.cidx);
     int* status = reinterpret_cast<int*>(ws + L.status);
-    HIP_OK(hipMemsetAsync(status, 0, 8, st));
     // ---- the present objects of every scene (mask -> rows), their state and decoder hidden rows
     {
         const size_t lds = ((size_t)3 * (DYN_MAX_SCENES + 1) + 257 + 2 * (size_t)n_max) * 4;
@@ -343,10 +164,10 @@ int aether_dyn_step_batched(const AetherDynFieldQueryParams* field_params, const
                                        ip(L.krowptr), ws + L.ws_prior, L.b_prior, fp(L.logits), fp(L.h1), fp(L.c1), stream))
         return rc;
     // ... state back into its slots and the hard Gumbel sample of the edge types (:137-141), one launch; a scene whose mask
-    // disagreed with its n poisons the rows (status[1] != 0)
+    // disagreed with its n poisons the rows (status[0] != 0)
     float* ew = edge_types ? edge_types : fp(L.ew);
     k_dyn_scatter_sample<<<blocks(E * (R / 4)), dim3(256), 0, st>>>(ip(L.slot), fp(L.h1), fp(L.c1), E, R, prior_h, prior_c,
-                                                                   fp(L.logits), uniform, c.gumbel_tau, K, ew, status + 1, 0);
+                                                                   fp(L.logits), uniform, c.gumbel_tau, K, ew, status, 0);
     // ---- decoder step on the callers' graphs (:775-870), rows back to their objects
     const DynPriorLayout PL(c.encoder_hidden, R, c.prior_hidden, n, E);
     const DynSharedNodes shared{reinterpret_cast<const float*>(ws + L.ws_prior + PL.ext),
@@ -363,7 +184,8 @@ int aether_dyn_step_batched(const AetherDynFieldQueryParams* field_params, const
     return AETHER_OK;
 }
 
-// The prediction loop for B scenes: aether_dyn_rollout with every per-step array TIME-MAJOR -- inputs [n_steps + 1][B][n_max][4],
+// ------------------------------------------------------------------ the prediction loop (predict_future, :245-273)
+// Per step the burn-in mix and aether_dyn_step_batched, queued without a host round trip.  Every per-step array is TIME-MAJOR -- inputs [n_steps + 1][B][n_max][4],
 // masks / burn_in_masks [n_steps][B][n_max], predictions [n_steps][B][n_max][4] -- and the host size arrays [n_steps][B].
 size_t aether_dyn_rollout_batched_workspace_bytes(const AetherDynStepConfig* config, int n_scenes, int n_objects_max, int n_steps,
                                                   const int64_t* n_present, const int64_t* n_edges, const int* in_degree) {
@@ -422,4 +244,57 @@ int aether_dyn_rollout_batched(const AetherDynFieldQueryParams* field_params, co
                                              nullptr, step_ws, step_bytes, stream)) return rc;
     }
     return AETHER_OK;
+}
+
+// ------------------------------------------------------------------ one scene: n_scenes = 1 of the above
+// The single-scene size functions take no in_degree: they size for the largest one a step accepts (n_edges / n_present).
+size_t aether_dyn_step_workspace_bytes(const AetherDynStepConfig* config, int n_objects_max, int64_t n_present,
+                                       int64_t n_edges) {
+    if (n_present < 2) {                         // (the batched entry takes an empty scene; a single step does not)
+        fail(AETHER_EINVAL, "dyn_step: a step needs 2..n_objects_max present objects");
+        return 0;
+    }
+    const int deg = (int)(n_edges / n_present);
+    return aether_dyn_step_batched_workspace_bytes(config, 1, n_objects_max, &n_present, &n_edges, &deg);
+}
+
+int aether_dyn_step(const AetherDynFieldQueryParams* field_params, const AetherDynPriorParams* prior_params,
+                    const AetherDynDecoderParams* decoder_params, const AetherDynStepConfig* config, int n_objects_max,
+                    int64_t n_present, int64_t n_edges, const float* state, const float* mask, const int64_t* node_inds,
+                    const int64_t* graph_send, const int64_t* graph_recv, const int64_t* edge2node, int in_degree,
+                    float* prior_h, float* prior_c, float* decoder_hidden, const float* uniform, float* prediction,
+                    float* edge_types, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!field_params || !prior_params || !decoder_params || !state || !mask || !graph_send || !graph_recv || !edge2node ||
+        !prior_h || !prior_c || !decoder_hidden || !uniform || !prediction || !workspace)
+        return fail(AETHER_EINVAL, "dyn_step: null pointer");
+    if (n_present < 2) return fail(AETHER_EINVAL, "dyn_step: a step needs 2..n_objects_max present objects");
+    return aether_dyn_step_batched(field_params, prior_params, decoder_params, config, 1, n_objects_max, &n_present, &n_edges,
+                                   &in_degree, state, mask, node_inds, graph_send, graph_recv, edge2node, prior_h, prior_c,
+                                   decoder_hidden, uniform, prediction, edge_types, workspace, workspace_bytes, stream);
+}
+
+size_t aether_dyn_rollout_workspace_bytes(const AetherDynStepConfig* config, int n_objects_max, int n_steps,
+                                          const int64_t* n_present, const int64_t* n_edges) {
+    if (!n_present || !n_edges || n_steps <= 0) return 0;
+    std::vector<int> deg((size_t)n_steps, 0);
+    for (int t = 0; t < n_steps; ++t)
+        if (n_present[t] > 0) deg[t] = (int)(n_edges[t] / n_present[t]);
+    return aether_dyn_rollout_batched_workspace_bytes(config, 1, n_objects_max, n_steps, n_present, n_edges, deg.data());
+}
+
+// The [n_steps] arrays of one scene are the [n_steps][1] arrays of the batched loop: the same memory.
+int aether_dyn_rollout(const AetherDynFieldQueryParams* field_params, const AetherDynPriorParams* prior_params,
+                       const AetherDynDecoderParams* decoder_params, const AetherDynStepConfig* config, int n_objects_max,
+                       int n_steps, const float* inputs, const float* masks, const float* burn_in_masks,
+                       const int64_t* n_present, const int64_t* n_edges, const int64_t* const* node_inds,
+                       const int64_t* const* graph_send, const int64_t* const* graph_recv, const int64_t* const* edge2node,
+                       const int* in_degree, const float* const* uniform, float* prior_h, float* prior_c,
+                       float* decoder_hidden, float* predictions, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!config || !inputs || !masks || !burn_in_masks || !n_present || !n_edges || !graph_send || !graph_recv || !edge2node ||
+        !in_degree || !uniform || !predictions || !workspace || !field_params || !prior_params || !decoder_params || !prior_h ||
+        !prior_c || !decoder_hidden)
+        return fail(AETHER_EINVAL, "dyn_rollout: null pointer");
+    return aether_dyn_rollout_batched(field_params, prior_params, decoder_params, config, 1, n_objects_max, n_steps, inputs, masks,
+                                      burn_in_masks, n_present, n_edges, in_degree, node_inds, graph_send, graph_recv, edge2node,
+                                      uniform, prior_h, prior_c, decoder_hidden, predictions, workspace, workspace_bytes, stream);
 }

@@ -431,7 +431,7 @@ static int knn_edges_impl(const float* x, int x_stride, const float* masks, int6
     const size_t lds_sel = (size_t)3 * N * 4 + 257 * 4, lds_wr = (size_t)2 * N * 4 + 257 * 4;
     if (ensure_dynamic_lds((const void*)k_knn_select, lds_sel) || ensure_dynamic_lds((const void*)k_knn_write, lds_wr))
         return AETHER_EHIP;
-    if (sums_zeroed) {                                    // (aether_dyn_step: k_dyn_present has cleared them)
+    if (sums_zeroed) {                                    // (aether_dyn_step_batched: k_dynb_present has cleared them)
     } else if (scene_nodes == scene_edges + n_scenes) {  // back to back: one memset node
         HIP_OK(hipMemsetAsync(scene_edges, 0, (size_t)2 * n_scenes * sizeof(int64_t), st));
     } else {

@@ -286,7 +286,7 @@ class AetherDynamicVars(nn.Module):
         present objects and their graph per time step.  ``uniform``: per-step Gumbel draws (list of [E_t, K]).
         With B > 1 scenes (inputs [B, T, Nmax, 4], node_inds[b][t], graph_info[b][t], uniform[t][b]) every time step is
         ONE batched call per stage (predict_future_batched) -- the reference raises on batch > 1 (:588-591).
-        One scene, default: the whole loop is ONE library call (``aether_dyn_rollout``).  With ``one_call_step = False``
+        One scene, default: the whole loop is ONE library call (``_predict_future_rollout``).  With ``one_call_step = False``
         (the staged calls + torch glue of rounds 1-2) ``graph=True`` replays a captured hipGraph per step signature
         (``_captured_step``); bit-identical to the eager loop either way."""
         if inputs.size(0) > 1:
@@ -298,7 +298,8 @@ class AetherDynamicVars(nn.Module):
             # aether_dyn_step.  ``graph=True`` is accepted and means the same thing here.  (replays of a
             # captured step in flight behind each other faulted while the decoder's all-types filter kernel was a graph
             # node -- a runtime replay problem, bisected and avoided in the library.)
-            return self._predict_future_rollout(inputs, masks, node_inds, graph_info, burn_in_masks, uniform)
+            return self._predict_future_rollout(inputs, masks, node_inds, graph_info, burn_in_masks,
+                                                None if uniform is None else [[u] for u in uniform])
         prior_state = self.encoder.get_initial_hidden(inputs)
         dec_state = self.decoder.get_initial_hidden(inputs)
         last = inputs[:, 0]
@@ -331,83 +332,13 @@ class AetherDynamicVars(nn.Module):
         return torch.stack(preds, dim=1)
 
     @torch.no_grad()
-    def _predict_future_rollout(self, inputs, masks, node_inds, graph_info, burn_in_masks, uniform=None):
-        """The whole loop of ``predict_future`` for one scene as ONE library call (``aether_dyn_rollout``): per step the
-        burn-in mix and ``aether_dyn_step``, queued on the current stream without a host round trip in between."""
-        if not inputs.is_cuda:
-            raise _lib.AetherHipError("aether_amd AetherDynamicVars runs on an MI355X only; got a CPU tensor "
-                                      "(there is no CPU fallback)")
-        if self.encoder.training:
-            raise _lib.AetherHipError("the prior step uses BatchNorm running statistics: call .eval() first")
-        lib = _lib.load()
-        dev = inputs.device
-        T, Nmax = int(inputs.size(1)), int(inputs.size(2))
-        n_steps, K = T - 1, self.num_edge_types
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        i64 = lambda t: t.to(device=dev, dtype=torch.int64).contiguous()
-        x, m, burn = f32(inputs)[0], f32(masks)[0], f32(burn_in_masks)[0]
-        if m.shape[0] < n_steps or burn.shape[0] < n_steps:
-            raise ValueError("masks / burn_in_masks must cover every step")
-        keep = []                                                  # device tensors the pointer arrays refer to
-        n_host = (C.c_int64 * n_steps)()
-        e_host = (C.c_int64 * n_steps)()
-        e2n_max = []                                               # largest edge id of every step's edge2node (one sync below)
-        deg = (C.c_int * n_steps)()
-        ptrs = {k: (C.c_void_p * n_steps)() for k in ("ni", "gs", "gr", "e2n", "u")}
-        for t in range(n_steps):
-            ni_t = node_inds[0][t]
-            n_t = int(ni_t.numel())
-            n_host[t] = n_t
-            if n_t < 2:
-                continue
-            gs, gr, e2n = (i64(g) for g in graph_info[0][t])
-            E = int(gs.numel())
-            if gr.numel() != E or e2n.ndim != 2 or e2n.shape[0] != n_t:
-                raise ValueError(f"graph_info of step {t} does not match its present objects")
-            u = f32(uniform[t]).reshape(-1, K) if uniform is not None else torch.rand(E, K, device=dev)
-            if u.shape[0] != E:
-                raise ValueError(f"uniform of step {t} must be [E, K]")
-            ni = i64(ni_t)
-            keep += [gs, gr, e2n, u, ni]
-            e_host[t] = E
-            e2n_max.append((t, E, e2n.max() if e2n.numel() else None))
-            deg[t] = int(e2n.shape[1])
-            for k, v in (("ni", ni), ("gs", gs), ("gr", gr), ("e2n", e2n), ("u", u)):
-                ptrs[k][t] = v.data_ptr()
-        cfg = self._step_config()
-        # edge2node holds edge ids of the step's graph: an id >= E would index past the step's message rows
-        live = [(t, E, mx) for t, E, mx in e2n_max if mx is not None]
-        if live:
-            mxs = torch.stack([mx for _, _, mx in live]).cpu().tolist()
-            for (t, E, _), mx in zip(live, mxs):
-                if mx >= E:
-                    raise ValueError(f"graph_info of step {t}: edge2node names edge {mx}, the graph has {E} edges")
-        need = lib.aether_dyn_rollout_workspace_bytes(C.byref(cfg), Nmax, n_steps, n_host, e_host)
-        if need == 0:
-            raise _lib.AetherHipError("aether_dyn_rollout_workspace_bytes: bad sizes (2..8192 object rows, hidden sizes, or a "
-                                      "step whose graph does not list n * min(knn_k, n - 1) edges, the size of the encoder's "
-                                      "own kNN graph)")
-        ws = self.__dict__.get("_step_ws")
-        if ws is None or ws.numel() < need or ws.device != dev:
-            ws = self.__dict__["_step_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        prior_h, prior_c = (f32(s)[0].clone() for s in self.encoder.get_initial_hidden(inputs))
-        dec = f32(self.decoder.get_initial_hidden(inputs))[0].clone()
-        preds = torch.empty(n_steps, Nmax, 4, dtype=torch.float32, device=dev)
-        fs, ps_e, ps_d = self._field_struct(), self.encoder._param_struct()[0], self.decoder._param_struct()
-        st = lib.aether_dyn_rollout(C.byref(fs), C.byref(ps_e), C.byref(ps_d), C.byref(cfg), Nmax, n_steps, x.data_ptr(),
-                                    m.data_ptr(), burn.data_ptr(), n_host, e_host, ptrs["ni"], ptrs["gs"], ptrs["gr"], ptrs["e2n"], deg,
-                                    ptrs["u"], prior_h.data_ptr(), prior_c.data_ptr(), dec.data_ptr(), preds.data_ptr(),
-                                    ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(st, "aether_dyn_rollout")
-        del keep
-        return preds.unsqueeze(0)
-
-    @torch.no_grad()
-    def _predict_future_rollout_batched(self, inputs, masks, node_inds, graph_info, burn_in_masks, uniform=None):
-        """``predict_future`` of B scenes as ONE library call (``aether_dyn_rollout_batched``): per step the burn-in mix and
-        ``aether_dyn_step_batched`` over the present objects of all scenes, queued without a host round trip.  The
-        per-scene index arrays of a step are concatenated in scene order (scene-local numbering, as the single-scene call
-        takes them); the time axis comes first in what the library sees."""
+    def _predict_future_rollout(self, inputs, masks, node_inds, graph_info, burn_in_masks, uniform=None, return_pack=False):
+        """``predict_future`` of B scenes (B = 1 included) as ONE library call (``aether_dyn_rollout_batched``): per step the
+        burn-in mix and ``aether_dyn_step_batched`` over the present objects of all scenes, queued on the current stream
+        without a host round trip in between.  The per-scene index arrays of a step are concatenated in scene order
+        (scene-local numbering); the time axis comes first in what the library sees.  ``uniform[t][b]``: the Gumbel draws
+        of scene b at step t ([E, K]); drawn here, one ``torch.rand`` per step that has edges, when omitted.
+        ``return_pack``: also return the arrays handed to the library (the tests call the C entry points with them)."""
         if not inputs.is_cuda:
             raise _lib.AetherHipError("aether_amd AetherDynamicVars runs on an MI355X only; got a CPU tensor "
                                       "(there is no CPU fallback)")
@@ -418,7 +349,8 @@ class AetherDynamicVars(nn.Module):
         B, T, Nmax = int(inputs.size(0)), int(inputs.size(1)), int(inputs.size(2))
         n_steps, K = T - 1, self.num_edge_types
         f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        i64 = lambda t: t.to(device=dev, dtype=torch.int64)
+        i64 = lambda t: t.to(device=dev, dtype=torch.int64).contiguous()
+        # time-major (views of the caller's tensors when B = 1: a dimension of size one has no stride to speak of)
         x = f32(inputs).transpose(0, 1).contiguous()                                   # [T][B][Nmax][4]
         m = f32(masks)[:, :n_steps].transpose(0, 1).contiguous()                       # [n_steps][B][Nmax]
         burn = f32(burn_in_masks)[:, :n_steps].transpose(0, 1).contiguous()
@@ -428,10 +360,10 @@ class AetherDynamicVars(nn.Module):
         e_host = (C.c_int64 * (n_steps * B))()
         deg = (C.c_int * (n_steps * B))()
         ptrs = {k: (C.c_void_p * n_steps)() for k in ("ni", "gs", "gr", "e2n", "u")}
-        keep, e2n_max = [], []
-        empty = torch.zeros(0, dtype=torch.int64, device=dev)
+        keep, e2n_range = [], []                                   # device tensors the pointer arrays refer to; (step, lo, hi, limit)
         for t in range(n_steps):
-            ni_l, gs_l, gr_l, e2n_l, u_l, bounds = [], [], [], [], [], []
+            live = {k: [] for k in ptrs}
+            bounds = []
             for b in range(B):
                 n_b = int(node_inds[b][t].numel())
                 n_host[t * B + b] = n_b
@@ -448,23 +380,31 @@ class AetherDynamicVars(nn.Module):
                     u = f32(uniform[t][b]).reshape(-1, K)
                     if u.shape[0] != E:
                         raise ValueError(f"uniform of scene {b}, step {t} must be [E, K]")
-                    u_l.append(u)
-                ni_l.append(i64(node_inds[b][t])); gs_l.append(gs); gr_l.append(gr); e2n_l.append(e2n.reshape(-1))
-            cat = lambda l: torch.cat(l).contiguous() if l else empty
-            E_t = sum(int(g.numel()) for g in gs_l)
-            u_t = torch.cat(u_l).contiguous() if uniform is not None and u_l else torch.rand(max(E_t, 1), K, device=dev)
-            step = dict(ni=cat(ni_l), gs=cat(gs_l), gr=cat(gr_l), e2n=cat(e2n_l), u=u_t)
+                    live["u"].append(u)
+                for k, v in (("ni", i64(node_inds[b][t])), ("gs", gs), ("gr", gr), ("e2n", e2n.reshape(-1))):
+                    live[k].append(v)
+            if not bounds:
+                continue                                       # nobody anywhere at this step: null pointers, no draws
+            if uniform is None:
+                live["u"] = [torch.rand(sum(E for E, _ in bounds), K, device=dev)]
+            step = {k: v[0] if len(v) == 1 else torch.cat(v) for k, v in live.items()}
             keep.append(step)
-            if step["e2n"].numel():        # edge2node names edges of its own scene's graph: one comparison per step
-                bound = torch.repeat_interleave(torch.tensor([e for e, _ in bounds], device=dev),
-                                                torch.tensor([c for _, c in bounds], device=dev), output_size=step["e2n"].numel())
-                e2n_max.append((t, ((step["e2n"] >= bound) | (step["e2n"] < 0)).any()))
             for k in ptrs:
                 ptrs[k][t] = step[k].data_ptr()
-        if e2n_max:                                                # (one device round trip for all steps)
-            flags = torch.stack([f for _, f in e2n_max]).cpu().tolist()
-            for (t, _), bad in zip(e2n_max, flags):
-                if bad:
+            # edge2node names edges of its own scene's graph: an id >= E would index past the scene's message rows
+            if not step["e2n"].numel():
+                continue
+            if len(bounds) == 1:
+                e2n_range.append((t, *torch.aminmax(step["e2n"]), bounds[0][0]))
+            else:
+                bound = torch.repeat_interleave(torch.tensor([E for E, _ in bounds], device=dev),
+                                                torch.tensor([c for _, c in bounds], device=dev),
+                                                output_size=step["e2n"].numel())
+                e2n_range.append((t, step["e2n"].min(), (step["e2n"] - bound).max(), 0))
+        if e2n_range:                                              # (one device round trip for all steps)
+            got = torch.stack([v for _, lo, hi, _ in e2n_range for v in (lo, hi)]).cpu().tolist()
+            for i, (t, _, _, limit) in enumerate(e2n_range):
+                if got[2 * i] < 0 or got[2 * i + 1] >= limit:
                     raise ValueError(f"graph_info of step {t}: an edge2node entry names an edge its scene's graph does not have")
         cfg = self._step_config()
         need = lib.aether_dyn_rollout_batched_workspace_bytes(C.byref(cfg), B, Nmax, n_steps, n_host, e_host, deg)
@@ -483,8 +423,11 @@ class AetherDynamicVars(nn.Module):
                                             prior_c.data_ptr(), dec.data_ptr(), preds.data_ptr(), ws.data_ptr(), ws.numel(),
                                             torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(st, "aether_dyn_rollout_batched")
-        del keep
-        return preds.transpose(0, 1).contiguous()
+        out = preds.transpose(0, 1).contiguous()
+        if return_pack:
+            return out, dict(cfg=cfg, n_objects_max=Nmax, n_steps=n_steps, inputs=x, masks=m, burn_in_masks=burn, n_present=n_host,
+                             n_edges=e_host, in_degree=deg, ptrs=ptrs, keep=keep)
+        return out
 
     @torch.no_grad()
     def predict_future_batched(self, inputs, masks, node_inds, graph_info, burn_in_masks, uniform=None):
@@ -493,7 +436,7 @@ class AetherDynamicVars(nn.Module):
         loop is ONE library call (``aether_dyn_rollout_batched``, up to 256 scenes); ``one_call_step = False`` keeps the
         staged calls with torch glue of round 2 (same stage kernels: bit-identical)."""
         if self.one_call_step and inputs.size(1) > 1 and inputs.size(0) <= 256:
-            return self._predict_future_rollout_batched(inputs, masks, node_inds, graph_info, burn_in_masks, uniform)
+            return self._predict_future_rollout(inputs, masks, node_inds, graph_info, burn_in_masks, uniform)
         B, n_steps = inputs.size(0), inputs.size(1) - 1
         prior_state = self.encoder.get_initial_hidden(inputs)
         dec_state = self.decoder.get_initial_hidden(inputs)

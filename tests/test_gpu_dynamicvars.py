@@ -502,3 +502,122 @@ def test_predict_future_captured_steps_equal_the_eager_loop():
     good = model.predict_future(inputs[:, :3].cuda(), masks[:, :3].cuda(), [node_inds], [graph_info], burn[:, :3].cuda(),
                                 uniform=U[:2])
     assert torch.equal(good, rollout[:, :2])                    # the refused calls queued nothing and touched no state
+
+
+_SMALLEST = {}
+
+
+def _smallest_scenes():
+    """Two scenes of 5 object rows over 6 time steps, built once: scene 0 has [2, 2, 0, 5, 3, 2] present objects per step
+    (k = min(10, n - 1) = 1 with two edges and in_degree 1, an empty step in the middle, a full scene), scene 1
+    [3, 0, 2, 2, 5, 4]; burn-in 2 steps; MODEL_PARAMS as they are (hidden 128, K = 3).  Returns the model, the oracle's
+    prediction for scene 0 and the inputs on the device; nothing in it is modified by the tests."""
+    if _SMALLEST:
+        return _SMALLEST
+    from aether_amd.nn.dynamicvars.aether_dynamicvars import AetherDynamicVars
+    import sys, os
+    from conftest import REPO
+    sys.path.insert(0, os.path.join(REPO, "oracle"))
+    from make_golden_dynamicvars import MODEL_PARAMS, perturb_bn_
+    torch.manual_seed(51)
+    model = AetherDynamicVars(dict(MODEL_PARAMS), device=None).eval()
+    perturb_bn_(model)
+    sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    model = model.cuda()
+    g = torch.Generator().manual_seed(52)
+    B, T, N, K = 2, 6, 5, MODEL_PARAMS["num_edge_types"]
+    counts = [[2, 2, 0, 5, 3, 2], [3, 0, 2, 2, 5, 4]]
+    inputs = torch.randn(B, T, N, 4, generator=g)
+    masks = torch.zeros(B, T, N)
+    for b in range(B):
+        for t, c in enumerate(counts[b]):
+            masks[b, t, torch.randperm(N, generator=g)[:c]] = 1
+    burn = torch.ones(B, T, N)
+    burn[:, 2:] = 0
+    node_inds, graph_info, U = [], [], [[None] * B for _ in range(T - 1)]
+    for b in range(B):
+        ni_b, gi_b = [], []
+        for t in range(T):
+            nv = counts[b][t]
+            if nv >= 2:
+                send, recv = get_knn_graph_info(inputs[b, t].cuda(), masks[b, t].cuda(), nv)
+                gi_b.append((send.cpu(), recv.cpu(), torch.argsort(recv, stable=True).view(-1, min(10, nv - 1)).cpu()))
+            else:
+                z = torch.zeros(0, dtype=torch.int64)
+                gi_b.append((z, z, torch.zeros(0, 1, dtype=torch.int64)))
+            ni_b.append(masks[b, t].nonzero()[:, -1])
+            if t < T - 1:
+                U[t][b] = torch.rand(gi_b[-1][0].numel(), K, generator=g)
+        node_inds.append(ni_b); graph_info.append(gi_b)
+    assert [gi[0].numel() for gi in graph_info[0]] == [2, 2, 0, 20, 6, 2] and graph_info[0][0][2].shape == (2, 1)
+    want0 = DO.predict_future(sd, inputs[:1], masks[:1], node_inds[0], graph_info[0], burn[:1], [U[t][0] for t in range(T - 1)],
+                              MODEL_PARAMS["gumbel_temp"], MODEL_PARAMS["skip_first"], MODEL_PARAMS["pos_representation"])
+    cu = lambda t: t.cuda()
+    _SMALLEST.update(model=model, want0=want0, T=T, N=N, K=K, inputs=cu(inputs), masks=cu(masks), burn=cu(burn),
+                     node_inds=[[cu(n) for n in ni_b] for ni_b in node_inds],
+                     graph_info=[[tuple(cu(x) for x in gi) for gi in gi_b] for gi_b in graph_info],
+                     uniform=[[cu(u) for u in U[t]] for t in range(T - 1)])
+    return _SMALLEST
+
+
+def test_predict_future_smallest_scenes_one_path():
+    """The smallest scenes the one-call path takes, as one scene and as scene 0 of two: bit-identical to the staged loop,
+    within 2 * TOL of the oracle, and within 2 * TOL of itself when a second scene shares the call (the stage GEMMs see other
+    row counts then: the tolerance of the 64-scene test, for the same reason)."""
+    s = _smallest_scenes()
+    model, T = s["model"], s["T"]
+    one = (s["inputs"][:1], s["masks"][:1], [s["node_inds"][0]], [s["graph_info"][0]], s["burn"][:1])
+    u0 = [s["uniform"][t][0] for t in range(T - 1)]
+    got = model.predict_future(*one, uniform=u0)
+    assert got.shape == (1, T - 1, s["N"], 4) and float(got[0, 2].abs().max()) == 0.0
+    model.one_call_step = False
+    try:
+        staged = model.predict_future(*one, uniform=u0)
+    finally:
+        model.one_call_step = True
+    assert torch.equal(got, staged)
+    err = scale_rel_err(got.cpu(), s["want0"])
+    print("smallest scenes, one scene vs oracle:", err)
+    assert err <= 2 * TOL
+    both = model.predict_future(s["inputs"], s["masks"], s["node_inds"], s["graph_info"], s["burn"], uniform=s["uniform"])
+    err2 = scale_rel_err(both[:1].cpu(), got.cpu())
+    print("smallest scenes, scene 0 of two vs alone:", err2)
+    assert both.shape == (2, T - 1, s["N"], 4) and err2 <= 2 * TOL
+
+
+def test_predict_future_draws_and_single_scene_entry_points():
+    """``uniform=None`` draws one ``torch.rand(E_t, K)`` per step that has edges and nothing else (a step with fewer than two
+    present objects draws nothing); and the exported single-scene names aether_dyn_rollout_workspace_bytes /
+    aether_dyn_rollout, called through ctypes with the arrays the module marshalled, give the module's result bit for bit."""
+    import ctypes as C
+    s = _smallest_scenes()
+    model, T, N, K = s["model"], s["T"], s["N"], s["K"]
+    one = (s["inputs"][:1], s["masks"][:1], [s["node_inds"][0]], [s["graph_info"][0]], s["burn"][:1])
+    torch.cuda.manual_seed(77)
+    free = model.predict_future(*one)
+    after = torch.rand(1, device="cuda")
+    torch.cuda.manual_seed(77)
+    hand = []
+    for t in range(T - 1):
+        E_t = s["graph_info"][0][t][0].numel()
+        hand.append(torch.rand(E_t, K, device="cuda") if E_t > 0 else torch.empty(0, K, device="cuda"))
+    assert torch.equal(torch.rand(1, device="cuda"), after)
+    assert torch.equal(model.predict_future(*one, uniform=hand), free)
+    again, pack = model._predict_future_rollout(*one, [[u] for u in hand], return_pack=True)
+    assert torch.equal(again, free)
+    lib = _lib.load()
+    cfg, p = pack["cfg"], pack["ptrs"]
+    need = lib.aether_dyn_rollout_workspace_bytes(C.byref(cfg), N, T - 1, pack["n_present"], pack["n_edges"])
+    assert need > 0
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    ph, pc = (h.float()[0].clone() for h in model.encoder.get_initial_hidden(one[0]))
+    dec = model.decoder.get_initial_hidden(one[0]).float().clone()
+    preds = torch.empty(T - 1, N, 4, dtype=torch.float32, device="cuda")
+    fs, ps_e, ps_d = model._field_struct(), model.encoder._param_struct()[0], model.decoder._param_struct()
+    st = lib.aether_dyn_rollout(C.byref(fs), C.byref(ps_e), C.byref(ps_d), C.byref(cfg), N, T - 1, pack["inputs"].data_ptr(),
+                                pack["masks"].data_ptr(), pack["burn_in_masks"].data_ptr(), pack["n_present"], pack["n_edges"],
+                                p["ni"], p["gs"], p["gr"], p["e2n"], pack["in_degree"], p["u"], ph.data_ptr(), pc.data_ptr(),
+                                dec.data_ptr(), preds.data_ptr(), ws.data_ptr(), ws.numel(),
+                                torch.cuda.current_stream().cuda_stream)
+    _lib.check(st, "aether_dyn_rollout")
+    assert torch.equal(preds.unsqueeze(0), free)
