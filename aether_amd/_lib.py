@@ -242,6 +242,16 @@ SIGNATURES = {
                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(AetherGraphInfo), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
+    "aether_rollout_dynamic_field_train_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                                                        C.c_int]),
+    "aether_rollout_dynamic_field_train_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                             C.POINTER(AetherGraphInfo), C.c_void_p, C.c_size_t, C.c_void_p,
+                                                             C.c_int, C.c_float, C.c_int, C.c_void_p]),
+    "aether_rollout_dynamic_field_backward": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.POINTER(AetherGraphInfo), C.c_void_p, C.c_size_t, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "aether_set_option": (C.c_int, [C.c_char_p, C.c_int]),
     "aether_mse_scratch_bytes": (C.c_size_t, []),
     "aether_mse_loss_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,

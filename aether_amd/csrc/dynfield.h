@@ -190,7 +190,10 @@ __device__ __forceinline__ float dsilu_f(float s) {       // d/ds [s sigmoid(s)]
     return sg * (1.0f + s * (1.0f - sg));
 }
 
-template <int D>
+// ACC (training through a rollout, host_rollout_train.inc): the row of `partial` is not cleared, every contribution is
+// ADDED to what the launches of the later steps left there -- an entry still belongs to one thread and the launches are
+// stream-ordered, so the sum over the steps has a fixed order too; k_dynfield_reduce then runs once for all steps.
+template <int D, bool ACC = false>
 __global__ void __launch_bounds__(256)
 kb_dynfield(AetherDynFieldParams P, const float* __restrict__ x, const float* __restrict__ vel,
             const float* __restrict__ charges, const float* __restrict__ gfield, float* __restrict__ partial, int N,
@@ -210,7 +213,10 @@ kb_dynfield(AetherDynFieldParams P, const float* __restrict__ x, const float* __
     const int64_t base = (int64_t)blockIdx.x * N;
     float* g = partial + (size_t)blockIdx.x * OF::total;
     auto silu_f = [](float s) { return s / (1.0f + expf(-s)); };
-    for (int e = tid; e < OF::total; e += 256) g[e] = 0.0f;
+    if constexpr (!ACC)
+        for (int e = tid; e < OF::total; e += 256) g[e] = 0.0f;
+    // an entry written once per launch (sections C and D): the value, or one more term of the sum over the steps
+    auto put = [&](int e, float v) { if constexpr (ACC) g[e] += v; else g[e] = v; };
     if (tid < 2 * DFH) { dmod[0][tid] = 0.0f; dmod[1][tid] = 0.0f; }
     if (tid < DFH) { dsum[tid] = 0.0f; ubar[tid] = 0.0f; }
     auto stage_x = [&](int c0, int cnt) {
@@ -419,25 +425,25 @@ kb_dynfield(AetherDynFieldParams P, const float* __restrict__ x, const float* __
         const float* w2 = f ? P.film2_w2 : P.film1_w2;
         const float* w4 = f ? P.film2_w4 : P.film1_w4;
         const int fo = f ? OF::film2 : OF::film1;
-        for (int e = tid; e < 2 * DFH * DFH; e += 256) g[fo + OF::F_w4 + e] = dmod[f][e >> 5] * fh[f][1][e & 31];
-        if (tid < 2 * DFH) g[fo + OF::F_b4 + tid] = dmod[f][tid];
+        for (int e = tid; e < 2 * DFH * DFH; e += 256) put(fo + OF::F_w4 + e, dmod[f][e >> 5] * fh[f][1][e & 31]);
+        if (tid < 2 * DFH) put(fo + OF::F_b4 + tid, dmod[f][tid]);
         if (tid < DFH) {
             float s = 0.0f;
             for (int o = 0; o < 2 * DFH; ++o) s = fmaf(w4[o * DFH + tid], dmod[f][o], s);
             dp1[tid] = s * dsilu_f(fpre[f][1][tid]);
         }
         __syncthreads();
-        for (int e = tid; e < DFH * DFH; e += 256) g[fo + OF::F_w2 + e] = dp1[e >> 5] * fh[f][0][e & 31];
+        for (int e = tid; e < DFH * DFH; e += 256) put(fo + OF::F_w2 + e, dp1[e >> 5] * fh[f][0][e & 31]);
         if (tid < DFH) {
-            g[fo + OF::F_b2 + tid] = dp1[tid];
+            put(fo + OF::F_b2 + tid, dp1[tid]);
             float s = 0.0f;
             for (int o = 0; o < DFH; ++o) s = fmaf(w2[o * DFH + tid], dp1[o], s);
             dp0[tid] = s * dsilu_f(fpre[f][0][tid]);
         }
         __syncthreads();
-        for (int e = tid; e < DFH * DFH; e += 256) g[fo + OF::F_w0 + e] = dp0[e >> 5] * summary[e & 31];
+        for (int e = tid; e < DFH * DFH; e += 256) put(fo + OF::F_w0 + e, dp0[e >> 5] * summary[e & 31]);
         if (tid < DFH) {
-            g[fo + OF::F_b0 + tid] = dp0[tid];
+            put(fo + OF::F_b0 + tid, dp0[tid]);
             float s = 0.0f;
             for (int o = 0; o < DFH; ++o) s = fmaf(w0[o * DFH + tid], dp0[o], s);
             dsum[tid] += s;
@@ -516,8 +522,8 @@ kb_dynfield(AetherDynFieldParams P, const float* __restrict__ x, const float* __
         }
         __syncthreads();
     }
-    for (int e = tid; e < DFH * DFH; e += 256) g[OF::nn_w2 + e] = dsum[e >> 5] * ubar[e & 31];
-    if (tid < DFH) g[OF::nn_b2 + tid] = dsum[tid] * wsum;
+    for (int e = tid; e < DFH * DFH; e += 256) put(OF::nn_w2 + e, dsum[e >> 5] * ubar[e & 31]);
+    if (tid < DFH) put(OF::nn_b2 + tid, dsum[tid] * wsum);
 }
 
 // grads.<tensor>[i] = sum over graphs of partial[graph][offset + i].  A thread summing all graphs one after the other

@@ -124,8 +124,9 @@ def _hand_over_grads(module, plist, views, dst_flat, dst_views, aliased, need, s
     autograd returns for the parameters.  A parameter whose .grad is unset gets the view of the flat buffer itself (like
     DDP's gradient_as_bucket_view); a .grad that already is that view is accumulated into in place (``aliased``: the
     backward wrote into the second buffer); any other existing .grad is accumulated by autograd.  ``skip``: indices of
-    parameters that never get a gradient (they do not reach the output): None, .grad left as it is."""
-    if module.dp_group is not None:            # one fused all-reduce of the flat buffer (RCCL)
+    parameters that never get a gradient (they do not reach the output): None, .grad left as it is.  ``dst_flat`` None:
+    ``dst_views`` are this call's own tensors, finished by the module (mean included) -- handed to autograd as they are."""
+    if module.dp_group is not None and dst_flat is not None:      # one fused all-reduce of the flat buffer (RCCL)
         import torch.distributed as dist
         dist.all_reduce(dst_flat, group=module.dp_group)
         dst_flat.div_(dist.get_world_size(module.dp_group))
@@ -140,7 +141,7 @@ def _hand_over_grads(module, plist, views, dst_flat, dst_views, aliased, need, s
             v.add_(dv)
             out.append(None)
         else:
-            out.append(dv.clone())
+            out.append(dv if dst_flat is None else dv.clone())
     return out
 
 
@@ -161,17 +162,18 @@ def _f32g(t):
 
 
 class _RolloutStep(torch.autograd.Function):
-    """aether_rollout_train_forward / aether_rollout_backward behind torch.autograd: the whole k-step rollout is ONE
-    autograd node (parameters, and x / vel where they require a gradient)."""
+    """aether_rollout_train_forward / aether_rollout_backward (for a model with a latent field, ``num_nodes`` not None:
+    aether_rollout_dynamic_field_train_forward / aether_rollout_dynamic_field_backward) behind torch.autograd: the whole
+    k-step rollout is ONE autograd node (parameters, and x / vel where they require a gradient)."""
 
-    N_FIXED = 8          # module, x, vel, charges, graph, n_edges, steps, dt precede the parameters
+    N_FIXED = 9          # module, x, vel, charges, graph, n_edges, steps, dt, num_nodes precede the parameters
 
     @staticmethod
-    def forward(ctx, module, x, vel, charges, graph, n_edges, steps, dt, *params):
+    def forward(ctx, module, x, vel, charges, graph, n_edges, steps, dt, num_nodes, *params):
         ps = module._rollout_train_params(x.device)
-        traj, ws, token = module._rollout_train_forward(ps, x, vel, charges, graph, n_edges, steps, dt)
+        traj, ws, token = module._rollout_train_forward(ps, x, vel, charges, graph, n_edges, steps, dt, num_nodes)
         ctx.module = module
-        ctx.saved = (x, vel, charges, graph, ws, n_edges, steps, dt, token)
+        ctx.saved = (x, vel, charges, graph, ws, n_edges, steps, dt, num_nodes, token)
         ctx.consumed = False
         ctx.save_for_backward(traj)
         return traj
@@ -183,23 +185,18 @@ class _RolloutStep(torch.autograd.Function):
             raise RuntimeError("trying to backward through a differentiable_rollout a second time: the first backward "
                                "consumed its workspace (call differentiable_rollout again)")
         ctx.consumed = True
-        x, vel, charges, (gbuf, ginfo), ws, n_edges, steps, dt, _token = ctx.saved
+        x, vel, charges, graph, ws, n_edges, steps, dt, num_nodes, _token = ctx.saved
         traj, = ctx.saved_tensors
         plist, views, dst_flat, dst_views, aliased, gs, finish = module._grad_destination()
         g = grad_traj.to(torch.float32).contiguous()
         gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
         gv = torch.empty_like(vel) if ctx.needs_input_grad[2] else None
         ps = module._rollout_train_params(x.device, refresh=False)
-        st = _lib.load().aether_rollout_backward(ps, gs, module.num_dims, module._kw, x.shape[0], n_edges, x.data_ptr(),
-                                                 vel.data_ptr(), charges.data_ptr(), gbuf.data_ptr(), C.byref(ginfo),
-                                                 ws.data_ptr(), ws.numel(), traj.data_ptr(), g.data_ptr(),
-                                                 None if gx is None else gx.data_ptr(), None if gv is None else gv.data_ptr(),
-                                                 steps, dt, torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(st, "aether_rollout_backward")
+        module._rollout_train_backward(ps, gs, x, vel, charges, graph, ws, n_edges, traj, g, gx, gv, steps, dt, num_nodes)
         if finish is not None:
             finish()
         out = _hand_over_grads(module, plist, views, dst_flat, dst_views, aliased, ctx.needs_input_grad[_RolloutStep.N_FIXED:])
-        return (None, gx, gv, None, None, None, None, None) + tuple(out)
+        return (None, gx, gv, None, None, None, None, None, None) + tuple(out)
 
 
 # -- a model inside its kernel-width engine --------------------------------------------------------------------------
@@ -598,32 +595,56 @@ class FrameModule(nn.Module):
 
     # -- training through the rollout ------------------------------------------------------
     def _rollout_train_params(self, device, refresh=True):
-        """byref of the AetherParams a training rollout runs on; ``refresh``: bring copies of the parameters up to date
-        first (the forward does, the backward reads what the forward read)."""
+        """byref of the AetherParams a training rollout runs on -- for a model with a latent field the pair (that, byref of
+        its AetherDynFieldParams); ``refresh``: bring copies of the parameters up to date first (the forward does, the
+        backward reads what the forward read)."""
         raise NotImplementedError
 
     def _grad_destination(self):
         """Where a backward writes the parameter gradients -> (parameters, views of the flat gradient buffer, destination
-        flat buffer and its views, is that the second buffer, byref of the destinations' AetherParams, a callable that
-        finishes them (engine-shaped scratch cut to the model's shapes) or None)."""
+        flat buffer and its views, is that the second buffer, byref of the destinations' AetherParams (with a latent field:
+        the pair of ``_rollout_train_params``), a callable that finishes them (engine-shaped scratch cut to the model's
+        shapes) or None)."""
         raise NotImplementedError
 
-    def _rollout_train_forward(self, ps, x, vel, charges, graph, n_edges, steps, dt):
-        """``aether_rollout_train_forward`` -> (trajectory [steps, n_nodes, D], workspace, its token)."""
+    def _rollout_train_forward(self, ps, x, vel, charges, graph, n_edges, steps, dt, num_nodes=None):
+        """``aether_rollout_train_forward`` (``num_nodes`` None) or ``aether_rollout_dynamic_field_train_forward``
+        -> (trajectory [steps, n_nodes, D], workspace, its token)."""
         gbuf, ginfo = graph
         n_nodes, D = x.shape
         lib = _lib.load()
-        nbytes = lib.aether_rollout_train_workspace_bytes(n_nodes, n_edges, D, self._kw, steps)
+        if num_nodes is None:
+            nbytes = lib.aether_rollout_train_workspace_bytes(n_nodes, n_edges, D, self._kw, steps)
+        else:
+            nbytes = lib.aether_rollout_dynamic_field_train_workspace_bytes(n_nodes, n_edges, D, self._kw, num_nodes, steps)
         ws, token = _train_workspace(self, max(nbytes, 256), x.device, slot="_rollout_train_ws")
         # an optimizer step follows: the inference workspace's weight images are stale from here on (``_step``)
         self._ws_key = self._wimg_key = None
         traj = torch.empty(steps, n_nodes, D, dtype=torch.float32, device=x.device)
-        st = lib.aether_rollout_train_forward(ps, D, self._kw, n_nodes, n_edges, x.data_ptr(), vel.data_ptr(),
-                                              charges.data_ptr(), gbuf.data_ptr(), C.byref(ginfo), ws.data_ptr(), ws.numel(),
-                                              traj.data_ptr(), steps, dt, self.flags & _FORCED,
-                                              torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(st, "aether_rollout_train_forward")
+        tail = (x.data_ptr(), vel.data_ptr(), charges.data_ptr(), gbuf.data_ptr(), C.byref(ginfo), ws.data_ptr(), ws.numel(),
+                traj.data_ptr(), steps, dt, self.flags & _FORCED, torch.cuda.current_stream(x.device).cuda_stream)
+        if num_nodes is None:
+            _lib.check(lib.aether_rollout_train_forward(ps, D, self._kw, n_nodes, n_edges, *tail), "aether_rollout_train_forward")
+        else:
+            _lib.check(lib.aether_rollout_dynamic_field_train_forward(*ps, D, self._kw, n_nodes, n_edges, num_nodes, *tail),
+                       "aether_rollout_dynamic_field_train_forward")
         return traj, ws, token
+
+    def _rollout_train_backward(self, ps, gs, x, vel, charges, graph, ws, n_edges, traj, grad_traj, gx, gv, steps, dt,
+                                num_nodes=None):
+        """``aether_rollout_backward`` (``num_nodes`` None) or ``aether_rollout_dynamic_field_backward`` into ``gs`` (the
+        model's ``_grad_destination``) and ``gx`` / ``gv`` (None: not wanted).  Consumes ``ws``."""
+        gbuf, ginfo = graph
+        lib = _lib.load()
+        tail = (x.data_ptr(), vel.data_ptr(), charges.data_ptr(), gbuf.data_ptr(), C.byref(ginfo), ws.data_ptr(), ws.numel(),
+                traj.data_ptr(), grad_traj.data_ptr(), None if gx is None else gx.data_ptr(),
+                None if gv is None else gv.data_ptr(), steps, dt, torch.cuda.current_stream(x.device).cuda_stream)
+        if num_nodes is None:
+            _lib.check(lib.aether_rollout_backward(ps, gs, self.num_dims, self._kw, x.shape[0], n_edges, *tail),
+                       "aether_rollout_backward")
+        else:
+            _lib.check(lib.aether_rollout_dynamic_field_backward(*ps, *gs, self.num_dims, self._kw, x.shape[0], n_edges,
+                                                                 num_nodes, *tail), "aether_rollout_dynamic_field_backward")
 
     def _rollout_grad(self, x, vel, edges, charges, steps, dt, num_nodes=None):
         """The rollout of ``_rollout`` attached to autograd (``_RolloutStep``): gradients for the parameters that require
@@ -638,7 +659,8 @@ class FrameModule(nn.Module):
         if self._kw != 64:
             raise _lib.AetherHipError("rollout training: 64-wide engine only")
         graph = self.prepare_graph((send, recv), n_nodes)
-        return _RolloutStep.apply(self, _f32g(x), _f32g(vel), _f32(charges), graph, E, steps, float(dt), *self._param_list())
+        return _RolloutStep.apply(self, _f32g(x), _f32g(vel), _f32(charges), graph, E, steps, float(dt),
+                                  None if num_nodes is None else int(num_nodes), *self._param_list())
 
     def differentiable_rollout(self, x, vel, edges, charges, steps, dt=1.0):
         """``rollout`` for training: positions ``[steps, n_nodes, D]`` of the same protocol, attached to autograd for the

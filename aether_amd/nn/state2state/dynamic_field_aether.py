@@ -6,7 +6,9 @@ Same constructor, ``forward(h, x, edges, vel, edge_attr_orig, charges, num_nodes
 summary + FiLM field net, :11-48), everything after it from the same kernels as ``Aether``
 (``aether_forward_field``).  With gradients enabled the step goes through ``_DynStep``: ``aether_backward_field``
 (GNN gradients + dL/dfield) and ``aether_dynamic_field_backward`` (FiLM field net, modulators, attention pooling),
-so the training loop of experiments/lorentz/main.py:200-260 works unchanged.  No CPU fallback.
+so the training loop of experiments/lorentz/main.py:200-260 works unchanged.  ``differentiable_rollout(..., num_nodes=N)``
+trains through the device rollout (``_frame._RolloutStep``: ``aether_rollout_dynamic_field_train_forward`` /
+``aether_rollout_dynamic_field_backward``).  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -264,10 +266,47 @@ class DynamicFieldAether(FrameModule):
             raise ValueError("num_nodes (objects per graph) is required, as in forward")
         return self._rollout(x, vel, edges, charges, steps, dt, num_nodes=num_nodes)
 
+    # -- training through the rollout (``_RolloutStep``) -----------------------------------
+    grad_as_view = False         # gradients are handed to autograd as tensors of their own (``_grad_destination``)
+
+    def _rollout_train_params(self, device, refresh=True):
+        ps, fps = self._current_structs(device) if refresh else self._structs(device)
+        return C.byref(ps), C.byref(fps)
+
+    def _grad_destination(self):
+        """One fresh flat buffer per backward, as ``_DynStep``: the kernels write kernel-shaped tensors into it, a narrow
+        model's GNN gradients are cut back to the parameters' shapes afterwards."""
+        plist = self._param_list()
+        names, offsets, total = self._grad_layout()
+        flat = torch.zeros(total, dtype=torch.float32, device=plist[0].device)
+        kshapes = self._kernel_shapes()
+        kgrads = {n: flat[o:o + int(np.prod(kshapes[n]))].view(kshapes[n]) for n, o in zip(names, offsets)}
+        gtensors = dict(kgrads)
+        gtensors.update(self._dummy)                                 # field_net.net.* slots: not written in this mode
+        gs, gfs = _lib.params_struct(gtensors), self._dyn_struct(kgrads)
+        narrow = self.hidden_size != self._kw
+        dst = [torch.empty_like(p) if narrow and n.startswith("gnn.") else kgrads[n] for n, p in zip(names, plist)]
+
+        def finish():
+            if self.dp_group is not None:          # one all-reduce of the flat gradient buffer (RCCL), then the mean
+                import torch.distributed as dist
+                dist.all_reduce(flat, group=self.dp_group)
+                flat.div_(dist.get_world_size(self.dp_group))
+            if narrow:
+                for n, p, d in zip(names, plist, dst):
+                    if n.startswith("gnn."):
+                        cut(d, kgrads[n], _pad_blocks(n, p.shape, self.hidden_size, self._kw))
+        return plist, dst, None, dst, False, (C.byref(gs), C.byref(gfs)), finish
+
     def differentiable_rollout(self, x, vel, edges, charges, steps, dt=1.0, num_nodes=None):
-        """Not built: the backward through a rollout exists for the built-in field net and the zero field only (the
-        latent field's own backward would have to join the chain between the steps)."""
-        raise _lib.AetherHipError("DynamicFieldAether.differentiable_rollout: not built")
+        """``rollout`` for training (``FrameModule.differentiable_rollout``) with the latent field recomputed from the
+        current state every step, and differentiated with it: gradients for the GNN and the field net's parameters and,
+        where they require one, ``x`` and ``vel`` (``aether_rollout_dynamic_field_train_forward`` /
+        ``aether_rollout_dynamic_field_backward``).  ``num_nodes``: objects per graph, as in ``forward``."""
+        if num_nodes is None:
+            raise _lib.AetherHipError("DynamicFieldAether.differentiable_rollout: not built without num_nodes (the objects "
+                                      "per graph cannot be inferred from the inputs: pass num_nodes, as in forward)")
+        return self._rollout_grad(x, vel, edges, charges, steps, dt, num_nodes=int(num_nodes))
 
     def forward(self, h, x, edges, vel, edge_attr_orig, charges, num_nodes):
         """``h`` is ignored, as in the reference (dynamic_field_aether.py:79-100)."""

@@ -84,14 +84,15 @@ class _MseLoss(torch.autograd.Function):
         return ctx.saved_tensors[0] * g, None
 
 
-def rollout_loss(model, x, vel, edges, charges, targets, dt: float = 1.0):
+def rollout_loss(model, x, vel, edges, charges, targets, dt: float = 1.0, **rollout_kwargs):
     """The k-step ("push-forward") training loss: mean over all steps and elements of the squared error between the
     device rollout ``model.differentiable_rollout(x, vel, edges, charges, steps = targets.shape[0], dt)`` and
     ``targets [steps, n_nodes, D]`` (the positions at t = 1 .. steps).  ``.backward()`` runs the backward through time
-    on the device; where a runner computes ``loss_mse(model(...), target)`` for one step, it calls this instead."""
+    on the device; where a runner computes ``loss_mse(model(...), target)`` for one step, it calls this instead.
+    ``rollout_kwargs`` go to ``differentiable_rollout`` (``DynamicFieldAether``: ``num_nodes``, the objects per graph)."""
     if targets.dim() != 3:
         raise ValueError("targets must be [steps, n_nodes, D]")
-    traj = model.differentiable_rollout(x, vel, edges, charges, targets.shape[0], dt)
+    traj = model.differentiable_rollout(x, vel, edges, charges, targets.shape[0], dt, **rollout_kwargs)
     if traj.shape != targets.shape:
         raise ValueError(f"targets must be {tuple(traj.shape)}, got {tuple(targets.shape)}")
     return _MseLoss.apply(traj.reshape(-1), targets.reshape(-1))

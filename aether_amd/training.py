@@ -191,19 +191,22 @@ class GraphedRolloutTrainStep(GraphedTrainStep):
     """``GraphedTrainStep`` for the k-step loss: ONE hipGraph holds the rollout forward, the loss and the backward through
     time (``model.differentiable_rollout``: ``aether_rollout_train_forward`` / ``aether_rollout_backward``); capture,
     optimizer graph and all-reduce are that class's.  ``example_args``: ``(x, vel, edges, charges)`` of
-    ``differentiable_rollout``; ``example_target``: ``[steps, n_nodes, D]``, the positions at t = 1 .. steps (its first
+    ``differentiable_rollout``, or ``(x, vel, edges, charges, num_nodes)`` for a model that takes the objects per graph
+    (``DynamicFieldAether``); ``example_target``: ``[steps, n_nodes, D]``, the positions at t = 1 .. steps (its first
     dimension is the number of steps); ``loss_fn`` None: the mean squared error over all steps and elements
     (``aether_amd.rollout.rollout_loss``)."""
 
     def __init__(self, model, example_args, example_target, dt=1.0, **kwargs):
-        if example_target.dim() != 3 or len(example_args) != 4:
-            raise ValueError("GraphedRolloutTrainStep: example_args = (x, vel, edges, charges), example_target [steps, n_nodes, D]")
+        if example_target.dim() != 3 or len(example_args) not in (4, 5):
+            raise ValueError("GraphedRolloutTrainStep: example_args = (x, vel, edges, charges) or (x, vel, edges, charges, "
+                             "num_nodes), example_target [steps, n_nodes, D]")
         self.dt = float(dt)                 # (before the base constructor: it runs warm-up steps)
         super().__init__(model, example_args, example_target, **kwargs)
 
     def _forward_backward(self):
-        x, vel, edges, charges = self.args
-        traj = self.model.differentiable_rollout(x, vel, edges, charges, self.target.shape[0], self.dt)
+        x, vel, edges, charges = self.args[:4]
+        extra = {"num_nodes": self.args[4]} if len(self.args) == 5 else {}
+        traj = self.model.differentiable_rollout(x, vel, edges, charges, self.target.shape[0], self.dt, **extra)
         if self.loss_fn is None:
             from .optim import mse_loss_grad
             loss, grad = mse_loss_grad(traj, self.target)

@@ -364,6 +364,37 @@ int aether_rollout_backward(const AetherParams* params, const AetherParams* grad
                             int64_t n_edges, const float* x0, const float* vel0, const float* charges, const void* graph,
                             const AetherGraphInfo* info, void* workspace, size_t workspace_bytes, const float* trajectory,
                             const float* grad_trajectory, float* grad_x0, float* grad_vel0, int steps, float dt, void* stream);
+/*
+ * The same for the dynamic-field model (nn/state2state/dynamic_field_aether.py:79-100 as the step): the protocol, the
+ * contract and the checks of the two entries above, with the latent field recomputed from (x_t, v_t) every step as in
+ * aether_rollout_dynamic_field -- the training forward writes the trajectory of that call, bit for bit.  Further checks:
+ * dyn_params and every pointer inside dyn_grads non-null, 1..2048 nodes per graph, n_nodes a multiple of nodes_per_graph.
+ *   forward, step t : aether_dynamic_field on (x_t, v_t), then the kept step with that field (one launch more than above).
+ *   backward, step t: the step's backward with dL/dfield (aether_backward_field), the field net's backward on it
+ *                     (recomputed from x_t, v_t: no field is kept per step) giving dL/d[x | v] through the field, the
+ *                     input gradients with that term folded in (aether_backward_inputs(field_input_grad)), the chain
+ *                     launch as above: one launch more per step, and one per call --
+ *   dyn_grads       : OVERWRITTEN with the 27 field-net gradients summed over the steps.  The sum over the steps runs in
+ *                     the per-graph partial rows (each entry owned by one thread, step steps-1 first), the sum over the
+ *                     graphs once per call: no float atomics, the same bits on every run.
+ *   grads           : as above; grads->field_* (the built-in field net, bypassed) are not written.
+ * workspace: aether_rollout_dynamic_field_train_workspace_bytes(...) bytes = that of the entries above + one partial row
+ * per graph + three per-node buffers (field, dL/dfield, dL/d[x | v]); 0 for sizes the entries refuse.
+ */
+size_t aether_rollout_dynamic_field_train_workspace_bytes(int64_t n_nodes, int64_t n_edges, int num_dims, int hidden,
+                                                          int nodes_per_graph, int steps);
+int aether_rollout_dynamic_field_train_forward(const AetherParams* params, const AetherDynFieldParams* dyn_params, int num_dims,
+                                               int hidden, int64_t n_nodes, int64_t n_edges, int nodes_per_graph,
+                                               const float* x0, const float* vel0, const float* charges, const void* graph,
+                                               const AetherGraphInfo* info, void* workspace, size_t workspace_bytes,
+                                               float* trajectory, int steps, float dt, int flags, void* stream);
+int aether_rollout_dynamic_field_backward(const AetherParams* params, const AetherDynFieldParams* dyn_params,
+                                          const AetherParams* grads, const AetherDynFieldParams* dyn_grads, int num_dims,
+                                          int hidden, int64_t n_nodes, int64_t n_edges, int nodes_per_graph, const float* x0,
+                                          const float* vel0, const float* charges, const void* graph,
+                                          const AetherGraphInfo* info, void* workspace, size_t workspace_bytes,
+                                          const float* trajectory, const float* grad_trajectory, float* grad_x0,
+                                          float* grad_vel0, int steps, float dt, void* stream);
 
 /*
  * seq2seq Aether, field query: replaces Aether.predict_field
