@@ -407,7 +407,11 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     const int eb = wg.eb, m = wg.m;                      // (= rowptr[nb], rowptr[ne] - rowptr[nb]: kept with the descriptor)
     const int n_tiles = (m + 15) >> 4;
     const int na = wg.na;                                // edges [0, na) of the local order have own senders
-    volatile int* arrived = reinterpret_cast<volatile int*>(smem + L::ARRIVED);
+    // An LDS-typed word: plain ds_write / ds_read.  (Through a generic volatile pointer every access was a flat_ instruction
+    // with sc0 sc1 and a full vmcnt(0) drain -- two of them here, in front of wave 0's first loads.)  volatile: the spin in
+    // wait_partner_rows re-reads the word in every iteration.
+    typedef __attribute__((address_space(3))) volatile int lds_word;
+    lds_word* arrived = (lds_word*)(smem + L::ARRIVED);
     if (tid == 0) { arrived[0] = 0; arrived[1] = 0; }    // ordered before any use by the prologue's barriers
 #ifdef AETHER_FUSED_STAMPS
     const unsigned long long t_entry = wall_clock64();
@@ -456,7 +460,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     const int f_local = 16 * (NW * (lane >> 4) + wave) + (lane & 15);
     const bool f_have = lane < 16 * FR && f_local < m;       // this lane builds the features of edge f_local
     int4 f_e = make_int4(0, 0, 0, 0);                        // {sorted position, sender, receiver, original edge}
-    f32x2 f_ea = {0.0f, 0.0f};                               // its two edge attributes (q_i q_j: the first only)
+    f32x2 f_ea = {0.0f, 0.0f};                               // its two edge attributes (rollout: q_i, q_j)
     int4 t_e[ROUNDS];                                        // per (round, lane i): the tile's edge i
     // The segment records of the wave's tiles (k_graph_tiles) are the same for all lanes: tile index from the wave index in
     // a scalar register (as dma_images), so they arrive by scalar loads and stay in scalar registers.  Requested here, in
@@ -474,25 +478,48 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             for (int w = 0; w < 4; ++w) seg_rows[r][w] = __builtin_amdgcn_readfirstlane(rec[2 + w]);
         }
     }
+    // node-sum ownership (step 1 of the node phase): thread -> (node slot, 4 columns).  The node's nrange record is first
+    // used in layer 1's node phase; it is requested here with the edge records (loaded behind the P2 barrier it was one
+    // more full round trip in front of layer 1's tiles).
+    const int aslot = (tid >> 4) & (FUSED_MAX_NODES - 1), ac4 = (tid & 15) * 4;
+    int4 nr_rec;
+    // Every load of the index stages is unconditional, on a clamped index, and the lanes (or workgroups) that have no such
+    // edge or node select their constant AFTER the wait (index_select): a load in an exec-masked region gets a wait of its
+    // own.  A workgroup without edges (or nodes) reads its own descriptor instead of a record: 16 valid bytes.
+    const int4* own_desc = reinterpret_cast<const int4*>(wgdesc + blockIdx.x);
+    const int4* le_base = m > 0 ? ledge + eb : own_desc;
+    const int4* nr_base = n > 0 ? reinterpret_cast<const int4*>(nrange) + nb : own_desc;
+    const float* ea_base = m > 0 ? edge_attr_orig : reinterpret_cast<const float*>(own_desc);
+    const float* qattr = dbg.step.qattr;
     auto index_stage_a = [&]() {
-        if (f_have) f_e = ledge[eb + f_local];
+        f_e = le_base[f_have ? f_local : 0];
 #pragma unroll
         for (int r = 0; r < ROUNDS; ++r) {
             const int tile = NW * r + wave, local = 16 * tile + i;
-            t_e[r] = m > 0 ? ledge[eb + (local < m ? local : 0)] : make_int4(0, vb, nb, 0);
+            t_e[r] = le_base[local < m ? local : 0];
+        }
+        nr_rec = nr_base[aslot < n ? aslot : 0];
+    };
+    auto index_select = [&]() {
+        if (!f_have) f_e = make_int4(0, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < ROUNDS; ++r) {
+            t_e[r].x = m > 0 ? t_e[r].x : 0; t_e[r].y = m > 0 ? t_e[r].y : vb;
+            t_e[r].z = m > 0 ? t_e[r].z : nb; t_e[r].w = m > 0 ? t_e[r].w : 0;
         }
     };
     // (returns its result: written through the capture, the two floats were kept in scratch memory -- 8 bytes per thread
     // stored and re-loaded, + 1 MB of WRITE_SIZE per launch in the first version)
+    // Lanes without an edge hold a zero record (index_select) and load element 0; P2 reads f_ea only on lanes that have
+    // the edge.  The two values come back as loaded (rollout: q_i and q_j, multiplied in P2): arithmetic on them here
+    // would be a wait for them in the middle of the field net.
     auto index_stage_b = [&]() -> f32x2 {
-        f32x2 v = {0.0f, 0.0f};
-        if (f_have) {
-            if (dbg.step.qattr) {          // main.py:243-246: q_i q_j (the distance is computed with the features)
-                v[0] = dbg.step.qattr[f_e.y] * dbg.step.qattr[f_e.z];
-            } else {
-                const float* ea = edge_attr_orig + 2 * (int64_t)f_e.w;
-                v[0] = ea[0]; v[1] = ea[1];
-            }
+        f32x2 v;
+        if (qattr) {                       // main.py:243-246: q_i q_j (the distance is computed with the features)
+            v[0] = qattr[f_e.y]; v[1] = qattr[f_e.z];
+        } else {
+            const float* ea = ea_base + 2 * (int64_t)f_e.w;
+            v[0] = ea[0]; v[1] = ea[1];
         }
         return v;
     };
@@ -501,54 +528,120 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     // aether.py:108-134 (field), geometry.py:7-73 + aether.py:33-50 (frames), locs.py:214-218 (x0).
     // Wave t owns the visible nodes 16t .. 16t+15 as the 16 columns of its MFMA tiles; the three
     // Linear layers chain in accumulator layout, lanes q == 0 end up with the node's force and build
-    // its frame, and x0 = res(rel_feat) is one more tile product: no workgroup barrier in between,
-    // every global load (inputs, 2,080 field parameters, res weights) issued up front.
+    // its frame, and x0 = res(rel_feat) is one more tile product: no workgroup barrier in between.
+    // The field wave's load block is: every pointer it needs out of the kernel arguments (scalar loads, one wait),
+    // then every vector load (inputs, 2,080 field parameters, res weights, the external field, this wave's edge and
+    // node records) back to back and unconditional, on clamped indices, then ONE vmcnt(0); lanes whose element does not exist select
+    // their zero behind that wait.  (Left to the compiler the block held three scalar round trips and three vmcnt(0):
+    // a conditional load becomes an exec-masked region with a wait of its own.)  The only loads behind the wait are
+    // the edge attributes, whose address needs the edge record: they are issued behind the layer-1 MFMAs.
     {
         const int vtiles = (nv + 15) >> 4;
         if (wave < vtiles) {
+            const float* p_emb = P.field_emb; const float* p_w0 = P.field_w0; const float* p_b0 = P.field_b0;
+            const float* p_w2 = P.field_w2; const float* p_b2 = P.field_b2; const float* p_w4 = P.field_w4;
+            const float* p_b4 = P.field_b4; const float* p_rb = P.l1_res_b; const float* p_rw = P.l1_res_w;
+            const float* p_ext = dbg.step.ext_field ? dbg.step.ext_field : x;      // (no external field: x again, not used)
+            asm volatile("" :: "s"(p_emb), "s"(p_w0), "s"(p_b0), "s"(p_w2), "s"(p_b2), "s"(p_w4), "s"(p_b4), "s"(p_rb),
+                         "s"(p_rw), "s"(p_ext), "s"(x), "s"(vel), "s"(charges), "s"(le_base), "s"(nr_base), "s"(ea_base),
+                         "s"(qattr));                          // all in scalar registers before the first vector load
             const int node = 16 * wave + i;                    // visible slot
             const bool live = node < nv;
             const int64_t g = vb + (live ? node : 0);
-            float pz[D], vz[D];
+            float pz[D], vz[D], ef[D];
 #pragma unroll
-            for (int d = 0; d < D; ++d) { pz[d] = x[g * D + d]; vz[d] = vel[g * D + d]; }
+            for (int d = 0; d < D; ++d) { pz[d] = x[g * D + d]; vz[d] = vel[g * D + d]; ef[d] = p_ext[g * D + d]; }
             const float ch = charges[g];
             // layer-1 operands: B = z[k][node], A = W0[16mb + i][k], k = 4s + q (FIN = 2D + 16 <= 24)
             float zc[6][3], a1[2][6];
 #pragma unroll
             for (int s4 = 0; s4 < 6; ++s4) {
                 const int k = 4 * s4 + q;
+                const int ke = (k >= 2 * D && k < FIN) ? k - 2 * D : 0, kw = k < FIN ? k : 0;
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
-                    zc[s4][c] = (k >= 2 * D && k < FIN) ? P.field_emb[c * 16 + (k - 2 * D)] : 0.0f;
+                    zc[s4][c] = (4 * s4 + 3 >= 2 * D && 4 * s4 < FIN) ? p_emb[c * 16 + ke] : 0.0f;
 #pragma unroll
-                for (int mb = 0; mb < 2; ++mb) a1[mb][s4] = k < FIN ? P.field_w0[(16 * mb + i) * FIN + k] : 0.0f;
+                for (int mb = 0; mb < 2; ++mb) a1[mb][s4] = 4 * s4 < FIN ? p_w0[(16 * mb + i) * FIN + kw] : 0.0f;
             }
             f32x4 w2f[2][2], w4f[2], acc1[2], acc2[2];
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb) {
-                acc1[mb] = ld4(P.field_b0 + 16 * mb + 4 * q);
-                acc2[mb] = ld4(P.field_b2 + 16 * mb + 4 * q);
+                acc1[mb] = ld4(p_b0 + 16 * mb + 4 * q);
+                acc2[mb] = ld4(p_b2 + 16 * mb + 4 * q);
 #pragma unroll
-                for (int a = 0; a < 2; ++a) w2f[mb][a] = ld4(P.field_w2 + (16 * mb + i) * 32 + 16 * a + 4 * q);
+                for (int a = 0; a < 2; ++a) w2f[mb][a] = ld4(p_w2 + (16 * mb + i) * 32 + 16 * a + 4 * q);
             }
 #pragma unroll
-            for (int a = 0; a < 2; ++a)
-                w4f[a] = i < D ? ld4(P.field_w4 + i * 32 + 16 * a + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int a = 0; a < 2; ++a) w4f[a] = ld4(p_w4 + (i < D ? i : 0) * 32 + 16 * a + 4 * q);
             f32x4 acc3 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc3[r] = (4 * q + r < D) ? P.field_b4[4 * q + r] : 0.0f;
+            for (int r = 0; r < 4; ++r) acc3[r] = r < D ? p_b4[4 * q + r < D ? 4 * q + r : 0] : 0.0f;
             // x0 operands: A = W_res[16mb + i][D + k], k = 4s + q < 2D (the first D inputs of rel_feat are zero)
             float ar[4][2];
             f32x4 acc0[4];
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) {
-                acc0[mb] = ld4(P.l1_res_b + 16 * mb + 4 * q);
+                acc0[mb] = ld4(p_rb + 16 * mb + 4 * q);
 #pragma unroll
                 for (int s4 = 0; s4 < 2; ++s4)
-                    ar[mb][s4] = 4 * s4 + q < 2 * D ? P.l1_res_w[(16 * mb + i) * 3 * D + D + 4 * s4 + q] : 0.0f;
+                    ar[mb][s4] = 4 * s4 < 2 * D ? p_rw[(16 * mb + i) * 3 * D + D + (4 * s4 + q < 2 * D ? 4 * s4 + q : 0)] : 0.0f;
             }
             index_stage_a();                                    // behind this wave's own inputs (in-order returns: they do not wait for it)
+            // The one wait of the block, in the form the compiler's wait-count pass sees (simm16 of vmcnt(0) alone): it places none
+            // of its own in front of the MFMAs.
+            // Nothing is scheduled across the wait (sched_barrier), and every loaded value is named right behind it (empty
+            // statements), the ones used last first: the scheduler would otherwise sink the loads whose values the first
+            // MFMAs do not need below the wait, and the wait-count pass would add waits of its own for them.
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+            __builtin_amdgcn_sched_barrier(0);
+            auto landed = [](auto v) { asm volatile("" :: "v"(v)); };
+            auto landed4 = [](const int4& v) { asm volatile("" :: "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); };
+            landed4(f_e); landed4(nr_rec);
+#pragma unroll
+            for (int r = 0; r < ROUNDS; ++r) landed4(t_e[r]);
+#pragma unroll
+            for (int d = 0; d < D; ++d) { landed(pz[d]); landed(vz[d]); landed(ef[d]); }
+            landed(ch);
+#pragma unroll
+            for (int s4 = 0; s4 < 6; ++s4) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    if (4 * s4 + 3 >= 2 * D && 4 * s4 < FIN) landed(zc[s4][c]);
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb)
+                    if (4 * s4 < FIN) landed(a1[mb][s4]);
+            }
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb) { landed(acc1[mb]); landed(acc2[mb]); landed(w2f[mb][0]); landed(w2f[mb][1]); }
+            landed(w4f[0]); landed(w4f[1]);
+#pragma unroll
+            for (int r = 0; r < D; ++r) landed(acc3[r]);
+#pragma unroll
+            for (int mb = 0; mb < 4; ++mb) {
+                landed(acc0[mb]);
+#pragma unroll
+                for (int s4 = 0; s4 < 2; ++s4)
+                    if (4 * s4 < 2 * D) landed(ar[mb][s4]);
+            }
+#pragma unroll
+            for (int s4 = 0; s4 < 6; ++s4) {
+                const int k = 4 * s4 + q;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) zc[s4][c] = (k >= 2 * D && k < FIN) ? zc[s4][c] : 0.0f;
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb) a1[mb][s4] = k < FIN ? a1[mb][s4] : 0.0f;
+            }
+#pragma unroll
+            for (int a = 0; a < 2; ++a) w4f[a] = i < D ? w4f[a] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc3[r] = (4 * q + r < D) ? acc3[r] : 0.0f;
+#pragma unroll
+            for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+                for (int s4 = 0; s4 < 2; ++s4) ar[mb][s4] = 4 * s4 + q < 2 * D ? ar[mb][s4] : 0.0f;
+            index_select();
             long ci = (long)(ch + 1.0f);                        // charge_to_index: (q + 1).long(), aether.py:127-129
             ci = ci < 0 ? 0 : (ci > 2 ? 2 : ci);
 #pragma unroll
@@ -563,6 +656,8 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             f32x4 hh[2];
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb) hh[mb] = silu4(acc1[mb]);
+            // the edge record is opaque up to here: the attribute loads, whose addresses need it, stay behind the layer-1 MFMAs
+            asm volatile("" : "+v"(f_e.y), "+v"(f_e.z), "+v"(f_e.w) : "v"(hh[0][0]));
             f_ea = index_stage_b();                                    // (the records are back by now; measured: asked for earlier, nothing gained)
 #pragma unroll
             for (int a = 0; a < 2; ++a)
@@ -581,7 +676,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                 float f[D], R[D][D], cv[D], cf[D];
 #pragma unroll
                 for (int d = 0; d < D; ++d)
-                    f[d] = dbg.step.ext_field ? dbg.step.ext_field[(int64_t)(vb + node) * D + d] : acc3[d];
+                    f[d] = dbg.step.ext_field ? ef[d] : acc3[d];       // (live: g = vb + node)
                 node_frame<D>(vz, f, R, cv, cf);
                 float* ni = ninfo + node * 24;
 #pragma unroll
@@ -616,6 +711,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             }
         } else {
             index_stage_a();
+            index_select();
             f_ea = index_stage_b();
             // rows of unused node slots are zero
             for (int idx = tid - 64 * vtiles; idx < (FUSED_MAX_NODES - n) * (H / 4); idx += THREADS - 64 * vtiles)
@@ -661,7 +757,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                             const float df = njl[NI::P + d] - nrl[NI::P + d];
                             d2 += df * df;
                         }
-                        eal[0] = r0 == 0 ? f_ea[0] : dbg.step.qattr[ks] * dbg.step.qattr[kr];
+                        eal[0] = r0 == 0 ? f_ea[0] * f_ea[1] : dbg.step.qattr[ks] * dbg.step.qattr[kr];
                         eal[1] = sqrtf(d2);
                     } else if (r0 == 0) {
                         eal[0] = f_ea[0]; eal[1] = f_ea[1];
@@ -711,24 +807,28 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     }
     FUSED_STAMP(3);
 
-    // node-sum ownership (step 1 of the node phase): thread -> (node slot, 4 columns).  The in-edge
-    // sum of a node arrives as per-(receiver, tile) partial rows `part[node + tile]`.
-    // Two runs of tiles per node (own senders / partner's senders, see FusedWG); the second run's rows are offset by n.
-    const int aslot = (tid >> 4) & (FUSED_MAX_NODES - 1), ac4 = (tid & 15) * 4;
-    int at0 = 0, at1 = 0, bt0 = 0, bt1 = 0;
+    // node sums (step 1 of the node phase; aslot, ac4 above): the in-edge sum of a node arrives as per-(receiver, tile)
+    // partial rows `part[node + tile]`.  Two runs of tiles per node (own senders / partner's senders, see FusedWG); the
+    // second run's rows are offset by n.  The record arrived during P1 (index_stage_a).
+    // The four tile bounds (each below 2 * 32 + 16 partial rows) travel through the layers as bytes of one register.
+    unsigned arange = 0;
     float adeg = 1.0f;
     if (aslot < n) {
-        const int4 nr = *reinterpret_cast<const int4*>(nrange + 4 * (int64_t)(nb + aslot));
-        at0 = nr.x >> 4;
-        at1 = nr.y > nr.x ? ((nr.y - 1) >> 4) + 1 : at0;
-        bt0 = (nr.z >> 4) + n;
-        bt1 = nr.w > nr.z ? ((nr.w - 1) >> 4) + 1 + n : bt0;
+        const int4 nr = nr_rec;
+        const int at0 = nr.x >> 4;
+        const int at1 = nr.y > nr.x ? ((nr.y - 1) >> 4) + 1 : at0;
+        const int bt0 = (nr.z >> 4) + n;
+        const int bt1 = nr.w > nr.z ? ((nr.w - 1) >> 4) + 1 + n : bt0;
+        arange = (unsigned)at0 | (unsigned)at1 << 8 | (unsigned)bt0 << 16 | (unsigned)bt1 << 24;
         const int deg = (nr.y - nr.x) + (nr.w - nr.z);
         adeg = (float)(deg > 1 ? deg : 1);
     }
 
     // next layer's W_s / W_r fragments (after layer 4: out_w0 / out_w3): fp16 x 2 pieces of the wave's row block, k blocks 0, 1
     f16x8 wsh[2], wsl[2], wrh[2], wrl[2];
+    // the node phase's fragments come by buffer loads (issue_loads): descriptor of the whole image set, the lane's 16 bytes
+    const auto wimg_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dbg.wimg), 0, FUSED_WIMG_SET * 4, 0x00020000);
+    const int lane16 = lane * 16;
 #pragma unroll 1
     for (int layer = 1; layer <= 4; ++layer) {
         // ------------------------------------------------------------ edge tiles (locs.py:227-238)
@@ -757,22 +857,46 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         // layer 4 has no next edge layer: wsv / wrv carry the out-MLP fragments (out_w0, out_w3) instead
         // part 1: W3; 2, 3: W4 halves; 4: W_s / W_r.  A wave spreads the parts over
         // its last tile (a burst of ~20 loads per wave blocks at issue until the L2 returns drain).
+        // No part waits for an earlier one: every fragment is a buffer load whose address is the image set's descriptor, the
+        // wave-uniform block offset in a scalar register and ONE lane-offset register shared by all of them.  (As
+        // global loads from a pointer each fragment had a 64-bit address pair of its own, which the compiler allocated
+        // in the destination registers of fragments still in flight -- a vmcnt(0) in front of every part.)
+        auto frag = [&](int block_bytes, int kb) -> f16x8 {
+            return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(wimg_rsrc, lane16, block_bytes + kb * 1024, 0));
+        };
+        // term 0 / term 1 (hi / lo pieces) of row block mb of a <MBN, KBN> image: k blocks of 64 fragments, 1 KiB each
+        auto load_frags = [&](int which, int mb, int MBN, int KBN, int kb0, int nkb, f16x8* wh, f16x8* wl) {
+            // The three-tile KEEP kernel sits at the register ceiling: it keeps the loads through a pointer.  Their waits
+            // are what lets a part's address pair live in registers of fragments that have landed; without them the
+            // kernel spills 16 bytes instead of 12.
+            if constexpr (ROUNDS == 3 && KEEP) {
+                const f16x8* w = reinterpret_cast<const f16x8*>(dbg.wimg + fused_nimg_offset(layer, which)) +
+                                 __builtin_amdgcn_readfirstlane(mb) * (KBN * 64);
+#pragma unroll
+                for (int kb = kb0; kb < kb0 + nkb; ++kb) {
+                    wh[kb] = w[kb * 64 + lane];
+                    wl[kb] = w[MBN * KBN * 64 + kb * 64 + lane];
+                }
+                return;
+            }
+            // (the layer's offset is opaque: hoisted out of the layer loop, the block offsets of all parts occupy scalar
+            // registers through the tiles, and their spills vector registers)
+            int lbytes = (layer - 1) * (FUSED_NIMG_LAYER * 4);
+            asm volatile("" : "+s"(lbytes));
+            const int blk = fused_nimg_offset(1, which) * 4 + lbytes + __builtin_amdgcn_readfirstlane(mb) * (KBN * 1024);
+#pragma unroll
+            for (int kb = kb0; kb < kb0 + nkb; ++kb) {
+                wh[kb] = frag(blk, kb);
+                wl[kb] = frag(blk + MBN * KBN * 1024, kb);
+            }
+        };
         auto issue_loads = [&](int part) {
             // (round 4: fragments of the prepared fp16 x 2 images, fused_nimg_offset -- same bytes per weight as fp32)
-            if (part == 1 && act3) load_split_frags<8, 2>(dbg.wimg + fused_nimg_offset(layer, 0), mb2, lane, w3h, w3l);
-            if ((part == 2 || part == 3) && do3) {
-                const f16x8* w = reinterpret_cast<const f16x8*>(dbg.wimg + fused_nimg_offset(layer, 1)) +
-                                 __builtin_amdgcn_readfirstlane(mb3) * (4 * 64);
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    const int kb = 2 * (part - 2) + kk;
-                    w4h[kb] = w[kb * 64 + lane];
-                    w4l[kb] = w[4 * 4 * 64 + kb * 64 + lane];
-                }
-            }
+            if (part == 1 && act3) load_frags(0, mb2, 8, 2, 0, 2, w3h, w3l);
+            if ((part == 2 || part == 3) && do3) load_frags(1, mb3, 4, 4, 2 * (part - 2), 2, w4h, w4l);
             if (part == 4 && (layer < 4 ? true : act3)) {
-                if (layer == 4 || do_s) load_split_frags<4, 2>(dbg.wimg + fused_nimg_offset(layer, 2), mb3, lane, wsh, wsl);
-                if (layer == 4 || do_r) load_split_frags<4, 2>(dbg.wimg + fused_nimg_offset(layer, 3), mb3, lane, wrh, wrl);
+                if (layer == 4 || do_s) load_frags(2, mb3, 4, 2, 0, 2, wsh, wsl);
+                if (layer == 4 || do_r) load_frags(3, mb3, 4, 2, 0, 2, wrh, wrl);
             }
         };
         // Split mode, layers 2-4: the partner workgroup's P_s rows are in flight when the edge phase starts.  The
@@ -952,6 +1076,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         // step 1: n = x_prev + (sum of the node's partial rows, in tile order) / max(deg, 1)
         if (tid < FUSED_MAX_NODES * 16) {
             f32x4 sum = f32x4{0.f, 0.f, 0.f, 0.f};
+            const int at0 = arange & 0xFF, at1 = (arange >> 8) & 0xFF, bt0 = (arange >> 16) & 0xFF, bt1 = arange >> 24;
             for (int t = at0; t < at1; ++t) sum += ld4(part + (aslot + t) * LDW + ac4);
             for (int t = bt0; t < bt1; ++t) sum += ld4(part + (aslot + t) * LDW + ac4);
             const f32x4 nv = ld4(xbuf + aslot * LDW + ac4) + sum / adeg;
