@@ -226,6 +226,7 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 constexpr int64_t FUSED_TABLE_MAX_EDGES = 4 << 20;
 int g_fused_split = 1;        // aether_set_option("fused_split", 0|1): two workgroups per group when CUs are idle
+int g_fused_waves12 = 1;     // aether_set_option("fused_waves12", 0|1): 12-wave k_fused for one-node-tile workgroups of 9-12 edge tiles (inference)
 int g_graph_build = 1;       // aether_set_option("graph_build", 0|1): 1 aether_graph_build_counting counts, 0 it forwards to aether_graph_build
 constexpr int FUSED_PAIR_STRIDE = 8;   // distance of the two workgroups of a split group (8: both on one XCD -- workgroup b
                                        // runs on XCD b % 8 -- 47.25 -> 46.56 us per launch at cfg2; a placement hint only:
@@ -494,7 +495,12 @@ int fused_impl(const AetherParams& P, int64_t Nn, int64_t E, const AetherGraphIn
               : fused_launch<D, NWV, R, false>(P, x, vel, charges, ea, gp(G.perm), gp(G.send_s),      \
                                                gp(G.recv_s), gp(G.rowptr), wgd, trec,                 \
                                                reinterpret_cast<const int4*>(graph + G.ledge), gp(G.nrange), info.n_groups, dbg, out, st)
-    if (tiles <= 8) { AETHER_FUSED_CASE(8, 1); }
+    // 9-12 tiles and one node tile in every workgroup (every split N = 17..20 group, unsplit groups of 12-14 nodes): twelve
+    // waves with one tile each instead of eight of which four run two (fused.h); inference only
+    if (g_fused_waves12 && !keep && tiles >= 9 && tiles <= 12 && info.max_group_nodes <= 16)
+        rc = fused_launch<D, 12, 1, false>(P, x, vel, charges, ea, gp(G.perm), gp(G.send_s), gp(G.recv_s), gp(G.rowptr), wgd, trec,
+                                           reinterpret_cast<const int4*>(graph + G.ledge), gp(G.nrange), info.n_groups, dbg, out, st);
+    else if (tiles <= 8) { AETHER_FUSED_CASE(8, 1); }
     else if (tiles <= 16) { AETHER_FUSED_CASE(8, 2); }
     else { AETHER_FUSED_CASE(8, 3); }
 #undef AETHER_FUSED_CASE
@@ -989,6 +995,11 @@ int aether_set_option(const char* name, int value) {
     if (!name) return fail(AETHER_EINVAL, "set_option: null name");
     if (!strcmp(name, "fused_split")) {      // takes effect at the next aether_graph_build
         g_fused_split = value != 0;
+        return AETHER_OK;
+    }
+    if (!strcmp(name, "fused_waves12")) {    // read at every launch
+        if (value != 0 && value != 1) return fail(AETHER_EINVAL, "set_option: fused_waves12 must be 0 or 1");
+        g_fused_waves12 = value;
         return AETHER_OK;
     }
     if (!strcmp(name, "graph_build")) {      // read by aether_graph_build_counting

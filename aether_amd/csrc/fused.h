@@ -20,6 +20,12 @@
 //   * node-level GEMMs are split along their output rows over the waves; their weights come from L2
 //     in MFMA fragment shape (each is used once per group and layer), all issued before the barrier
 //     that ends the edge phase.
+//   * waves per workgroup: 8, a wave owning up to ROUNDS edge tiles per layer (tile = NW * round + wave) -- or, for
+//     inference on workgroups of 9-12 tiles and one node tile (every half of a split N = 17..20 graph), 12 with one
+//     tile each (k_fused<D, 12, 1, false>): three waves per SIMD hide each other's LDS round trips and MFMA / SiLU
+//     chains, where four of eight waves ran a second tile alone on their SIMD.  Same tiles, records, partial rows and
+//     hand-off; the node phase's row blocks are dealt to the twelve waves (wf_h / wf_l below), the arithmetic is the
+//     8-wave kernel's and the outputs are bit-identical.
 // References: see common.h / streamed.h; the arithmetic per stage is identical to the streamed path.
 #pragma once
 #include "common.h"
@@ -386,7 +392,11 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     using L = FusedLds<NW, ROUNDS>;
     constexpr int THREADS = NW * 64;
     constexpr int FIN = 2 * D + 16;
-    static_assert(NW == 8, "waves 0-7 run the node phase (12 and 16 waves per workgroup were measured: DESIGN.md 4.1)");
+    // NW == 12 (ROUNDS == 1, inference): twelve waves with one edge tile each, for workgroups of 9-12 tiles and one node
+    // tile (n <= 16: the host dispatches it only then); the node phase's roles are spread over the twelve waves and
+    // share one set of fragment registers (wf_h / wf_l below, DESIGN.md 4.1 "Wave roles in the node phase").
+    static_assert(NW == 8 || NW == 12, "waves 0-7 run the node phase; NW == 12 adds four waves that run step 3 (DESIGN.md 4.1)");
+    static_assert(NW == 8 || (ROUNDS == 1 && !KEEP), "the 12-wave kernel owns one tile per wave and saves nothing for the backward");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* wA = smem + L::WA;
     float* wB = smem + L::WB;
@@ -813,6 +823,15 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     // The four tile bounds (each below 2 * 32 + 16 partial rows) travel through the layers as bytes of one register.
     unsigned arange = 0;
     float adeg = 1.0f;
+    if constexpr (NW == 12) {
+        // The edge attributes and the nrange record are read in exec-masked regions only (P2: lanes that build an edge;
+        // below: threads that own a node slot).  On the path around such a region the compiler's wait-count pass carries
+        // the loads as still in flight into the layer loop, and the first instruction there that reuses one of their
+        // registers gets a vmcnt(0) -- behind part 1 of the node phase's prefetch, in every tile of every layer (1,800 of a
+        // tile's 7,600 cycles in the first stamped build).  Naming the values here puts that wait in front of the loop,
+        // where they have long landed.
+        asm volatile("" :: "v"(f_ea[0]), "v"(f_ea[1]), "v"(nr_rec.x), "v"(nr_rec.y), "v"(nr_rec.z), "v"(nr_rec.w));
+    }
     if (aslot < n) {
         const int4 nr = nr_rec;
         const int at0 = nr.x >> 4;
@@ -826,6 +845,11 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
 
     // next layer's W_s / W_r fragments (after layer 4: out_w0 / out_w3): fp16 x 2 pieces of the wave's row block, k blocks 0, 1
     f16x8 wsh[2], wsl[2], wrh[2], wrl[2];
+    // NW == 12: ONE set of four hi and four lo fragments per wave for all its roles (registers are allocated statically,
+    // whatever the wave's run-time role).  Waves 0-7: slots 0, 1 = W3 row block `wave`; slots 2, 3 = the next layer's
+    // W_s (waves 0-3) or W_r (waves 4-7), row block wave & 3 (layer 4: out_w0 / out_w3).  Waves 8-11: slots 0-3 = the
+    // four k blocks of W4 row block wave & 3.  w3* / w4* / ws* / wr* are not used then.
+    f16x8 wf_h[4], wf_l[4];
     // the node phase's fragments come by buffer loads (issue_loads): descriptor of the whole image set, the lane's 16 bytes
     const auto wimg_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dbg.wimg), 0, FUSED_WIMG_SET * 4, 0x00020000);
     const int lane16 = lane * 16;
@@ -843,10 +867,10 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         // One node tile (split mode, small groups): step 3 runs on waves 4-7, which own at most one edge tile per layer,
         // so a two-tile wave (0-3) never asks for the W4 fragments nor carries them through its last tile; in step 4 waves
         // 0-3 compute P_s and waves 4-7 P_r, all on tile 0.  Two node tiles: wave -> (mb3, tn3) in steps 3 and 4.
-        const bool one_tile = n <= 16;
+        const bool one_tile = NW == 12 ? true : n <= 16;
         const int tn4 = one_tile ? 0 : tn3;
         const int tn3s = tn4;
-        const bool do3 = act3 && (one_tile ? wave >= 4 : 16 * tn3 < n);
+        const bool do3 = NW == 12 ? wave >= 8 : act3 && (one_tile ? wave >= 4 : 16 * tn3 < n);   // (NW == 12: mb3 = wave & 3, tn3 = 0)
         const bool do_s = act3 && (one_tile ? wave < 4 : true);
         const bool do_r = act3 && (one_tile ? wave >= 4 : true);
         // Every register load of the node phase is issued BEFORE the end of the wave's last edge tile, so that
@@ -891,12 +915,42 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             }
         };
         auto issue_loads = [&](int part) {
+            if constexpr (NW == 12) {
+                // The wave's role picks the image and the row block by scalar selects -- no branch on the role around a
+                // load; the fragments, their k order and the hi / lo pieces are those of load_frags.  Every wave issues
+                // four fragments with part 1 (slots 0, 1) and four with part 3 (slots 2, 3); parts 2 and 4 are empty.
+                const int wv = __builtin_amdgcn_readfirstlane(wave);
+                int lbytes = (layer - 1) * (FUSED_NIMG_LAYER * 4);
+                asm volatile("" : "+s"(lbytes));
+                const bool w4 = wv >= 8;
+                // slots 0, 1: W3 <8, 2> row block wv, or k blocks 0, 1 of W4 <4, 4> row block wv & 3 (lo pieces 16 KiB behind
+                // the hi pieces in both images); slots 2, 3: k blocks 2, 3 of the same W4 row block, or W_s / W_r <4, 2>
+                // row block wv & 3 (lo pieces 8 KiB behind)
+                const int blk01 = lbytes + (w4 ? fused_nimg_offset(1, 1) * 4 + (wv & 3) * 4096 : fused_nimg_offset(1, 0) * 4 + wv * 2048);
+                const int blk23 = w4 ? blk01 + 2048 : lbytes + (wv < 4 ? fused_nimg_offset(1, 2) : fused_nimg_offset(1, 3)) * 4 + (wv & 3) * 2048;
+                const int lo23 = w4 ? 16 * 1024 : 8 * 1024;
+                if (part == 1) {
+#pragma unroll
+                    for (int kb = 0; kb < 2; ++kb) {
+                        wf_h[kb] = frag(blk01, kb);
+                        wf_l[kb] = frag(blk01 + 16 * 1024, kb);
+                    }
+                }
+                if (part == 3) {
+#pragma unroll
+                    for (int kb = 0; kb < 2; ++kb) {
+                        wf_h[2 + kb] = frag(blk23, kb);
+                        wf_l[2 + kb] = frag(blk23 + lo23, kb);
+                    }
+                }
+            } else {
             // (round 4: fragments of the prepared fp16 x 2 images, fused_nimg_offset -- same bytes per weight as fp32)
             if (part == 1 && act3) load_frags(0, mb2, 8, 2, 0, 2, w3h, w3l);
             if ((part == 2 || part == 3) && do3) load_frags(1, mb3, 4, 4, 2 * (part - 2), 2, w4h, w4l);
             if (part == 4 && (layer < 4 ? true : act3)) {
                 if (layer == 4 || do_s) load_frags(2, mb3, 4, 2, 0, 2, wsh, wsl);
                 if (layer == 4 || do_r) load_frags(3, mb3, 4, 2, 0, 2, wrh, wrl);
+            }
             }
         };
         // Split mode, layers 2-4: the partner workgroup's P_s rows are in flight when the edge phase starts.  The
@@ -950,6 +1004,42 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             const int np = nv - n;                              // partner rows = visible slots outside [off, off + n)
             typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
             const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(dbg.ps[layer - 2] + (int64_t)vb * H, 0, nv * H * 4, 0x00020000);
+            FUSED_WSTAMP(layer, 0, 6);
+            if constexpr (NW == 12) {
+                // Seven of the twelve tiles wait for these rows (one round: nothing else to run meanwhile), so the copy is
+                // on the edge phase's critical path.  Four loads in flight per lane and ONE wait per 256 pieces (16 rows)
+                // instead of a load, a wait and a store per 64 pieces: the flagship's 10 rows took three dependent L2
+                // round trips.  Every load is unconditional on a clamped piece (piece 0 exists: np >= 1); the same
+                // loads of the same bytes, the same stores.
+                for (int base = 0; base < np * 16; base += 256) {
+                    u32x4 v[4];
+                    int dst[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int idx = base + 64 * j + lane, idc = idx < np * 16 ? idx : 0;
+                        int slot = idc >> 4;
+                        if (slot >= off) slot += n;
+                        const int c = (idc & 15) * 4;
+                        v[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (slot * H + c) * 4, 0, 16);   // aux 16 = sc1
+                        dst[j] = idx < np * 16 ? slot * LDW + c : -1;
+                    }
+                    // one wait that the compiler's wait-count pass sees, nothing scheduled across it, every loaded value
+                    // named behind it (as the field wave's load block): left alone, the compiler sinks a load whose value
+                    // only a predicated store reads into that store's exec-masked region, with a wait of its own
+                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_s_waitcnt(0x0F70);
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) asm volatile("" :: "v"(v[j]));
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        f32x4 f;
+#pragma unroll
+                        for (int r4 = 0; r4 < 4; ++r4) f[r4] = __uint_as_float(v[j][r4]);
+                        if (dst[j] >= 0) st4(psb + dst[j], f);
+                    }
+                }
+            } else
             for (int idx = lane; idx < np * 16; idx += 64) {
                 int slot = idx >> 4;
                 if (slot >= off) slot += n;
@@ -963,6 +1053,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // rows are in LDS before the word says so
             __builtin_amdgcn_wave_barrier();
             if (lane == 0) arrived[0] = layer;
+            FUSED_WSTAMP(layer, 0, 7);
         };
         auto wait_partner_rows = [&]() {
             while (__builtin_amdgcn_readfirstlane(arrived[0]) < layer) __builtin_amdgcn_s_sleep(1);
@@ -1099,7 +1190,13 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                     f32x4 nv[4];
 #pragma unroll
                     for (int a = 0; a < 4; ++a) nv[a] = ld4(nbuf + (16 * tn + i) * LDW + 16 * a + 4 * q);
-                    const f32x4 acc = gemm_split_regs<2>(w3h, w3l, nv, bv);
+                    f32x4 acc;
+                    if constexpr (NW == 12) {
+                        const f16x8 wh2[2] = {wf_h[0], wf_h[1]}, wl2[2] = {wf_l[0], wf_l[1]};
+                        acc = gemm_split_regs<2>(wh2, wl2, nv, bv);
+                    } else {
+                        acc = gemm_split_regs<2>(w3h, w3l, nv, bv);
+                    }
                     st4(ubuf + (16 * tn + i) * LDU + 16 * mb2 + 4 * q, silu4(acc));
                 }
             }
@@ -1116,8 +1213,13 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                 f32x4 uv[4];
 #pragma unroll
                 for (int a = 0; a < 4; ++a) uv[a] = ld4(ubuf + (16 * tn3s + i) * LDU + 16 * (4 * hk + a) + 4 * q);
-                const f16x8 wh2[2] = {w4h[2 * hk], w4h[2 * hk + 1]}, wl2[2] = {w4l[2 * hk], w4l[2 * hk + 1]};
-                acc = gemm_split_regs<2>(wh2, wl2, uv, acc);
+                if constexpr (NW == 12) {
+                    const f16x8 wh2[2] = {wf_h[2 * hk], wf_h[2 * hk + 1]}, wl2[2] = {wf_l[2 * hk], wf_l[2 * hk + 1]};
+                    acc = gemm_split_regs<2>(wh2, wl2, uv, acc);
+                } else {
+                    const f16x8 wh2[2] = {w4h[2 * hk], w4h[2 * hk + 1]}, wl2[2] = {w4l[2 * hk], w4l[2 * hk + 1]};
+                    acc = gemm_split_regs<2>(wh2, wl2, uv, acc);
+                }
             }
             acc += ld4(nbuf + (16 * tn3s + i) * LDW + 16 * mb3 + 4 * q);
             st4(xbuf + (16 * tn3s + i) * LDW + 16 * mb3 + 4 * q, acc);
@@ -1133,7 +1235,13 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
 #pragma unroll
                 for (int a = 0; a < 4; ++a) xv[a] = ld4(xbuf + (16 * tn4 + i) * LDW + 16 * a + 4 * q);
                 if (do_s) {
-                    const f32x4 accs = gemm_split_regs<2>(wsh, wsl, xv, f32x4{0.f, 0.f, 0.f, 0.f});
+                    f32x4 accs;
+                    if constexpr (NW == 12) {
+                        const f16x8 wh2[2] = {wf_h[2], wf_h[3]}, wl2[2] = {wf_l[2], wf_l[3]};
+                        accs = gemm_split_regs<2>(wh2, wl2, xv, f32x4{0.f, 0.f, 0.f, 0.f});
+                    } else {
+                        accs = gemm_split_regs<2>(wsh, wsl, xv, f32x4{0.f, 0.f, 0.f, 0.f});
+                    }
                     if (16 * tn4 + i < n) {      // sender rows live in the visible numbering
                         st4(psb + (off + 16 * tn4 + i) * LDW + 16 * mb3 + 4 * q, accs);
                         float* gps = dbg.ps[layer - 1] + (int64_t)(nb + 16 * tn4 + i) * H + 16 * mb3 + 4 * q;
@@ -1153,7 +1261,13 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                     }
                 }
                 if (do_r) {
-                    const f32x4 accr = gemm_split_regs<2>(wrh, wrl, xv, ld4(cb + CB_B1N + 16 * mb3 + 4 * q));
+                    f32x4 accr;
+                    if constexpr (NW == 12) {
+                        const f16x8 wh2[2] = {wf_h[2], wf_h[3]}, wl2[2] = {wf_l[2], wf_l[3]};
+                        accr = gemm_split_regs<2>(wh2, wl2, xv, ld4(cb + CB_B1N + 16 * mb3 + 4 * q));
+                    } else {
+                        accr = gemm_split_regs<2>(wrh, wrl, xv, ld4(cb + CB_B1N + 16 * mb3 + 4 * q));
+                    }
                     st4(prb + (16 * tn4 + i) * LDW + 16 * mb3 + 4 * q, accr);
                     if (keep && 16 * tn4 + i < n)
                         st4(dbg.pr[layer - 1] + (int64_t)(nb + 16 * tn4 + i) * H + 16 * mb3 + 4 * q, accr);
@@ -1180,14 +1294,23 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     {
         float* o1 = smem + L::OBUF1;
         float* o2 = smem + L::OBUF2;
-        const int mb = wave & 3, tn = (wave >> 2) & 1;
+        const int mb = wave & 3, tn = NW == 12 ? 0 : (wave >> 2) & 1;
         const bool act = wave < 8 && 16 * tn < n;
+        // NW == 12 (one node tile): stage 1 on waves 0-3, which hold out_w0, stage 2 on waves 4-7, which hold out_w3
+        const bool act1 = NW == 12 ? wave < 4 && n > 0 : act;
+        const bool act2 = NW == 12 ? wave >= 4 && wave < 8 && n > 0 : act;
         const float* cb = cblk;                          // slot 0: block 4 (out_b0, out_b3, out_b6, out_w6)
-        if (act) {
+        if (act1) {
             f32x4 xv[4];
 #pragma unroll
             for (int a = 0; a < 4; ++a) xv[a] = ld4(xbuf + (16 * tn + i) * LDW + 16 * a + 4 * q);
-            const f32x4 acc = gemm_split_regs<2>(wsh, wsl, xv, ld4(cb + CB_B1N + 16 * mb + 4 * q));
+            f32x4 acc;
+            if constexpr (NW == 12) {
+                const f16x8 wh2[2] = {wf_h[2], wf_h[3]}, wl2[2] = {wf_l[2], wf_l[3]};
+                acc = gemm_split_regs<2>(wh2, wl2, xv, ld4(cb + CB_B1N + 16 * mb + 4 * q));
+            } else {
+                acc = gemm_split_regs<2>(wsh, wsl, xv, ld4(cb + CB_B1N + 16 * mb + 4 * q));
+            }
             f32x4 v = silu4(acc);
             if constexpr (KEEP) {
                 if (dbg.step.drop1 != nullptr && 16 * tn + i < n)
@@ -1199,11 +1322,17 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             if (blockIdx.x == 0 && tid == 0 && dbg.step.dropword != nullptr) *dbg.step.dropword = dbg.step.drop1 != nullptr ? 1 : 0;
         }
         lds_barrier();
-        if (act) {
+        if (act2) {
             f32x4 xv[4];
 #pragma unroll
             for (int a = 0; a < 4; ++a) xv[a] = ld4(o1 + (16 * tn + i) * LDW + 16 * a + 4 * q);
-            const f32x4 acc = gemm_split_regs<2>(wrh, wrl, xv, ld4(cb + CB_OB3 + 16 * mb + 4 * q));
+            f32x4 acc;
+            if constexpr (NW == 12) {
+                const f16x8 wh2[2] = {wf_h[2], wf_h[3]}, wl2[2] = {wf_l[2], wf_l[3]};
+                acc = gemm_split_regs<2>(wh2, wl2, xv, ld4(cb + CB_OB3 + 16 * mb + 4 * q));
+            } else {
+                acc = gemm_split_regs<2>(wrh, wrl, xv, ld4(cb + CB_OB3 + 16 * mb + 4 * q));
+            }
             f32x4 v = silu4(acc);
             if constexpr (KEEP) {
                 if (dbg.step.drop2 != nullptr && 16 * tn + i < n)

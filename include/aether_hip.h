@@ -1050,7 +1050,10 @@ int aether_adamw_step(const AetherAdamWTensor* tensors, int n_tensors, float* st
 /*
  * Tuning knobs (process-wide; not thread-safe); any other name returns AETHER_EINVAL:
  * "fused_split" 0|1 (two workgroups per group when there are fewer groups than half the CUs; default 1; read by
- * aether_graph_build), "graph_build" 0|1 (aether_graph_build_counting: 1, the default, builds by counting; 0 forwards
+ * aether_graph_build), "fused_waves12" 0|1 (inference step of small-graph groups: when every workgroup has one node
+ * tile (<= 16 own nodes) and the largest has 9-12 edge tiles, run the fused kernel with twelve waves and one edge
+ * tile per wave instead of eight waves with up to two; same arithmetic, same bits; default 1; read at every
+ * launch), "graph_build" 0|1 (aether_graph_build_counting: 1, the default, builds by counting; 0 forwards
  * every call to the sorting aether_graph_build), "fused_backward" 0|1 (one-launch backward for small-graph groups; default 1, 0 sends them through
  * the layer-by-layer kernels), "outer_defer_max_edges" n (aether_backward keeps every layer's weight-gradient operands
  * and multiplies them in one launch when n_edges <= n, default 2^20; changes aether_workspace_bytes), "edge_acc"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic: where does k_fused spend its time?  Builds the stamped library variant, runs the
 headline workload and prints the median (over workgroups) time between phase stamps.
-Run on the GPU box:  python tools/fused_phases.py [--dims 2] [--batch 128] [--nodes 20]"""
+Run on the GPU box:  python tools/fused_phases.py [--dims 2] [--batch 128] [--nodes 20] [--lib STAMPED.so] [--opt name=value]"""
 import argparse, contextlib, io, os, sys
 import numpy as np
 import torch
@@ -11,8 +11,12 @@ from aether_amd import build as B, _lib
 ap = argparse.ArgumentParser()
 ap.add_argument("--dims", type=int, default=2); ap.add_argument("--batch", type=int, default=128)
 ap.add_argument("--nodes", type=int, default=20); ap.add_argument("--keep", action="store_true", help="time the save-for-backward variant")
+ap.add_argument("--lib", default=None, help="a stamped library built beforehand (build.build_diagnostic) instead of building one")
+ap.add_argument("--opt", action="append", default=[], help="name=value passed to aether_set_option (fused_waves12=0: the 8-wave kernel)")
 a = ap.parse_args()
-_lib.LIB_PATH = B.build_diagnostic()
+_lib.LIB_PATH = os.path.abspath(a.lib) if a.lib else B.build_diagnostic()
+for kv in a.opt:
+    _lib.check(_lib.load().aether_set_option(kv.split("=")[0].encode(), int(kv.split("=")[1])), "set_option")
 from aether_amd.nn.state2state.aether import Aether
 from aether_amd.synthetic import make_batch
 torch.manual_seed(1)
@@ -56,13 +60,17 @@ print(f"  shader clock during the kernel: {clk:.0f} MHz (s_memtime cycles / wall
 print("  layer-2 per-wave tile timeline, cycles since kernel entry (median over workgroups):")
 print("   wave round   start  wait rows  gemm1+silu1  gemm2+silu2+stage  sums   | total")
 sums = []
-for w in range(8):
+for w in range(12):            # 8 or 12 waves per workgroup (FUSED_WSTAMP: 24 slots per wave from slot 64, 64 + 24 * 12 <= FUSED_STAMPS)
     for r in range(3):
         v = med[64 + w * 24 + r * 8: 64 + w * 24 + r * 8 + 6]
         if v[5] == 0: continue
         d = [v[1] - v[0], v[2] - v[1], v[4] - v[2], v[5] - v[4]]      # stamps 0, 1, 2, 4 (tile parked, sums begin), 5
         sums.append(d[3])
         print(f"   {w:4d} {r:5d} {v[0]:8.0f} {d[0]:9.0f} {d[1]:12.0f} {d[2]:18.0f} {d[3]:6.0f}    | {v[5]-v[0]:6.0f}")
+for w in range(12):            # the wave that copies the partner's rows (split groups): slots 6, 7 of its first round
+    v = med[64 + w * 24: 64 + w * 24 + 8]
+    if v[6] > 0:
+        print(f"  partner-row receive on wave {w}: flag seen at {v[6]:.0f}, rows published at {v[7]:.0f} (copy {v[7]-v[6]:.0f} cycles)")
 if sums:
     print(f"  receiver sums per tile (wait for the parked tile, column reads, adds, stores): median {np.median(sums):.0f}, "
           f"min {min(sums):.0f}, max {max(sums):.0f} cycles over {len(sums)} tiles")
