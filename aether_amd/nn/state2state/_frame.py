@@ -355,6 +355,7 @@ class FrameModule(nn.Module):
         self._ws = None
         self._ws_bytes = {}
         self._last_ws = None
+        self._last_ws_keep = False        # was _last_ws written in the keep (training) layout? (debug_fetch)
         self._wimg_key = None             # (_ws_key, parameter versions) whose split weight images the workspace holds
         self._ws_key = None               # (workspace, shape, graph) of the last completed inference call
         self._rollout_train_ws, self._rollout_train_ws_token = None, None     # differentiable_rollout (_train_workspace)
@@ -517,6 +518,7 @@ class FrameModule(nn.Module):
         _lib.check(st, label)
         self._ws_key, self._wimg_key = pending
         self._last_ws = None if train and self.TRAIN_WS_PER_CALL else ws          # (debug_fetch reads it)
+        self._last_ws_keep = bool(flags & _lib.FLAG_KEEP_INTERMEDIATES)
         return out, ws, token
 
     def _backward(self, label, ps, gs, x, vel, charges, graph, ws, n_edges, grad_out, grad_field=None):
@@ -590,7 +592,7 @@ class FrameModule(nn.Module):
                                                     float(dt), flags, stream)
             _lib.check(st, "aether_rollout_dynamic_field")
         self._ws_key, self._wimg_key = pending
-        self._last_ws = ws
+        self._last_ws, self._last_ws_keep = ws, False
         return traj
 
     # -- training through the rollout ------------------------------------------------------
@@ -671,7 +673,33 @@ class FrameModule(nn.Module):
         return self._rollout_grad(x, vel, edges, charges, steps, dt)
 
     # -- test hooks -------------------------------------------------------------------
+    PER_LAYER = tuple(f"x{k}" for k in range(1, 5)) + tuple(f"e{k}" for k in range(1, 5)) + ("efeat",)
+
+    def _fetchable(self, name):
+        """Does the layout ``_last_ws`` was written with hold ``name`` where aether_debug_fetch_h looks for it?  The library
+        computes per-layer offsets from the training layout, whatever the workspace's.  At width 64 (WsLayout) the node
+        states and messages lie in the forward prefix both layouts share; the layer-1 features follow it and exist in the
+        training layout only.  Above 64 (WideLayout) the features and node states precede the first region whose size
+        depends on the layout; the messages follow it, and an inference workspace lets the layers share two of them.
+        This table restates ``WsLayout`` (csrc/aether_hip.hip) and ``WideLayout`` (csrc/wide_impl.inc) because the check has
+        to come before any library call; tests/test_gpu_buffer_contract.py holds it to them from outside: every tensor it
+        lets through after an inference-layout call is fetched and compared with the oracle.
+        Whether a tensor was WRITTEN is another matter and not decided here: a training forward without
+        FLAG_KEEP_INTERMEDIATES in ``flags`` runs with FLAG_BACKWARD_ONLY and leaves e4 unwritten in a keep-layout
+        workspace, and the fused inference kernel need not write its messages to memory at all."""
+        if name not in self.PER_LAYER or self._last_ws_keep:
+            return True
+        if self._kw == 64:
+            return name != "efeat"
+        return name[0] == "x" or name == "efeat"
+
     def debug_fetch(self, name, n_nodes, n_edges, cols):
+        if self._last_ws is None:
+            raise ValueError("debug_fetch: no forward has left a workspace on this module")
+        if not self._fetchable(name):
+            raise ValueError(f"debug_fetch({name!r}): the last call wrote its workspace in the inference layout, which does "
+                             "not hold this tensor where the training layout does; set FLAG_KEEP_INTERMEDIATES in "
+                             "``flags`` (or run a training forward) first")
         dev = next(self.parameters()).device
         rows = n_edges if name.startswith("e") else n_nodes
         dst = torch.empty(rows, cols, dtype=torch.float32, device=dev)

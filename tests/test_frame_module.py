@@ -165,3 +165,31 @@ def test_narrow_rollout_syncs_its_engine_without_autograd():
     with pytest.raises(_lib.AetherHipError, match="got a CPU tensor"):
         a.rollout(torch.zeros(4, 2), torch.zeros(4, 2), [torch.zeros(2, dtype=torch.long)] * 2, torch.zeros(4, 1), 1)
     assert seen == [False] and a._engine_key == key
+
+
+@pytest.mark.parametrize("H,keep,refused", [
+    (64, False, {"efeat"}), (64, True, set()), (20, False, {"efeat"}),
+    (128, False, {"e1", "e2", "e3", "e4"}), (128, True, set())])
+def test_debug_fetch_refuses_a_layout_that_does_not_hold_the_tensor(H, keep, refused, monkeypatch):
+    """aether_debug_fetch_h computes per-layer offsets from the training layout.  After a call that wrote the inference
+    layout, the tensors whose offset differs there (WsLayout: the layer-1 features, which follow the forward prefix;
+    WideLayout: the messages, which follow the first region sized by the layout) raise ValueError before any library call."""
+    m = quiet(Aether, 4, H, 0.0, 2)
+    eng = m.__dict__.get("_engine", m)
+    assert eng._last_ws is None and eng._last_ws_keep is False
+    with pytest.raises(ValueError, match="no forward has left a workspace"):
+        eng.debug_fetch("x1", 3, 6, eng._kw)
+    eng._last_ws, eng._last_ws_keep = torch.zeros(16, dtype=torch.uint8), keep
+
+    def no_library():
+        raise AssertionError("the library was reached")
+    monkeypatch.setattr(_lib, "load", no_library)
+    names = F.FrameModule.PER_LAYER + ("field", "R", "canon")
+    assert len(F.FrameModule.PER_LAYER) == 9
+    for name in names:
+        if name in refused:
+            with pytest.raises(ValueError, match="inference layout"):
+                eng.debug_fetch(name, 3, 6, eng._kw)
+        else:
+            with pytest.raises(AssertionError, match="the library was reached"):
+                eng.debug_fetch(name, 3, 6, eng._kw)

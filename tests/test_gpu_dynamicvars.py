@@ -507,13 +507,9 @@ def test_predict_future_captured_steps_equal_the_eager_loop():
 _SMALLEST = {}
 
 
-def _smallest_scenes():
-    """Two scenes of 5 object rows over 6 time steps, built once: scene 0 has [2, 2, 0, 5, 3, 2] present objects per step
-    (k = min(10, n - 1) = 1 with two edges and in_degree 1, an empty step in the middle, a full scene), scene 1
-    [3, 0, 2, 2, 5, 4]; burn-in 2 steps; MODEL_PARAMS as they are (hidden 128, K = 3).  Returns the model, the oracle's
-    prediction for scene 0 and the inputs on the device; nothing in it is modified by the tests."""
-    if _SMALLEST:
-        return _SMALLEST
+def _scene_model():
+    """AetherDynamicVars(MODEL_PARAMS) under torch.manual_seed(51), BatchNorm statistics perturbed, in eval mode on the CPU
+    -> (model, copy of its state dict, MODEL_PARAMS)."""
     from aether_amd.nn.dynamicvars.aether_dynamicvars import AetherDynamicVars
     import sys, os
     from conftest import REPO
@@ -522,11 +518,15 @@ def _smallest_scenes():
     torch.manual_seed(51)
     model = AetherDynamicVars(dict(MODEL_PARAMS), device=None).eval()
     perturb_bn_(model)
-    sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
-    model = model.cuda()
-    g = torch.Generator().manual_seed(52)
-    B, T, N, K = 2, 6, 5, MODEL_PARAMS["num_edge_types"]
-    counts = [[2, 2, 0, 5, 3, 2], [3, 0, 2, 2, 5, 4]]
+    return model, {k: v.detach().clone() for k, v in model.state_dict().items()}, MODEL_PARAMS
+
+
+def _scenes(counts, N, seed, K):
+    """len(counts) scenes of N object rows over len(counts[0]) time steps with ``counts[b][t]`` present objects (random rows),
+    kNN graphs (k = 10) in each scene's own numbering, burn-in 2 steps, Gumbel draws for K edge types: host tensors
+    inputs, masks, burn, node_inds[b][t], graph_info[b][t] = (send, recv, edge2node), uniform[t][b]."""
+    g = torch.Generator().manual_seed(seed)
+    B, T = len(counts), len(counts[0])
     inputs = torch.randn(B, T, N, 4, generator=g)
     masks = torch.zeros(B, T, N)
     for b in range(B):
@@ -549,6 +549,22 @@ def _smallest_scenes():
             if t < T - 1:
                 U[t][b] = torch.rand(gi_b[-1][0].numel(), K, generator=g)
         node_inds.append(ni_b); graph_info.append(gi_b)
+    return dict(inputs=inputs, masks=masks, burn=burn, node_inds=node_inds, graph_info=graph_info, uniform=U)
+
+
+def _smallest_scenes():
+    """Two scenes of 5 object rows over 6 time steps, built once: scene 0 has [2, 2, 0, 5, 3, 2] present objects per step
+    (k = min(10, n - 1) = 1 with two edges and in_degree 1, an empty step in the middle, a full scene), scene 1
+    [3, 0, 2, 2, 5, 4]; burn-in 2 steps; MODEL_PARAMS as they are (hidden 128, K = 3).  Returns the model, the oracle's
+    prediction for scene 0 and the inputs on the device; nothing in it is modified by the tests."""
+    if _SMALLEST:
+        return _SMALLEST
+    model, sd, MODEL_PARAMS = _scene_model()
+    model = model.cuda()
+    T, N, K = 6, 5, MODEL_PARAMS["num_edge_types"]
+    h = _scenes([[2, 2, 0, 5, 3, 2], [3, 0, 2, 2, 5, 4]], N, 52, K)
+    inputs, masks, burn, node_inds, graph_info, U = (h[k] for k in ("inputs", "masks", "burn", "node_inds", "graph_info",
+                                                                    "uniform"))
     assert [gi[0].numel() for gi in graph_info[0]] == [2, 2, 0, 20, 6, 2] and graph_info[0][0][2].shape == (2, 1)
     want0 = DO.predict_future(sd, inputs[:1], masks[:1], node_inds[0], graph_info[0], burn[:1], [U[t][0] for t in range(T - 1)],
                               MODEL_PARAMS["gumbel_temp"], MODEL_PARAMS["skip_first"], MODEL_PARAMS["pos_representation"])
