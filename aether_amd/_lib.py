@@ -60,6 +60,11 @@ class AetherGraphInfo(C.Structure):
                 ("max_group_nodes", C.c_int32), ("max_group_edges", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AetherDynScenePack(C.Structure):                 # host view of a scene pack: device pointers + per-step strides
+    _fields_ = [("node_inds", C.c_void_p), ("graph_send", C.c_void_p), ("graph_recv", C.c_void_p),
+                ("edge2node", C.c_void_p), ("node_stride", C.c_int64), ("edge_stride", C.c_int64)]
+
+
 FLAG_KEEP_INTERMEDIATES = 1
 FLAG_FORCE_STREAMED = 2
 FLAG_FORCE_FUSED = 4
@@ -193,6 +198,12 @@ SIGNATURES = {
                                                                C.c_void_p]),
     "aether_dyn_rollout_batched": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 +
                                    [C.c_void_p] * 3 + [C.c_void_p] * 5 + [C.c_void_p] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "aether_dyn_scene_pack_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "aether_dyn_scene_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                        C.POINTER(AetherDynScenePack), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aether_dyn_eval_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "aether_dyn_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 +
+                                   [C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "aether_sim_charged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
                                      C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_double, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),

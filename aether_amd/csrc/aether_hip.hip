@@ -49,6 +49,8 @@
 #include "egnn.h"
 #include "clof.h"
 #include "graph_build.h"
+#include "dyn_pack.h"
+#include "dyn_eval.h"
 
 #include <mutex>
 #include <type_traits>
@@ -1259,6 +1261,7 @@ static int graph_build_tables(const GraphLayout& G, char* g, int64_t n_edges, in
 }
 
 #include "host_graph_build.inc"
+#include "host_dyn_pack.inc"
 
 int aether_graph_matches(const int64_t* send, const int64_t* recv, int64_t n_edges, int64_t n_nodes, const void* graph,
                          void* stream) {

@@ -49,6 +49,31 @@ __device__ inline int block_exclusive_scan(int* val, int n, int* part, const int
     return total;
 }
 
+// bi[0..16): the present objects nearest to object i of a scene held in LDS (px, py positions, pm masks), nearest first,
+// -1 where the scene has fewer; equal distances keep index order.
+__device__ inline void knn_nearest(const float* px, const float* py, const float* pm, int N, int i, int (&bi)[KNN_MAX_K]) {
+    float bd[KNN_MAX_K];
+#pragma unroll
+    for (int p = 0; p < KNN_MAX_K; ++p) { bd[p] = INFINITY; bi[p] = -1; }
+    const float xi = px[i], yi = py[i];
+    for (int j = 0; j < N; ++j) {
+        if (j == i || pm[j] == 0.0f) continue;
+        const float dx = __fsub_rn(xi, px[j]), dy = __fsub_rn(yi, py[j]);
+        float cd = __fsqrt_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+        int ci = j;
+        if (!(cd < bd[KNN_MAX_K - 1])) continue;
+        bool shifting = false;                           // stable insertion: equal distances keep index order
+#pragma unroll
+        for (int p = 0; p < KNN_MAX_K; ++p) {
+            if (shifting || cd < bd[p]) {                // once placed, everything behind moves down one slot
+                const float td = bd[p]; const int ti = bi[p];
+                bd[p] = cd; bi[p] = ci; cd = td; ci = ti;
+                shifting = true;
+            }
+        }
+    }
+}
+
 // nbr[s][i][0..k): neighbours of object i, nearest first (local object ids); cnt[s][i]: how many are real.
 // scene_nodes[s], scene_edges[s] (zeroed by the host): present objects and edges of the scene.
 __global__ void __launch_bounds__(256)
@@ -74,27 +99,8 @@ k_knn_select(const float* __restrict__ x, int x_stride, const float* __restrict_
         int c = 0;
         if (pm[i] != 0.0f) {
             ++my_nodes;
-            float bd[KNN_MAX_K];
             int bi[KNN_MAX_K];
-#pragma unroll
-            for (int p = 0; p < KNN_MAX_K; ++p) { bd[p] = INFINITY; bi[p] = -1; }
-            const float xi = px[i], yi = py[i];
-            for (int j = 0; j < N; ++j) {
-                if (j == i || pm[j] == 0.0f) continue;
-                const float dx = __fsub_rn(xi, px[j]), dy = __fsub_rn(yi, py[j]);
-                float cd = __fsqrt_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
-                int ci = j;
-                if (!(cd < bd[KNN_MAX_K - 1])) continue;
-                bool shifting = false;                           // stable insertion: equal distances keep index order
-#pragma unroll
-                for (int p = 0; p < KNN_MAX_K; ++p) {
-                    if (shifting || cd < bd[p]) {                // once placed, everything behind moves down one slot
-                        const float td = bd[p]; const int ti = bi[p];
-                        bd[p] = cd; bi[p] = ci; cd = td; ci = ti;
-                        shifting = true;
-                    }
-                }
-            }
+            knn_nearest(px, py, pm, N, i, bi);
             int* out = nbr + ((size_t)s * N + i) * k;
 #pragma unroll
             for (int p = 0; p < KNN_MAX_K; ++p)

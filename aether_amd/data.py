@@ -138,3 +138,87 @@ class SimulatedFieldDataset:
 
     def __len__(self):
         return len(self.feats)
+
+
+def burn_in_masks_of(masks, max_burn_in_count):
+    """The data set's burn-in masks (experiments/ind/single_ind_data.py:73-81) for masks [..., T, N] of zeros and ones: an
+    object is observed at its first ``max_burn_in_count`` present frames.  The reference's loop counts the observed frames
+    of an object so far and compares with the limit; that count is min(exclusive cumsum of the mask, limit), so the mask
+    is  masks * (exclusive cumsum over time < max_burn_in_count)  -- one cumsum, on whatever device ``masks`` is."""
+    m = (masks == 1).to(torch.float32)
+    seen = torch.cumsum(m, dim=-2) - m
+    return m * (seen < max_burn_in_count).to(torch.float32)
+
+
+class SceneDataset:
+    """The inD runner's data set (experiments/ind/single_ind_data.py ``IndData``) kept on the device, for evaluation:
+    padded scenes, burn-in masks, un-normalisation, and batches that carry a ``ScenePack`` (the per-frame graphs of the
+    batch, built on the device in one library call) instead of per-scene Python lists.  There is no inD file loader: the
+    recordings are licensed.  The caller hands over the normalised tracks.
+
+    ``feats`` / ``masks``: per-scene tensors [T_s, N_s, 4] / [T_s, N_s] or padded ones [S, T, N, 4] / [S, T, N]; scenes
+    are zero-padded to the longest and the widest as ``ind_collate_fn`` does (:235-256).  ``stats``: None, a scalar
+    ``vel_norm_max`` or ``(min_feats, max_feats)`` -- what the reference loads from its two statistics files (:122-141).
+    ``non_linear_masks``: [S][N_s] flags (the reference's attribute of that name); evaluation skips tracks whose flag is 0.
+    """
+
+    def __init__(self, feats, masks, max_burn_in_count=-1, stats=None, non_linear_masks=None, k=10, device="cuda"):
+        feats = list(feats) if not torch.is_tensor(feats) else list(feats.unbind(0))
+        masks = list(masks) if not torch.is_tensor(masks) else list(masks.unbind(0))
+        if len(feats) != len(masks) or not feats:
+            raise ValueError("SceneDataset: feats and masks must hold the same, non-zero number of scenes")
+        self.device, self.k = torch.device(device), int(k)
+        self.shapes = [(int(f.shape[0]), int(f.shape[1])) for f in feats]
+        S, T, N = len(feats), max(s[0] for s in self.shapes), max(s[1] for s in self.shapes)
+        self.feats = torch.zeros(S, T, N, 4, dtype=torch.float32, device=self.device)
+        self.masks = torch.zeros(S, T, N, dtype=torch.float32, device=self.device)
+        for i, (f, m) in enumerate(zip(feats, masks)):
+            if tuple(m.shape) != self.shapes[i] or f.shape[-1] != 4:
+                raise ValueError(f"SceneDataset: scene {i}: feats must be [T, N, 4] and masks [T, N]")
+            self.feats[i, :f.shape[0], :f.shape[1]] = f.to(self.device, torch.float32)
+            self.masks[i, :m.shape[0], :m.shape[1]] = m.to(self.device, torch.float32)
+        self.max_burn_in_count = max_burn_in_count
+        self.burn_in_masks = burn_in_masks_of(self.masks, max_burn_in_count)
+        self.vel_norm_norm = stats is not None and not isinstance(stats, (tuple, list))
+        one = torch.ones(4, dtype=torch.float32, device=self.device)
+        if stats is None:
+            self.scale, self.offset = one, torch.zeros_like(one)
+        elif self.vel_norm_norm:
+            self.scale = one * torch.as_tensor(stats, dtype=torch.float32, device=self.device).reshape(())
+            self.offset = torch.zeros_like(one)
+        else:
+            lo, hi = (torch.as_tensor(s, dtype=torch.float32, device=self.device).reshape(-1) * one for s in stats)
+            self.scale, self.offset = (hi - lo) / 2.0, (hi - lo) / 2.0 + lo           # (x + 1) (max - min) / 2 + min
+        self.non_linear_masks = None
+        if non_linear_masks is not None:
+            self.non_linear_masks = torch.zeros(S, N, dtype=torch.float32, device=self.device)
+            for i, nl in enumerate(non_linear_masks):
+                nl = torch.as_tensor(nl).to(self.device, torch.float32).reshape(-1)
+                self.non_linear_masks[i, :nl.numel()] = nl
+
+    def unnormalize_data(self, feats):
+        """:122-141 for a tensor [..., 4]."""
+        return feats * self.scale.to(feats.device) + self.offset.to(feats.device)
+
+    def __len__(self):
+        return len(self.shapes)
+
+    def __getitem__(self, index):
+        """The reference's entry (:177-183) of one scene, un-padded: node_inds[t] and graph_info[t] are views into a
+        one-scene pack, in the form ``predict_future`` takes after ``ind_collate_fn`` / ``unsqueeze(0)``."""
+        from .nn.dynamicvars.aether_dynamicvars import pack_scenes
+        T, N = self.shapes[index]
+        sl = (slice(index, index + 1), slice(0, T), slice(0, N))
+        node_inds, graph_info = pack_scenes(self.feats[sl], self.masks[sl], self.k).as_lists()
+        return {"inputs": self.feats[sl][0], "masks": self.masks[sl][0], "burn_in_masks": self.burn_in_masks[sl][0],
+                "node_inds": node_inds[0], "graph_info": graph_info[0]}
+
+    def batches(self, batch_size):
+        """Padded batches in data-set order: the tensors of ``ind_collate_fn`` plus ``pack`` (a ``ScenePack`` of the batch)
+        and ``keep`` (the batch's non_linear_masks, or None)."""
+        from .nn.dynamicvars.aether_dynamicvars import pack_scenes
+        for lo in range(0, len(self), batch_size):
+            sl = slice(lo, lo + batch_size)
+            yield {"inputs": self.feats[sl], "masks": self.masks[sl], "burn_in_masks": self.burn_in_masks[sl],
+                   "pack": pack_scenes(self.feats[sl], self.masks[sl], self.k),
+                   "keep": None if self.non_linear_masks is None else self.non_linear_masks[sl]}

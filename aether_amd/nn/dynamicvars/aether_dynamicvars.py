@@ -31,8 +31,80 @@ class _DynStepConfig(C.Structure):                      # AetherDynStepConfig of
                                        "knn_k")] + [("gumbel_tau", C.c_float)]
 
 
+class ScenePack:
+    """The per-frame graphs of B scenes, built on the device by ``pack_scenes`` (``aether_dyn_scene_pack``): what the
+    reference's data set keeps as Python lists per scene and per frame (experiments/ind/single_ind_data.py:70-89).
+    ``buf`` holds the arrays, ``view`` the device pointers and per-frame strides into it, ``n_present`` / ``n_edges`` /
+    ``in_degree`` the host arrays [n_frames][B] the rollout takes as they are."""
+
+    def __init__(self, buf, view, n_present, n_edges, in_degree, n_scenes, n_frames, n_objects_max, k):
+        self.buf, self.view, self.n_present, self.n_edges, self.in_degree = buf, view, n_present, n_edges, in_degree
+        self.n_scenes, self.n_frames, self.n_objects_max, self.k = n_scenes, n_frames, n_objects_max, k
+
+    def _frames(self, ptr, stride):
+        """[n_frames][stride] int64 view of one of the pack's arrays."""
+        lo = ptr - self.buf.data_ptr()
+        return self.buf[lo:lo + self.n_frames * stride * 8].view(torch.int64).view(self.n_frames, stride)
+
+    def arrays(self):
+        """(node_inds [n_frames][B Nmax], graph_send, graph_recv, edge2node [n_frames][B Nmax k]): views into the pack; of
+        frame t the first sum_b n_present[t][b] / sum_b n_edges[t][b] entries are meaningful."""
+        v = self.view
+        return (self._frames(v.node_inds, v.node_stride), self._frames(v.graph_send, v.edge_stride),
+                self._frames(v.graph_recv, v.edge_stride), self._frames(v.edge2node, v.edge_stride))
+
+    def counts(self):
+        """(n_present, n_edges, in_degree) as host int64 tensors [n_frames][B]."""
+        shape = (self.n_frames, self.n_scenes)
+        return tuple(torch.tensor(list(a), dtype=torch.int64).view(shape) for a in (self.n_present, self.n_edges,
+                                                                                     self.in_degree))
+
+    def as_lists(self):
+        """-> (node_inds[b][t], graph_info[b][t] = (send, recv, edge2node [n][in_degree])): views into the pack, in the form
+        ``predict_future`` takes (the compatibility path: this is per-(scene, frame) Python again)."""
+        ni, gs, gr, e2n = self.arrays()
+        n, e, d = (c.tolist() for c in self.counts())
+        B = self.n_scenes
+        node_inds, graph_info = [[] for _ in range(B)], [[] for _ in range(B)]
+        for t in range(self.n_frames):
+            no = eo = 0
+            for b in range(B):
+                nb, eb = n[t][b], e[t][b]
+                node_inds[b].append(ni[t, no:no + nb])
+                graph_info[b].append((gs[t, eo:eo + eb], gr[t, eo:eo + eb],
+                                      e2n[t, eo:eo + eb].view(nb, d[t][b]) if nb else e2n[t, eo:eo].view(0, 1)))
+                no += nb; eo += eb
+        return node_inds, graph_info
+
+
+@torch.no_grad()
+def pack_scenes(inputs, masks, k=10):
+    """inputs [B, T, Nmax, 4], masks [B, T, Nmax] (device) -> ``ScenePack`` of all T frames: present rows, kNN graph of the
+    ground-truth positions (``k`` neighbours) and edge2node per (scene, frame), in ONE library call with one
+    device-to-host copy (the counts).  Raises if a scene has exactly one present object in a frame."""
+    if not inputs.is_cuda:
+        raise _lib.AetherHipError("pack_scenes runs on an MI355X only; got a CPU tensor (there is no CPU fallback)")
+    lib = _lib.load()
+    dev = inputs.device
+    B, T, Nmax = int(inputs.size(0)), int(inputs.size(1)), int(inputs.size(2))
+    if inputs.size(-1) != 4 or tuple(masks.shape) != (B, T, Nmax):
+        raise ValueError("pack_scenes: inputs must be [B, T, Nmax, 4] and masks [B, T, Nmax]")
+    x = inputs.detach().to(torch.float32).transpose(0, 1).contiguous()                  # time-major, as the rollout takes it
+    m = masks.detach().to(device=dev, dtype=torch.float32).transpose(0, 1).contiguous()
+    need = lib.aether_dyn_scene_pack_bytes(B, Nmax, T, int(k))
+    if need == 0:
+        raise _lib.AetherHipError("aether_dyn_scene_pack_bytes: " + lib.aether_last_error().decode())
+    buf = torch.empty(need, dtype=torch.uint8, device=dev)
+    view = _lib.AetherDynScenePack()
+    n_present, n_edges, in_degree = (C.c_int64 * (T * B))(), (C.c_int64 * (T * B))(), (C.c_int * (T * B))()
+    st = lib.aether_dyn_scene_pack(x.data_ptr(), m.data_ptr(), B, Nmax, T, int(k), buf.data_ptr(), buf.numel(), C.byref(view),
+                                   n_present, n_edges, in_degree, torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, "aether_dyn_scene_pack")
+    return ScenePack(buf, view, n_present, n_edges, in_degree, B, T, Nmax, int(k))
+
+
 class AetherDynamicVars(nn.Module):
-    one_call_step = True        # predict_future's steps go through aether_dyn_step (False: the three staged calls + torch glue)
+    one_call_step = True       # predict_future's steps go through aether_dyn_step (False: the three staged calls + torch glue)
 
     def __init__(self, params, device="cuda"):
         super().__init__()
@@ -428,6 +500,67 @@ class AetherDynamicVars(nn.Module):
             return out, dict(cfg=cfg, n_objects_max=Nmax, n_steps=n_steps, inputs=x, masks=m, burn_in_masks=burn, n_present=n_host,
                              n_edges=e_host, in_degree=deg, ptrs=ptrs, keep=keep)
         return out
+
+    @torch.no_grad()
+    def predict_future_packed(self, inputs, masks, burn_in_masks, pack, uniform=None):
+        """``predict_future`` of B scenes (1..256) on a ``ScenePack`` of the same inputs and masks: ONE
+        ``aether_dyn_rollout_batched`` call on the pack's arrays.  No per-(scene, step) Python, no host lists and no
+        edge2node range check (the library built them).  ``uniform``: None (one ``torch.rand`` for the call, step by step
+        and scene by scene in the rows of one tensor) or ``uniform[t][b]`` ([E, K]) as ``predict_future`` takes it."""
+        if not inputs.is_cuda:
+            raise _lib.AetherHipError("aether_amd AetherDynamicVars runs on an MI355X only; got a CPU tensor "
+                                      "(there is no CPU fallback)")
+        if self.encoder.training:
+            raise _lib.AetherHipError("the prior step uses BatchNorm running statistics: call .eval() first")
+        lib = _lib.load()
+        dev = inputs.device
+        B, T, Nmax = int(inputs.size(0)), int(inputs.size(1)), int(inputs.size(2))
+        n_steps, K = T - 1, self.num_edge_types
+        cfg = self._step_config()
+        if (pack.n_scenes, pack.n_objects_max) != (B, Nmax) or pack.n_frames < n_steps or n_steps < 1:
+            raise ValueError("the pack was built for other scenes (scenes, object rows or frames differ)")
+        if pack.k != cfg.knn_k:
+            raise ValueError(f"the rollout needs a pack with k = {cfg.knn_k}")
+        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        x = f32(inputs).transpose(0, 1).contiguous()                                   # [T][B][Nmax][4]
+        m = f32(masks)[:, :n_steps].transpose(0, 1).contiguous()                       # [n_steps][B][Nmax]
+        burn = f32(burn_in_masks)[:, :n_steps].transpose(0, 1).contiguous()
+        if m.shape[0] < n_steps or burn.shape[0] < n_steps:
+            raise ValueError("masks / burn_in_masks must cover every step")
+        v = pack.view
+        steps = torch.arange(n_steps, dtype=torch.int64)
+        e_step = torch.tensor(list(pack.n_edges), dtype=torch.int64).view(pack.n_frames, B)[:n_steps].sum(1)
+        if uniform is None:
+            u = torch.rand(int(e_step.sum()), K, device=dev)
+        else:
+            n_host = pack.n_present
+            rows = [f32(uniform[t][b]).reshape(-1, K) for t in range(n_steps) for b in range(B) if n_host[t * B + b] >= 2]
+            u = torch.cat(rows) if rows else torch.empty(0, K, device=dev)
+            if u.shape[0] != int(e_step.sum()):
+                raise ValueError("uniform[t][b] must be [E, K] of the scene's graph at that step")
+        u_off = torch.cumsum(e_step, 0) - e_step
+        arr = lambda vals: (C.c_void_p * n_steps)(*vals.tolist())
+        ptrs = dict(ni=arr(v.node_inds + steps * (v.node_stride * 8)), gs=arr(v.graph_send + steps * (v.edge_stride * 8)),
+                    gr=arr(v.graph_recv + steps * (v.edge_stride * 8)), e2n=arr(v.edge2node + steps * (v.edge_stride * 8)),
+                    u=arr((u.data_ptr() if u.numel() else pack.buf.data_ptr()) + u_off * (K * 4)))
+        need = lib.aether_dyn_rollout_batched_workspace_bytes(C.byref(cfg), B, Nmax, n_steps, pack.n_present, pack.n_edges,
+                                                              pack.in_degree)
+        if need == 0:
+            raise _lib.AetherHipError("aether_dyn_rollout_batched_workspace_bytes failed: " + lib.aether_last_error().decode())
+        ws = self.__dict__.get("_step_ws")
+        if ws is None or ws.numel() < need or ws.device != dev:
+            ws = self.__dict__["_step_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        prior_h, prior_c = (f32(s)[0].clone() for s in self.encoder.get_initial_hidden(inputs))
+        dec = f32(self.decoder.get_initial_hidden(inputs)).clone()
+        preds = torch.empty(n_steps, B, Nmax, 4, dtype=torch.float32, device=dev)
+        fs, ps_e, ps_d = self._field_struct(), self.encoder._param_struct()[0], self.decoder._param_struct()
+        st = lib.aether_dyn_rollout_batched(C.byref(fs), C.byref(ps_e), C.byref(ps_d), C.byref(cfg), B, Nmax, n_steps,
+                                            x.data_ptr(), m.data_ptr(), burn.data_ptr(), pack.n_present, pack.n_edges,
+                                            pack.in_degree, ptrs["ni"], ptrs["gs"], ptrs["gr"], ptrs["e2n"], ptrs["u"],
+                                            prior_h.data_ptr(), prior_c.data_ptr(), dec.data_ptr(), preds.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(st, "aether_dyn_rollout_batched")
+        return preds.transpose(0, 1).contiguous()
 
     @torch.no_grad()
     def predict_future_batched(self, inputs, masks, node_inds, graph_info, burn_in_masks, uniform=None):

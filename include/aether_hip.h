@@ -1021,6 +1021,73 @@ int aether_dyn_rollout_batched(const AetherDynFieldQueryParams* field_params, co
                                size_t workspace_bytes, void* stream);
 
 /*
+ * Scene pack: the data side of the variable-N family on the device.  Replaces, for B scenes and every frame at once, what
+ * the reference's data set builds per scene and per frame on the host (experiments/ind/single_ind_data.py:70-89):
+ * node_inds = mask[step].nonzero()[:, -1] (:82) and get_knn_graph_info (:186-217) -- the kNN graph of the frame's
+ * ground-truth positions (:193-211) and edge2node_inds = (tmp_inds == recv).nonzero()[:, 1].view(-1, k) (:213-215).
+ *   inputs [n_steps (+ 1)][B][n_objects_max][4], masks [n_steps][B][n_objects_max] : TIME-MAJOR, exactly what
+ *            aether_dyn_rollout_batched takes (the same tensors serve both calls); the first n_steps frames are read
+ *   k      : neighbours per object, 1..16; a scene with n present objects has in_degree = min(k, n - 1) per object.  The
+ *            rollout needs k = its config's knn_k.
+ *   pack   : device buffer of aether_dyn_scene_pack_bytes(...) bytes, 8-byte aligned.  n_scenes 1..256,
+ *            n_objects_max 1..512.
+ *   view   : HOST struct, out: device pointers into `pack` and the per-step strides (in elements).  Step t's arrays start
+ *            at node_inds + t * node_stride, graph_send / graph_recv / edge2node + t * edge_stride (node_stride =
+ *            B * n_objects_max, edge_stride = B * n_objects_max * k: a fixed capacity, so the rollout's per-step pointers are
+ *            host arithmetic).  Within a step the scenes with n >= 2 follow one another in scene order, each in its own
+ *            compacted numbering: node_inds the present rows, ascending; edges in aether_knn_edges' order (querying object
+ *            by querying object, nearest first, equal distances in index order; send = the querying object); edge2node the
+ *            scene's edge ids in stable order of graph_recv (argsort(recv, stable=True)), viewed as [n][in_degree].  Only
+ *            these entries are written; the rest of each step's capacity is left as it was.
+ *   n_present, n_edges, in_degree : HOST arrays [n_steps][B], out, as aether_dyn_rollout_batched takes them.
+ * Synchronisation: ONE device-to-host copy (the counts, into pinned memory) and ONE hipStreamSynchronize per call; nothing
+ * else is synchronised.  No atomics that could change a result: the same input gives the same bytes.
+ * Refused before anything is queued: null pointers, n_scenes outside 1..256, k outside 1..16, n_objects_max outside 1..512
+ * (AETHER_EINVAL), pack_bytes too small (AETHER_ESPACE).  Refused after the count copy (AETHER_EINVAL): a (scene, step)
+ * with exactly one present object -- the rollout refuses it and the reference fails there; aether_last_error names the
+ * first such scene and step.  aether_dyn_scene_pack_bytes is host arithmetic only (0 + aether_last_error on bad sizes).
+ */
+typedef struct AetherDynScenePack {
+    int64_t* node_inds;
+    int64_t* graph_send;
+    int64_t* graph_recv;
+    int64_t* edge2node;
+    int64_t node_stride, edge_stride;
+} AetherDynScenePack;
+size_t aether_dyn_scene_pack_bytes(int n_scenes, int n_objects_max, int n_steps, int k);
+int aether_dyn_scene_pack(const float* inputs, const float* masks, int n_scenes, int n_objects_max, int n_steps, int k,
+                          void* pack, size_t pack_bytes, AetherDynScenePack* view, int64_t* n_present, int64_t* n_edges,
+                          int* in_degree, void* stream);
+
+/*
+ * The inD runner's forward-prediction metric (experiments/ind/evaluate.py:29-80) for B scenes per call; the reference
+ * computes it at batch 1 with a Python loop over objects and several .item() calls per object.
+ *   preds, truth  : [B][n_steps][n_objects_max][feat_stride >= 4] -- predict_future's result and inputs[:, 1:]; the first
+ *                   four features enter (:59-62)
+ *   masks, burn_in_masks : [B][n_steps + 1][n_objects_max], the latter after the caller applied `strict` (:26-28)
+ *   scale[4], offset[4]  : device; the un-normalisation y = scale_f x + offset_f (both modes of single_ind_data.py:122-141)
+ *   keep          : [B][n_objects_max] or NULL, the data set's non_linear_masks (:55-58); 0 = skip the track
+ *   error_norm    : report_error_norm (:63-68): L2 norms of the position / velocity error instead of their MSE
+ * Per track (scene, object): skipped without a burn-in entry (:52); pred_mask = (masks - burn_in_masks)[1:] (:29), `first`
+ * its first non-zero step, `num` its sum; the errors of steps first .. first + num - 1, each multiplied by pred_mask, are
+ * added to horizons 0 .. num - 1 and counts[h] += pred_mask[first + h] (:76-80).
+ *   sums [3][n_steps] (total, position, velocity), counts [n_steps] : device fp64; the call ADDS to them, so a data set is
+ *                   a sequence of calls (zero them before the first).  The metric is sums / counts.
+ *   stats int64[2]: device; stats[0] += tracks whose predicted steps are not contiguous (the reference's bad count, :72-75);
+ *                   stats[1] = max(stats[1], longest pred_mask sum of any track of the call): the length of the reference's
+ *                   result (:41-46)
+ *   scratch       : aether_dyn_eval_scratch_bytes(...) bytes of device memory, 8-byte aligned; rewritten by every call
+ * One wave per track writes its contributions as a row of scratch; a second kernel adds the rows column by column in a
+ * fixed order in fp64.  No atomics.  Stream-ordered, no host synchronisation.  Errors are computed in fp64 from the fp32
+ * inputs.
+ */
+size_t aether_dyn_eval_scratch_bytes(int n_scenes, int n_objects_max, int n_steps);
+int aether_dyn_eval_accumulate(const float* preds, const float* truth, int feat_stride, const float* masks,
+                               const float* burn_in_masks, const float* scale, const float* offset, const float* keep,
+                               int error_norm, int n_scenes, int n_objects_max, int n_steps, double* sums, double* counts,
+                               int64_t* stats, void* scratch, size_t scratch_bytes, void* stream);
+
+/*
  * The rest of the runner's training step (experiments/lorentz/main.py:86,164,289-292): nn.MSELoss with the seed of its
  * backward, and optim.AdamW over every parameter tensor -- one launch each (torch: 4 + 3).
  *
