@@ -229,13 +229,15 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 constexpr int64_t FUSED_TABLE_MAX_EDGES = 4 << 20;
 int g_fused_split = 1;        // aether_set_option("fused_split", 0|1): two workgroups per group when CUs are idle
 int g_fused_waves12 = 1;     // aether_set_option("fused_waves12", 0|1): 12-wave k_fused for one-node-tile workgroups of 9-12 edge tiles (inference)
+int g_fused_granules = 1;   // aether_set_option("fused_granules", 0|1): the split halves of the 12-wave k_fused hand their P_s rows over as tagged granules (0: rows + flag)
 int g_graph_build = 1;       // aether_set_option("graph_build", 0|1): 1 aether_graph_build_counting counts, 0 it forwards to aether_graph_build
 constexpr int FUSED_PAIR_STRIDE = 8;   // distance of the two workgroups of a split group (8: both on one XCD -- workgroup b
                                        // runs on XCD b % 8 -- 47.25 -> 46.56 us per launch at cfg2; a placement hint only:
                                        // the hand-off protocol is the cross-XCD one either way)
 
+constexpr int64_t FUSED_GRAN_MAX_NODES = 4096;
 struct GraphLayout {
-    size_t perm, send_s, recv_s, rowptr, gsel, wgdesc, tdesc, trec, lorder, ledge, nrange, hflags, sperm, srowptr, keys,
+    size_t perm, send_s, recv_s, rowptr, gsel, wgdesc, tdesc, trec, lorder, ledge, nrange, hflags, hgran, hgran_bytes, sperm, srowptr, keys,
         vals, diff, cross, flag, cub, total, cub_bytes;
     int64_t max_wgs, max_tiles;
     GraphLayout(int64_t E, int64_t Nn, bool with_sort_scratch = true) {
@@ -256,6 +258,11 @@ struct GraphLayout {
         ledge = take(tables ? 4 * e4 : 16);     // ... and {sorted position, sender, receiver, original edge} in that order
         nrange = take(tables ? (size_t)Nn * 16 : 4);                 // per node: local index ranges of its two runs
         hflags = take((size_t)(2 * max_wgs + 64) * 4);               // split-mode hand-off flags: forward | backward
+        // hand-off granules of the 12-wave kernel (fused.h): per node three rows (one per layer hand-off) of H 8-byte granules,
+        // on lines of their own behind the flags.  Only a view that can be split has them: a split view has at most
+        // 256 workgroups (two per group, groups <= half the CUs) of at most 16 own nodes each where that kernel runs.
+        hgran_bytes = tables && Nn <= FUSED_GRAN_MAX_NODES ? (size_t)3 * Nn * H * 8 : 0;
+        hgran = take(hgran_bytes ? hgran_bytes : 16);
         sperm = take(e4);                       // receiver-sorted positions grouped by sender (stable)
         srowptr = take((size_t)(Nn + 1) * 4);
         keys = take(e4); vals = take(e4);
@@ -443,13 +450,13 @@ int prepare_weights(const AetherParams& P, char* ws, bool split_images, bool tra
                                  transposes, st);
 }
 
-template <int D, int NW, int ROUNDS, bool KEEP>
+template <int D, int NW, int ROUNDS, bool KEEP, bool GRAN = false>
 int fused_launch(const AetherParams& P, const float* x, const float* vel, const float* charges,
                  const float* ea, const int32_t* perm, const int32_t* send_s, const int32_t* recv_s,
                  const int32_t* rowptr, const FusedWG* wgdesc, const uint32_t* trec,
                  const int4* ledge, const int32_t* nrange, int n_groups, const FusedDebug& dbg, float* out,
                  hipStream_t st) {
-    auto kern = k_fused<D, NW, ROUNDS, KEEP>;
+    auto kern = k_fused<D, NW, ROUNDS, KEEP, GRAN>;
     constexpr size_t lds = (size_t)FusedLds<NW, ROUNDS>::TOTAL * 4;
     if (ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return AETHER_EHIP;
     ProfScope ps(K_FUSED, st);
@@ -499,10 +506,15 @@ int fused_impl(const AetherParams& P, int64_t Nn, int64_t E, const AetherGraphIn
                                                reinterpret_cast<const int4*>(graph + G.ledge), gp(G.nrange), info.n_groups, dbg, out, st)
     // 9-12 tiles and one node tile in every workgroup (every split N = 17..20 group, unsplit groups of 12-14 nodes): twelve
     // waves with one tile each instead of eight of which four run two (fused.h); inference only
-    if (g_fused_waves12 && !keep && tiles >= 9 && tiles <= 12 && info.max_group_nodes <= 16)
-        rc = fused_launch<D, 12, 1, false>(P, x, vel, charges, ea, gp(G.perm), gp(G.send_s), gp(G.recv_s), gp(G.rowptr), wgd, trec,
-                                           reinterpret_cast<const int4*>(graph + G.ledge), gp(G.nrange), info.n_groups, dbg, out, st);
-    else if (tiles <= 8) { AETHER_FUSED_CASE(8, 1); }
+    if (g_fused_waves12 && !keep && tiles >= 9 && tiles <= 12 && info.max_group_nodes <= 16) {
+        // split view (info.reserved) with a granule block: the hand-off as tagged granules, unless the option says rows + flag
+        if (g_fused_granules && info.reserved == 1 && G.hgran_bytes != 0)
+            rc = fused_launch<D, 12, 1, false, true>(P, x, vel, charges, ea, gp(G.perm), gp(G.send_s), gp(G.recv_s), gp(G.rowptr), wgd, trec,
+                                                     reinterpret_cast<const int4*>(graph + G.ledge), gp(G.nrange), info.n_groups, dbg, out, st);
+        else
+            rc = fused_launch<D, 12, 1, false>(P, x, vel, charges, ea, gp(G.perm), gp(G.send_s), gp(G.recv_s), gp(G.rowptr), wgd, trec,
+                                               reinterpret_cast<const int4*>(graph + G.ledge), gp(G.nrange), info.n_groups, dbg, out, st);
+    } else if (tiles <= 8) { AETHER_FUSED_CASE(8, 1); }
     else if (tiles <= 16) { AETHER_FUSED_CASE(8, 2); }
     else { AETHER_FUSED_CASE(8, 3); }
 #undef AETHER_FUSED_CASE
@@ -999,6 +1011,11 @@ int aether_set_option(const char* name, int value) {
         g_fused_split = value != 0;
         return AETHER_OK;
     }
+    if (!strcmp(name, "fused_granules")) {    // read at every launch
+        if (value != 0 && value != 1) return fail(AETHER_EINVAL, "set_option: fused_granules must be 0 or 1");
+        g_fused_granules = value;
+        return AETHER_OK;
+    }
     if (!strcmp(name, "fused_waves12")) {    // read at every launch
         if (value != 0 && value != 1) return fail(AETHER_EINVAL, "set_option: fused_waves12 must be 0 or 1");
         g_fused_waves12 = value;
@@ -1197,7 +1214,8 @@ static int graph_build_tables(const GraphLayout& G, char* g, int64_t n_edges, in
             mgn = 0; mge = 0;
             auto add_wg = [&](int vb, int ve, int nb, int ne, int partner) {
                 const int m = h_rowptr[ne] - h_rowptr[nb];
-                FusedWG w = {vb, ve, nb, ne, (int)tiles.size(), partner, 0, (int)h_rowptr[nb], m, 0, 0, 0};
+                FusedWG w = {vb, ve, nb, ne, (int)tiles.size(), partner, 0, (int)h_rowptr[nb], m,
+                              split && G.hgran_bytes ? (int)(G.hgran - G.hflags) : 0, 0, 0};
                 for (int t = 0; t < (m + 15) / 16; ++t) tiles.push_back(FusedTile{(int)wgs.size(), t});
                 if (ne - nb > mgn) mgn = ne - nb;
                 if (m > mge) mge = m;
@@ -1239,6 +1257,7 @@ static int graph_build_tables(const GraphLayout& G, char* g, int64_t n_edges, in
             if ((int64_t)tiles.size() <= G.max_tiles) {
                 HIP_OK(hipMemcpyAsync(g + G.wgdesc, wgs.data(), wgs.size() * sizeof(FusedWG), hipMemcpyHostToDevice, st));
                 HIP_OK(hipMemsetAsync(g + G.hflags, 0, (size_t)(2 * G.max_wgs + 64) * 4, st));
+                if (split && G.hgran_bytes) HIP_OK(hipMemsetAsync(g + G.hgran, 0, G.hgran_bytes, st));     // tag 0: nothing published
                 k_graph_lorder<<<dim3((unsigned)wgs.size()), dim3(512), 0, st>>>(
                     (FusedWG*)(g + G.wgdesc), (const int32_t*)(g + G.send_s), recv_s, (const int32_t*)(g + G.perm), rowptr,
                     (int32_t*)(g + G.lorder), (int4*)(g + G.ledge), (int32_t*)(g + G.nrange));

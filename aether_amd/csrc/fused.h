@@ -232,7 +232,9 @@ constexpr int FUSED_STAMPS = 512;
 // receiver-sorted (unsplit: na = m, the identity).  Tiles of the first run need nothing from the partner, so
 // the forward starts with them while the partner's rows are in flight -- and the backward starts with the
 // second run, whose sender-side sums the partner waits for.
-struct FusedWG { int vb, ve, nb, ne, tile0, partner, na, eb, m, pad1, pad2, pad3; };   // eb, m: first in-edge (sorted position) and in-edge count of [nb, ne)
+// goff: the view's granule block (12-wave kernel, tagged-granule hand-off): its byte offset from the hand-off flags, 0 when
+// the view has none; the same in every workgroup of a view.
+struct FusedWG { int vb, ve, nb, ne, tile0, partner, na, eb, m, goff, pad2, pad3; };   // eb, m: first in-edge (sorted position) and in-edge count of [nb, ne)
 struct FusedTile { int wg, t; };             // workgroup descriptor index, tile index within the workgroup
 
 // Local edge order of every workgroup (one block per workgroup; m <= FUSED_MAX_EDGES <= blockDim.x) and the
@@ -376,10 +378,122 @@ k_graph_gtiles(const int32_t* __restrict__ recv_s, int64_t n_edges, uint32_t* __
     graph_gtile(recv_s, n_edges, gsel, (int64_t)blockIdx.x, threadIdx.x);
 }
 
+// ---------------------------------------------------------------- hand-off as tagged granules (12-wave kernel)
+// Split mode, k_fused<D, 12, 1, false, true>: the two workgroups of a group hand their P_s rows over as 8-byte granules
+// {tag, fp32 bits} (cdna_hip_programming.md Guideline 16, form R2: "the data IS the flag") -- no flag, no drain of the
+// stores, no order between them.  The granule of column c of node g for the hand-off behind layer l (tag l, row l - 1 of
+// the node's three) lies at flags + goff + ((3 g + l - 1) * H + c) * 8 in the graph view: zero between launches, written
+// once per launch, zeroed again by its reader.  Free functions, called from k_fused<D, 12, 1, false, true> only.
+constexpr int GRAN_ROW = H * 8, GRAN_NODE = 3 * GRAN_ROW;      // bytes of one row of granules, of a node's three rows
+typedef unsigned int gran_u32x4 __attribute__((ext_vector_type(4)));
+
+// descriptor of the granules of a workgroup's visible nodes [vb, vb + nv) (rows in the numbering of ninfo / psb)
+__device__ __forceinline__ auto gran_rsrc(int* flags, int goff, int vb, int nv) {
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(flags) + goff + (int64_t)vb * GRAN_NODE, 0, nv * GRAN_NODE,
+                                             0x00020000);
+}
+
+// Producer (step 4 of layers 1-3): the lane's four columns c0 .. c0 + 3 of visible row `row` as four granules, two 16-byte
+// sc1 stores (the 8-byte halves of such a store land whole: MI355X_MICROARCH.md, visibility).  Nothing waits for them and
+// nothing signals them: the partner reads until it sees the tags.
+template <class Rsrc>
+__device__ __forceinline__ void gran_publish(Rsrc rsrc, int row, int c0, int layer, f32x4 val) {
+    const unsigned tag = (unsigned)layer;
+    const gran_u32x4 g01 = {tag, __float_as_uint(val[0]), tag, __float_as_uint(val[1])};
+    const gran_u32x4 g23 = {tag, __float_as_uint(val[2]), tag, __float_as_uint(val[3])};
+    const int voff = row * GRAN_NODE + c0 * 8, soff = (layer - 1) * GRAN_ROW;
+    __builtin_amdgcn_raw_buffer_store_b128(g01, rsrc, voff, soff, 16);          // aux 16 = sc1
+    __builtin_amdgcn_raw_buffer_store_b128(g23, rsrc, voff + 16, soff, 16);
+}
+
+// Consumer (start of the edge phase of layers 2-4), ONE wave: re-read the partner's rows -- the visible rows outside
+// [off, off + n) -- of the hand-off behind layer - 1, every 16-byte piece {tag, value, tag, value}, NL pieces per lane, all
+// in flight together, ONE wait per pass, until every tag says layer - 1; the pass that finds them all carries the values
+// already, and they go to the rows of psb.  sc1 loads, the only loads of those bytes in the launch.  Bounded by TIME like
+// the flag poll of the other protocol (5 s of the 100 MHz wall clock) with the same error path: the host-mapped word and
+// arrived[1].  Five pieces per lane cover 10 partner rows (every split of N <= 20 but the most uneven); more rows, a
+// second sweep.
+template <class Rsrc, class LdsWord>
+__device__ __forceinline__ void gran_receive(Rsrc rsrc, int layer, int nv, int n, int off, int lane, float* psb,
+                                             LdsWord* arrived, int* errword) {
+    constexpr int NL = 5;
+    const int npieces = (nv - n) * (H / 2);
+    const unsigned tag = (unsigned)(layer - 1);
+    const int soff = (layer - 2) * GRAN_ROW;
+    for (int base = 0; base < npieces; base += 64 * NL) {
+        int src[NL];
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+            // every load is unconditional on a clamped piece (piece 0 exists: there is a partner row)
+            const int idx = base + 64 * j + lane, idc = idx < npieces ? idx : 0;
+            int slot = idc >> 5;
+            if (slot >= off) slot += n;
+            src[j] = slot * GRAN_NODE + (idc & 31) * 16;
+        }
+        gran_u32x4 v[NL];
+        unsigned spins = 0;
+        unsigned long long t_first = 0;
+        bool gave_up = false;
+        for (;;) {
+            asm volatile("" ::: "memory");                      // a pass loads again: nothing is carried over from the last one
+#pragma unroll
+            for (int j = 0; j < NL; ++j) v[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, src[j], soff, 16);   // aux 16 = sc1
+            // one wait that the compiler's wait-count pass sees, nothing scheduled across it, every loaded value named behind it
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+            __builtin_amdgcn_sched_barrier(0);
+            bool ok = true;
+#pragma unroll
+            for (int j = 0; j < NL; ++j) {
+                asm volatile("" : "+v"(v[j]));
+                ok = ok && v[j][0] == tag && v[j][2] == tag;
+            }
+            if (__all(ok)) break;
+            __builtin_amdgcn_s_sleep(1);
+            if ((++spins & 1023u) == 0) {
+                const unsigned long long now = wall_clock64();
+                if (t_first == 0) t_first = now;
+                if (now - t_first <= 500000000ull) continue;
+                // partner not resident: give up, never hang -- and say so (see the flag poll in k_fused)
+                if (lane == 0) {
+                    if (errword) __hip_atomic_store(errword, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    arrived[1] = 1;
+                }
+                gave_up = true;
+                break;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+            if (base + 64 * j + lane < npieces) {
+                const int row = src[j] / GRAN_NODE, c = ((src[j] % GRAN_NODE) >> 4) * 2;
+                *reinterpret_cast<f32x2*>(psb + row * LDW + c) = f32x2{__uint_as_float(v[j][1]), __uint_as_float(v[j][3])};
+            }
+        }
+        if (gave_up) break;                                     // no second wait
+    }
+}
+
+// Re-arm (after the layer-4 edge phase), `nthreads` threads of which this is thread t: zero the granules this workgroup
+// consumed -- the partner's rows, all three of a node lie behind one another.  Every one of them was seen with its tag (or
+// the launch has reported an error), so the partner's store of this launch is in memory before this one; the next launch
+// starts behind it.
+template <class Rsrc>
+__device__ __forceinline__ void gran_rearm(Rsrc rsrc, int nv, int n, int off, int t, int nthreads) {
+    constexpr int PIECES = GRAN_NODE / 16;
+    const gran_u32x4 zero = {0u, 0u, 0u, 0u};
+    for (int idx = t; idx < (nv - n) * PIECES; idx += nthreads) {
+        int slot = idx / PIECES;
+        const int piece = idx - slot * PIECES;
+        if (slot >= off) slot += n;
+        __builtin_amdgcn_raw_buffer_store_b128(zero, rsrc, slot * GRAN_NODE + piece * 16, 0, 16);   // aux 16 = sc1
+    }
+}
+
 #ifndef AETHER_R3_DEFER
 #define AETHER_R3_DEFER 0      // diagnostic: 1 = three-tile variants request the node-phase weights after the tile loop (spill-free, slower)
 #endif
-template <int D, int NW, int ROUNDS, bool KEEP>
+template <int D, int NW, int ROUNDS, bool KEEP, bool GRAN = false>
 __global__ void __launch_bounds__(NW * 64)
 k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ vel,
         const float* __restrict__ charges, const float* __restrict__ edge_attr_orig,
@@ -397,6 +511,11 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     // share one set of fragment registers (wf_h / wf_l below, DESIGN.md 4.1 "Wave roles in the node phase").
     static_assert(NW == 8 || NW == 12, "waves 0-7 run the node phase; NW == 12 adds four waves that run step 3 (DESIGN.md 4.1)");
     static_assert(NW == 8 || (ROUNDS == 1 && !KEEP), "the 12-wave kernel owns one tile per wave and saves nothing for the backward");
+    // GRAN (12 waves, split views): the own P_s rows go to the partner as tagged granules (gran_* above) instead of rows +
+    // flag.  An instantiation holds ONE of the two protocols -- with both, the scalar registers of the unused one pushed
+    // three dozen others into vector-register lanes, read back at the top of every layer (+1.0 us per step).  Both
+    // workgroups of a pair run the same launch, so the two protocols never meet.
+    static_assert(!GRAN || NW == 12, "granules are the 12-wave kernel's hand-off");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* wA = smem + L::WA;
     float* wB = smem + L::WB;
@@ -973,6 +1092,15 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             }
         };
         auto receive_partner_rows = [&]() {
+            if constexpr (GRAN) {             // no flag to poll, the rows' own tags say when they are there
+                FUSED_WSTAMP(layer, 0, 6);
+                gran_receive(gran_rsrc(dbg.flags, wg.goff, vb, nv), layer, nv, n, off, lane, psb, arrived, dbg.errword);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // rows are in LDS before the word says so
+                __builtin_amdgcn_wave_barrier();
+                if (lane == 0) arrived[0] = layer;
+                FUSED_WSTAMP(layer, 0, 7);
+                return;
+            }
             // second half of the hand-off (first half: end of the previous node phase), run by ONE wave: lane 0
             // polls the partner's flag (bounded: a wait that gives up reports through dbg.errword), then the wave
             // reads the partner's rows with sc1 (L1-bypassing) 16-byte buffer loads -- the only loads of those
@@ -1230,6 +1358,9 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         FUSED_STAMP(4 + 8 * (layer - 1) + 5);
         // step 4: next layer's node terms P_s = W_s x, P_r = W_r x + b1 (locs.py:233 split)
         if (layer < 4) {
+            // granules: the LDS-DMA of the next layer's images and constants (issued in step 1) is waited for HERE, where it
+            // has long landed, and not in front of the closing barrier: the granule stores below stay in flight across it
+            if constexpr (GRAN) __builtin_amdgcn_s_waitcnt(0x0F70);
             if (16 * tn4 < n) {
                 f32x4 xv[4];
 #pragma unroll
@@ -1245,7 +1376,9 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                     if (16 * tn4 + i < n) {      // sender rows live in the visible numbering
                         st4(psb + (off + 16 * tn4 + i) * LDW + 16 * mb3 + 4 * q, accs);
                         float* gps = dbg.ps[layer - 1] + (int64_t)(nb + 16 * tn4 + i) * H + 16 * mb3 + 4 * q;
-                        if (wg.partner >= 0) {       // write-through (sc1) payload: no release fence needed
+                        if (GRAN && wg.partner >= 0) {
+                            gran_publish(gran_rsrc(dbg.flags, wg.goff, vb, nv), off + 16 * tn4 + i, 16 * mb3 + 4 * q, layer, accs);
+                        } else if (wg.partner >= 0) {       // write-through (sc1) payload: no release fence needed
                             // ONE 16-byte sc1 store per lane (aux 16): an 8-byte sc1 store is a fabric write of its
                             // own, 2.7 x the time per byte (MI355X_MICROARCH.md, visibility price list)
                             typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -1279,15 +1412,23 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             // before the barrier, then one lane raises the flag.  The partner picks the rows up after
             // the first GEMM of its next edge phase (receive_partner_rows), as this workgroup does with
             // the partner's: the flag's flight time hides behind those 64 MFMAs.
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // hand-off stores; LDS-DMA images and constants
+            // (granules: no drain, no flag -- the stores are on their way, the DMA was waited for above)
+            if (!GRAN)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // hand-off stores; LDS-DMA images and constants
             lds_barrier();   // P_s / P_r and the staged weights are visible to the next edge tiles
-            if (wg.partner >= 0 && tid == 0)
+            if (!GRAN && wg.partner >= 0 && tid == 0)
                 __hip_atomic_store(dbg.flags + blockIdx.x, layer, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             FUSED_STAMP(4 + 8 * (layer - 1) + 6);
         }
     }
     if (wg.partner >= 0 && tid == 0)       // the partner's last flag value has been consumed: re-arm it
         __hip_atomic_store(dbg.flags + wg.partner, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (GRAN) {
+        // ... and the granules this workgroup consumed: the partner's rows of all three slots, zeroed by the waves that have
+        // no stage of the out MLP, under it.  Every one of them was seen with its tag (or the launch has reported an
+        // error), so the partner's store of this launch is in memory before this one; the next launch starts behind it.
+        if (wg.partner >= 0 && wave >= 8) gran_rearm(gran_rsrc(dbg.flags, wg.goff, vb, nv), nv, n, off, tid - 512, 256);
+    }
 
     // ---------------------------------------------------------------- out MLP + globalise + residual
     // locs.py:160-168,193; local_to_global.py:12-13; aether.py:185

@@ -1120,7 +1120,10 @@ int aether_adamw_step(const AetherAdamWTensor* tensors, int n_tensors, float* st
  * aether_graph_build), "fused_waves12" 0|1 (inference step of small-graph groups: when every workgroup has one node
  * tile (<= 16 own nodes) and the largest has 9-12 edge tiles, run the fused kernel with twelve waves and one edge
  * tile per wave instead of eight waves with up to two; same arithmetic, same bits; default 1; read at every
- * launch), "graph_build" 0|1 (aether_graph_build_counting: 1, the default, builds by counting; 0 forwards
+ * launch), "fused_granules" 0|1 (that twelve-wave kernel on a split view: the two workgroups of a group hand their
+ * P_s rows over as 8-byte {layer tag, value} granules that the receiver re-reads until every tag matches, instead of
+ * rows, a store drain and a flag; same bits; 0 gives the rows + flag protocol of the eight-wave kernels; values other
+ * than 0 and 1 are refused; default 1; read at every launch), "graph_build" 0|1 (aether_graph_build_counting: 1, the default, builds by counting; 0 forwards
  * every call to the sorting aether_graph_build), "fused_backward" 0|1 (one-launch backward for small-graph groups; default 1, 0 sends them through
  * the layer-by-layer kernels), "outer_defer_max_edges" n (aether_backward keeps every layer's weight-gradient operands
  * and multiplies them in one launch when n_edges <= n, default 2^20; changes aether_workspace_bytes), "edge_acc"
