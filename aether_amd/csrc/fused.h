@@ -33,6 +33,9 @@
 #ifndef AETHER_SUMS_SELECT
 #define AETHER_SUMS_SELECT 0   // diagnostic: 1 = branch-free receiver sums (a store per row, rows that end no segment into a spare row)
 #endif
+#ifndef AETHER_LATE_WAIT_FIRST
+#define AETHER_LATE_WAIT_FIRST 0   // diagnostic: 1 = a tile with a partner sender waits for the partner's rows in front of its first Linear (same arithmetic)
+#endif
 
 namespace {
 
@@ -218,9 +221,17 @@ constexpr int FUSED_STAMPS = 512;
             dbg.stamps[blockIdx.x * FUSED_STAMPS + 64 + wave * 24 + (r_) * 8 + (k_)] =            \
                 (float)(__builtin_amdgcn_s_memtime() - c_entry);                                 \
     } while (0)
+// one more stamp per (wave, round), behind the 12 x 24 slots above: the partner's rows are there (front of the late add)
+#define FUSED_WSTAMP_ROWS(layer_, r_)                                                             \
+    do {                                                                                         \
+        if ((layer_) == 2 && lane == 0 && blockIdx.x < 4096 && wave < 16)                        \
+            dbg.stamps[blockIdx.x * FUSED_STAMPS + 352 + wave * 4 + (r_)] =                       \
+                (float)(__builtin_amdgcn_s_memtime() - c_entry);                                 \
+    } while (0)
 #else
 #define FUSED_STAMP(id)
 #define FUSED_WSTAMP(layer_, r_, k_)
+#define FUSED_WSTAMP_ROWS(layer_, r_)
 #endif
 
 // One workgroup's share of a group: it sees nodes [vb, ve) (whole graphs: every sender of its edges)
@@ -1073,23 +1084,50 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             }
         };
         // Split mode, layers 2-4: the partner workgroup's P_s rows are in flight when the edge phase starts.  The
-        // workgroup walks the tiles whose senders it owns first (local order, FusedWG); the LAST wave -- it has the
-        // fewest tiles, and its only one needs the partner -- polls the partner's flag, copies the rows into LDS and
-        // sets an LDS word; a wave waits on that word only before its first tile with a partner sender.  No
+        // workgroup walks the tiles whose senders it owns first (local order, FusedWG); ONE wave (recv_wave below) polls
+        // the partner's flag or granules, copies the rows into LDS and sets an LDS word; a wave waits on that word only
+        // in its first tile with a partner sender, and there only behind the tile's first Linear (late_add).  No
         // workgroup barrier, and nobody waits while there is work that does not need the rows.
         const bool xch = wg.partner >= 0 && layer > 1;
-        auto front_gemm = [&](int r, f32x4 (&acc)[4], bool last) {
+        // Layers 2-4 of a split view: an edge whose sender the partner owns (local position >= na) starts its accumulator
+        // at P_r alone; its P_s row is added behind the product (late_add), so that the first Linear of a tile runs
+        // under the wait for the partner's rows.  late_tile (wave-uniform): the tile holds such an edge.  A select, not a
+        // product with 0: the row that such a lane reads here is the previous layer's and may hold anything.  Every
+        // other edge -- all of them in an unsplit view -- starts at P_r + P_s.  One rule in every instantiation that adds late (see the tile loop).
+        auto front_gemm = [&](int r, f32x4 (&acc)[4], bool last, bool late_tile) {
             if (layer == 1) {
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb) acc[mb] = ld4(cb + CB_B1 + 16 * mb + 4 * q);
                 f32x4 bop[2] = {e[r][0], e[r][1]};
                 gemm_split<4, 1>(wA, bop, acc, lane);
             } else {
+                f32x4 pr[4];
 #pragma unroll
-                for (int mb = 0; mb < 4; ++mb)
-                    acc[mb] = ld4(prb + rl[r] * LDW + 16 * mb + 4 * q) + ld4(psb + sl[r] * LDW + 16 * mb + 4 * q);
+                for (int mb = 0; mb < 4; ++mb) {
+                    pr[mb] = ld4(prb + rl[r] * LDW + 16 * mb + 4 * q);
+                    acc[mb] = pr[mb] + ld4(psb + sl[r] * LDW + 16 * mb + 4 * q);
+                }
+                if (late_tile) {
+                    const bool late = 16 * (NW * r + wave) + i >= na;
+#pragma unroll
+                    for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) acc[mb][c] = late ? pr[mb][c] : acc[mb][c];
+                }
                 gemm_split<4, 2>(wA, e[r], acc, lane);
             }
+        };
+        // ... and the partner senders' P_s rows, in front of the first SiLU (the caller has waited for them)
+        auto late_add = [&](int r, f32x4 (&acc)[4]) {
+            const bool late = 16 * (NW * r + wave) + i >= na;
+            f32x4 ps[4];           // four reads in flight and one wait (read by read, a late tile paid four LDS round trips)
+#pragma unroll
+            for (int mb = 0; mb < 4; ++mb) ps[mb] = ld4(psb + sl[r] * LDW + 16 * mb + 4 * q);
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ps[0]), "+v"(ps[1]), "+v"(ps[2]), "+v"(ps[3]));
+#pragma unroll
+            for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[mb][c] = late ? acc[mb][c] + ps[mb][c] : acc[mb][c];
         };
         auto receive_partner_rows = [&]() {
             if constexpr (GRAN) {             // no flag to poll, the rows' own tags say when they are there
@@ -1264,20 +1302,44 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
 #pragma unroll
                 for (int part = 1; part < 5; ++part) issue_loads(part);
             }
-            if (xch && wave == NW - 1) receive_partner_rows();
-            bool have_rows = !xch || wave == NW - 1;
+            // Who receives.  Flag protocol: the last wave -- it has the fewest tiles.  Granules: wave 0 when its tile is wholly
+            // own-sender (na >= 16), in front of that tile: it needs no rows itself, so every wave that does -- the last
+            // one included -- runs its first Linear under the sweep, and wave 0's late tile still ends before theirs.
+            // Otherwise (hardly an own sender in the workgroup) the last wave as before.  The receiver is fixed before the
+            // tile loop: it receives whether or not it owns a tile (N = 17: 9 tiles on 12 waves), the others wait for it.
+            const int recv_wave = GRAN && na >= 16 ? 0 : NW - 1;
+            if (xch && wave == recv_wave) receive_partner_rows();
+            bool have_rows = !xch || wave == recv_wave;
 #pragma unroll
             for (int r = 0; r < ROUNDS; ++r) {
                 if (r < nvalid) {
                     const bool last = r == nvalid - 1;
+                    // a partner sender in this tile (wave-uniform)
+                    const bool partner_tile = xch && 16 * (NW * r + wave + 1) > na;
+                    // The late add belongs to the workgroups of 9-16 tiles: the 12-wave kernels and the two-tile kernels,
+                    // which are compared with them bit for bit.  The one-tile 8-wave kernels keep P_r + P_s in one
+                    // rounding and the wait in front of the tile (HISTORY R17); three-tile kernels run unsplit views only.
+                    constexpr bool LATE = NW == 12 || ROUNDS == 2;
+                    const bool late_tile = LATE && partner_tile;
                     FUSED_WSTAMP(layer, r, 0);
-                    if (!have_rows && 16 * (NW * r + wave + 1) > na) {      // first tile with a partner sender
-                        wait_partner_rows();
-                        have_rows = true;
+                    if constexpr (!LATE || AETHER_LATE_WAIT_FIRST) {
+                        if (partner_tile && !have_rows) {
+                            wait_partner_rows();
+                            have_rows = true;
+                        }
                     }
                     FUSED_WSTAMP(layer, r, 1);
                     f32x4 acc[4], h1[4];
-                    front_gemm(r, acc, last);
+                    front_gemm(r, acc, last, late_tile);
+                    FUSED_WSTAMP(layer, r, 3);
+                    if (late_tile) {
+                        if (!have_rows) {      // first tile with a partner sender: the rows are needed from here on
+                            wait_partner_rows();
+                            have_rows = true;
+                        }
+                        FUSED_WSTAMP_ROWS(layer, r);
+                        late_add(r, acc);
+                    }
                     front_act(r, acc, h1, last);
                     FUSED_WSTAMP(layer, r, 2);
                     back(r, h1, last);

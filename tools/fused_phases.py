@@ -58,7 +58,7 @@ for k in order:
 clk = np.median(st[:, 41] / st[:, 40])
 print(f"  shader clock during the kernel: {clk:.0f} MHz (s_memtime cycles / wall us)")
 print("  layer-2 per-wave tile timeline, cycles since kernel entry (median over workgroups):")
-print("   wave round   start  wait rows  gemm1+silu1  gemm2+silu2+stage  sums   | total")
+print("   wave round   start  wait rows  gemm1+silu1  gemm2+silu2+stage  sums   | total   [gemm1 | wait rows + receive | late add + silu1]")
 sums = []
 for w in range(12):            # 8 or 12 waves per workgroup (FUSED_WSTAMP: 24 slots per wave from slot 64, 64 + 24 * 12 <= FUSED_STAMPS)
     for r in range(3):
@@ -66,7 +66,11 @@ for w in range(12):            # 8 or 12 waves per workgroup (FUSED_WSTAMP: 24 s
         if v[5] == 0: continue
         d = [v[1] - v[0], v[2] - v[1], v[4] - v[2], v[5] - v[4]]      # stamps 0, 1, 2, 4 (tile parked, sums begin), 5
         sums.append(d[3])
-        print(f"   {w:4d} {r:5d} {v[0]:8.0f} {d[0]:9.0f} {d[1]:12.0f} {d[2]:18.0f} {d[3]:6.0f}    | {v[5]-v[0]:6.0f}")
+        # stamp 3: first GEMM done; FUSED_WSTAMP_ROWS (slot 352 + 4 wave + round): rows there, tiles with a partner sender only
+        rows = med[352 + 4 * w + r]
+        late = f"   [{v[3]-v[1]:5.0f} | {rows-v[3]:5.0f} | {v[2]-rows:5.0f}]" if v[3] > 0 and rows > 0 else \
+               f"   [{v[3]-v[1]:5.0f} |     - | {v[2]-v[3]:5.0f}]" if v[3] > 0 else ""
+        print(f"   {w:4d} {r:5d} {v[0]:8.0f} {d[0]:9.0f} {d[1]:12.0f} {d[2]:18.0f} {d[3]:6.0f}    | {v[5]-v[0]:6.0f}{late}")
 for w in range(12):            # the wave that copies the partner's rows (split groups): slots 6, 7 of its first round
     v = med[64 + w * 24: 64 + w * 24 + 8]
     if v[6] > 0:
