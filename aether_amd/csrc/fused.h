@@ -36,6 +36,9 @@
 #ifndef AETHER_LATE_WAIT_FIRST
 #define AETHER_LATE_WAIT_FIRST 0   // diagnostic: 1 = a tile with a partner sender waits for the partner's rows in front of its first Linear (same arithmetic)
 #endif
+#ifndef AETHER_EARLY_PRODUCT
+#define AETHER_EARLY_PRODUCT 1     // diagnostic: 0 = the 12-wave kernels run the next layer's W_e e product inside the edge tile again (same arithmetic)
+#endif
 
 namespace {
 
@@ -221,6 +224,7 @@ constexpr int FUSED_STAMPS = 512;
             dbg.stamps[blockIdx.x * FUSED_STAMPS + 64 + wave * 24 + (r_) * 8 + (k_)] =            \
                 (float)(__builtin_amdgcn_s_memtime() - c_entry);                                 \
     } while (0)
+// (k_ = 8, 9 with r_ = 0: begin and end of the early W_e e product, in the slots of the round the 12-wave kernels do not have)
 // one more stamp per (wave, round), behind the 12 x 24 slots above: the partner's rows are there (front of the late add)
 #define FUSED_WSTAMP_ROWS(layer_, r_)                                                             \
     do {                                                                                         \
@@ -501,6 +505,59 @@ __device__ __forceinline__ void gran_rearm(Rsrc rsrc, int nv, int n, int off, in
     }
 }
 
+// gemm_split (common.h) for a wave that has nobody to hide its latencies behind (the early product of the 12-wave
+// kernels, in the node phase), in a fixed schedule that keeps 16 registers of weight fragments: the MBN row blocks go two by
+// two, a pair's six MFMAs alternate between its two accumulators (no MFMA waits for the one in front of it), and the next
+// pair's w_lo / w_hi fragments are requested as soon as this pair's have been read for the last time.  Left to the
+// compiler the first k block ran as four chains of three dependent MFMAs with an LDS round trip in front of each.
+// Every accumulator sees the same products in the same order as in gemm_split_core (per k block: w_lo x_hi, w_hi x_lo,
+// w_hi x_hi), and the operand scale is gemm_split_keep's: the same bits.
+template <int MBN, int KBN>
+__device__ __forceinline__ void gemm_split_paired(const float* __restrict__ img, const f32x4 (&act)[2 * KBN], f32x4 (&acc)[MBN], int lane) {
+    static_assert(MBN % 2 == 0, "row blocks go in pairs");
+    constexpr int TERM = MBN * KBN * 64, NG = KBN * (MBN / 2);
+    const f16x8* w = reinterpret_cast<const f16x8*>(img);
+    const SplitScale sc = split_scale_of(act);
+    f32x4 x[2 * KBN];
+#pragma unroll
+    for (int b = 0; b < 2 * KBN; ++b) x[b] = act[b];
+    if (sc.on) {                                                // (wave-uniform)
+#pragma unroll
+        for (int b = 0; b < 2 * KBN; ++b) x[b] = x[b] * sc.s;
+#pragma unroll
+        for (int mb = 0; mb < MBN; ++mb) acc[mb] = acc[mb] * sc.s;
+    }
+    // group g = (k block g / (MBN / 2), row blocks 2 (g % (MBN / 2)) and + 1)
+    auto frag = [&](int g, int j, bool lo) -> f16x8 {
+        const int kb = g / (MBN / 2), mb = 2 * (g % (MBN / 2)) + j;
+        return w[(lo ? TERM : 0) + (mb * KBN + kb) * 64 + lane];
+    };
+    f16x8 xh[KBN], xl[KBN];
+    f16x8 wl0 = frag(0, 0, true), wl1 = frag(0, 1, true), wh0 = frag(0, 0, false), wh1 = frag(0, 1, false);
+    split8(x[0], x[1], xh[0], xl[0]);
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        const int kb = g / (MBN / 2), m0 = 2 * (g % (MBN / 2)), m1 = m0 + 1;
+        __builtin_amdgcn_sched_barrier(0);
+        acc[m0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl0, xh[kb], acc[m0], 0, 0, 0);
+        acc[m1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl1, xh[kb], acc[m1], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (g + 1 < NG) { wl0 = frag(g + 1, 0, true); wl1 = frag(g + 1, 1, true); }
+        // the next k block's pieces: vector-ALU work next to this pair's last MFMAs
+        if (g + 1 < NG && (g + 1) % (MBN / 2) == 0) split8(x[2 * (kb + 1)], x[2 * (kb + 1) + 1], xh[kb + 1], xl[kb + 1]);
+        acc[m0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh0, xl[kb], acc[m0], 0, 0, 0);
+        acc[m1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh1, xl[kb], acc[m1], 0, 0, 0);
+        acc[m0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh0, xh[kb], acc[m0], 0, 0, 0);
+        acc[m1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh1, xh[kb], acc[m1], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (g + 1 < NG) { wh0 = frag(g + 1, 0, false); wh1 = frag(g + 1, 1, false); }
+    }
+    if (sc.on) {
+#pragma unroll
+        for (int mb = 0; mb < MBN; ++mb) acc[mb] = acc[mb] * sc.inv_s;
+    }
+}
+
 #ifndef AETHER_R3_DEFER
 #define AETHER_R3_DEFER 0      // diagnostic: 1 = three-tile variants request the node-phase weights after the tile loop (spill-free, slower)
 #endif
@@ -527,6 +584,13 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     // three dozen others into vector-register lanes, read back at the top of every layer (+1.0 us per step).  Both
     // workgroups of a pair run the same launch, so the two protocols never meet.
     static_assert(!GRAN || NW == 12, "granules are the 12-wave kernel's hand-off");
+    // The kernels that run workgroups of 9-16 tiles -- the 12-wave kernels and the two-tile 8-wave kernels, compared bit for
+    // bit -- share one rule for the first Linear of layers 2-4: g = W_e e from +0.0f accumulators, then g + (P_r + P_s),
+    // or (g + P_r) + P_s on an edge whose sender the partner owns (front_gemm / late_add below).  g needs nothing but
+    // the message tile, so the 12-wave kernels (EARLY) compute it under the previous layer's node phase, where the
+    // matrix pipe is idle, and keep it in the tile's registers: e[0] is dead behind the product.
+    constexpr bool LATE = NW == 12 || ROUNDS == 2;
+    constexpr bool EARLY = NW == 12 && AETHER_EARLY_PRODUCT;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* wA = smem + L::WA;
     float* wB = smem + L::WB;
@@ -1094,6 +1158,8 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         // under the wait for the partner's rows.  late_tile (wave-uniform): the tile holds such an edge.  A select, not a
         // product with 0: the row that such a lane reads here is the previous layer's and may hold anything.  Every
         // other edge -- all of them in an unsplit view -- starts at P_r + P_s.  One rule in every instantiation that adds late (see the tile loop).
+        // In those (LATE) the start is not the product's accumulator any more: the product g runs from zeros -- in the 12-wave
+        // kernels under the previous node phase -- and the start is added to it, g + (P_r + P_s) or (g + P_r) + P_s.
         auto front_gemm = [&](int r, f32x4 (&acc)[4], bool last, bool late_tile) {
             if (layer == 1) {
 #pragma unroll
@@ -1101,20 +1167,36 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                 f32x4 bop[2] = {e[r][0], e[r][1]};
                 gemm_split<4, 1>(wA, bop, acc, lane);
             } else {
-                f32x4 pr[4];
+                f32x4 pr[4], st[4];          // st: what the product is added to, P_r + P_s or P_r alone
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb) {
                     pr[mb] = ld4(prb + rl[r] * LDW + 16 * mb + 4 * q);
-                    acc[mb] = pr[mb] + ld4(psb + sl[r] * LDW + 16 * mb + 4 * q);
+                    st[mb] = pr[mb] + ld4(psb + sl[r] * LDW + 16 * mb + 4 * q);
                 }
                 if (late_tile) {
                     const bool late = 16 * (NW * r + wave) + i >= na;
 #pragma unroll
                     for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
-                        for (int c = 0; c < 4; ++c) acc[mb][c] = late ? pr[mb][c] : acc[mb][c];
+                        for (int c = 0; c < 4; ++c) st[mb][c] = late ? pr[mb][c] : st[mb][c];
                 }
-                gemm_split<4, 2>(wA, e[r], acc, lane);
+                if constexpr (LATE) {
+                    if constexpr (EARLY) {           // the tile holds g already (early_product, previous node phase)
+#pragma unroll
+                        for (int mb = 0; mb < 4; ++mb) acc[mb] = e[r][mb] + st[mb];
+                    } else {
+                        f32x4 g[4];
+#pragma unroll
+                        for (int mb = 0; mb < 4; ++mb) g[mb] = f32x4{0.f, 0.f, 0.f, 0.f};
+                        gemm_split<4, 2>(wA, e[r], g, lane);
+#pragma unroll
+                        for (int mb = 0; mb < 4; ++mb) acc[mb] = g[mb] + st[mb];
+                    }
+                } else {
+#pragma unroll
+                    for (int mb = 0; mb < 4; ++mb) acc[mb] = st[mb];
+                    gemm_split<4, 2>(wA, e[r], acc, lane);
+                }
             }
         };
         // ... and the partner senders' P_s rows, in front of the first SiLU (the caller has waited for them)
@@ -1225,6 +1307,19 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             while (__builtin_amdgcn_readfirstlane(arrived[0]) < layer) __builtin_amdgcn_s_sleep(1);
             asm volatile("" ::: "memory");
         };
+        // 12 waves: g = W_e(layer + 1) e of the wave's tile, in place, under this layer's node phase (the image is in wA
+        // behind the "u complete" barrier).  gemm_split as the tile would run it: same k order, small terms first, same
+        // operand scale.  A wave without a tile has nothing to multiply.
+        auto early_product = [&]() {
+            if (n_tiles > wave) {
+                f32x4 g[4];
+#pragma unroll
+                for (int mb = 0; mb < 4; ++mb) g[mb] = f32x4{0.f, 0.f, 0.f, 0.f};
+                gemm_split_paired<4, 2>(wA, e[0], g, lane);
+#pragma unroll
+                for (int mb = 0; mb < 4; ++mb) e[0][mb] = g[mb];
+            }
+        };
         auto front_act = [&](int r, f32x4 (&acc)[4], f32x4 (&h1)[4], bool last) {
             if (last && !(AETHER_R3_DEFER && ROUNDS >= 3)) issue_loads(1);
 #pragma unroll
@@ -1319,7 +1414,6 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                     // The late add belongs to the workgroups of 9-16 tiles: the 12-wave kernels and the two-tile kernels,
                     // which are compared with them bit for bit.  The one-tile 8-wave kernels keep P_r + P_s in one
                     // rounding and the wait in front of the tile (HISTORY R17); three-tile kernels run unsplit views only.
-                    constexpr bool LATE = NW == 12 || ROUNDS == 2;
                     const bool late_tile = LATE && partner_tile;
                     FUSED_WSTAMP(layer, r, 0);
                     if constexpr (!LATE || AETHER_LATE_WAIT_FIRST) {
@@ -1367,7 +1461,9 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         // The wave's W3 / W4 / W_s / W_r fragments have arrived: a wait the compiler's wait-count pass sees (simm16 of
         // vmcnt(0) alone), so that it places none of its own in steps 2-4 -- in particular none behind the LDS-DMA below.
         __builtin_amdgcn_s_waitcnt(0x0F70);
-        if (layer < 4) dma_images(layer + 1);    // next layer's images and constants: in flight under steps 2-4, waited for before step 4's barrier
+        // next layer's images and constants: in flight under step 2 (12 waves with the early product: waited for in front
+        // of the "u complete" barrier) or steps 2-4 (waited for before step 4's barrier)
+        if (layer < 4) dma_images(layer + 1);
         lds_barrier();       // n complete
         FUSED_STAMP(4 + 8 * (layer - 1) + 7);
         // step 2: u = SiLU(W3 n + b3): rows 16*mb2.. of u for both node tiles
@@ -1391,8 +1487,22 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                 }
             }
         }
+        if constexpr (EARLY) {
+            // the one vmcnt wait between step 1's barrier and step 4's closing barrier: this wave's fragments of the next
+            // layer's images have landed; behind the barrier wA holds W_e(layer + 1) whole
+            if (layer < 4) __builtin_amdgcn_s_waitcnt(0x0F70);
+        }
         lds_barrier();       // u complete
         FUSED_STAMP(4 + 8 * (layer - 1) + 4);
+        if constexpr (EARLY) {
+            // waves 0-7 have nothing to do in step 3: their tile's product for the next layer runs here, next to the four
+            // waves (8-11) of step 3, and never between a barrier and node-phase work that somebody waits for
+            if (layer < 4 && wave < 8) {
+                FUSED_WSTAMP(layer + 1, 0, 8);
+                early_product();
+                FUSED_WSTAMP(layer + 1, 0, 9);
+            }
+        }
 
         // step 3: x = n + W4 u + b4: rows 16*mb3.. of node tile tn3s (one node tile: on waves 4-7)
         if (do3) {
@@ -1422,7 +1532,16 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         if (layer < 4) {
             // granules: the LDS-DMA of the next layer's images and constants (issued in step 1) is waited for HERE, where it
             // has long landed, and not in front of the closing barrier: the granule stores below stay in flight across it
-            if constexpr (GRAN) __builtin_amdgcn_s_waitcnt(0x0F70);
+            // (with the early product it was waited for in front of the "u complete" barrier)
+            if constexpr (GRAN && !EARLY) __builtin_amdgcn_s_waitcnt(0x0F70);
+            if constexpr (EARLY) {
+                // ... and waves 8-11, which ran step 3, have nothing to do in step 4
+                if (wave >= 8) {
+                    FUSED_WSTAMP(layer + 1, 0, 8);
+                    early_product();
+                    FUSED_WSTAMP(layer + 1, 0, 9);
+                }
+            }
             if (16 * tn4 < n) {
                 f32x4 xv[4];
 #pragma unroll

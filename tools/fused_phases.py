@@ -71,6 +71,12 @@ for w in range(12):            # 8 or 12 waves per workgroup (FUSED_WSTAMP: 24 s
         late = f"   [{v[3]-v[1]:5.0f} | {rows-v[3]:5.0f} | {v[2]-rows:5.0f}]" if v[3] > 0 and rows > 0 else \
                f"   [{v[3]-v[1]:5.0f} |     - | {v[2]-v[3]:5.0f}]" if v[3] > 0 else ""
         print(f"   {w:4d} {r:5d} {v[0]:8.0f} {d[0]:9.0f} {d[1]:12.0f} {d[2]:18.0f} {d[3]:6.0f}    | {v[5]-v[0]:6.0f}{late}")
+early = [(w, med[64 + w * 24 + 8], med[64 + w * 24 + 9]) for w in range(12)]     # FUSED_WSTAMP(2, 0, 8 / 9): 12-wave kernels only
+if any(t1 > 0 for _, _, t1 in early):
+    print("  layer 2's W_e e product under layer 1's node phase (waves 0-7: step 3's window, waves 8-11: step 4's), cycles since kernel entry:")
+    for w, t0, t1 in early:
+        if t1 > 0:
+            print(f"   wave {w:2d}: {t0:8.0f} .. {t1:8.0f}  ({t1 - t0:5.0f})")
 for w in range(12):            # the wave that copies the partner's rows (split groups): slots 6, 7 of its first round
     v = med[64 + w * 24: 64 + w * 24 + 8]
     if v[6] > 0:
