@@ -258,7 +258,7 @@ struct GraphLayout {
         ledge = take(tables ? 4 * e4 : 16);     // ... and {sorted position, sender, receiver, original edge} in that order
         nrange = take(tables ? (size_t)Nn * 16 : 4);                 // per node: local index ranges of its two runs
         hflags = take((size_t)(2 * max_wgs + 64) * 4);               // split-mode hand-off flags: forward | backward
-        // hand-off granules of the 12-wave kernel (fused.h): per node three rows (one per layer hand-off) of H 8-byte granules,
+        // hand-off granules of the 12-wave kernel (fused_handoff.h): per node three rows (one per layer hand-off) of H 8-byte granules,
         // on lines of their own behind the flags.  Only a view that can be split has them: a split view has at most
         // 256 workgroups (two per group, groups <= half the CUs) of at most 16 own nodes each where that kernel runs.
         hgran_bytes = tables && Nn <= FUSED_GRAN_MAX_NODES ? (size_t)3 * Nn * H * 8 : 0;
@@ -409,7 +409,7 @@ BwdWT transposed_weights(const AetherParams& P, float* base, TransposeBatch& TB)
 
 // Everything derived from the weights alone, in ONE launch in front of the step: the split images of the edge-MLP
 // matrices the fused forward copies into LDS (blocks 0-7), the node phase's (blocks 8-31), the per-layer constants
-// blocks (biases, out_w6: the last image block; fused.h CB_*) and, when the intermediates are kept for a backward, the
+// blocks (biases, out_w6: the last image block; fused_layout.h CB_*) and, when the intermediates are kept for a backward, the
 // transposed copies its kernels read (the remaining blocks).
 __global__ void __launch_bounds__(512)
 k_prepare_weights(AetherParams P, int f1, int nd, float* __restrict__ wimg, TransposeBatch TB, int split_blocks) {
@@ -450,18 +450,26 @@ int prepare_weights(const AetherParams& P, char* ws, bool split_images, bool tra
                                  transposes, st);
 }
 
+// Operands of one k_fused launch: the same for every instance of the kernel.
+struct FusedLaunch {
+    const AetherParams& P;
+    const float *x, *vel, *charges, *ea;
+    const int32_t *perm, *send_s, *recv_s, *rowptr;       // graph view
+    const FusedWG* wgdesc; const uint32_t* trec; const int4* ledge; const int32_t* nrange;
+    int n_groups;
+    const FusedDebug& dbg;
+    float* out;
+    hipStream_t st;
+};
+
 template <int D, int NW, int ROUNDS, bool KEEP, bool GRAN = false>
-int fused_launch(const AetherParams& P, const float* x, const float* vel, const float* charges,
-                 const float* ea, const int32_t* perm, const int32_t* send_s, const int32_t* recv_s,
-                 const int32_t* rowptr, const FusedWG* wgdesc, const uint32_t* trec,
-                 const int4* ledge, const int32_t* nrange, int n_groups, const FusedDebug& dbg, float* out,
-                 hipStream_t st) {
+int fused_launch(const FusedLaunch& a) {
     auto kern = k_fused<D, NW, ROUNDS, KEEP, GRAN>;
     constexpr size_t lds = (size_t)FusedLds<NW, ROUNDS>::TOTAL * 4;
     if (ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return AETHER_EHIP;
-    ProfScope ps(K_FUSED, st);
-    kern<<<dim3((unsigned)n_groups), dim3(NW * 64), lds, st>>>(P, x, vel, charges, ea, perm, send_s, recv_s,
-                                                              rowptr, wgdesc, trec, ledge, nrange, dbg, out);
+    ProfScope ps(K_FUSED, a.st);
+    kern<<<dim3((unsigned)a.n_groups), dim3(NW * 64), lds, a.st>>>(a.P, a.x, a.vel, a.charges, a.ea, a.perm, a.send_s, a.recv_s,
+                                                                  a.rowptr, a.wgdesc, a.trec, a.ledge, a.nrange, a.dbg, a.out);
     return AETHER_OK;
 }
 
@@ -490,34 +498,25 @@ int fused_impl(const AetherParams& P, int64_t Nn, int64_t E, const AetherGraphIn
     dbg.errword = async_error_word();
     dbg.wimg = pw ? pw->wimg : wp(W.wimg);
     dbg.step = step;
-    const FusedWG* wgd = reinterpret_cast<const FusedWG*>(graph + G.wgdesc);
-    const uint32_t* trec = reinterpret_cast<const uint32_t*>(graph + G.trec);
     (void)ws_reused;
     const int tiles = (info.max_group_edges + 15) / 16;
     // split-GEMM variants: 3 x bf16 images of the eight edge-MLP matrices; training: the backward's transposed copies
     if (!pw && prepare_weights<D>(P, ws, !weights_prepared, keep, Nn, E, st)) return AETHER_EHIP;
+    const FusedLaunch a{P, x, vel, charges, ea, gp(G.perm), gp(G.send_s), gp(G.recv_s), gp(G.rowptr),
+                        reinterpret_cast<const FusedWG*>(graph + G.wgdesc), reinterpret_cast<const uint32_t*>(graph + G.trec),
+                        reinterpret_cast<const int4*>(graph + G.ledge), gp(G.nrange), info.n_groups, dbg, out, st};
     int rc;
-#define AETHER_FUSED_CASE(NWV, R)                                                                     \
-    rc = keep ? fused_launch<D, NWV, R, true>(P, x, vel, charges, ea, gp(G.perm), gp(G.send_s),       \
-                                              gp(G.recv_s), gp(G.rowptr), wgd, trec,                  \
-                                              reinterpret_cast<const int4*>(graph + G.ledge), gp(G.nrange), info.n_groups, dbg, out, st) \
-              : fused_launch<D, NWV, R, false>(P, x, vel, charges, ea, gp(G.perm), gp(G.send_s),      \
-                                               gp(G.recv_s), gp(G.rowptr), wgd, trec,                 \
-                                               reinterpret_cast<const int4*>(graph + G.ledge), gp(G.nrange), info.n_groups, dbg, out, st)
     // 9-12 tiles and one node tile in every workgroup (every split N = 17..20 group, unsplit groups of 12-14 nodes): twelve
     // waves with one tile each instead of eight of which four run two (fused.h); inference only
     if (g_fused_waves12 && !keep && tiles >= 9 && tiles <= 12 && info.max_group_nodes <= 16) {
         // split view (info.reserved) with a granule block: the hand-off as tagged granules, unless the option says rows + flag
         if (g_fused_granules && info.reserved == 1 && G.hgran_bytes != 0)
-            rc = fused_launch<D, 12, 1, false, true>(P, x, vel, charges, ea, gp(G.perm), gp(G.send_s), gp(G.recv_s), gp(G.rowptr), wgd, trec,
-                                                     reinterpret_cast<const int4*>(graph + G.ledge), gp(G.nrange), info.n_groups, dbg, out, st);
+            rc = fused_launch<D, 12, 1, false, true>(a);
         else
-            rc = fused_launch<D, 12, 1, false>(P, x, vel, charges, ea, gp(G.perm), gp(G.send_s), gp(G.recv_s), gp(G.rowptr), wgd, trec,
-                                               reinterpret_cast<const int4*>(graph + G.ledge), gp(G.nrange), info.n_groups, dbg, out, st);
-    } else if (tiles <= 8) { AETHER_FUSED_CASE(8, 1); }
-    else if (tiles <= 16) { AETHER_FUSED_CASE(8, 2); }
-    else { AETHER_FUSED_CASE(8, 3); }
-#undef AETHER_FUSED_CASE
+            rc = fused_launch<D, 12, 1, false>(a);
+    } else if (tiles <= 8) rc = keep ? fused_launch<D, 8, 1, true>(a) : fused_launch<D, 8, 1, false>(a);
+    else if (tiles <= 16) rc = keep ? fused_launch<D, 8, 2, true>(a) : fused_launch<D, 8, 2, false>(a);
+    else rc = keep ? fused_launch<D, 8, 3, true>(a) : fused_launch<D, 8, 3, false>(a);
     if (rc != AETHER_OK) return rc;
     HIP_OK(hipGetLastError());
     return AETHER_OK;

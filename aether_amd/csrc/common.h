@@ -279,6 +279,59 @@ __device__ __forceinline__ void gemm_split(const float* __restrict__ img, const 
     (void)gemm_split_keep<MBN, KBN>(img, act, acc, lane, xh, xl);
 }
 
+// gemm_split for a wave that has nobody to hide its latencies behind (the early product of the 12-wave
+// kernels, in the node phase), in a fixed schedule that keeps 16 registers of weight fragments: the MBN row blocks go two by
+// two, a pair's six MFMAs alternate between its two accumulators (no MFMA waits for the one in front of it), and the next
+// pair's w_lo / w_hi fragments are requested as soon as this pair's have been read for the last time.  Left to the
+// compiler the first k block ran as four chains of three dependent MFMAs with an LDS round trip in front of each.
+// Every accumulator sees the same products in the same order as in gemm_split_core (per k block: w_lo x_hi, w_hi x_lo,
+// w_hi x_hi), and the operand scale is gemm_split_keep's: the same bits.
+template <int MBN, int KBN>
+__device__ __forceinline__ void gemm_split_paired(const float* __restrict__ img, const f32x4 (&act)[2 * KBN], f32x4 (&acc)[MBN], int lane) {
+    static_assert(MBN % 2 == 0, "row blocks go in pairs");
+    constexpr int TERM = MBN * KBN * 64, NG = KBN * (MBN / 2);
+    const f16x8* w = reinterpret_cast<const f16x8*>(img);
+    const SplitScale sc = split_scale_of(act);
+    f32x4 x[2 * KBN];
+#pragma unroll
+    for (int b = 0; b < 2 * KBN; ++b) x[b] = act[b];
+    if (sc.on) {                                                // (wave-uniform)
+#pragma unroll
+        for (int b = 0; b < 2 * KBN; ++b) x[b] = x[b] * sc.s;
+#pragma unroll
+        for (int mb = 0; mb < MBN; ++mb) acc[mb] = acc[mb] * sc.s;
+    }
+    // group g = (k block g / (MBN / 2), row blocks 2 (g % (MBN / 2)) and + 1)
+    auto frag = [&](int g, int j, bool lo) -> f16x8 {
+        const int kb = g / (MBN / 2), mb = 2 * (g % (MBN / 2)) + j;
+        return w[(lo ? TERM : 0) + (mb * KBN + kb) * 64 + lane];
+    };
+    f16x8 xh[KBN], xl[KBN];
+    f16x8 wl0 = frag(0, 0, true), wl1 = frag(0, 1, true), wh0 = frag(0, 0, false), wh1 = frag(0, 1, false);
+    split8(x[0], x[1], xh[0], xl[0]);
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        const int kb = g / (MBN / 2), m0 = 2 * (g % (MBN / 2)), m1 = m0 + 1;
+        __builtin_amdgcn_sched_barrier(0);
+        acc[m0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl0, xh[kb], acc[m0], 0, 0, 0);
+        acc[m1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl1, xh[kb], acc[m1], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (g + 1 < NG) { wl0 = frag(g + 1, 0, true); wl1 = frag(g + 1, 1, true); }
+        // the next k block's pieces: vector-ALU work next to this pair's last MFMAs
+        if (g + 1 < NG && (g + 1) % (MBN / 2) == 0) split8(x[2 * (kb + 1)], x[2 * (kb + 1) + 1], xh[kb + 1], xl[kb + 1]);
+        acc[m0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh0, xl[kb], acc[m0], 0, 0, 0);
+        acc[m1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh1, xl[kb], acc[m1], 0, 0, 0);
+        acc[m0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh0, xh[kb], acc[m0], 0, 0, 0);
+        acc[m1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh1, xh[kb], acc[m1], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (g + 1 < NG) { wh0 = frag(g + 1, 0, false); wh1 = frag(g + 1, 1, false); }
+    }
+    if (sc.on) {
+#pragma unroll
+        for (int mb = 0; mb < MBN; ++mb) acc[mb] = acc[mb] * sc.inv_s;
+    }
+}
+
 // The same product with the weight fragments of ONE 16-row block held in registers (k_fused's node phase: a wave owns a row
 // block of W3 / W4 / W_s / W_r and applies it to one or two node tiles): wh / wl = the image's fragments (mb, kb = 0 .. KBN).
 template <int KBN>

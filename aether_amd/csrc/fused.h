@@ -27,172 +27,15 @@
 //     hand-off; the node phase's row blocks are dealt to the twelve waves (wf_h / wf_l below), the arithmetic is the
 //     8-wave kernel's and the outputs are bit-identical.
 // References: see common.h / streamed.h; the arithmetic per stage is identical to the streamed path.
+// This file: FusedDebug, the stamp macros of the diagnostic build, the kernel.  LDS layout, weight images and constants
+// blocks: fused_layout.h; the graph view's records and their kernels: fused_graph.h; the granule hand-off: fused_handoff.h.
 #pragma once
 #include "common.h"
-
-#ifndef AETHER_SUMS_SELECT
-#define AETHER_SUMS_SELECT 0   // diagnostic: 1 = branch-free receiver sums (a store per row, rows that end no segment into a spare row)
-#endif
-#ifndef AETHER_LATE_WAIT_FIRST
-#define AETHER_LATE_WAIT_FIRST 0   // diagnostic: 1 = a tile with a partner sender waits for the partner's rows in front of its first Linear (same arithmetic)
-#endif
-#ifndef AETHER_EARLY_PRODUCT
-#define AETHER_EARLY_PRODUCT 1     // diagnostic: 0 = the 12-wave kernels run the next layer's W_e e product inside the edge tile again (same arithmetic)
-#endif
+#include "fused_layout.h"
+#include "fused_graph.h"
+#include "fused_handoff.h"
 
 namespace {
-
-constexpr int FUSED_MAX_NODES = 32;          // two 16-node MFMA tiles
-constexpr int FUSED_MAX_EDGES = 384;         // 24 tiles (N=20 fully connected: 380 edges)
-constexpr int FUSED_MAX_TILES = FUSED_MAX_EDGES / 16;
-constexpr int LDU = 2 * H + 8;               // padded LDS row for the 128-wide update hidden
-
-// The edge MLP's two 64 x 64 contractions run as three fp16 MFMA terms on operands split into two fp16 pieces (common.h,
-// gemm_split); the weight images (2 x 8 KB each instead of 18 KB of padded fp32) fit every variant since the layer-1 features of the
-// 17-24 tile one are built two rounds at a time.
-constexpr int FUSED_WIMG = SPLIT_WIMG;                   // floats of a split image of a 64 x 64 matrix (16 KB)
-// Per-layer constants block (plain fp32, written by k_prepare_weights next to the images, copied into LDS with them): every
-// bias the kernel adds while layer l is in LDS, so that nothing between the node phase's barriers waits for global memory.
-constexpr int FUSED_CBLK = 768;                          // floats per layer (3 KiB = three LDS-DMA fragments)
-constexpr int CB_B1 = 0;                                 // [64]  bias of the tile's first Linear (layer 1: l1_msg_b0; layers 2-4: zeros)
-constexpr int CB_B2 = 64;                                // [64]  b2
-constexpr int CB_B3 = 128;                               // [128] b3
-constexpr int CB_B4 = 256;                               // [64]  b4
-constexpr int CB_B1N = 320;                              // [64]  layers 1-3: next layer's ln_msg_b0 (the P_r bias); layer 4: out_b0
-constexpr int CB_OB3 = 384;                              // [64]  layer 4: out_b3
-constexpr int CB_OB6 = 448;                              // [4]   layer 4: out_b6, zero padded
-constexpr int CB_OW6 = 512;                              // [3][64] layer 4: out_w6 rows 0..D-1; everything else in a block is zero
-template <int NW, int ROUNDS> struct FusedLds {          // offsets in floats
-    static constexpr int WSZ = FUSED_WIMG;
-    static constexpr int WA = 0;                                   // W_e  (layer 1: W1) split image
-    static constexpr int WB = WA + WSZ;                            // W2
-    static constexpr int CBLK = WB + WSZ;                          // [2][FUSED_CBLK] constants of layer l in slot l & 1
-    static constexpr int XBUF = CBLK + 2 * FUSED_CBLK;             // [32][LDW]  x_{l-1} / x_l
-    static constexpr int NBUF = XBUF + FUSED_MAX_NODES * LDW;      // [32][LDW]  n = x + mean
-    static constexpr int PS = NBUF + FUSED_MAX_NODES * LDW;        // [32][LDW]  W_s x
-    static constexpr int PR = PS + FUSED_MAX_NODES * LDW;          // [32][LDW]  W_r x + b1
-    static constexpr int NINFO = PR + FUSED_MAX_NODES * LDW;       // [32][24]   NodeInfo records
-    // one row per (receiver, tile).  A split workgroup walks its edges in two receiver-sorted runs (own senders,
-    // then the partner's: see FusedWG), whose rows are kept apart by an offset of n: 2 * 32 + 16 rows for up to
-    // 16 tiles; with 17-24 tiles (ROUNDS == 3) only unsplit workgroups are built: 32 + 24 rows.
-    static constexpr int PART_ROWS = ROUNDS == 3 ? FUSED_MAX_NODES + FUSED_MAX_TILES : 2 * FUSED_MAX_NODES + 16;
-    static constexpr int PART_SPARE = AETHER_SUMS_SELECT ? 1 : 0;  // diagnostic build: one row nobody reads
-    static constexpr int PART = NINFO + FUSED_MAX_NODES * 24;      // [PART_ROWS][LDW]  per-(receiver, tile) sums
-    static constexpr int ARRIVED = PART + (PART_ROWS + PART_SPARE) * LDW;   // [4] ints: split mode, layer whose partner rows are in LDS
-    static constexpr int SCRATCH = ARRIVED + 4;                    // aliased by the regions below
-    static constexpr int FEAT_ROWS = 16 * (ROUNDS < 2 ? ROUNDS : 2);           // per wave: two rounds of features at a time
-    static constexpr int SCRATCH_SIZE =
-        NW * FEAT_ROWS * LDF > NW * 16 * LDST ? NW * FEAT_ROWS * LDF : NW * 16 * LDST;
-    static constexpr int TOTAL = SCRATCH + SCRATCH_SIZE;
-    static constexpr int FIELD_Z = SCRATCH;                            // [32][24]  p | v | emb
-    static constexpr int FIELD_H1 = FIELD_Z + FUSED_MAX_NODES * 24;    // [32][32]
-    static constexpr int FIELD_H2 = FIELD_H1 + FUSED_MAX_NODES * 32;   // [32][32]
-    static constexpr int FIELD_F = FIELD_H2 + FUSED_MAX_NODES * 32;    // [32][4]
-    static constexpr int FIELD_W = FIELD_F + FUSED_MAX_NODES * 4;      // field-net parameters (2,080 floats)
-    static constexpr int FW0 = FIELD_W;                                // [32][22]
-    static constexpr int FW2 = FW0 + 32 * 22;                          // [32][32]
-    static constexpr int FW4 = FW2 + 32 * 32;                          // [3][32]
-    static constexpr int FB = FW4 + 3 * 32;                            // b0[32] b2[32] b4[4]
-    static constexpr int FEMB = FB + 68;                               // [3][16]
-    static constexpr int FIELD_END = FEMB + 48;
-    static constexpr int FEAT = SCRATCH;                               // [NW waves][FEAT_ROWS][LDF]
-    static constexpr int WSTAGE = SCRATCH;                             // [NW waves][16][LDST] tile staging
-    static constexpr int UBUF = SCRATCH;                               // [32][LDU]
-    static constexpr int OBUF1 = SCRATCH;                              // [32][LDW]
-    static constexpr int OBUF2 = SCRATCH + FUSED_MAX_NODES * LDW;      // [32][LDW]
-    static_assert(FIELD_END <= TOTAL, "field scratch");
-    static_assert(UBUF + FUSED_MAX_NODES * LDU <= TOTAL, "ubuf");
-    static_assert(OBUF2 + FUSED_MAX_NODES * LDW <= TOTAL, "obuf");
-    static_assert(TOTAL * 4 <= 160 * 1024, "LDS budget");
-};
-
-// Split (2 x fp16) images of the edge-MLP weights in global memory, in the exact order the kernel keeps them in LDS
-// (stage_split4): per layer l = 1..4 image A (layer 1: W1 padded to K = 32, FUSED_WIMG / 2 floats; layers 2-4: W_e)
-// and image B (W2).  k_prepare_weights (aether_hip.hip) writes them once per weight version; k_fused copies them with LDS-DMA.
-// Round 4: the node phase's weights as split images too (its GEMMs moved from the fp32 MFMA to the matrix pipe): per layer
-// W3 [128][64] (stage_split4<8, 2>), W4 [64][128] (<4, 4>), and the NEXT layer's W_s, W_r (<4, 2> each; layer 4: out_w0, out_w3).
-constexpr int FUSED_NIMG_W3 = 2 * 8 * 2 * 64 * 4, FUSED_NIMG_W4 = 2 * 4 * 4 * 64 * 4, FUSED_NIMG_WS = 2 * 4 * 2 * 64 * 4;
-constexpr int FUSED_NIMG_LAYER = FUSED_NIMG_W3 + FUSED_NIMG_W4 + 2 * FUSED_NIMG_WS;
-constexpr int FUSED_WIMG_SET = 8 * FUSED_WIMG + 4 * FUSED_NIMG_LAYER + 4 * FUSED_CBLK;   // floats reserved (layer 1's image A uses half of its slot)
-constexpr int FUSED_SPLIT_BLOCKS = 8 + 4 * 6 + 1;        // blocks of k_prepare_weights that write images (512 threads each)
-__device__ __host__ constexpr int fused_wimg_offset(int layer, int which) { return ((layer - 1) * 2 + which) * FUSED_WIMG; }
-// which: 0 W3, 1 W4, 2 W_s (next layer / out_w0), 3 W_r (next layer / out_w3)
-__device__ __host__ constexpr int fused_nimg_offset(int layer, int which) {
-    return 8 * FUSED_WIMG + (layer - 1) * FUSED_NIMG_LAYER +
-           (which == 0 ? 0 : which == 1 ? FUSED_NIMG_W3 : which == 2 ? FUSED_NIMG_W3 + FUSED_NIMG_W4 : FUSED_NIMG_W3 + FUSED_NIMG_W4 + FUSED_NIMG_WS);
-}
-__device__ __host__ constexpr int fused_cblk_offset(int layer) { return 8 * FUSED_WIMG + 4 * FUSED_NIMG_LAYER + (layer - 1) * FUSED_CBLK; }
-
-// Float c of layer's constants block (layout: CB_* above).
-__device__ __forceinline__ float fused_cblk_value(const AetherParams& P, int nd, int layer, int c) {
-    if (c < CB_B2) return layer == 1 ? P.l1_msg_b0[c] : 0.0f;
-    if (c < CB_B3) return (layer == 1 ? P.l1_msg_b2 : P.ln_msg_b2[layer - 2])[c - CB_B2];
-    if (c < CB_B4) return (layer == 1 ? P.l1_upd_b0 : P.ln_upd_b0[layer - 2])[c - CB_B3];
-    if (c < CB_B1N) return (layer == 1 ? P.l1_upd_b2 : P.ln_upd_b2[layer - 2])[c - CB_B4];
-    if (c < CB_OB3) return (layer < 4 ? P.ln_msg_b0[layer - 1] : P.out_b0)[c - CB_B1N];
-    if (layer < 4) return 0.0f;
-    if (c < CB_OB6) return P.out_b3[c - CB_OB3];
-    if (c < CB_OB6 + 4) return c - CB_OB6 < nd ? P.out_b6[c - CB_OB6] : 0.0f;
-    if (c >= CB_OW6 && c < CB_OW6 + nd * H) return P.out_w6[c - CB_OW6];
-    return 0.0f;
-}
-
-__device__ __forceinline__ void split_weights_block(const AetherParams& P, int f1, int nd, float* __restrict__ wimg, int block, int tid) {
-    if (block == FUSED_SPLIT_BLOCKS - 1) {                // the four constants blocks
-        for (int idx = tid; idx < 4 * FUSED_CBLK; idx += 512)
-            wimg[fused_cblk_offset(1) + idx] = fused_cblk_value(P, nd, idx / FUSED_CBLK + 1, idx % FUSED_CBLK);
-        return;
-    }
-    if (block >= 8) {                                     // node-phase images: six blocks per layer
-        const int nbk = block - 8, layer = nbk / 6 + 1, part = nbk % 6;
-        if (part < 2) {                                   // W3 rows 64 part ..: 1,024 float4
-            const float* w3 = layer == 1 ? P.l1_upd_w0 : P.ln_upd_w0[layer - 2];
-            float* img = wimg + fused_nimg_offset(layer, 0);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int idx = tid + 512 * j, rr = 64 * part + (idx >> 4), cc = (idx & 15) * 4;
-                stage_split4<8, 2>(img, rr, cc, ld4(w3 + (size_t)rr * H + cc));
-            }
-        } else if (part < 4) {                            // W4 [64][128], rows 32 (part - 2) ..
-            const float* w4 = layer == 1 ? P.l1_upd_w2 : P.ln_upd_w2[layer - 2];
-            float* img = wimg + fused_nimg_offset(layer, 1);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int idx = tid + 512 * j, rr = 32 * (part - 2) + (idx >> 5), cc = (idx & 31) * 4;
-                stage_split4<4, 4>(img, rr, cc, ld4(w4 + (size_t)rr * (2 * H) + cc));
-            }
-        } else {                                          // W_s / W_r of the next layer (layer 4: out_w0 / out_w3)
-            const float* src = layer < 4 ? P.ln_msg_w0[layer - 1] + (part == 4 ? 0 : H) : (part == 4 ? P.out_w0 : P.out_w3);
-            const int ld = layer < 4 ? 3 * H : H;
-            float* img = wimg + fused_nimg_offset(layer, part - 2);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int idx = tid + 512 * j, rr = idx >> 4, cc = (idx & 15) * 4;
-                stage_split4<4, 2>(img, rr, cc, ld4(src + (size_t)rr * ld + cc));
-            }
-        }
-        return;
-    }
-    const int layer = block / 2 + 1, which = block & 1;
-    float* img = wimg + fused_wimg_offset(layer, which);
-    if (which == 0 && layer == 1) {                       // W1 [64][f1] -> K padded to 32: one float4 per thread
-        const int r = tid >> 3, c0 = (tid & 7) * 4;
-        f32x4 v;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) v[b] = c0 + b < f1 ? P.l1_msg_w0[r * f1 + c0 + b] : 0.0f;
-        stage_split4<4, 1>(img, r, c0, v);
-        return;
-    }
-    const float* src;
-    int ld;
-    if (which == 0) { src = P.ln_msg_w0[layer - 2] + 2 * H; ld = 3 * H; }             // W_e = W1[:, 128:192]
-    else { src = layer == 1 ? P.l1_msg_w2 : P.ln_msg_w2[layer - 2]; ld = H; }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int idx = tid + 512 * j, rr = idx >> 4, cc = (idx & 15) * 4;
-        stage_split4<4, 2>(img, rr, cc, ld4(src + (size_t)rr * ld + cc));
-    }
-}
 
 // Optional global copies of the intermediates (same layout as the streamed path's workspace), so
 // that the parity tests and (later) the backward can read them.
@@ -238,329 +81,6 @@ constexpr int FUSED_STAMPS = 512;
 #define FUSED_WSTAMP_ROWS(layer_, r_)
 #endif
 
-// One workgroup's share of a group: it sees nodes [vb, ve) (whole graphs: every sender of its edges)
-// and owns nodes [nb, ne) -- their in-edges, their node updates, their outputs.  Unsplit: own = visible.
-// Split (two workgroups per group, when there are fewer groups than half the CUs): the partner owns
-// the rest and the two exchange their P_s rows once per layer through global memory.
-// A workgroup walks its m in-edges in a LOCAL order (lorder[eb + local] = offset into the receiver-sorted
-// range): first the `na` edges whose sender it owns, then the edges from the partner's nodes, each run
-// receiver-sorted (unsplit: na = m, the identity).  Tiles of the first run need nothing from the partner, so
-// the forward starts with them while the partner's rows are in flight -- and the backward starts with the
-// second run, whose sender-side sums the partner waits for.
-// goff: the view's granule block (12-wave kernel, tagged-granule hand-off): its byte offset from the hand-off flags, 0 when
-// the view has none; the same in every workgroup of a view.
-struct FusedWG { int vb, ve, nb, ne, tile0, partner, na, eb, m, goff, pad2, pad3; };   // eb, m: first in-edge (sorted position) and in-edge count of [nb, ne)
-struct FusedTile { int wg, t; };             // workgroup descriptor index, tile index within the workgroup
-
-// Local edge order of every workgroup (one block per workgroup; m <= FUSED_MAX_EDGES <= blockDim.x) and the
-// local index ranges of every own node's in-edges in the two runs: nrange[node] = {a_beg, a_end, b_beg, b_end}.
-__global__ void __launch_bounds__(512)
-k_graph_lorder(FusedWG* __restrict__ wgdesc, const int32_t* __restrict__ send_s, const int32_t* __restrict__ recv_s,
-               const int32_t* __restrict__ perm, const int32_t* __restrict__ rowptr, int32_t* __restrict__ lorder,
-               int4* __restrict__ ledge, int32_t* __restrict__ nrange) {
-    __shared__ int wsum[2][8];
-    __shared__ int cnt_a[FUSED_MAX_NODES + 1], cnt_b[FUSED_MAX_NODES + 1];
-    const FusedWG wg = wgdesc[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int eb = rowptr[wg.nb], m = rowptr[wg.ne] - eb, n = wg.ne - wg.nb;
-    const bool valid = tid < m;
-    const bool split = wg.partner >= 0;
-    const int snd = valid ? send_s[eb + tid] : -1;
-    const bool own = valid && (!split || (snd >= wg.nb && snd < wg.ne));
-    const bool oth = valid && !own;
-    const unsigned long long bo = __ballot(own), bt = __ballot(oth);
-    const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    if (lane == 0) { wsum[0][wave] = __popcll(bo); wsum[1][wave] = __popcll(bt); }
-    if (tid <= FUSED_MAX_NODES) { cnt_a[tid] = 0; cnt_b[tid] = 0; }
-    __syncthreads();
-    int base_o = 0, base_t = 0, na = 0;
-    for (int w = 0; w < 8; ++w) {
-        if (w < wave) { base_o += wsum[0][w]; base_t += wsum[1][w]; }
-        na += wsum[0][w];
-    }
-    // ledge: the same order with everything the forward kernel's feature phase looks up per edge in one 16-byte record
-    // {sorted position, sender, receiver, original edge}: one round trip instead of three dependent ones (k_fused, P2)
-    if (valid) {
-        const int pos = own ? base_o + __popcll(bo & below) : na + base_t + __popcll(bt & below);
-        lorder[eb + pos] = tid;
-        ledge[eb + pos] = make_int4(eb + tid, snd, recv_s[eb + tid], perm[eb + tid]);
-    }
-    if (tid == 0) wgdesc[blockIdx.x].na = na;
-    // per-node run lengths (thread per own node, a handful of edges each), then a serial prefix
-    if (tid < n) {
-        int ca = 0, cb = 0;
-        for (int k = rowptr[wg.nb + tid]; k < rowptr[wg.nb + tid + 1]; ++k) {
-            const int sd = send_s[k];
-            if (!split || (sd >= wg.nb && sd < wg.ne)) ++ca; else ++cb;
-        }
-        cnt_a[tid] = ca; cnt_b[tid] = cb;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int pa = 0, pb = na;
-        for (int s = 0; s < n; ++s) {
-            int32_t* o = nrange + 4 * (int64_t)(wg.nb + s);
-            o[0] = pa; o[1] = pa + cnt_a[s]; o[2] = pb; o[3] = pb + cnt_b[s];
-            pa += cnt_a[s]; pb += cnt_b[s];
-        }
-    }
-}
-
-// Per-tile structure of a workgroup's edge list in LOCAL order, built once with the graph: one record of
-// FUSED_TREC dwords per tile, the same for all 64 lanes of the tile's wave (k_fused keeps it in scalar registers).
-// A segment = consecutive rows with one receiver inside one run; its partial row is receiver + tile (+ n in the
-// second run), at most 2 * 32 + 15 < 256.
-//   dword 0      bit k: row k is the last row of its segment (padding rows end nothing)
-//   dword 1      number of segments
-//   dwords 2-5   partial row of segment s in byte s (segment order = row order), 0xFF behind the last segment
-//   dwords 6, 7  zero
-constexpr int FUSED_TREC = 8;
-__global__ void __launch_bounds__(64)
-k_graph_tiles(const FusedTile* __restrict__ tdesc, const FusedWG* __restrict__ wgdesc,
-              const int32_t* __restrict__ recv_s, const int32_t* __restrict__ rowptr,
-              const int32_t* __restrict__ lorder, uint32_t* __restrict__ trec) {
-    const FusedTile T = tdesc[blockIdx.x];
-    const FusedWG wg = wgdesc[T.wg];
-    const int eb = rowptr[wg.nb], m = rowptr[wg.ne] - eb, n = wg.ne - wg.nb;
-    const int na = wg.na;
-    const int lane = threadIdx.x, i = lane & 15, q = lane >> 4;
-    const int local = 16 * T.t + i;
-    const bool valid = local < m;
-    const int rcv = valid ? recv_s[eb + lorder[eb + local]] - wg.nb : -1;
-    // row i ends its segment when the next row is padding, has another receiver or opens the second run
-    const int next = __shfl_down(rcv, 1, 16);
-    const bool ends = valid && (i == 15 || next != rcv || local + 1 == na);
-    const unsigned emask = (unsigned)__ballot(q == 0 && ends) & 0xFFFFu;
-    const int second = (wg.partner >= 0 && local >= na) ? n : 0;
-    const int myrow = rcv + T.t + second;                 // (meaningful on rows that end a segment)
-    // lane j < FUSED_TREC assembles dword j; the row lookups run on all lanes (shuffles)
-    const int j = lane & (FUSED_TREC - 1);
-    unsigned w = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        const int seg = 4 * (j - 2) + b;                  // dwords 2-5: segments 0..15
-        unsigned mm = emask;
-        for (int t = 0; t < seg && mm != 0; ++t) mm &= mm - 1;
-        const bool exists = seg >= 0 && seg < 16 && mm != 0;
-        const int k = mm != 0 ? __ffs(mm) - 1 : 0;
-        const int row = __shfl(myrow, k);
-        w |= (exists ? (unsigned)row & 0xFFu : 0xFFu) << (8 * b);
-    }
-    if (j == 0) w = emask;
-    if (j == 1) w = (unsigned)__popc(emask);
-    if (j >= 6) w = 0;
-    if (lane < FUSED_TREC) trec[(size_t)blockIdx.x * FUSED_TREC + lane] = w;
-}
-
-// The same structure for the whole receiver-sorted edge list (tile t = sorted positions 16t..16t+15),
-// one word per lane, for the streamed edge kernels (streamed.h::tile_receiver_sums):
-// bits 0-3 segment-matrix column; per result register r4: first row of segment 4q+r4 (4 bits), valid (1 bit).
-__device__ inline void graph_gtile(const int32_t* __restrict__ recv_s, int64_t n_edges, uint32_t* __restrict__ gsel,
-                                   int64_t tile, int lane) {
-    const int i = lane & 15, q = lane >> 4;
-    const int64_t k = tile * 16 + i;
-    const bool valid = k < n_edges;
-    const int rcv = valid ? recv_s[k] : -1;
-    const int prev = __shfl_up(rcv, 1, 16);
-    const unsigned smask = (unsigned)__ballot(q == 0 && i > 0 && rcv != prev) & 0xFFFFu;
-    const unsigned vmask = (unsigned)__ballot(q == 0 && valid) & 0xFFFFu;
-    unsigned w = 0;
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) {
-        const int edge = 4 * s4 + q;
-        const int seg_of_edge = __popc(smask & ((2u << edge) - 1u));
-        if (((vmask >> edge) & 1u) && seg_of_edge == i) w |= 1u << s4;
-    }
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-        const int seg = 4 * q + r4;
-        unsigned mm = smask;
-        int s0 = 0;
-        bool exists = true;
-        for (int t = 0; t < seg; ++t) {
-            if (mm == 0) { exists = false; break; }
-            s0 = __ffs(mm) - 1;
-            mm &= mm - 1;
-        }
-        const unsigned ok = (exists && ((vmask >> s0) & 1u)) ? 16u : 0u;
-        w |= ((unsigned)s0 | ok) << (4 + 5 * r4);
-    }
-    gsel[(size_t)tile * 64 + lane] = w;
-}
-
-__global__ void __launch_bounds__(64)
-k_graph_gtiles(const int32_t* __restrict__ recv_s, int64_t n_edges, uint32_t* __restrict__ gsel) {
-    graph_gtile(recv_s, n_edges, gsel, (int64_t)blockIdx.x, threadIdx.x);
-}
-
-// ---------------------------------------------------------------- hand-off as tagged granules (12-wave kernel)
-// Split mode, k_fused<D, 12, 1, false, true>: the two workgroups of a group hand their P_s rows over as 8-byte granules
-// {tag, fp32 bits} (cdna_hip_programming.md Guideline 16, form R2: "the data IS the flag") -- no flag, no drain of the
-// stores, no order between them.  The granule of column c of node g for the hand-off behind layer l (tag l, row l - 1 of
-// the node's three) lies at flags + goff + ((3 g + l - 1) * H + c) * 8 in the graph view: zero between launches, written
-// once per launch, zeroed again by its reader.  Free functions, called from k_fused<D, 12, 1, false, true> only.
-constexpr int GRAN_ROW = H * 8, GRAN_NODE = 3 * GRAN_ROW;      // bytes of one row of granules, of a node's three rows
-typedef unsigned int gran_u32x4 __attribute__((ext_vector_type(4)));
-
-// descriptor of the granules of a workgroup's visible nodes [vb, vb + nv) (rows in the numbering of ninfo / psb)
-__device__ __forceinline__ auto gran_rsrc(int* flags, int goff, int vb, int nv) {
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(flags) + goff + (int64_t)vb * GRAN_NODE, 0, nv * GRAN_NODE,
-                                             0x00020000);
-}
-
-// Producer (step 4 of layers 1-3): the lane's four columns c0 .. c0 + 3 of visible row `row` as four granules, two 16-byte
-// sc1 stores (the 8-byte halves of such a store land whole: MI355X_MICROARCH.md, visibility).  Nothing waits for them and
-// nothing signals them: the partner reads until it sees the tags.
-template <class Rsrc>
-__device__ __forceinline__ void gran_publish(Rsrc rsrc, int row, int c0, int layer, f32x4 val) {
-    const unsigned tag = (unsigned)layer;
-    const gran_u32x4 g01 = {tag, __float_as_uint(val[0]), tag, __float_as_uint(val[1])};
-    const gran_u32x4 g23 = {tag, __float_as_uint(val[2]), tag, __float_as_uint(val[3])};
-    const int voff = row * GRAN_NODE + c0 * 8, soff = (layer - 1) * GRAN_ROW;
-    __builtin_amdgcn_raw_buffer_store_b128(g01, rsrc, voff, soff, 16);          // aux 16 = sc1
-    __builtin_amdgcn_raw_buffer_store_b128(g23, rsrc, voff + 16, soff, 16);
-}
-
-// Consumer (start of the edge phase of layers 2-4), ONE wave: re-read the partner's rows -- the visible rows outside
-// [off, off + n) -- of the hand-off behind layer - 1, every 16-byte piece {tag, value, tag, value}, NL pieces per lane, all
-// in flight together, ONE wait per pass, until every tag says layer - 1; the pass that finds them all carries the values
-// already, and they go to the rows of psb.  sc1 loads, the only loads of those bytes in the launch.  Bounded by TIME like
-// the flag poll of the other protocol (5 s of the 100 MHz wall clock) with the same error path: the host-mapped word and
-// arrived[1].  Five pieces per lane cover 10 partner rows (every split of N <= 20 but the most uneven); more rows, a
-// second sweep.
-template <class Rsrc, class LdsWord>
-__device__ __forceinline__ void gran_receive(Rsrc rsrc, int layer, int nv, int n, int off, int lane, float* psb,
-                                             LdsWord* arrived, int* errword) {
-    constexpr int NL = 5;
-    const int npieces = (nv - n) * (H / 2);
-    const unsigned tag = (unsigned)(layer - 1);
-    const int soff = (layer - 2) * GRAN_ROW;
-    for (int base = 0; base < npieces; base += 64 * NL) {
-        int src[NL];
-#pragma unroll
-        for (int j = 0; j < NL; ++j) {
-            // every load is unconditional on a clamped piece (piece 0 exists: there is a partner row)
-            const int idx = base + 64 * j + lane, idc = idx < npieces ? idx : 0;
-            int slot = idc >> 5;
-            if (slot >= off) slot += n;
-            src[j] = slot * GRAN_NODE + (idc & 31) * 16;
-        }
-        gran_u32x4 v[NL];
-        unsigned spins = 0;
-        unsigned long long t_first = 0;
-        bool gave_up = false;
-        for (;;) {
-            asm volatile("" ::: "memory");                      // a pass loads again: nothing is carried over from the last one
-#pragma unroll
-            for (int j = 0; j < NL; ++j) v[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, src[j], soff, 16);   // aux 16 = sc1
-            // one wait that the compiler's wait-count pass sees, nothing scheduled across it, every loaded value named behind it
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_waitcnt(0x0F70);
-            __builtin_amdgcn_sched_barrier(0);
-            bool ok = true;
-#pragma unroll
-            for (int j = 0; j < NL; ++j) {
-                asm volatile("" : "+v"(v[j]));
-                ok = ok && v[j][0] == tag && v[j][2] == tag;
-            }
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(1);
-            if ((++spins & 1023u) == 0) {
-                const unsigned long long now = wall_clock64();
-                if (t_first == 0) t_first = now;
-                if (now - t_first <= 500000000ull) continue;
-                // partner not resident: give up, never hang -- and say so (see the flag poll in k_fused)
-                if (lane == 0) {
-                    if (errword) __hip_atomic_store(errword, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    arrived[1] = 1;
-                }
-                gave_up = true;
-                break;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NL; ++j) {
-            if (base + 64 * j + lane < npieces) {
-                const int row = src[j] / GRAN_NODE, c = ((src[j] % GRAN_NODE) >> 4) * 2;
-                *reinterpret_cast<f32x2*>(psb + row * LDW + c) = f32x2{__uint_as_float(v[j][1]), __uint_as_float(v[j][3])};
-            }
-        }
-        if (gave_up) break;                                     // no second wait
-    }
-}
-
-// Re-arm (after the layer-4 edge phase), `nthreads` threads of which this is thread t: zero the granules this workgroup
-// consumed -- the partner's rows, all three of a node lie behind one another.  Every one of them was seen with its tag (or
-// the launch has reported an error), so the partner's store of this launch is in memory before this one; the next launch
-// starts behind it.
-template <class Rsrc>
-__device__ __forceinline__ void gran_rearm(Rsrc rsrc, int nv, int n, int off, int t, int nthreads) {
-    constexpr int PIECES = GRAN_NODE / 16;
-    const gran_u32x4 zero = {0u, 0u, 0u, 0u};
-    for (int idx = t; idx < (nv - n) * PIECES; idx += nthreads) {
-        int slot = idx / PIECES;
-        const int piece = idx - slot * PIECES;
-        if (slot >= off) slot += n;
-        __builtin_amdgcn_raw_buffer_store_b128(zero, rsrc, slot * GRAN_NODE + piece * 16, 0, 16);   // aux 16 = sc1
-    }
-}
-
-// gemm_split (common.h) for a wave that has nobody to hide its latencies behind (the early product of the 12-wave
-// kernels, in the node phase), in a fixed schedule that keeps 16 registers of weight fragments: the MBN row blocks go two by
-// two, a pair's six MFMAs alternate between its two accumulators (no MFMA waits for the one in front of it), and the next
-// pair's w_lo / w_hi fragments are requested as soon as this pair's have been read for the last time.  Left to the
-// compiler the first k block ran as four chains of three dependent MFMAs with an LDS round trip in front of each.
-// Every accumulator sees the same products in the same order as in gemm_split_core (per k block: w_lo x_hi, w_hi x_lo,
-// w_hi x_hi), and the operand scale is gemm_split_keep's: the same bits.
-template <int MBN, int KBN>
-__device__ __forceinline__ void gemm_split_paired(const float* __restrict__ img, const f32x4 (&act)[2 * KBN], f32x4 (&acc)[MBN], int lane) {
-    static_assert(MBN % 2 == 0, "row blocks go in pairs");
-    constexpr int TERM = MBN * KBN * 64, NG = KBN * (MBN / 2);
-    const f16x8* w = reinterpret_cast<const f16x8*>(img);
-    const SplitScale sc = split_scale_of(act);
-    f32x4 x[2 * KBN];
-#pragma unroll
-    for (int b = 0; b < 2 * KBN; ++b) x[b] = act[b];
-    if (sc.on) {                                                // (wave-uniform)
-#pragma unroll
-        for (int b = 0; b < 2 * KBN; ++b) x[b] = x[b] * sc.s;
-#pragma unroll
-        for (int mb = 0; mb < MBN; ++mb) acc[mb] = acc[mb] * sc.s;
-    }
-    // group g = (k block g / (MBN / 2), row blocks 2 (g % (MBN / 2)) and + 1)
-    auto frag = [&](int g, int j, bool lo) -> f16x8 {
-        const int kb = g / (MBN / 2), mb = 2 * (g % (MBN / 2)) + j;
-        return w[(lo ? TERM : 0) + (mb * KBN + kb) * 64 + lane];
-    };
-    f16x8 xh[KBN], xl[KBN];
-    f16x8 wl0 = frag(0, 0, true), wl1 = frag(0, 1, true), wh0 = frag(0, 0, false), wh1 = frag(0, 1, false);
-    split8(x[0], x[1], xh[0], xl[0]);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        const int kb = g / (MBN / 2), m0 = 2 * (g % (MBN / 2)), m1 = m0 + 1;
-        __builtin_amdgcn_sched_barrier(0);
-        acc[m0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl0, xh[kb], acc[m0], 0, 0, 0);
-        acc[m1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl1, xh[kb], acc[m1], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (g + 1 < NG) { wl0 = frag(g + 1, 0, true); wl1 = frag(g + 1, 1, true); }
-        // the next k block's pieces: vector-ALU work next to this pair's last MFMAs
-        if (g + 1 < NG && (g + 1) % (MBN / 2) == 0) split8(x[2 * (kb + 1)], x[2 * (kb + 1) + 1], xh[kb + 1], xl[kb + 1]);
-        acc[m0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh0, xl[kb], acc[m0], 0, 0, 0);
-        acc[m1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh1, xl[kb], acc[m1], 0, 0, 0);
-        acc[m0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh0, xh[kb], acc[m0], 0, 0, 0);
-        acc[m1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh1, xh[kb], acc[m1], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (g + 1 < NG) { wh0 = frag(g + 1, 0, false); wh1 = frag(g + 1, 1, false); }
-    }
-    if (sc.on) {
-#pragma unroll
-        for (int mb = 0; mb < MBN; ++mb) acc[mb] = acc[mb] * sc.inv_s;
-    }
-}
-
-#ifndef AETHER_R3_DEFER
-#define AETHER_R3_DEFER 0      // diagnostic: 1 = three-tile variants request the node-phase weights after the tile loop (spill-free, slower)
-#endif
 template <int D, int NW, int ROUNDS, bool KEEP, bool GRAN = false>
 __global__ void __launch_bounds__(NW * 64)
 k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ vel,
@@ -579,7 +99,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     // share one set of fragment registers (wf_h / wf_l below, DESIGN.md 4.1 "Wave roles in the node phase").
     static_assert(NW == 8 || NW == 12, "waves 0-7 run the node phase; NW == 12 adds four waves that run step 3 (DESIGN.md 4.1)");
     static_assert(NW == 8 || (ROUNDS == 1 && !KEEP), "the 12-wave kernel owns one tile per wave and saves nothing for the backward");
-    // GRAN (12 waves, split views): the own P_s rows go to the partner as tagged granules (gran_* above) instead of rows +
+    // GRAN (12 waves, split views): the own P_s rows go to the partner as tagged granules (fused_handoff.h) instead of rows +
     // flag.  An instantiation holds ONE of the two protocols -- with both, the scalar registers of the unused one pushed
     // three dozen others into vector-register lanes, read back at the top of every layer (+1.0 us per step).  Both
     // workgroups of a pair run the same launch, so the two protocols never meet.
@@ -590,7 +110,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     // the message tile, so the 12-wave kernels (EARLY) compute it under the previous layer's node phase, where the
     // matrix pipe is idle, and keep it in the tile's registers: e[0] is dead behind the product.
     constexpr bool LATE = NW == 12 || ROUNDS == 2;
-    constexpr bool EARLY = NW == 12 && AETHER_EARLY_PRODUCT;
+    constexpr bool EARLY = NW == 12;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* wA = smem + L::WA;
     float* wB = smem + L::WB;
@@ -1321,18 +841,18 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             }
         };
         auto front_act = [&](int r, f32x4 (&acc)[4], f32x4 (&h1)[4], bool last) {
-            if (last && !(AETHER_R3_DEFER && ROUNDS >= 3)) issue_loads(1);
+            if (last) issue_loads(1);
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) h1[mb] = silu4(acc[mb]);
         };
         auto back = [&](int r, const f32x4 (&h1)[4], bool last) {
             const int tile = NW * r + wave;
             f32x4 acc2[4];
-            if (last && !(AETHER_R3_DEFER && ROUNDS >= 3)) issue_loads(2);
+            if (last) issue_loads(2);
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) acc2[mb] = ld4(cb + CB_B2 + 16 * mb + 4 * q);
             gemm_split<4, 2>(wB, h1, acc2, lane);
-            if (last && !(AETHER_R3_DEFER && ROUNDS >= 3)) issue_loads(3);
+            if (last) issue_loads(3);
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) e[r][mb] = silu4(acc2[mb]);
             if constexpr (KEEP) {
@@ -1369,27 +889,16 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
 #pragma unroll
                 for (int k = 0; k < 16; ++k) {
                     sum += cv[k];
-#if AETHER_SUMS_SELECT
-                    // branch-free form: every row stores, rows that end nothing into the spare row behind PART
-                    const bool end = (ends >> k) & 1u;
-                    const unsigned row = end ? (unsigned)lo & 0xFFu : (unsigned)L::PART_ROWS;
-                    pcol[row * LDW] = sum;
-                    sum = end ? 0.0f : sum;
-                    const unsigned long long nlo = (lo >> 8) | (hi << 56), nhi = hi >> 8;
-                    lo = end ? nlo : lo;
-                    hi = end ? nhi : hi;
-#else
                     if ((ends >> k) & 1u) {
                         pcol[((unsigned)lo & 0xFFu) * LDW] = sum;
                         sum = 0.0f;
                         lo = (lo >> 8) | (hi << 56);
                         hi >>= 8;
                     }
-#endif
                 }
             }
             __builtin_amdgcn_wave_barrier();
-            if (last && !(AETHER_R3_DEFER && ROUNDS >= 3)) issue_loads(4);
+            if (last) issue_loads(4);
         };
         {
             const int nvalid = n_tiles > wave ? (n_tiles - wave + NW - 1) / NW : 0;    // wave-uniform
@@ -1416,7 +925,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                     // rounding and the wait in front of the tile (HISTORY R17); three-tile kernels run unsplit views only.
                     const bool late_tile = LATE && partner_tile;
                     FUSED_WSTAMP(layer, r, 0);
-                    if constexpr (!LATE || AETHER_LATE_WAIT_FIRST) {
+                    if constexpr (!LATE) {
                         if (partner_tile && !have_rows) {
                             wait_partner_rows();
                             have_rows = true;
@@ -1439,9 +948,6 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                     back(r, h1, last);
                     FUSED_WSTAMP(layer, r, 5);
                 }
-            }
-            if constexpr (AETHER_R3_DEFER && ROUNDS >= 3) {
-                if (nvalid > 0) { issue_loads(1); issue_loads(2); issue_loads(3); issue_loads(4); }
             }
         }
         FUSED_STAMP(4 + 8 * (layer - 1) + 2);

@@ -83,7 +83,7 @@ struct FbLayer {
     const float* msg_w2; const float* msg_b2;
     const float* upd_w0; const float* upd_b0;            // W3 [128][64], b3
     const float* w4t; const float* w3t; const float* w2t; const float* w0t;     // transposed copies (k_transpose)
-    const float* img_e; const float* img_2;  // the forward's split images of W_e (layer 1: W1) and W2 (fused.h, fused_wimg_offset)
+    const float* img_e; const float* img_2;  // the forward's split images of W_e (layer 1: W1) and W2 (fused_layout.h, fused_wimg_offset)
     float* U; float* DPU; float* DPS; float* DPR;        // row tensors of the node-level weight-gradient products
     float* DXout;              // dL/dx_{l-1} (layers 2-4)
 };
@@ -318,7 +318,7 @@ k_fused_bwd(FbArgs A) {
     for (int r = 0; r < ROUNDS; ++r) {
         const int local = 16 * (NWV * r + wave) + i;
         const bool ok = local < m;
-        // one record per edge in local order (fused.h, k_graph_lorder): {sorted position, sender, receiver, original edge};
+        // one record per edge in local order (fused_graph.h, k_graph_lorder): {sorted position, sender, receiver, original edge};
         // a padding row borrows the slots of the workgroup's first edge (its contributions are masked by ke < 0)
         const int4 le = m > 0 ? A.ledge[eb + (ok ? local : 0)] : make_int4(eb, vb, nb, 0);
         ke[r] = ok ? le.x : -1;

@@ -12,6 +12,7 @@
 // A list is ordered in LDS by counting, for every element, the smaller ones: the order of the result is a function of
 // (key, value) alone, whatever order the atomics arrived in.  Integers only.  No kernel reads its grid or block size.
 #pragma once
+#include "fused_graph.h"
 
 namespace {
 
@@ -167,7 +168,7 @@ k_gb_recv(const int64_t* __restrict__ send, int64_t n_nodes, const int32_t* __re
 }
 
 // Workgroups [0, n_nodes): the out-edges of one sender each (sorted positions, ascending).  The workgroups behind
-// them: one tile of the streamed kernels' tile table each (fused.h, graph_gtile).
+// them: one tile of the streamed kernels' tile table each (fused_graph.h, graph_gtile).
 __global__ void __launch_bounds__(64)
 k_gb_send(int n_nodes, const int32_t* __restrict__ srowptr, int32_t* __restrict__ sperm,
           const int32_t* __restrict__ recv_s, int64_t n_edges, uint32_t* __restrict__ gsel) {

@@ -14,14 +14,13 @@ import torch
 
 from conftest import load_state_dict, scale_rel_err
 from aether_amd import _lib
-from aether_amd.nn.state2state.aether import Aether
 from aether_amd.synthetic import make_batch
 from oracle import aether_oracle as O
+from fused_cases import KERNELS, fused_model, oracle_of, run_model, to_device
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
 GTOL = 5e-5
-KERNELS = {"inference": _lib.FLAG_FORCE_FUSED, "keep": _lib.FLAG_FORCE_FUSED | _lib.FLAG_KEEP_INTERMEDIATES}
 # (D, N, B): split pairs with one node tile, two rounds (2-D, 3-D); one round; three rounds with two node tiles, unsplit;
 # split pairs with fewer than 16 tiles
 SHAPES = [(2, 20, 2), (3, 20, 2), (2, 5, 3), (2, 18, 130), (2, 12, 2)]
@@ -44,34 +43,18 @@ def _batch(D, N, B):
     return make_batch(B, N, D, seed=910 + N + D)
 
 
-def _oracle64_of(sd, inp):
-    sd64 = {k: v.double() for k, v in sd.items()}
-    return O.aether_forward(sd64, inp["x"].double(), inp["vel"].double(), inp["edges"], inp["edge_attr"].double(),
-                            inp["charges"].double())
-
-
 @functools.lru_cache(maxsize=None)
 def _oracle64(D, N, B):
-    return _oracle64_of(_state_dict(D), _batch(D, N, B))
+    return oracle_of(_state_dict(D), _batch(D, N, B))
 
 
-def _model(D, flags, sd=None):
-    m = Aether(2 * D, 64, 0.0, D, device="cuda")
-    m.load_state_dict(_state_dict(D) if sd is None else sd)
-    m.flags = flags
-    return m
+def _model(D, flags):
+    return fused_model(D, flags, _state_dict(D))
 
 
 def _args(inp, dev="cuda"):
     return (inp["h"].to(dev), inp["x"].to(dev), [e.to(dev) for e in inp["edges"]], inp["vel"].to(dev),
             inp["edge_attr"].to(dev), inp["charges"].to(dev))
-
-
-def _run(m, inp):
-    with torch.no_grad():
-        out = m(*_args(inp))
-    torch.cuda.synchronize()
-    return out.cpu()
 
 
 def _info(m, inp):
@@ -93,7 +76,7 @@ def test_forward_matches_oracle(D, N, B, kernel):
         assert info.n_groups == B and tiles == 20, (info.n_groups, info.max_group_edges)
     else:
         assert info.n_groups == 2 * B and tiles < 16, (info.n_groups, info.max_group_edges)
-    out = _run(m, inp)
+    out = run_model(m, to_device(inp))
     err = scale_rel_err(out.double(), _oracle64(D, N, B))
     print(f"D={D} N={N} B={B} {kernel}: groups={info.n_groups} tiles={tiles} err={err:.2e}")
     assert torch.isfinite(out).all() and err <= TOL, err
@@ -126,7 +109,7 @@ def test_changed_biases_reach_the_next_call(how):
     D, N, B = 2, 20, 2
     inp = _batch(D, N, B)
     m = _model(D, KERNELS["inference"]).eval()
-    first = _run(m, inp)
+    first = run_model(m, to_device(inp))
     assert scale_rel_err(first.double(), _oracle64(D, N, B)) <= TOL
     sd2 = {k: v.clone() for k, v in _state_dict(D).items()}
     for k in STALE_KEYS:
@@ -138,8 +121,8 @@ def test_changed_biases_reach_the_next_call(how):
                 params[k].add_(0.3)
     else:
         m.load_state_dict(sd2)
-    second = _run(m, inp)
-    want = _oracle64_of(sd2, inp)
+    second = run_model(m, to_device(inp))
+    want = oracle_of(sd2, inp)
     moved = scale_rel_err(want, _oracle64(D, N, B))
     err = scale_rel_err(second.double(), want)
     print(f"{how}: the new biases move the oracle by {moved:.2e}; err={err:.2e}")
@@ -170,7 +153,7 @@ def test_twenty_calls_are_bit_equal():
     D, N, B = 2, 20, 2
     inp = _batch(D, N, B)
     m = _model(D, KERNELS["inference"])
-    first = _run(m, inp)
+    first = run_model(m, to_device(inp))
     assert scale_rel_err(first.double(), _oracle64(D, N, B)) <= TOL
     for _ in range(19):
-        assert torch.equal(_run(m, inp), first)
+        assert torch.equal(run_model(m, to_device(inp)), first)

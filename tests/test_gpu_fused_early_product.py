@@ -16,40 +16,15 @@ import pytest
 import torch
 
 from conftest import load_state_dict, scale_rel_err
-from aether_amd import _lib
 from aether_amd.edges import prepare_edge_attr
-from aether_amd.nn.state2state.aether import Aether
 from aether_amd.synthetic import make_batch
 from oracle import aether_oracle as O
+from fused_cases import (TOL, call_model, check_four_ways, four_ways, fused_model, no_async_error, oracle_of, run_model,
+                         set_option, tiles_of, to_device, uses_twelve_waves)
+from fused_cases import options_restored  # noqa: F401  (autouse fixture: applies to the tests of this file)
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-5
 GTOL = 5e-5
-DISPATCHES = [(0, 0), (0, 1), (1, 0), (1, 1)]            # (fused_waves12, fused_granules)
-
-
-def _option(name, value):
-    _lib.check(_lib.load().aether_set_option(name, value), "set_option")
-
-
-@pytest.fixture(autouse=True)
-def _options_restored():
-    """The options are back at their defaults after every test of this file, whatever it did."""
-    try:
-        yield
-    finally:
-        _option(b"fused_granules", 1)
-        _option(b"fused_waves12", 1)
-        _option(b"fused_split", 1)
-
-
-def _tiles(info):
-    return (info.max_group_edges + 15) // 16
-
-
-def _uses_twelve_waves(info):
-    """The dispatch rule of fused_impl for an inference launch with fused_waves12 = 1."""
-    return 9 <= _tiles(info) <= 12 and info.max_group_nodes <= 16
 
 
 @functools.lru_cache(maxsize=None)
@@ -57,67 +32,9 @@ def _inputs(D, N, B):
     return make_batch(B, N, D, seed=1800 + 10 * N + D)
 
 
-def _oracle_of(sd, inp, dtype=torch.float64, **kw):
-    c = lambda t: t.to(dtype)
-    with torch.no_grad():
-        return O.aether_forward({k: c(v) for k, v in sd.items()}, c(inp["x"]), c(inp["vel"]), inp["edges"],
-                                c(inp["edge_attr"]), c(inp["charges"]), **kw)
-
-
 @functools.lru_cache(maxsize=None)
 def _oracle(D, N, B):
-    return _oracle_of(load_state_dict(D), _inputs(D, N, B))
-
-
-def _model(D, sd=None):
-    m = Aether(2 * D, 64, 0.0, D, device="cuda")
-    m.load_state_dict(load_state_dict(D) if sd is None else sd)
-    m.flags = _lib.FLAG_FORCE_FUSED
-    return m
-
-
-def _dev(inp):
-    d = {k: v.cuda() for k, v in inp.items() if torch.is_tensor(v)}
-    d["edges"] = [e.cuda() for e in inp["edges"]]
-    return d
-
-
-def _call(m, d):
-    with torch.no_grad():
-        return m(d["h"], d["x"], d["edges"], d["vel"], d["edge_attr"], d["charges"])
-
-
-def _run(m, d):
-    out = _call(m, d)
-    torch.cuda.synchronize()
-    return out.cpu()
-
-
-def _four_ways(m, d):
-    outs = []
-    for waves12, granules in DISPATCHES:
-        _option(b"fused_waves12", waves12)
-        _option(b"fused_granules", granules)
-        outs.append(_run(m, d))
-    _option(b"fused_waves12", 1)
-    _option(b"fused_granules", 1)
-    return outs
-
-
-def _no_async_error():
-    assert _lib.load().aether_check_async_error() == 0
-
-
-def _check_four_ways(m, d, want, what):
-    outs = _four_ways(m, d)
-    for (waves12, granules), o in zip(DISPATCHES, outs):
-        err = scale_rel_err(o.double(), want)
-        print(f"{what} waves12={waves12} granules={granules}: err={err:.2e}")
-        assert torch.isfinite(o).all() and err <= TOL, (waves12, granules, err)
-    for o in outs[1:]:
-        assert torch.equal(o, outs[0])
-    _no_async_error()
-    return outs[0]
+    return oracle_of(load_state_dict(D), _inputs(D, N, B))
 
 
 # N = 20: 190 in-edges per half = 12 tiles, every wave multiplies, na = 90 (tile 5 straddles it).  N = 17: 9 tiles on 12
@@ -126,13 +43,13 @@ def _check_four_ways(m, d, want, what):
 @pytest.mark.parametrize("B", [1, 3])
 @pytest.mark.parametrize("D,N", [(2, 20), (3, 20), (2, 17)])
 def test_four_dispatches_give_the_same_bits_and_match_the_oracle(D, N, B):
-    d = _dev(_inputs(D, N, B))
-    m = _model(D)
+    d = to_device(_inputs(D, N, B))
+    m = fused_model(D)
     info = m.prepare_graph(d["edges"], B * N)[1]
     assert info.n_groups == 2 * B and info.reserved & 1, (info.n_groups, info.reserved)
-    assert _uses_twelve_waves(info), (info.max_group_nodes, info.max_group_edges)
-    assert _tiles(info) == (12 if N == 20 else 9)
-    _check_four_ways(m, d, _oracle(D, N, B), f"D={D} N={N} B={B} tiles={_tiles(info)}")
+    assert uses_twelve_waves(info), (info.max_group_nodes, info.max_group_edges)
+    assert tiles_of(info) == (12 if N == 20 else 9)
+    check_four_ways(m, d, _oracle(D, N, B), f"D={D} N={N} B={B} tiles={tiles_of(info)}")
 
 
 def test_complete_bipartite_graph_has_no_own_sender():
@@ -144,13 +61,13 @@ def test_complete_bipartite_graph_has_no_own_sender():
     rows, cols = inp["edges"]
     keep = (rows // N == cols // N) & ((rows % N < P) != (cols % N < P))
     inp = dict(inp, edges=[rows[keep], cols[keep]], edge_attr=inp["edge_attr"][keep])
-    d = _dev(inp)
-    m = _model(D)
+    d = to_device(inp)
+    m = fused_model(D)
     info = m.prepare_graph(d["edges"], B * N)[1]
-    assert info.n_groups == 2 * B and info.reserved & 1 and _uses_twelve_waves(info), \
+    assert info.n_groups == 2 * B and info.reserved & 1 and uses_twelve_waves(info), \
         (info.n_groups, info.reserved, info.max_group_nodes, info.max_group_edges)
     assert info.max_group_nodes == P and info.max_group_edges == P * P
-    _check_four_ways(m, d, _oracle_of(load_state_dict(D), inp), "K(12,12)")
+    check_four_ways(m, d, oracle_of(load_state_dict(D), inp), "K(12,12)")
 
 
 @pytest.mark.parametrize("N", [14, 12])
@@ -158,13 +75,13 @@ def test_unsplit_views_run_twelve_waves_without_a_partner(N):
     """fused_split = 0: one workgroup per graph, 182 in-edges = 12 tiles (N = 14) or 132 = 9 tiles, the last one with four
     rows (N = 12).  No hand-off at all; every edge is g + (P_r + P_s)."""
     D, B = 2, 2
-    d = _dev(_inputs(D, N, B))
-    m = _model(D)
-    _option(b"fused_split", 0)                           # read when the graph view is built
+    d = to_device(_inputs(D, N, B))
+    m = fused_model(D)
+    set_option(b"fused_split", 0)                       # read when the graph view is built
     info = m.prepare_graph(d["edges"], B * N)[1]
-    _option(b"fused_split", 1)
-    assert info.n_groups == B and not info.reserved & 1 and _uses_twelve_waves(info), (info.n_groups, info.reserved)
-    _check_four_ways(m, d, _oracle(D, N, B), f"unsplit N={N}")
+    set_option(b"fused_split", 1)
+    assert info.n_groups == B and not info.reserved & 1 and uses_twelve_waves(info), (info.n_groups, info.reserved)
+    check_four_ways(m, d, _oracle(D, N, B), f"unsplit N={N}")
 
 
 def test_two_models_alternate_on_one_view():
@@ -172,31 +89,31 @@ def test_two_models_alternate_on_one_view():
     its own launch's next image has landed finds the other model's image of a neighbouring launch there (or the
     previous layer's): the output would differ from the model's first."""
     D, N, B = 2, 20, 2
-    d = _dev(_inputs(D, N, B))
+    d = to_device(_inputs(D, N, B))
     sd_a = load_state_dict(D)
     g = torch.Generator().manual_seed(1841)
     sd_b = {k: v + 0.05 * v.abs().max() * torch.randn(v.shape, generator=g) for k, v in sd_a.items()}
-    ma, mb = _model(D, sd_a), _model(D, sd_b)
-    assert _uses_twelve_waves(ma.prepare_graph(d["edges"], B * N)[1])
-    first_a, first_b = _run(ma, d), _run(mb, d)
+    ma, mb = fused_model(D, sd=sd_a), fused_model(D, sd=sd_b)
+    assert uses_twelve_waves(ma.prepare_graph(d["edges"], B * N)[1])
+    first_a, first_b = run_model(ma, d), run_model(mb, d)
     assert scale_rel_err(first_a.double(), _oracle(D, N, B)) <= TOL
-    assert scale_rel_err(first_b.double(), _oracle_of(sd_b, _inputs(D, N, B))) <= TOL
+    assert scale_rel_err(first_b.double(), oracle_of(sd_b, _inputs(D, N, B))) <= TOL
     assert not torch.equal(first_a, first_b)
     outs = []
     for _ in range(10):
-        outs.append(_call(ma, d).clone())
-        outs.append(_call(mb, d).clone())
+        outs.append(call_model(ma, d).clone())
+        outs.append(call_model(mb, d).clone())
     torch.cuda.synchronize()
     for k, o in enumerate(outs):
         assert torch.equal(o.cpu(), first_b if k & 1 else first_a), k
-    _no_async_error()
+    no_async_error()
 
 
 def test_rollout_of_three_steps_equals_three_single_steps():
     D, N, B = 2, 20, 2
-    d = _dev(_inputs(D, N, B))
-    m = _model(D)
-    assert _uses_twelve_waves(m.prepare_graph(d["edges"], B * N)[1])
+    d = to_device(_inputs(D, N, B))
+    m = fused_model(D)
+    assert uses_twelve_waves(m.prepare_graph(d["edges"], B * N)[1])
     whole = m.rollout(d["x"], d["vel"], d["edges"], d["charges"], 3, 1.0)
     x, vel = d["x"], d["vel"]
     for t in range(3):
@@ -205,24 +122,24 @@ def test_rollout_of_three_steps_equals_three_single_steps():
         x, vel = nxt, (nxt - x) / 1.0          # the protocol's next velocity at dt = 1: one exact fp32 subtraction
     torch.cuda.synchronize()
     assert torch.isfinite(whole).all()
-    _no_async_error()
+    no_async_error()
 
 
 def test_ten_captured_steps_replayed_five_times_equal_eager():
     D, N, B = 2, 20, 3
-    m = _model(D)
-    d = _dev(_inputs(D, N, B))
-    eager = _run(m, d)
+    m = fused_model(D)
+    d = to_device(_inputs(D, N, B))
+    eager = run_model(m, d)
     assert scale_rel_err(eager.double(), _oracle(D, N, B)) <= TOL
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         for _ in range(3):
-            _call(m, d)
+            call_model(m, d)
     torch.cuda.current_stream().wait_stream(side)
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
-        outs = [_call(m, d) for _ in range(10)]
+        outs = [call_model(m, d) for _ in range(10)]
     for rep in range(5):
         for o in outs:
             o.fill_(float("nan"))
@@ -230,7 +147,7 @@ def test_ten_captured_steps_replayed_five_times_equal_eager():
         torch.cuda.synchronize()
         for k, o in enumerate(outs):
             assert torch.equal(o.cpu(), eager), (rep, k)
-    _no_async_error()
+    no_async_error()
 
 
 # layer 1's message MLP with its first Linear (weight and bias) times 2^a and its second times 2^b: its messages, the
@@ -248,13 +165,13 @@ def test_operand_scale_branch_with_zero_start_accumulators(a, b):
     for lin, p2 in (("0", a), ("2", b)):
         sd[f"gnn.layer_1.message_fn.{lin}.weight"] *= 2.0 ** p2
         sd[f"gnn.layer_1.message_fn.{lin}.bias"] *= 2.0 ** p2
-    res = _oracle_of(sd, inp, return_all=True)
+    res = oracle_of(sd, inp, return_all=True)
     rowmax = res["e1"].abs().max(dim=1).values
     assert (rowmax.min() >= 2.0 ** 15) if k > 0 else (0 < rowmax.max() < 2.0 ** -6), (rowmax.min(), rowmax.max())
-    own = scale_rel_err(_oracle_of(sd, inp, torch.float32), res["out"])
+    own = scale_rel_err(oracle_of(sd, inp, torch.float32), res["out"])
     print(f"2^{a} x 2^{b}: fp32 oracle against fp64 {own:.2e}")
     assert own <= TOL / 4
-    _check_four_ways(_model(D, sd), _dev(inp), res["out"], f"scale 2^{a} x 2^{b}")
+    check_four_ways(fused_model(D, sd=sd), to_device(inp), res["out"], f"scale 2^{a} x 2^{b}")
 
 
 def test_inf_in_one_graph_stays_in_that_graph():
@@ -268,22 +185,22 @@ def test_inf_in_one_graph_stays_in_that_graph():
     rows, cols = clean["edges"]
     bad = dict(clean, x=x, edge_attr=prepare_edge_attr(x, clean["edges"], clean["charges"][rows] * clean["charges"][cols]))
     assert torch.equal(bad["edge_attr"][rows >= N], clean["edge_attr"][rows >= N])     # the other graphs' inputs are the same
-    m = _model(D)
-    dc, db = _dev(clean), _dev(bad)
+    m = fused_model(D)
+    dc, db = to_device(clean), to_device(bad)
     info = m.prepare_graph(dc["edges"], B * N)[1]
     assert info.n_groups == 2 * B and info.reserved & 1
-    want = _four_ways(m, dc)
-    got = _four_ways(m, db)
+    want = four_ways(m, dc)
+    got = four_ways(m, db)
     mask = torch.isnan(got[0]) | torch.isinf(got[0])
     assert mask[:N].any() and not mask[N:].any()
     for w, g in zip(want, got):
         assert torch.equal(w, want[0])
         assert torch.equal(g[N:], w[N:])
         assert torch.equal(torch.isnan(g) | torch.isinf(g), mask)
-    again = _four_ways(m, dc)
+    again = four_ways(m, dc)
     for a in again:
         assert torch.equal(a, want[0])
-    _no_async_error()
+    no_async_error()
 
 
 def test_training_forward_and_all_parameter_gradients():
@@ -296,10 +213,10 @@ def test_training_forward_and_all_parameter_gradients():
     want = O.aether_forward(sdg, inp["x"].double(), inp["vel"].double(), inp["edges"], inp["edge_attr"].double(),
                             inp["charges"].double())
     torch.nn.functional.mse_loss(want, inp["target"].double()).backward()
-    d = _dev(inp)
-    m = _model(D)
-    assert _uses_twelve_waves(m.prepare_graph(d["edges"], B * N)[1])
-    inference = _run(m, d)
+    d = to_device(inp)
+    m = fused_model(D)
+    assert uses_twelve_waves(m.prepare_graph(d["edges"], B * N)[1])
+    inference = run_model(m, d)
     m.zero_grad(set_to_none=True)
     out = m(d["h"], d["x"], d["edges"], d["vel"], d["edge_attr"], d["charges"])
     torch.nn.functional.mse_loss(out, d["target"]).backward()
@@ -312,4 +229,4 @@ def test_training_forward_and_all_parameter_gradients():
         err = scale_rel_err(p.grad.detach().cpu(), sdg[k].grad)
         print(f"{k}: {err:.2e}")
         assert err <= GTOL, (k, err)
-    _no_async_error()
+    no_async_error()

@@ -21,6 +21,7 @@ from conftest import load_state_dict, scale_rel_err
 from aether_amd.edges import prepare_edge_attr
 from aether_amd.synthetic import make_batch
 from oracle import aether_oracle as O
+from fused_cases import KERNELS, fused_model, oracle_of, run_model, to_device
 
 TOL = 1e-5
 GTOL = 5e-5
@@ -85,10 +86,7 @@ def _dims(inp):
 @functools.lru_cache(maxsize=None)
 def _want64(name):
     inp = _case(name)
-    sd64 = {k: v.double() for k, v in load_state_dict(_dims(inp)).items()}
-    with torch.no_grad():
-        return O.aether_forward(sd64, inp["x"].double(), inp["vel"].double(), inp["edges"], inp["edge_attr"].double(),
-                                inp["charges"].double())
+    return oracle_of(load_state_dict(_dims(inp)), inp)
 
 
 @functools.lru_cache(maxsize=None)
@@ -255,30 +253,6 @@ def test_fp32_oracle_stays_below_a_quarter_of_the_gradient_bar(name):
 
 
 # ------------------------------------------------------------------------------------------------------ on the GPU
-def _kernels():
-    from aether_amd import _lib
-    return {"inference": _lib.FLAG_FORCE_FUSED, "keep": _lib.FLAG_FORCE_FUSED | _lib.FLAG_KEEP_INTERMEDIATES}
-
-
-def _model(D, flags):
-    from aether_amd.nn.state2state.aether import Aether
-    m = Aether(2 * D, 64, 0.0, D, device="cuda")
-    m.load_state_dict(load_state_dict(D))
-    m.flags = flags
-    return m
-
-
-def _dev(inp):
-    d = {k: v.cuda() for k, v in inp.items() if torch.is_tensor(v)}
-    d["edges"] = [e.cuda() for e in inp["edges"]]
-    return d
-
-
-def _run(m, d):
-    with torch.no_grad():
-        out = m(d["h"], d["x"], d["edges"], d["vel"], d["edge_attr"], d["charges"])
-    torch.cuda.synchronize()
-    return out.cpu()
 
 
 @pytest.mark.gpu
@@ -286,13 +260,13 @@ def _run(m, d):
 @pytest.mark.parametrize("name", list(CASES))
 def test_forward_matches_the_fp64_oracle(name, kernel):
     inp = _case(name)
-    m = _model(_dims(inp), _kernels()[kernel])
-    d = _dev(inp)
+    m = fused_model(_dims(inp), KERNELS[kernel])
+    d = to_device(inp)
     info = m.prepare_graph(d["edges"], inp["x"].shape[0])[1]
     f = _facts(name)
     assert info.n_groups == f["workgroups"], (info.n_groups, f["workgroups"])      # the restatement is the builder's
     assert (info.max_group_edges + 15) // 16 == f["max_tiles"], (info.max_group_edges, f["max_tiles"])
-    out = _run(m, d)
+    out = run_model(m, d)
     err = scale_rel_err(out.double(), _want64(name))
     print(f"{name} {kernel}: workgroups={info.n_groups} tiles={f['max_tiles']} err={err:.2e}")
     assert torch.isfinite(out).all() and err <= TOL, err
@@ -303,10 +277,9 @@ def test_forward_matches_the_fp64_oracle(name, kernel):
 def test_training_forward_and_gradients(name):
     inp = _case(name)
     want, g64 = _oracle_grads(name, True)
-    from aether_amd import _lib
-    m = _model(_dims(inp), _lib.FLAG_FORCE_FUSED)
+    m = fused_model(_dims(inp), KERNELS["inference"])
     m.zero_grad(set_to_none=True)
-    d = _dev(inp)
+    d = to_device(inp)
     out = m(d["h"], d["x"], d["edges"], d["vel"], d["edge_attr"], d["charges"])
     torch.nn.functional.mse_loss(out, d["target"]).backward()
     torch.cuda.synchronize()
@@ -319,20 +292,19 @@ def test_training_forward_and_gradients(name):
 @pytest.mark.gpu
 def test_twenty_calls_are_bit_equal():
     inp = _case("n20_b2_d2")
-    d = _dev(inp)
-    for kernel, flags in _kernels().items():
-        m = _model(2, flags)
-        first = _run(m, d)
+    d = to_device(inp)
+    for kernel, flags in KERNELS.items():
+        m = fused_model(2, flags)
+        first = run_model(m, d)
         for _ in range(19):
-            assert torch.equal(_run(m, d), first), kernel
+            assert torch.equal(run_model(m, d), first), kernel
 
 
 @pytest.mark.gpu
 def test_rollout_of_three_steps_equals_three_rollouts_of_one():
-    from aether_amd import _lib
     inp = _case("n20_b2_d2")
-    d = _dev(inp)
-    m = _model(2, _lib.FLAG_FORCE_FUSED)
+    d = to_device(inp)
+    m = fused_model(2, KERNELS["inference"])
     whole = m.rollout(d["x"], d["vel"], d["edges"], d["charges"], 3, 1.0)
     x, vel = d["x"], d["vel"]
     for t in range(3):

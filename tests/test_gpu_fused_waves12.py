@@ -18,10 +18,10 @@ import pytest
 import torch
 
 from conftest import GOLDEN, load_state_dict, scale_rel_err
-from aether_amd import _lib
-from aether_amd.nn.state2state.aether import Aether
 from aether_amd.synthetic import make_batch
 from oracle import aether_oracle as O
+from fused_cases import fused_model, oracle_of, run_model, set_option, tiles_of, to_device, uses_twelve_waves
+from fused_cases import options_restored  # noqa: F401  (autouse fixture: applies to the tests of this file)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -31,74 +31,30 @@ SHAPES = [(2, 20, 1), (3, 20, 1), (2, 17, 1), (2, 18, 1), (2, 14, 0), (2, 13, 0)
 TILES = {(20, 1): 12, (17, 1): 9, (18, 1): 10, (14, 0): 12, (13, 0): 10, (12, 0): 9, (16, 1): 8}
 
 
-def _option(name, value):
-    _lib.check(_lib.load().aether_set_option(name, value), "set_option")
-
-
-@pytest.fixture(autouse=True)
-def _options_restored():
-    """Both options are back at their defaults after every test of this file, whatever it did."""
-    try:
-        yield
-    finally:
-        _option(b"fused_waves12", 1)
-        _option(b"fused_split", 1)
-
-
-def _uses_twelve_waves(info):
-    """The dispatch rule of fused_impl for an inference launch with fused_waves12 = 1."""
-    tiles = (info.max_group_edges + 15) // 16
-    return 9 <= tiles <= 12 and info.max_group_nodes <= 16
-
-
 @functools.lru_cache(maxsize=None)
 def _case(D, N):
     inp = make_batch(B, N, D, seed=1300 + 10 * N + D)
-    sd64 = {k: v.double() for k, v in load_state_dict(D).items()}
-    with torch.no_grad():
-        want = O.aether_forward(sd64, inp["x"].double(), inp["vel"].double(), inp["edges"], inp["edge_attr"].double(),
-                                inp["charges"].double())
-    return inp, want
-
-
-def _model(D):
-    m = Aether(2 * D, 64, 0.0, D, device="cuda")
-    m.load_state_dict(load_state_dict(D))
-    m.flags = _lib.FLAG_FORCE_FUSED
-    return m
-
-
-def _dev(inp):
-    d = {k: v.cuda() for k, v in inp.items() if torch.is_tensor(v)}
-    d["edges"] = [e.cuda() for e in inp["edges"]]
-    return d
-
-
-def _run(m, d):
-    with torch.no_grad():
-        out = m(d["h"], d["x"], d["edges"], d["vel"], d["edge_attr"], d["charges"])
-    torch.cuda.synchronize()
-    return out.cpu()
+    return inp, oracle_of(load_state_dict(D), inp)
 
 
 @pytest.mark.parametrize("D,N,split", SHAPES)
 def test_matches_the_fp64_oracle_and_the_eight_wave_kernel(D, N, split):
     inp, want = _case(D, N)
-    d = _dev(inp)
-    m = _model(D)
-    _option(b"fused_split", split)                       # read when the graph view is built
+    d = to_device(inp)
+    m = fused_model(D)
+    set_option(b"fused_split", split)                   # read when the graph view is built
     info = m.prepare_graph(d["edges"], B * N)[1]
-    _option(b"fused_split", 1)
-    tiles = (info.max_group_edges + 15) // 16
+    set_option(b"fused_split", 1)
+    tiles = tiles_of(info)
     assert tiles == TILES[(N, split)] and info.max_group_nodes <= 16, (tiles, info.max_group_nodes)
     assert info.n_groups == (2 * B if split else B) and bool(info.reserved & 1) == bool(split)
     # 8 tiles stay on k_fused<D, 8, 1>; everything else here is in the 12-wave kernel's range
-    assert _uses_twelve_waves(info) == (N != 16), (tiles, info.max_group_nodes)
-    _option(b"fused_waves12", 0)
-    eight = _run(m, d)
-    _option(b"fused_waves12", 1)
-    twelve = _run(m, d)
-    again = _run(m, d)
+    assert uses_twelve_waves(info) == (N != 16), (tiles, info.max_group_nodes)
+    set_option(b"fused_waves12", 0)
+    eight = run_model(m, d)
+    set_option(b"fused_waves12", 1)
+    twelve = run_model(m, d)
+    again = run_model(m, d)
     err = scale_rel_err(twelve.double(), want)
     print(f"D={D} N={N} split={split}: groups={info.n_groups} tiles={tiles} err={err:.2e}")
     assert torch.isfinite(twelve).all() and err <= TOL, err
@@ -108,16 +64,16 @@ def test_matches_the_fp64_oracle_and_the_eight_wave_kernel(D, N, split):
 
 def test_rollout_of_three_steps_equals_three_single_steps():
     inp, _ = _case(2, 20)
-    d = _dev(inp)
-    m = _model(2)
-    assert _uses_twelve_waves(m.prepare_graph(d["edges"], B * 20)[1])
+    d = to_device(inp)
+    m = fused_model(2)
+    assert uses_twelve_waves(m.prepare_graph(d["edges"], B * 20)[1])
     whole = m.rollout(d["x"], d["vel"], d["edges"], d["charges"], 3, 1.0)
     x, vel = d["x"], d["vel"]
     for t in range(3):
         nxt = m.rollout(x, vel, d["edges"], d["charges"], 1, 1.0)[0]
         assert torch.equal(nxt, whole[t]), t
         x, vel = nxt, (nxt - x) / 1.0          # the protocol's next velocity at dt = 1: one exact fp32 subtraction
-    _option(b"fused_waves12", 0)
+    set_option(b"fused_waves12", 0)
     eight = m.rollout(d["x"], d["vel"], d["edges"], d["charges"], 3, 1.0)
     torch.cuda.synchronize()
     assert torch.isfinite(whole).all() and torch.equal(whole, eight)
@@ -133,7 +89,7 @@ def test_dynamic_field_forward_matches_the_fp64_oracle():
                                               inp["edges"], inp["edge_attr"].double(), inp["charges"].double(), 20)
     m = DynamicFieldAether(4, 64, 0.0, 2, device="cuda")
     m.load_state_dict(sd)
-    d = _dev(inp)
+    d = to_device(inp)
 
     def run():
         with torch.no_grad():
@@ -142,7 +98,7 @@ def test_dynamic_field_forward_matches_the_fp64_oracle():
         return out.cpu()
 
     twelve = run()
-    _option(b"fused_waves12", 0)
+    set_option(b"fused_waves12", 0)
     eight = run()
     err = scale_rel_err(twelve.double(), want)
     print(f"dynamic field: err={err:.2e}")

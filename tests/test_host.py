@@ -208,6 +208,86 @@ def test_built_library_passes_the_isa_check():
             assert not [ins for ins in body if "v_accvgpr_" in ins], name
 
 
+def _isa_check():
+    import sys
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import isa_check
+    return isa_check
+
+
+def test_isa_check_only_reads_the_library_it_checks(tmp_path):
+    """llvm-objcopy --dump-section without an output file rewrites its input in place (the built library lost 64 bytes
+    and got a new mtime with every check); disassemble() and kernel_notes() hand it a throw-away output now.  On a copy
+    of the library: bytes, size and mtime are what they were, and both functions still see the code object."""
+    import hashlib
+    import shutil
+    isa_check = _isa_check()
+    _lib.load()                                                   # builds the library if it is stale
+    lib = str(tmp_path / "libcopy.so")
+    shutil.copy(_lib.LIB_PATH, lib)
+
+    def state():
+        st = os.stat(lib)
+        return hashlib.sha256(open(lib, "rb").read()).hexdigest(), st.st_size, st.st_mtime_ns
+
+    before = state()
+    notes = isa_check.kernel_notes(lib, counts=True)
+    gtiles = [k for k in notes if "k_graph_gtiles" in k]
+    assert len(notes) > 300 and len(gtiles) == 1, (len(notes), gtiles)
+    seg, hidden, priv, counts = notes[gtiles[0]]
+    assert seg >= 24 and priv == 0 and counts["vgpr_count"] > 0 and counts["sgpr_count"] > 0, notes[gtiles[0]]
+    assert set(counts) == {"vgpr_count", "sgpr_count", "agpr_count", "group_segment_fixed_size"}, counts
+    kernels = dict(isa_check.split_kernels(isa_check.disassemble(lib, gtiles)))      # one small kernel: objdump is the slow part
+    assert list(kernels) == gtiles and "s_endpgm" in kernels[gtiles[0]], list(kernels)
+    assert state() == before
+    assert sorted(os.listdir(tmp_path)) == ["libcopy.so"]
+
+
+_ISA_A = """\
+\t.text
+_Z5k_onePf:                             ; @_Z5k_onePf
+; %bb.0:
+\ts_load_dwordx2 s[0:1], s[0:1], 0x0
+\tv_mov_b32_e32 v0, 0
+\ts_waitcnt lgkmcnt(0)
+\tglobal_store_dword v0, v0, s[0:1]
+\ts_endpgm
+.Lfunc_end0:
+_Z5k_twoPf:                             ; @_Z5k_twoPf
+\tv_mov_b32_e32 v1, 1.0
+\ts_endpgm
+"""
+
+
+def test_isa_check_diff_reports_what_differs(tmp_path):
+    """isa_check.py --diff on compiler .s texts: identical texts report nothing and return 0; one changed instruction in
+    one function names that function and returns non-zero, and so does a function that one side does not have."""
+    isa_check = _isa_check()
+    a = tmp_path / "a.s"
+    a.write_text(_ISA_A)
+
+    def diff(name, text):
+        other, lines = tmp_path / name, []
+        other.write_text(text)
+        n = isa_check.diff_builds(str(a), str(other), out=lines.append)
+        assert isa_check.main([str(a), "--diff", str(other)]) == (1 if n else 0)
+        return n, lines
+
+    # comments and labels are not instructions
+    n, lines = diff("same.s", _ISA_A.replace("; %bb.0:\n", "").replace("; @_Z5k_twoPf", "; the second one"))
+    assert n == 0 and len(lines) == 1 and "2 vs 2 functions" in lines[0] and "0 differing" in lines[0], lines
+    n, lines = diff("moved.s", _ISA_A.replace("v_mov_b32_e32 v1, 1.0", "v_mov_b32_e32 v2, 1.0"))
+    assert n == 1 and len(lines) == 2 and lines[0].startswith("DIFF _Z5k_twoPf: instructions differ (2 vs 2, first at 0)"), lines
+    assert "_Z5k_onePf" not in lines[0] and "1 differing" in lines[1], lines
+    n, lines = diff("longer.s", _ISA_A.replace("\ts_waitcnt lgkmcnt(0)\n", "\ts_waitcnt lgkmcnt(0)\n\ts_nop 0\n"))
+    assert n == 1 and lines[0].startswith("DIFF _Z5k_onePf: instructions differ (5 vs 6, first at 3)"), lines
+    n, lines = diff("missing.s", _ISA_A[:_ISA_A.index("_Z5k_twoPf:")])
+    assert n == 1 and lines[0].startswith("DIFF _Z5k_twoPf: only in " + str(a)) and "2 vs 1 functions" in lines[1], lines
+    extra = _ISA_A + "_Z7k_threePf:\n\ts_endpgm\n"
+    n, lines = diff("extra.s", extra)
+    assert n == 1 and lines[0].startswith("DIFF _Z7k_threePf: only in " + str(tmp_path / "extra.s")), lines
+
+
 def test_host_side_size_functions_of_the_round_3_entries():
     """Pure host arithmetic of the C ABI (no GPU): the dropout masks lie inside the training workspace, 256-byte aligned;
     aether_dyn_step's workspace covers its four stages and refuses the sizes the step would refuse; the rollout's covers

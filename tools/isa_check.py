@@ -43,6 +43,7 @@ Scans the gfx950 disassembly of every kernel.
           step at N = 20).
 
 Usage: isa_check.py [libaether_hip.so | file.s] [--all] [--kernel SUBSTR]
+       isa_check.py [libaether_hip.so | file.s] --diff OTHER    same functions, instruction lists and notes as OTHER?
 """
 from __future__ import annotations
 
@@ -60,43 +61,49 @@ _REG = re.compile(r"\b([av])(?:\[(\d+):(\d+)\]|(\d+))")
 _LOADS = ("ds_read", "ds_load", "global_load", "buffer_load", "scratch_load", "flat_load")
 
 
-def disassemble(path: str) -> str:
-    """gfx950 disassembly of a shared library's embedded code object (or the text of a .s file)."""
-    if path.endswith(".s"):
-        return open(path).read()
+def _with_code_object(path: str, tool_args):
+    """stdout of an LLVM tool run on the gfx950 code object embedded in a shared library.  The library is only read:
+    llvm-objcopy without an output file rewrites its input in place, so it gets a throw-away one."""
     with tempfile.TemporaryDirectory() as td:
         co, fat = os.path.join(td, "dev.co"), os.path.join(td, "fat.bin")
-        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", path],
-                       check=True, capture_output=True)
-        bundler = os.path.join(LLVM, "clang-offload-bundler")
-        subprocess.run([bundler, "--type=o", "--unbundle", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                        f"--input={fat}", f"--output={co}"], check=True, capture_output=True)
-        if not os.path.exists(co) or os.path.getsize(co) == 0:
-            raise RuntimeError(f"no gfx950 code object in {path}")
-        out = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co],
-                             check=True, capture_output=True, text=True).stdout
-    return out
-
-
-def kernel_notes(path: str):
-    """{kernel name: (kernarg segment bytes, [hidden_* argument kinds])} from the code object's metadata notes."""
-    with tempfile.TemporaryDirectory() as td:
-        co, fat = os.path.join(td, "dev.co"), os.path.join(td, "fat.bin")
-        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", path],
-                       check=True, capture_output=True)
+        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", path,
+                        os.path.join(td, "discard.so")], check=True, capture_output=True)
         subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--unbundle",
                         "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"],
                        check=True, capture_output=True)
-        txt = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True,
-                             text=True).stdout
+        if not os.path.exists(co) or os.path.getsize(co) == 0:
+            raise RuntimeError(f"no gfx950 code object in {path}")
+        return subprocess.run([os.path.join(LLVM, tool_args[0]), *tool_args[1:], co], check=True, capture_output=True,
+                              text=True).stdout
+
+
+def disassemble(path: str, symbols=()) -> str:
+    """gfx950 disassembly of a shared library's embedded code object -- all of it, or the functions named in `symbols` --
+    or the text of a .s file."""
+    if path.endswith(".s"):
+        return open(path).read()
+    only = [f"--disassemble-symbols={','.join(symbols)}"] if symbols else ["-d"]
+    return _with_code_object(path, ["llvm-objdump", *only, "--no-show-raw-insn"])
+
+
+_NOTE_COUNTS = ("vgpr_count", "sgpr_count", "agpr_count", "group_segment_fixed_size")
+
+
+def kernel_notes(path: str, counts: bool = False):
+    """{kernel name: (kernarg segment bytes, [hidden_* argument kinds], private segment bytes)} from the code object's
+    metadata notes; with `counts` a fourth entry {VGPR, SGPR and AGPR counts, LDS bytes}."""
+    txt = _with_code_object(path, ["llvm-readelf", "--notes"])
     out = {}
     for blk in txt.split("  - .agpr_count:")[1:]:
+        blk = "    .agpr_count:" + blk
         name = re.search(r"\.name:\s+(\S+)", blk)
         seg = re.search(r"\.kernarg_segment_size:\s+(\d+)", blk)
         priv = re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
         if name:
             out[name.group(1)] = (int(seg.group(1)) if seg else -1, re.findall(r"\.value_kind:\s+(hidden_\w+)", blk),
                                   int(priv.group(1)) if priv else 0)
+            if counts:
+                out[name.group(1)] += ({k: int(m.group(1)) for k in _NOTE_COUNTS if (m := re.search(rf"\.{k}:\s+(\d+)", blk))},)
     return out
 
 
@@ -233,8 +240,42 @@ def check_async_lds_dest(body):
     return viol
 
 
+def diff_builds(path: str, other: str, out=print) -> int:
+    """--diff: per function, the instruction lists of two builds (libraries or .s files) and, between two libraries, the
+    kernels' notes.  Prints what differs and returns the number of differences -- the check of a change that must leave
+    the device code as it is."""
+    def load(p):
+        return dict(split_kernels(disassemble(p))), ({} if p.endswith(".s") else kernel_notes(p, counts=True))
+    (fa, na), (fb, nb) = load(path), load(other)
+    if path.endswith(".s") or other.endswith(".s"):
+        na = nb = {}
+    bad = 0
+    for name in sorted(set(fa) | set(fb)):
+        what = []
+        if name not in fa or name not in fb:
+            what.append(f"only in {path if name in fa else other}")
+        else:
+            if fa[name] != fb[name]:
+                a, b = fa[name], fb[name]
+                first = next((k for k, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
+                what.append(f"instructions differ ({len(a)} vs {len(b)}, first at {first})")
+            if na.get(name) != nb.get(name):
+                what.append(f"notes differ ({na.get(name)} vs {nb.get(name)})")
+        if what:
+            out(f"DIFF {name}: {'; '.join(what)}")
+            bad += 1
+    out(f"isa_check --diff: {len(fa)} vs {len(fb)} functions ({sum('k_fused' in n for n in fa)} vs "
+        f"{sum('k_fused' in n for n in fb)} k_fused), {len(na)} vs {len(nb)} kernel notes, {bad} differing")
+    return bad
+
+
 def main(argv):
+    other = argv[argv.index("--diff") + 1] if "--diff" in argv else None
+    if other is not None:
+        argv = [a for k, a in enumerate(argv) if k != argv.index("--diff") + 1]
     path = next((a for a in argv if not a.startswith("--")), DEFAULT_LIB)
+    if other is not None:
+        return 1 if diff_builds(path, other) else 0
     show_all = "--all" in argv
     only = argv[argv.index("--kernel") + 1] if "--kernel" in argv else None
     txt = disassemble(path)
