@@ -121,6 +121,19 @@ SIGNATURES = {
                         [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6),
     "aether_s2s_rollout": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_float, C.c_int64, C.c_int64] + [C.c_void_p] * 4 +
                            [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3),
+    "aether_s2s_charges_plan_bytes": (C.c_size_t, [C.c_int] * 7),
+    "aether_s2s_charges_plan_build": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "aether_s2s_charges_workspace_bytes": (C.c_size_t, [C.c_int] * 6 + [C.c_int64, C.c_int64]),
+    "aether_s2s_charges_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_float, C.c_int64, C.c_int64] +
+                                [C.c_void_p] * 12 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6),
+    "aether_s2s_charges_encoder_features": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 9 + [C.c_int64, C.c_int64] +
+                                            [C.c_void_p] * 7 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 2),
+    "aether_s2s_charges_rollout": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_float, C.c_int64, C.c_int64] +
+                                   [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 +
+                                   [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3),
+    "aether_s2s_charges_field_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "aether_s2s_charges_field": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                                                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "aether_s2s_markov_decoder_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64, C.c_int64]),
     "aether_s2s_markov_decoder_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64] +
                                        [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -312,17 +325,21 @@ class AetherHipError(RuntimeError):
     pass
 
 
-def load():
-    """Load the library (once).  Raises if it has not been built."""
+def load(path=None):
+    """Load the library (once).  Raises if it has not been built.  ``path``: load that build instead (an older one as a
+    timing yardstick, tools/s2s_charges_time.py --lib); entries it does not have yet stay unbound."""
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(LIB_PATH):
+    lib_path = LIB_PATH if path is None else os.path.abspath(path)
+    if not os.path.exists(lib_path):
         raise AetherHipError(
-            f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+            f"{lib_path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `python aether_amd/build.py`).  There is no CPU fallback.")
-    lib = C.CDLL(LIB_PATH)
+    lib = C.CDLL(lib_path)
     for name, (res, args) in SIGNATURES.items():
+        if path is not None and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

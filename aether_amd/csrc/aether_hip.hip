@@ -40,6 +40,7 @@
 #include "s2s_filter.h"
 #include "s2s_step.h"
 #include "s2s_markov.h"
+#include "s2s_charges.h"
 #include "dynfield.h"
 #include "s2s_dynfield.h"
 #include "knn.h"
@@ -148,6 +149,9 @@ int take_async_error() {
     if (g_async_host && *(volatile int*)g_async_host) {
         const int code = *(volatile int*)g_async_host;
         *(volatile int*)g_async_host = 0;
+        if (code == 3)
+            return fail(AETHER_EHIP, "an earlier aether_s2s_charges_* call was given a charge index outside {0, 1}: the outputs "
+                                     "of that node were filled with NaN");
         if (code == 2)
             return fail(AETHER_EHIP, "an earlier aether_dyn_step found a different number of non-zero mask entries than "
                                      "n_present: its outputs were filled with NaN");
@@ -995,6 +999,7 @@ const char* aether_last_error(void) { return g_err; }
 #include "host_seq2seq.inc"
 #include "host_s2s_step.inc"
 #include "host_s2s_markov.inc"
+#include "host_s2s_charges.inc"
 #include "host_s2s_dynfield.inc"
 #include "host_dynamicvars.inc"
 #include "host_dyn_step.inc"

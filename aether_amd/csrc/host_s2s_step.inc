@@ -28,7 +28,9 @@ struct S2SPlanLayout {
     // res1, lin2's bias permuted from c Ku + k to k h + c, and the images of lin1 and of lin2's per-type h x h blocks
     size_t m_l1p = 0, m_r1p = 0, m_b2 = 0, m_i_l1 = 0, m_i_l2[4] = {0, 0, 0, 0};
     static bool splittable(int M, int Kk) { return M % 128 == 0 && Kk % 32 == 0; }
-    S2SPlanLayout(int D, int he, int hd, int K, int R, int prior_layers = 1, int ph = 0, int markov_ku = -1, int mlp_hidden = 0) {
+    // filt_R > 0: the filter image has that many features instead of EA (the charge-aware model's folded filter, EA + 4)
+    S2SPlanLayout(int D, int he, int hd, int K, int R, int prior_layers = 1, int ph = 0, int markov_ku = -1, int mlp_hidden = 0,
+                  int filt_R = 0) {
         const S2SDims d(D);
         const bool rec = markov_ku < 0;
         const int Kr = rec ? K : 0;
@@ -36,7 +38,7 @@ struct S2SPlanLayout {
         ldg = S2S_RFG + 2 * hd;
         size_t off = 0;
         auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-        fimg = take(filt_image_bytes(d.EA, he));
+        fimg = take(filt_image_bytes(filt_R > 0 ? filt_R : d.EA, he));
         res1p = take((size_t)he * d.RFp * 4);
         bn = take((size_t)4 * he * 4);
         for (int k = 0; k < 4; ++k) p1p[k] = take(k < Kr ? (size_t)hd * d.EAp * 4 : 0);
@@ -240,6 +242,24 @@ struct S2SStepArgs : S2SSizes {
     const float* mod = nullptr;
     int64_t batch = 0;
     int num_objects = 0;
+    // The charge-aware model (host_s2s_charges.inc; null: the plain one).  fp / pp / dp then hold the chargeless slices of the
+    // widened layers, whose biases the tables below carry: the jobs of those layers take no bias vector.
+    const struct S2SChargeArgs* chg = nullptr;
+    // ext_logits [E][K] (charge-aware entries): the sample is taken from these logits and the prior (filter .. prior_fc_out) is
+    // skipped, h1 / c1 are not written: the decoder on given logits.  features_out [E][he]: the front stops behind mlp4 and
+    // leaves its rows there (the per-time-step features of the full-sequence encoder).
+    const float* ext_logits = nullptr;
+    float* features_out = nullptr;
+};
+
+// nidx [Nn] in {0, 1, 2}, eidx [E] in 0 .. 3 (k_s2s_charge_index); bias tables of field_net.0, encoder.res1, the three gates
+// (3 rows each) and present_msg_fc1[k] (4 rows); ea: the edge features with the four indicator columns [E][EA + 4]; b2: the
+// folded filter bias (its image is the plan's, EA + 4 features)
+struct S2SChargeArgs {
+    const int32_t *nidx, *eidx;
+    const float* nscale;           // [Nn]: 1, or NaN where nidx is 2 (row scale of the output MLP's last hidden layer)
+    const float *t_f0, *t_res1, *t_gr, *t_gi, *t_gn, *t_p1[4], *b2;
+    float* ea;
 };
 
 // The state a step reads and the one it writes: x [Nn][2D], dh [Nn][hd] (null with the Markov decoder, which has none),
@@ -297,8 +317,9 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
         dispatch_dim(D, [&](auto DD) {
             k_s2s_rff<decltype(DD)::value><<<dim3(rb), dim3(256), 0, st>>>(x_in, 2 * D, a.fp->B, half, wp(L.gamma), Nn);
         });
-        T.j[T.n++] = s2s_job(1, a.fp->w0, he, a.fp->b0, wp(L.gamma), he, wp(L.fh1), he, he, he, Nn);
+        T.j[T.n++] = s2s_job(1, a.fp->w0, he, a.chg ? nullptr : a.fp->b0, wp(L.gamma), he, wp(L.fh1), he, he, he, Nn);
         T.j[T.n - 1].Wimg = a.field_images ? im(P.i_f0) : nullptr;
+        if (a.chg) { T.j[T.n - 1].btab = a.chg->t_f0; T.j[T.n - 1].bidx = a.chg->nidx; T.j[T.n - 1].bstride = he; }
     }
     if (int rc = first_jobs(T)) return rc;
     if (int rc = s2s_launch_jobs(T, st)) return rc;
@@ -326,10 +347,15 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
             constexpr int Dc = decltype(DD)::value;
             k_s2s_node_prep<Dc><<<nb4, dim3(256), 0, st>>>(x_in, ext_field, fh2, w4, b4, fk, fout, wp(L.ext), wp(L.rel), wp(L.Rinv),
                                                            wp(L.relp), d.RFp, wp(L.wide), ldg, counts, Nn);
-            k_s2s_edge_prep<Dc><<<blocks(E), dim3(256), 0, st>>>(wp(L.ext), a.send, a.recv, wp(L.rel), a.polar, wp(L.ea), wp(L.eap),
-                                                                 wp(L.epos), E);
+            if (a.chg)
+                k_s2s_edge_prep_charges<Dc><<<blocks(E), dim3(256), 0, st>>>(wp(L.ext), a.send, a.recv, wp(L.rel), a.polar, a.chg->ea,
+                                                                             wp(L.eap), wp(L.epos), E, a.chg->eidx);
+            else
+                k_s2s_edge_prep<Dc><<<blocks(E), dim3(256), 0, st>>>(wp(L.ext), a.send, a.recv, wp(L.rel), a.polar, wp(L.ea), wp(L.eap),
+                                                                     wp(L.epos), E);
         });
     }
+    if (a.ext_logits == nullptr) {     // (the prior: not for the decoder on given logits)
     // ---- anisotropic edge filter (:391)
     {
         const f16x8* image = reinterpret_cast<const f16x8*>(a.plan + P.fimg);
@@ -345,9 +371,12 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
     do {                                                                                                                 \
         const size_t lds = filt_lds_bytes(RR);                                                                           \
         if (ensure_dynamic_lds(reinterpret_cast<const void*>(k_s2s_filter_split<RR>), lds)) return AETHER_EHIP;          \
-        k_s2s_filter_split<RR><<<grid, dim3(512), lds, st>>>(image, p->filt_b2, wp(L.ea), bimg, dst, he, E, L.splits, 1, (int)grid.x);   \
+        k_s2s_filter_split<RR><<<grid, dim3(512), lds, st>>>(image, filt_b2, filt_ea, bimg, dst, he, E, L.splits, 1, (int)grid.x);   \
     } while (0)
-        if (D == 2) FILT_LAUNCH(24); else FILT_LAUNCH(39);
+        const float* filt_b2 = a.chg ? a.chg->b2 : p->filt_b2;
+        const float* filt_ea = a.chg ? a.chg->ea : wp(L.ea);
+        if (a.chg) { if (D == 2) FILT_LAUNCH(28); else FILT_LAUNCH(43); }       // + the four one-hot charge features
+        else if (D == 2) FILT_LAUNCH(24); else FILT_LAUNCH(39);
 #undef FILT_LAUNCH
         // x = edge2node(edge_attr) (:393-394): planes added and in-edges summed in one pass
         k_s2s_planes_segsum<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(dst, L.splits, (int64_t)E * he, a.order, a.rowptr,
@@ -356,7 +385,9 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
     const float *bn3s = pl(P.bn), *bn3b = pl(P.bn) + he, *bn4s = pl(P.bn) + 2 * he, *bn4b = pl(P.bn) + 3 * he;
     auto one = [&](S2SJob J) { T.n = 0; T.j[T.n++] = J; return s2s_launch_jobs(T, st); };
     // + res1(rel_feat) (:395), mlp3 (RefNRIMLP, eval)
-    { S2SJob J = s2s_job(0, pl(P.res1p), d.RFp, p->res1_b, wp(L.relp), d.RFp, wp(L.X0), he, he, d.RFp, Nn); J.accumulate = 1;
+    { S2SJob J = s2s_job(0, pl(P.res1p), d.RFp, a.chg ? nullptr : p->res1_b, wp(L.relp), d.RFp, wp(L.X0), he, he, d.RFp, Nn);
+      J.accumulate = 1;
+      if (a.chg) { J.btab = a.chg->t_res1; J.bidx = a.chg->nidx; J.bstride = he; }
       T.n = 0; T.j[T.n++] = J;
       if (int rc = res1_jobs(T)) return rc;
       if (int rc = s2s_launch_jobs(T, st)) return rc; }
@@ -377,9 +408,11 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
     { S2SJob J = s2s_job(4, p->mlp4_w0 + 2 * he, 3 * he, nullptr, wp(L.eaf), he, wp(L.T1e), he, he, he, E);
       J.Wimg = im(P.i_mlp4e); J.g1 = Ps; J.i1 = a.send; J.g2 = Pr; J.i2 = a.recv;
       if (int rc = one(J)) return rc; }
-    { S2SJob J = s2s_job(4, p->mlp4_w3, he, p->mlp4_b3, wp(L.T1e), he, wp(L.X4), he, he, he, E); J.post_scale = bn4s; J.post_shift = bn4b;
+    { S2SJob J = s2s_job(4, p->mlp4_w3, he, p->mlp4_b3, wp(L.T1e), he, a.features_out ? a.features_out : wp(L.X4), he, he, he, E);
+      J.post_scale = bn4s; J.post_shift = bn4b;
       J.Wimg = im(P.i_mlp4_3);
       if (int rc = one(J)) return rc; }
+    if (a.features_out) return AETHER_OK;
     // one LSTM step per edge (:400-407), prior_fc_out (:408)
     { S2SJob J = s2s_job(0, p->lstm_w_ih, he, pl(P.lb), wp(L.X4), he, wp(L.G), 4 * R, 4 * R, he, E);      // [W_ih | W_hh] . [x | h0]
       J.W2 = p->lstm_w_hh; J.X2 = h0; J.K2 = R; J.ldw2 = R; J.ldx2 = R; J.Wimg = im(P.i_ih); J.W2img = im(P.i_hh);
@@ -407,9 +440,10 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
             cur_k = M;
         }
     }
+    }
     // ---- hard Gumbel sample (:92-98) and the per-type edge lists of the decoder
     if (edges != nullptr)
-        k_s2s_gumbel_select<<<blocks(E), dim3(256), 0, st>>>(wp(L.logits), uniform, a.tau, K, k0, edges, lists, counts, E);
+        k_s2s_gumbel_select<<<blocks(E), dim3(256), 0, st>>>(a.ext_logits ? a.ext_logits : wp(L.logits), uniform, a.tau, K, k0, edges, lists, counts, E);
     return AETHER_OK;
 }
 
@@ -427,7 +461,9 @@ int s2s_out_tail(const S2SStepArgs& a, char* ws, const DecoderParams* q, const f
         return s2s_launch_jobs(T, st);
     };
     if (int rc = one(s2s_job(2, q->out0_w, hd, q->out0_b, in, hd, wp(a.L.o1), hd, hd, hd, Nn), a.P.i_out0)) return rc;
-    if (int rc = one(s2s_job(2, q->out3_w, hd, q->out3_b, wp(a.L.o1), hd, wp(a.L.o2), hd, hd, hd, Nn), a.P.i_out3)) return rc;
+    { S2SJob J = s2s_job(2, q->out3_w, hd, q->out3_b, wp(a.L.o1), hd, wp(a.L.o2), hd, hd, hd, Nn);
+      if (a.chg) { J.scale = a.chg->nscale; J.sstride = 1; }       // 1, or NaN for a node whose charge index was out of range
+      if (int rc = one(J, a.P.i_out3)) return rc; }
     dispatch_dim(a.D, [&](auto DD) {
         k_s2s_out_globalize<decltype(DD)::value><<<dim3((unsigned)((Nn + 3) / 4)), dim3(256), 0, st>>>(
             wp(a.L.o2), q->out6_w, q->out6_b, hd, x_in, wp(a.L.Rinv), x_out, Nn);
@@ -487,9 +523,10 @@ int s2s_step_impl(const S2SStepArgs& a, char* ws, const float* x_in, const float
         return J;
     };
     auto pmsg1 = [&](int k) {
-        S2SJob J = s2s_job(2, pl(P.p1p[k]), d.EAp, q->pmsg_fc1_b[k], wp(L.eap), d.EAp, wp(L.T1p) + (size_t)k * E * hd, hd, hd,
-                           d.EAp, E);
+        S2SJob J = s2s_job(2, pl(P.p1p[k]), d.EAp, a.chg ? nullptr : q->pmsg_fc1_b[k], wp(L.eap), d.EAp,
+                           wp(L.T1p) + (size_t)k * E * hd, hd, hd, d.EAp, E);
         J.xidx = lists + (size_t)k * E; J.n_dev = counts + k; J.Wimg = im(P.i_pmsg1[k]);
+        if (a.chg) { J.btab = a.chg->t_p1[k]; J.bidx = a.chg->eidx; J.bstride = hd; }     // (row of the table: by edge id, after xidx)
         return J;
     };
     auto pmsg2 = [&](int k) {
@@ -510,16 +547,24 @@ int s2s_step_impl(const S2SStepArgs& a, char* ws, const float* x_in, const float
                                                                      wide + S2S_RFG + hd, ldg, hd);
     // GRU-style gate (:638-646): four K-concatenated products in one launch
     T.n = 0;
-    T.j[T.n++] = s2s_job(0, pl(P.wr), ldg, pl(P.br), wide, ldg, wp(L.rp), hd, hd, S2S_RFG + 2 * hd, Nn);
+    T.j[T.n++] = s2s_job(0, pl(P.wr), ldg, a.chg ? nullptr : pl(P.br), wide, ldg, wp(L.rp), hd, hd, S2S_RFG + 2 * hd, Nn);
     T.j[T.n - 1].Wimg = im(P.i_wr);
-    T.j[T.n++] = s2s_job(0, pl(P.wi), ldg, pl(P.bi), wide, ldg, wp(L.ip), hd, hd, S2S_RFG + 2 * hd, Nn);
+    T.j[T.n++] = s2s_job(0, pl(P.wi), ldg, a.chg ? nullptr : pl(P.bi), wide, ldg, wp(L.ip), hd, hd, S2S_RFG + 2 * hd, Nn);
     T.j[T.n - 1].Wimg = im(P.i_wi);
-    T.j[T.n++] = s2s_job(0, pl(P.wn), ldg, pl(P.bn_), wide, ldg, wp(L.np_), hd, hd, S2S_RFG + hd, Nn);
+    T.j[T.n++] = s2s_job(0, pl(P.wn), ldg, a.chg ? nullptr : pl(P.bn_), wide, ldg, wp(L.np_), hd, hd, S2S_RFG + hd, Nn);
     T.j[T.n - 1].Wimg = im(P.i_wn);
+    if (a.chg) {                                               // rows of the summed gate biases + the charge term
+        const float* gate_tables[3] = {a.chg->t_gr, a.chg->t_gi, a.chg->t_gn};
+        for (int g = 0; g < 3; ++g) { T.j[g].btab = gate_tables[g]; T.j[g].bidx = a.chg->nidx; T.j[g].bstride = hd; }
+    }
     T.j[T.n++] = s2s_job(0, q->hidden_h_w, hd, nullptr, wide + S2S_RFG + hd, ldg, wp(L.hh), hd, hd, hd, Nn);
     T.j[T.n - 1].Wimg = im(P.i_hh2);
     if (int rc = s2s_launch_jobs(T, st)) return rc;
-    k_s2s_gate<<<blocks(Nn * hd), dim3(256), 0, st>>>(wp(L.rp), wp(L.ip), wp(L.np_), wp(L.hh), dh_in, dh_out, Nn * hd);
+    if (a.chg)
+        k_s2s_gate_charges<<<blocks(Nn * hd), dim3(256), 0, st>>>(wp(L.rp), wp(L.ip), wp(L.np_), wp(L.hh), dh_in, dh_out, Nn * hd,
+                                                                 a.chg->nidx, hd);
+    else
+        k_s2s_gate<<<blocks(Nn * hd), dim3(256), 0, st>>>(wp(L.rp), wp(L.ip), wp(L.np_), wp(L.hh), dh_in, dh_out, Nn * hd);
     return s2s_out_tail(a, ws, q, dh_out, x_in, x_out, st);
 }
 
@@ -652,11 +697,11 @@ void s2s_out_images(char* base, hipStream_t st, const S2SPlanLayout& P, const fl
 
 // The prepared weights of the shared half of the step (field query, prior) into a plan of either layout.
 void s2s_plan_build_front(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp, int D, int he, int rnn_hidden,
-                          int prior_layers, int prior_hidden, const S2SPlanLayout& P, char* base, hipStream_t st) {
+                          int prior_layers, int prior_hidden, const S2SPlanLayout& P, char* base, hipStream_t st, int filt_R = 0) {
     const S2SDims d(D);
     auto fl = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-    filter_images_launch(pp->filt_w2, d.EA, he, base + P.fimg, st);
+    filter_images_launch(pp->filt_w2, filt_R > 0 ? filt_R : d.EA, he, base + P.fimg, st);
     k_s2s_pad_rows<<<blocks((int64_t)he * d.RFp), dim3(256), 0, st>>>(pp->res1_w, d.RF, d.RF, fl(P.res1p), d.RFp, he);
     k_s2s_bn_affine<<<blocks(he), dim3(256), 0, st>>>(pp->mlp3_bn_w, pp->mlp3_bn_b, pp->mlp3_bn_mean, pp->mlp3_bn_var, fl(P.bn),
                                                      fl(P.bn) + he, he);

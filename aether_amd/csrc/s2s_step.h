@@ -38,6 +38,10 @@ struct S2SJob {
     // (n: the row of Y), after the bias and the gathers and before act; both [graphs][M].  Never with act == 5.
     const float* film_gamma; const float* film_beta;
     int film_rows;
+    // Per-row bias table (the charge-aware model, s2s_charges.h): + btab[bidx[r] * bstride + m] with r the row of X (after
+    // xidx), added where the gathers are.  bidx must be in range (k_s2s_charge_index makes it so).  NULL: the bias vector only.
+    const float* btab; const int32_t* bidx;
+    int bstride;
 };
 struct S2SJobs { int n; S2SJob j[S2S_MAX_JOBS]; };
 
@@ -159,11 +163,17 @@ k_s2s_linear_jobs(const S2SJobs jobs) {
         const float* g1 = J.g1 != nullptr ? J.g1 + (size_t)J.i1[nsrc] * M : nullptr;
         const float* g2 = J.g2 != nullptr ? J.g2 + (size_t)J.i2[nsrc] * M : nullptr;
         const size_t film_off = J.film_gamma != nullptr ? (size_t)(n / J.film_rows) * M : 0;     // per row: a tile may hold rows of several graphs
+        const float* bt = J.btab != nullptr ? J.btab + (size_t)J.bidx[J.xidx != nullptr ? J.xidx[nsrc] : nsrc] * J.bstride : nullptr;
 #pragma unroll
         for (int mb = 0; mb < MT; ++mb) {
             const int m = m0 + 16 * mb + 4 * q;
             f32x4 v = acc[mb][nb];
             if (g1 != nullptr && m + 3 < M) v += ld4(g1 + m) + ld4(g2 + m);
+            if (bt != nullptr) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (m + r < M) v[r] += bt[m + r];
+            }
             if (J.film_gamma != nullptr) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
@@ -483,6 +493,7 @@ k_s2s_gemm_split(const S2SJobs jobs) {
         const float* g2 = J.g2 != nullptr ? J.g2 + (size_t)J.i2[nsrc] * M : nullptr;
         const float sc = J.scale != nullptr ? J.scale[(size_t)n * J.sstride] : 1.0f;
         const size_t film_off = J.film_gamma != nullptr ? (size_t)(n / J.film_rows) * M : 0;     // per row: a tile may hold rows of several graphs
+        const float* bt = J.btab != nullptr ? J.btab + (size_t)J.bidx[J.xidx != nullptr ? J.xidx[nsrc] : nsrc] * J.bstride : nullptr;
         if (act == 5) {                                       // LSTM cell on the gate pre-activations (rows interleaved by unit)
             const int Ru = M >> 2;
 #pragma unroll
@@ -502,6 +513,7 @@ k_s2s_gemm_split(const S2SJobs jobs) {
             const int m = m0 + 16 * mb + 4 * q;
             f32x4 v = acc[mb][nb] * inv_xs[nb];
             if (g1 != nullptr) v += ld4(g1 + m) + ld4(g2 + m);
+            if (bt != nullptr) v += ld4(bt + m);
             if (J.film_gamma != nullptr) {
                 const f32x4 ga = ld4(J.film_gamma + film_off + m), be = ld4(J.film_beta + film_off + m);
 #pragma unroll
@@ -710,6 +722,7 @@ k_s2s_gemm_split_r1(const S2SJobs jobs) {
         const float* g2 = J.g2 != nullptr ? J.g2 + (size_t)J.i2[nsrc] * M : nullptr;
         const float sc = J.scale != nullptr ? J.scale[(size_t)n * J.sstride] : 1.0f;
         const size_t film_off = J.film_gamma != nullptr ? (size_t)(n / J.film_rows) * M : 0;     // per row: a tile may hold rows of several graphs
+        const float* bt = J.btab != nullptr ? J.btab + (size_t)J.bidx[J.xidx != nullptr ? J.xidx[nsrc] : nsrc] * J.bstride : nullptr;
         if (act == 5) {                                       // LSTM cell on the gate pre-activations (rows interleaved by unit)
             const int Ru = M >> 2;
 #pragma unroll
@@ -729,6 +742,7 @@ k_s2s_gemm_split_r1(const S2SJobs jobs) {
             const int m = m0 + 16 * mb + 4 * q;
             f32x4 v = acc[mb][nb] * inv_xs[nb];
             if (g1 != nullptr) v += ld4(g1 + m) + ld4(g2 + m);
+            if (bt != nullptr) v += ld4(bt + m);
             if (J.film_gamma != nullptr) {
                 const f32x4 ga = ld4(J.film_gamma + film_off + m), be = ld4(J.film_beta + film_off + m);
 #pragma unroll

@@ -7,6 +7,8 @@ velocities only -- averaged over the data set.  Inputs stay in HBM (no DataLoade
 """
 from __future__ import annotations
 
+import inspect
+
 import torch
 
 
@@ -18,9 +20,15 @@ def eval_forward_prediction(model, dataset, burn_in_steps, forward_pred_steps, b
     D = num_dims if num_dims is not None else getattr(dataset, "ndim", 2)
     feats = dataset.feats
     tot, pos, vel = [], [], []
+    # a charge-aware model (AetherCharges) takes the batch's charges, as experiments/electrostatic/evaluate.py:42-45 passes them
+    charges = getattr(dataset, "charges", None)
+    takes_charges = charges is not None and "charges" in inspect.signature(model.predict_future).parameters
     for lo in range(0, len(dataset), batch_size):
         inputs = feats[lo:lo + batch_size]
-        preds = model.predict_future(inputs[:, :burn_in_steps], forward_pred_steps, **predict_kwargs)
+        kwargs = dict(predict_kwargs)
+        if takes_charges and "charges" not in kwargs:
+            kwargs["charges"] = charges[lo:lo + batch_size].reshape(inputs.shape[0], -1).to(inputs.device)
+        preds = model.predict_future(inputs[:, :burn_in_steps], forward_pred_steps, **kwargs)
         gt = inputs[:, burn_in_steps:burn_in_steps + forward_pred_steps]
         p, g = dataset.torch_unnormalize(preds), dataset.torch_unnormalize(gt)
         se = (p - g) ** 2

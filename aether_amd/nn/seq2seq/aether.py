@@ -123,12 +123,16 @@ class _FieldHook:
     of them None, nullable decoder-state pointers and the step a ``field_out`` pointer -- else None: the decoder's;
     ``plan_tail`` / ``ws_tail``: the scalars that follow num_edge_types in the plan / workspace size calls; ``call(B, N)``: the
     arguments that follow n_edges in a step / rollout call; ``burn_field(burn_in [T0, B, N, 2D] or None)``: the arguments that
-    follow burn_in in a rollout call (the shared entries take the burn-in frames' field, queried in one batch)."""
+    follow burn_in in a rollout call (the shared entries take the burn-in frames' field, queried in one batch).
+    ``names``: the same five names for entries shaped as the decoder's own (one decoder struct, no ``field_out``);
+    ``plan_head``: what a plan build of those takes between the decoder struct and num_dims; ``after_field``: what their step
+    takes between ext_field and the decoder state."""
 
     def __init__(self, struct, tensors, entries=None, plan_tail=(), ws_tail=(), call=lambda B, N: (),
-                 burn_field=lambda burn_in: ()):
+                 burn_field=lambda burn_in: (), names=None, plan_head=(), after_field=()):
         self.struct, self.tensors, self.entries = struct, tensors, entries
         self.plan_tail, self.ws_tail, self.call, self.burn_field = plan_tail, ws_tail, call, burn_field
+        self.names, self.plan_head, self.after_field = names, plan_head, after_field
 
     def decoders(self, dec, pd):
         """The decoder argument(s) of an entry call."""
@@ -162,6 +166,8 @@ class _StepLoop:
         """Names of (plan bytes, plan build, workspace bytes, step, rollout)."""
         if hook.entries is not None:
             return hook.entries
+        if hook.names is not None:
+            return hook.names
         e = self.decoder._fused_entries
         return (e[0], e[1], "aether_s2s_step_workspace_bytes", e[2], e[3])
 
@@ -191,8 +197,8 @@ class _StepLoop:
             buf = hit[1] if hit is not None and hit[1].numel() == nbytes and hit[1].device == torch.device(device) else \
                 torch.empty(nbytes, dtype=torch.uint8, device=device)
             pf = hook.struct
-            _lib.check(getattr(lib, build_entry)(None if pf is None else C.byref(pf), C.byref(pe), *hook.decoders(dec, pd), D, he,
-                                                 hd, R, n_layers, prior_hidden, K, *extra, buf.data_ptr(), nbytes,
+            _lib.check(getattr(lib, build_entry)(None if pf is None else C.byref(pf), C.byref(pe), *hook.decoders(dec, pd),
+                                                 *hook.plan_head, D, he, hd, R, n_layers, prior_hidden, K, *extra, buf.data_ptr(), nbytes,
                                                  torch.cuda.current_stream(device).cuda_stream), build_entry)
             hit = self.__dict__["_plan_cache"] = (key, buf)
         return hit[1]
@@ -258,7 +264,7 @@ class _StepLoop:
         st = getattr(lib, entry)(None if pf is None else C.byref(pf), C.byref(pe), *hook.decoders(self.decoder, pd),
                                  plan.data_ptr(), *scal,
                                  send.data_ptr(), recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), xf.data_ptr(),
-                                 None if ff is None else ff.data_ptr(), *ptr(dhf), h0.data_ptr(), c0.data_ptr(),
+                                 None if ff is None else ff.data_ptr(), *hook.after_field, *ptr(dhf), h0.data_ptr(), c0.data_ptr(),
                                  uf.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), *ptr(dh_out), h1.data_ptr(),
                                  c1.data_ptr(), edges.data_ptr(), *field_out, torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(st, entry)

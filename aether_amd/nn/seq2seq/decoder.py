@@ -30,7 +30,9 @@ class _DecoderParams(C.Structure):
 
 
 class RecurrentDecoder(nn.Module):
-    def __init__(self, params, device="cuda"):
+    def __init__(self, params, device="cuda", charge_dim=0):
+        """``charge_dim`` (the charge-aware ablation, ablations/aether_charges.py:583-599): that many embedding columns
+        behind the inputs of ``input_r / _i / _n``, twice as many behind those of ``present_msg_fc1``."""
         super().__init__()
         self.num_vars = num_vars = params["num_vars"]
         input_size = params["input_size"]
@@ -63,11 +65,12 @@ class RecurrentDecoder(nn.Module):
         self.num_relative_features = 4 * self.num_dims + self.num_orientations
         self.num_pos_features = self.num_dims + self.num_orientations
         nrf, D = self.num_relative_features, self.num_dims
-        self.present_msg_fc1 = nn.ModuleList([nn.Linear(2 * nrf + input_size + D, n_hid) for _ in range(edge_types)])
+        self.present_msg_fc1 = nn.ModuleList([nn.Linear(2 * nrf + input_size + D + 2 * charge_dim, n_hid)
+                                              for _ in range(edge_types)])
         self.present_msg_fc2 = nn.ModuleList([nn.Linear(n_hid, n_hid) for _ in range(edge_types)])
-        self.input_r = nn.Linear(input_size + nrf + D, n_hid, bias=True)
-        self.input_i = nn.Linear(input_size + nrf + D, n_hid, bias=True)
-        self.input_n = nn.Linear(input_size + nrf + D, n_hid, bias=True)
+        self.input_r = nn.Linear(input_size + nrf + D + charge_dim, n_hid, bias=True)
+        self.input_i = nn.Linear(input_size + nrf + D + charge_dim, n_hid, bias=True)
+        self.input_n = nn.Linear(input_size + nrf + D + charge_dim, n_hid, bias=True)
         self.localizer = AugmentedLocalizer(num_vars, use_3d=self.use_3d, pos_representation="polar")
         self.send_edges, self.recv_edges = torch.where(~torch.eye(num_vars, dtype=bool))
         self._cache = {}

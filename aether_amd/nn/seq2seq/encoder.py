@@ -101,7 +101,9 @@ def _mlp_out(n_in, n_hidden, n_out, num_layers):
 
 
 class Encoder(nn.Module):
-    def __init__(self, params, device="cuda"):
+    def __init__(self, params, device="cuda", charge_dim=0):
+        """``charge_dim`` (the charge-aware ablation, ablations/aether_charges.py:333-337): that many embedding columns
+        behind the inputs of ``res1``, twice as many behind the filter's edge features."""
         super().__init__()
         self.num_vars = num_vars = params["num_vars"]
         self.num_edges = params["num_edge_types"]
@@ -130,8 +132,8 @@ class Encoder(nn.Module):
         self.num_orientations = D * (D - 1) // 2
         self.num_relative_features = nrf = 4 * D + self.num_orientations
         self.num_pos_features = D + self.num_orientations
-        self.res1 = nn.Linear(inp_size + nrf + D, hidden_size)
-        self.edge_filter = _AnisotropicEdgeFilter(2 * nrf + inp_size + D, self.num_pos_features, hidden_size,
+        self.res1 = nn.Linear(inp_size + nrf + D + charge_dim, hidden_size)
+        self.edge_filter = _AnisotropicEdgeFilter(2 * nrf + inp_size + D + 2 * charge_dim, self.num_pos_features, hidden_size,
                                                   hidden_size)
         self.pos_representation = params.get("pos_representation", "cart")
         self.localizer = AugmentedLocalizer(num_vars, use_3d=self.use_3d, pos_representation=self.pos_representation)
@@ -237,6 +239,17 @@ class Encoder(nn.Module):
                                                  recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), ws.data_ptr(),
                                                  ws.numel(), feats[t0:t1].data_ptr(), stream)
             _lib.check(st, "aether_s2s_encoder_features")
+        return self._sequence_heads(feats, B)
+
+    def _sequence_heads(self, feats, B):
+        """The recurrent half of ``forward`` (aether.py:374-382) on the per-time-step features [T, B * E, h]: both LSTMs
+        through time, both heads over all (time, edge) rows -> (prior_logits, posterior_logits, prior_state)."""
+        lib = _lib.load()
+        dev = feats.device
+        T = feats.shape[0]
+        h, R, K = self.hidden_size, self.rnn_hidden_size, self.num_edges
+        E1 = self.recv_edges.shape[0]
+        stream = torch.cuda.current_stream(dev).cuda_stream
         rows = B * E1
         gates = torch.empty(rows, 4 * R, dtype=torch.float32, device=dev)
 

@@ -34,14 +34,16 @@ class _CoordinateEmbedding(nn.Module):
 class FieldQuery(nn.Module):
     """``predict_field``: ``x[..., :D]`` -> (field ``[..., D]``, coords), as aether.py:86-90."""
 
-    def __init__(self, num_dims=2, hidden_size=512, rff_std=1.0, device="cuda"):
+    def __init__(self, num_dims=2, hidden_size=512, rff_std=1.0, device="cuda", charge_dim=0):
+        """``charge_dim`` (the charge-aware ablation, ablations/aether_charges.py:73-79): that many embedding columns behind
+        the Fourier features; ``forward`` is then the owner's (AetherCharges.predict_field)."""
         super().__init__()
         if hidden_size % 32 != 0:
             raise ValueError("hidden_size must be a multiple of 32")        # the reference requires it even (aether.py:80-81)
         if num_dims not in (2, 3):
             raise ValueError("num_dims must be 2 or 3")
         self.num_dims, self.hidden_size = num_dims, hidden_size
-        self.field_net = nn.Sequential(nn.Linear(hidden_size, hidden_size), nn.SiLU(),
+        self.field_net = nn.Sequential(nn.Linear(hidden_size + charge_dim, hidden_size), nn.SiLU(),
                                        nn.Linear(hidden_size, hidden_size), nn.SiLU(),
                                        nn.Linear(hidden_size, num_dims))
         self.coordinate_embedding = _CoordinateEmbedding(num_dims, hidden_size // 2, rff_std)

@@ -589,6 +589,76 @@ int aether_s2s_rollout(const AetherS2SFieldParams* field, const AetherS2SPriorPa
                        float* edges_out, void* stream);
 
 /*
+ * The charge-aware seq2seq Aether, AetherCharges of nn/seq2seq/ablations/aether_charges.py (the model the electrostatic runner
+ * passes charges= to): the seq2seq Aether whose field query (:88-98), encoder (:368-432) and recurrent decoder (:615-680) also
+ * see emb[c], a 16-wide nn.Embedding(2, 16) of every particle's charge sign (:86, charge_to_index :100-102).  The entries are
+ * aether_s2s_plan_* / aether_s2s_step / aether_s2s_rollout with the same stages and launches per step; the parameter structs
+ * are the plain model's with the widened tensors of the reference:
+ *   field->w0 [he][he + 16]; prior->res1_w [he][7D + O + 16], prior->filt_w2 [(EA + 32) he][he], prior->filt_b2 [(EA + 32) he]
+ *   (EA = 2 (4D + O) + 3D); decoder->pmsg_fc1_w[k] [hd][EA + 32], decoder->input_{r,i,n}_w [hd][7D + O + 16].
+ * The embedding has two rows, so what it feeds is folded into tables when the plan is built (exact algebra, re-associated
+ * fp32 sums): a Linear over [features | emb[c]] adds one of 2 bias rows per node (b + W_c emb[c]; the gates' rows carry the
+ * sum of their biases), over [features | emb[c_recv] | emb[c_send]] one of 4 rows per edge; the 32 embedding features of the
+ * anisotropic filter become four one-hot features (recv 0 / 1, send 0 / 1) whose weight blocks are sum_j emb[c][j] block_j,
+ * so the filter GEMM runs on EA + 4 = 28 / 43 features, not 56 / 71.
+ *   aether_s2s_charges_plan_build      : charge_embedding float[2][16] (charge_embedding.weight) and the structs above -> plan
+ *                                        (device, 256-byte aligned, aether_s2s_charges_plan_bytes); rebuild after the weights change
+ *   aether_s2s_charges_workspace_bytes : of a step / rollout (aether_s2s_step_workspace_bytes + index arrays and edge rows)
+ *   aether_s2s_charges_step / _rollout : as aether_s2s_step / aether_s2s_rollout (replacing single_step_forward :104-113 with
+ *                                        predict_field and Encoder.single_step_forward, and the loop of predict_future :169-208)
+ *                                        with charge_index int32[n_nodes] = charge_to_index(charges), 0 or 1 per node.
+ *                                        _step with ext_logits [n_edges][K] != NULL (then ext_field too) is the decoder on given
+ *                                        logits, single_step_forward :104-113 as calculate_loss :147-149 calls it: the sample
+ *                                        is taken from them, the prior is skipped, h0 / c0 / h1 / c1 may be NULL
+ *   aether_s2s_charges_encoder_features: the per-time-step half of Encoder.forward (:371-389: local frames, filter on the folded
+ *                                        image, res1 with its table, mlp3, mlp4) on a flattened batch of (time, graph) items with
+ *                                        their field -> features [n_edges][he], the input of aether_s2s_lstm_step / _mlp_head;
+ *                                        workspace as for a step
+ *   aether_s2s_charges_field           : predict_field alone (:88-98) on n_points rows x [n_points][x_stride] with a charge
+ *                                        index each -> field [n_points][D]; workspace aether_s2s_charges_field_workspace_bytes
+ * A charge index outside {0, 1} reads no table out of bounds: that node's outputs are NaN (in a rollout the NaN spreads
+ * through its graph, never to another graph) and the asynchronous error word is set -- the next aether_check_async_error
+ * returns AETHER_EHIP -- as for the other inputs the library can only find inconsistent on the device.
+ */
+size_t aether_s2s_charges_plan_bytes(int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
+                                     int prior_hidden, int num_edge_types);
+int aether_s2s_charges_plan_build(const AetherS2SFieldParams* field, const AetherS2SPriorParams* prior,
+                                  const AetherS2SDecoderParams* decoder, const float* charge_embedding, int num_dims,
+                                  int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden,
+                                  int num_edge_types, void* plan, size_t plan_bytes, void* stream);
+size_t aether_s2s_charges_workspace_bytes(int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_hidden,
+                                          int num_edge_types, int64_t n_nodes, int64_t n_edges);
+int aether_s2s_charges_step(const AetherS2SFieldParams* field, const AetherS2SPriorParams* prior,
+                            const AetherS2SDecoderParams* decoder, const void* plan, int num_dims, int encoder_hidden,
+                            int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types,
+                            int skip_first, int polar, int num_vars, float tau, int64_t n_nodes, int64_t n_edges,
+                            const int32_t* charge_index, const int64_t* send, const int64_t* recv, const int64_t* order,
+                            const int64_t* rowptr, const float* inputs, const float* ext_field, const float* ext_logits,
+                            const float* decoder_hidden_in, const float* h0, const float* c0, const float* uniform,
+                            void* workspace, size_t workspace_bytes,
+                            float* outputs, float* decoder_hidden_out, float* h1, float* c1, float* edges_out, void* stream);
+int aether_s2s_charges_rollout(const AetherS2SFieldParams* field, const AetherS2SPriorParams* prior,
+                               const AetherS2SDecoderParams* decoder, const void* plan, int num_dims, int encoder_hidden,
+                               int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types,
+                               int skip_first, int polar, int num_vars, float tau, int64_t n_nodes, int64_t n_edges,
+                               const int32_t* charge_index, const int64_t* send, const int64_t* recv, const int64_t* order,
+                               const int64_t* rowptr, int burn_in_steps, const float* burn_in, int steps, const float* inputs,
+                               float* decoder_state, float* h, float* c, const float* uniform, void* workspace,
+                               size_t workspace_bytes, float* predictions, float* edges_out, void* stream);
+int aether_s2s_charges_encoder_features(const AetherS2SFieldParams* field, const AetherS2SPriorParams* prior,
+                                        const AetherS2SDecoderParams* decoder, const void* plan, int num_dims, int encoder_hidden,
+                                        int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types,
+                                        int polar, int num_vars, int64_t n_nodes, int64_t n_edges, const int32_t* charge_index,
+                                        const int64_t* send, const int64_t* recv, const int64_t* order, const int64_t* rowptr,
+                                        const float* inputs, const float* field_values, void* workspace, size_t workspace_bytes,
+                                        float* features, void* stream);
+size_t aether_s2s_charges_field_workspace_bytes(int64_t n_points, int hidden);
+int aether_s2s_charges_field(const AetherS2SFieldParams* field, const void* plan, int num_dims, int encoder_hidden,
+                             int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types,
+                             int64_t n_points, const float* x, int x_stride, const int32_t* charge_index, void* workspace,
+                             size_t workspace_bytes, float* field_out, void* stream);
+
+/*
  * seq2seq Aether with decoder_type 'ref_mlp': one step of the Markov decoder (MarkovDecoder, nn/seq2seq/aether.py:413-503,
  * with MLPEdgeFilter of nn/nn/anisotropic_filter.py:43-71) on a flattened batch -- local frames of [inputs | field]
  * (AugmentedLocalizer, polar), edge MLP relu(lin2(relu(lin1(edge_attr)))) whose output column c Ku + k is channel c of used
