@@ -36,7 +36,7 @@ int s2s_markov_step_impl(const S2SStepArgs& a, char* ws, const float* x_in, cons
                          bool decode, hipStream_t st) {
     const int D = a.D, hd = a.hd, K = a.K, k0 = a.skip_first ? 1 : 0, ku = K - k0;
     const int64_t Nn = a.Nn, E = a.E;
-    const S2SDims d(D);
+    const S2SDims d(D, a.locs);
     const AetherS2SMarkovParams* mp = a.mp;
     const S2SPlanLayout& P = a.P;
     const S2SStepLayout& L = a.L;
@@ -76,8 +76,8 @@ int s2s_markov_step_impl(const S2SStepArgs& a, char* ws, const float* x_in, cons
 
 // The Markov decoder's prepared weights (ku used edge types) into a plan of its layout.
 void s2s_plan_build_markov(const AetherS2SMarkovParams* mp, int D, int hd, int ku, const S2SPlanLayout& P, char* base,
-                           hipStream_t st) {
-    const S2SDims d(D);
+                           hipStream_t st, int locs = 0) {
+    const S2SDims d(D, locs);
     auto fl = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     k_s2s_pad_rows<<<blocks((int64_t)hd * d.EAp), dim3(256), 0, st>>>(mp->lin1_w, d.EA, d.EA, fl(P.m_l1p), d.EAp, hd);

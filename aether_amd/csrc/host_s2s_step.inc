@@ -9,10 +9,13 @@ int s2s_fail(int code, const char* what, const char* why) {
     return fail(code, msg);
 }
 
+// locs: the plain localizer of the seq2seq LoCS (s2s_locs.h) -- 3D + O features per edge, rel_feat 2D wide, no origin edge
 struct S2SDims {
     int D, O, NF, RF, RFp, EA, EAp, EP;
-    explicit S2SDims(int D_) : D(D_) {
-        O = D * (D - 1) / 2; NF = 4 * D + O; RF = 3 * D + NF; EA = NF + RF; EP = D + O;
+    explicit S2SDims(int D_, int locs = 0) : D(D_) {
+        O = D * (D - 1) / 2; EP = D + O;
+        if (locs) { NF = 3 * D + O; RF = 2 * D; } else { NF = 4 * D + O; RF = 3 * D + NF; }
+        EA = NF + RF;
         RFp = (RF + 15) / 16 * 16; EAp = (EA + 31) / 32 * 32;      // EAp: whole 32-wide k blocks (split GEMM)
     }
 };
@@ -29,9 +32,10 @@ struct S2SPlanLayout {
     size_t m_l1p = 0, m_r1p = 0, m_b2 = 0, m_i_l1 = 0, m_i_l2[4] = {0, 0, 0, 0};
     static bool splittable(int M, int Kk) { return M % 128 == 0 && Kk % 32 == 0; }
     // filt_R > 0: the filter image has that many features instead of EA (the charge-aware model's folded filter, EA + 4)
+    // locs: the widths of the plain localizer (S2SDims), no field net
     S2SPlanLayout(int D, int he, int hd, int K, int R, int prior_layers = 1, int ph = 0, int markov_ku = -1, int mlp_hidden = 0,
-                  int filt_R = 0) {
-        const S2SDims d(D);
+                  int filt_R = 0, int locs = 0) {
+        const S2SDims d(D, locs);
         const bool rec = markov_ku < 0;
         const int Kr = rec ? K : 0;
         const int64_t hr = rec ? hd : 0;
@@ -54,6 +58,7 @@ struct S2SPlanLayout {
             i_a[k] = k < Kr ? image(hd, hd) : 0; i_s[k] = k < Kr ? image(hd, hd) : 0;
         }
         if (mlp_hidden > 0) { i_f0 = i_f2 = 0; i_film1 = image(mlp_hidden, he); i_film2 = image(mlp_hidden, mlp_hidden); }
+        else if (locs) i_f0 = i_f2 = 0;
         else { i_f0 = image(he, he); i_f2 = image(he, he); }
         i_mlp3_0 = image(he, he); i_mlp3_3 = image(he, he); i_ps = image(he, he);
         i_pr = image(he, he);
@@ -75,14 +80,16 @@ struct S2SStepLayout {
         total;
     int splits;
     // mlp_hidden > 0: the field query is the FiLM net, whose hidden rows (fh1, fh2) are mlp_hidden wide
-    S2SStepLayout(int D, int he, int hd, int R, int ph, int K, int64_t Nn, int64_t E, int mlp_hidden = 0) {
-        const S2SDims d(D);
+    // locs: the widths of the plain localizer, and no field query: gamma, fh1, fh2, field and ext are empty
+    S2SStepLayout(int D, int he, int hd, int R, int ph, int K, int64_t Nn, int64_t E, int mlp_hidden = 0, int locs = 0) {
+        const S2SDims d(D, locs);
         size_t off = 0;
         auto take = [&](size_t floats) { size_t o = off; off = align_up(off + floats * 4, 256); return o; };
         const size_t nn = (size_t)Nn, ee = (size_t)E, h = (size_t)he, g = (size_t)hd;
         const size_t fw = (size_t)(mlp_hidden > he ? mlp_hidden : he);
-        gamma = take(nn * h); fh1 = take(nn * fw); fh2 = take(nn * fw); field = take(nn * D);
-        ext = take(nn * 3 * D); rel = take(nn * d.RF); relp = take(nn * d.RFp); Rinv = take(nn * D * D);
+        const size_t fq = locs ? 0 : nn;                       // rows of the field query's buffers
+        gamma = take(fq * h); fh1 = take(fq * fw); fh2 = take(fq * fw); field = take(fq * D);
+        ext = take(fq * 3 * D); rel = take(nn * d.RF); relp = take(nn * d.RFp); Rinv = take(nn * D * D);
         ea = take(ee * d.EA); eap = take(ee * d.EAp); epos = take(ee * d.EP);
         bimg = take((filt_bimg_bytes(E, (int)h) + 3) / 4);
         splits = S2SPriorLayout::filter_splits(he, E);
@@ -223,6 +230,7 @@ struct S2SSizes {
     int D, he, hd, R, prior_layers, ph, K, skip_first, polar, num_vars;
     float tau;
     int64_t Nn, E;
+    int locs = 0;              // the seq2seq LoCS: plain localizer in front of the step, no field (host_s2s_locs.inc)
 };
 
 // Everything a step reads besides its state: made once per entry call (s2s_step_args).  Exactly one of dp (recurrent
@@ -288,19 +296,20 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
                    float* edges, FirstJobs&& first_jobs, Res1Jobs&& res1_jobs, hipStream_t st) {
     const int D = a.D, he = a.he, R = a.R, K = a.K, k0 = a.skip_first ? 1 : 0;
     const int64_t Nn = a.Nn, E = a.E;
-    const S2SDims d(D);
+    const S2SDims d(D, a.locs);
     auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto pl = [&](size_t off) { return reinterpret_cast<const float*>(a.plan + off); };
     auto im = [&](size_t off) { return off ? reinterpret_cast<const void*>(a.plan + off) : nullptr; };
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     const AetherS2SPriorParams* p = a.pp;
+    const bool query = !ext_field && !a.locs;                  // the built-in field query runs (LoCS has no field)
     S2SJobs T;
     const int ldg = P.ldg;
     // ---- field query (aether.py:86-90); its first layer shares a launch with first_jobs
     T.n = 0;
     const int mh = a.mlp_hidden;
     const size_t mplane = (size_t)a.batch * mh;
-    if (!ext_field && a.film) {
+    if (query && a.film) {
         // the FiLM net (dynamic_field_aether.py:117-134, nn/nn/filmed_network.py:27-35): linear_1 - FiLM - SiLU here, linear_2 -
         // FiLM - SiLU below, linear_3 in k_s2s_node_prep
         const int half = he / 2;
@@ -311,7 +320,7 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
         S2SJob J = s2s_job(1, a.film->lin1_w, he, a.film->lin1_b, wp(L.gamma), he, wp(L.fh1), mh, mh, he, Nn);
         J.film_gamma = a.mod; J.film_beta = a.mod + mplane; J.film_rows = a.num_objects; J.Wimg = im(P.i_film1);
         T.j[T.n++] = J;
-    } else if (!ext_field) {
+    } else if (query) {
         const int half = he / 2;
         const unsigned rb = (unsigned)((Nn * half + 255) / 256);
         dispatch_dim(D, [&](auto DD) {
@@ -323,12 +332,12 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
     }
     if (int rc = first_jobs(T)) return rc;
     if (int rc = s2s_launch_jobs(T, st)) return rc;
-    if (!ext_field && a.film) {
+    if (query && a.film) {
         S2SJob J = s2s_job(1, a.film->lin2_w, mh, a.film->lin2_b, wp(L.fh1), mh, wp(L.fh2), mh, mh, mh, Nn);
         J.film_gamma = a.mod + 2 * mplane; J.film_beta = a.mod + 3 * mplane; J.film_rows = a.num_objects; J.Wimg = im(P.i_film2);
         T.n = 0; T.j[T.n++] = J;
         if (int rc = s2s_launch_jobs(T, st)) return rc;
-    } else if (!ext_field) {
+    } else if (query) {
         T.n = 0; T.j[T.n++] = s2s_job(1, a.fp->w2, he, a.fp->b2, wp(L.fh1), he, wp(L.fh2), he, he, he, Nn);
         T.j[T.n - 1].Wimg = a.field_images ? im(P.i_f2) : nullptr;
         if (int rc = s2s_launch_jobs(T, st)) return rc;
@@ -336,7 +345,15 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
     // ---- last field layer + local frames of [inputs | field], once for the prior and the decoder (:385-388, :620-622)
     int* counts = reinterpret_cast<int*>(ws + L.counts);
     int64_t* lists = reinterpret_cast<int64_t*>(ws + L.lists);
-    {
+    if (a.locs) {                      // the plain localizer on the inputs themselves (locs.py:343, :572)
+        dispatch_dim(D, [&](auto DD) {
+            constexpr int Dc = decltype(DD)::value;
+            k_s2s_locs_node_prep<Dc><<<blocks(Nn), dim3(256), 0, st>>>(x_in, wp(L.rel), wp(L.Rinv), wp(L.relp), d.RFp, wp(L.wide), ldg,
+                                                                      counts, Nn);
+            k_s2s_locs_edge_prep<Dc><<<blocks(E), dim3(256), 0, st>>>(x_in, a.send, a.recv, wp(L.rel), a.polar, wp(L.ea), wp(L.eap),
+                                                                      wp(L.epos), E);
+        });
+    } else {
         const float* fh2 = ext_field ? nullptr : wp(L.fh2);
         const float* w4 = ext_field ? nullptr : a.film ? a.film->lin3_w : a.fp->w4;
         const float* b4 = ext_field ? nullptr : a.film ? a.film->lin3_b : a.fp->b4;
@@ -376,6 +393,7 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
         const float* filt_b2 = a.chg ? a.chg->b2 : p->filt_b2;
         const float* filt_ea = a.chg ? a.chg->ea : wp(L.ea);
         if (a.chg) { if (D == 2) FILT_LAUNCH(28); else FILT_LAUNCH(43); }       // + the four one-hot charge features
+        else if (a.locs) { if (D == 2) FILT_LAUNCH(11); else FILT_LAUNCH(18); } // the plain localizer's 5D + O
         else if (D == 2) FILT_LAUNCH(24); else FILT_LAUNCH(39);
 #undef FILT_LAUNCH
         // x = edge2node(edge_attr) (:393-394): planes added and in-edges summed in one pass
@@ -440,6 +458,10 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
             cur_k = M;
         }
     }
+    } else {                           // (given logits: what rides in the prior's res1 launch goes alone)
+        T.n = 0;
+        if (int rc = res1_jobs(T)) return rc;
+        if (int rc = s2s_launch_jobs(T, st)) return rc;
     }
     // ---- hard Gumbel sample (:92-98) and the per-type edge lists of the decoder
     if (edges != nullptr)
@@ -479,7 +501,7 @@ int s2s_step_impl(const S2SStepArgs& a, char* ws, const float* x_in, const float
                   float* edges_out, hipStream_t st) {
     const int D = a.D, hd = a.hd, K = a.K, k0 = a.skip_first ? 1 : 0;
     const int64_t Nn = a.Nn, E = a.E;
-    const S2SDims d(D);
+    const S2SDims d(D, a.locs);
     const S2SPlanLayout& P = a.P;
     const S2SStepLayout& L = a.L;
     auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
@@ -697,8 +719,9 @@ void s2s_out_images(char* base, hipStream_t st, const S2SPlanLayout& P, const fl
 
 // The prepared weights of the shared half of the step (field query, prior) into a plan of either layout.
 void s2s_plan_build_front(const AetherS2SFieldParams* fp, const AetherS2SPriorParams* pp, int D, int he, int rnn_hidden,
-                          int prior_layers, int prior_hidden, const S2SPlanLayout& P, char* base, hipStream_t st, int filt_R = 0) {
-    const S2SDims d(D);
+                          int prior_layers, int prior_hidden, const S2SPlanLayout& P, char* base, hipStream_t st, int filt_R = 0,
+                          int locs = 0) {
+    const S2SDims d(D, locs);
     auto fl = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     filter_images_launch(pp->filt_w2, filt_R > 0 ? filt_R : d.EA, he, base + P.fimg, st);
@@ -725,8 +748,8 @@ void s2s_plan_build_front(const AetherS2SFieldParams* fp, const AetherS2SPriorPa
 
 // The recurrent decoder's prepared weights into a plan of its layout.
 void s2s_plan_build_recurrent(const AetherS2SDecoderParams* dp, int D, int hd, int K, const S2SPlanLayout& P, char* base,
-                              hipStream_t st) {
-    const S2SDims d(D);
+                              hipStream_t st, int locs = 0) {
+    const S2SDims d(D, locs);
     auto fl = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     for (int k = 0; k < K; ++k)

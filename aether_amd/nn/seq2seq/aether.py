@@ -126,13 +126,21 @@ class _FieldHook:
     follow burn_in in a rollout call (the shared entries take the burn-in frames' field, queried in one batch).
     ``names``: the same five names for entries shaped as the decoder's own (one decoder struct, no ``field_out``);
     ``plan_head``: what a plan build of those takes between the decoder struct and num_dims; ``after_field``: what their step
-    takes between ext_field and the decoder state."""
+    takes between ext_field and the decoder state.
+    ``no_field`` (with ``entries``): a model without a field (the seq2seq LoCS) -- its plan build, step and rollout take no field
+    struct, the step takes ``ext_logits`` where the others take ``ext_field`` and ``logits_out`` where they take ``field_out``."""
 
     def __init__(self, struct, tensors, entries=None, plan_tail=(), ws_tail=(), call=lambda B, N: (),
-                 burn_field=lambda burn_in: (), names=None, plan_head=(), after_field=()):
+                 burn_field=lambda burn_in: (), names=None, plan_head=(), after_field=(), no_field=False):
         self.struct, self.tensors, self.entries = struct, tensors, entries
         self.plan_tail, self.ws_tail, self.call, self.burn_field = plan_tail, ws_tail, call, burn_field
-        self.names, self.plan_head, self.after_field = names, plan_head, after_field
+        self.names, self.plan_head, self.after_field, self.no_field = names, plan_head, after_field, no_field
+
+    def field(self):
+        """The field-struct argument of a plan build / step / rollout call."""
+        if self.no_field:
+            return ()
+        return (None if self.struct is None else C.byref(self.struct),)
 
     def decoders(self, dec, pd):
         """The decoder argument(s) of an entry call."""
@@ -196,8 +204,7 @@ class _StepLoop:
                 raise _lib.AetherHipError("fused seq2seq step: encoder_hidden must be a multiple of 128, decoder_hidden of 32")
             buf = hit[1] if hit is not None and hit[1].numel() == nbytes and hit[1].device == torch.device(device) else \
                 torch.empty(nbytes, dtype=torch.uint8, device=device)
-            pf = hook.struct
-            _lib.check(getattr(lib, build_entry)(None if pf is None else C.byref(pf), C.byref(pe), *hook.decoders(dec, pd),
+            _lib.check(getattr(lib, build_entry)(*hook.field(), C.byref(pe), *hook.decoders(dec, pd),
                                                  *hook.plan_head, D, he, hd, R, n_layers, prior_hidden, K, *extra, buf.data_ptr(), nbytes,
                                                  torch.cuda.current_stream(device).cuda_stream), build_entry)
             hit = self.__dict__["_plan_cache"] = (key, buf)
@@ -230,11 +237,15 @@ class _StepLoop:
         return lib, plan, ws, enc._graph(B, N, device), (pf, pe, pd), scal, hook
 
     @torch.no_grad()
-    def _fused_step(self, x, decoder_hidden, prior_hidden, uniform, field=None, return_field=False):
+    def _fused_step(self, x, decoder_hidden, prior_hidden, uniform, field=None, return_field=False, logits=None,
+                    return_logits=False):
         """One autoregressive step: x [B, N, 2D], decoder_hidden [B, N, hd], prior_hidden (h, c) [B, E, rnn], uniform
         [B, E, K]; ``field`` [B, N, D] replaces the built-in field query -> (predictions, decoder_hidden, (h, c), edges).
         With the Markov decoder, which has no state, ``decoder_hidden`` is ignored and comes back as None.
-        ``return_field`` (models whose step entry has a ``field_out``): also the field [B, N, D] the built-in query computed."""
+        ``return_field`` (models whose step entry has a ``field_out``): also the field [B, N, D] the built-in query computed.
+        A model without a field (``_FieldHook.no_field``): ``logits`` [B, E, K] makes the step the decoder on given logits --
+        the sample is taken from them, the prior is skipped, ``prior_hidden`` is not read and comes back as None;
+        ``return_logits``: also the prior's logits [B, E, K] the sample was taken from."""
         if not x.is_cuda:
             raise _lib.AetherHipError("aether_amd seq2seq models run on an MI355X only; got a CPU tensor (there is no CPU fallback)")
         B, N, _ = x.shape
@@ -244,33 +255,47 @@ class _StepLoop:
         E1 = self.encoder.recv_edges.shape[0]
         entry = self._entries(hook)[3]
         f32 = lambda t: t.detach().to(torch.float32).contiguous()
-        xf, h0, c0, uf = f32(x), f32(prior_hidden[0]), f32(prior_hidden[1]), f32(uniform)
+        xf, uf = f32(x), f32(uniform)
         dhf = f32(decoder_hidden) if self.decoder._has_state else None
-        if xf.shape != (B, N, 2 * D) or (dhf is not None and dhf.shape != (B, N, hd)) or h0.shape != (B, E1, R) or \
-                c0.shape != h0.shape or uf.numel() != B * E1 * K:
+        if hook.no_field and (field is not None or return_field):
+            raise ValueError("this model has no field")
+        if (logits is not None or return_logits) and (not hook.no_field or (logits is not None and return_logits)):
+            raise _lib.AetherHipError("logits / return_logits: the step of a model without a field takes given logits or "
+                                      "returns the prior's, not both")
+        lg = None if logits is None else f32(logits)
+        h0 = c0 = h1 = c1 = None
+        if lg is None:
+            h0, c0 = f32(prior_hidden[0]), f32(prior_hidden[1])
+            h1, c1 = torch.empty_like(h0), torch.empty_like(c0)
+        if xf.shape != (B, N, 2 * D) or (dhf is not None and dhf.shape != (B, N, hd)) or uf.numel() != B * E1 * K or \
+                (lg is None and (h0.shape != (B, E1, R) or c0.shape != h0.shape)) or (lg is not None and lg.shape != (B, E1, K)):
             raise ValueError("fused step: input shapes do not match the model")
         ff = None if field is None else f32(field)
-        if ff is None and pf is None:
+        if ff is None and pf is None and not hook.no_field:
             raise _lib.AetherHipError("this model has no built-in field query: pass the field")
         out = torch.empty_like(xf)
         dh_out = None if dhf is None else torch.empty_like(dhf)
-        h1, c1 = torch.empty_like(h0), torch.empty_like(c0)
         edges = torch.empty(B, E1, K, dtype=torch.float32, device=dev)
         if return_field and (hook.entries is None or ff is not None):
             raise _lib.AetherHipError("return_field: only the field a FiLM step computes itself can be returned")
         fout = torch.empty(B, N, D, dtype=torch.float32, device=dev) if return_field else None
-        field_out = () if hook.entries is None else (None if fout is None else fout.data_ptr(),)
+        lout = torch.empty(B, E1, K, dtype=torch.float32, device=dev) if return_logits else None
+        opt = lambda t: None if t is None else t.data_ptr()
+        field_out = () if hook.entries is None else (opt(lout if hook.no_field else fout),)
         ptr = hook.state
-        st = getattr(lib, entry)(None if pf is None else C.byref(pf), C.byref(pe), *hook.decoders(self.decoder, pd),
+        st = getattr(lib, entry)(*hook.field(), C.byref(pe), *hook.decoders(self.decoder, pd),
                                  plan.data_ptr(), *scal,
                                  send.data_ptr(), recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), xf.data_ptr(),
-                                 None if ff is None else ff.data_ptr(), *hook.after_field, *ptr(dhf), h0.data_ptr(), c0.data_ptr(),
-                                 uf.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), *ptr(dh_out), h1.data_ptr(),
-                                 c1.data_ptr(), edges.data_ptr(), *field_out, torch.cuda.current_stream(dev).cuda_stream)
+                                 opt(lg if hook.no_field else ff), *hook.after_field, *ptr(dhf), opt(h0), opt(c0),
+                                 uf.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), *ptr(dh_out), opt(h1),
+                                 opt(c1), edges.data_ptr(), *field_out, torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(st, entry)
+        state = None if lg is not None else (h1, c1)
         if return_field:
-            return out, dh_out, (h1, c1), edges, fout
-        return out, dh_out, (h1, c1), edges
+            return out, dh_out, state, edges, fout
+        if return_logits:
+            return out, dh_out, state, edges, lout
+        return out, dh_out, state, edges
 
     @torch.no_grad()
     def _fused_rollout(self, burn_in, x_last, decoder_hidden, prior_hidden, steps, uniform, return_edges,
@@ -283,8 +308,10 @@ class _StepLoop:
         B, N, _ = x_last.shape
         dev = x_last.device
         lib, plan, ws, (send, recv, order, rowptr), (pf, pe, pd), scal, hook = self._step_common(B, N, dev)
-        if pf is None:
+        if pf is None and not hook.no_field:
             raise _lib.AetherHipError("this model has no built-in field query: step it with _fused_step")
+        if not x_last.is_cuda:
+            raise _lib.AetherHipError("aether_amd seq2seq models run on an MI355X only; got a CPU tensor (there is no CPU fallback)")
         D, he, hd, R, K = self._step_sizes()
         E1 = self.encoder.recv_edges.shape[0]
         entry = self._entries(hook)[4]
@@ -299,7 +326,7 @@ class _StepLoop:
         uf = f32(uniform.reshape(T0 + steps, B, E1, K))
         preds = torch.empty(steps, B, N, 2 * D, dtype=torch.float32, device=dev)
         edges = torch.empty(steps, B, E1, K, dtype=torch.float32, device=dev) if return_edges else None
-        st = getattr(lib, entry)(C.byref(pf), C.byref(pe), *hook.decoders(self.decoder, pd), plan.data_ptr(), *scal,
+        st = getattr(lib, entry)(*hook.field(), C.byref(pe), *hook.decoders(self.decoder, pd), plan.data_ptr(), *scal,
                                  send.data_ptr(), recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), T0,
                                  None if bi is None else bi.data_ptr(), *hook.burn_field(bi if batched_burn_in else None), int(steps), xl.data_ptr(),
                                  *hook.state(dh), h.data_ptr(), c.data_ptr(), uf.data_ptr(),
@@ -413,23 +440,33 @@ class _EvalLoss:
         with torch.no_grad():           # (not a decorator: evaluate.py:42-45 inspects this method's argument names)
             return self._calculate_loss_eval(inputs, teacher_forcing, return_edges, return_logits, use_prior_logits, uniform)
 
+    def _sequence_logits(self, inputs):
+        """The full-sequence encoder on inputs[:, :-1] -> (prior_logits, posterior_logits [B, T - 1, E, K], the field of those
+        frames [B, N, T - 1, D], function giving the field of a later state); a model without a field gives None for both."""
+        predicted_field, field_fn = self._sequence_field(inputs)                     # [B, N, T - 1, D]
+        prior_logits, posterior_logits, _ = self.encoder(inputs[:, :-1], predicted_field)
+        return prior_logits, posterior_logits, predicted_field, field_fn
+
+    def _loss_step(self, inputs, decoder_hidden, logits, field, uniform):
+        """One decoder step of the evaluation loss on a hard sample of ``logits``."""
+        return self.single_step_forward(inputs, decoder_hidden, logits, True, field, uniform=uniform)
+
     def _calculate_loss_eval(self, inputs, teacher_forcing, return_edges, return_logits, use_prior_logits, uniform):
         B, T, N, _ = inputs.shape
         decoder_hidden = self.decoder.get_initial_hidden(inputs)
-        predicted_field, field_fn = self._sequence_field(inputs)                     # [B, N, T - 1, D]
-        prior_logits, posterior_logits, _ = self.encoder(inputs[:, :-1], predicted_field)
+        prior_logits, posterior_logits, predicted_field, field_fn = self._sequence_logits(inputs)
         tf_steps = self.val_teacher_forcing_steps
         all_predictions, edges, predictions = [], None, None
         for step in range(T - 1):
             if (teacher_forcing and (tf_steps == -1 or step < tf_steps)) or step == 0:
-                current_inputs, current_field = inputs[:, step], predicted_field[:, :, step].contiguous()
+                current_inputs = inputs[:, step]
+                current_field = None if predicted_field is None else predicted_field[:, :, step].contiguous()
             else:
                 current_inputs = predictions
-                current_field = field_fn(predictions)
+                current_field = None if field_fn is None else field_fn(predictions)
             logits = (prior_logits if use_prior_logits else posterior_logits)[:, step].contiguous()
-            predictions, decoder_hidden, edges = self.single_step_forward(
-                current_inputs, decoder_hidden, logits, True, current_field,
-                uniform=None if uniform is None else uniform[step])
+            predictions, decoder_hidden, edges = self._loss_step(
+                current_inputs, decoder_hidden, logits, current_field, None if uniform is None else uniform[step])
             all_predictions.append(predictions)
         all_predictions = torch.stack(all_predictions, dim=1)
         return self._loss_terms(inputs, all_predictions, prior_logits, posterior_logits, edges, return_edges, return_logits)

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from ... import _lib
-from .localizer import AugmentedLocalizer
+from .localizer import AugmentedLocalizer, Localizer
 
 
 class _DecoderParams(C.Structure):
@@ -30,10 +30,20 @@ class _DecoderParams(C.Structure):
 
 
 class RecurrentDecoder(nn.Module):
-    def __init__(self, params, device="cuda", charge_dim=0):
+    def __init__(self, params, device="cuda", charge_dim=0, localizer="augmented"):
         """``charge_dim`` (the charge-aware ablation, ablations/aether_charges.py:583-599): that many embedding columns
-        behind the inputs of ``input_r / _i / _n``, twice as many behind those of ``present_msg_fc1``."""
+        behind the inputs of ``input_r / _i / _n``, twice as many behind those of ``present_msg_fc1``.
+        ``localizer='plain'``: the recurrent decoder of the seq2seq LoCS (nn/seq2seq/locs.py:457-531) -- the plain ``Localizer``
+        with ``params['pos_representation']``, 3D + O relative features, ``input_r / _i / _n`` on the 2D-wide ``rel_feat``
+        created where the reference creates them (in front of ``present_r``).  Its step runs through the model
+        (``aether_s2s_locs_step``): ``forward`` of the module raises."""
         super().__init__()
+        if localizer not in ("augmented", "plain"):
+            raise ValueError("localizer must be 'augmented' or 'plain'")
+        self.localizer_kind = localizer
+        plain = localizer == "plain"
+        if plain and charge_dim:
+            raise ValueError("charge_dim is the charge-aware Aether's: not with localizer='plain'")
         self.num_vars = num_vars = params["num_vars"]
         input_size = params["input_size"]
         n_hid = params["decoder_hidden"]
@@ -53,6 +63,10 @@ class RecurrentDecoder(nn.Module):
         self.hidden_r = nn.Linear(n_hid, n_hid, bias=False)
         self.hidden_i = nn.Linear(n_hid, n_hid, bias=False)
         self.hidden_h = nn.Linear(n_hid, n_hid, bias=False)
+        if plain:                                                      # (locs.py:483-485)
+            self.input_r = nn.Linear(input_size, n_hid, bias=True)
+            self.input_i = nn.Linear(input_size, n_hid, bias=True)
+            self.input_n = nn.Linear(input_size, n_hid, bias=True)
         self.present_r = nn.Linear(n_hid, n_hid, bias=True)
         self.present_i = nn.Linear(n_hid, n_hid, bias=True)
         self.present_n = nn.Linear(n_hid, n_hid, bias=True)
@@ -62,16 +76,19 @@ class RecurrentDecoder(nn.Module):
         self.use_3d = params.get("use_3d", False)
         self.num_dims = 3 if self.use_3d else 2
         self.num_orientations = self.num_dims * (self.num_dims - 1) // 2
-        self.num_relative_features = 4 * self.num_dims + self.num_orientations
+        self.num_relative_features = (3 if plain else 4) * self.num_dims + self.num_orientations
         self.num_pos_features = self.num_dims + self.num_orientations
         nrf, D = self.num_relative_features, self.num_dims
-        self.present_msg_fc1 = nn.ModuleList([nn.Linear(2 * nrf + input_size + D + 2 * charge_dim, n_hid)
-                                              for _ in range(edge_types)])
+        pmsg_in = nrf + input_size if plain else 2 * nrf + input_size + D + 2 * charge_dim
+        self.present_msg_fc1 = nn.ModuleList([nn.Linear(pmsg_in, n_hid) for _ in range(edge_types)])
         self.present_msg_fc2 = nn.ModuleList([nn.Linear(n_hid, n_hid) for _ in range(edge_types)])
-        self.input_r = nn.Linear(input_size + nrf + D + charge_dim, n_hid, bias=True)
-        self.input_i = nn.Linear(input_size + nrf + D + charge_dim, n_hid, bias=True)
-        self.input_n = nn.Linear(input_size + nrf + D + charge_dim, n_hid, bias=True)
-        self.localizer = AugmentedLocalizer(num_vars, use_3d=self.use_3d, pos_representation="polar")
+        if plain:
+            self.localizer = Localizer(num_vars, use_3d=self.use_3d, pos_representation=params["pos_representation"])
+        else:
+            self.input_r = nn.Linear(input_size + nrf + D + charge_dim, n_hid, bias=True)
+            self.input_i = nn.Linear(input_size + nrf + D + charge_dim, n_hid, bias=True)
+            self.input_n = nn.Linear(input_size + nrf + D + charge_dim, n_hid, bias=True)
+            self.localizer = AugmentedLocalizer(num_vars, use_3d=self.use_3d, pos_representation="polar")
         self.send_edges, self.recv_edges = torch.where(~torch.eye(num_vars, dtype=bool))
         self._cache = {}
         if device is not None:
@@ -126,6 +143,9 @@ class RecurrentDecoder(nn.Module):
     def forward(self, inputs, hidden, edges, predicted_field):
         """aether.py:590-654.  inputs [B, N, 2D], hidden [B, N, h], edges [B, N(N-1), K], predicted_field
         [B, N, D] -> (outputs [B, N, 2D], hidden [B, N, h])."""
+        if self.localizer_kind == "plain":
+            raise _lib.AetherHipError("the decoder step of the seq2seq LoCS runs through the model (LoCS.single_step_forward: "
+                                      "aether_s2s_locs_step), not as a call of the module")
         if not inputs.is_cuda:
             raise _lib.AetherHipError("aether_amd RecurrentDecoder runs on an MI355X only; got a CPU tensor "
                                       "(there is no CPU fallback)")

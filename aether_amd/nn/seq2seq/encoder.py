@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from ... import _lib
-from .localizer import AugmentedLocalizer
+from .localizer import AugmentedLocalizer, Localizer
 
 
 class _PriorParams(C.Structure):
@@ -101,10 +101,22 @@ def _mlp_out(n_in, n_hidden, n_out, num_layers):
 
 
 class Encoder(nn.Module):
-    def __init__(self, params, device="cuda", charge_dim=0):
+    def __init__(self, params, device="cuda", charge_dim=0, localizer="augmented"):
         """``charge_dim`` (the charge-aware ablation, ablations/aether_charges.py:333-337): that many embedding columns
-        behind the inputs of ``res1``, twice as many behind the filter's edge features."""
+        behind the inputs of ``res1``, twice as many behind the filter's edge features.
+        ``localizer='plain'``: the encoder of the seq2seq LoCS (nn/seq2seq/locs.py:211-289) -- the plain ``Localizer``, 3D + O
+        relative features, ``res1`` on the 2D-wide ``rel_feat`` created where the reference creates it (behind ``mlp4``), and
+        ``params['pos_representation']`` required.  Its computation runs through the model's fused entries
+        (``aether_s2s_locs_*``), which need the decoder's plan: ``forward`` / ``single_step_forward`` of the module raise."""
         super().__init__()
+        if localizer not in ("augmented", "plain"):
+            raise ValueError("localizer must be 'augmented' or 'plain'")
+        self.localizer_kind = localizer
+        plain = localizer == "plain"
+        if plain and charge_dim:
+            raise ValueError("charge_dim is the charge-aware Aether's: not with localizer='plain'")
+        if plain and params["pos_representation"] not in ("cart", "polar"):        # (a required key, locs.py:281)
+            raise ValueError("pos_representation must be 'cart' or 'polar'")
         self.num_vars = num_vars = params["num_vars"]
         self.num_edges = params["num_edge_types"]
         if params["encoder_dropout"] != 0.0:
@@ -120,6 +132,8 @@ class Encoder(nn.Module):
         # creation order = the reference's (aether.py:265-330)
         self.mlp3 = _RefNRIMLP(hidden_size, hidden_size, hidden_size)
         self.mlp4 = _RefNRIMLP(hidden_size * 3, hidden_size, hidden_size)
+        if plain:
+            self.res1 = nn.Linear(inp_size, hidden_size)               # (locs.py:228-230: in front of the LSTMs)
         self.forward_rnn = nn.LSTM(hidden_size, rnn_hidden_size, batch_first=True)
         self.reverse_rnn = nn.LSTM(hidden_size, rnn_hidden_size, batch_first=True)
         self.encoder_fc_out = _mlp_out(2 * rnn_hidden_size, params.get("encoder_mlp_hidden"), self.num_edges,
@@ -130,13 +144,18 @@ class Encoder(nn.Module):
         self.use_3d = params.get("use_3d", False)
         self.num_dims = D = 3 if self.use_3d else 2
         self.num_orientations = D * (D - 1) // 2
-        self.num_relative_features = nrf = 4 * D + self.num_orientations
+        self.num_relative_features = nrf = (3 if plain else 4) * D + self.num_orientations
         self.num_pos_features = D + self.num_orientations
-        self.res1 = nn.Linear(inp_size + nrf + D + charge_dim, hidden_size)
-        self.edge_filter = _AnisotropicEdgeFilter(2 * nrf + inp_size + D + 2 * charge_dim, self.num_pos_features, hidden_size,
-                                                  hidden_size)
-        self.pos_representation = params.get("pos_representation", "cart")
-        self.localizer = AugmentedLocalizer(num_vars, use_3d=self.use_3d, pos_representation=self.pos_representation)
+        if plain:
+            self.edge_filter = _AnisotropicEdgeFilter(nrf + inp_size, self.num_pos_features, hidden_size, hidden_size)
+            self.pos_representation = params["pos_representation"]
+            self.localizer = Localizer(num_vars, use_3d=self.use_3d, pos_representation=self.pos_representation)
+        else:
+            self.res1 = nn.Linear(inp_size + nrf + D + charge_dim, hidden_size)
+            self.edge_filter = _AnisotropicEdgeFilter(2 * nrf + inp_size + D + 2 * charge_dim, self.num_pos_features,
+                                                      hidden_size, hidden_size)
+            self.pos_representation = params.get("pos_representation", "cart")
+            self.localizer = AugmentedLocalizer(num_vars, use_3d=self.use_3d, pos_representation=self.pos_representation)
         for m in self.modules():                                   # Encoder.init_weights, aether.py:332-336
             if isinstance(m, nn.Linear):
                 nn.init.xavier_normal_(m.weight.data)
@@ -200,6 +219,11 @@ class Encoder(nn.Module):
         _lib.check(st, "aether_s2s_mlp_head")
         return out
 
+    def _not_plain(self, what):
+        if self.localizer_kind == "plain":
+            raise _lib.AetherHipError(f"Encoder.{what} of the seq2seq LoCS runs through the model (LoCS._encoder_forward, "
+                                      "LoCS.predict_future: aether_s2s_locs_*), not as a call of the module")
+
     @torch.no_grad()
     def forward(self, inputs, predicted_field, max_edges_per_call=400_000):
         """The full-sequence encoder, aether.py:350-382 (evaluation: BatchNorm running statistics).  inputs
@@ -208,6 +232,7 @@ class Encoder(nn.Module):
         takes).  The per-time-step features are independent across time: T x B graphs go through
         ``aether_s2s_encoder_features`` in chunks of time steps; the two LSTMs step through time with
         ``aether_s2s_lstm_step``; the heads run once over all (time, edge) rows."""
+        self._not_plain("forward")
         if not inputs.is_cuda:
             raise _lib.AetherHipError("aether_amd Encoder runs on an MI355X only; got a CPU tensor "
                                       "(there is no CPU fallback)")
@@ -279,6 +304,7 @@ class Encoder(nn.Module):
     def single_step_forward(self, inputs, prior_state, predicted_field):
         """aether.py:384-410.  inputs [B, N, 2D], prior_state (h, c) each [B, E, rnn], predicted_field
         [B, N, D] -> (prior_logits [B, E, K], (h', c'))."""
+        self._not_plain("single_step_forward")
         if not inputs.is_cuda:
             raise _lib.AetherHipError("aether_amd Encoder runs on an MI355X only; got a CPU tensor "
                                       "(there is no CPU fallback)")

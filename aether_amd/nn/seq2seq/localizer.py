@@ -14,6 +14,40 @@ import torch.nn as nn
 from ... import _lib
 
 
+class Localizer(nn.Module):
+    """The plain localizer of the seq2seq LoCS (nn/utils/global_to_local.py:8-62): the reference's constructor, attributes
+    and ``set_edge_index``.  It holds no parameters; the frames themselves are built inside the fused step
+    (``aether_s2s_locs_step``, csrc/s2s_locs.h: ``rel_feat`` [.., 2D], ``edge_attr`` [.., 5D + O], ``edge_pos`` by
+    ``_edge_pos_idx_fn``), so ``forward`` is not a separate library call."""
+
+    _edge_pos_idx_fn = {(0, "cart"): [0, 1, 2], (0, "polar"): [2, 3, 4],
+                        (1, "cart"): [0, 1, 2, 3, 4, 5], (1, "polar"): [3, 4, 5, 6, 7, 8]}
+
+    def __init__(self, num_vars, use_3d=False, pos_representation="polar", batched=False):
+        super().__init__()
+        if pos_representation not in ("cart", "polar"):
+            raise ValueError("pos_representation must be 'cart' or 'polar'")
+        if batched:
+            raise ValueError("batched=True (the variable-N setting) is not part of the seq2seq LoCS here")
+        self.num_vars = num_vars
+        self.use_3d = bool(use_3d)
+        self.pos_representation = pos_representation
+        self.batched = False
+        self.send_edges, self.recv_edges = torch.where(~torch.eye(num_vars, dtype=bool))
+        self.edge_pos_idx = self._edge_pos_idx_fn[(int(self.use_3d), pos_representation)]
+        self.num_dims = 3 if self.use_3d else 2
+        self.num_orientations = self.num_dims * (self.num_dims - 1) // 2
+        self.num_relative_features = 3 * self.num_dims + self.num_orientations
+        self.num_pos_features = self.num_dims + self.num_orientations
+
+    def set_edge_index(self, send_edges, recv_edges):
+        self.send_edges, self.recv_edges = send_edges, recv_edges
+
+    def forward(self, x):
+        raise _lib.AetherHipError("the plain Localizer runs inside the fused LoCS step (aether_s2s_locs_step); it is not a "
+                                  "separate library call, and there is no CPU fallback")
+
+
 class AugmentedLocalizer(nn.Module):
     def __init__(self, num_objects, use_3d=False, pos_representation="polar"):
         super().__init__()

@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from ... import _lib
 from .decoder import RecurrentDecoder
-from .localizer import AugmentedLocalizer
+from .localizer import AugmentedLocalizer, Localizer
 
 
 class _MarkovParams(C.Structure):
@@ -39,8 +39,16 @@ class MLPEdgeFilter(nn.Module):
 
 
 class MarkovDecoder(nn.Module):
-    def __init__(self, params, device="cuda"):
+    def __init__(self, params, device="cuda", localizer="augmented"):
+        """``localizer='plain'``: the Markov decoder of the seq2seq LoCS (nn/seq2seq/locs.py:368-420) -- the plain ``Localizer``
+        with ``params['pos_representation']``, 3D + O relative features, ``res1`` on the 2D-wide ``rel_feat`` created where
+        the reference creates it (in front of ``out_mlp``).  Its step runs through the model (``aether_s2s_locs_step``):
+        ``forward`` of the module raises."""
         super().__init__()
+        if localizer not in ("augmented", "plain"):
+            raise ValueError("localizer must be 'augmented' or 'plain'")
+        self.localizer_kind = localizer
+        plain = localizer == "plain"
         self.num_vars = params["num_vars"]
         self.edge_types = params["num_edge_types"]
         n_hid = params["decoder_hidden"]
@@ -58,15 +66,21 @@ class MarkovDecoder(nn.Module):
         self.use_3d = params.get("use_3d", False)
         self.num_dims = D = 3 if self.use_3d else 2
         self.num_orientations = D * (D - 1) // 2
-        self.num_relative_features = nrf = 4 * D + self.num_orientations
+        self.num_relative_features = nrf = (3 if plain else 4) * D + self.num_orientations
         self.num_pos_features = D + self.num_orientations
-        # creation order = the reference's (aether.py:426-453): identical RNG consumption under a seed
+        # creation order = the reference's (aether.py:426-453; locs.py:383-419): identical RNG consumption under a seed
+        if plain:
+            self.res1 = nn.Linear(in_size, n_hid)
         self.out_mlp = nn.Sequential(nn.Linear(n_hid, n_hid), nn.ReLU(), nn.Dropout(p=self.dropout_prob),
                                      nn.Linear(n_hid, n_hid), nn.ReLU(), nn.Dropout(p=self.dropout_prob),
                                      nn.Linear(n_hid, in_size))
-        self.res1 = nn.Linear(in_size + nrf + D, n_hid)
-        self.edge_filter = MLPEdgeFilter(2 * nrf + in_size + D, n_hid, n_hid * self.num_used_edge_types)
-        self.localizer = AugmentedLocalizer(self.num_vars, use_3d=self.use_3d, pos_representation="polar")
+        if plain:
+            self.edge_filter = MLPEdgeFilter(nrf + in_size, n_hid, n_hid * self.num_used_edge_types)
+            self.localizer = Localizer(self.num_vars, use_3d=self.use_3d, pos_representation=params["pos_representation"])
+        else:
+            self.res1 = nn.Linear(in_size + nrf + D, n_hid)
+            self.edge_filter = MLPEdgeFilter(2 * nrf + in_size + D, n_hid, n_hid * self.num_used_edge_types)
+            self.localizer = AugmentedLocalizer(self.num_vars, use_3d=self.use_3d, pos_representation="polar")
         self.send_edges, self.recv_edges = torch.where(~torch.eye(self.num_vars, dtype=bool))
         self._cache = {}
         if device is not None:
@@ -95,6 +109,9 @@ class MarkovDecoder(nn.Module):
     def forward(self, inputs, hidden, edges, predicted_field):
         """aether.py:459-503.  inputs [B, N, 2D], edges [B, N(N-1), K] (one-hot or soft), predicted_field [B, N, D]
         -> (outputs [B, N, 2D], None).  ``hidden`` is ignored (the decoder has no state)."""
+        if self.localizer_kind == "plain":
+            raise _lib.AetherHipError("the decoder step of the seq2seq LoCS runs through the model (LoCS.single_step_forward: "
+                                      "aether_s2s_locs_step), not as a call of the module")
         if not inputs.is_cuda:
             raise _lib.AetherHipError("aether_amd MarkovDecoder runs on an MI355X only; got a CPU tensor "
                                       "(there is no CPU fallback)")

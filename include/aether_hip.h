@@ -833,6 +833,72 @@ int aether_s2s_dynfield_rollout(const AetherS2SFilmParams* film, const AetherS2S
                                 void* workspace, size_t workspace_bytes, float* predictions, float* edges_out, void* stream);
 
 /*
+ * The seq2seq LoCS baseline, LoCS of nn/seq2seq/locs.py (--model_type nn.seq2seq.locs.LoCS of the electrostatic and
+ * gravitational runners): the seq2seq Aether without a field, on the plain Localizer (nn/utils/global_to_local.py:46-62;
+ * canonicalize_inputs, create_edge_attr_pos_vel, create_3d_edge_attr_pos_vel of nn/utils/canonicalization.py:12-30, :78-108,
+ * :175-202).  No virtual origin node, no force columns: rel_feat is 2D wide (2-D [0, 0, |v|, 0], 3-D [0_3 | R^T v]), an edge
+ * has 3D + O features (O = D (D - 1) / 2) and its row [features | rel_feat[recv]] is 5D + O = 11 / 18 wide, where Aether's is
+ * 24 / 39; the anisotropic filter GEMM, the step's dominant cost, runs on those 11 / 18 features.  The parameter structs are
+ * the plain model's with the reference's tensor shapes:
+ *   prior->res1_w [he][2D], prior->filt_w2 [(5D + O) he][he], prior->filt_b2 [(5D + O) he];
+ *   decoder->pmsg_fc1_w[k] [hd][5D + O], decoder->input_{r,i,n}_w [hd][2D]      (RecurrentDecoder, locs.py:457-604)
+ *   markov->lin1_w [hd][5D + O], markov->res1_w [hd][2D]                        (MarkovDecoder, locs.py:368-454)
+ * Exactly one of decoder / markov is given (the other NULL), as for the aether_s2s_dynfield_* entries.  There is no field
+ * query: nothing of it is in the plan or the workspace and none of its kernels is launched.  `polar` is
+ * params['pos_representation'] == 'polar', which both the encoder's and the decoder's Localizer take (locs.py:279-282,
+ * :416-419, :527-530; Localizer._edge_pos_idx_fn): it selects edge_pos, which only the encoder's filter reads.
+ *   aether_s2s_locs_plan_bytes / _plan_build : prepared weights (device, 256-byte aligned); rebuild after the weights change
+ *   aether_s2s_locs_workspace_bytes          : of a step / rollout / encoder_features call
+ *   aether_s2s_locs_step                     : Encoder.single_step_forward (locs.py:341-365), the hard Gumbel sample and the
+ *                                              decoder (LoCS.single_step_forward :69-77) as one call; arguments as
+ *                                              aether_s2s_step without the field.  With ext_logits [n_edges][K] != NULL it is
+ *                                              the decoder on given logits, as calculate_loss :101-102 calls it: the sample
+ *                                              is taken from them, the prior is skipped, h0 / c0 / h1 / c1 may be NULL.
+ *                                              decoder_hidden_in / _out are NULL with the Markov decoder; logits_out (or
+ *                                              NULL) [n_edges][K]: the prior's logits the sample was taken from (not with
+ *                                              ext_logits: AETHER_EINVAL)
+ *   aether_s2s_locs_rollout                  : the loops of predict_future (:122-151) as aether_s2s_rollout; decoder_state
+ *                                              is NULL with the Markov decoder, whose burn-in steps run the prior only
+ *   aether_s2s_locs_encoder_features         : the per-time-step half of Encoder.forward (:309-326: local frames, filter,
+ *                                              res1, mlp3, mlp4) on a flattened batch of (time, graph) items -> features
+ *                                              [n_edges][he], the input of aether_s2s_lstm_step / aether_s2s_mlp_head
+ * Sizes as for aether_s2s_step (AETHER_EINVAL otherwise; the size calls return 0); AETHER_EINVAL: both or neither decoder,
+ * a NULL pointer; AETHER_ESPACE: plan or workspace too small.  Stream-ordered, no host synchronisation (capturable); nothing
+ * outside the workspace and the outputs is written.
+ */
+size_t aether_s2s_locs_plan_bytes(const AetherS2SDecoderParams* decoder, const AetherS2SMarkovParams* markov, int num_dims,
+                                  int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden,
+                                  int num_edge_types, int skip_first);
+int aether_s2s_locs_plan_build(const AetherS2SPriorParams* prior, const AetherS2SDecoderParams* decoder,
+                               const AetherS2SMarkovParams* markov, int num_dims, int encoder_hidden, int decoder_hidden,
+                               int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, int skip_first, void* plan,
+                               size_t plan_bytes, void* stream);
+size_t aether_s2s_locs_workspace_bytes(int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_hidden,
+                                       int num_edge_types, int64_t n_nodes, int64_t n_edges);
+int aether_s2s_locs_step(const AetherS2SPriorParams* prior, const AetherS2SDecoderParams* decoder,
+                         const AetherS2SMarkovParams* markov, const void* plan, int num_dims, int encoder_hidden,
+                         int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, int skip_first,
+                         int polar, int num_vars, float tau, int64_t n_nodes, int64_t n_edges, const int64_t* send,
+                         const int64_t* recv, const int64_t* order, const int64_t* rowptr, const float* inputs,
+                         const float* ext_logits, const float* decoder_hidden_in, const float* h0, const float* c0,
+                         const float* uniform, void* workspace, size_t workspace_bytes, float* outputs, float* decoder_hidden_out,
+                         float* h1, float* c1, float* edges_out, float* logits_out, void* stream);
+int aether_s2s_locs_rollout(const AetherS2SPriorParams* prior, const AetherS2SDecoderParams* decoder,
+                            const AetherS2SMarkovParams* markov, const void* plan, int num_dims, int encoder_hidden,
+                            int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types,
+                            int skip_first, int polar, int num_vars, float tau, int64_t n_nodes, int64_t n_edges,
+                            const int64_t* send, const int64_t* recv, const int64_t* order, const int64_t* rowptr,
+                            int burn_in_steps, const float* burn_in, int steps, const float* inputs, float* decoder_state,
+                            float* h, float* c, const float* uniform, void* workspace, size_t workspace_bytes, float* predictions,
+                            float* edges_out, void* stream);
+int aether_s2s_locs_encoder_features(const AetherS2SPriorParams* prior, const AetherS2SDecoderParams* decoder,
+                                     const AetherS2SMarkovParams* markov, const void* plan, int num_dims, int encoder_hidden,
+                                     int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types,
+                                     int skip_first, int polar, int num_vars, int64_t n_nodes, int64_t n_edges, const int64_t* send,
+                                     const int64_t* recv, const int64_t* order, const int64_t* rowptr, const float* inputs,
+                                     void* workspace, size_t workspace_bytes, float* features, void* stream);
+
+/*
  * k-nearest-neighbour edge builder for variable-N scenes: replaces Encoder.knn_edges
  * (nn/dynamicvars/aether_dynamicvars.py:559-586; the same method in the other *_dynamicvars.py) and the send /
  * recv half of get_knn_graph_info (experiments/ind/single_ind_data.py:186-217).
