@@ -1,0 +1,119 @@
+"""The update metric of tests/update_parity.py sees a split GEMM lose one of its three terms; the position metric of the
+forward parity tests does not.  CPU only: the kernels are not run, their arithmetic is restated inside the fp64 oracle.
+
+csrc/common.h (gemm_split): every operand of a `gnn.*` Linear is two fp16 pieces, x = hi + lo with hi = fp16(x) and
+lo = fp16(x - hi); the product is w_hi x_hi + w_hi x_lo + w_lo x_hi accumulated in fp32.  `split_linears` puts that
+into the oracle (everything else stays fp64) and can leave one cross term out of one layer -- the slip a hand-scheduled
+GEMM makes with a swapped fragment or a term lost in a re-ordering -- or keep only the hi piece of every weight.
+
+Per case: (a) the full three-term arithmetic passes FACTOR x the fp32 restatement's floor, (b) every degraded variant
+fails it, (c) every degraded variant passes scale_rel_err <= 1e-5, which is why test_gpu_update_parity.py exists.
+(b) is a condition on the inputs (seeds below), not on any kernel.
+
+The second half holds the inputs of tests/test_gpu_update_parity.py to the rule their seeds were chosen by, on this
+machine's CPU: a floor that is not a lucky draw, a bar the design's arithmetic meets, Gumbel samples away from a tie."""
+import pytest
+import torch
+
+from conftest import scale_rel_err
+import update_cases as U
+import update_s2s_cases as S2S
+from update_cases import split_linears
+from update_parity import DEGENERATE, FACTOR, update_err, update_floor
+from aether_amd.nn.state2state.aether import Aether
+from aether_amd.synthetic import make_batch
+from oracle import aether_oracle as O
+
+OLD_TOL = 1e-5
+LAYERS = ["gnn.layer_2.message_fn.0", "gnn.layer_3.update_fn.0", "gnn.out_mlp.3"]
+TERMS = ["w_lo*x_hi", "w_hi*x_lo"]
+# D, H, B, N, input seed (tests/update_cases.py says how a seed is chosen: B2N5 has 30 elements, and at seeds 5 .. 11 its
+# floor is degenerate or the full arithmetic does not meet the bar)
+CASES = [(2, 64, 16, 20, 5), (3, 64, 6, 7, 5), (2, 128, 4, 20, 5), (2, 32, 6, 7, 5), (3, 64, 2, 5, 12)]
+
+
+@pytest.fixture(scope="module", params=CASES, ids=lambda c: "D%d_H%d_B%dN%d_s%d" % c)
+def case(request):
+    D, H, B, N, seed = request.param
+    torch.manual_seed(11)
+    m = Aether(2 * D, H, 0.0, D, device="cpu")
+    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    sd64 = {k: v.double() for k, v in sd.items()}
+    inp = make_batch(B, N, D, seed=seed)
+    args64 = (inp["x"].double(), inp["vel"].double(), inp["edges"], inp["edge_attr"].double(), inp["charges"].double())
+    with torch.no_grad(), U.one_thread():
+        want = O.aether_forward(sd64, *args64)
+        want32 = O.aether_forward(sd, inp["x"], inp["vel"], inp["edges"], inp["edge_attr"], inp["charges"])
+    floor = update_floor(want32, inp["x"], want)
+
+    def run(**kw):
+        """out as the kernel forms it: fl32(x + update32)."""
+        with torch.no_grad(), U.one_thread(), split_linears(**kw):
+            out = O.aether_forward(sd64, *args64)
+        return (inp["x"] + (out - inp["x"].double()).float())
+
+    return dict(x=inp["x"], want=want, floor=floor, run=run)
+
+
+def test_floor_is_not_degenerate(case):
+    assert case["floor"] >= DEGENERATE, case["floor"]
+    assert case["floor"] <= 1e-6, case["floor"]
+
+
+def test_full_three_term_arithmetic_passes(case):
+    err = update_err(case["run"](), case["x"], case["want"])
+    print(f"all terms: new={err:.2e} floor={case['floor']:.2e}")
+    assert err <= FACTOR * case["floor"], (err, case["floor"])
+
+
+@pytest.mark.parametrize("term", TERMS)
+@pytest.mark.parametrize("layer", LAYERS)
+def test_one_dropped_term_fails_the_update_bar_and_passes_the_position_bar(case, layer, term):
+    got = case["run"](drop=(layer, term))
+    new, old = update_err(got, case["x"], case["want"]), scale_rel_err(got, case["want"])
+    print(f"{layer} without {term}: old={old:.2e} new={new:.2e} floor={case['floor']:.2e} new/floor={new / case['floor']:.1f}")
+    assert new > FACTOR * case["floor"], (new, case["floor"])
+    assert old <= OLD_TOL, old
+
+
+def test_hi_only_weights_fail_the_update_bar_and_pass_the_position_bar(case):
+    got = case["run"](hi_only_weights=True)
+    new, old = update_err(got, case["x"], case["want"]), scale_rel_err(got, case["want"])
+    print(f"hi-only weights: old={old:.2e} new={new:.2e} floor={case['floor']:.2e} new/floor={new / case['floor']:.1f}")
+    assert new > FACTOR * case["floor"], (new, case["floor"])
+    assert old <= OLD_TOL, old
+
+
+# ---- the cases of tests/test_gpu_update_parity.py, without a GPU -----------------------------------------------------------
+@pytest.mark.parametrize("fc", U.FORWARD_CASES, ids=U.case_id)
+def test_gpu_forward_case_has_a_typical_floor_and_a_bar_the_design_meets(fc):
+    name, case = fc
+    x, want64, want32 = U.references(name, case)
+    floor = update_floor(want32, x, want64)
+    print(f"{U.case_id(fc)}: floor={floor:.2e}")
+    assert floor >= U.TYPICAL, floor
+    if name in U.SPLIT_FAMILIES:
+        err = update_err(U.emulated(name, case), x, want64)
+        print(f"{U.case_id(fc)}: three-term split arithmetic err={err:.2e} ratio={err / floor:.2f}")
+        assert err <= FACTOR * floor, (err, floor)
+
+
+@pytest.mark.parametrize("fc", U.ROLLOUT_CASES, ids=U.case_id)
+def test_gpu_rollout_case_has_a_typical_floor_at_every_step(fc):
+    name, case = fc
+    x, want64, want32 = U.references(name, case, U.ROLLOUT_STEPS)
+    prev = torch.cat([x.double()[None], want64[:-1]])
+    floors = [update_floor(want32[t], prev[t], want64[t]) for t in range(U.ROLLOUT_STEPS)]
+    print(f"{U.case_id(fc)}: floors " + " ".join(f"{f:.2e}" for f in floors))
+    assert torch.isfinite(want64).all() and min(floors) >= U.TYPICAL, floors
+
+
+@pytest.mark.parametrize("steps", [1, S2S.STEPS])
+@pytest.mark.parametrize("case", S2S.CASES, ids=S2S.case_id)
+def test_gpu_seq2seq_case_has_a_typical_floor_and_no_sample_near_a_tie(case, steps):
+    ref = S2S.references(case, steps)
+    floors = [update_floor(ref["want32"][t], ref["prev"][t], ref["want64"][t]) for t in range(steps)]
+    print(f"{S2S.case_id(case)} steps={steps}: gap={ref['gap']:.1e} floors " + " ".join(f"{f:.2e}" for f in floors))
+    assert min(floors) >= S2S.TYPICAL, floors
+    assert ref["gap"] >= S2S.GAP, ref["gap"]
+    assert torch.equal(ref["types64"], ref["types32"])

@@ -1,0 +1,300 @@
+"""The cases of tests/test_gpu_update_parity.py: per model family how to build the drop-in under a seed, its inputs, its
+CPU restatement in a dtype and the call on the device.  Test helper, not a test module.
+
+Everything a bar is taken against is computed here, on the CPU: `references(family, case)` gives the input positions
+and the restatement's output in fp64 and in fp32, from the state_dict of the module built under the case's seed (the
+drop-ins initialise on the CPU and move, so a module built on the device under the same seed has the same weights).
+tests/test_update_metric.py holds every case's fp32 floor away from the degenerate range without a GPU.
+
+Seeds.  The floor is a maximum over B N D elements.  At shapes with hundreds of elements (B6N7, B2N20, B4N20) it is
+1.1e-7 .. 3.8e-7 over eight input seeds; at the small shapes it spreads from exactly 0 to 3e-7 (B1N2 has 4 or 6 elements),
+and the same correct arithmetic -- `emulated` below, the three-term split product inside the fp64 oracle -- then sits
+anywhere from 0 to 14 floors.  Such a floor is a lucky draw of the restatement, not a statement about fp32: the bar it
+sets would be tighter than the bar the same kernel gets at a larger shape.  So the input seed of a case is the first of
+5, 6, 7, ... at which (i) the floor is at least TYPICAL = 1e-7, the lower end of what the restatement shows at the
+larger shapes (and 5 x update_parity.DEGENERATE), and (ii) for the models whose restatement runs on the oracle's
+`gnn.*` Linears, the design's own arithmetic meets the bar.  Both are properties of the CPU restatement, looked up before
+any kernel ran; tests/test_update_metric.py asserts them for every case.  fp32 results move with the host CPU (a floor by
+up to a factor 2 - 5 between two of them, on one thread each): the seeds below met the rule on both hosts they were
+looked up on."""
+from __future__ import annotations
+
+import contextlib
+import functools
+import io
+
+import torch
+
+import clof_restatement as CR
+import egnn_restatement as ER
+import locs_restatement as LR
+import test_clof as TC
+from aether_amd import _lib
+from aether_amd.synthetic import make_batch
+from gnn_shape_checks import Clof, Egnn
+from oracle import aether_oracle as O
+
+
+def _pieces(t):
+    t32 = t.float()
+    hi = t32.half()
+    lo = (t32 - hi.float()).half()
+    return hi.double(), lo.double()
+
+
+TERMS = ("w_lo*x_hi", "w_hi*x_lo")
+
+
+@contextlib.contextmanager
+def split_linears(drop=None, hi_only_weights=False):
+    """The arithmetic the library's GEMMs are designed to do (csrc/common.h, gemm_split), put into the oracle's `gnn.*`
+    Linears while active: both operands as two fp16 pieces, w_hi x_hi + w_hi x_lo + w_lo x_hi, an fp32 result; the rest
+    of the oracle keeps its dtype.  `drop` = (layer name, one of TERMS) leaves that term out of that layer's product;
+    `hi_only_weights` leaves w_lo out of every layer."""
+    plain = O._linear
+
+    def linear(sd, name, x):
+        if not name.startswith("gnn."):
+            return plain(sd, name, x)
+        wh, wl = _pieces(sd[name + ".weight"])
+        xh, xl = _pieces(x)
+        acc = xh @ wh.T
+        if drop != (name, "w_hi*x_lo"):
+            acc = acc + xl @ wh.T
+        if not hi_only_weights and drop != (name, "w_lo*x_hi"):
+            acc = acc + xh @ wl.T
+        return (acc.float() + sd[name + ".bias"].float()).to(x.dtype)
+
+    O._linear = linear
+    try:
+        yield
+    finally:
+        O._linear = plain
+
+
+@contextlib.contextmanager
+def one_thread():
+    """The restatements on one thread: a fixed reduction order, so that a floor does not move with the thread count."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(n)
+
+
+def _quiet(fn, *a, **k):
+    with contextlib.redirect_stdout(io.StringIO()):
+        return fn(*a, **k)
+
+
+def _cast(t, dtype):
+    return t.to(dtype) if torch.is_tensor(t) and t.is_floating_point() else t
+
+
+def state_of(m, dtype=torch.float32):
+    return {k: v.detach().cpu().to(dtype) if v.is_floating_point() else v.detach().cpu() for k, v in m.state_dict().items()}
+
+
+def to_cuda(inp):
+    return {k: ([e.cuda() for e in v] if k == "edges" else (v.cuda() if torch.is_tensor(v) else v)) for k, v in inp.items()}
+
+
+# ---- Aether, LoCS, DynamicFieldAether: make_batch inputs ------------------------------------------------------------------
+# case = (D, H, B, N, model seed, input seed)
+class AetherFamily:
+    name = "Aether"
+
+    @staticmethod
+    def build(case, device):
+        from aether_amd.nn.state2state.aether import Aether
+        D, H = case[0], case[1]
+        torch.manual_seed(case[4])
+        return _quiet(Aether, 2 * D, H, 0.0, D, device=device)
+
+    @staticmethod
+    def inputs(case):
+        D, _, B, N, _, seed = case
+        return {k: v for k, v in make_batch(B, N, D, seed=seed).items() if k != "meta"}
+
+    @staticmethod
+    def restate(sd, inp, case):
+        return O.aether_forward(sd, inp["x"], inp["vel"], inp["edges"], inp["edge_attr"], inp["charges"])
+
+    @staticmethod
+    def call(m, g, case):
+        return m(g["h"], g["x"], g["edges"], g["vel"], g["edge_attr"], g["charges"])
+
+    @staticmethod
+    def rollout(m, g, case, steps):
+        return m.rollout(g["x"], g["vel"], g["edges"], g["charges"], steps)
+
+    @staticmethod
+    def restate_rollout(sd, inp, case, steps):
+        return O.rollout(sd, inp["x"], inp["vel"], inp["edges"], inp["charges"], steps)
+
+
+class LocsFamily(AetherFamily):
+    name = "LoCS"
+
+    @staticmethod
+    def build(case, device):
+        from aether_amd.nn.state2state.locs import LoCS
+        D, H = case[0], case[1]
+        torch.manual_seed(case[4])
+        return _quiet(LoCS, 2 * D, H, 0.0, D, device=device)
+
+    @staticmethod
+    def restate(sd, inp, case):
+        return LR.forward(sd, inp["x"], inp["vel"], inp["edges"], inp["edge_attr"])
+
+    @staticmethod
+    def call(m, g, case):
+        return m(g["h"], g["x"], g["edges"], g["vel"], g["edge_attr"])
+
+    @staticmethod
+    def restate_rollout(sd, inp, case, steps):
+        return LR.rollout(sd, inp["x"], inp["vel"], inp["edges"], inp["charges"], steps)
+
+
+class DynFieldFamily(AetherFamily):
+    name = "DynamicFieldAether"
+
+    @staticmethod
+    def build(case, device):
+        from aether_amd.nn.state2state.dynamic_field_aether import DynamicFieldAether
+        D, H = case[0], case[1]
+        torch.manual_seed(case[4])
+        return _quiet(DynamicFieldAether, 2 * D, H, 0.0, D, device=device)
+
+    @staticmethod
+    def restate(sd, inp, case):
+        return O.dynamic_field_aether_forward(sd, inp["x"], inp["vel"], inp["edges"], inp["edge_attr"], inp["charges"],
+                                              case[3])
+
+    @staticmethod
+    def call(m, g, case):
+        return m(None, g["x"], g["edges"], g["vel"], g["edge_attr"], g["charges"], case[3])
+
+
+# ---- EGNN-Aether and the ClofNets: the Lorentz runner's inputs (3-D, squared distance), hidden 64, as their tests -----------
+# case = (model, layers, B, N, model seed, input seed)
+class GnnFamily:
+    def __init__(self, K, model, **kw):
+        self.K, self.model, self.kw, self.name = K, model, kw, {"egnn_aether": "EGNN_vel_Aether", "clof": "ClofNet",
+                                                                "clof_vel": "ClofNet_vel", "clof_vel_gbf": "ClofNet_vel_gbf"}[model]
+
+    def cfg(self, case):
+        return self.K.cfg(self.model, 64, case[1], case[4], case[3], **self.kw)
+
+    def build(self, case, device):
+        return self.K.build(self.cfg(case), device)
+
+    def inputs(self, case):
+        return ER.runner_batch(case[2], case[3], case[5])
+
+    def restate(self, sd, inp, case):
+        cfg = self.cfg(case)
+        a = (inp["h"], inp["x"], inp["edges"], inp["vel"], inp["edge_attr"])
+        if self.K is Egnn:
+            return ER.forward(sd, *a, inp["charges"], cfg["L"], cfg["norm_diff"], cfg["tanh"])[0]
+        return CR.forward(sd, CR.VARIANTS[self.model], *a, cfg["L"], cfg["N"], **TC.kwargs(cfg))[0]
+
+    def call(self, m, g, case):
+        a, kw = self.K.args(g, self.cfg(case))
+        return m(*a, **kw)
+
+    def rollout(self, m, g, case, steps):
+        kw = dict(n_nodes=case[3]) if self.K is Clof else {}
+        return m.rollout(g["x"], g["vel"], g["edges"], g["charges"], steps, 1.0, **kw)
+
+    def restate_rollout(self, sd, inp, case, steps):
+        """The protocol of tests/test_gpu_gnn_rollout.py: h = |v|, edge_attr = [q q, |dx|^2], v' = x' - x."""
+        x, vel, q = inp["x"], inp["vel"], inp["charges"].reshape(-1, 1)
+        row, col = inp["edges"]
+        qq = q[row] * q[col]
+        traj = []
+        for _ in range(steps):
+            step = dict(x=x, vel=vel, charges=q, edges=inp["edges"], h=torch.sqrt((vel ** 2).sum(1, keepdim=True)),
+                        edge_attr=torch.cat([qq, ((x[row] - x[col]) ** 2).sum(1, keepdim=True)], 1))
+            xn = self.restate(sd, step, case)
+            vel, x = xn - x, xn
+            traj.append(x)
+        return torch.stack(traj)
+
+
+AETHER, LOCS, DYNFIELD = AetherFamily, LocsFamily, DynFieldFamily
+EGNN = GnnFamily(Egnn, "egnn_aether", norm_diff=True)
+CLOF = GnnFamily(Clof, "clof", norm_diff=True)
+CLOF_VEL = GnnFamily(Clof, "clof_vel", norm_diff=True)
+CLOF_VEL_GBF = GnnFamily(Clof, "clof_vel_gbf", norm_diff=True)
+FAMILIES = {f.name: f for f in (AETHER, LOCS, DYNFIELD, EGNN, CLOF, CLOF_VEL, CLOF_VEL_GBF)}
+
+
+def _in_dtype(inp, dtype):
+    return {k: (v if k == "edges" else _cast(v, dtype)) for k, v in inp.items()}
+
+
+def references_from(family, case, sd32, steps=0):
+    """(x fp32, want fp64, want fp32) of one forward, or with `steps` of the rollout ([steps, n, D] each, x the input)."""
+    inp = family.inputs(case)
+    out = []
+    with torch.no_grad(), one_thread():
+        for dtype in (torch.float64, torch.float32):
+            sd = {k: _cast(v, dtype) for k, v in sd32.items()}
+            i = _in_dtype(inp, dtype)
+            out.append(family.restate_rollout(sd, i, case, steps) if steps else family.restate(sd, i, case))
+    return inp["x"].float(), out[0], out[1]
+
+
+@functools.lru_cache(maxsize=None)
+def references(family_name, case, steps=0):
+    """The same from a module built on the CPU under the case's seed."""
+    family = FAMILIES[family_name]
+    return references_from(family, case, state_of(family.build(case, "cpu")), steps)
+
+
+SPLIT_FAMILIES = ("Aether", "LoCS", "DynamicFieldAether")       # their restatements go through the oracle's `gnn.*` Linears
+
+
+@functools.lru_cache(maxsize=None)
+def emulated(family_name, case):
+    """The output the design's arithmetic gives on a case's inputs: the fp64 restatement under `split_linears`, formed
+    as the kernels form it, fl32(x + fl32(update)).  An input on which this arithmetic by itself leaves the bar would say
+    nothing about a kernel."""
+    family = FAMILIES[family_name]
+    sd = {k: _cast(v, torch.float64) for k, v in state_of(family.build(case, "cpu")).items()}
+    inp = family.inputs(case)
+    with torch.no_grad(), one_thread(), split_linears():
+        out = family.restate(sd, _in_dtype(inp, torch.float64), case)
+    x = inp["x"].float()
+    return x + (out - x.double()).float()
+
+
+# ---- the case tables --------------------------------------------------------------------------------------------------
+MODEL_SEED = 11
+TYPICAL = 1e-7
+STREAMED = _lib.FLAG_FORCE_STREAMED
+# Aether at hidden 64, (D, 64, B, N, model seed, input seed): B2N5 -- edge tiles span graph boundaries; B6N7; B2N20 -- two
+# node tiles, the 12-wave / two-tile-wave kernels; B1N2
+AETHER_64 = [(2, 64, 2, 5, MODEL_SEED, 5), (2, 64, 6, 7, MODEL_SEED, 5), (2, 64, 2, 20, MODEL_SEED, 5), (2, 64, 1, 2, MODEL_SEED, 8),
+             (3, 64, 2, 5, MODEL_SEED, 12), (3, 64, 6, 7, MODEL_SEED, 5), (3, 64, 2, 20, MODEL_SEED, 5), (3, 64, 1, 2, MODEL_SEED, 9)]
+# narrow (zero-padded to 64); wide (multiples of 64) and padded wide
+AETHER_NARROW = [(2, 20, 6, 7, MODEL_SEED, 5), (3, 32, 6, 7, MODEL_SEED, 5)]
+AETHER_WIDE = [(2, 128, 4, 20, MODEL_SEED, 5), (2, 192, 4, 20, MODEL_SEED, 5), (2, 70, 3, 5, MODEL_SEED, 5)]
+LOCS_CASES = [(2, 64, 3, 7, MODEL_SEED, 5), (2, 64, 4, 5, MODEL_SEED, 5), (3, 64, 3, 7, MODEL_SEED, 6), (3, 64, 4, 5, MODEL_SEED, 5)]
+DYNFIELD_CASES = [(2, 64, 1, 2, MODEL_SEED, 5), (2, 64, 4, 5, MODEL_SEED, 5), (3, 64, 1, 2, MODEL_SEED, 17), (3, 64, 4, 5, MODEL_SEED, 5)]
+GNN_CASES = [(fam.name, (fam.model, 2, B, 5, MODEL_SEED, 5)) for fam in (EGNN, CLOF, CLOF_VEL, CLOF_VEL_GBF) for B in (2, 4)]
+ROLLOUT_STEPS = 5
+ROLLOUT_CASES = [("Aether", (2, 64, 2, 5, MODEL_SEED, 5)), ("LoCS", (2, 64, 2, 5, MODEL_SEED, 7)),
+                 ("EGNN_vel_Aether", ("egnn_aether", 4, 2, 5, MODEL_SEED, 25)),
+                 ("ClofNet_vel", ("clof_vel", 4, 2, 5, MODEL_SEED, 25))]
+FORWARD_CASES = ([("Aether", c) for c in AETHER_64 + AETHER_NARROW + AETHER_WIDE] + [("LoCS", c) for c in LOCS_CASES] +
+                 [("DynamicFieldAether", c) for c in DYNFIELD_CASES] + GNN_CASES)
+
+
+def case_id(fc):
+    name, c = fc
+    if isinstance(c[0], str):
+        return f"{name}-L{c[1]}-B{c[2]}N{c[3]}-s{c[5]}"
+    return f"{name}-D{c[0]}-H{c[1]}-B{c[2]}N{c[3]}-s{c[5]}"
