@@ -976,7 +976,8 @@ int backward_inputs_impl(const AetherParams& P, int64_t Nn, int64_t E, const flo
     WsLayout W(Nn, E, D, true);
     auto gp = [&](size_t off) { return reinterpret_cast<const int32_t*>(graph + off); };
     auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    kb_inputs<D><<<dim3((unsigned)((Nn + 7) / 8)), dim3(256), 0, st>>>(P, x, vel, charges, wp(W.nodeinfo), out, g_out, wp(W.DA),
+    (void)out;       // (part of the C ABI: y is formed from the backward's o2 rows, input_grad.h)
+    kb_inputs<D><<<dim3((unsigned)((Nn + 7) / 8)), dim3(256), 0, st>>>(P, x, vel, charges, wp(W.nodeinfo), wp(W.O2), g_out, wp(W.DA),
                                                                        wp(W.DN), wp(W.DF), gp(G.rowptr), gp(G.send_s),
                                                                        gp(G.recv_s), gp(G.srowptr), gp(G.sperm), grad_x,
                                                                        grad_vel, Nn, field_gz);

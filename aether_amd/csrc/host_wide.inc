@@ -109,11 +109,11 @@ int aether_backward_inputs_h(const AetherParams* params, int num_dims, int hidde
     auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     const dim3 grid((unsigned)((n_nodes + 7) / 8));
     if (num_dims == 2)
-        kb_inputs<2><<<grid, dim3(256), 0, st>>>(*params, x, vel, charges, wp(W.nodeinfo), out, grad_out, wp(W.DA), wp(W.DN),
+        kb_inputs<2><<<grid, dim3(256), 0, st>>>(*params, x, vel, charges, wp(W.nodeinfo), wp(W.o2), grad_out, wp(W.DA), wp(W.DN),
                                                wp(W.DF), gp(G.rowptr), gp(G.send_s), gp(G.recv_s), gp(G.srowptr),
                                                gp(G.sperm), grad_x, grad_vel, n_nodes, field_input_grad, hidden);
     else
-        kb_inputs<3><<<grid, dim3(256), 0, st>>>(*params, x, vel, charges, wp(W.nodeinfo), out, grad_out, wp(W.DA), wp(W.DN),
+        kb_inputs<3><<<grid, dim3(256), 0, st>>>(*params, x, vel, charges, wp(W.nodeinfo), wp(W.o2), grad_out, wp(W.DA), wp(W.DN),
                                                wp(W.DF), gp(G.rowptr), gp(G.send_s), gp(G.recv_s), gp(G.srowptr),
                                                gp(G.sperm), grad_x, grad_vel, n_nodes, field_input_grad, hidden);
     if (grad_edge_attr && n_edges > 0) {

@@ -4,7 +4,9 @@
 // The reference's forward (nn/state2state/aether.py:169-186) is differentiable in x / vel.  aether_backward leaves behind
 // everything this needs: DA = dL/d(layer-1 edge features) [E][FPAD] (sorted edge order), DN1 = dL/dn_1 [Nn][64] and
 // DF = dL/df [Nn][16] (kb_field).  Positions and velocities enter through
-//   * out = p + R(v) y                                   (aether.py:182-185; y = R^T (out - p) is recovered from the output)
+//   * out = p + R(v) y                                   (aether.py:182-185; y = Wo6 o2 + b6 from the o2 rows the backward's
+//                                                          out-MLP kernel left: R^T (out - p) would carry the rounding of
+//                                                          out = fl(p + R y), 2^-24 |p|, into y -- 2e-6 of y at |p| = 50 |y|)
 //   * the field net z = [p | v | emb(q)]                  (aether.py:127-134: dz = W0^T dpre1, recomputed here from DF)
 //   * rel_feat = [0 | R^T v | R^T f]                      (aether.py:39-48; through layer_1.res and the features' receiver columns)
 //   * the edge features of j -> i in i's frame            (aether.py:52-92, geometry.py:7-101):
@@ -108,14 +110,14 @@ __device__ __forceinline__ void euler_grad(const float* __restrict__ da, const f
 template <int D>
 __global__ void __launch_bounds__(256)
 kb_inputs(AetherParams P, const float* __restrict__ x, const float* __restrict__ vel, const float* __restrict__ charges,
-          const float* __restrict__ nodeinfo, const float* __restrict__ out, const float* __restrict__ g_out,
-          const float* __restrict__ DA, const float* __restrict__ DN1, const float* __restrict__ DF,
+          const float* __restrict__ nodeinfo, const float* __restrict__ o2 /* [n_nodes][hid]: the out MLP's last input */,
+          const float* __restrict__ g_out, const float* __restrict__ DA, const float* __restrict__ DN1, const float* __restrict__ DF,
           const int32_t* __restrict__ rowptr, const int32_t* __restrict__ send_s, const int32_t* __restrict__ recv_s,
           const int32_t* __restrict__ srowptr, const int32_t* __restrict__ sperm, float* __restrict__ grad_x,
           float* __restrict__ grad_v, int64_t n_nodes,
           const float* __restrict__ field_gz = nullptr /* [n_nodes][2D]: dL/d[p | v] through an EXTERNAL field (the
           dynamic-field variant, aether_dynamic_field_backward_inputs); null = the built-in field net, recomputed below */,
-          int hid = H /* width of DN1 / rows of W_res (wide.h) */) {
+          int hid = H /* width of DN1 and o2 / rows of W_res (wide.h) */) {
     using NI = NodeInfo<D>;
     constexpr int FIN = 2 * D + 16;
     constexpr int O = D * (D - 1) / 2;
@@ -207,14 +209,18 @@ kb_inputs(AetherParams P, const float* __restrict__ x, const float* __restrict__
 #pragma unroll
         for (int a = 0; a < D; ++a) GR[b][a] = sum32(GR[b][a]);
     }
-    // ---- node level: rel_feat = [0 | R^T v | R^T f], out = p + R y
+    // ---- node level: rel_feat = [0 | R^T v | R^T f], out = p + R y with y = Wo6 o2 + b6
     float y[D], go[D];
 #pragma unroll
-    for (int a = 0; a < D; ++a) {
-        float s = 0.f;
+    for (int a = 0; a < D; ++a) y[a] = 0.f;
+    for (int o = t; o < hid; o += 32) {
+        const float oo = o2[nc * hid + o];
 #pragma unroll
-        for (int b = 0; b < D; ++b) s += ni[NI::R + b * D + a] * (out[nc * D + b] - ni[NI::P + b]);
-        y[a] = s;
+        for (int a = 0; a < D; ++a) y[a] += P.out_w6[a * hid + o] * oo;
+    }
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        y[a] = sum32(y[a]) + P.out_b6[a];
         go[a] = g_out[nc * D + a];
     }
 #pragma unroll

@@ -244,7 +244,8 @@ int aether_rollout_dynamic_field(const AetherParams* params, const AetherDynFiel
 /*
  * Gradients with respect to the INPUTS of the step (round 3) -- the reference's forward is differentiable in x / vel
  * (nn/state2state/aether.py:169-186).  Call after aether_backward, on the same workspace (it reads what that call left:
- * dL/d(layer-1 edge features), dL/dn_1, dL/df) with `out` = the forward's output and the same grad_out:
+ * dL/d(layer-1 edge features), dL/dn_1, dL/df and the out MLP's last input o2, from which y of x + R(v) y is formed) with
+ * `out` = the forward's output (kept in the signature; no longer read) and the same grad_out:
  *   grad_x [n_nodes][D], grad_vel [n_nodes][D] (overwritten); grad_edge_attr [n_edges][2] in the caller's edge order, or
  *   NULL.  field_input_grad = NULL: the built-in field net (its input gradient is recomputed from dL/df).  For a step that
  *   ran through aether_forward_field: after aether_backward_field, float[n_nodes][2D] = dL/d[x | vel] THROUGH the external
