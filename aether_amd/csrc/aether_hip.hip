@@ -990,6 +990,49 @@ int backward_inputs_impl(const AetherParams& P, int64_t Nn, int64_t E, const flo
 
 #include "wide_impl.inc"
 
+// Test hook of the split helpers (aether_debug_split; tests/test_gpu_split_forms.py): one workgroup of 12 waves, three per
+// SIMD as in the 12-wave k_fused.  Wave w takes the tiles w, w + 12, .. ([16 rows][64] floats each), runs the range test and
+// gemm_split<4, 2> (through gemm_split_keep, which also hands out the pieces) against a fixed 64 x 64 weight image in LDS,
+// and writes the pieces of the (scaled) operand, the SplitScale decision and the product.  Every wave's vector work runs
+// between and beside the other waves' 16-bit MFMAs.
+constexpr int DEBUG_SPLIT_WAVES = 12;
+__global__ void __launch_bounds__(64 * DEBUG_SPLIT_WAVES)
+k_debug_split(const float* __restrict__ x, int n_tiles, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo, int* __restrict__ on,
+              float* __restrict__ scale, float* __restrict__ y) {
+    __shared__ __attribute__((aligned(16))) float img[SPLIT_WIMG];
+    // W[r][c]: a multiple of 2^-6 of magnitude < 1/2 plus a multiple of 2^-15, so that both pieces are populated
+    for (int idx = threadIdx.x; idx < 64 * 16; idx += 64 * DEBUG_SPLIT_WAVES) {
+        const int r = idx >> 4, c = (idx & 15) * 4;
+        f32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            v[j] = (float)((r * 29 + (c + j) * 13) % 61 - 30) * 0.015625f + (float)((r * 7 + (c + j) * 3) % 17) * 0.000030517578125f;
+        stage_split4<4, 2>(img, r, c, v);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, q = lane >> 4;
+    for (int t = wave; t < n_tiles; t += DEBUG_SPLIT_WAVES) {
+        const size_t row = ((size_t)t * 16 + i) * 64;
+        f32x4 act[4], acc[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) { act[b] = ld4(x + row + 16 * b + 4 * q); acc[b] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        f16x8 xh[2], xl[2];
+        const SplitScale sc = gemm_split_keep<4, 2>(img, act, acc, lane, xh, xl);
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            // elements j < 4: features 32 kb + 4 q + j; j >= 4: 32 kb + 16 + 4 q + (j - 4)
+            const u32x4 h = __builtin_bit_cast(u32x4, xh[kb]), l = __builtin_bit_cast(u32x4, xl[kb]);
+            *reinterpret_cast<u32x2*>(hi + row + 32 * kb + 4 * q) = u32x2{h[0], h[1]};
+            *reinterpret_cast<u32x2*>(hi + row + 32 * kb + 16 + 4 * q) = u32x2{h[2], h[3]};
+            *reinterpret_cast<u32x2*>(lo + row + 32 * kb + 4 * q) = u32x2{l[0], l[1]};
+            *reinterpret_cast<u32x2*>(lo + row + 32 * kb + 16 + 4 * q) = u32x2{l[2], l[3]};
+        }
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) st4(y + row + 16 * mb + 4 * q, acc[mb]);
+        if (lane == 0) { on[t] = sc.on ? 1 : 0; scale[t] = sc.s; }
+    }
+}
+
 }  // namespace
 
 // =================================================================== C ABI
@@ -1626,6 +1669,15 @@ int64_t aether_debug_fetch(const char* name, int num_dims, int64_t n_nodes, int6
     if (!strcmp(name, "efeat"))      // layer-1 edge features [E][FPAD] (kept with KEEP_INTERMEDIATES), sorted order
         return copy2d((const float*)(ws + W.feat), n_edges, FPAD, 0, FPAD);
     return fail(AETHER_EINVAL, "debug_fetch: unknown name");
+}
+
+int aether_debug_split(const float* x, int n_tiles, uint16_t* hi, uint16_t* lo, int* on, float* scale, float* y) {
+    if (!x || !hi || !lo || !on || !scale || !y) return fail(AETHER_EINVAL, "debug_split: null pointer");
+    if (n_tiles < 0) return fail(AETHER_EINVAL, "debug_split: n_tiles");
+    if (n_tiles == 0) return AETHER_OK;
+    k_debug_split<<<dim3(1), dim3(64 * DEBUG_SPLIT_WAVES), 0, nullptr>>>(x, n_tiles, hi, lo, on, scale, y);
+    HIP_OK(hipGetLastError());
+    return AETHER_OK;
 }
 
 #include "host_wide.inc"

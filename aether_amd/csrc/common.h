@@ -140,7 +140,7 @@ __device__ __forceinline__ void gemm_tile(const float* __restrict__ w, int ldw,
 // Round 4 (every split GEMM of the library: gemm_split / gemm_split_T below, k_wgemm, k_s2s_gemm_split, k_s2s_filter_split):
 // two fp16 pieces, x = hi + lo with hi = fp16(x),
 // lo = fp16(x - hi) -- 22 significand bits -- and THREE terms  hi*hi + hi*lo + lo*hi  (lo*lo <= 2^-22 relative): half the
-// MFMAs and 2.5 instead of 5 vector instructions per split value, for an error of 2^-22 instead of 2^-24 per product
+// MFMAs and 2 instead of 5 vector instructions per split value, for an error of 2^-22 instead of 2^-24 per product
 // (parity bar: 1e-5 = 2^-16.6).  fp16 has a narrow exponent range (normal from 2^-14, top 65,504); it is handled so:
 //   * weights are split as they are: a weight's lo piece is a subnormal below |w| = 2^-3 (absolute error <= 2^-25 there),
 //     which the fp16 MFMA reads exactly; |w| >= 65,504 cannot be represented (outputs come out non-finite, not wrong);
@@ -156,21 +156,47 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // ---- two fp16 pieces
 constexpr int SPLIT_WIMG = 2 * 4 * 2 * 64 * 4;          // floats of the split image of a 64 x 64 matrix (2 terms x 8 KB)
+// lo = fp16(x - fp32(hi)) as one instruction per value: v_fma_mixlo_f16 / v_fma_mixhi_f16 computes fma(fp32(h), -1, x) -- one
+// rounding of the same exact number as the subtraction, and for finite x in fp16's range x - hi is exact in fp32 -- and
+// rounds it into the low / high half of the destination.  The compiler does not select the instruction from
+// (_Float16)fmaf((float)h, -1.0f, x) (it folds the product into v_sub_f32), hence asm; not volatile, so it is scheduled like
+// any other vector code.  The fp16 source is always read from the LOW half of its register (op_sel 0 on src0): the
+// high-half read is the operand form rule R3 keeps out of packed fp32 math, and nothing here needs it.
+// AETHER_SPLIT_PARENT_FORMS builds the forms of before (cvt / cvt / sub / cvt and the fmaxf tree) for the bit comparison of
+// tests/test_gpu_split_forms.py; never the product.
 __device__ __forceinline__ void split_f16x2(float x, _Float16& h, _Float16& l) {
     h = (_Float16)x;
+#ifdef AETHER_SPLIT_PARENT_FORMS
     l = (_Float16)(x - (float)h);
+#else
+    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(h), "v"(x));
+#endif
+}
+// two values: hi = (fp16(x0), fp16(x1)) by v_cvt_pk_f16_f32 (round to nearest even), lo by one mix instruction each; the
+// second value's hi is moved to a low half first (one shift).  Four instructions per pair.
+__device__ __forceinline__ void split_pair(const f32x2 x, f16x2& h, f16x2& l) {
+    h = __builtin_convertvector(x, f16x2);
+#ifdef AETHER_SPLIT_PARENT_FORMS
+    l = __builtin_convertvector(x - __builtin_convertvector(h, f32x2), f16x2);
+#else
+    const unsigned hb = __builtin_bit_cast(unsigned, h), h1 = hb >> 16;
+    unsigned lb;
+    // (one statement for the pair: as two, k_edge_layer -- 12 waves, 168 registers -- spilled 20 bytes)
+    asm("v_fma_mixlo_f16 %0, %1, -1.0, %3 op_sel_hi:[1,0,0]\n\tv_fma_mixhi_f16 %0, %2, -1.0, %4 op_sel_hi:[1,0,0]"
+        : "=&v"(lb) : "v"(hb), "v"(h1), "v"(x[0]), "v"(x[1]));
+    l = __builtin_bit_cast(f16x2, lb);
+#endif
 }
 // The lane's B fragment of one 32-deep k block from two accumulator-layout blocks: element j < 4 is hidden unit
 // 32 kb + 4 q + j, element j >= 4 is 32 kb + 16 + 4 q + (j - 4) -- a permutation of the natural k order; weight images
-// (stage_split4) are written in the same order.  On pairs (the library is built without the SLP vectoriser, build.py):
-// v_cvt_pk_f16_f32, two v_cvt_f32_f16, v_pk_add_f32, v_cvt_pk_f16_f32 -- five instructions per two values.
+// (stage_split4) are written in the same order.  On pairs (split_pair): v_cvt_pk_f16_f32, v_lshrrev_b32, v_fma_mixlo_f16,
+// v_fma_mixhi_f16 -- four instructions per two values (five before: cvt_pk, two v_cvt_f32_f16, v_pk_add_f32, cvt_pk).
 __device__ __forceinline__ void split8(const f32x4 v0, const f32x4 v1, f16x8& hi, f16x8& lo) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
         const f32x2 x = p < 2 ? f32x2{v0[2 * p], v0[2 * p + 1]} : f32x2{v1[2 * p - 4], v1[2 * p - 3]};
-        const f16x2 h = __builtin_convertvector(x, f16x2);
-        const f32x2 r = x - __builtin_convertvector(h, f32x2);
-        const f16x2 l = __builtin_convertvector(r, f16x2);
+        f16x2 h, l;
+        split_pair(x, h, l);
         hi[2 * p] = h[0]; hi[2 * p + 1] = h[1];
         lo[2 * p] = l[0]; lo[2 * p + 1] = l[1];
     }
@@ -183,10 +209,11 @@ __device__ __forceinline__ void stage_split4(float* img, int row, int col, const
     const int mb = row >> 4, m = row & 15, kb = col >> 5, c5 = col & 31, half = c5 >> 4, qq = (c5 & 15) >> 2;
     f16x4 h, l;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        _Float16 a, b;
-        split_f16x2(v[j], a, b);
-        h[j] = a; l[j] = b;
+    for (int p = 0; p < 2; ++p) {
+        f16x2 a, b;
+        split_pair(f32x2{v[2 * p], v[2 * p + 1]}, a, b);
+        h[2 * p] = a[0]; h[2 * p + 1] = a[1];
+        l[2 * p] = b[0]; l[2 * p + 1] = b[1];
     }
     const int frag = (mb * KBN + kb) * 64 + m + 16 * qq;
     constexpr int TERM = MBN * KBN * 64;                        // fragments per term
@@ -208,11 +235,22 @@ __device__ __forceinline__ unsigned wave_max_exponent(float m) { return (wave_ma
 // in [121, 141], i.e. 2^-6 <= max < 2^15; or 0: all zeros), or a power-of-two scale that puts the maximum into 2^13..2^14
 // (exponent clamped to +-40).  Wave-uniform.
 struct SplitScale { bool on; float s, inv_s; };
+// max(m, |v[0]|, .., |v[3]|) for m that is not a NaN; a NaN element is dropped (fmaxf, and v_max3_f32 in IEEE mode).  As a
+// chain of max(max(m, |a|), |b|) it is two v_max3_f32 with abs modifiers; as the tree max(max(m, max(|a|, |b|)), max(|c|, |d|))
+// of before the compiler first quieted every |x| with a v_max_f32 x, x of its own: 28 instructions for 16 values, not 8.
+__device__ __forceinline__ float absmax4(float m, const f32x4 v) {
+#ifdef AETHER_SPLIT_PARENT_FORMS
+    return fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+#else
+    m = fmaxf(fmaxf(m, fabsf(v[0])), fabsf(v[1]));
+    return fmaxf(fmaxf(m, fabsf(v[2])), fabsf(v[3]));
+#endif
+}
 template <int N>
 __device__ __forceinline__ SplitScale split_scale_of(const f32x4 (&act)[N]) {
     float m = 0.0f;
 #pragma unroll
-    for (int b = 0; b < N; ++b) m = fmaxf(fmaxf(m, fmaxf(fabsf(act[b][0]), fabsf(act[b][1]))), fmaxf(fabsf(act[b][2]), fabsf(act[b][3])));
+    for (int b = 0; b < N; ++b) m = absmax4(m, act[b]);
     // The common case costs two compares: no lane at or above 2^15, some lane at or above 2^-6 (or nothing but zeros).  Only
     // the other case needs the maximum itself (the DPP reduction).
     const bool big = __builtin_amdgcn_ballot_w64(m >= 32768.0f) != 0ull;

@@ -63,7 +63,7 @@ k_s2s_absmax(const float* __restrict__ x, int64_t n4 /* float4 count */, float* 
     float m = 0.0f;
     for (int64_t idx = (int64_t)blockIdx.x * 1024 + threadIdx.x; idx < n4; idx += (int64_t)(FILT_TRAILER - 1) * 1024) {
         const f32x4 v = ld4(x + 4 * idx);
-        m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+        m = absmax4(m, v);
     }
     __shared__ float red[1024];
     red[threadIdx.x] = m;

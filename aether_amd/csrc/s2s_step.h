@@ -363,7 +363,7 @@ k_s2s_gemm_split(const S2SJobs jobs) {
             float v = 0.0f;
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh)
-                v = fmaxf(fmaxf(v, fmaxf(fabsf(xa[nb][hh][0]), fabsf(xa[nb][hh][1]))), fmaxf(fabsf(xa[nb][hh][2]), fabsf(xa[nb][hh][3])));
+                v = absmax4(v, xa[nb][hh]);
             unsigned u = __float_as_uint(v);
             const auto r16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
             u = r16[0] > r16[1] ? r16[0] : r16[1];
@@ -633,7 +633,7 @@ k_s2s_gemm_split_r1(const S2SJobs jobs) {
             float v = 0.0f;
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh)
-                v = fmaxf(fmaxf(v, fmaxf(fabsf(xa[nb][hh][0]), fabsf(xa[nb][hh][1]))), fmaxf(fabsf(xa[nb][hh][2]), fabsf(xa[nb][hh][3])));
+                v = absmax4(v, xa[nb][hh]);
             v = fmaxf(v, __shfl_xor(v, 16));
             v = fmaxf(v, __shfl_xor(v, 32));                      // the row's maximum over this step's 32 k, in all four q lanes
             m[nb] = v;

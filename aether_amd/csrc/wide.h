@@ -82,7 +82,7 @@ k_wgemm(const WGemmArgs G) {
         float m = 0.0f;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            m = fmaxf(fmaxf(m, fmaxf(fabsf(va[j][0]), fabsf(va[j][1]))), fmaxf(fabsf(va[j][2]), fabsf(va[j][3])));
+            m = absmax4(m, va[j]);
         const unsigned wm = wave_max_bits(m);                      // one LDS atomic per wave, not per lane
         if (lane == 0) atomicMax(smax + (kb & 1), wm);
     };

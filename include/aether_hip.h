@@ -207,6 +207,16 @@ int64_t aether_debug_fetch(const char* name, int num_dims, int64_t n_nodes, int6
                            const void* workspace, float* dst, void* stream);
 
 /*
+ * Test hook of the fp16 split that every split GEMM of the library shares (csrc/common.h: split_scale_of, split8).
+ * x = n_tiles tiles of [16 rows][64] floats (device).  One workgroup of 12 waves (three per SIMD) runs, per tile, the range
+ * test and the 64 x 64 split GEMM against a fixed weight image, each wave beside the other waves' MFMAs, and writes
+ *   hi, lo [n_tiles][16][64]  bit patterns of the fp16 pieces of s * x,   on, scale [n_tiles]  the decision and s,
+ *   y [n_tiles][16][64]       the product.
+ * Launches on the null stream.  Returns AETHER_OK or a negative error.
+ */
+int aether_debug_split(const float* x, int n_tiles, uint16_t* hi, uint16_t* lo, int* on, float* scale, float* y);
+
+/*
  * Dynamic-field variant of the state2state model: DynamicFieldAether.forward
  * (nn/state2state/dynamic_field_aether.py:79-100) = aether_dynamic_field (LatentFieldNetwork, :31-48:
  * attention-pooled graph summary + FiLM field net, hidden 32) followed by aether_forward_field, i.e.
