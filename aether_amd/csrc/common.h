@@ -394,6 +394,61 @@ __device__ __forceinline__ f32x4 gemm_split_regs(const f16x8 (&wh)[KBN], const f
     if (sc.on) acc = acc * sc.inv_s;
     return acc;
 }
+// ---- a 64-deep operand that several waves multiply (k_fused's 12-wave node phase): split ONCE, by the waves that produce it.
+// The producer of units 16 mb + 4 q .. + 3 of item i holds half mb & 1 of fragment kb = mb >> 1 of consumer lane (i, q)
+// (split8's order), so it stores its hi and lo pieces as one 8-byte LDS write each into [hi | lo][kb 2][lane 64] x 16 bytes,
+// and a consumer reads its four fragments back as they stand.  The same split_pair on the same fp32 values as split8.
+constexpr int SPLIT_PIECES = 2 * 2 * 64 * 4;            // floats of one 64-deep operand's pieces (4 KB)
+__device__ __forceinline__ void pieces_store(float* __restrict__ pieces, int i, int q, int mb, const f32x4 v) {
+    f16x4 h, l;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        f16x2 a, b;
+        split_pair(f32x2{v[2 * p], v[2 * p + 1]}, a, b);
+        h[2 * p] = a[0]; h[2 * p + 1] = a[1];
+        l[2 * p] = b[0]; l[2 * p + 1] = b[1];
+    }
+    const int at = ((mb >> 1) * 64 + i + 16 * q) * 4 + (mb & 1) * 2;
+    *reinterpret_cast<f16x4*>(pieces + at) = h;
+    *reinterpret_cast<f16x4*>(pieces + SPLIT_PIECES / 2 + at) = l;
+}
+// split_scale_of's three wave-wide facts about the producing wave's share of the operand (m = absmax4 over the lane's values:
+// the same compares, a NaN dropped the same way) as one word in the wave's own slot: bit 0 some |v| >= 2^15, bit 1 some
+// |v| >= 2^-6, bit 2 some |v| > 0.  A consumer ORs the producers' words.
+__device__ __forceinline__ void range_word_store(float* __restrict__ slot, float m, int lane) {
+    const unsigned big = __builtin_amdgcn_ballot_w64(m >= 32768.0f) != 0ull;
+    const unsigned some = __builtin_amdgcn_ballot_w64(m >= 0.015625f) != 0ull;
+    const unsigned any = __builtin_amdgcn_ballot_w64(m > 0.0f) != 0ull;
+    if (lane == 0) *reinterpret_cast<unsigned*>(slot) = big | some << 1 | any << 2;
+}
+// gemm_split_regs<2> on such an operand: `pieces` / `words` as above (four producing waves), `rows` = the lane's fp32 values
+// (block a at rows + 16 a), read only when the operand needs a scale -- then gemm_split_regs as it stands, scale included.
+// Plain path: no range test and no split in front of the six MFMAs, which run in gemm_split_regs' order.
+__device__ __forceinline__ f32x4 gemm_pieces_regs(const f16x8 (&wh)[2], const f16x8 (&wl)[2], const float* __restrict__ pieces,
+                                                  const float* __restrict__ words, const float* __restrict__ rows, int lane, f32x4 acc) {
+    const f16x8* pc = reinterpret_cast<const f16x8*>(pieces);
+    const u32x4 w = *reinterpret_cast<const u32x4*>(words);
+    f16x8 xh[2], xl[2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+        xh[kb] = pc[kb * 64 + lane];
+        xl[kb] = pc[128 + kb * 64 + lane];
+    }
+    const unsigned f = __builtin_amdgcn_readfirstlane(w[0] | w[1] | w[2] | w[3]);
+    if (__builtin_expect((f & 1u) || ((f & 4u) && !(f & 2u)), 0)) {      // big || (any && !some), wave-uniform
+        f32x4 act[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) act[a] = ld4(rows + 16 * a);
+        return gemm_split_regs<2>(wh, wl, act, acc);
+    }
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[kb], xh[kb], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kb], xl[kb], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kb], xh[kb], acc, 0, 0, 0);
+    }
+    return acc;
+}
 // the lane's fragments (mb, kb = 0 .. KBN) of both terms from an image of MBN row blocks in global memory
 template <int MBN, int KBN>
 __device__ __forceinline__ void load_split_frags(const float* __restrict__ img, int mb, int lane, f16x8 (&wh)[KBN], f16x8 (&wl)[KBN]) {

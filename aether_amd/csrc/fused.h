@@ -962,6 +962,13 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             for (int t = bt0; t < bt1; ++t) sum += ld4(part + (aslot + t) * LDW + ac4);
             const f32x4 nv = ld4(xbuf + aslot * LDW + ac4) + sum / adeg;
             st4(nbuf + aslot * LDW + ac4, nv);
+            if constexpr (NW == 12) {
+                // the one node tile's 16 rows (waves 0-3) also as step 2's B fragments, with the waves' range words
+                if (wave < 4) {
+                    pieces_store(smem + L::NPC, aslot, tid & 3, (tid & 15) >> 2, nv);
+                    range_word_store(smem + L::PFLAG + wave, absmax4(0.0f, nv), lane);
+                }
+            }
             if (keep && aslot < n) st4(dbg.n[layer - 1] + (int64_t)(nb + aslot) * H + ac4, nv);
         }
         // The wave's W3 / W4 / W_s / W_r fragments have arrived: a wait the compiler's wait-count pass sees (simm16 of
@@ -977,19 +984,22 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             float* ubuf = smem + L::UBUF;
             const f32x4 bv = ld4(cb + CB_B3 + 16 * mb2 + 4 * q);
 #pragma unroll
-            for (int tn = 0; tn < 2; ++tn) {
+            for (int tn = 0; tn < (NW == 12 ? 1 : 2); ++tn) {
                 if (16 * tn < n) {
-                    f32x4 nv[4];
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) nv[a] = ld4(nbuf + (16 * tn + i) * LDW + 16 * a + 4 * q);
-                    f32x4 acc;
                     if constexpr (NW == 12) {
+                        // n comes split from step 1; u goes on to step 3 split, half mb2 >> 2 of its 128 units
                         const f16x8 wh2[2] = {wf_h[0], wf_h[1]}, wl2[2] = {wf_l[0], wf_l[1]};
-                        acc = gemm_split_regs<2>(wh2, wl2, nv, bv);
+                        const f32x4 uv = silu4(gemm_pieces_regs(wh2, wl2, smem + L::NPC, smem + L::PFLAG, nbuf + i * LDW + 4 * q, lane, bv));
+                        st4(ubuf + i * LDU + 16 * mb2 + 4 * q, uv);
+                        pieces_store(smem + L::UPC + (mb2 >> 2) * SPLIT_PIECES, i, q, mb2 & 3, uv);
+                        range_word_store(smem + L::PFLAG + 4 + mb2, absmax4(0.0f, uv), lane);
                     } else {
-                        acc = gemm_split_regs<2>(w3h, w3l, nv, bv);
+                        f32x4 nv[4];
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) nv[a] = ld4(nbuf + (16 * tn + i) * LDW + 16 * a + 4 * q);
+                        const f32x4 acc = gemm_split_regs<2>(w3h, w3l, nv, bv);
+                        st4(ubuf + (16 * tn + i) * LDU + 16 * mb2 + 4 * q, silu4(acc));
                     }
-                    st4(ubuf + (16 * tn + i) * LDU + 16 * mb2 + 4 * q, silu4(acc));
                 }
             }
         }
@@ -1016,19 +1026,24 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             f32x4 acc = ld4(cb + CB_B4 + 16 * mb3 + 4 * q);
 #pragma unroll
             for (int hk = 0; hk < 2; ++hk) {                   // k halves of 64 (each with its own range check): fewer live registers
-                f32x4 uv[4];
-#pragma unroll
-                for (int a = 0; a < 4; ++a) uv[a] = ld4(ubuf + (16 * tn3s + i) * LDU + 16 * (4 * hk + a) + 4 * q);
                 if constexpr (NW == 12) {
                     const f16x8 wh2[2] = {wf_h[2 * hk], wf_h[2 * hk + 1]}, wl2[2] = {wf_l[2 * hk], wf_l[2 * hk + 1]};
-                    acc = gemm_split_regs<2>(wh2, wl2, uv, acc);
+                    acc = gemm_pieces_regs(wh2, wl2, smem + L::UPC + hk * SPLIT_PIECES, smem + L::PFLAG + 4 + 4 * hk,
+                                           ubuf + i * LDU + 64 * hk + 4 * q, lane, acc);
                 } else {
+                    f32x4 uv[4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) uv[a] = ld4(ubuf + (16 * tn3s + i) * LDU + 16 * (4 * hk + a) + 4 * q);
                     const f16x8 wh2[2] = {w4h[2 * hk], w4h[2 * hk + 1]}, wl2[2] = {w4l[2 * hk], w4l[2 * hk + 1]};
                     acc = gemm_split_regs<2>(wh2, wl2, uv, acc);
                 }
             }
             acc += ld4(nbuf + (16 * tn3s + i) * LDW + 16 * mb3 + 4 * q);
             st4(xbuf + (16 * tn3s + i) * LDW + 16 * mb3 + 4 * q, acc);
+            if constexpr (NW == 12) {             // x split for step 4 / the out MLP (waves 8-11 here)
+                pieces_store(smem + L::XPC, i, q, mb3, acc);
+                range_word_store(smem + L::PFLAG + 12 + mb3, absmax4(0.0f, acc), lane);
+            }
             if (keep && 16 * tn3s + i < n)
                 st4(dbg.x[layer] + (int64_t)(nb + 16 * tn3s + i) * H + 16 * mb3 + 4 * q, acc);
         }
@@ -1050,13 +1065,16 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             }
             if (16 * tn4 < n) {
                 f32x4 xv[4];
+                if constexpr (NW != 12) {         // (12 waves: x comes split from step 3)
 #pragma unroll
-                for (int a = 0; a < 4; ++a) xv[a] = ld4(xbuf + (16 * tn4 + i) * LDW + 16 * a + 4 * q);
+                    for (int a = 0; a < 4; ++a) xv[a] = ld4(xbuf + (16 * tn4 + i) * LDW + 16 * a + 4 * q);
+                }
                 if (do_s) {
                     f32x4 accs;
                     if constexpr (NW == 12) {
                         const f16x8 wh2[2] = {wf_h[2], wf_h[3]}, wl2[2] = {wf_l[2], wf_l[3]};
-                        accs = gemm_split_regs<2>(wh2, wl2, xv, f32x4{0.f, 0.f, 0.f, 0.f});
+                        accs = gemm_pieces_regs(wh2, wl2, smem + L::XPC, smem + L::PFLAG + 12, xbuf + i * LDW + 4 * q, lane,
+                                                f32x4{0.f, 0.f, 0.f, 0.f});
                     } else {
                         accs = gemm_split_regs<2>(wsh, wsl, xv, f32x4{0.f, 0.f, 0.f, 0.f});
                     }
@@ -1084,7 +1102,8 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                     f32x4 accr;
                     if constexpr (NW == 12) {
                         const f16x8 wh2[2] = {wf_h[2], wf_h[3]}, wl2[2] = {wf_l[2], wf_l[3]};
-                        accr = gemm_split_regs<2>(wh2, wl2, xv, ld4(cb + CB_B1N + 16 * mb3 + 4 * q));
+                        accr = gemm_pieces_regs(wh2, wl2, smem + L::XPC, smem + L::PFLAG + 12, xbuf + i * LDW + 4 * q, lane,
+                                                ld4(cb + CB_B1N + 16 * mb3 + 4 * q));
                     } else {
                         accr = gemm_split_regs<2>(wrh, wrl, xv, ld4(cb + CB_B1N + 16 * mb3 + 4 * q));
                     }
@@ -1129,14 +1148,15 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         const bool act2 = NW == 12 ? wave >= 4 && wave < 8 && n > 0 : act;
         const float* cb = cblk;                          // slot 0: block 4 (out_b0, out_b3, out_b6, out_w6)
         if (act1) {
-            f32x4 xv[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) xv[a] = ld4(xbuf + (16 * tn + i) * LDW + 16 * a + 4 * q);
             f32x4 acc;
             if constexpr (NW == 12) {
                 const f16x8 wh2[2] = {wf_h[2], wf_h[3]}, wl2[2] = {wf_l[2], wf_l[3]};
-                acc = gemm_split_regs<2>(wh2, wl2, xv, ld4(cb + CB_B1N + 16 * mb + 4 * q));
+                acc = gemm_pieces_regs(wh2, wl2, smem + L::XPC, smem + L::PFLAG + 12, xbuf + i * LDW + 4 * q, lane,
+                                       ld4(cb + CB_B1N + 16 * mb + 4 * q));
             } else {
+                f32x4 xv[4];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) xv[a] = ld4(xbuf + (16 * tn + i) * LDW + 16 * a + 4 * q);
                 acc = gemm_split_regs<2>(wsh, wsl, xv, ld4(cb + CB_B1N + 16 * mb + 4 * q));
             }
             f32x4 v = silu4(acc);
@@ -1145,20 +1165,25 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                     v = v * ld4(dbg.step.drop1 + (int64_t)(nb + 16 * tn + i) * H + 16 * mb + 4 * q);
             }
             st4(o1 + (16 * tn + i) * LDW + 16 * mb + 4 * q, v);
+            if constexpr (NW == 12) {             // o1 split for stage 2 (waves 0-3 here)
+                pieces_store(smem + L::OPC, i, q, mb, v);
+                range_word_store(smem + L::PFLAG + 16 + mb, absmax4(0.0f, v), lane);
+            }
         }
         if constexpr (KEEP) {
             if (blockIdx.x == 0 && tid == 0 && dbg.step.dropword != nullptr) *dbg.step.dropword = dbg.step.drop1 != nullptr ? 1 : 0;
         }
         lds_barrier();
         if (act2) {
-            f32x4 xv[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) xv[a] = ld4(o1 + (16 * tn + i) * LDW + 16 * a + 4 * q);
             f32x4 acc;
             if constexpr (NW == 12) {
                 const f16x8 wh2[2] = {wf_h[2], wf_h[3]}, wl2[2] = {wf_l[2], wf_l[3]};
-                acc = gemm_split_regs<2>(wh2, wl2, xv, ld4(cb + CB_OB3 + 16 * mb + 4 * q));
+                acc = gemm_pieces_regs(wh2, wl2, smem + L::OPC, smem + L::PFLAG + 16, o1 + i * LDW + 4 * q, lane,
+                                       ld4(cb + CB_OB3 + 16 * mb + 4 * q));
             } else {
+                f32x4 xv[4];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) xv[a] = ld4(o1 + (16 * tn + i) * LDW + 16 * a + 4 * q);
                 acc = gemm_split_regs<2>(wrh, wrl, xv, ld4(cb + CB_OB3 + 16 * mb + 4 * q));
             }
             f32x4 v = silu4(acc);

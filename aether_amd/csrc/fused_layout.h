@@ -62,6 +62,16 @@ template <int NW, int ROUNDS> struct FusedLds {          // offsets in floats
     static constexpr int UBUF = SCRATCH;                               // [32][LDU]
     static constexpr int OBUF1 = SCRATCH;                              // [32][LDW]
     static constexpr int OBUF2 = SCRATCH + FUSED_MAX_NODES * LDW;      // [32][LDW]
+    // 12 waves: the node phase's shared operands (n, u, x, the out MLP's o1) as fp16 pieces in the consumers' B-fragment
+    // shape, written by the operand's producer next to the fp32 rows (common.h, pieces_store): u as two 64-unit halves.
+    // Behind UBUF / OBUF2 in the part of SCRATCH that only the edge phase's tile staging uses: written and read between
+    // the barrier that ends a layer's edge tiles and the one that starts the next layer's, where the staging rows are idle.
+    static constexpr int NPC = SCRATCH + (LDU > 2 * LDW ? LDU : 2 * LDW) * FUSED_MAX_NODES;   // [hi | lo][2 k blocks][64 lanes] x 16 bytes
+    static constexpr int UPC = NPC + SPLIT_PIECES;                     // [2 halves] of the same
+    static constexpr int XPC = UPC + 2 * SPLIT_PIECES;
+    static constexpr int OPC = XPC + SPLIT_PIECES;
+    static constexpr int PFLAG = OPC + SPLIT_PIECES;                   // [5 operands][4 producing waves] range words (n, u half 0, u half 1, x, o1)
+    static_assert(NW != 12 || (NPC >= OBUF2 + FUSED_MAX_NODES * LDW && NPC >= UBUF + FUSED_MAX_NODES * LDU && PFLAG + 5 * 4 <= TOTAL && NPC % 4 == 0), "operand pieces");
     static_assert(FIELD_END <= TOTAL, "field scratch");
     static_assert(UBUF + FUSED_MAX_NODES * LDU <= TOTAL, "ubuf");
     static_assert(OBUF2 + FUSED_MAX_NODES * LDW <= TOTAL, "obuf");
