@@ -179,6 +179,16 @@ SIGNATURES = {
                                 [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3),
     "aether_s2s_locs_encoder_features": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_int64, C.c_int64] +
                                          [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 2),
+    "aether_s2s_dnri_plan_bytes": (C.c_size_t, [C.c_void_p] * 2 + [C.c_int] * 8),
+    "aether_s2s_dnri_plan_build": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "aether_s2s_dnri_workspace_bytes": (C.c_size_t, [C.c_int] * 6 + [C.c_int64, C.c_int64]),
+    "aether_s2s_dnri_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_float, C.c_int64, C.c_int64] +
+                             [C.c_void_p] * 10 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 7),
+    "aether_s2s_dnri_rollout": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_float, C.c_int64, C.c_int64] +
+                                [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 +
+                                [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3),
+    "aether_s2s_dnri_encoder_features": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_int64, C.c_int64] +
+                                         [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 2),
     "aether_knn_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "aether_knn_edges": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 6 +
                          [C.c_size_t, C.c_void_p]),

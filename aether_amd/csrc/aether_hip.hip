@@ -42,6 +42,7 @@
 #include "s2s_markov.h"
 #include "s2s_charges.h"
 #include "s2s_locs.h"
+#include "s2s_dnri.h"
 #include "dynfield.h"
 #include "s2s_dynfield.h"
 #include "knn.h"
@@ -1047,6 +1048,7 @@ const char* aether_last_error(void) { return g_err; }
 #include "host_s2s_charges.inc"
 #include "host_s2s_dynfield.inc"
 #include "host_s2s_locs.inc"
+#include "host_s2s_dnri.inc"
 #include "host_dynamicvars.inc"
 #include "host_dyn_step.inc"
 #include "host_sim.inc"

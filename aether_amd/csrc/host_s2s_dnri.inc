@@ -1,0 +1,492 @@
+// Host side of the C ABI: the seq2seq dNRI baseline (nn/seq2seq/dnri.py) on the job-table engine of host_s2s_step.inc -- plan,
+// step (also as the decoder on given logits), device rollout and the encoder's per-time-step features, one set of entries for
+// both decoders: exactly one of dp (DNRI_Decoder) and mp (DNRI_MLP_Decoder) is given.  The model has no frames: no localizer,
+// edge-attribute, filter or globalise launch is made and no buffer is sized for one (s2s_dnri.h).  Included by aether_hip.hip
+// inside its extern "C" block after host_s2s_locs.inc; not a stand-alone source file.
+
+namespace {
+
+struct DnriSizes {
+    int D, he, hd, R, prior_layers, ph, K, skip_first, num_vars;
+    float tau;
+    int64_t Nn, E;
+};
+
+// Prepared weights (device).  ku >= 1: the MLP decoder with that many used edge types; -1: the recurrent decoder.
+struct DnriPlanLayout {
+    size_t bn, lb, lbp, o1p, total;
+    size_t i_w3[4], i_m2s, i_m2r, i_m3_0, i_ps, i_pr, i_m4e, i_ih, i_hh, i_prior[4];                  // fp16 x 2 images (0: none)
+    size_t i_a[4], i_s[4], i_msg2[4], i_hr, i_hi, i_hh2, i_out1, i_out2;
+    int ldo1;                                   // row stride of the padded out_fc1: S2S_RFG + hd
+    DnriPlanLayout(int he, int hd, int K, int R, int prior_layers, int ph, int ku) {
+        const bool rec = ku < 0;
+        ldo1 = S2S_RFG + hd;
+        size_t off = 0;
+        auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+        auto image = [&](int M, int Kk) { return S2SPlanLayout::splittable(M, Kk) ? take((size_t)M * Kk * 4) : (size_t)0; };
+        bn = take((size_t)8 * he * 4);                       // scale | shift of mlp1 .. mlp4
+        lb = take((size_t)4 * R * 4);
+        lbp = take((size_t)4 * R * 4);                       // gates interleaved by unit (the fused LSTM cell of the split GEMM)
+        o1p = take(rec ? 0 : (size_t)hd * ldo1 * 4);
+        for (int l = 0; l < 4; ++l) i_w3[l] = image(he, he);
+        i_m2s = image(he, he); i_m2r = image(he, he); i_m3_0 = image(he, he); i_ps = image(he, he); i_pr = image(he, he);
+        i_m4e = image(he, he); i_ih = image(4 * R, he); i_hh = image(4 * R, R);
+        for (int l = 0; l < 4; ++l) i_prior[l] = l + 1 < prior_layers ? image(ph, l == 0 ? R : ph) : 0;
+        for (int k = 0; k < 4; ++k) {
+            i_a[k] = rec && k < K ? image(hd, hd) : 0; i_s[k] = rec && k < K ? image(hd, hd) : 0;
+            i_msg2[k] = k < K ? image(hd, hd) : 0;
+        }
+        if (rec) { i_hr = image(hd, hd); i_hi = image(hd, hd); i_hh2 = image(hd, hd); i_out1 = image(hd, hd); }
+        else { i_hr = i_hi = i_hh2 = 0; i_out1 = image(hd, ldo1); }
+        i_out2 = image(hd, hd);
+        total = off;
+    }
+};
+
+// The workspace of a step / rollout: node rows of the prior, its edge rows, the sample, the decoder's rows and the ping-pong
+// state of the rollout.  Nothing of a frame: no rel_feat, Rinv, edge_attr, edge_pos, filter image / planes, present messages.
+struct DnriStepLayout {
+    size_t X1a, X1, PsPr, T2, X2, X2n, X3a, X3, T4, X4, G, Y1, Y2, logits, edges, lists, counts, A, S, Tm, M, agg, hr, hi, hh, o1,
+        o2, xa, da, db, ha, hb, ca, cb, total;
+    int ldagg;
+    DnriStepLayout(int D, int he, int hd, int R, int ph, int K, int64_t Nn, int64_t E) {
+        size_t off = 0;
+        auto take = [&](size_t floats) { size_t o = off; off = align_up(off + floats * 4, 256); return o; };
+        const size_t nn = (size_t)Nn, ee = (size_t)E, h = (size_t)he, g = (size_t)hd;
+        ldagg = S2S_RFG + hd;
+        X1a = take(nn * h); X1 = take(nn * h); PsPr = take(2 * nn * h); T2 = take(ee * h); X2 = take(ee * h); X2n = take(nn * h);
+        X3a = take(nn * h); X3 = take(nn * h); T4 = take(ee * h); X4 = take(ee * h); G = take(ee * 4 * (size_t)R);
+        Y1 = take(ee * (size_t)(ph > 0 ? ph : 1)); Y2 = take(ee * (size_t)(ph > 0 ? ph : 1));
+        logits = take(ee * K); edges = take(ee * K); lists = take(ee * K * 2); counts = take(64);
+        A = take((size_t)K * nn * g); S = take((size_t)K * nn * g); Tm = take((size_t)K * ee * g); M = take(ee * g);
+        agg = take(nn * (size_t)ldagg);                      // [inputs, 0 .. | agg] (MLP decoder); the recurrent one uses hd columns
+        hr = take(nn * g); hi = take(nn * g); hh = take(nn * g); o1 = take(nn * g); o2 = take(nn * g);
+        xa = take(nn * 2 * D); da = take(nn * g); db = take(nn * g);
+        ha = take(ee * (size_t)R); hb = take(ee * (size_t)R); ca = take(ee * (size_t)R); cb = take(ee * (size_t)R);
+        total = off;
+    }
+};
+
+struct DnriArgs : DnriSizes {
+    const AetherS2SDnriPriorParams* pp; const AetherS2SDnriDecoderParams* dp; const AetherS2SDnriMlpParams* mp;
+    const char* plan;
+    const int64_t *send, *recv, *order, *rowptr;
+    DnriPlanLayout P;
+    DnriStepLayout L;
+    const float* ext_logits = nullptr;          // the decoder on given logits: the prior is skipped
+    float* features_out = nullptr;              // the prior stops behind mlp4 and leaves its rows there
+};
+
+// Used edge types of the MLP decoder (-1: the recurrent decoder; 0: no decoder, both, or no used type)
+int s2s_dnri_ku(const void* dp, const void* mp, int K, int skip_first) {
+    if ((dp != nullptr) == (mp != nullptr)) return 0;
+    if (K - (skip_first ? 1 : 0) < 1) return 0;
+    return dp ? -1 : K - (skip_first ? 1 : 0);
+}
+
+bool s2s_dnri_sizes_ok(int D, int he, int hd, int R, int prior_layers, int ph, int K) {
+    return (D == 2 || D == 3) && he >= 128 && he % 128 == 0 && hd >= 32 && hd % 32 == 0 && R >= 16 && R % 16 == 0 && K >= 1 &&
+           K <= 4 && prior_layers >= 1 && prior_layers <= 4 && (prior_layers == 1 || (ph >= 16 && ph % 16 == 0));
+}
+
+// The checks every step / rollout / features entry makes before anything is queued, but the workspace's size
+int s2s_dnri_entry_check(const char* what, const AetherS2SDnriPriorParams* pp, const AetherS2SDnriDecoderParams* dp,
+                         const AetherS2SDnriMlpParams* mp, const void* plan, const DnriSizes& z, bool pointers, int burn_in_steps,
+                         int steps) {
+    if ((dp != nullptr) == (mp != nullptr)) return s2s_fail(AETHER_EINVAL, what, "exactly one of the two decoders must be given");
+    if (!pp || !plan) return s2s_fail(AETHER_EINVAL, what, "null pointer");
+    if (!s2s_dnri_sizes_ok(z.D, z.he, z.hd, z.R, z.prior_layers, z.ph, z.K))
+        return s2s_fail(AETHER_EINVAL, what, "num_dims 2 | 3, encoder_hidden % 128, decoder_hidden % 32, rnn / prior hidden % 16");
+    if (z.K - (z.skip_first ? 1 : 0) < 1) return s2s_fail(AETHER_EINVAL, what, "no used edge type");
+    if (z.num_vars < 2 || z.Nn <= 0 || z.E <= 0) return s2s_fail(AETHER_EINVAL, what, "bad sizes");
+    if (!pointers) return s2s_fail(AETHER_EINVAL, what, "null pointer");
+    if (burn_in_steps < 0 || steps < 0 || burn_in_steps + steps == 0) return s2s_fail(AETHER_EINVAL, what, "no steps");
+    if (!(z.tau > 0.0f)) return s2s_fail(AETHER_EINVAL, what, "tau must be positive");
+    return AETHER_OK;
+}
+
+// (after s2s_dnri_entry_check: the layouts take the sizes as valid)
+extern "C++" DnriArgs s2s_dnri_args(const AetherS2SDnriPriorParams* pp, const AetherS2SDnriDecoderParams* dp,
+                                    const AetherS2SDnriMlpParams* mp, const void* plan, const DnriSizes& z, const int64_t* send,
+                                    const int64_t* recv, const int64_t* order, const int64_t* rowptr) {
+    return DnriArgs{z, pp, dp, mp, (const char*)plan, send, recv, order, rowptr,
+                    DnriPlanLayout(z.he, z.hd, z.K, z.R, z.prior_layers, z.ph, s2s_dnri_ku(dp, mp, z.K, z.skip_first)),
+                    DnriStepLayout(z.D, z.he, z.hd, z.R, z.ph, z.K, z.Nn, z.E)};
+}
+
+// The prior step (dnri.py:403-424) and the hard Gumbel sample (:62-67) up to the per-type edge lists.  x_in [Nn][2D], h0 / c0
+// [E][R], uniform [E][K] -> h1, c1 and, when `edges` is not null, the sample [E][K] with its lists / counts in the workspace.
+// first_jobs(T): the recurrent decoder's first-layer products of its state, which share the launch of mlp1's second layer.
+extern "C++" template <class FirstJobs>
+int s2s_dnri_front(const DnriArgs& a, char* ws, const float* x_in, const float* h0, const float* c0, const float* uniform,
+                   float* h1, float* c1, float* edges, FirstJobs&& first_jobs, hipStream_t st) {
+    const int D = a.D, he = a.he, R = a.R, K = a.K, k0 = a.skip_first ? 1 : 0;
+    const int64_t Nn = a.Nn, E = a.E;
+    const DnriPlanLayout& P = a.P;
+    const DnriStepLayout& L = a.L;
+    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto pl = [&](size_t off) { return reinterpret_cast<const float*>(a.plan + off); };
+    auto im = [&](size_t off) { return off ? reinterpret_cast<const void*>(a.plan + off) : nullptr; };
+    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    const AetherS2SDnriPriorParams* p = a.pp;
+    int* counts = reinterpret_cast<int*>(ws + L.counts);
+    int64_t* lists = reinterpret_cast<int64_t*>(ws + L.lists);
+    S2SJobs T;
+    auto one = [&](S2SJob J) { T.n = 0; T.j[T.n++] = J; return s2s_launch_jobs(T, st); };
+    auto bns = [&](int l) { return pl(P.bn) + (size_t)2 * l * he; };
+    // the step's edge counters; for the MLP decoder (when the step decodes) the raw state where out_fc1 reads it and the node
+    // products of its first message layer
+    {
+        const AetherS2SDnriMlpParams* m = edges != nullptr ? a.mp : nullptr;
+        const int per = a.hd / 4 > S2S_RFG ? a.hd / 4 : S2S_RFG;
+        const float* none = nullptr;
+        k_s2s_dnri_node_prep<<<m ? blocks(Nn * per) : dim3(1), dim3(256), 0, st>>>(
+            x_in, 2 * D, m ? wp(L.agg) : nullptr, L.ldagg, counts, Nn, m ? m->msg_fc1_w[0] : none, m ? m->msg_fc1_w[1] : none,
+            m ? m->msg_fc1_w[2] : none, m ? m->msg_fc1_w[3] : none, m ? m->msg_fc1_b[0] : none, m ? m->msg_fc1_b[1] : none,
+            m ? m->msg_fc1_b[2] : none, m ? m->msg_fc1_b[3] : none, K, k0, wp(L.A), wp(L.S), a.hd, per);
+    }
+    if (a.ext_logits == nullptr) {
+        // mlp1 on the raw state (:405): its first Linear has 2D columns -- a narrow layer
+        { NarrowLayers N1{};
+          N1.W[0] = p->mlp_w0[0]; N1.b[0] = p->mlp_b0[0]; N1.Y[0] = wp(L.X1a); N1.n = 1;
+          k_s2s_narrow_layers<<<blocks(Nn * (he / 4)), dim3(256), 0, st>>>(N1, x_in, 2 * D, 2 * D, he, 4, Nn); }
+        { S2SJob J = s2s_job(4, p->mlp_w3[0], he, p->mlp_b3[0], wp(L.X1a), he, wp(L.X1), he, he, he, Nn);
+          J.post_scale = bns(0); J.post_shift = bns(0) + he; J.Wimg = im(P.i_w3[0]);
+          T.n = 0; T.j[T.n++] = J;
+          if (int rc = first_jobs(T)) return rc;
+          if (int rc = s2s_launch_jobs(T, st)) return rc; }
+        // node2edge, mlp2 (:406-407): the first Linear on [x_send | x_recv] as its two halves' node products
+        float* Ps = wp(L.PsPr);
+        float* Pr = Ps + (size_t)Nn * he;
+        T.n = 0;
+        T.j[T.n++] = s2s_job(0, p->mlp_w0[1], 2 * he, p->mlp_b0[1], wp(L.X1), he, Ps, he, he, he, Nn);
+        T.j[T.n - 1].Wimg = im(P.i_m2s);
+        T.j[T.n++] = s2s_job(0, p->mlp_w0[1] + he, 2 * he, nullptr, wp(L.X1), he, Pr, he, he, he, Nn);
+        T.j[T.n - 1].Wimg = im(P.i_m2r);
+        if (int rc = s2s_launch_jobs(T, st)) return rc;
+        k_s2s_dnri_pair_elu<<<blocks(E * (he / 4)), dim3(256), 0, st>>>(Ps, Pr, a.send, a.recv, wp(L.T2), he, E);
+        { S2SJob J = s2s_job(4, p->mlp_w3[1], he, p->mlp_b3[1], wp(L.T2), he, wp(L.X2), he, he, he, E);
+          J.post_scale = bns(1); J.post_shift = bns(1) + he; J.Wimg = im(P.i_w3[1]);
+          if (int rc = one(J)) return rc; }
+        // edge2node (:344-351, :409): in-edge sum / (num_vars - 1); mlp3 (:410)
+        k_s2s_segment_mean<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(wp(L.X2), a.order, a.rowptr, wp(L.X2n), he,
+                                                                    (float)(a.num_vars - 1), nullptr);
+        { S2SJob J = s2s_job(4, p->mlp_w0[2], he, p->mlp_b0[2], wp(L.X2n), he, wp(L.X3a), he, he, he, Nn); J.Wimg = im(P.i_m3_0);
+          if (int rc = one(J)) return rc; }
+        { S2SJob J = s2s_job(4, p->mlp_w3[2], he, p->mlp_b3[2], wp(L.X3a), he, wp(L.X3), he, he, he, Nn);
+          J.post_scale = bns(2); J.post_shift = bns(2) + he; J.Wimg = im(P.i_w3[2]);
+          if (int rc = one(J)) return rc; }
+        // mlp4 on [x_send | x_recv | skip] (:411-413): node halves in one launch, the edge third with the gathers in its epilogue
+        T.n = 0;
+        T.j[T.n++] = s2s_job(0, p->mlp_w0[3], 3 * he, p->mlp_b0[3], wp(L.X3), he, Ps, he, he, he, Nn);
+        T.j[T.n - 1].Wimg = im(P.i_ps);
+        T.j[T.n++] = s2s_job(0, p->mlp_w0[3] + he, 3 * he, nullptr, wp(L.X3), he, Pr, he, he, he, Nn);
+        T.j[T.n - 1].Wimg = im(P.i_pr);
+        if (int rc = s2s_launch_jobs(T, st)) return rc;
+        { S2SJob J = s2s_job(4, p->mlp_w0[3] + 2 * he, 3 * he, nullptr, wp(L.X2), he, wp(L.T4), he, he, he, E);
+          J.Wimg = im(P.i_m4e); J.g1 = Ps; J.i1 = a.send; J.g2 = Pr; J.i2 = a.recv;
+          if (int rc = one(J)) return rc; }
+        { S2SJob J = s2s_job(4, p->mlp_w3[3], he, p->mlp_b3[3], wp(L.T4), he, a.features_out ? a.features_out : wp(L.X4), he, he,
+                             he, E);
+          J.post_scale = bns(3); J.post_shift = bns(3) + he; J.Wimg = im(P.i_w3[3]);
+          if (int rc = one(J)) return rc; }
+        if (a.features_out) return AETHER_OK;
+        // one LSTM step per edge (:415-421), prior_fc_out (:422)
+        { S2SJob J = s2s_job(0, p->lstm_w_ih, he, pl(P.lb), wp(L.X4), he, wp(L.G), 4 * R, 4 * R, he, E);      // [W_ih | W_hh] . [x | h0]
+          J.W2 = p->lstm_w_hh; J.X2 = h0; J.K2 = R; J.ldw2 = R; J.ldx2 = R; J.Wimg = im(P.i_ih); J.W2img = im(P.i_hh);
+          T.n = 0; T.j[T.n++] = J;
+          if (s2s_jobs_take_split(T)) {                        // the cell update is the split GEMM's epilogue (S2SJob act 5)
+              T.j[0].act = 5; T.j[0].bias = pl(P.lbp); T.j[0].cell_c0 = c0; T.j[0].cell_h1 = h1; T.j[0].cell_c1 = c1;
+              if (int rc = s2s_launch_jobs(T, st)) return rc;
+          } else {
+              T.j[0].Wimg = nullptr; T.j[0].W2img = nullptr;   // (the interleaved images fit the fused form only)
+              if (int rc = s2s_launch_jobs(T, st)) return rc;
+              k_s2s_lstm_cell<<<blocks(E * R), dim3(256), 0, st>>>(wp(L.G), c0, h1, c1, R, E);
+          } }
+        const float* cur = h1;
+        int cur_k = R;
+        for (int l = 0; l < a.prior_layers; ++l) {
+            const bool last = l + 1 == a.prior_layers;
+            float* dst = last ? wp(L.logits) : wp(l % 2 == 0 ? L.Y1 : L.Y2);
+            const int M = last ? K : a.ph;
+            S2SJob J = s2s_job(last ? 0 : 4, p->prior_w[l], cur_k, p->prior_b[l], cur, cur_k, dst, M, M, cur_k, E);
+            if (!last) J.Wimg = im(P.i_prior[l]);
+            if (int rc = one(J)) return rc;
+            cur = dst;
+            cur_k = M;
+        }
+    } else {                           // (given logits: what rides in mlp1's launch goes alone)
+        T.n = 0;
+        if (int rc = first_jobs(T)) return rc;
+        if (int rc = s2s_launch_jobs(T, st)) return rc;
+    }
+    if (edges != nullptr)
+        k_s2s_gumbel_select<<<blocks(E), dim3(256), 0, st>>>(a.ext_logits ? a.ext_logits : wp(L.logits), uniform, a.tau, K, k0, edges,
+                                                           lists, counts, E);
+    return AETHER_OK;
+}
+
+// One step.  x_in [Nn][2D], dh_in [Nn][hd] (recurrent decoder), h0 / c0 [E][R], uniform [E][K] -> x_out, dh_out, h1, c1 (+
+// edges_out [E][K] when not null).  decode = false (MLP decoder only): the prior alone -- no sample, no decoder.
+int s2s_dnri_step_impl(const DnriArgs& a, char* ws, const float* x_in, const float* dh_in, const float* h0, const float* c0,
+                       const float* uniform, float* x_out, float* dh_out, float* h1, float* c1, float* edges_out, bool decode,
+                       hipStream_t st) {
+    const int D = a.D, hd = a.hd, K = a.K, k0 = a.skip_first ? 1 : 0;
+    const int64_t Nn = a.Nn, E = a.E;
+    const DnriPlanLayout& P = a.P;
+    const DnriStepLayout& L = a.L;
+    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto pl = [&](size_t off) { return reinterpret_cast<const float*>(a.plan + off); };
+    auto im = [&](size_t off) { return off ? reinterpret_cast<const void*>(a.plan + off) : nullptr; };
+    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    const AetherS2SDnriDecoderParams* q = a.dp;
+    const AetherS2SDnriMlpParams* m = a.mp;
+    int* counts = reinterpret_cast<int*>(ws + L.counts);
+    int64_t* lists = reinterpret_cast<int64_t*>(ws + L.lists);
+    float* edges = !decode ? nullptr : edges_out ? edges_out : wp(L.edges);
+    float* A = wp(L.A);
+    float* S = wp(L.S);
+    S2SJobs T;
+    // the receiver | sender halves of msg_fc1 on the hidden state (:489-493, :508) ride in mlp1's launch
+    auto first_jobs = [&](S2SJobs& F) {
+        if (q == nullptr) return (int)AETHER_OK;
+        for (int k = k0; k < K; ++k) {
+            if (F.n > S2S_MAX_JOBS - 2) { if (int rc = s2s_launch_jobs(F, st)) return rc; F.n = 0; }
+            F.j[F.n++] = s2s_job(0, q->msg_fc1_w[k], 2 * hd, q->msg_fc1_b[k], dh_in, hd, A + (size_t)k * Nn * hd, hd, hd, hd, Nn);
+            F.j[F.n - 1].Wimg = im(P.i_a[k]);
+            F.j[F.n++] = s2s_job(0, q->msg_fc1_w[k] + hd, 2 * hd, nullptr, dh_in, hd, S + (size_t)k * Nn * hd, hd, hd, hd, Nn);
+            F.j[F.n - 1].Wimg = im(P.i_s[k]);
+        }
+        return (int)AETHER_OK;
+    };
+    if (int rc = s2s_dnri_front(a, ws, x_in, h0, c0, uniform, h1, c1, edges, first_jobs, st)) return rc;
+    if (!decode) return AETHER_OK;
+    // ---- first message layer of the sampled type, per edge, from its node products (rows of unsampled edges of M cleared)
+    if (q)
+        k_s2s_dnri_pair<false><<<blocks(E * (hd / 4)), dim3(256), 0, st>>>(A, S, Nn, a.send, a.recv, edges, K, k0, wp(L.Tm), wp(L.M), hd, E);
+    else
+        k_s2s_dnri_pair<true><<<blocks(E * (hd / 4)), dim3(256), 0, st>>>(A, S, Nn, a.send, a.recv, edges, K, k0, wp(L.Tm), wp(L.M), hd, E);
+    // ---- second layer of every used type in one launch: rows through the type's list, scaled by the sample's weight
+    {
+        T.n = 0;
+        for (int k = k0; k < K; ++k) {
+            S2SJob J = s2s_job(q ? 3 : 2, q ? q->msg_fc2_w[k] : m->msg_fc2_w[k], hd, q ? q->msg_fc2_b[k] : m->msg_fc2_b[k],
+                               wp(L.Tm) + (size_t)k * E * hd, hd, wp(L.M), hd, hd, hd, E);
+            J.xidx = lists + (size_t)k * E; J.yidx = lists + (size_t)k * E; J.n_dev = counts + k;
+            J.scale = edges + k; J.sstride = K; J.Wimg = im(P.i_msg2[k]);
+            T.j[T.n++] = J;
+        }
+        if (int rc = s2s_launch_jobs(T, st)) return rc;
+    }
+    const float* o_in;
+    if (q) {
+        // / norm, sum per receiver / (N - 1) (:512-516); GRU gate on the raw inputs (:519-525)
+        k_s2s_dnri_aggregate<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(wp(L.M), a.order, a.rowptr, wp(L.agg), hd, hd, (float)(K - k0),
+                                                                      (float)(a.num_vars - 1));
+        T.n = 0;
+        T.j[T.n++] = s2s_job(0, q->hidden_r_w, hd, nullptr, wp(L.agg), hd, wp(L.hr), hd, hd, hd, Nn); T.j[T.n - 1].Wimg = im(P.i_hr);
+        T.j[T.n++] = s2s_job(0, q->hidden_i_w, hd, nullptr, wp(L.agg), hd, wp(L.hi), hd, hd, hd, Nn); T.j[T.n - 1].Wimg = im(P.i_hi);
+        T.j[T.n++] = s2s_job(0, q->hidden_h_w, hd, nullptr, wp(L.agg), hd, wp(L.hh), hd, hd, hd, Nn); T.j[T.n - 1].Wimg = im(P.i_hh2);
+        if (int rc = s2s_launch_jobs(T, st)) return rc;
+        k_s2s_dnri_gate<<<blocks(Nn * (hd / 4)), dim3(256), 0, st>>>(x_in, 2 * D, q->input_r_w, q->input_r_b, q->input_i_w,
+                                                                    q->input_i_b, q->input_n_w, q->input_n_b, wp(L.hr), wp(L.hi),
+                                                                    wp(L.hh), dh_in, dh_out, hd, Nn);
+        o_in = dh_out;
+    } else {
+        // plain sum per receiver behind the staged inputs (:612-616): out_fc1 reads [inputs, 0 .. | agg]
+        k_s2s_dnri_aggregate<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(wp(L.M), a.order, a.rowptr, wp(L.agg) + S2S_RFG, L.ldagg, hd,
+                                                                      1.0f, 1.0f);
+        o_in = nullptr;
+    }
+    // ---- output MLP and residual (:528-532, :619-624)
+    auto one = [&](S2SJob J, size_t image) { T.n = 1; T.j[0] = J; T.j[0].Wimg = im(image); return s2s_launch_jobs(T, st); };
+    if (q) { if (int rc = one(s2s_job(2, q->out1_w, hd, q->out1_b, o_in, hd, wp(L.o1), hd, hd, hd, Nn), P.i_out1)) return rc; }
+    else if (int rc = one(s2s_job(2, pl(P.o1p), P.ldo1, m->out1_b, wp(L.agg), L.ldagg, wp(L.o1), hd, hd, P.ldo1, Nn), P.i_out1)) return rc;
+    if (int rc = one(s2s_job(2, q ? q->out2_w : m->out2_w, hd, q ? q->out2_b : m->out2_b, wp(L.o1), hd, wp(L.o2), hd, hd, hd, Nn),
+                     P.i_out2)) return rc;
+    const float* w3 = q ? q->out3_w : m->out3_w;
+    const float* b3 = q ? q->out3_b : m->out3_b;
+    dispatch_dim(D, [&](auto DD) {
+        k_s2s_dnri_out<decltype(DD)::value><<<dim3((unsigned)((Nn + 3) / 4)), dim3(256), 0, st>>>(wp(L.o2), w3, b3, hd, x_in, x_out, Nn);
+    });
+    return AETHER_OK;
+}
+
+DnriSizes s2s_dnri_sizes(int D, int he, int hd, int R, int prior_layers, int ph, int K, int skip_first, int num_vars, float tau,
+                         int64_t Nn, int64_t E) {
+    return DnriSizes{D, he, hd, R, prior_layers, ph, K, skip_first, num_vars, tau, Nn, E};
+}
+}  // namespace
+
+/* see include/aether_hip.h */
+size_t aether_s2s_dnri_plan_bytes(const AetherS2SDnriDecoderParams* dp, const AetherS2SDnriMlpParams* mp, int num_dims,
+                                  int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden,
+                                  int num_edge_types, int skip_first) {
+    const int ku = s2s_dnri_ku(dp, mp, num_edge_types, skip_first);
+    if (ku == 0 || !s2s_dnri_sizes_ok(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden, num_edge_types))
+        return 0;
+    return DnriPlanLayout(encoder_hidden, decoder_hidden, num_edge_types, rnn_hidden, prior_layers, prior_hidden, ku).total;
+}
+
+int aether_s2s_dnri_plan_build(const AetherS2SDnriPriorParams* pp, const AetherS2SDnriDecoderParams* dp,
+                               const AetherS2SDnriMlpParams* mp, int num_dims, int encoder_hidden, int decoder_hidden,
+                               int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, int skip_first, void* plan,
+                               size_t plan_bytes, void* stream) {
+    const char* what = "s2s_dnri_plan_build";
+    if (!pp || !plan) return s2s_fail(AETHER_EINVAL, what, "null pointer");
+    if ((dp != nullptr) == (mp != nullptr)) return s2s_fail(AETHER_EINVAL, what, "exactly one of the two decoders must be given");
+    const int D = num_dims, he = encoder_hidden, hd = decoder_hidden, K = num_edge_types, R = rnn_hidden;
+    const size_t need = aether_s2s_dnri_plan_bytes(dp, mp, D, he, hd, R, prior_layers, prior_hidden, K, skip_first);
+    if (int rc = s2s_plan_buffer_check(what, need, plan, plan_bytes)) return rc;
+    const DnriPlanLayout P(he, hd, K, R, prior_layers, prior_hidden, s2s_dnri_ku(dp, mp, K, skip_first));
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)plan;
+    auto fl = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
+    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    for (int l = 0; l < 4; ++l) {
+        k_s2s_bn_affine<<<blocks(he), dim3(256), 0, st>>>(pp->mlp_bn_w[l], pp->mlp_bn_b[l], pp->mlp_bn_mean[l], pp->mlp_bn_var[l],
+                                                         fl(P.bn) + (size_t)2 * l * he, fl(P.bn) + (size_t)(2 * l + 1) * he, he);
+        s2s_image(base, st, P.i_w3[l], pp->mlp_w3[l], he, he, he);
+    }
+    k_s2s_add_vec<<<blocks(4 * R), dim3(256), 0, st>>>(pp->lstm_b_ih, pp->lstm_b_hh, fl(P.lb), 4 * R);
+    k_s2s_lstm_bias_interleave<<<blocks(4 * R), dim3(256), 0, st>>>(pp->lstm_b_ih, pp->lstm_b_hh, fl(P.lbp), R);
+    s2s_image(base, st, P.i_m2s, pp->mlp_w0[1], he, he, 2 * he);
+    s2s_image(base, st, P.i_m2r, pp->mlp_w0[1] + he, he, he, 2 * he);
+    s2s_image(base, st, P.i_m3_0, pp->mlp_w0[2], he, he, he);
+    s2s_image(base, st, P.i_ps, pp->mlp_w0[3], he, he, 3 * he);
+    s2s_image(base, st, P.i_pr, pp->mlp_w0[3] + he, he, he, 3 * he);
+    s2s_image(base, st, P.i_m4e, pp->mlp_w0[3] + 2 * he, he, he, 3 * he);
+    s2s_image(base, st, P.i_ih, pp->lstm_w_ih, 4 * R, he, he, R);                  // gates interleaved by unit (S2SJob act 5)
+    s2s_image(base, st, P.i_hh, pp->lstm_w_hh, 4 * R, R, R, R);
+    for (int l = 0; l + 1 < prior_layers; ++l)
+        s2s_image(base, st, P.i_prior[l], pp->prior_w[l], prior_hidden, l == 0 ? R : prior_hidden, l == 0 ? R : prior_hidden);
+    if (dp) {
+        for (int k = 0; k < K; ++k) {
+            s2s_image(base, st, P.i_a[k], dp->msg_fc1_w[k], hd, hd, 2 * hd);
+            s2s_image(base, st, P.i_s[k], dp->msg_fc1_w[k] + hd, hd, hd, 2 * hd);
+            s2s_image(base, st, P.i_msg2[k], dp->msg_fc2_w[k], hd, hd, hd);
+        }
+        s2s_image(base, st, P.i_hr, dp->hidden_r_w, hd, hd, hd);
+        s2s_image(base, st, P.i_hi, dp->hidden_i_w, hd, hd, hd);
+        s2s_image(base, st, P.i_hh2, dp->hidden_h_w, hd, hd, hd);
+        s2s_image(base, st, P.i_out1, dp->out1_w, hd, hd, hd);
+        s2s_image(base, st, P.i_out2, dp->out2_w, hd, hd, hd);
+    } else {
+        for (int k = skip_first ? 1 : 0; k < K; ++k) s2s_image(base, st, P.i_msg2[k], mp->msg_fc2_w[k], hd, hd, hd);
+        k_s2s_dnri_pad_front<<<blocks((int64_t)hd * P.ldo1), dim3(256), 0, st>>>(mp->out1_w, 2 * D, S2S_RFG, hd, fl(P.o1p), hd);
+        s2s_image(base, st, P.i_out1, fl(P.o1p), hd, P.ldo1, P.ldo1);
+        s2s_image(base, st, P.i_out2, mp->out2_w, hd, hd, hd);
+    }
+    HIP_OK(hipGetLastError());
+    return AETHER_OK;
+}
+
+size_t aether_s2s_dnri_workspace_bytes(int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_hidden,
+                                       int num_edge_types, int64_t n_nodes, int64_t n_edges) {
+    if ((num_dims != 2 && num_dims != 3) || encoder_hidden <= 0 || decoder_hidden <= 0 || rnn_hidden <= 0 || prior_hidden < 0 ||
+        num_edge_types < 1 || num_edge_types > 4 || n_nodes <= 0 || n_edges <= 0)
+        return 0;
+    return DnriStepLayout(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_hidden, num_edge_types, n_nodes, n_edges).total;
+}
+
+int aether_s2s_dnri_step(const AetherS2SDnriPriorParams* pp, const AetherS2SDnriDecoderParams* dp, const AetherS2SDnriMlpParams* mp,
+                         const void* plan, int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
+                         int prior_hidden, int num_edge_types, int skip_first, int polar, int num_vars, float tau, int64_t n_nodes,
+                         int64_t n_edges, const int64_t* send, const int64_t* recv, const int64_t* order, const int64_t* rowptr,
+                         const float* inputs, const float* ext_logits, const float* decoder_hidden_in, const float* h0,
+                         const float* c0, const float* uniform, void* workspace, size_t workspace_bytes, float* outputs,
+                         float* decoder_hidden_out, float* h1, float* c1, float* edges_out, float* logits_out, void* stream) {
+    (void)polar;
+    const char* what = "s2s_dnri_step";
+    const DnriSizes z = s2s_dnri_sizes(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden,
+                                       num_edge_types, skip_first, num_vars, tau, n_nodes, n_edges);
+    if (int rc = s2s_dnri_entry_check(what, pp, dp, mp, plan, z,
+                                      send && recv && order && rowptr && inputs && uniform && workspace && outputs &&
+                                          (ext_logits || (h0 && c0 && h1 && c1)) && (mp || (decoder_hidden_in && decoder_hidden_out)),
+                                      0, 1)) return rc;
+    if (logits_out && ext_logits) return s2s_fail(AETHER_EINVAL, what, "logits_out is the prior's logits: not with ext_logits");
+    DnriArgs a = s2s_dnri_args(pp, dp, mp, plan, z, send, recv, order, rowptr);
+    if (workspace_bytes < a.L.total) return s2s_fail(AETHER_ESPACE, what, "workspace too small");
+    a.ext_logits = ext_logits;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = s2s_dnri_step_impl(a, (char*)workspace, inputs, mp ? nullptr : decoder_hidden_in, h0, c0, uniform, outputs,
+                                    mp ? nullptr : decoder_hidden_out, h1, c1, edges_out, true, st)) return rc;
+    if (logits_out)
+        HIP_OK(hipMemcpyAsync(logits_out, (const char*)workspace + a.L.logits, (size_t)n_edges * num_edge_types * sizeof(float),
+                              hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipGetLastError());
+    return AETHER_OK;
+}
+
+int aether_s2s_dnri_rollout(const AetherS2SDnriPriorParams* pp, const AetherS2SDnriDecoderParams* dp,
+                            const AetherS2SDnriMlpParams* mp, const void* plan, int num_dims, int encoder_hidden, int decoder_hidden,
+                            int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, int skip_first, int polar,
+                            int num_vars, float tau, int64_t n_nodes, int64_t n_edges, const int64_t* send, const int64_t* recv,
+                            const int64_t* order, const int64_t* rowptr, int burn_in_steps, const float* burn_in, int steps,
+                            const float* inputs, float* decoder_state, float* h, float* c, const float* uniform, void* workspace,
+                            size_t workspace_bytes, float* predictions, float* edges_out, void* stream) {
+    (void)polar;
+    const char* what = "s2s_dnri_rollout";
+    const DnriSizes z = s2s_dnri_sizes(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden,
+                                       num_edge_types, skip_first, num_vars, tau, n_nodes, n_edges);
+    if (int rc = s2s_dnri_entry_check(what, pp, dp, mp, plan, z,
+                                      send && recv && order && rowptr && inputs && h && c && uniform && workspace &&
+                                          (mp || decoder_state) && (steps <= 0 || predictions) && (burn_in_steps <= 0 || burn_in),
+                                      burn_in_steps, steps)) return rc;
+    const DnriArgs a = s2s_dnri_args(pp, dp, mp, plan, z, send, recv, order, rowptr);
+    if (workspace_bytes < a.L.total) return s2s_fail(AETHER_ESPACE, what, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const DnriStepLayout& L = a.L;
+    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    const size_t dbytes = (size_t)a.Nn * a.hd * 4, rbytes = (size_t)a.E * a.R * 4;
+    const size_t ustep = (size_t)a.E * a.K, xstep = (size_t)a.Nn * 2 * a.D;
+    // state ping-pong inside the workspace (the decoder's only when it has a state)
+    float *dcur = dp ? wp(L.da) : nullptr, *dnext = dp ? wp(L.db) : nullptr;
+    float *hcur = wp(L.ha), *hnext = wp(L.hb), *ccur = wp(L.ca), *cnext = wp(L.cb);
+    if (dcur) HIP_OK(hipMemcpyAsync(dcur, decoder_state, dbytes, hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipMemcpyAsync(hcur, h, rbytes, hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipMemcpyAsync(ccur, c, rbytes, hipMemcpyDeviceToDevice, st));
+    const int total = burn_in_steps + steps;
+    const float* xcur = burn_in_steps > 0 ? burn_in : inputs;
+    for (int t = 0; t < total; ++t) {
+        // A burn-in step's prediction is discarded.  The recurrent decoder still needs the step for its state: the whole step,
+        // its output into L.xa.  The MLP decoder has no state: the prior only -- no sample, no decoder, no output.
+        const bool teacher = t < burn_in_steps, decode = !teacher || dp != nullptr;
+        float* xout = !teacher ? predictions + (size_t)(t - burn_in_steps) * xstep : decode ? wp(L.xa) : nullptr;
+        float* eout = (!teacher && edges_out) ? edges_out + (size_t)(t - burn_in_steps) * ustep : nullptr;
+        if (int rc = s2s_dnri_step_impl(a, ws, xcur, dcur, hcur, ccur, uniform + (size_t)t * ustep, xout, dnext, hnext, cnext, eout,
+                                        decode, st)) return rc;
+        std::swap(dcur, dnext); std::swap(hcur, hnext); std::swap(ccur, cnext);
+        if (t + 1 < burn_in_steps) xcur = burn_in + (size_t)(t + 1) * xstep;
+        else if (t + 1 == burn_in_steps) xcur = inputs;
+        else xcur = xout;
+    }
+    if (dcur) HIP_OK(hipMemcpyAsync(decoder_state, dcur, dbytes, hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipMemcpyAsync(h, hcur, rbytes, hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipMemcpyAsync(c, ccur, rbytes, hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipGetLastError());
+    return AETHER_OK;
+}
+
+int aether_s2s_dnri_encoder_features(const AetherS2SDnriPriorParams* pp, const AetherS2SDnriDecoderParams* dp,
+                                     const AetherS2SDnriMlpParams* mp, const void* plan, int num_dims, int encoder_hidden,
+                                     int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types,
+                                     int skip_first, int polar, int num_vars, int64_t n_nodes, int64_t n_edges, const int64_t* send,
+                                     const int64_t* recv, const int64_t* order, const int64_t* rowptr, const float* inputs,
+                                     void* workspace, size_t workspace_bytes, float* features, void* stream) {
+    (void)polar;
+    const char* what = "s2s_dnri_encoder_features";
+    const DnriSizes z = s2s_dnri_sizes(num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden,
+                                       num_edge_types, skip_first, num_vars, 1.0f, n_nodes, n_edges);
+    if (int rc = s2s_dnri_entry_check(what, pp, dp, mp, plan, z,
+                                      send && recv && order && rowptr && inputs && workspace && features, 0, 1)) return rc;
+    DnriArgs a = s2s_dnri_args(pp, dp, mp, plan, z, send, recv, order, rowptr);
+    if (workspace_bytes < a.L.total) return s2s_fail(AETHER_ESPACE, what, "workspace too small");
+    a.features_out = features;
+    auto no_jobs = [](S2SJobs&) { return (int)AETHER_OK; };
+    if (int rc = s2s_dnri_front(a, (char*)workspace, inputs, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, no_jobs,
+                                (hipStream_t)stream)) return rc;
+    HIP_OK(hipGetLastError());
+    return AETHER_OK;
+}

@@ -910,6 +910,102 @@ int aether_s2s_locs_encoder_features(const AetherS2SPriorParams* prior, const Ae
                                      void* workspace, size_t workspace_bytes, float* features, void* stream);
 
 /*
+ * The seq2seq dNRI baseline, DNRI of nn/seq2seq/dnri.py (--model_type nn.seq2seq.dnri.DNRI of the electrostatic and
+ * gravitational runners).  The model has no local frames: no localizer, no edge attributes, no hyper-network filter and no
+ * rotation of the prediction; nothing of them is in the plan or the workspace and none of their kernels is launched.
+ *   DNRI_Encoder.single_step_forward (dnri.py:403-424): mlp1 on the raw state [n_nodes][2D], node2edge ([x_send | x_recv],
+ *     :334-342), mlp2, edge2node (in-edge sum / (num_vars - 1), :344-351), mlp3, node2edge | skip, mlp4, one LSTM step per edge,
+ *     prior_fc_out.  Each mlp is a RefNRIMLP (nn/utils/model_utils.py): Linear, ELU, Linear, ELU, BatchNorm1d on its running
+ *     statistics.
+ *   DNRI_Decoder.forward (:479-534): messages tanh(msg_fc2[k](tanh(msg_fc1[k]([h_recv | h_send])))) * edges[.., k] / norm (norm:
+ *     the number of used edge types), summed per receiver / (num_vars - 1); the GRU gate, whose input_r / _i / _n act on the raw
+ *     inputs and which has no present-message terms; out_fc1 / 2 (ReLU), out_fc3; outputs = inputs + prediction.
+ *   DNRI_MLP_Decoder.forward (decoder_type 'ref_mlp', :574-624): messages relu(msg_fc2[k](relu(msg_fc1[k]([x_recv | x_send])))) *
+ *     edges[.., k] on the raw inputs, summed per receiver with no division; out_fc1 on [inputs | agg]; no state.
+ * Exactly one of decoder / mlp is given (the other NULL).  The entries mirror aether_s2s_locs_* argument for argument; `polar`
+ * is accepted for that reason and ignored (the model has no position representation).
+ *   aether_s2s_dnri_plan_bytes / _plan_build : prepared weights (device, 256-byte aligned): BatchNorm affines, summed LSTM
+ *                                              biases, the padded out_fc1 of the MLP decoder, fp16 x 2 images of the layers the
+ *                                              split GEMM takes; rebuild after the weights change
+ *   aether_s2s_dnri_workspace_bytes          : of a step / rollout / encoder_features call (smaller than LoCS's at the same
+ *                                              sizes: no frame, edge-attribute, filter or present-message buffer)
+ *   aether_s2s_dnri_step                     : DNRI_Encoder.single_step_forward, the hard Gumbel sample and the decoder
+ *                                              (DNRI.single_step_forward :62-69) as one call.  With ext_logits [n_edges][K] !=
+ *                                              NULL it is the decoder on given logits, as calculate_loss :87-91 calls it: the
+ *                                              prior is skipped, h0 / c0 / h1 / c1 may be NULL.  decoder_hidden_in / _out are
+ *                                              NULL with the MLP decoder; logits_out (or NULL) [n_edges][K]: the prior's logits
+ *                                              the sample was taken from (not with ext_logits: AETHER_EINVAL)
+ *   aether_s2s_dnri_rollout                  : the loops of predict_future (:111-136): burn_in_steps teacher-forced steps on
+ *                                              burn_in [T0][n_nodes][2D] (the prior path is causal, so the step gives what the
+ *                                              full-sequence encoder gives there), then `steps` steps from inputs; decoder_state
+ *                                              (NULL with the MLP decoder, whose burn-in steps run the prior only), h, c are
+ *                                              read first and written last; uniform [T0 + steps][n_edges][K]
+ *   aether_s2s_dnri_encoder_features         : the per-time-step half of DNRI_Encoder.forward (:376-384, mlp1 .. mlp4) on a
+ *                                              flattened batch of (time, graph) items -> features [n_edges][he], the input of
+ *                                              aether_s2s_lstm_step / aether_s2s_mlp_head
+ * Sizes: num_dims 2 or 3, encoder_hidden a multiple of 128, decoder_hidden of 32, rnn_hidden of 16, 1..4 prior layers
+ * (prior_hidden a multiple of 16 when there are several), 1..4 edge types of which at least one is used (AETHER_EINVAL
+ * otherwise; the size calls return 0).  AETHER_EINVAL: both or neither decoder, a NULL pointer; AETHER_ESPACE: plan or
+ * workspace too small.  Everything is checked before anything is queued.  Stream-ordered, no host synchronisation
+ * (capturable); nothing outside the workspace and the outputs is written.
+ */
+typedef struct AetherS2SDnriPriorParams {
+    const float* mlp_w0[4]; const float* mlp_b0[4];      /* mlp1 .. mlp4, first Linear: [he][2D], [he][2he], [he][he], [he][3he] */
+    const float* mlp_w3[4]; const float* mlp_b3[4];      /* second Linear: [he][he], [he] */
+    const float* mlp_bn_w[4]; const float* mlp_bn_b[4]; const float* mlp_bn_mean[4]; const float* mlp_bn_var[4];   /* [he] */
+    const float* lstm_w_ih; const float* lstm_w_hh; const float* lstm_b_ih; const float* lstm_b_hh; /* forward_rnn: [4R][he], [4R][R] */
+    const float* prior_w[4]; const float* prior_b[4];    /* prior_fc_out */
+} AetherS2SDnriPriorParams;
+typedef struct AetherS2SDnriDecoderParams {
+    const float* msg_fc1_w[4]; const float* msg_fc1_b[4];    /* [hd][2hd] (receiver | sender halves), [hd] */
+    const float* msg_fc2_w[4]; const float* msg_fc2_b[4];    /* [hd][hd], [hd] */
+    const float* hidden_r_w; const float* hidden_i_w; const float* hidden_h_w;      /* [hd][hd], no bias */
+    const float* input_r_w; const float* input_r_b;
+    const float* input_i_w; const float* input_i_b;
+    const float* input_n_w; const float* input_n_b;          /* [hd][2D], [hd] */
+    const float* out1_w; const float* out1_b; const float* out2_w; const float* out2_b;   /* out_fc1 / 2: [hd][hd], [hd] */
+    const float* out3_w; const float* out3_b;                /* out_fc3: [2D][hd], [2D] */
+} AetherS2SDnriDecoderParams;
+typedef struct AetherS2SDnriMlpParams {
+    const float* msg_fc1_w[4]; const float* msg_fc1_b[4];    /* [hd][4D] (receiver | sender halves), [hd] */
+    const float* msg_fc2_w[4]; const float* msg_fc2_b[4];    /* [hd][hd], [hd] */
+    const float* out1_w; const float* out1_b;                /* out_fc1: [hd][2D + hd] on [inputs | agg], [hd] */
+    const float* out2_w; const float* out2_b;                /* out_fc2: [hd][hd], [hd] */
+    const float* out3_w; const float* out3_b;                /* out_fc3: [2D][hd], [2D] */
+} AetherS2SDnriMlpParams;
+size_t aether_s2s_dnri_plan_bytes(const AetherS2SDnriDecoderParams* decoder, const AetherS2SDnriMlpParams* mlp, int num_dims,
+                                  int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden,
+                                  int num_edge_types, int skip_first);
+int aether_s2s_dnri_plan_build(const AetherS2SDnriPriorParams* prior, const AetherS2SDnriDecoderParams* decoder,
+                               const AetherS2SDnriMlpParams* mlp, int num_dims, int encoder_hidden, int decoder_hidden,
+                               int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, int skip_first, void* plan,
+                               size_t plan_bytes, void* stream);
+size_t aether_s2s_dnri_workspace_bytes(int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_hidden,
+                                       int num_edge_types, int64_t n_nodes, int64_t n_edges);
+int aether_s2s_dnri_step(const AetherS2SDnriPriorParams* prior, const AetherS2SDnriDecoderParams* decoder,
+                         const AetherS2SDnriMlpParams* mlp, const void* plan, int num_dims, int encoder_hidden,
+                         int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, int skip_first,
+                         int polar, int num_vars, float tau, int64_t n_nodes, int64_t n_edges, const int64_t* send,
+                         const int64_t* recv, const int64_t* order, const int64_t* rowptr, const float* inputs,
+                         const float* ext_logits, const float* decoder_hidden_in, const float* h0, const float* c0,
+                         const float* uniform, void* workspace, size_t workspace_bytes, float* outputs, float* decoder_hidden_out,
+                         float* h1, float* c1, float* edges_out, float* logits_out, void* stream);
+int aether_s2s_dnri_rollout(const AetherS2SDnriPriorParams* prior, const AetherS2SDnriDecoderParams* decoder,
+                            const AetherS2SDnriMlpParams* mlp, const void* plan, int num_dims, int encoder_hidden,
+                            int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types,
+                            int skip_first, int polar, int num_vars, float tau, int64_t n_nodes, int64_t n_edges,
+                            const int64_t* send, const int64_t* recv, const int64_t* order, const int64_t* rowptr,
+                            int burn_in_steps, const float* burn_in, int steps, const float* inputs, float* decoder_state,
+                            float* h, float* c, const float* uniform, void* workspace, size_t workspace_bytes, float* predictions,
+                            float* edges_out, void* stream);
+int aether_s2s_dnri_encoder_features(const AetherS2SDnriPriorParams* prior, const AetherS2SDnriDecoderParams* decoder,
+                                     const AetherS2SDnriMlpParams* mlp, const void* plan, int num_dims, int encoder_hidden,
+                                     int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types,
+                                     int skip_first, int polar, int num_vars, int64_t n_nodes, int64_t n_edges, const int64_t* send,
+                                     const int64_t* recv, const int64_t* order, const int64_t* rowptr, const float* inputs,
+                                     void* workspace, size_t workspace_bytes, float* features, void* stream);
+
+/*
  * k-nearest-neighbour edge builder for variable-N scenes: replaces Encoder.knn_edges
  * (nn/dynamicvars/aether_dynamicvars.py:559-586; the same method in the other *_dynamicvars.py) and the send /
  * recv half of get_knn_graph_info (experiments/ind/single_ind_data.py:186-217).
