@@ -415,8 +415,9 @@ BwdWT transposed_weights(const AetherParams& P, float* base, TransposeBatch& TB)
 
 // Everything derived from the weights alone, in ONE launch in front of the step: the split images of the edge-MLP
 // matrices the fused forward copies into LDS (blocks 0-7), the node phase's (blocks 8-31), the per-layer constants
-// blocks (biases, out_w6: the last image block; fused_layout.h CB_*) and, when the intermediates are kept for a backward, the
-// transposed copies its kernels read (the remaining blocks).
+// blocks (biases, out_w6: block 32; fused_layout.h CB_*), the field image of the 12-wave kernels' field wave (the last 25
+// image blocks, one per chunk; fused_layout.h FI_*) and, when the intermediates are kept for a backward, the transposed copies its kernels read
+// (the remaining blocks).
 __global__ void __launch_bounds__(512)
 k_prepare_weights(AetherParams P, int f1, int nd, float* __restrict__ wimg, TransposeBatch TB, int split_blocks) {
     if ((int)blockIdx.x < split_blocks) {
@@ -1680,6 +1681,11 @@ int aether_debug_split(const float* x, int n_tiles, uint16_t* hi, uint16_t* lo, 
     k_debug_split<<<dim3(1), dim3(64 * DEBUG_SPLIT_WAVES), 0, nullptr>>>(x, n_tiles, hi, lo, on, scale, y);
     HIP_OK(hipGetLastError());
     return AETHER_OK;
+}
+
+int aether_debug_fused_packed_edge(int wave, int lane) {
+    if (wave < 0 || wave >= FUSED_PACK_WAVES || lane < 0 || lane >= FUSED_PACK_LANES) return -1;
+    return fused_packed_edge(wave, lane);
 }
 
 #include "host_wide.inc"

@@ -75,10 +75,21 @@ constexpr int FUSED_STAMPS = 512;
             dbg.stamps[blockIdx.x * FUSED_STAMPS + 352 + wave * 4 + (r_)] =                       \
                 (float)(__builtin_amdgcn_s_memtime() - c_entry);                                 \
     } while (0)
+// the field wave's pieces (wave 0, shader-clock cycles since entry), behind the slots above: 0 first vector load issued,
+// 1 the block's vmcnt(0) passed, 2 last MFMA of the field net retired, 3 frame stored, 4 x0 stored.  `dep_`: a vector
+// register the stamp waits for (the wave issues in order: the move stalls until the value is there).
+#define FUSED_PSTAMP(k_, dep_)                                                                    \
+    do {                                                                                         \
+        asm volatile("v_mov_b32 %0, %0" : "+v"(dep_));                                           \
+        if (wave == 0 && lane == 0 && blockIdx.x < 4096)                                         \
+            dbg.stamps[blockIdx.x * FUSED_STAMPS + 400 + (k_)] =                                  \
+                (float)(__builtin_amdgcn_s_memtime() - c_entry);                                 \
+    } while (0)
 #else
 #define FUSED_STAMP(id)
 #define FUSED_WSTAMP(layer_, r_, k_)
 #define FUSED_WSTAMP_ROWS(layer_, r_)
+#define FUSED_PSTAMP(k_, dep_)
 #endif
 
 template <int D, int NW, int ROUNDS, bool KEEP, bool GRAN = false>
@@ -181,8 +192,15 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     // k_graph_lorder), and every wave asks for its records and attributes during P1 -- only two of the eight waves work
     // there (<= 32 visible nodes), behind their own inputs.
     constexpr int FR = ROUNDS < 2 ? ROUNDS : 2;              // rounds of the first feature pass (lane >> 4)
-    const int f_local = 16 * (NW * (lane >> 4) + wave) + (lane & 15);
-    const bool f_have = lane < 16 * FR && f_local < m;       // this lane builds the features of edge f_local
+    // NW == 12 (PACKED): the features are built by one wave per SIMD -- waves 0-3, lanes 0-47, edge 48 wave + lane, that is
+    // row lane & 15 of tile 3 wave + (lane >> 4) -- and go into the OWNING wave's rows of L::FEAT (tile t belongs to wave t).
+    // With every wave building its own 16 edges on a quarter of its lanes, the three waves of a SIMD ran the same
+    // ~200-instruction chain one after the other: a wave64 instruction holds the SIMD's vector issue for four cycles
+    // whatever its exec mask.  t_e, sl, rl and nr_rec stay per owner.
+    constexpr bool PACKED = NW == 12;
+    constexpr bool FIMG = NW == 12;      // the field wave's weight operands come as the prepared field image (P1)
+    const int f_local = PACKED ? fused_packed_edge(wave, lane) : 16 * (NW * (lane >> 4) + wave) + (lane & 15);
+    const bool f_have = (PACKED ? wave < FUSED_PACK_WAVES && lane < FUSED_PACK_LANES : lane < 16 * FR) && f_local < m;   // this lane builds the features of edge f_local
     int4 f_e = make_int4(0, 0, 0, 0);                        // {sorted position, sender, receiver, original edge}
     f32x2 f_ea = {0.0f, 0.0f};                               // its two edge attributes (rollout: q_i, q_j)
     int4 t_e[ROUNDS];                                        // per (round, lane i): the tile's edge i
@@ -259,59 +277,89 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     // their zero behind that wait.  (Left to the compiler the block held three scalar round trips and three vmcnt(0):
     // a conditional load becomes an exec-masked region with a wait of its own.)  The only loads behind the wait are
     // the edge attributes, whose address needs the edge record: they are issued behind the layer-1 MFMAs.
+    // NW == 12 (FIMG): the parameters come as the field image that k_prepare_weights writes once per weight version --
+    // 25 buffer loads of 16 bytes in place of 42 loads (D = 2; 28 of them 4-byte gathers), their address instructions and
+    // the selects behind the wait; the same fp32 values reach the same MFMAs in the same order.
     {
         const int vtiles = (nv + 15) >> 4;
         if (wave < vtiles) {
-            const float* p_emb = P.field_emb; const float* p_w0 = P.field_w0; const float* p_b0 = P.field_b0;
-            const float* p_w2 = P.field_w2; const float* p_b2 = P.field_b2; const float* p_w4 = P.field_w4;
-            const float* p_b4 = P.field_b4; const float* p_rb = P.l1_res_b; const float* p_rw = P.l1_res_w;
-            const float* p_ext = dbg.step.ext_field ? dbg.step.ext_field : x;      // (no external field: x again, not used)
-            asm volatile("" :: "s"(p_emb), "s"(p_w0), "s"(p_b0), "s"(p_w2), "s"(p_b2), "s"(p_w4), "s"(p_b4), "s"(p_rb),
-                         "s"(p_rw), "s"(p_ext), "s"(x), "s"(vel), "s"(charges), "s"(le_base), "s"(nr_base), "s"(ea_base),
-                         "s"(qattr));                          // all in scalar registers before the first vector load
-            const int node = 16 * wave + i;                    // visible slot
-            const bool live = node < nv;
-            const int64_t g = vb + (live ? node : 0);
+            const float* p_ext;
+            int node;                                          // visible slot
+            bool live;
+            int64_t g;
             float pz[D], vz[D], ef[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d) { pz[d] = x[g * D + d]; vz[d] = vel[g * D + d]; ef[d] = p_ext[g * D + d]; }
-            const float ch = charges[g];
+            float ch;
             // layer-1 operands: B = z[k][node], A = W0[16mb + i][k], k = 4s + q (FIN = 2D + 16 <= 24)
             float zc[6][3], a1[2][6];
-#pragma unroll
-            for (int s4 = 0; s4 < 6; ++s4) {
-                const int k = 4 * s4 + q;
-                const int ke = (k >= 2 * D && k < FIN) ? k - 2 * D : 0, kw = k < FIN ? k : 0;
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    zc[s4][c] = (4 * s4 + 3 >= 2 * D && 4 * s4 < FIN) ? p_emb[c * 16 + ke] : 0.0f;
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb) a1[mb][s4] = 4 * s4 < FIN ? p_w0[(16 * mb + i) * FIN + kw] : 0.0f;
-            }
             f32x4 w2f[2][2], w4f[2], acc1[2], acc2[2];
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) {
-                acc1[mb] = ld4(p_b0 + 16 * mb + 4 * q);
-                acc2[mb] = ld4(p_b2 + 16 * mb + 4 * q);
-#pragma unroll
-                for (int a = 0; a < 2; ++a) w2f[mb][a] = ld4(p_w2 + (16 * mb + i) * 32 + 16 * a + 4 * q);
-            }
-#pragma unroll
-            for (int a = 0; a < 2; ++a) w4f[a] = ld4(p_w4 + (i < D ? i : 0) * 32 + 16 * a + 4 * q);
             f32x4 acc3 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc3[r] = r < D ? p_b4[4 * q + r < D ? 4 * q + r : 0] : 0.0f;
             // x0 operands: A = W_res[16mb + i][D + k], k = 4s + q < 2D (the first D inputs of rel_feat are zero)
             float ar[4][2];
             f32x4 acc0[4];
+            f32x4 fimg[FIMG ? FUSED_FIMG_CHUNKS : 1];
+            if constexpr (FIMG) {
+                // The weight operands come as the field image (fused_layout.h, FI_*): 25 16-byte buffer loads on one lane
+                // offset and immediate chunk offsets, every mask already a zero -- no parameter pointer, no address
+                // arithmetic and no select behind the wait.  The descriptor covers the image alone.
+                const auto fimg_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dbg.wimg) + fused_fimg_offset(), 0, FUSED_FIMG * 4, 0x00020000);
+                p_ext = dbg.step.ext_field ? dbg.step.ext_field : x;      // (no external field: x again, not used)
+                asm volatile("" :: "s"(fimg_rsrc), "s"(p_ext), "s"(x), "s"(vel), "s"(charges), "s"(le_base), "s"(nr_base),
+                             "s"(ea_base), "s"(qattr));            // all in scalar registers before the first vector load
+                node = 16 * wave + i;
+                live = node < nv;
+                g = vb + (live ? node : 0);
+                FUSED_PSTAMP(0, f_e.x);
 #pragma unroll
-            for (int mb = 0; mb < 4; ++mb) {
-                acc0[mb] = ld4(p_rb + 16 * mb + 4 * q);
+                for (int d = 0; d < D; ++d) { pz[d] = x[g * D + d]; vz[d] = vel[g * D + d]; ef[d] = p_ext[g * D + d]; }
+                ch = charges[g];
 #pragma unroll
-                for (int s4 = 0; s4 < 2; ++s4)
-                    ar[mb][s4] = 4 * s4 < 2 * D ? p_rw[(16 * mb + i) * 3 * D + D + (4 * s4 + q < 2 * D ? 4 * s4 + q : 0)] : 0.0f;
+                for (int c = 0; c < FUSED_FIMG_CHUNKS; ++c)
+                    fimg[c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(fimg_rsrc, lane * 16, c * 1024, 0));
+            } else {
+                const float* p_emb = P.field_emb; const float* p_w0 = P.field_w0; const float* p_b0 = P.field_b0;
+                const float* p_w2 = P.field_w2; const float* p_b2 = P.field_b2; const float* p_w4 = P.field_w4;
+                const float* p_b4 = P.field_b4; const float* p_rb = P.l1_res_b; const float* p_rw = P.l1_res_w;
+                p_ext = dbg.step.ext_field ? dbg.step.ext_field : x;      // (no external field: x again, not used)
+                asm volatile("" :: "s"(p_emb), "s"(p_w0), "s"(p_b0), "s"(p_w2), "s"(p_b2), "s"(p_w4), "s"(p_b4), "s"(p_rb),
+                             "s"(p_rw), "s"(p_ext), "s"(x), "s"(vel), "s"(charges), "s"(le_base), "s"(nr_base), "s"(ea_base),
+                             "s"(qattr));                          // all in scalar registers before the first vector load
+                node = 16 * wave + i;
+                live = node < nv;
+                g = vb + (live ? node : 0);
+                FUSED_PSTAMP(0, f_e.x);
+#pragma unroll
+                for (int d = 0; d < D; ++d) { pz[d] = x[g * D + d]; vz[d] = vel[g * D + d]; ef[d] = p_ext[g * D + d]; }
+                ch = charges[g];
+#pragma unroll
+                for (int s4 = 0; s4 < 6; ++s4) {
+                    const int k = 4 * s4 + q;
+                    const int ke = (k >= 2 * D && k < FIN) ? k - 2 * D : 0, kw = k < FIN ? k : 0;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+                        zc[s4][c] = (4 * s4 + 3 >= 2 * D && 4 * s4 < FIN) ? p_emb[c * 16 + ke] : 0.0f;
+#pragma unroll
+                    for (int mb = 0; mb < 2; ++mb) a1[mb][s4] = 4 * s4 < FIN ? p_w0[(16 * mb + i) * FIN + kw] : 0.0f;
+                }
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb) {
+                    acc1[mb] = ld4(p_b0 + 16 * mb + 4 * q);
+                    acc2[mb] = ld4(p_b2 + 16 * mb + 4 * q);
+#pragma unroll
+                    for (int a = 0; a < 2; ++a) w2f[mb][a] = ld4(p_w2 + (16 * mb + i) * 32 + 16 * a + 4 * q);
+                }
+#pragma unroll
+                for (int a = 0; a < 2; ++a) w4f[a] = ld4(p_w4 + (i < D ? i : 0) * 32 + 16 * a + 4 * q);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc3[r] = r < D ? p_b4[4 * q + r < D ? 4 * q + r : 0] : 0.0f;
+#pragma unroll
+                for (int mb = 0; mb < 4; ++mb) {
+                    acc0[mb] = ld4(p_rb + 16 * mb + 4 * q);
+#pragma unroll
+                    for (int s4 = 0; s4 < 2; ++s4)
+                        ar[mb][s4] = 4 * s4 < 2 * D ? p_rw[(16 * mb + i) * 3 * D + D + (4 * s4 + q < 2 * D ? 4 * s4 + q : 0)] : 0.0f;
+                }
             }
-            index_stage_a();                                    // behind this wave's own inputs (in-order returns: they do not wait for it)
+            index_stage_a();                                  // behind this wave's own inputs (in-order returns: they do not wait for it)
             // The one wait of the block, in the form the compiler's wait-count pass sees (simm16 of vmcnt(0) alone): it places none
             // of its own in front of the MFMAs.
             // Nothing is scheduled across the wait (sched_barrier), and every loaded value is named right behind it (empty
@@ -320,6 +368,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_waitcnt(0x0F70);
             __builtin_amdgcn_sched_barrier(0);
+            FUSED_PSTAMP(1, f_e.x);
             auto landed = [](auto v) { asm volatile("" :: "v"(v)); };
             auto landed4 = [](const int4& v) { asm volatile("" :: "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); };
             landed4(f_e); landed4(nr_rec);
@@ -328,43 +377,71 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
 #pragma unroll
             for (int d = 0; d < D; ++d) { landed(pz[d]); landed(vz[d]); landed(ef[d]); }
             landed(ch);
+            if constexpr (FIMG) {
 #pragma unroll
-            for (int s4 = 0; s4 < 6; ++s4) {
+                for (int c = 0; c < FUSED_FIMG_CHUNKS; ++c) landed(fimg[c]);
+                // the operands are the image's slots as they stand (FI_*): register names, no instruction
+                auto slot = [&](int s) { return fimg[s >> 2][s & 3]; };
 #pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    if (4 * s4 + 3 >= 2 * D && 4 * s4 < FIN) landed(zc[s4][c]);
+                for (int mb = 0; mb < 2; ++mb) {
+                    acc1[mb] = fimg[FI_ACC1 / 4 + mb]; acc2[mb] = fimg[FI_ACC2 / 4 + mb];
 #pragma unroll
-                for (int mb = 0; mb < 2; ++mb)
-                    if (4 * s4 < FIN) landed(a1[mb][s4]);
+                    for (int a = 0; a < 2; ++a) w2f[mb][a] = fimg[FI_W2F / 4 + 2 * mb + a];
+#pragma unroll
+                    for (int s4 = 0; s4 < 6; ++s4) a1[mb][s4] = slot(FI_A1 + 6 * mb + s4);
+                }
+#pragma unroll
+                for (int a = 0; a < 2; ++a) w4f[a] = fimg[FI_W4F / 4 + a];
+                acc3 = fimg[FI_ACC3 / 4];
+#pragma unroll
+                for (int s4 = 0; s4 < 6; ++s4)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) zc[s4][c] = slot(FI_ZC + 3 * s4 + c);
+#pragma unroll
+                for (int mb = 0; mb < 4; ++mb) {
+                    acc0[mb] = fimg[FI_ACC0 / 4 + mb];
+#pragma unroll
+                    for (int s4 = 0; s4 < 2; ++s4) ar[mb][s4] = slot(FI_AR + 2 * mb + s4);
+                }
+            } else {
+#pragma unroll
+                for (int s4 = 0; s4 < 6; ++s4) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+                        if (4 * s4 + 3 >= 2 * D && 4 * s4 < FIN) landed(zc[s4][c]);
+#pragma unroll
+                    for (int mb = 0; mb < 2; ++mb)
+                        if (4 * s4 < FIN) landed(a1[mb][s4]);
+                }
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb) { landed(acc1[mb]); landed(acc2[mb]); landed(w2f[mb][0]); landed(w2f[mb][1]); }
+                landed(w4f[0]); landed(w4f[1]);
+#pragma unroll
+                for (int r = 0; r < D; ++r) landed(acc3[r]);
+#pragma unroll
+                for (int mb = 0; mb < 4; ++mb) {
+                    landed(acc0[mb]);
+#pragma unroll
+                    for (int s4 = 0; s4 < 2; ++s4)
+                        if (4 * s4 < 2 * D) landed(ar[mb][s4]);
+                }
+#pragma unroll
+                for (int s4 = 0; s4 < 6; ++s4) {
+                    const int k = 4 * s4 + q;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) zc[s4][c] = (k >= 2 * D && k < FIN) ? zc[s4][c] : 0.0f;
+#pragma unroll
+                    for (int mb = 0; mb < 2; ++mb) a1[mb][s4] = k < FIN ? a1[mb][s4] : 0.0f;
+                }
+#pragma unroll
+                for (int a = 0; a < 2; ++a) w4f[a] = i < D ? w4f[a] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc3[r] = (4 * q + r < D) ? acc3[r] : 0.0f;
+#pragma unroll
+                for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+                    for (int s4 = 0; s4 < 2; ++s4) ar[mb][s4] = 4 * s4 + q < 2 * D ? ar[mb][s4] : 0.0f;
             }
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) { landed(acc1[mb]); landed(acc2[mb]); landed(w2f[mb][0]); landed(w2f[mb][1]); }
-            landed(w4f[0]); landed(w4f[1]);
-#pragma unroll
-            for (int r = 0; r < D; ++r) landed(acc3[r]);
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb) {
-                landed(acc0[mb]);
-#pragma unroll
-                for (int s4 = 0; s4 < 2; ++s4)
-                    if (4 * s4 < 2 * D) landed(ar[mb][s4]);
-            }
-#pragma unroll
-            for (int s4 = 0; s4 < 6; ++s4) {
-                const int k = 4 * s4 + q;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) zc[s4][c] = (k >= 2 * D && k < FIN) ? zc[s4][c] : 0.0f;
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb) a1[mb][s4] = k < FIN ? a1[mb][s4] : 0.0f;
-            }
-#pragma unroll
-            for (int a = 0; a < 2; ++a) w4f[a] = i < D ? w4f[a] : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc3[r] = (4 * q + r < D) ? acc3[r] : 0.0f;
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-                for (int s4 = 0; s4 < 2; ++s4) ar[mb][s4] = 4 * s4 + q < 2 * D ? ar[mb][s4] : 0.0f;
             index_select();
             long ci = (long)(ch + 1.0f);                        // charge_to_index: (q + 1).long(), aether.py:127-129
             ci = ci < 0 ? 0 : (ci > 2 ? 2 : ci);
@@ -395,6 +472,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int b = 0; b < 4; ++b) acc3 = mfma16(w4f[a][b], hh[a][b], acc3);
+            FUSED_PSTAMP(2, acc3[0]);
             // lanes q == 0: acc3[d] = force component d of node i -> frame + NodeInfo record
             if (q == 0 && live) {
                 float f[D], R[D][D], cv[D], cf[D];
@@ -417,6 +495,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                 }
             }
             __builtin_amdgcn_wave_barrier();
+            FUSED_PSTAMP(3, acc3[0]);
             // x0 = W_res[:, D:] [cv | cf] + b (own nodes only; cv, cf are contiguous in the record)
 #pragma unroll
             for (int s4 = 0; s4 < 2; ++s4) {
@@ -433,6 +512,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                     if (keep) st4(dbg.x[0] + (int64_t)(nb + own) * H + 16 * mb + 4 * q, acc0[mb]);
                 }
             }
+            FUSED_PSTAMP(4, acc0[3][0]);
         } else {
             index_stage_a();
             index_select();
@@ -460,9 +540,9 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         for (int r0 = 0; r0 < ROUNDS; r0 += 2) {               // two rounds (32 scratch rows) per pass
             constexpr int PASS = 2;
             const int nr_pass = ROUNDS - r0 < PASS ? ROUNDS - r0 : PASS;
-            if (lane < 16 * nr_pass) {
+            if (PACKED ? wave < FUSED_PACK_WAVES && lane < FUSED_PACK_LANES : lane < 16 * nr_pass) {
                 const int r = r0 + (lane >> 4), ii = lane & 15;
-                const int local = 16 * (NW * r + wave) + ii;
+                const int local = PACKED ? f_local : 16 * (NW * r + wave) + ii;
                 float o[FPAD];
                 if (local < m) {
                     // position in the receiver-sorted edge list, sender, receiver (first pass: requested during P1)
@@ -496,9 +576,12 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                 }
 #pragma unroll
                 for (int t = 0; t < FPAD; t += 4)
-                    st4(scratch + lane * LDF + t, f32x4{o[t], o[t + 1], o[t + 2], o[t + 3]});
+                    st4((PACKED ? smem + L::FEAT + local * LDF : scratch + lane * LDF) + t, f32x4{o[t], o[t + 1], o[t + 2], o[t + 3]});
             }
-            __builtin_amdgcn_wave_barrier();
+            // PACKED: the rows were written by another wave (row `local` of L::FEAT is row local & 15 of wave local >> 4).
+            // Every wave of every workgroup arrives here, whether it built rows, owns a tile, or the group has no edge.
+            if constexpr (PACKED) lds_barrier();
+            else __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int rr = 0; rr < PASS; ++rr) {
                 const int r = r0 + rr;
@@ -565,7 +648,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     // four k blocks of W4 row block wave & 3.  w3* / w4* / ws* / wr* are not used then.
     f16x8 wf_h[4], wf_l[4];
     // the node phase's fragments come by buffer loads (issue_loads): descriptor of the whole image set, the lane's 16 bytes
-    const auto wimg_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dbg.wimg), 0, FUSED_WIMG_SET * 4, 0x00020000);
+    const auto wimg_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dbg.wimg), 0, FUSED_WIMG_SPLIT * 4, 0x00020000);
     const int lane16 = lane * 16;
 #pragma unroll 1
     for (int layer = 1; layer <= 4; ++layer) {

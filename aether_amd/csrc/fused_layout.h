@@ -9,6 +9,12 @@ constexpr int FUSED_MAX_NODES = 32;          // two 16-node MFMA tiles
 constexpr int FUSED_MAX_EDGES = 384;         // 24 tiles (N=20 fully connected: 380 edges)
 constexpr int FUSED_MAX_TILES = FUSED_MAX_EDGES / 16;
 constexpr int LDU = 2 * H + 8;               // padded LDS row for the 128-wide update hidden
+// 12-wave kernels: the layer-1 features of all (at most 12) tiles are built by one wave per SIMD -- waves 0-3, lanes 0-47 --
+// each lane the edge below in the workgroup's local order: row lane & 15 of tile 3 wave + (lane >> 4), whose owner is
+// wave `tile`.  4 x 48 = 192 edges = the 12 tiles.
+constexpr int FUSED_PACK_WAVES = 4, FUSED_PACK_LANES = 48;
+__device__ __host__ constexpr int fused_packed_edge(int wave, int lane) { return FUSED_PACK_LANES * wave + lane; }
+static_assert(FUSED_PACK_WAVES * FUSED_PACK_LANES == 12 * 16 && FUSED_PACK_LANES % 16 == 0, "every row of the twelve tiles has one builder");
 
 // The edge MLP's two 64 x 64 contractions run as three fp16 MFMA terms on operands split into two fp16 pieces (common.h,
 // gemm_split); the weight images (2 x 8 KB each instead of 18 KB of padded fp32) fit every variant since the layer-1 features of the
@@ -85,8 +91,30 @@ template <int NW, int ROUNDS> struct FusedLds {          // offsets in floats
 // W3 [128][64] (stage_split4<8, 2>), W4 [64][128] (<4, 4>), and the NEXT layer's W_s, W_r (<4, 2> each; layer 4: out_w0, out_w3).
 constexpr int FUSED_NIMG_W3 = 2 * 8 * 2 * 64 * 4, FUSED_NIMG_W4 = 2 * 4 * 4 * 64 * 4, FUSED_NIMG_WS = 2 * 4 * 2 * 64 * 4;
 constexpr int FUSED_NIMG_LAYER = FUSED_NIMG_W3 + FUSED_NIMG_W4 + 2 * FUSED_NIMG_WS;
-constexpr int FUSED_WIMG_SET = 8 * FUSED_WIMG + 4 * FUSED_NIMG_LAYER + 4 * FUSED_CBLK;   // floats reserved (layer 1's image A uses half of its slot)
-constexpr int FUSED_SPLIT_BLOCKS = 8 + 4 * 6 + 1;        // blocks of k_prepare_weights that write images (512 threads each)
+// Field image (12-wave kernels): what the field wave's MFMAs consume of the field net, W_res[:, D:] and their biases --
+// fp32, in lane-fragment order (lane = 16 q + i), the k < FIN, i < D and 4q + r < D masks baked in as zeros -- so that the
+// wave fetches them as FUSED_FIMG_CHUNKS 16-byte buffer loads per lane (chunk c, lane L: floats 256 c + 4 L ..) instead of
+// 42 loads (D = 2), two thirds of them 4-byte gathers with per-lane addresses, and the mask selects behind the wait.  Slot s of a lane is float s & 3 of chunk s >> 2.
+// Behind everything else in the set: no other offset moves.
+constexpr int FI_ACC1 = 0;                               // [2 mb][4]     field_b0[16 mb + 4q + r]      (accumulator layout)
+constexpr int FI_ACC2 = 8;                               // [2 mb][4]     field_b2
+constexpr int FI_W2F = 16;                               // [2 mb][2 a][4] field_w2[16 mb + i][16 a + 4q + r]
+constexpr int FI_W4F = 32;                               // [2 a][4]      field_w4[i][16 a + 4q + r], i < D
+constexpr int FI_ACC3 = 40;                              // [4]           field_b4[4q + r], 4q + r < D
+constexpr int FI_ACC0 = 44;                              // [4 mb][4]     l1_res_b[16 mb + 4q + r]
+constexpr int FI_A1 = 60;                                // [2 mb][6 s]   field_w0[16 mb + i][4s + q], 4s + q < FIN
+constexpr int FI_ZC = 72;                                // [6 s][3 c]    field_emb[c][4s + q - 2D], 2D <= 4s + q < FIN
+constexpr int FI_AR = 90;                                // [4 mb][2 s]   l1_res_w[16 mb + i][D + 4s + q], 4s + q < 2D
+constexpr int FI_END = 98;
+constexpr int FUSED_FIMG_CHUNKS = (FI_END + 3) / 4;      // 25
+constexpr int FUSED_FIMG = FUSED_FIMG_CHUNKS * 256;      // floats (25 KiB)
+constexpr int FUSED_WIMG_SPLIT = 8 * FUSED_WIMG + 4 * FUSED_NIMG_LAYER + 4 * FUSED_CBLK;   // the split images and constants blocks (layer 1's image A uses half of its slot)
+constexpr int FUSED_WIMG_SET = FUSED_WIMG_SPLIT + FUSED_FIMG;   // floats reserved
+// blocks of k_prepare_weights that write images (512 threads each): 8 edge images, 24 node images, the constants blocks,
+// and one block per chunk of the field image (a thread writes one float: the launch is as long as its longest block, and
+// every training step runs it)
+constexpr int FUSED_SPLIT_BLOCKS = 8 + 4 * 6 + 1 + FUSED_FIMG_CHUNKS;
+__device__ __host__ constexpr int fused_fimg_offset() { return FUSED_WIMG_SPLIT; }
 __device__ __host__ constexpr int fused_wimg_offset(int layer, int which) { return ((layer - 1) * 2 + which) * FUSED_WIMG; }
 // which: 0 W3, 1 W4, 2 W_s (next layer / out_w0), 3 W_r (next layer / out_w3)
 __device__ __host__ constexpr int fused_nimg_offset(int layer, int which) {
@@ -109,8 +137,44 @@ __device__ __forceinline__ float fused_cblk_value(const AetherParams& P, int nd,
     return 0.0f;
 }
 
+// Slot `slot` of lane 16 q + i of the field image (layout: FI_* above).  Reads the tensors the 8-wave kernels' field wave
+// reads, at the same indices and under the same conditions; a masked element is +0.0f and is not read.
+__device__ __forceinline__ float fused_fimg_value(const AetherParams& P, int nd, int slot, int i, int q) {
+    const int fin = 2 * nd + 16;
+    if (slot < FI_ACC2) return P.field_b0[16 * (slot >> 2) + 4 * q + (slot & 3)];
+    if (slot < FI_W2F) return P.field_b2[16 * ((slot - FI_ACC2) >> 2) + 4 * q + (slot & 3)];
+    if (slot < FI_W4F) {
+        const int s = slot - FI_W2F, mb = s >> 3, a = (s >> 2) & 1;
+        return P.field_w2[(16 * mb + i) * 32 + 16 * a + 4 * q + (s & 3)];
+    }
+    if (slot < FI_ACC3) {
+        const int s = slot - FI_W4F;
+        return i < nd ? P.field_w4[i * 32 + 16 * (s >> 2) + 4 * q + (s & 3)] : 0.0f;
+    }
+    if (slot < FI_ACC0) return 4 * q + (slot - FI_ACC3) < nd ? P.field_b4[4 * q + (slot - FI_ACC3)] : 0.0f;
+    if (slot < FI_A1) return P.l1_res_b[16 * ((slot - FI_ACC0) >> 2) + 4 * q + (slot & 3)];
+    if (slot < FI_ZC) {
+        const int s = slot - FI_A1, mb = s / 6, k = 4 * (s % 6) + q;
+        return k < fin ? P.field_w0[(16 * mb + i) * fin + k] : 0.0f;
+    }
+    if (slot < FI_AR) {
+        const int s = slot - FI_ZC, c = s % 3, k = 4 * (s / 3) + q;
+        return (k >= 2 * nd && k < fin) ? P.field_emb[c * 16 + k - 2 * nd] : 0.0f;
+    }
+    if (slot < FI_END) {
+        const int s = slot - FI_AR, mb = s >> 1, k = 4 * (s & 1) + q;
+        return k < 2 * nd ? P.l1_res_w[(16 * mb + i) * 3 * nd + nd + k] : 0.0f;
+    }
+    return 0.0f;
+}
+
 __device__ __forceinline__ void split_weights_block(const AetherParams& P, int f1, int nd, float* __restrict__ wimg, int block, int tid) {
-    if (block == FUSED_SPLIT_BLOCKS - 1) {                // the four constants blocks
+    if (block >= FUSED_SPLIT_BLOCKS - FUSED_FIMG_CHUNKS) {   // the field image: chunk c = 256 floats, float 4 lane + r is slot 4 c + r
+        const int c = block - (FUSED_SPLIT_BLOCKS - FUSED_FIMG_CHUNKS), lane = tid >> 2;
+        if (tid < 256) wimg[fused_fimg_offset() + 256 * c + tid] = fused_fimg_value(P, nd, 4 * c + (tid & 3), lane & 15, lane >> 4);
+        return;
+    }
+    if (block == FUSED_SPLIT_BLOCKS - FUSED_FIMG_CHUNKS - 1) {   // the four constants blocks
         for (int idx = tid; idx < 4 * FUSED_CBLK; idx += 512)
             wimg[fused_cblk_offset(1) + idx] = fused_cblk_value(P, nd, idx / FUSED_CBLK + 1, idx % FUSED_CBLK);
         return;

@@ -217,6 +217,13 @@ int64_t aether_debug_fetch(const char* name, int num_dims, int64_t n_nodes, int6
 int aether_debug_split(const float* x, int n_tiles, uint16_t* hi, uint16_t* lo, int* on, float* scale, float* y);
 
 /*
+ * Test hook of the 12-wave fused kernels' layer-1 feature build (csrc/fused_layout.h: fused_packed_edge): the edge, in the
+ * workgroup's local order, whose features lane `lane` of wave `wave` builds, or -1 for a (wave, lane) that builds none.
+ * Edge f is row f & 15 of tile f >> 4, which wave f >> 4 owns.  Host only: needs no GPU.
+ */
+int aether_debug_fused_packed_edge(int wave, int lane);
+
+/*
  * Dynamic-field variant of the state2state model: DynamicFieldAether.forward
  * (nn/state2state/dynamic_field_aether.py:79-100) = aether_dynamic_field (LatentFieldNetwork, :31-48:
  * attention-pooled graph summary + FiLM field net, hidden 32) followed by aether_forward_field, i.e.

@@ -57,6 +57,15 @@ for k in order:
     prev = med[k]
 clk = np.median(st[:, 41] / st[:, 40])
 print(f"  shader clock during the kernel: {clk:.0f} MHz (s_memtime cycles / wall us)")
+pv = med[400:405]                 # FUSED_PSTAMP: the field wave (wave 0) inside "field+frames+x0", cycles since entry
+if pv[4] > 0:
+    us = lambda c: c / clk
+    print("  field wave (wave 0), cycles since kernel entry (microseconds at the shader clock):")
+    for name, t0, t1 in (("entry -> first vector load issued", 0.0, pv[0]), ("-> vmcnt(0) passed", pv[0], pv[1]),
+                         ("-> last MFMA of the field net", pv[1], pv[2]), ("-> frame stored", pv[2], pv[3]),
+                         ("-> x0 stored", pv[3], pv[4])):
+        print(f"   {name:36s} t={t1:7.0f}  d={t1 - t0:6.0f}  ({us(t1 - t0):5.2f} us)")
+    print(f"   -> barrier behind P1 (thread 0)      t={med[2] * clk:7.0f}  d={med[2] * clk - pv[4]:6.0f}  ({med[2] - us(pv[4]):5.2f} us)")
 print("  layer-2 per-wave tile timeline, cycles since kernel entry (median over workgroups):")
 print("   wave round   start  wait rows  gemm1+silu1  gemm2+silu2+stage  sums   | total   [gemm1 | wait rows + receive | late add + silu1]")
 sums = []
