@@ -259,6 +259,7 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
     "aether_debug_split": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     "aether_debug_fused_packed_edge": (C.c_int, [C.c_int, C.c_int]),
+    "aether_debug_fused_wave_role": (C.c_int, [C.c_int, C.c_int]),
     "aether_workspace_bytes_h": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int]),
     "aether_dropout_mask_offset_h": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "aether_forward_h": (C.c_int, [C.POINTER(AetherParams), C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,

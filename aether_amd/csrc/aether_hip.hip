@@ -1688,6 +1688,13 @@ int aether_debug_fused_packed_edge(int wave, int lane) {
     return fused_packed_edge(wave, lane);
 }
 
+int aether_debug_fused_wave_role(int what, int wave) {
+    if (wave < 0 || wave >= 12) return -1;
+    if (what == 0) return wave >= FUSED_FRAME_WAVE0 && fused_frame_tile(wave) < FUSED_MAX_NODES / 16 ? fused_frame_tile(wave) : -1;
+    if (what == 1) return wave >= FUSED_X0_WAVE0 && fused_x0_rowblock(wave) < FUSED_X0_WAVES ? fused_x0_rowblock(wave) : -1;
+    return -1;
+}
+
 #include "host_wide.inc"
 #include "host_rollout_train.inc"
 

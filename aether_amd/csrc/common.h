@@ -696,6 +696,45 @@ __device__ __forceinline__ void node_frame(const float (&v)[D], const float (&f)
     }
 }
 
+// node_frame in its two halves (12-wave k_fused: the frame is built beside the field net, cf where the force is read).
+// The same operations in the same order as node_frame: R and cv = R^T v need the velocity alone ...
+template <int D>
+__device__ __forceinline__ void node_frame_vel(const float (&v)[D], float (&R)[D][D], float (&cv)[D]) {
+    float theta = atan2f(v[1], v[0]);
+    if (theta < 0.0f) theta += TWO_PI_F;
+    float c = cosf(theta), s = sinf(theta);
+    if constexpr (D == 2) {
+        R[0][0] = c; R[0][1] = -s; R[1][0] = s; R[1][1] = c;
+    } else {
+        float rho = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        float cz = v[2] / (rho + EPS_F);
+        cz = fminf(fmaxf(cz, -1.0f), 1.0f);
+        float phi = acosf(cz);
+        float cp = cosf(phi), sp = sinf(phi);
+        R[0][0] = cp * c; R[0][1] = -s;  R[0][2] = sp * c;
+        R[1][0] = cp * s; R[1][1] = c;   R[1][2] = sp * s;
+        R[2][0] = -sp;    R[2][1] = 0.f; R[2][2] = cp;
+    }
+#pragma unroll
+    for (int a = 0; a < D; ++a) {                             // R^T v
+        float sv = 0.f;
+#pragma unroll
+        for (int b = 0; b < D; ++b) sv += R[b][a] * v[b];
+        cv[a] = sv;
+    }
+}
+// ... and cf = R^T f needs the field too: D * D multiply-adds on the stored R (row-major, as in the NodeInfo record).
+template <int D>
+__device__ __forceinline__ void node_frame_force(const float* __restrict__ R, const float* __restrict__ f, float* __restrict__ cf) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) {                             // R^T f
+        float sf = 0.f;
+#pragma unroll
+        for (int b = 0; b < D; ++b) sf += R[b * D + a] * f[b];
+        cf[a] = sf;
+    }
+}
+
 // Local-frame edge features for edge j -> i (aether.py:52-100, geometry.py:76-101), followed by
 // [rel_feat[recv] | edge_attr_orig] (aether.py:99,177); `nj` / `nir` are NodeInfo records.
 template <int D>

@@ -78,18 +78,23 @@ constexpr int FUSED_STAMPS = 512;
 // the field wave's pieces (wave 0, shader-clock cycles since entry), behind the slots above: 0 first vector load issued,
 // 1 the block's vmcnt(0) passed, 2 last MFMA of the field net retired, 3 frame stored, 4 x0 stored.  `dep_`: a vector
 // register the stamp waits for (the wave issues in order: the move stalls until the value is there).
-#define FUSED_PSTAMP(k_, dep_)                                                                    \
+// 12-wave kernels: 3 = the force stored (the frame is the frame wave's), 4 not written; FUSED_PSTAMP_W, wave `w_`: 5 the
+// frame wave of node tile 0 has its inputs, 6 its frames stored; 7 x0 wave of row block 0 behind the P1 barrier, 8 its
+// rows of x0 stored.
+#define FUSED_PSTAMP_W(w_, k_, dep_)                                                              \
     do {                                                                                         \
         asm volatile("v_mov_b32 %0, %0" : "+v"(dep_));                                           \
-        if (wave == 0 && lane == 0 && blockIdx.x < 4096)                                         \
+        if (wave == (w_) && lane == 0 && blockIdx.x < 4096)                                      \
             dbg.stamps[blockIdx.x * FUSED_STAMPS + 400 + (k_)] =                                  \
                 (float)(__builtin_amdgcn_s_memtime() - c_entry);                                 \
     } while (0)
+#define FUSED_PSTAMP(k_, dep_) FUSED_PSTAMP_W(0, k_, dep_)
 #else
 #define FUSED_STAMP(id)
 #define FUSED_WSTAMP(layer_, r_, k_)
 #define FUSED_WSTAMP_ROWS(layer_, r_)
 #define FUSED_PSTAMP(k_, dep_)
+#define FUSED_PSTAMP_W(w_, k_, dep_)
 #endif
 
 template <int D, int NW, int ROUNDS, bool KEEP, bool GRAN = false>
@@ -199,6 +204,13 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     // whatever its exec mask.  t_e, sl, rl and nr_rec stay per owner.
     constexpr bool PACKED = NW == 12;
     constexpr bool FIMG = NW == 12;      // the field wave's weight operands come as the prepared field image (P1)
+    // NW == 12 (FRAMES): the field wave runs the field net and stores the force alone.  R and cv = R^T v need the velocity
+    // only: wave FUSED_FRAME_WAVE0 + t builds them for visible node tile t while the field net runs (P1's else branch);
+    // cf = R^T f is D * D multiply-adds that each reader does on its register copy of the record (P2's receiver record,
+    // the x0 waves), so the record's CF words are not written and no wave waits for another inside P1.  x0 is first read in
+    // step 1 of layer 1's node phase: waves FUSED_X0_WAVE0 .. + 3 compute it behind the P1 barrier, next to the feature build.
+    constexpr bool FRAMES = NW == 12;
+    f32x4 x0_acc = f32x4{0.f, 0.f, 0.f, 0.f}, x0_ar = f32x4{0.f, 0.f, 0.f, 0.f};   // FRAMES: an x0 wave's two chunks of the field image
     const int f_local = PACKED ? fused_packed_edge(wave, lane) : 16 * (NW * (lane >> 4) + wave) + (lane & 15);
     const bool f_have = (PACKED ? wave < FUSED_PACK_WAVES && lane < FUSED_PACK_LANES : lane < 16 * FR) && f_local < m;   // this lane builds the features of edge f_local
     int4 f_e = make_int4(0, 0, 0, 0);                        // {sorted position, sender, receiver, original edge}
@@ -271,6 +283,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
     // Wave t owns the visible nodes 16t .. 16t+15 as the 16 columns of its MFMA tiles; the three
     // Linear layers chain in accumulator layout, lanes q == 0 end up with the node's force and build
     // its frame, and x0 = res(rel_feat) is one more tile product: no workgroup barrier in between.
+    // (NW == 12, FRAMES above: the field wave stops at the force; frames on waves 2, 3 in the else branch, x0 behind the barrier.)
     // The field wave's load block is: every pointer it needs out of the kernel arguments (scalar loads, one wait),
     // then every vector load (inputs, 2,080 field parameters, res weights, the external field, this wave's edge and
     // node records) back to back and unconditional, on clamped indices, then ONE vmcnt(0); lanes whose element does not exist select
@@ -314,7 +327,8 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                 ch = charges[g];
 #pragma unroll
                 for (int c = 0; c < FUSED_FIMG_CHUNKS; ++c)
-                    fimg[c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(fimg_rsrc, lane * 16, c * 1024, 0));
+                    if (fused_fimg_field_chunk(c))                // (19 of the 25: the x0 operands are the x0 waves')
+                        fimg[c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(fimg_rsrc, lane * 16, c * 1024, 0));
             } else {
                 const float* p_emb = P.field_emb; const float* p_w0 = P.field_w0; const float* p_b0 = P.field_b0;
                 const float* p_w2 = P.field_w2; const float* p_b2 = P.field_b2; const float* p_w4 = P.field_w4;
@@ -379,7 +393,8 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             landed(ch);
             if constexpr (FIMG) {
 #pragma unroll
-                for (int c = 0; c < FUSED_FIMG_CHUNKS; ++c) landed(fimg[c]);
+                for (int c = 0; c < FUSED_FIMG_CHUNKS; ++c)
+                    if (fused_fimg_field_chunk(c)) landed(fimg[c]);
                 // the operands are the image's slots as they stand (FI_*): register names, no instruction
                 auto slot = [&](int s) { return fimg[s >> 2][s & 3]; };
 #pragma unroll
@@ -397,12 +412,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                 for (int s4 = 0; s4 < 6; ++s4)
 #pragma unroll
                     for (int c = 0; c < 3; ++c) zc[s4][c] = slot(FI_ZC + 3 * s4 + c);
-#pragma unroll
-                for (int mb = 0; mb < 4; ++mb) {
-                    acc0[mb] = fimg[FI_ACC0 / 4 + mb];
-#pragma unroll
-                    for (int s4 = 0; s4 < 2; ++s4) ar[mb][s4] = slot(FI_AR + 2 * mb + s4);
-                }
+                static_assert(FRAMES, "FI_ACC0 / FI_AR: the x0 waves' operands, loaded by them (P1's else branch)");
             } else {
 #pragma unroll
                 for (int s4 = 0; s4 < 6; ++s4) {
@@ -473,50 +483,96 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
 #pragma unroll
                 for (int b = 0; b < 4; ++b) acc3 = mfma16(w4f[a][b], hh[a][b], acc3);
             FUSED_PSTAMP(2, acc3[0]);
-            // lanes q == 0: acc3[d] = force component d of node i -> frame + NodeInfo record
-            if (q == 0 && live) {
-                float f[D], R[D][D], cv[D], cf[D];
+            if constexpr (FRAMES) {
+                // lanes q == 0: acc3[d] = force component d of node i -> the record's F words; the rest of the record is the
+                // frame wave's, x0 the x0 waves'
+                if (q == 0 && live) {
 #pragma unroll
-                for (int d = 0; d < D; ++d)
-                    f[d] = dbg.step.ext_field ? ef[d] : acc3[d];       // (live: g = vb + node)
-                node_frame<D>(vz, f, R, cv, cf);
-                float* ni = ninfo + node * 24;
-#pragma unroll
-                for (int d = 0; d < D; ++d) {
-                    ni[NI::P + d] = pz[d]; ni[NI::V + d] = vz[d]; ni[NI::F + d] = f[d];
-                    ni[NI::CV + d] = cv[d]; ni[NI::CF + d] = cf[d];
-#pragma unroll
-                    for (int e = 0; e < D; ++e) ni[NI::R + d * D + e] = R[d][e];
+                    for (int d = 0; d < D; ++d)
+                        ninfo[node * 24 + NI::F + d] = dbg.step.ext_field ? ef[d] : acc3[d];       // (live: g = vb + node)
                 }
-                if (keep && node >= off && node < off + n) {
-                    float* gni = dbg.nodeinfo + (int64_t)(vb + node) * NI::STRIDE;
+                FUSED_PSTAMP(3, acc3[0]);
+            } else {
+                // lanes q == 0: acc3[d] = force component d of node i -> frame + NodeInfo record
+                if (q == 0 && live) {
+                    float f[D], R[D][D], cv[D], cf[D];
 #pragma unroll
-                    for (int t = 0; t < NI::STRIDE; ++t) gni[t] = t < NI::CF + D ? ni[t] : 0.0f;
+                    for (int d = 0; d < D; ++d)
+                        f[d] = dbg.step.ext_field ? ef[d] : acc3[d];       // (live: g = vb + node)
+                    node_frame<D>(vz, f, R, cv, cf);
+                    float* ni = ninfo + node * 24;
+#pragma unroll
+                    for (int d = 0; d < D; ++d) {
+                        ni[NI::P + d] = pz[d]; ni[NI::V + d] = vz[d]; ni[NI::F + d] = f[d];
+                        ni[NI::CV + d] = cv[d]; ni[NI::CF + d] = cf[d];
+#pragma unroll
+                        for (int e = 0; e < D; ++e) ni[NI::R + d * D + e] = R[d][e];
+                    }
+                    if (keep && node >= off && node < off + n) {
+                        float* gni = dbg.nodeinfo + (int64_t)(vb + node) * NI::STRIDE;
+#pragma unroll
+                        for (int t = 0; t < NI::STRIDE; ++t) gni[t] = t < NI::CF + D ? ni[t] : 0.0f;
+                    }
                 }
-            }
-            __builtin_amdgcn_wave_barrier();
-            FUSED_PSTAMP(3, acc3[0]);
-            // x0 = W_res[:, D:] [cv | cf] + b (own nodes only; cv, cf are contiguous in the record)
+                __builtin_amdgcn_wave_barrier();
+                FUSED_PSTAMP(3, acc3[0]);
+                // x0 = W_res[:, D:] [cv | cf] + b (own nodes only; cv, cf are contiguous in the record)
 #pragma unroll
-            for (int s4 = 0; s4 < 2; ++s4) {
-                const int k = 4 * s4 + q;
-                const float rk = (live && k < 2 * D) ? ninfo[node * 24 + NI::CV + k] : 0.0f;
+                for (int s4 = 0; s4 < 2; ++s4) {
+                    const int k = 4 * s4 + q;
+                    const float rk = (live && k < 2 * D) ? ninfo[node * 24 + NI::CV + k] : 0.0f;
 #pragma unroll
-                for (int mb = 0; mb < 4; ++mb) acc0[mb] = mfma16(ar[mb][s4], rk, acc0[mb]);
-            }
-            const int own = node - off;
-            if (own >= 0 && own < n) {
-#pragma unroll
-                for (int mb = 0; mb < 4; ++mb) {
-                    st4(xbuf + own * LDW + 16 * mb + 4 * q, acc0[mb]);
-                    if (keep) st4(dbg.x[0] + (int64_t)(nb + own) * H + 16 * mb + 4 * q, acc0[mb]);
+                    for (int mb = 0; mb < 4; ++mb) acc0[mb] = mfma16(ar[mb][s4], rk, acc0[mb]);
                 }
+                const int own = node - off;
+                if (own >= 0 && own < n) {
+#pragma unroll
+                    for (int mb = 0; mb < 4; ++mb) {
+                        st4(xbuf + own * LDW + 16 * mb + 4 * q, acc0[mb]);
+                        if (keep) st4(dbg.x[0] + (int64_t)(nb + own) * H + 16 * mb + 4 * q, acc0[mb]);
+                    }
+                }
+                FUSED_PSTAMP(4, acc0[3][0]);
             }
-            FUSED_PSTAMP(4, acc0[3][0]);
         } else {
+            // FRAMES: the frame wave's inputs and an x0 wave's operands go out in front of the index loads: unconditional, on
+            // clamped indices (a wave without that role loads node vb and row block wave & 3 and uses neither)
+            const int ft = fused_frame_tile(wave), fnode = 16 * ft + i;
+            const bool fwave = FRAMES && ft >= 0 && ft < vtiles;
+            const bool flive = fwave && fnode < nv;
+            float pz[D], vz[D];
+            if constexpr (FRAMES) {
+                const auto fimg_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dbg.wimg) + fused_fimg_offset(), 0, FUSED_FIMG * 4, 0x00020000);
+                const int64_t g = vb + (flive ? fnode : 0);
+#pragma unroll
+                for (int d = 0; d < D; ++d) { pz[d] = x[g * D + d]; vz[d] = vel[g * D + d]; }
+                const int mb = __builtin_amdgcn_readfirstlane(fused_x0_rowblock(wave)) & 3;
+                x0_acc = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(fimg_rsrc, lane * 16, (FI_ACC0 / 4 + mb) * 1024, 0));
+                x0_ar = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(fimg_rsrc, lane * 16, ((FI_AR + 2 * mb) >> 2) * 1024, 0));
+            }
             index_stage_a();
             index_select();
             f_ea = index_stage_b();
+            if constexpr (FRAMES) {
+                // the inputs are read in an exec-masked region only: named here, the wait for them stands in front of it (the
+                // first loads of the wave: the index loads stay in flight)
+#pragma unroll
+                for (int d = 0; d < D; ++d) asm volatile("" :: "v"(pz[d]), "v"(vz[d]));
+                FUSED_PSTAMP_W(FUSED_FRAME_WAVE0, 5, vz[0]);
+                // lanes 0-15 of a frame wave: P, V, R, CV of the node's record (F: the field wave; CF: not stored)
+                if (flive && q == 0) {
+                    float R[D][D], cv[D];
+                    node_frame_vel<D>(vz, R, cv);
+                    float* ni = ninfo + fnode * 24;
+#pragma unroll
+                    for (int d = 0; d < D; ++d) {
+                        ni[NI::P + d] = pz[d]; ni[NI::V + d] = vz[d]; ni[NI::CV + d] = cv[d];
+#pragma unroll
+                        for (int e = 0; e < D; ++e) ni[NI::R + d * D + e] = R[d][e];
+                    }
+                }
+                FUSED_PSTAMP_W(FUSED_FRAME_WAVE0, 6, vz[0]);
+            }
             // rows of unused node slots are zero
             for (int idx = tid - 64 * vtiles; idx < (FUSED_MAX_NODES - n) * (H / 4); idx += THREADS - 64 * vtiles)
                 st4(xbuf + (n + (idx >> 4)) * LDW + (idx & 15) * 4, f32x4{0.f, 0.f, 0.f, 0.f});
@@ -526,6 +582,52 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         lds_barrier();
     }
     FUSED_STAMP(2);
+
+    // ---------------------------------------------------------------- x0 (12 waves), beside P2's feature build
+    // x0 = W_res[:, D:] [cv | cf] + b (locs.py:214-218), own nodes only: wave FUSED_X0_WAVE0 + mb computes rows 16 mb .. + 15
+    // for every visible node tile that holds own nodes -- the field wave's two MFMAs per accumulator in its k order, on
+    // the same operands.  The rows are published by P2's barriers, three barriers before step 1 of layer 1 reads them.
+    if constexpr (FRAMES) {
+        // (loaded in P1's else branch, read in a branch on the wave index: named here so that the compiler's wait for
+        // them stands behind the vmcnt(0) above and not in the layer loop, see f_ea below)
+        asm volatile("" :: "v"(x0_acc), "v"(x0_ar));
+        const int mb = __builtin_amdgcn_readfirstlane(fused_x0_rowblock(wave));
+        if (mb >= 0 && mb < FUSED_X0_WAVES) {
+            FUSED_PSTAMP_W(FUSED_X0_WAVE0, 7, x0_acc[0]);
+            const float ar[2] = {(mb & 1) ? x0_ar[0] : x0_ar[2], (mb & 1) ? x0_ar[1] : x0_ar[3]};
+            const int vtiles = (nv + 15) >> 4;
+            for (int t = 0; t < vtiles; ++t) {
+                const int lo = 16 * t > off ? 16 * t : off, hi = 16 * t + 16 < off + n ? 16 * t + 16 : off + n;
+                if (lo >= hi) continue;                        // no own node in this tile
+                const int node = 16 * t + i;
+                const bool live = node < nv;
+                const float* ni = ninfo + (live ? node : 0) * 24;
+                float rec[2 * D];                                  // [cv | cf]
+#pragma unroll
+                for (int d = 0; d < D; ++d) rec[d] = ni[NI::CV + d];
+                {
+                    float Rl[D * D], fl[D];
+#pragma unroll
+                    for (int d = 0; d < D; ++d) fl[d] = ni[NI::F + d];
+#pragma unroll
+                    for (int d = 0; d < D * D; ++d) Rl[d] = ni[NI::R + d];
+                    node_frame_force<D>(Rl, fl, rec + D);
+                }
+                f32x4 acc = x0_acc;
+#pragma unroll
+                for (int s4 = 0; s4 < 2; ++s4) {
+                    const int k = 4 * s4 + q;
+                    float rk = 0.0f;
+#pragma unroll
+                    for (int kk = 4 * s4; kk < 4 * s4 + 4 && kk < 2 * D; ++kk) rk = (live && k == kk) ? rec[kk] : rk;
+                    acc = mfma16(ar[s4], rk, acc);
+                }
+                const int own = node - off;
+                if (own >= 0 && own < n) st4(xbuf + own * LDW + 16 * mb + 4 * q, acc);
+            }
+            FUSED_PSTAMP_W(FUSED_X0_WAVE0, 8, x0_acc[0]);
+        }
+    }
 
     // ---------------------------------------------------------------- P2: edge features -> B operands
     // Wave w owns tiles {w, w+NW, ..}.  Per tile, 16 lanes each build the features of one edge into
@@ -553,6 +655,9 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                     float njl[NI::STRIDE], nrl[NI::STRIDE];
 #pragma unroll
                     for (int t = 0; t < NI::STRIDE; ++t) { njl[t] = nj[t]; nrl[t] = nr[t]; }
+                    // FRAMES: the record's CF words were not written (LDS keeps the previous launch's): cf = R^T f of the
+                    // receiver from the copy; the sender's are not read
+                    if constexpr (FRAMES) node_frame_force<D>(nrl + NI::R, nrl + NI::F, nrl + NI::CF);
                     float eal[2];
                     if (dbg.step.qattr) {          // main.py:243-246: [q_i q_j, sqrt(sum((x_i - x_j)^2))]
                         float d2 = 0.0f;

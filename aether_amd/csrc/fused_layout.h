@@ -15,6 +15,16 @@ constexpr int LDU = 2 * H + 8;               // padded LDS row for the 128-wide 
 constexpr int FUSED_PACK_WAVES = 4, FUSED_PACK_LANES = 48;
 __device__ __host__ constexpr int fused_packed_edge(int wave, int lane) { return FUSED_PACK_LANES * wave + lane; }
 static_assert(FUSED_PACK_WAVES * FUSED_PACK_LANES == 12 * 16 && FUSED_PACK_LANES % 16 == 0, "every row of the twelve tiles has one builder");
+// 12-wave kernels, wave roles of the prologue behind the field waves (waves 0, 1: visible node tiles 0, 1):
+//   * wave FUSED_FRAME_WAVE0 + t builds the frames of visible node tile t (R and cv need the velocity alone) while the
+//     field wave of that tile runs the field net;
+//   * behind the P1 barrier wave FUSED_X0_WAVE0 + mb computes rows 16 mb .. 16 mb + 15 of x0 for every visible node tile
+//     that holds own nodes (four row blocks = the 64 rows), while waves 0-3 build the layer-1 features.
+constexpr int FUSED_FRAME_WAVE0 = 2, FUSED_X0_WAVE0 = 4, FUSED_X0_WAVES = 4;
+__device__ __host__ constexpr int fused_frame_tile(int wave) { return wave - FUSED_FRAME_WAVE0; }       // (a frame wave when 0 <= tile < vtiles)
+__device__ __host__ constexpr int fused_x0_rowblock(int wave) { return wave - FUSED_X0_WAVE0; }        // (an x0 wave when 0 <= block < 4)
+static_assert(FUSED_FRAME_WAVE0 >= FUSED_MAX_NODES / 16 && FUSED_FRAME_WAVE0 + FUSED_MAX_NODES / 16 <= 12 && FUSED_X0_WAVE0 + FUSED_X0_WAVES <= 12 &&
+              FUSED_X0_WAVES * 16 == H, "frame waves behind the field waves, one x0 wave per 16 of the H rows");
 
 // The edge MLP's two 64 x 64 contractions run as three fp16 MFMA terms on operands split into two fp16 pieces (common.h,
 // gemm_split); the weight images (2 x 8 KB each instead of 18 KB of padded fp32) fit every variant since the layer-1 features of the
@@ -107,6 +117,16 @@ constexpr int FI_ZC = 72;                                // [6 s][3 c]    field_
 constexpr int FI_AR = 90;                                // [4 mb][2 s]   l1_res_w[16 mb + i][D + 4s + q], 4s + q < 2D
 constexpr int FI_END = 98;
 constexpr int FUSED_FIMG_CHUNKS = (FI_END + 3) / 4;      // 25
+// 12-wave kernels: x0 is computed behind the P1 barrier by the x0 waves (FUSED_X0_WAVE0 + mb), each of which loads the two
+// chunks of its row block -- FI_ACC0 / 4 + mb and the chunk of slots FI_AR + 2 mb, FI_AR + 2 mb + 1 (elements 2, 3 of it for an
+// even mb, 0, 1 for an odd one).  The field wave loads the chunks that hold a slot of the field net: 19 of the 25.
+static_assert(FI_ACC0 % 4 == 0 && FI_AR % 4 == 2, "an x0 wave's operands: one whole chunk and half of another");
+__device__ __host__ constexpr bool fused_fimg_x0_slot(int s) { return (s >= FI_ACC0 && s < FI_A1) || (s >= FI_AR && s < FI_END); }
+__device__ __host__ constexpr bool fused_fimg_field_chunk(int c) {
+    for (int r = 0; r < 4; ++r)
+        if (4 * c + r < FI_END && !fused_fimg_x0_slot(4 * c + r)) return true;
+    return false;
+}
 constexpr int FUSED_FIMG = FUSED_FIMG_CHUNKS * 256;      // floats (25 KiB)
 constexpr int FUSED_WIMG_SPLIT = 8 * FUSED_WIMG + 4 * FUSED_NIMG_LAYER + 4 * FUSED_CBLK;   // the split images and constants blocks (layer 1's image A uses half of its slot)
 constexpr int FUSED_WIMG_SET = FUSED_WIMG_SPLIT + FUSED_FIMG;   // floats reserved

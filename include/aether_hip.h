@@ -224,6 +224,14 @@ int aether_debug_split(const float* x, int n_tiles, uint16_t* hi, uint16_t* lo, 
 int aether_debug_fused_packed_edge(int wave, int lane);
 
 /*
+ * Test hook of the 12-wave fused kernels' wave roles behind the field waves (csrc/fused_layout.h), wave in 0 .. 11:
+ *   what 0  the visible node tile whose frames the wave builds (fused_frame_tile), or -1;
+ *   what 1  the 16-row block of x0 the wave computes behind the prologue's barrier (fused_x0_rowblock), or -1.
+ * Host only: needs no GPU.
+ */
+int aether_debug_fused_wave_role(int what, int wave);
+
+/*
  * Dynamic-field variant of the state2state model: DynamicFieldAether.forward
  * (nn/state2state/dynamic_field_aether.py:79-100) = aether_dynamic_field (LatentFieldNetwork, :31-48:
  * attention-pooled graph summary + FiLM field net, hidden 32) followed by aether_forward_field, i.e.

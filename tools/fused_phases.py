@@ -57,15 +57,29 @@ for k in order:
     prev = med[k]
 clk = np.median(st[:, 41] / st[:, 40])
 print(f"  shader clock during the kernel: {clk:.0f} MHz (s_memtime cycles / wall us)")
-pv = med[400:405]                 # FUSED_PSTAMP: the field wave (wave 0) inside "field+frames+x0", cycles since entry
-if pv[4] > 0:
-    us = lambda c: c / clk
+pv = med[400:409]                 # FUSED_PSTAMP: the field wave (wave 0) inside "field+frames+x0", cycles since entry
+us = lambda c: c / clk
+if pv[4] > 0:                     # 8-wave kernels: the field wave builds the frame and x0 itself
     print("  field wave (wave 0), cycles since kernel entry (microseconds at the shader clock):")
     for name, t0, t1 in (("entry -> first vector load issued", 0.0, pv[0]), ("-> vmcnt(0) passed", pv[0], pv[1]),
                          ("-> last MFMA of the field net", pv[1], pv[2]), ("-> frame stored", pv[2], pv[3]),
                          ("-> x0 stored", pv[3], pv[4])):
         print(f"   {name:36s} t={t1:7.0f}  d={t1 - t0:6.0f}  ({us(t1 - t0):5.2f} us)")
     print(f"   -> barrier behind P1 (thread 0)      t={med[2] * clk:7.0f}  d={med[2] * clk - pv[4]:6.0f}  ({med[2] - us(pv[4]):5.2f} us)")
+elif pv[3] > 0:                   # 12-wave kernels: force alone; frames on wave 2 (FUSED_PSTAMP_W 5, 6), x0 on wave 4 (7, 8)
+    print("  field wave (wave 0), cycles since kernel entry (microseconds at the shader clock):")
+    for name, t0, t1 in (("entry -> first vector load issued", 0.0, pv[0]), ("-> vmcnt(0) passed", pv[0], pv[1]),
+                         ("-> last MFMA of the field net", pv[1], pv[2]), ("-> force stored", pv[2], pv[3])):
+        print(f"   {name:36s} t={t1:7.0f}  d={t1 - t0:6.0f}  ({us(t1 - t0):5.2f} us)")
+    print(f"   -> barrier behind P1 (thread 0)      t={med[2] * clk:7.0f}  d={med[2] * clk - pv[3]:6.0f}  ({med[2] - us(pv[3]):5.2f} us)")
+    print("  frame wave of node tile 0 (wave 2), beside the field net:")
+    print(f"   entry -> x, vel landed               t={pv[5]:7.0f}  d={pv[5]:6.0f}  ({us(pv[5]):5.2f} us)")
+    print(f"   -> frames stored                     t={pv[6]:7.0f}  d={pv[6] - pv[5]:6.0f}  ({us(pv[6] - pv[5]):5.2f} us)"
+          f"   ({us(pv[3] - pv[6]):5.2f} us before the force)")
+    print("  x0 wave of row block 0 (wave 4), behind the P1 barrier, beside the feature build:")
+    print(f"   behind the barrier                   t={pv[7]:7.0f}")
+    print(f"   -> x0 rows stored                    t={pv[8]:7.0f}  d={pv[8] - pv[7]:6.0f}  ({us(pv[8] - pv[7]):5.2f} us)"
+          f"   (edge features, thread 0: {med[3] - med[2]:5.2f} us)")
 print("  layer-2 per-wave tile timeline, cycles since kernel entry (median over workgroups):")
 print("   wave round   start  wait rows  gemm1+silu1  gemm2+silu2+stage  sums   | total   [gemm1 | wait rows + receive | late add + silu1]")
 sums = []
