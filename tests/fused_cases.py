@@ -39,6 +39,16 @@ def uses_twelve_waves(info):
     return 9 <= tiles_of(info) <= 12 and info.max_group_nodes <= 16
 
 
+def fused_instance(info, keep, waves12=1, granules=1):
+    """The dispatch rule of fused_impl -> (NW, ROUNDS, KEEP, GRAN) of the k_fused instance a launch on this view runs.
+    Twelve waves: not keeping, 9 .. 12 tiles, every workgroup within one node tile; the hand-off as granules where the
+    view is split.  Otherwise eight waves with one, two or three rounds of edge tiles."""
+    tiles, keep = tiles_of(info), bool(keep)
+    if waves12 and not keep and 9 <= tiles <= 12 and info.max_group_nodes <= 16:
+        return (12, 1, False, bool(granules and (info.reserved & 1)))
+    return (8, 1 if tiles <= 8 else 2 if tiles <= 16 else 3, keep, False)
+
+
 def oracle_of(sd, inp, dtype=torch.float64, **kw):
     c = lambda t: t.to(dtype)
     with torch.no_grad():

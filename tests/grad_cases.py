@@ -149,18 +149,24 @@ def state_dict(family, D, H):
     return U.state_of(build(family, D, H))
 
 
-def _special_graph(name, seed):
-    """The graphs of test_gpu_fused_waits.py's cases of that name, under an input seed of this file's rule."""
+def _special_graph(name, seed, D=2):
+    """The graphs of test_gpu_fused_waits.py's cases of that name (2-D) and of tests/irregular_graphs.py, under an input
+    seed of this file's rule."""
+    import irregular_graphs as IG
     import test_gpu_fused_waits as W
+    if name in IG.GRAPHS:
+        return IG.build(name, D, seed)
+    assert D == 2, (name, D)
     return {"star_32": W._star, "isolated_n12": W._isolated}[name](seed)
 
 
 @functools.lru_cache(maxsize=None)
 def step_inputs(case):
-    """case = (family, D, H, B, N, input seed, dropout, graph); graph "full" or a case name of test_gpu_fused_waits.py.
+    """case = (family, D, H, B, N, input seed, dropout, graph); graph "full", a case name of test_gpu_fused_waits.py or a graph of
+    tests/irregular_graphs.py (B = 1, N = all its nodes).
     -> (inputs, the two dropout masks or None)."""
     family, D, H, B, N, seed, p, graph = case
-    inp = make_batch(B, N, D, seed=seed) if graph == "full" else _special_graph(graph, seed)
+    inp = make_batch(B, N, D, seed=seed) if graph == "full" else _special_graph(graph, seed, D)
     assert inp["x"].shape == (B * N, D)
     masks = None
     if p > 0:
@@ -248,6 +254,19 @@ AETHER_FUSED = [_a(3, 64, 2, 20), _a(2, 64, 4, 18), _a(2, 64, 1, 32, 8, graph="s
                 _a(2, 64, 2, 12, 5, graph="isolated_n12")]
 # streamed only: degree above 64 -- the row sums run as their own kernel
 AETHER_STREAMED = [_a(2, 64, 1, 70)]
+# the graphs of tests/irregular_graphs.py, B = 1 and N = all nodes.  k_fused_bwd: packed scenes of different sizes; with
+# `fused_split` off 11 tiles in one workgroup (the three-tiles-per-wave round) beside an edge-less group; split halves of
+# 11 tiles with the hand-off
+IRREGULAR_FUSED = [_a(3, 64, 1, 53, 5, graph="knn_mixed_k10"), _a(2, 64, 1, 16, 5, graph="multi16_E170"),
+                   _a(3, 64, 1, 60, 5, graph="knn_2x30_k11")]
+IRREGULAR_FUSED_SPLIT = {"knn_mixed_k10": 1, "multi16_E170": 0, "knn_2x30_k11": 1}          # the `fused_split` option
+# `fused_split` off: 19 tiles in one workgroup, more than k_fused_bwd takes -- the keeping k_fused, then the backward
+# layer by layer
+IRREGULAR_LAYERWISE = [_a(2, 64, 1, 32, 6, graph="multi32_hub40"), _a(3, 64, 1, 32, 5, graph="multi32_hub40")]
+# streamed: in-degree 86 on duplicated edges -- the row sums run as their own kernel
+IRREGULAR_STREAMED = [_a(2, 64, 1, 32, 6, graph="multi32_hub80")]
+IRREGULAR_STEP_CASES = IRREGULAR_FUSED + IRREGULAR_LAYERWISE + IRREGULAR_STREAMED
+FUSED_BWD_MAX_EDGES = 12 * 16                   # fused_backward_applies (csrc/aether_hip.hip): beyond, backward.h
 EDGE_ACC_CASE = _a(3, 64, 6, 7)
 EDGE_ACC_OPTIONS = (3, 0)                       # test_edge_level_weight_gradients_accumulated_in_the_edge_kernel
 # narrow (zero-padded to 64), wide (k_wgemm backwards) and padded wide
@@ -257,7 +276,7 @@ DROPOUT_CASE = _a(3, 64, 6, 7, p=0.1)
 _OTHER_SEEDS = {("LoCS", 3, 5): 7}
 OTHER_CASES = [_a(D, 64, 2, N, _OTHER_SEEDS.get((f, D, N), 5), family=f) for f in ("LoCS", "DynamicFieldAether")
                for D in (2, 3) for N in (5, 20)]
-STEP_CASES = AETHER_BOTH + AETHER_FUSED + AETHER_STREAMED + AETHER_WIDTHS + [DROPOUT_CASE] + OTHER_CASES
+STEP_CASES = AETHER_BOTH + AETHER_FUSED + AETHER_STREAMED + AETHER_WIDTHS + [DROPOUT_CASE] + OTHER_CASES + IRREGULAR_STEP_CASES
 TEETH_CASE = AETHER_BOTH[0]
 
 

@@ -40,10 +40,11 @@ def _model(case, path, sd=None):
     return m
 
 
-def _step(m, case, inp, masks):
-    """One forward / backward of MSELoss on the device -> {parameter | d/dx | d/dvel | d/dedge_attr: gradient}."""
+def _step(m, case, inp, masks, g=None):
+    """One forward / backward of MSELoss on the device -> {parameter | d/dx | d/dvel | d/dedge_attr: gradient}.  `g`: the
+    inputs on the device, where the caller has them already."""
     family, N = case[0], case[4]
-    g = U.to_cuda(inp)
+    g = U.to_cuda(inp) if g is None else g
     if masks is not None:
         m.train()
         m._dropout_masks = masks.cuda()
@@ -63,10 +64,30 @@ def _step(m, case, inp, masks):
     return got
 
 
-def _check_step(case, path, tag=""):
+def _check_step(case, path, tag="", prepare=None):
+    """`prepare(m, inputs) -> inputs on the device`: called before the step, e.g. to build the graph view under an option."""
     r = G.step_case(case)
-    got = _step(_model(case, path), case, r["inp"], r["masks"])
+    m = _model(case, path)
+    g = None if prepare is None else prepare(m, r["inp"])
+    got = _step(m, case, r["inp"], r["masks"], g)
     return check_grads(f"{G.case_id(case)} {path}{tag}", got, r["g32"], r["g64"])
+
+
+def _view_under(split, expect):
+    """-> prepare(m, inp): builds the model's graph view with `fused_split` = split on the index tensors the step then
+    runs on (it finds the view in the module's cache under these tensors) and asserts `expect(info)`."""
+    def prepare(m, inp):
+        g = U.to_cuda(inp)
+        try:
+            _set_option(b"fused_split", split)
+            info = m.prepare_graph(g["edges"], inp["x"].shape[0])[1]
+        finally:
+            _set_option(b"fused_split", 1)
+        assert info.n_groups > 0 and bool(info.reserved & 1) == bool(split), (info.n_groups, info.reserved)
+        assert expect(info), (info.n_groups, info.max_group_nodes, info.max_group_edges, info.reserved)
+        assert m.prepare_graph(g["edges"], inp["x"].shape[0])[1] is info
+        return g
+    return prepare
 
 
 def _ids(cases):
@@ -84,6 +105,31 @@ def test_aether_fused(case):
 def test_aether_streamed(case):
     """kb_node, kb_edge, kb_edge_acc8, kb_gather, kb_sum_g, k_outer + k_reduce_both; N = 70: degree above 64, the row sums
     run as their own kernel."""
+    _check_step(case, "streamed")
+
+
+@pytest.mark.parametrize("case", G.IRREGULAR_FUSED, ids=_ids(G.IRREGULAR_FUSED))
+def test_aether_fused_on_irregular_graphs(case):
+    """k_fused<KEEP> + k_fused_bwd on the graphs of tests/irregular_graphs.py: packed kNN scenes of 2 .. 12 nodes; 11 edge
+    tiles in one workgroup (three tiles per wave) with a hub of in-degree 28, duplicated edges and an edge-less group;
+    split halves of 11 tiles, the last one partial, with the hand-off."""
+    split = G.IRREGULAR_FUSED_SPLIT[case[7]]
+    tiles = {"knn_mixed_k10": lambda t: t <= 8, "multi16_E170": lambda t: t == 11, "knn_2x30_k11": lambda t: t == 11}[case[7]]
+    fused_bwd = lambda info: info.max_group_edges <= G.FUSED_BWD_MAX_EDGES and tiles((info.max_group_edges + 15) // 16)
+    _check_step(case, "fused", f" fused_split={split}", _view_under(split, fused_bwd))
+
+
+@pytest.mark.parametrize("case", G.IRREGULAR_LAYERWISE, ids=_ids(G.IRREGULAR_LAYERWISE))
+def test_aether_fused_forward_and_layerwise_backward_on_an_irregular_graph(case):
+    """multi32_hub40 with `fused_split` off: 300 edges in one workgroup, more than 12 tiles, so `fused_backward_applies`
+    is false -- k_fused<D, 8, 3, KEEP> and the layer-by-layer backward behind it."""
+    layerwise = lambda info: info.max_group_edges > G.FUSED_BWD_MAX_EDGES
+    _check_step(case, "fused", " fused_split=0", _view_under(0, layerwise))
+
+
+@pytest.mark.parametrize("case", G.IRREGULAR_STREAMED, ids=_ids(G.IRREGULAR_STREAMED))
+def test_aether_streamed_on_an_irregular_graph(case):
+    """multi32_hub80: in-degree 86 on duplicated edges, the row sums as their own kernel."""
     _check_step(case, "streamed")
 
 

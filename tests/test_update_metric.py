@@ -10,12 +10,15 @@ Per case: (a) the full three-term arithmetic passes FACTOR x the fp32 restatemen
 fails it, (c) every degraded variant passes scale_rel_err <= 1e-5, which is why test_gpu_update_parity.py exists.
 (b) is a condition on the inputs (seeds below), not on any kernel.
 
-The second half holds the inputs of tests/test_gpu_update_parity.py to the rule their seeds were chosen by, on this
-machine's CPU: a floor that is not a lucky draw, a bar the design's arithmetic meets, Gumbel samples away from a tie."""
+The second half holds the inputs of tests/test_gpu_update_parity.py and tests/test_gpu_fused_irregular.py to the rule
+their seeds were chosen by, on this machine's CPU: a floor that is not a lucky draw, a bar the design's arithmetic meets,
+Gumbel samples away from a tie; the graphs of tests/irregular_graphs.py to the structure they are there for, and the
+update bar to its teeth on one of them."""
 import pytest
 import torch
 
 from conftest import scale_rel_err
+import irregular_graphs as IG
 import update_cases as U
 import update_s2s_cases as S2S
 from update_cases import split_linears
@@ -85,7 +88,7 @@ def test_hi_only_weights_fail_the_update_bar_and_pass_the_position_bar(case):
 
 
 # ---- the cases of tests/test_gpu_update_parity.py, without a GPU -----------------------------------------------------------
-@pytest.mark.parametrize("fc", U.FORWARD_CASES, ids=U.case_id)
+@pytest.mark.parametrize("fc", U.FORWARD_CASES + U.IRREGULAR_CASES, ids=U.case_id)
 def test_gpu_forward_case_has_a_typical_floor_and_a_bar_the_design_meets(fc):
     name, case = fc
     x, want64, want32 = U.references(name, case)
@@ -98,7 +101,7 @@ def test_gpu_forward_case_has_a_typical_floor_and_a_bar_the_design_meets(fc):
         assert err <= FACTOR * floor, (err, floor)
 
 
-@pytest.mark.parametrize("fc", U.ROLLOUT_CASES, ids=U.case_id)
+@pytest.mark.parametrize("fc", U.ROLLOUT_CASES + U.IRREGULAR_ROLLOUT_CASES, ids=U.case_id)
 def test_gpu_rollout_case_has_a_typical_floor_at_every_step(fc):
     name, case = fc
     x, want64, want32 = U.references(name, case, U.ROLLOUT_STEPS)
@@ -106,6 +109,54 @@ def test_gpu_rollout_case_has_a_typical_floor_at_every_step(fc):
     floors = [update_floor(want32[t], prev[t], want64[t]) for t in range(U.ROLLOUT_STEPS)]
     print(f"{U.case_id(fc)}: floors " + " ".join(f"{f:.2e}" for f in floors))
     assert torch.isfinite(want64).all() and min(floors) >= U.TYPICAL, floors
+
+
+# ---- the graphs of tests/irregular_graphs.py (tests/test_gpu_fused_irregular.py) ----------------------------------------------
+@pytest.mark.parametrize("D", [2, 3])
+@pytest.mark.parametrize("name", list(IG.GRAPHS))
+def test_irregular_graphs_have_their_structure(name, D):
+    """From the edge list alone, at the seed the case runs under."""
+    want = IG.structure(name)
+    inp = IG.build(name, D, U.IRREGULAR_SEEDS[(name, D)])
+    send, recv = inp["edges"]
+    n = inp["x"].shape[0]
+    assert inp["x"].shape == (n, D) and send.dtype == recv.dtype == torch.int64
+    assert (n, send.numel(), recv.numel()) == (want["nodes"], want["edges"], want["edges"])
+    assert inp["edge_attr"].shape == (want["edges"], 2)
+    assert int(send.min()) >= 0 and int(recv.min()) >= 0 and int(send.max()) < n and int(recv.max()) < n
+    indeg = torch.bincount(recv, minlength=n)
+    assert int(indeg.max()) == want["max_in"] and want["max_in"] >= want["max_in_above"] + 1, int(indeg.max())
+    assert int((indeg == 0).sum()) == want["no_in"]
+    assert not bool((send == recv).any())
+    pairs = send * n + recv
+    assert (pairs.unique().numel() < pairs.numel()) == want["duplicates"]
+    assert IG.components(send, recv, n) == want["components"]
+    if want["duplicates"]:                          # the multigraphs: the last two nodes have no edge at all
+        assert int(torch.bincount(send, minlength=n)[-2:].sum()) == 0 and int(indeg[-3:].sum()) == 0
+        assert int(indeg[0]) == want["max_in"]
+    else:                                           # the kNN scenes: every node receives min(k, n - 1) edges, in its scene
+        sizes = torch.tensor(want["components"])
+        assert torch.equal(indeg, torch.minimum(sizes - 1, torch.tensor(want["max_in"])).repeat_interleave(sizes))
+    # not in receiver order: `perm` of the graph view is no identity
+    assert not torch.equal(recv, recv.sort().values)
+
+
+def test_one_dropped_term_on_an_irregular_graph_fails_the_update_bar_and_passes_the_position_bar():
+    """multi32_hub40 at D 3: `gnn.layer_2.message_fn.0` without one cross term, the rest of the three-term arithmetic."""
+    case = U.IRREGULAR_TEETH_CASE
+    family = U.FAMILIES["Aether-irregular"]
+    x, want64, want32 = U.references("Aether-irregular", case)
+    floor = update_floor(want32, x, want64)
+    sd = {k: U._cast(v, torch.float64) for k, v in U.state_of(family.build(case, "cpu")).items()}
+    inp = U._in_dtype(family.inputs(case), torch.float64)
+    for term in TERMS:
+        with torch.no_grad(), U.one_thread(), split_linears(drop=("gnn.layer_2.message_fn.0", term)):
+            out = family.restate(sd, inp, case)
+        got = x + (out - x.double()).float()
+        new, old = update_err(got, x, want64), scale_rel_err(got, want64)
+        print(f"{U.case_id(('Aether-irregular', case))} without {term}: old={old:.2e} new={new:.2e} new/floor={new / floor:.1f}")
+        assert new > FACTOR * floor, (term, new, floor)
+        assert old <= OLD_TOL, (term, old)
 
 
 @pytest.mark.parametrize("steps", [1, S2S.STEPS])

@@ -1,4 +1,4 @@
-"""The cases of tests/test_gpu_update_parity.py: per model family how to build the drop-in under a seed, its inputs, its
+"""The cases of tests/test_gpu_update_parity.py and tests/test_gpu_fused_irregular.py: per model family how to build the drop-in under a seed, its inputs, its
 CPU restatement in a dtype and the call on the device.  Test helper, not a test module.
 
 Everything a bar is taken against is computed here, on the CPU: `references(family, case)` gives the input positions
@@ -134,6 +134,16 @@ class AetherFamily:
         return O.rollout(sd, inp["x"], inp["vel"], inp["edges"], inp["charges"], steps)
 
 
+class IrregularFamily(AetherFamily):
+    """Aether on a graph of tests/irregular_graphs.py: case = (D, 64, 1, graph name, model seed, input seed)."""
+    name = "Aether-irregular"
+
+    @staticmethod
+    def inputs(case):
+        import irregular_graphs as IG
+        return IG.build(case[3], case[0], case[5])
+
+
 class LocsFamily(AetherFamily):
     name = "LoCS"
 
@@ -223,12 +233,12 @@ class GnnFamily:
         return torch.stack(traj)
 
 
-AETHER, LOCS, DYNFIELD = AetherFamily, LocsFamily, DynFieldFamily
+AETHER, LOCS, DYNFIELD, IRREGULAR = AetherFamily, LocsFamily, DynFieldFamily, IrregularFamily
 EGNN = GnnFamily(Egnn, "egnn_aether", norm_diff=True)
 CLOF = GnnFamily(Clof, "clof", norm_diff=True)
 CLOF_VEL = GnnFamily(Clof, "clof_vel", norm_diff=True)
 CLOF_VEL_GBF = GnnFamily(Clof, "clof_vel_gbf", norm_diff=True)
-FAMILIES = {f.name: f for f in (AETHER, LOCS, DYNFIELD, EGNN, CLOF, CLOF_VEL, CLOF_VEL_GBF)}
+FAMILIES = {f.name: f for f in (AETHER, LOCS, DYNFIELD, IRREGULAR, EGNN, CLOF, CLOF_VEL, CLOF_VEL_GBF)}
 
 
 def _in_dtype(inp, dtype):
@@ -254,7 +264,7 @@ def references(family_name, case, steps=0):
     return references_from(family, case, state_of(family.build(case, "cpu")), steps)
 
 
-SPLIT_FAMILIES = ("Aether", "LoCS", "DynamicFieldAether")       # their restatements go through the oracle's `gnn.*` Linears
+SPLIT_FAMILIES = ("Aether", "LoCS", "DynamicFieldAether", "Aether-irregular")       # their restatements go through the oracle's `gnn.*` Linears
 
 
 @functools.lru_cache(maxsize=None)
@@ -289,6 +299,24 @@ ROLLOUT_STEPS = 5
 ROLLOUT_CASES = [("Aether", (2, 64, 2, 5, MODEL_SEED, 5)), ("LoCS", (2, 64, 2, 5, MODEL_SEED, 7)),
                  ("EGNN_vel_Aether", ("egnn_aether", 4, 2, 5, MODEL_SEED, 25)),
                  ("ClofNet_vel", ("clof_vel", 4, 2, 5, MODEL_SEED, 25))]
+# Aether on the graphs of tests/irregular_graphs.py (tests/test_gpu_fused_irregular.py), (graph, D) -> input seed under
+# the rule above; the topology of a named graph does not depend on it
+IRREGULAR_SEEDS = {("knn_mixed_k4", 2): 6, ("knn_mixed_k4", 3): 6, ("knn_mixed_k10", 2): 5, ("knn_mixed_k10", 3): 5,
+                   ("knn_2x24_k7", 2): 6, ("knn_2x24_k7", 3): 5, ("knn_2x30_k11", 2): 5, ("knn_2x30_k11", 3): 5,
+                   ("knn_32_k10", 2): 5, ("knn_32_k10", 3): 6, ("knn_2x32_k12", 2): 6, ("knn_2x32_k12", 3): 5,
+                   ("multi32_hub40", 2): 5, ("multi32_hub40", 3): 6, ("multi32_hub80", 2): 5, ("multi32_hub80", 3): 7,
+                   ("multi16_E170", 2): 6, ("multi16_E170", 3): 5, ("multi16_E250", 2): 5, ("multi16_E250", 3): 5}
+
+
+def irregular_case(graph, D):
+    return (D, 64, 1, graph, MODEL_SEED, IRREGULAR_SEEDS[(graph, D)])
+
+
+IRREGULAR_CASES = [("Aether-irregular", irregular_case(g, D)) for (g, D) in IRREGULAR_SEEDS]
+# five steps on a shuffled edge list with packed scenes, and on one with duplicated edges and an edge-less group
+IRREGULAR_ROLLOUT_CASES = [("Aether-irregular", irregular_case("knn_mixed_k10", 2)),
+                           ("Aether-irregular", irregular_case("multi16_E250", 3))]
+IRREGULAR_TEETH_CASE = irregular_case("multi32_hub40", 3)
 FORWARD_CASES = ([("Aether", c) for c in AETHER_64 + AETHER_NARROW + AETHER_WIDE] + [("LoCS", c) for c in LOCS_CASES] +
                  [("DynamicFieldAether", c) for c in DYNFIELD_CASES] + GNN_CASES)
 
@@ -297,4 +325,6 @@ def case_id(fc):
     name, c = fc
     if isinstance(c[0], str):
         return f"{name}-L{c[1]}-B{c[2]}N{c[3]}-s{c[5]}"
+    if isinstance(c[3], str):
+        return f"{name}-D{c[0]}-{c[3]}-s{c[5]}"
     return f"{name}-D{c[0]}-H{c[1]}-B{c[2]}N{c[3]}-s{c[5]}"
