@@ -60,6 +60,24 @@ class AetherGraphInfo(C.Structure):
                 ("max_group_nodes", C.c_int32), ("max_group_edges", C.c_int32), ("reserved", C.c_int32)]
 
 
+S2S_LAUNCH_KINDS = ("k_s2s_linear_jobs", "k_s2s_gemm_split<1>", "k_s2s_gemm_split<2>", "k_s2s_gemm_split_r1<1>",
+                    "k_s2s_gemm_split_r1<2>")
+S2S_LAUNCH_LOG = 96
+
+
+class AetherS2SLaunchRecord(C.Structure):
+    """include/aether_hip.h: one dense-layer table of a seq2seq step, as the host launched it."""
+    _fields_ = [(f, C.c_int32) for f in ("kind", "jobs", "images", "M", "K", "K2", "wgs", "reserved")] + \
+               [(f, C.c_int64) for f in ("N", "min_n", "tiles64", "wg128")]
+
+
+class AetherS2SLaunchStats(C.Structure):
+    """include/aether_hip.h: aether_s2s_launch_stats (test hook; host integers, nothing under graph replay)."""
+    _fields_ = [(f, C.c_int64 * len(S2S_LAUNCH_KINDS)) for f in ("launches", "jobs", "max_n", "max_m", "max_k", "max_k2")] + \
+               [(f, C.c_int64) for f in ("filter_one", "filter_many", "filter_max_splits", "logged")] + \
+               [("log", AetherS2SLaunchRecord * S2S_LAUNCH_LOG)]
+
+
 class AetherDynScenePack(C.Structure):                 # host view of a scene pack: device pointers + per-step strides
     _fields_ = [("node_inds", C.c_void_p), ("graph_send", C.c_void_p), ("graph_recv", C.c_void_p),
                 ("edge2node", C.c_void_p), ("node_stride", C.c_int64), ("edge_stride", C.c_int64)]
@@ -258,6 +276,8 @@ SIGNATURES = {
     "aether_debug_fetch": (C.c_int64, [C.c_char_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "aether_debug_split": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    "aether_s2s_launch_stats": (C.c_int, [C.POINTER(AetherS2SLaunchStats)]),
+    "aether_s2s_launch_stats_reset": (None, []),
     "aether_debug_fused_packed_edge": (C.c_int, [C.c_int, C.c_int]),
     "aether_debug_fused_wave_role": (C.c_int, [C.c_int, C.c_int]),
     "aether_workspace_bytes_h": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int]),

@@ -301,6 +301,12 @@ int g_linear_kwaves = 4;                        // aether_set_option("linear_kwa
 int g_gemm_split = 1;                           // aether_set_option("gemm_split", 0 | 1 | 2 | 3): fp16 x 2 GEMM for the >= 128-workgroup layers of the fused seq2seq step (2 / 3: force a kernel structure)
 constexpr int FILTER_WGS = 256;                 // workgroups of k_s2s_filter_split: one per CU
 int g_filter_splits = 0;                        // aether_set_option("filter_splits", n): k-splits of the filter GEMM, 0 = by balance
+AetherS2SLaunchStats g_s2s_stats = {};          // aether_s2s_launch_stats: what s2s_launch_jobs and the filter launches chose (host only)
+
+void s2s_stats_filter(int splits) {
+    if (splits > 1) ++g_s2s_stats.filter_many; else ++g_s2s_stats.filter_one;
+    if (splits > g_s2s_stats.filter_max_splits) g_s2s_stats.filter_max_splits = splits;
+}
 
 
 struct WsLayout {
@@ -1682,6 +1688,14 @@ int aether_debug_split(const float* x, int n_tiles, uint16_t* hi, uint16_t* lo, 
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }
+
+int aether_s2s_launch_stats(AetherS2SLaunchStats* stats) {
+    if (!stats) return fail(AETHER_EINVAL, "s2s_launch_stats: null pointer");
+    *stats = g_s2s_stats;
+    return AETHER_OK;
+}
+
+void aether_s2s_launch_stats_reset(void) { g_s2s_stats = AetherS2SLaunchStats{}; }
 
 int aether_debug_fused_packed_edge(int wave, int lane) {
     if (wave < 0 || wave >= FUSED_PACK_WAVES || lane < 0 || lane >= FUSED_PACK_LANES) return -1;

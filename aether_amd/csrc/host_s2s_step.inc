@@ -131,6 +131,30 @@ bool s2s_jobs_take_split(const S2SJobs& T) {
     return true;
 }
 
+// One table's launch into the record of aether_s2s_launch_stats (kind: see include/aether_hip.h)
+void s2s_stats_jobs(const S2SJobs& T, int kind, int64_t wg128, int wgs) {
+    AetherS2SLaunchStats& G = g_s2s_stats;
+    AetherS2SLaunchRecord r{};
+    int best = 0;
+    r.kind = kind; r.jobs = T.n; r.images = 1; r.wgs = wgs; r.wg128 = wg128; r.min_n = T.j[0].N;
+    for (int t = 0; t < T.n; ++t) {
+        const S2SJob& J = T.j[t];
+        if (J.N * J.M > T.j[best].N * T.j[best].M) best = t;
+        if (J.N < r.min_n) r.min_n = J.N;
+        r.tiles64 += ((J.N + 63) / 64) * ((J.M + 127) / 128);
+        if (!(J.Wimg != nullptr && J.M % 128 == 0 && J.K % 32 == 0 && (J.W2 == nullptr || (J.W2img != nullptr && J.K2 % 32 == 0)) &&
+              (J.g1 == nullptr || J.g2 != nullptr))) r.images = 0;
+        if (J.N > G.max_n[kind]) G.max_n[kind] = J.N;
+        if (J.M > G.max_m[kind]) G.max_m[kind] = J.M;
+        if (J.K > G.max_k[kind]) G.max_k[kind] = J.K;
+        if (J.W2 != nullptr && J.K2 > G.max_k2[kind]) G.max_k2[kind] = J.K2;
+    }
+    r.N = T.j[best].N; r.M = T.j[best].M; r.K = T.j[best].K; r.K2 = T.j[best].W2 != nullptr ? T.j[best].K2 : 0;
+    ++G.launches[kind]; G.jobs[kind] += T.n;
+    if (G.logged < AETHER_S2S_LAUNCH_LOG) G.log[G.logged] = r;
+    ++G.logged;
+}
+
 int s2s_launch_jobs(S2SJobs& T, hipStream_t st) {
     if (T.n <= 0) return AETHER_OK;
     for (int t = 0; t < T.n; ++t) {
@@ -184,8 +208,10 @@ int s2s_launch_jobs(S2SJobs& T, hipStream_t st) {
             // aether_set_option("gemm_split", 2 | 3) forces the second / the first.
             if (g_gemm_split == 2 || (g_gemm_split != 3 && wgs > 256)) {
                 const size_t lds = (size_t)GS1_NST * GS_STAGE * 16;
+                s2s_stats_jobs(T, rows == 128 ? 4 : 3, wg128, wgs);
                 if (rows == 128) S2S_GS_LAUNCH(k_s2s_gemm_split_r1, 2, lds); else S2S_GS_LAUNCH(k_s2s_gemm_split_r1, 1, lds);
             } else {
+                s2s_stats_jobs(T, rows == 128 ? 2 : 1, wg128, wgs);
                 if (rows == 128) S2S_GS_LAUNCH(k_s2s_gemm_split, 2, gs_lds_bytes(2)); else S2S_GS_LAUNCH(k_s2s_gemm_split, 1, gs_lds_bytes(1));
             }
 #undef S2S_GS_LAUNCH
@@ -203,6 +229,7 @@ int s2s_launch_jobs(S2SJobs& T, hipStream_t st) {
         wg += (int)(gx * gy);
     }
     if (wg == 0) return AETHER_OK;
+    s2s_stats_jobs(T, 0, 0, wg);
     bool two = false;
     for (int t = 0; t < T.n; ++t) two = two || T.j[t].W2 != nullptr;
 #define S2S_JOBS(MT, NT, KW)                                                                            \
@@ -384,6 +411,7 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
         const int64_t units = ((E + 255) / 256) * (he / 64) * L.splits;
         const dim3 grid((unsigned)(units < FILTER_WGS ? units : FILTER_WGS));
         float* dst = L.splits > 1 ? wp(L.fpart) : wp(L.eaf);
+        s2s_stats_filter(L.splits);
 #define FILT_LAUNCH(RR)                                                                                                  \
     do {                                                                                                                 \
         const size_t lds = filt_lds_bytes(RR);                                                                           \

@@ -307,6 +307,7 @@ int s2s_prior_features(const AetherS2SPriorParams* p, int D, int h, int polar, i
         const int64_t units = ((E + 255) / 256) * (h / 64) * L.splits;
         const dim3 grid((unsigned)(units < FILTER_WGS ? units : FILTER_WGS));
         float* dst = L.splits > 1 ? wp(L.fpart) : wp(L.eaf);
+        s2s_stats_filter(L.splits);
 #define FILT_LAUNCH(RR)                                                                                                  \
     do {                                                                                                                 \
         const size_t lds = filt_lds_bytes(RR);                                                                           \

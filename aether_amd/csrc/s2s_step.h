@@ -216,9 +216,15 @@ k_s2s_linear_jobs(const S2SJobs jobs) {
 // fp16's exponent range: every ROW of activations carries a power-of-two scale s that only ever shrinks while the K loop
 // runs -- the first k step sets it from the row's maximum (max -> 2^13..2^14), a later step whose scaled values would reach
 // 2^15 lowers it and multiplies the row's accumulators by the ratio (exact); the epilogue divides by the final s.  Every
-// value is thus represented to 2^-22 of the largest value its row has shown so far.  Weights are split as they are
-// (|w| < 65,504; a lo piece below |w| = 2^-3 is a subnormal: absolute error <= 2^-25).
+// value is thus represented to 2^-22 of the largest value its row has shown so far.  Weights are split times GS_WSCALE = 2^8,
+// which the bias takes on with the first row scale and the epilogue takes out again (exact; no instruction in front of the
+// first DMA: a multiply of the bias there cost 1.2 % of a step).  A lo piece is an fp16 subnormal below |w| GS_WSCALE = 2^-3,
+// with an absolute error of up to 2^-25 there, and a Linear's weights are all of +-1 / sqrt(K) = +-2^-4 or less: split as
+// they were, every weight of a 256- or 512-wide layer sat below that -- 2^-21 of the largest weight instead of 2^-22 of each,
+// seen as 4.6 x the fp32 restatement's error on rows with O(1) activations (tests/test_gpu_s2s_split_parity.py, n4035-rows).
+// With the scale the same holds only below |w| = 2^-11, at 2^-33 absolute; |w| must stay below 65,504 / 2^8 = 255.
 // gate_units > 0: image row 4 u + g is row g * gate_units + u of W (the four gates of an LSTM unit side by side)
+constexpr float GS_WSCALE = 256.0f;
 __global__ void __launch_bounds__(256)
 k_s2s_gemm_image(const float* __restrict__ W, int M, int K, int ldw, f16x8* __restrict__ img, int gate_units) {
     const int oct = K >> 3;
@@ -231,7 +237,7 @@ k_s2s_gemm_image(const float* __restrict__ W, int M, int K, int ldw, f16x8* __re
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         _Float16 a, b;
-        split_f16x2(j < 4 ? v0[j] : v1[j - 4], a, b);
+        split_f16x2((j < 4 ? v0[j] : v1[j - 4]) * GS_WSCALE, a, b);
         hi[j] = a; lo[j] = b;
     }
     const int a32 = o >> 2, q = o & 3, mb = m >> 4, i = m & 15;
@@ -389,7 +395,7 @@ k_s2s_gemm_split(const S2SJobs jobs) {
                 sh = sh > 40 ? 40 : (sh < -40 ? -40 : sh);
                 float ns = __int_as_float((127 + sh) << 23);
                 float ratio;
-                if (xs[nb] == 0.0f) ratio = ns;                   // first time: the accumulators hold the bias
+                if (xs[nb] == 0.0f) ratio = ns * GS_WSCALE;       // first time: the accumulators hold the bias (the sums come out times the images' scale)
                 else if (xm[nb] * xs[nb] >= 32768.0f) { ns = ns < xs[nb] ? ns : xs[nb]; ratio = ns / xs[nb]; }    // (powers of two: exact)
                 else { ns = xs[nb]; ratio = 1.0f; }
 #pragma unroll
@@ -481,7 +487,7 @@ k_s2s_gemm_split(const S2SJobs jobs) {
 #undef GS_XTIE
     float inv_xs[NB];
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) inv_xs[nb] = xs[nb] != 0.0f ? 1.0f / xs[nb] : 1.0f;      // (powers of two: exact)
+    for (int nb = 0; nb < NB; ++nb) inv_xs[nb] = xs[nb] != 0.0f ? 1.0f / (xs[nb] * GS_WSCALE) : 1.0f;      // (powers of two: exact)
     const int act = J.act;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
@@ -648,7 +654,7 @@ k_s2s_gemm_split_r1(const S2SJobs jobs) {
                 sh = sh > 40 ? 40 : (sh < -40 ? -40 : sh);
                 float ns = __int_as_float((127 + sh) << 23);
                 float ratio;
-                if (xs[nb] == 0.0f) ratio = ns;                   // first time: the accumulators hold the bias
+                if (xs[nb] == 0.0f) ratio = ns * GS_WSCALE;       // first time: the accumulators hold the bias (the sums come out times the images' scale)
                 else if (m[nb] * xs[nb] >= 32768.0f) { ns = ns < xs[nb] ? ns : xs[nb]; ratio = ns / xs[nb]; }    // (powers of two: exact)
                 else { ns = xs[nb]; ratio = 1.0f; }
 #pragma unroll
@@ -710,7 +716,7 @@ k_s2s_gemm_split_r1(const S2SJobs jobs) {
     }
     float inv_xs[NB];
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) inv_xs[nb] = xs[nb] != 0.0f ? 1.0f / xs[nb] : 1.0f;      // (powers of two: exact)
+    for (int nb = 0; nb < NB; ++nb) inv_xs[nb] = xs[nb] != 0.0f ? 1.0f / (xs[nb] * GS_WSCALE) : 1.0f;      // (powers of two: exact)
     const int act = J.act;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {

@@ -217,6 +217,35 @@ int64_t aether_debug_fetch(const char* name, int num_dims, int64_t n_nodes, int6
 int aether_debug_split(const float* x, int n_tiles, uint16_t* hi, uint16_t* lo, int* on, float* scale, float* y);
 
 /*
+ * Test hook: what the host chose for the dense-layer tables and the edge filter of the seq2seq steps since the last reset.
+ * Kinds of a table's launch: 0 the fp32 job kernel (k_s2s_linear_jobs), 1 k_s2s_gemm_split<1> (64-row tiles), 2 <2> (128-row
+ * tiles), 3 k_s2s_gemm_split_r1<1>, 4 k_s2s_gemm_split_r1<2>.  Per kind: launches, jobs, and the largest N, M, K, K2 of a job.
+ * The first AETHER_S2S_LAUNCH_LOG launches are also kept one by one, in order: `N`, `M`, `K`, `K2` of the job with the largest
+ * N * M (the one the tiling is chosen for), `min_n` the fewest rows of a job, `images` whether every job could run on the
+ * split kernels (a prepared image for every weight, M a multiple of 128, K and K2 of 32), `tiles64` the sum of
+ * ceil(N / 64) * ceil(M / 128) the switch is decided by, `wg128` the sum of ceil(N / 128) * (M / 128) the tile height is
+ * decided by (0 unless the table went split), `wgs` the launch's workgroups.  filter_*: launches of k_s2s_filter_split with
+ * splits == 1 and with more, and the largest splits.  Plain host integers, updated when a launch is issued: they mean nothing
+ * for the replays of a captured graph, and are not synchronised between host threads.
+ */
+#define AETHER_S2S_LAUNCH_KINDS 5
+#define AETHER_S2S_LAUNCH_LOG 96
+typedef struct AetherS2SLaunchRecord {
+    int32_t kind, jobs, images, M, K, K2, wgs, reserved;
+    int64_t N, min_n, tiles64, wg128;
+} AetherS2SLaunchRecord;
+typedef struct AetherS2SLaunchStats {
+    int64_t launches[AETHER_S2S_LAUNCH_KINDS], jobs[AETHER_S2S_LAUNCH_KINDS];
+    int64_t max_n[AETHER_S2S_LAUNCH_KINDS], max_m[AETHER_S2S_LAUNCH_KINDS], max_k[AETHER_S2S_LAUNCH_KINDS],
+        max_k2[AETHER_S2S_LAUNCH_KINDS];
+    int64_t filter_one, filter_many, filter_max_splits;
+    int64_t logged;                                    /* launches since the reset; min(logged, LOG) records are valid */
+    AetherS2SLaunchRecord log[AETHER_S2S_LAUNCH_LOG];
+} AetherS2SLaunchStats;
+int aether_s2s_launch_stats(AetherS2SLaunchStats* stats);   /* copies the block out; AETHER_EINVAL for a null pointer */
+void aether_s2s_launch_stats_reset(void);
+
+/*
  * Test hook of the 12-wave fused kernels' layer-1 feature build (csrc/fused_layout.h: fused_packed_edge): the edge, in the
  * workgroup's local order, whose features lane `lane` of wave `wave` builds, or -1 for a (wave, lane) that builds none.
  * Edge f is row f & 15 of tile f >> 4, which wave f >> 4 owns.  Host only: needs no GPU.
