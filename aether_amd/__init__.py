@@ -10,6 +10,8 @@ Widened rows of SURVEY.md 8f (each mirrors the reference module of the same name
 * ``aether_amd.nn.seq2seq.{aether.Aether, dynamic_field_aether.DynamicFieldAether}`` (+ ``encoder``, ``decoder``, ``field``,
   ``localizer``)
 * ``aether_amd.nn.dynamicvars.{aether_dynamicvars.AetherDynamicVars, encoder.Encoder, decoder.Decoder}``
+* ``aether_amd.nn.dynamicvars.dnri_dynamicvars.{DNRIDynamicVars, DNRI_DynamicVars_Encoder, DNRI_DynamicVars_Decoder}`` (the
+  variable-N family's dNRI baseline, on the same scene engine)
 * data side: ``aether_amd.knn``, ``aether_amd.sim``, ``aether_amd.data``, ``aether_amd.evaluate``, ``aether_amd.rollout``
 
 Everything computes in ``libaether_hip.so`` (``include/aether_hip.h``); there is no CPU fallback.

@@ -249,6 +249,22 @@ SIGNATURES = {
                                                                C.c_void_p]),
     "aether_dyn_rollout_batched": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 +
                                    [C.c_void_p] * 3 + [C.c_void_p] * 5 + [C.c_void_p] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "aether_dyn_dnri_prior_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
+    "aether_dyn_dnri_prior_step": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_int64, C.c_int64] + [C.c_void_p] * 8 +
+                                   [C.c_size_t] + [C.c_void_p] * 4),
+    "aether_dyn_dnri_decoder_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64, C.c_int64]),
+    "aether_dyn_dnri_decoder_step_batched": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64] +
+                                             [C.c_void_p] * 7 + [C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                                 C.c_void_p, C.c_void_p]),
+    "aether_dyn_dnri_step_batched_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                                  C.c_void_p]),
+    "aether_dyn_dnri_step_batched": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_void_p] * 12 +
+                                     [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "aether_dyn_dnri_rollout_batched_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                                     C.c_void_p, C.c_void_p]),
+    "aether_dyn_dnri_rollout_batched": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 +
+                                        [C.c_void_p] * 3 + [C.c_void_p] * 5 + [C.c_void_p] * 4 +
+                                        [C.c_void_p, C.c_size_t, C.c_void_p]),
     "aether_dyn_scene_pack_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "aether_dyn_scene_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                         C.POINTER(AetherDynScenePack), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -47,6 +47,7 @@
 #include "s2s_dynfield.h"
 #include "knn.h"
 #include "dyn_step.h"
+#include "dyn_dnri.h"
 #include "sim.h"
 #include "train_step.h"
 #include "egnn.h"
@@ -1058,6 +1059,7 @@ const char* aether_last_error(void) { return g_err; }
 #include "host_s2s_dnri.inc"
 #include "host_dynamicvars.inc"
 #include "host_dyn_step.inc"
+#include "host_dyn_dnri.inc"
 #include "host_sim.inc"
 #include "host_train.inc"
 #include "host_gnn_common.inc"

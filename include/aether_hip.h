@@ -1308,6 +1308,93 @@ int aether_dyn_rollout_batched(const AetherDynFieldQueryParams* field_params, co
                                size_t workspace_bytes, void* stream);
 
 /*
+ * The variable-N dNRI baseline (nn/dynamicvars/dnri_dynamicvars.py: DNRIDynamicVars, prediction path) on the same scene
+ * engine.  The model has no field, no local frames, no edge attributes and no filter: none of their kernels is launched and
+ * no buffer is sized for one.  The entries mirror the Aether ones argument for argument, minus the field parameters.
+ *
+ * aether_dyn_dnri_prior_step replaces DNRI_DynamicVars_Encoder.compute_feat_transform for one time step (:386-432) + the
+ * LSTM / prior half of single_step_forward (:552-566) on the present objects, compacted: mlp1 on the raw 4 columns,
+ * [x_send | x_recv] -> mlp2 (kept as the skip), index_add_ over the receiver (:374-377, a plain SUM), mlp3,
+ * [x_send | x_recv | skip] -> mlp4 (RefNRIMLP in eval mode; the four bn pointers of a layer may be NULL: no_encoder_bn), one
+ * LSTM step per edge, prior_fc_out.
+ *   inputs [n][4];  send, recv int64[e]: the encoder's own kNN graph (aether_knn_edges: the query object is the sender),
+ *   order, rowptr: its edges grouped by recv (CSR);  h0, c0 [e][R]: the LSTM state rows of the CALLER's edges, row e for edge
+ *   e of the caller's graph (:554-559: the pairing is positional, so both graphs list n min(k, n - 1) edges; the slot
+ *   arithmetic stays with the caller);  logits [e][K], h1, c1 [e][R].  `polar` is ignored (there is no frame).
+ *
+ * aether_dyn_dnri_decoder_step_batched replaces DNRI_DynamicVars_Decoder.forward (:618-688) on the present objects of one or
+ * several scenes, concatenated: pre_msg = [h_recv | h_send], tanh(msg_fc2(tanh(msg_fc1))) z_k / (number of used types) per
+ * used type, sum over the agg_order rows / agg_div_node (the scene's num_vars - 1; NULL: the scalar agg_div), the GRU-style
+ * gate with input_r / _i / _n on the raw inputs, out_fc1-3 with ReLU and the residual.  decoder_dropout is 0 (the reference
+ * drops in eval mode too, :653, :678-679: refused by the module, not reproduced).
+ *   inputs [n][4], hidden_in [n][h], edge_w [e][K] with ONE-HOT rows (hard samples: every edge sits in one type's list);
+ *   send, recv int64[e]; agg_order, agg_rowptr as aether_dyn_decoder_step_batched;  outputs [n][4], hidden_out [n][h].
+ *   n >= 2 and e >= 1: a scene with one present object is not taken.  `polar` is ignored.
+ */
+typedef struct AetherDynDnriPriorParams {
+    const float* mlp_w0[4]; const float* mlp_b0[4];      /* mlp1 .. mlp4, first Linear: [h][4], [h][2h], [h][h], [h][3h] */
+    const float* mlp_w3[4]; const float* mlp_b3[4];      /* second Linear: [h][h], [h] */
+    const float* mlp_bn_w[4]; const float* mlp_bn_b[4]; const float* mlp_bn_mean[4]; const float* mlp_bn_var[4];   /* [h] or NULL */
+    const float* lstm_w_ih; const float* lstm_w_hh; const float* lstm_b_ih; const float* lstm_b_hh; /* forward_rnn: [4R][h], [4R][R] */
+    const float* prior_w[4]; const float* prior_b[4];    /* prior_fc_out */
+} AetherDynDnriPriorParams;
+typedef struct AetherDynDnriDecoderParams {
+    const float* msg_fc1_w[4]; const float* msg_fc1_b[4];    /* [h][2h] (receiver | sender halves), [h] */
+    const float* msg_fc2_w[4]; const float* msg_fc2_b[4];    /* [h][h], [h] */
+    const float* hidden_r_w; const float* hidden_i_w; const float* hidden_h_w;      /* [h][h], no bias */
+    const float* input_r_w; const float* input_r_b;
+    const float* input_i_w; const float* input_i_b;
+    const float* input_n_w; const float* input_n_b;          /* [h][4], [h] */
+    const float* out1_w; const float* out1_b; const float* out2_w; const float* out2_b;   /* out_fc1 / 2: [h][h], [h] */
+    const float* out3_w; const float* out3_b;                /* out_fc3: [4][h], [4] */
+} AetherDynDnriDecoderParams;
+size_t aether_dyn_dnri_prior_workspace_bytes(int hidden, int rnn_hidden, int prior_hidden, int64_t n_nodes, int64_t n_edges);
+int aether_dyn_dnri_prior_step(const AetherDynDnriPriorParams* params, int hidden, int rnn_hidden, int prior_layers,
+                               int prior_hidden, int num_edge_types, int polar, int64_t n_nodes, int64_t n_edges,
+                               const float* inputs, const float* h0, const float* c0, const int64_t* send, const int64_t* recv,
+                               const int64_t* order, const int64_t* rowptr, void* workspace, size_t workspace_bytes,
+                               float* logits, float* h1, float* c1, void* stream);
+size_t aether_dyn_dnri_decoder_workspace_bytes(int hidden, int num_edge_types, int64_t n_nodes, int64_t n_edges);
+int aether_dyn_dnri_decoder_step_batched(const AetherDynDnriDecoderParams* params, int hidden, int num_edge_types, int skip_first,
+                                         int polar, int64_t n_nodes, int64_t n_edges, const float* inputs,
+                                         const float* hidden_in, const float* edge_w, const int64_t* send, const int64_t* recv,
+                                         const int64_t* agg_order, const int64_t* agg_rowptr, float agg_div,
+                                         const float* agg_div_node, void* workspace, size_t workspace_bytes, float* outputs,
+                                         float* hidden_out, void* stream);
+/*
+ * One prediction step (the body of DNRIDynamicVars.predict_future's loop, :165-174) and the whole loop (:152-175) for
+ * 1 .. 256 scenes as ONE call each: aether_dyn_step_batched / aether_dyn_rollout_batched without the field stage, with the
+ * same arrays, conventions and checks -- n_scenes = 1 is the single-scene call.  AetherDynStepConfig is reused; its
+ * field_hidden, encoder_polar and decoder_polar members are ignored.  Per scene n_present is 0 or 2 .. n_objects_max and
+ * n_edges = n_present * min(knn_k, n_present - 1); a scene with exactly one present object is refused by name, as the engine
+ * refuses it for the Aether model (the reference's dNRI itself would run it with zero messages).  Every step of every scene is
+ * validated on the host before anything is queued: a refused call has queued nothing and touched no state.  A mask that
+ * disagrees with n_present poisons the step's outputs and the state rows it would have written with NaN, and the next call
+ * returns AETHER_EHIP (async error word).  The stages are the two entries above (same kernels, same order): results equal
+ * the staged calls bit for bit.  The workspace is smaller than aether_dyn_step_batched_workspace_bytes for the same sizes.
+ */
+size_t aether_dyn_dnri_step_batched_workspace_bytes(const AetherDynStepConfig* config, int n_scenes, int n_objects_max,
+                                                    const int64_t* n_present, const int64_t* n_edges, const int* in_degree);
+int aether_dyn_dnri_step_batched(const AetherDynDnriPriorParams* prior_params, const AetherDynDnriDecoderParams* decoder_params,
+                                 const AetherDynStepConfig* config, int n_scenes, int n_objects_max, const int64_t* n_present,
+                                 const int64_t* n_edges, const int* in_degree, const float* state, const float* mask,
+                                 const int64_t* node_inds, const int64_t* graph_send, const int64_t* graph_recv,
+                                 const int64_t* edge2node, float* prior_h, float* prior_c, float* decoder_hidden,
+                                 const float* uniform, float* prediction, float* edge_types, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+size_t aether_dyn_dnri_rollout_batched_workspace_bytes(const AetherDynStepConfig* config, int n_scenes, int n_objects_max,
+                                                       int n_steps, const int64_t* n_present, const int64_t* n_edges,
+                                                       const int* in_degree);
+int aether_dyn_dnri_rollout_batched(const AetherDynDnriPriorParams* prior_params, const AetherDynDnriDecoderParams* decoder_params,
+                                    const AetherDynStepConfig* config, int n_scenes, int n_objects_max, int n_steps,
+                                    const float* inputs, const float* masks, const float* burn_in_masks, const int64_t* n_present,
+                                    const int64_t* n_edges, const int* in_degree, const int64_t* const* node_inds,
+                                    const int64_t* const* graph_send, const int64_t* const* graph_recv,
+                                    const int64_t* const* edge2node, const float* const* uniform, float* prior_h, float* prior_c,
+                                    float* decoder_hidden, float* predictions, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+
+/*
  * Scene pack: the data side of the variable-N family on the device.  Replaces, for B scenes and every frame at once, what
  * the reference's data set builds per scene and per frame on the host (experiments/ind/single_ind_data.py:70-89):
  * node_inds = mask[step].nonzero()[:, -1] (:82) and get_knn_graph_info (:186-217) -- the kNN graph of the frame's
