@@ -2,7 +2,7 @@
 // host_dyn_step.inc -- the staged prior and decoder steps, one prediction step and the whole prediction loop as ONE call for
 // 1 .. 256 scenes (dyn_dnri.h has the kernels).  The model has no field and no frames: no field, localizer, edge-attribute or
 // filter launch is made and no buffer is sized for one.  Included by aether_hip.hip inside its extern "C" block, after
-// host_dyn_step.inc (whose scene checks it shares); not a stand-alone source file.
+// host_dyn_step.inc (whose scene checks and step / rollout drivers it shares); not a stand-alone source file.
 
 namespace {
 // Workspace of the prior step: node rows, edge rows, the BatchNorm affines and the summed LSTM biases.
@@ -191,30 +191,61 @@ int dyn_dnri_decoder_impl(const AetherDynDnriDecoderParams* p, int h, int K, int
     return AETHER_OK;
 }
 
-struct DynDnriBatchLayout {
-    size_t idx, cidx, cur_in, cur_h, rowptr_dec, div_node, status, ksend, krecv, ksums, ktot, korder, krowptr, send, recv, order,
-        slot, h0, c0, h1, c1, logits, ew, new_h, ws_knn, ws_prior, ws_dec, total;
-    size_t b_knn, b_prior, b_dec;
-    int knn_k;
-    DynDnriBatchLayout(const AetherDynStepConfig& c, int B, int n_max, const DynBatchSizes& Z) {
-        size_t off = 0;
-        auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-        const size_t nn = (size_t)Z.n_total, ee = (size_t)Z.e_total, oo = (size_t)Z.o_total, R = (size_t)c.rnn_hidden,
-                     K = (size_t)c.num_edge_types, rows = (size_t)B * n_max;
-        knn_k = std::min(c.knn_k, n_max - 1);
-        idx = take(nn * 8); cidx = take(rows * 4); cur_in = take(nn * 16); cur_h = take(nn * c.decoder_hidden * 4);
-        rowptr_dec = take((nn + 1) * 8); div_node = take(nn * 4); status = take((size_t)(1 + DYN_MAX_SCENES) * 4);
-        const size_t kcap = std::max(ee, rows * (size_t)(knn_k > 0 ? knn_k : 1));      // whatever the masks hold
-        ksend = take(kcap * 8); krecv = take(kcap * 8); ksums = take((size_t)2 * B * 8); ktot = take(64);
-        korder = take(ee * 8); krowptr = take((nn + 1) * 8);
-        send = take(ee * 8); recv = take(ee * 8); order = take((oo + 1) * 8); slot = take(ee * 8);
-        h0 = take(ee * R * 4); c0 = take(ee * R * 4); h1 = take(ee * R * 4); c1 = take(ee * R * 4);
-        logits = take(ee * K * 4); ew = take(ee * K * 4); new_h = take(nn * c.decoder_hidden * 4);
-        b_knn = aether_knn_workspace_bytes(B, n_max, knn_k > 0 ? knn_k : 1);
+struct DynDnriBatchLayout : DynSceneLayout {
+    size_t ws_prior, ws_dec;
+    size_t b_prior, b_dec;
+    DynDnriBatchLayout(const AetherDynStepConfig& c, int B, int n_max, const DynBatchSizes& Z) : DynSceneLayout(c, B, n_max, Z) {
         b_prior = DynDnriPriorLayout(c.encoder_hidden, c.rnn_hidden, c.prior_hidden, Z.n_total, Z.e_total).total;
         b_dec = DynDnriDecLayout(c.decoder_hidden, c.num_edge_types, Z.n_total, Z.e_total).total;
-        ws_knn = take(b_knn); ws_prior = take(b_prior); ws_dec = take(b_dec);
-        total = off;
+        ws_prior = take(b_prior); ws_dec = take(b_dec);
+    }
+};
+
+// DNRIDynamicVars on the driver of host_dyn_step.inc: present, kNN, csr, index, prior, sample, decoder (whose last kernel
+// writes the rows back to their objects: no finish launch).
+struct DynDnriModel {
+    using Layout = DynDnriBatchLayout;
+    using Ctx = DynStepCtx<Layout>;
+    static constexpr const char* step_name = "dyn_dnri_step_batched";
+    static constexpr const char* rollout_name = "dyn_dnri_rollout_batched";
+    const AetherDynDnriPriorParams* prior_params;
+    const AetherDynDnriDecoderParams* decoder_params;
+    bool params_ok() const { return prior_params && decoder_params; }
+    int config_check(const char* entry, const AetherDynStepConfig& c) const {
+        if (c.skip_first && c.num_edge_types < 2) return dyn_fail(AETHER_EINVAL, entry, "skip_first needs two edge types");
+        if (c.prior_layers < 1 || c.prior_layers > 4 || (c.prior_layers > 1 && (c.prior_hidden < 16 || c.prior_hidden % 16 != 0)))
+            return dyn_fail(AETHER_EINVAL, entry, "1..4 prior layers, prior_hidden a multiple of 16");
+        return AETHER_OK;
+    }
+    size_t counts_offset(const Ctx& X) const {
+        return X.L.ws_dec + DynDnriDecLayout(X.c.decoder_hidden, X.c.num_edge_types, X.n, X.E).counts;
+    }
+    int field(const Ctx&) const { return AETHER_OK; }                  // (no field)
+    // the callers' graphs in the numbering of the batch, LSTM state rows of their edges (:554-559)
+    void index(const Ctx& X) const {
+        const Layout& L = X.L;
+        const int R = X.c.rnn_hidden;
+        const int64_t work = std::max<int64_t>(X.E * (R / 4), X.Z.o_total);
+        k_dynb_dnri_index<<<dyn_blocks(work), dim3(256), 0, X.st()>>>(X.S, X.graph_send, X.graph_recv, X.node_inds, X.ip(L.idx),
+                                                                     X.edge2node, R, X.prior_h, X.prior_c, X.ip(L.send),
+                                                                     X.ip(L.recv), X.ip(L.slot), X.fp(L.h0), X.fp(L.c0),
+                                                                     X.ip(L.order));
+    }
+    int prior(const Ctx& X) const {
+        const Layout& L = X.L;
+        const AetherDynStepConfig& c = X.c;
+        return dyn_dnri_prior_impl(prior_params, c.encoder_hidden, c.rnn_hidden, c.prior_layers, c.prior_hidden, c.num_edge_types,
+                                   X.n, X.E, X.fp(L.cur_in), X.fp(L.h0), X.fp(L.c0), X.ip(L.ksend), X.ip(L.krecv), X.ip(L.korder),
+                                   X.ip(L.krowptr), X.ws + L.ws_prior, L.b_prior, X.fp(L.logits), X.fp(L.h1), X.fp(L.c1), X.st());
+    }
+    // decoder step on the callers' graphs (:618-688); its last kernel writes the rows back to their objects
+    int decode(const Ctx& X, const float* ew) const {
+        const Layout& L = X.L;
+        const AetherDynStepConfig& c = X.c;
+        const DynDnriScatter sc{X.cidx(), X.status(), X.rows, X.decoder_hidden, true};
+        return dyn_dnri_decoder_impl(decoder_params, c.decoder_hidden, c.num_edge_types, c.skip_first, X.n, X.E, X.fp(L.cur_in),
+                                     X.fp(L.cur_h), ew, X.ip(L.send), X.ip(L.recv), X.ip(L.order), X.ip(L.rowptr_dec), 1.0f,
+                                     X.fp(L.div_node), X.ws + L.ws_dec, L.b_dec, X.prediction, X.fp(L.new_h), X.st(), &sc);
     }
 };
 }  // namespace
@@ -254,10 +285,7 @@ int aether_dyn_dnri_decoder_step_batched(const AetherDynDnriDecoderParams* param
 
 size_t aether_dyn_dnri_step_batched_workspace_bytes(const AetherDynStepConfig* config, int n_scenes, int n_objects_max,
                                                     const int64_t* n_present, const int64_t* n_edges, const int* in_degree) {
-    DynScenes S; DynBatchSizes Z;
-    if (dyn_batch_check(config, n_scenes, n_objects_max, n_present, n_edges, in_degree, &S, &Z)) return 0;
-    if (Z.n_total == 0) return 512;
-    return DynDnriBatchLayout(*config, n_scenes, n_objects_max, Z).total + 256;
+    return dyn_step_bytes<DynDnriBatchLayout>(config, n_scenes, n_objects_max, n_present, n_edges, in_degree);
 }
 
 int aether_dyn_dnri_step_batched(const AetherDynDnriPriorParams* prior_params, const AetherDynDnriDecoderParams* decoder_params,
@@ -267,91 +295,16 @@ int aether_dyn_dnri_step_batched(const AetherDynDnriPriorParams* prior_params, c
                                  const int64_t* edge2node, float* prior_h, float* prior_c, float* decoder_hidden,
                                  const float* uniform, float* prediction, float* edge_types, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-    if (!prior_params || !decoder_params || !state || !mask || !prior_h || !prior_c || !decoder_hidden || !prediction || !workspace)
-        return fail(AETHER_EINVAL, "dyn_dnri_step_batched: null pointer");
-    DynScenes S; DynBatchSizes Z;
-    if (int rc = dyn_batch_check(config, n_scenes, n_objects_max, n_present, n_edges, in_degree, &S, &Z)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const AetherDynStepConfig& c = *config;
-    const int B = n_scenes, n_max = n_objects_max, R = c.rnn_hidden, K = c.num_edge_types, hd = c.decoder_hidden;
-    const int64_t rows = (int64_t)B * n_max;
-    if (Z.n_total == 0) {                        // nobody anywhere: zeros, states untouched (:662-664)
-        HIP_OK(hipMemsetAsync(prediction, 0, (size_t)rows * 16, st));
-        return AETHER_OK;
-    }
-    if (!graph_send || !graph_recv || !edge2node || !uniform)
-        return fail(AETHER_EINVAL, "dyn_dnri_step_batched: null graph / uniform pointer");
-    if (c.skip_first && K < 2) return fail(AETHER_EINVAL, "dyn_dnri_step_batched: skip_first needs two edge types");
-    if (c.prior_layers < 1 || c.prior_layers > 4 || (c.prior_layers > 1 && (c.prior_hidden < 16 || c.prior_hidden % 16 != 0)))
-        return fail(AETHER_EINVAL, "dyn_dnri_step_batched: 1..4 prior layers, prior_hidden a multiple of 16");
-    const int n = (int)Z.n_total;
-    const int64_t E = Z.e_total;
-    DynDnriBatchLayout L(c, B, n_max, Z);
-    char* ws = reinterpret_cast<char*>(align_up((size_t)workspace, 256));
-    if (workspace_bytes < L.total + 256) return fail(AETHER_ESPACE, "dyn_dnri_step_batched: workspace too small");
-    if (take_async_error()) return AETHER_EHIP;
-    auto fp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto ip = [&](size_t off) { return reinterpret_cast<int64_t*>(ws + off); };
-    auto blocks = [](int64_t cnt) { return dim3((unsigned)((cnt + 255) / 256)); };
-    int* cidx = reinterpret_cast<int*>(ws + L.cidx);
-    int* status = reinterpret_cast<int*>(ws + L.status);
-    // ---- the present objects of every scene (mask -> rows), their state and decoder hidden rows
-    {
-        const size_t lds = ((size_t)3 * (DYN_MAX_SCENES + 1) + 257 + 2 * (size_t)n_max) * 4;
-        if (ensure_dynamic_lds(reinterpret_cast<const void*>(k_dynb_present), lds)) return AETHER_EHIP;
-        const DynDnriDecLayout DL(hd, K, n, E);
-        k_dynb_present<<<dim3((unsigned)B), dim3(256), lds, st>>>(S, state, mask, decoder_hidden, hd, ip(L.idx), cidx, fp(L.cur_in),
-                                                                 fp(L.cur_h), ip(L.rowptr_dec), fp(L.div_node), status,
-                                                                 async_error_word(), ip(L.ksums),
-                                                                 reinterpret_cast<int*>(ws + L.ws_dec + DL.counts));
-    }
-    // ---- the encoder's own kNN graphs (:408, :434-461), scene by scene, then grouped by receiver per scene
-    int64_t* ksums = ip(L.ksums);
-    if (int rc = knn_edges_impl(state, 4, mask, B, n_max, L.knn_k, ip(L.ksend), ip(L.krecv), ksums, ksums + B, ip(L.ktot),
-                                ws + L.ws_knn, L.b_knn, stream, true)) return rc;
-    {
-        const size_t lds = ((size_t)3 * (DYN_MAX_SCENES + 1) + 257 + 256 + (size_t)n_max) * 4;
-        if (ensure_dynamic_lds(reinterpret_cast<const void*>(k_dynb_csr), lds)) return AETHER_EHIP;
-        k_dynb_csr<<<dim3((unsigned)B), dim3(256), lds, st>>>(S, ip(L.ksend), ip(L.krecv), status, ip(L.korder), ip(L.krowptr));
-    }
-    // ---- the callers' graphs in the numbering of the batch, LSTM state rows of their edges (:554-559)
-    {
-        const int64_t work = std::max<int64_t>(E * (R / 4), Z.o_total);
-        k_dynb_dnri_index<<<blocks(work), dim3(256), 0, st>>>(S, graph_send, graph_recv, node_inds, ip(L.idx), edge2node, R, prior_h,
-                                                             prior_c, ip(L.send), ip(L.recv), ip(L.slot), fp(L.h0), fp(L.c0),
-                                                             ip(L.order));
-    }
-    if (int rc = dyn_dnri_prior_impl(prior_params, c.encoder_hidden, R, c.prior_layers, c.prior_hidden, K, n, E, fp(L.cur_in),
-                                     fp(L.h0), fp(L.c0), ip(L.ksend), ip(L.krecv), ip(L.korder), ip(L.krowptr), ws + L.ws_prior,
-                                     L.b_prior, fp(L.logits), fp(L.h1), fp(L.c1), st)) return rc;
-    // ... state back into its slots and the hard Gumbel sample of the edge types, one launch; a scene whose mask disagreed with
-    // its n poisons the rows (status[0] != 0)
-    float* ew = edge_types ? edge_types : fp(L.ew);
-    k_dyn_scatter_sample<<<blocks(E * (R / 4)), dim3(256), 0, st>>>(ip(L.slot), fp(L.h1), fp(L.c1), E, R, prior_h, prior_c,
-                                                                   fp(L.logits), uniform, c.gumbel_tau, K, ew, status, 0);
-    // ---- decoder step on the callers' graphs (:618-688); its last kernel writes the rows back to their objects
-    const DynDnriScatter sc{cidx, status, rows, decoder_hidden, true};
-    if (int rc = dyn_dnri_decoder_impl(decoder_params, hd, K, c.skip_first, n, E, fp(L.cur_in), fp(L.cur_h), ew, ip(L.send),
-                                       ip(L.recv), ip(L.order), ip(L.rowptr_dec), 1.0f, fp(L.div_node), ws + L.ws_dec, L.b_dec,
-                                       prediction, fp(L.new_h), st, &sc)) return rc;
-    HIP_OK(hipGetLastError());
-    return AETHER_OK;
+    return dyn_step_run(DynDnriModel{prior_params, decoder_params}, config, n_scenes, n_objects_max, n_present, n_edges, in_degree,
+                        state, mask, node_inds, graph_send, graph_recv, edge2node, prior_h, prior_c, decoder_hidden, uniform,
+                        prediction, edge_types, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------ the prediction loop (predict_future, :152-175)
 size_t aether_dyn_dnri_rollout_batched_workspace_bytes(const AetherDynStepConfig* config, int n_scenes, int n_objects_max,
                                                        int n_steps, const int64_t* n_present, const int64_t* n_edges,
                                                        const int* in_degree) {
-    if (!config || !n_present || !n_edges || !in_degree || n_steps <= 0 || n_scenes < 1) return 0;
-    size_t need = 0;
-    for (int t = 0; t < n_steps; ++t) {
-        const size_t b = aether_dyn_dnri_step_batched_workspace_bytes(config, n_scenes, n_objects_max,
-                                                                      n_present + (size_t)t * n_scenes,
-                                                                      n_edges + (size_t)t * n_scenes, in_degree + (size_t)t * n_scenes);
-        if (b == 0) return 0;
-        need = std::max(need, b);
-    }
-    return need + align_up((size_t)n_scenes * n_objects_max * 16, 256) + 256;
+    return dyn_rollout_bytes<DynDnriBatchLayout>(config, n_scenes, n_objects_max, n_steps, n_present, n_edges, in_degree);
 }
 
 int aether_dyn_dnri_rollout_batched(const AetherDynDnriPriorParams* prior_params, const AetherDynDnriDecoderParams* decoder_params,
@@ -362,45 +315,7 @@ int aether_dyn_dnri_rollout_batched(const AetherDynDnriPriorParams* prior_params
                                     const int64_t* const* edge2node, const float* const* uniform, float* prior_h, float* prior_c,
                                     float* decoder_hidden, float* predictions, void* workspace, size_t workspace_bytes,
                                     void* stream) {
-    if (!config || !inputs || !masks || !burn_in_masks || !n_present || !n_edges || !in_degree || !graph_send || !graph_recv ||
-        !edge2node || !uniform || !predictions || !workspace || !prior_params || !decoder_params || !prior_h || !prior_c ||
-        !decoder_hidden)
-        return fail(AETHER_EINVAL, "dyn_dnri_rollout_batched: null pointer");
-    if (n_steps <= 0) return fail(AETHER_EINVAL, "dyn_dnri_rollout_batched: n_steps must be positive");
-    const int B = n_scenes;
-    // every step of every scene is validated on the host before anything is queued
-    for (int t = 0; t < n_steps; ++t) {
-        DynScenes S; DynBatchSizes Z;
-        if (int rc = dyn_batch_check(config, B, n_objects_max, n_present + (size_t)t * B, n_edges + (size_t)t * B,
-                                     in_degree + (size_t)t * B, &S, &Z)) return rc;
-        if (Z.n_total > 0 && (!graph_send[t] || !graph_recv[t] || !edge2node[t] || !uniform[t]))
-            return fail(AETHER_EINVAL, "dyn_dnri_rollout_batched: a step's graph / uniform pointer is null");
-    }
-    if (config->skip_first && config->num_edge_types < 2)
-        return fail(AETHER_EINVAL, "dyn_dnri_rollout_batched: skip_first needs two edge types");
-    if (config->prior_layers < 1 || config->prior_layers > 4 ||
-        (config->prior_layers > 1 && (config->prior_hidden < 16 || config->prior_hidden % 16 != 0)))
-        return fail(AETHER_EINVAL, "dyn_dnri_rollout_batched: 1..4 prior layers, prior_hidden a multiple of 16");
-    const size_t need = aether_dyn_dnri_rollout_batched_workspace_bytes(config, B, n_objects_max, n_steps, n_present, n_edges, in_degree);
-    if (need == 0) return fail(AETHER_EINVAL, "dyn_dnri_rollout_batched: bad sizes");
-    if (workspace_bytes < need) return fail(AETHER_ESPACE, "dyn_dnri_rollout_batched: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(align_up((size_t)workspace, 256));
-    float* state = reinterpret_cast<float*>(ws);
-    const size_t rows = (size_t)B * n_objects_max;
-    char* step_ws = ws + align_up(rows * 16, 256);
-    const size_t step_bytes = workspace_bytes - (size_t)(step_ws - (char*)workspace);
-    const size_t row = rows * 4;
-    for (int t = 0; t < n_steps; ++t) {
-        const float* last = t == 0 ? inputs : predictions + (size_t)(t - 1) * row;
-        float* pred = predictions + (size_t)t * row;
-        k_dyn_mix<<<dim3((unsigned)((row + 255) / 256)), dim3(256), 0, st>>>(inputs + (size_t)t * row, last,
-                                                                            burn_in_masks + (size_t)t * rows, (int)rows, state);
-        if (int rc = aether_dyn_dnri_step_batched(prior_params, decoder_params, config, B, n_objects_max, n_present + (size_t)t * B,
-                                                  n_edges + (size_t)t * B, in_degree + (size_t)t * B, state,
-                                                  masks + (size_t)t * rows, node_inds ? node_inds[t] : nullptr, graph_send[t],
-                                                  graph_recv[t], edge2node[t], prior_h, prior_c, decoder_hidden, uniform[t], pred,
-                                                  nullptr, step_ws, step_bytes, stream)) return rc;
-    }
-    return AETHER_OK;
+    return dyn_rollout_run(DynDnriModel{prior_params, decoder_params}, config, n_scenes, n_objects_max, n_steps, inputs, masks,
+                           burn_in_masks, n_present, n_edges, in_degree, node_inds, graph_send, graph_recv, edge2node, uniform,
+                           prior_h, prior_c, decoder_hidden, predictions, workspace, workspace_bytes, stream);
 }

@@ -1,7 +1,8 @@
 // Host side of the C ABI: one prediction step of the variable-N model, and the whole prediction loop, as ONE call for
 // 1 .. 256 scenes (SURVEY 8f N2; dyn_step.h has the kernels).  Included by aether_hip.hip inside its extern "C" block,
-// after host_dynamicvars.inc.  aether_dyn_step / aether_dyn_rollout (one scene) are the n_scenes = 1 case of the batched
-// entry points and forward to them (end of this file).
+// after host_dynamicvars.inc.  The step and rollout drivers are templates over a model (dyn_step_run, dyn_rollout_run):
+// DynAetherModel here, DynDnriModel in host_dyn_dnri.inc.  aether_dyn_step / aether_dyn_rollout (one scene) are the
+// n_scenes = 1 case of the batched entry points and forward to them (end of this file).
 
 namespace {
 // One scene of a step: the configuration, and 2 <= n <= n_max present objects with the edge count of the encoder's kNN graph.
@@ -25,33 +26,42 @@ int dyn_step_check(const AetherDynStepConfig* c, int n_max, int64_t n, int64_t E
 }
 
 struct DynBatchSizes { int64_t n_total, e_total, o_total; };
-struct DynBatchLayout {
-    size_t idx, cidx, cur_in, cur_h, rowptr_dec, div_node, status, field_c, ext_full, ksend, krecv, ksums, ktot, korder, krowptr,
-        send, recv, ssend, srecv, order, slot, h0, c0, h1, c1, logits, ew, out_c, new_h, ws_field, ws_knn, ws_prior, ws_dec, total;
-    size_t b_field, b_knn, b_prior, b_dec;
+// The buffers of a step that every model on the scene engine uses.  A model's layout derives from this one and takes its own
+// buffers behind these.  Every take starts 256-aligned and is rounded to 256 bytes, so `total` is the sum of the rounded
+// sizes whatever the order of the takes.
+struct DynSceneLayout {
+    size_t idx, cidx, cur_in, cur_h, rowptr_dec, div_node, status, ksend, krecv, ksums, ktot, korder, krowptr, send, recv, order,
+        slot, h0, c0, h1, c1, logits, ew, new_h, ws_knn, total = 0;
+    size_t b_knn;
     int knn_k;
-    DynBatchLayout(const AetherDynStepConfig& c, int B, int n_max, const DynBatchSizes& Z) {
-        size_t off = 0;
-        auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    size_t take(size_t bytes) { size_t o = total; total = align_up(total + bytes, 256); return o; }
+    DynSceneLayout(const AetherDynStepConfig& c, int B, int n_max, const DynBatchSizes& Z) {
         const size_t nn = (size_t)Z.n_total, ee = (size_t)Z.e_total, oo = (size_t)Z.o_total, R = (size_t)c.rnn_hidden,
                      K = (size_t)c.num_edge_types, rows = (size_t)B * n_max;
         knn_k = std::min(c.knn_k, n_max - 1);
         idx = take(nn * 8); cidx = take(rows * 4); cur_in = take(nn * 16); cur_h = take(nn * c.decoder_hidden * 4);
-        rowptr_dec = take((nn + 1) * 8); div_node = take(nn * 4); status = take((size_t)(1 + DYN_MAX_SCENES) * 4); field_c = take(nn * 8);
-        ext_full = take(rows * 24);
+        rowptr_dec = take((nn + 1) * 8); div_node = take(nn * 4); status = take((size_t)(1 + DYN_MAX_SCENES) * 4);
         const size_t kcap = std::max(ee, rows * (size_t)(knn_k > 0 ? knn_k : 1));      // whatever the masks hold
         ksend = take(kcap * 8); krecv = take(kcap * 8); ksums = take((size_t)2 * B * 8); ktot = take(64);
         korder = take(ee * 8); krowptr = take((nn + 1) * 8);
-        send = take(ee * 8); recv = take(ee * 8); ssend = take(ee * 8); srecv = take(ee * 8); order = take((oo + 1) * 8);
-        slot = take(ee * 8);
+        send = take(ee * 8); recv = take(ee * 8); order = take((oo + 1) * 8); slot = take(ee * 8);
         h0 = take(ee * R * 4); c0 = take(ee * R * 4); h1 = take(ee * R * 4); c1 = take(ee * R * 4);
-        logits = take(ee * K * 4); ew = take(ee * K * 4); out_c = take(nn * 16); new_h = take(nn * c.decoder_hidden * 4);
-        b_field = aether_dyn_field_workspace_bytes(Z.n_total, c.field_hidden);
+        logits = take(ee * K * 4); ew = take(ee * K * 4); new_h = take(nn * c.decoder_hidden * 4);
         b_knn = aether_knn_workspace_bytes(B, n_max, knn_k > 0 ? knn_k : 1);
+        ws_knn = take(b_knn);
+    }
+};
+struct DynBatchLayout : DynSceneLayout {
+    size_t field_c, ext_full, ssend, srecv, out_c, ws_field, ws_prior, ws_dec;
+    size_t b_field, b_prior, b_dec;
+    DynBatchLayout(const AetherDynStepConfig& c, int B, int n_max, const DynBatchSizes& Z) : DynSceneLayout(c, B, n_max, Z) {
+        const size_t nn = (size_t)Z.n_total, ee = (size_t)Z.e_total;
+        field_c = take(nn * 8); ext_full = take((size_t)B * n_max * 24); ssend = take(ee * 8); srecv = take(ee * 8);
+        out_c = take(nn * 16);
+        b_field = aether_dyn_field_workspace_bytes(Z.n_total, c.field_hidden);
         b_prior = aether_dyn_prior_workspace_bytes(c.encoder_hidden, c.rnn_hidden, c.prior_hidden, Z.n_total, Z.e_total);
         b_dec = aether_dyn_decoder_workspace_bytes(c.decoder_hidden, Z.n_total, Z.e_total);
-        ws_field = take(b_field); ws_knn = take(b_knn); ws_prior = take(b_prior); ws_dec = take(b_dec);
-        total = off;
+        ws_field = take(b_field); ws_prior = take(b_prior); ws_dec = take(b_dec);
     }
 };
 
@@ -87,14 +97,227 @@ int dyn_batch_check(const AetherDynStepConfig* c, int B, int n_max, const int64_
     if (Z->e_total > INT32_MAX / 64) return fail(AETHER_EINVAL, "dyn_step_batched: too many edges");
     return AETHER_OK;
 }
+
+int dyn_fail(int code, const char* entry, const char* what) {
+    snprintf(g_err, sizeof(g_err), "%s: %s", entry, what);
+    return code;
+}
 }  // namespace
 
-size_t aether_dyn_step_batched_workspace_bytes(const AetherDynStepConfig* config, int n_scenes, int n_objects_max,
-                                               const int64_t* n_present, const int64_t* n_edges, const int* in_degree) {
+extern "C++" {
+namespace {
+dim3 dyn_blocks(int64_t cnt) { return dim3((unsigned)((cnt + 255) / 256)); }
+// What a model's own launches of a step see: the checked sizes, the carved workspace and the caller's arrays.
+template <class Layout>
+struct DynStepCtx {
+    const AetherDynStepConfig& c; const DynScenes& S; const DynBatchSizes& Z; const Layout& L;
+    char* ws; void* stream;
+    int n; int64_t E, rows;                      // present objects and edges of all scenes; n_scenes * n_objects_max
+    const float* state; const int64_t *node_inds, *graph_send, *graph_recv, *edge2node;
+    float *prior_h, *prior_c, *decoder_hidden, *prediction;
+    hipStream_t st() const { return (hipStream_t)stream; }
+    float* fp(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+    int64_t* ip(size_t off) const { return reinterpret_cast<int64_t*>(ws + off); }
+    int* cidx() const { return reinterpret_cast<int*>(ws + L.cidx); }
+    int* status() const { return reinterpret_cast<int*>(ws + L.status); }
+};
+template <class Layout>
+size_t dyn_step_bytes(const AetherDynStepConfig* config, int n_scenes, int n_objects_max, const int64_t* n_present,
+                      const int64_t* n_edges, const int* in_degree) {
     DynScenes S; DynBatchSizes Z;
     if (dyn_batch_check(config, n_scenes, n_objects_max, n_present, n_edges, in_degree, &S, &Z)) return 0;
     if (Z.n_total == 0) return 512;
-    return DynBatchLayout(*config, n_scenes, n_objects_max, Z).total + 256;
+    return Layout(*config, n_scenes, n_objects_max, Z).total + 256;
+}
+
+// One prediction step of 1 .. 256 scenes.  The driver owns the refusals, the all-empty case, the workspace, the scene
+// bookkeeping (present objects, the encoder's kNN graphs by receiver) and the sample; a Model supplies
+//   Layout (a DynSceneLayout), step_name / rollout_name (the entries' names in messages), params_ok(),
+//   config_check(entry, c), counts_offset(X) (where its decoder's `counts` words lie in the workspace),
+//   field(X) (launches between the present rows and the kNN graphs), index(X), prior(X), decode(X, edge types).
+template <class Model>
+int dyn_step_run(const Model& M, const AetherDynStepConfig* config, int B, int n_max, const int64_t* n_present,
+                 const int64_t* n_edges, const int* in_degree, const float* state, const float* mask, const int64_t* node_inds,
+                 const int64_t* graph_send, const int64_t* graph_recv, const int64_t* edge2node, float* prior_h, float* prior_c,
+                 float* decoder_hidden, const float* uniform, float* prediction, float* edge_types, void* workspace,
+                 size_t workspace_bytes, void* stream) {
+    const char* name = Model::step_name;
+    if (!M.params_ok() || !state || !mask || !prior_h || !prior_c || !decoder_hidden || !prediction || !workspace)
+        return dyn_fail(AETHER_EINVAL, name, "null pointer");
+    DynScenes S; DynBatchSizes Z;
+    if (int rc = dyn_batch_check(config, B, n_max, n_present, n_edges, in_degree, &S, &Z)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const AetherDynStepConfig& c = *config;
+    const int64_t rows = (int64_t)B * n_max;
+    if (Z.n_total == 0) {                        // nobody anywhere: zeros, states untouched
+        HIP_OK(hipMemsetAsync(prediction, 0, (size_t)rows * 16, st));
+        return AETHER_OK;
+    }
+    if (!graph_send || !graph_recv || !edge2node || !uniform) return dyn_fail(AETHER_EINVAL, name, "null graph / uniform pointer");
+    if (int rc = M.config_check(name, c)) return rc;
+    const typename Model::Layout L(c, B, n_max, Z);
+    char* ws = reinterpret_cast<char*>(align_up((size_t)workspace, 256));
+    if (workspace_bytes < L.total + 256) return dyn_fail(AETHER_ESPACE, name, "workspace too small");
+    if (take_async_error()) return AETHER_EHIP;
+    const DynStepCtx<typename Model::Layout> X{c, S, Z, L, ws, stream, (int)Z.n_total, Z.e_total, rows, state, node_inds,
+                                               graph_send, graph_recv, edge2node, prior_h, prior_c, decoder_hidden, prediction};
+    const int R = c.rnn_hidden;
+    // ---- the present objects of every scene (mask -> rows), their state and decoder hidden rows
+    {
+        const size_t lds = ((size_t)3 * (DYN_MAX_SCENES + 1) + 257 + 2 * (size_t)n_max) * 4;
+        if (ensure_dynamic_lds(reinterpret_cast<const void*>(k_dynb_present), lds)) return AETHER_EHIP;
+        k_dynb_present<<<dim3((unsigned)B), dim3(256), lds, st>>>(S, state, mask, decoder_hidden, c.decoder_hidden, X.ip(L.idx),
+                                                                 X.cidx(), X.fp(L.cur_in), X.fp(L.cur_h), X.ip(L.rowptr_dec),
+                                                                 X.fp(L.div_node), X.status(), async_error_word(), X.ip(L.ksums),
+                                                                 reinterpret_cast<int*>(ws + M.counts_offset(X)));
+    }
+    if (int rc = M.field(X)) return rc;
+    // ---- the encoder's own kNN graphs, scene by scene, then grouped by receiver per scene
+    int64_t* ksums = X.ip(L.ksums);
+    if (int rc = knn_edges_impl(state, 4, mask, B, n_max, L.knn_k, X.ip(L.ksend), X.ip(L.krecv), ksums, ksums + B, X.ip(L.ktot),
+                                ws + L.ws_knn, L.b_knn, stream, true)) return rc;
+    {
+        const size_t lds = ((size_t)3 * (DYN_MAX_SCENES + 1) + 257 + 256 + (size_t)n_max) * 4;
+        if (ensure_dynamic_lds(reinterpret_cast<const void*>(k_dynb_csr), lds)) return AETHER_EHIP;
+        k_dynb_csr<<<dim3((unsigned)B), dim3(256), lds, st>>>(S, X.ip(L.ksend), X.ip(L.krecv), X.status(), X.ip(L.korder),
+                                                             X.ip(L.krowptr));
+    }
+    // ---- the callers' graphs in the numbering of the batch and the LSTM state rows of their edges; the prior step
+    M.index(X);
+    if (int rc = M.prior(X)) return rc;
+    // ... state back into its slots and the hard Gumbel sample of the edge types, one launch; a scene whose mask disagreed with
+    // its n poisons the rows (status[0] != 0)
+    float* ew = edge_types ? edge_types : X.fp(L.ew);
+    k_dyn_scatter_sample<<<dyn_blocks(X.E * (R / 4)), dim3(256), 0, st>>>(X.ip(L.slot), X.fp(L.h1), X.fp(L.c1), X.E, R, prior_h,
+                                                                         prior_c, X.fp(L.logits), uniform, c.gumbel_tau,
+                                                                         c.num_edge_types, ew, X.status(), 0);
+    // ---- decoder step on the callers' graphs, rows back to their objects
+    if (int rc = M.decode(X, ew)) return rc;
+    HIP_OK(hipGetLastError());
+    return AETHER_OK;
+}
+
+// ------------------------------------------------------------------ the prediction loop (predict_future)
+// Per step the burn-in mix and the model's step, queued without a host round trip.  Every per-step array is TIME-MAJOR -- inputs
+// [n_steps + 1][B][n_max][4], masks / burn_in_masks [n_steps][B][n_max], predictions [n_steps][B][n_max][4] -- and the host
+// size arrays [n_steps][B].
+template <class Layout>
+size_t dyn_rollout_bytes(const AetherDynStepConfig* config, int n_scenes, int n_objects_max, int n_steps, const int64_t* n_present,
+                         const int64_t* n_edges, const int* in_degree) {
+    if (!config || !n_present || !n_edges || !in_degree || n_steps <= 0 || n_scenes < 1) return 0;
+    size_t need = 0;
+    for (int t = 0; t < n_steps; ++t) {
+        const size_t b = dyn_step_bytes<Layout>(config, n_scenes, n_objects_max, n_present + (size_t)t * n_scenes,
+                                                n_edges + (size_t)t * n_scenes, in_degree + (size_t)t * n_scenes);
+        if (b == 0) return 0;
+        need = std::max(need, b);
+    }
+    return need + align_up((size_t)n_scenes * n_objects_max * 16, 256) + 256;
+}
+
+template <class Model>
+int dyn_rollout_run(const Model& M, const AetherDynStepConfig* config, int B, int n_objects_max, int n_steps, const float* inputs,
+                    const float* masks, const float* burn_in_masks, const int64_t* n_present, const int64_t* n_edges,
+                    const int* in_degree, const int64_t* const* node_inds, const int64_t* const* graph_send,
+                    const int64_t* const* graph_recv, const int64_t* const* edge2node, const float* const* uniform, float* prior_h,
+                    float* prior_c, float* decoder_hidden, float* predictions, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+    const char* name = Model::rollout_name;
+    if (!config || !inputs || !masks || !burn_in_masks || !n_present || !n_edges || !in_degree || !graph_send || !graph_recv ||
+        !edge2node || !uniform || !predictions || !workspace || !M.params_ok() || !prior_h || !prior_c || !decoder_hidden)
+        return dyn_fail(AETHER_EINVAL, name, "null pointer");
+    if (n_steps <= 0) return dyn_fail(AETHER_EINVAL, name, "n_steps must be positive");
+    // every step of every scene is validated on the host before anything is queued
+    for (int t = 0; t < n_steps; ++t) {
+        DynScenes S; DynBatchSizes Z;
+        if (int rc = dyn_batch_check(config, B, n_objects_max, n_present + (size_t)t * B, n_edges + (size_t)t * B,
+                                     in_degree + (size_t)t * B, &S, &Z)) return rc;
+        if (Z.n_total > 0 && (!graph_send[t] || !graph_recv[t] || !edge2node[t] || !uniform[t]))
+            return dyn_fail(AETHER_EINVAL, name, "a step's graph / uniform pointer is null");
+    }
+    if (int rc = M.config_check(name, *config)) return rc;
+    const size_t need = dyn_rollout_bytes<typename Model::Layout>(config, B, n_objects_max, n_steps, n_present, n_edges, in_degree);
+    if (need == 0) return dyn_fail(AETHER_EINVAL, name, "bad sizes");
+    if (workspace_bytes < need) return dyn_fail(AETHER_ESPACE, name, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = reinterpret_cast<char*>(align_up((size_t)workspace, 256));
+    float* state = reinterpret_cast<float*>(ws);
+    const size_t rows = (size_t)B * n_objects_max;
+    char* step_ws = ws + align_up(rows * 16, 256);
+    const size_t step_bytes = workspace_bytes - (size_t)(step_ws - (char*)workspace);
+    const size_t row = rows * 4;
+    for (int t = 0; t < n_steps; ++t) {
+        const float* last = t == 0 ? inputs : predictions + (size_t)(t - 1) * row;
+        k_dyn_mix<<<dyn_blocks((int64_t)row), dim3(256), 0, st>>>(inputs + (size_t)t * row, last, burn_in_masks + (size_t)t * rows,
+                                                                 (int)rows, state);
+        if (int rc = dyn_step_run(M, config, B, n_objects_max, n_present + (size_t)t * B, n_edges + (size_t)t * B,
+                                  in_degree + (size_t)t * B, state, masks + (size_t)t * rows, node_inds ? node_inds[t] : nullptr,
+                                  graph_send[t], graph_recv[t], edge2node[t], prior_h, prior_c, decoder_hidden, uniform[t],
+                                  predictions + (size_t)t * row, nullptr, step_ws, step_bytes, stream)) return rc;
+    }
+    return AETHER_OK;
+}
+
+// AetherDynamicVars on the driver: present, field, kNN, csr, index, prior, sample, decoder, finish.
+struct DynAetherModel {
+    using Layout = DynBatchLayout;
+    using Ctx = DynStepCtx<Layout>;
+    static constexpr const char* step_name = "dyn_step_batched";
+    static constexpr const char* rollout_name = "dyn_rollout_batched";
+    const AetherDynFieldQueryParams* field_params;
+    const AetherDynPriorParams* prior_params;
+    const AetherDynDecoderParams* decoder_params;
+    bool params_ok() const { return field_params && prior_params && decoder_params; }
+    int config_check(const char*, const AetherDynStepConfig&) const { return AETHER_OK; }   // (the stages check what they read)
+    size_t counts_offset(const Ctx& X) const { return X.L.ws_dec + DynDecLayout(X.c.decoder_hidden, X.n, X.E).counts; }
+    // field at the present objects (:64-79)
+    int field(const Ctx& X) const {
+        return aether_dyn_field(field_params, X.c.field_hidden, X.n, X.fp(X.L.cur_in), X.ws + X.L.ws_field, X.L.b_field,
+                                X.fp(X.L.field_c), X.stream);
+    }
+    // the callers' graphs in the numbering of the batch, LSTM state rows of their edges (:680-694), ext_full (:823)
+    void index(const Ctx& X) const {
+        const Layout& L = X.L;
+        const int R = X.c.rnn_hidden;
+        const int64_t work = std::max<int64_t>(std::max<int64_t>(X.E * (R / 4), X.rows * 6), X.Z.o_total);
+        k_dynb_index<<<dyn_blocks(work), dim3(256), 0, X.st()>>>(X.S, X.graph_send, X.graph_recv, X.node_inds, X.ip(L.idx),
+                                                                X.edge2node, R, X.prior_h, X.prior_c, X.ip(L.send), X.ip(L.recv),
+                                                                X.ip(L.ssend), X.ip(L.srecv), X.ip(L.slot), X.fp(L.h0), X.fp(L.c0),
+                                                                X.ip(L.order), X.state, X.fp(L.field_c), X.cidx(), X.fp(L.ext_full));
+    }
+    int prior(const Ctx& X) const {
+        const Layout& L = X.L;
+        const AetherDynStepConfig& c = X.c;
+        return aether_dyn_prior_step(prior_params, c.encoder_hidden, c.rnn_hidden, c.prior_layers, c.prior_hidden, c.num_edge_types,
+                                     c.encoder_polar, X.n, X.E, X.fp(L.cur_in), X.fp(L.field_c), X.fp(L.h0), X.fp(L.c0),
+                                     X.ip(L.ksend), X.ip(L.krecv), X.ip(L.korder), X.ip(L.krowptr), X.ws + L.ws_prior, L.b_prior,
+                                     X.fp(L.logits), X.fp(L.h1), X.fp(L.c1), X.stream);
+    }
+    // decoder step on the callers' graphs (:775-870), rows back to their objects
+    int decode(const Ctx& X, const float* ew) const {
+        const Layout& L = X.L;
+        const AetherDynStepConfig& c = X.c;
+        const int hd = c.decoder_hidden;
+        const DynPriorLayout PL(c.encoder_hidden, c.rnn_hidden, c.prior_hidden, X.n, X.E);
+        const DynSharedNodes shared{reinterpret_cast<const float*>(X.ws + L.ws_prior + PL.ext),
+                                    reinterpret_cast<const float*>(X.ws + L.ws_prior + PL.rel),
+                                    reinterpret_cast<const float*>(X.ws + L.ws_prior + PL.Rinv), true};
+        if (int rc = dyn_decoder_impl(decoder_params, hd, c.num_edge_types, c.skip_first, c.decoder_polar, X.n, X.E, X.fp(L.cur_in),
+                                      X.fp(L.cur_h), ew, X.fp(L.field_c), X.fp(L.ext_full), X.ip(L.ssend), X.ip(L.srecv),
+                                      X.ip(L.send), X.ip(L.recv), X.ip(L.order), X.ip(L.rowptr_dec), 1.0f, X.fp(L.div_node),
+                                      X.ws + L.ws_dec, L.b_dec, X.fp(L.out_c), X.fp(L.new_h), X.st(), &shared)) return rc;
+        const int64_t work = std::max<int64_t>(X.rows * 4, (int64_t)X.n * (hd / 4));
+        k_dynb_finish<<<dyn_blocks(work), dim3(256), 0, X.st()>>>(X.fp(L.out_c), X.fp(L.new_h), X.cidx(), X.ip(L.idx), X.status(),
+                                                                 X.rows, X.n, hd, X.prediction, X.decoder_hidden);
+        return AETHER_OK;
+    }
+};
+}  // namespace
+}  // extern "C++"
+
+size_t aether_dyn_step_batched_workspace_bytes(const AetherDynStepConfig* config, int n_scenes, int n_objects_max,
+                                               const int64_t* n_present, const int64_t* n_edges, const int* in_degree) {
+    return dyn_step_bytes<DynBatchLayout>(config, n_scenes, n_objects_max, n_present, n_edges, in_degree);
 }
 
 int aether_dyn_step_batched(const AetherDynFieldQueryParams* field_params, const AetherDynPriorParams* prior_params,
@@ -104,100 +327,14 @@ int aether_dyn_step_batched(const AetherDynFieldQueryParams* field_params, const
                             const int64_t* graph_recv, const int64_t* edge2node, float* prior_h, float* prior_c,
                             float* decoder_hidden, const float* uniform, float* prediction, float* edge_types,
                             void* workspace, size_t workspace_bytes, void* stream) {
-    if (!field_params || !prior_params || !decoder_params || !state || !mask || !prior_h || !prior_c || !decoder_hidden ||
-        !prediction || !workspace)
-        return fail(AETHER_EINVAL, "dyn_step_batched: null pointer");
-    DynScenes S; DynBatchSizes Z;
-    if (int rc = dyn_batch_check(config, n_scenes, n_objects_max, n_present, n_edges, in_degree, &S, &Z)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const AetherDynStepConfig& c = *config;
-    const int B = n_scenes, n_max = n_objects_max, R = c.rnn_hidden, K = c.num_edge_types, hd = c.decoder_hidden;
-    const int64_t rows = (int64_t)B * n_max;
-    if (Z.n_total == 0) {                        // nobody anywhere: zeros, states untouched (:841-843)
-        HIP_OK(hipMemsetAsync(prediction, 0, (size_t)rows * 16, st));
-        return AETHER_OK;
-    }
-    if (!graph_send || !graph_recv || !edge2node || !uniform) return fail(AETHER_EINVAL, "dyn_step_batched: null graph / uniform pointer");
-    const int n = (int)Z.n_total;
-    const int64_t E = Z.e_total;
-    DynBatchLayout L(c, B, n_max, Z);
-    char* ws = reinterpret_cast<char*>(align_up((size_t)workspace, 256));
-    if (workspace_bytes < L.total + 256) return fail(AETHER_ESPACE, "dyn_step_batched: workspace too small");
-    if (take_async_error()) return AETHER_EHIP;
-    auto fp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto ip = [&](size_t off) { return reinterpret_cast<int64_t*>(ws + off); };
-    auto blocks = [](int64_t cnt) { return dim3((unsigned)((cnt + 255) / 256)); };
-    int* cidx = reinterpret_cast<int*>(ws + L.cidx);
-    int* status = reinterpret_cast<int*>(ws + L.status);
-    // ---- the present objects of every scene (mask -> rows), their state and decoder hidden rows
-    {
-        const size_t lds = ((size_t)3 * (DYN_MAX_SCENES + 1) + 257 + 2 * (size_t)n_max) * 4;
-        if (ensure_dynamic_lds(reinterpret_cast<const void*>(k_dynb_present), lds)) return AETHER_EHIP;
-        const DynDecLayout DL(hd, n, E);
-        k_dynb_present<<<dim3((unsigned)B), dim3(256), lds, st>>>(S, state, mask, decoder_hidden, hd, ip(L.idx), cidx, fp(L.cur_in),
-                                                                 fp(L.cur_h), ip(L.rowptr_dec), fp(L.div_node), status,
-                                                                 async_error_word(), ip(L.ksums),
-                                                                 reinterpret_cast<int*>(ws + L.ws_dec + DL.counts));
-    }
-    // ---- field at the present objects (:64-79)
-    if (int rc = aether_dyn_field(field_params, c.field_hidden, n, fp(L.cur_in), ws + L.ws_field, L.b_field, fp(L.field_c), stream))
-        return rc;
-    // ---- the encoder's own kNN graphs (:528, :559-586), scene by scene, then grouped by receiver per scene
-    int64_t* ksums = ip(L.ksums);
-    if (int rc = knn_edges_impl(state, 4, mask, B, n_max, L.knn_k, ip(L.ksend), ip(L.krecv), ksums, ksums + B, ip(L.ktot),
-                                ws + L.ws_knn, L.b_knn, stream, true)) return rc;
-    {
-        const size_t lds = ((size_t)3 * (DYN_MAX_SCENES + 1) + 257 + 256 + (size_t)n_max) * 4;
-        if (ensure_dynamic_lds(reinterpret_cast<const void*>(k_dynb_csr), lds)) return AETHER_EHIP;
-        k_dynb_csr<<<dim3((unsigned)B), dim3(256), lds, st>>>(S, ip(L.ksend), ip(L.krecv), status, ip(L.korder), ip(L.krowptr));
-    }
-    // ---- the callers' graphs in the numbering of the batch, LSTM state rows of their edges (:680-694), ext_full (:823)
-    {
-        const int64_t work = std::max<int64_t>(std::max<int64_t>(E * (R / 4), rows * 6), Z.o_total);
-        k_dynb_index<<<blocks(work), dim3(256), 0, st>>>(S, graph_send, graph_recv, node_inds, ip(L.idx), edge2node, R, prior_h,
-                                                        prior_c, ip(L.send), ip(L.recv), ip(L.ssend), ip(L.srecv), ip(L.slot),
-                                                        fp(L.h0), fp(L.c0), ip(L.order), state, fp(L.field_c), cidx,
-                                                        fp(L.ext_full));
-    }
-    if (int rc = aether_dyn_prior_step(prior_params, c.encoder_hidden, R, c.prior_layers, c.prior_hidden, K, c.encoder_polar, n, E,
-                                       fp(L.cur_in), fp(L.field_c), fp(L.h0), fp(L.c0), ip(L.ksend), ip(L.krecv), ip(L.korder),
-                                       ip(L.krowptr), ws + L.ws_prior, L.b_prior, fp(L.logits), fp(L.h1), fp(L.c1), stream))
-        return rc;
-    // ... state back into its slots and the hard Gumbel sample of the edge types (:137-141), one launch; a scene whose mask
-    // disagreed with its n poisons the rows (status[0] != 0)
-    float* ew = edge_types ? edge_types : fp(L.ew);
-    k_dyn_scatter_sample<<<blocks(E * (R / 4)), dim3(256), 0, st>>>(ip(L.slot), fp(L.h1), fp(L.c1), E, R, prior_h, prior_c,
-                                                                   fp(L.logits), uniform, c.gumbel_tau, K, ew, status, 0);
-    // ---- decoder step on the callers' graphs (:775-870), rows back to their objects
-    const DynPriorLayout PL(c.encoder_hidden, R, c.prior_hidden, n, E);
-    const DynSharedNodes shared{reinterpret_cast<const float*>(ws + L.ws_prior + PL.ext),
-                                reinterpret_cast<const float*>(ws + L.ws_prior + PL.rel),
-                                reinterpret_cast<const float*>(ws + L.ws_prior + PL.Rinv), true};
-    if (int rc = dyn_decoder_impl(decoder_params, hd, K, c.skip_first, c.decoder_polar, n, E, fp(L.cur_in), fp(L.cur_h), ew,
-                                  fp(L.field_c), fp(L.ext_full), ip(L.ssend), ip(L.srecv), ip(L.send), ip(L.recv), ip(L.order),
-                                  ip(L.rowptr_dec), 1.0f, fp(L.div_node), ws + L.ws_dec, L.b_dec, fp(L.out_c), fp(L.new_h), stream,
-                                  &shared)) return rc;
-    const int64_t work = std::max<int64_t>(rows * 4, (int64_t)n * (hd / 4));
-    k_dynb_finish<<<blocks(work), dim3(256), 0, st>>>(fp(L.out_c), fp(L.new_h), cidx, ip(L.idx), status, rows, n, hd, prediction,
-                                                     decoder_hidden);
-    HIP_OK(hipGetLastError());
-    return AETHER_OK;
+    return dyn_step_run(DynAetherModel{field_params, prior_params, decoder_params}, config, n_scenes, n_objects_max, n_present,
+                        n_edges, in_degree, state, mask, node_inds, graph_send, graph_recv, edge2node, prior_h, prior_c,
+                        decoder_hidden, uniform, prediction, edge_types, workspace, workspace_bytes, stream);
 }
 
-// ------------------------------------------------------------------ the prediction loop (predict_future, :245-273)
-// Per step the burn-in mix and aether_dyn_step_batched, queued without a host round trip.  Every per-step array is TIME-MAJOR -- inputs [n_steps + 1][B][n_max][4],
-// masks / burn_in_masks [n_steps][B][n_max], predictions [n_steps][B][n_max][4] -- and the host size arrays [n_steps][B].
 size_t aether_dyn_rollout_batched_workspace_bytes(const AetherDynStepConfig* config, int n_scenes, int n_objects_max, int n_steps,
                                                   const int64_t* n_present, const int64_t* n_edges, const int* in_degree) {
-    if (!config || !n_present || !n_edges || !in_degree || n_steps <= 0 || n_scenes < 1) return 0;
-    size_t need = 0;
-    for (int t = 0; t < n_steps; ++t) {
-        const size_t b = aether_dyn_step_batched_workspace_bytes(config, n_scenes, n_objects_max, n_present + (size_t)t * n_scenes,
-                                                                 n_edges + (size_t)t * n_scenes, in_degree + (size_t)t * n_scenes);
-        if (b == 0) return 0;
-        need = std::max(need, b);
-    }
-    return need + align_up((size_t)n_scenes * n_objects_max * 16, 256) + 256;
+    return dyn_rollout_bytes<DynBatchLayout>(config, n_scenes, n_objects_max, n_steps, n_present, n_edges, in_degree);
 }
 
 int aether_dyn_rollout_batched(const AetherDynFieldQueryParams* field_params, const AetherDynPriorParams* prior_params,
@@ -208,42 +345,9 @@ int aether_dyn_rollout_batched(const AetherDynFieldQueryParams* field_params, co
                                const int64_t* const* graph_recv, const int64_t* const* edge2node, const float* const* uniform,
                                float* prior_h, float* prior_c, float* decoder_hidden, float* predictions, void* workspace,
                                size_t workspace_bytes, void* stream) {
-    if (!config || !inputs || !masks || !burn_in_masks || !n_present || !n_edges || !in_degree || !graph_send || !graph_recv ||
-        !edge2node || !uniform || !predictions || !workspace || !field_params || !prior_params || !decoder_params || !prior_h ||
-        !prior_c || !decoder_hidden)
-        return fail(AETHER_EINVAL, "dyn_rollout_batched: null pointer");
-    if (n_steps <= 0) return fail(AETHER_EINVAL, "dyn_rollout_batched: n_steps must be positive");
-    const int B = n_scenes;
-    // every step of every scene is validated on the host before anything is queued
-    for (int t = 0; t < n_steps; ++t) {
-        DynScenes S; DynBatchSizes Z;
-        if (int rc = dyn_batch_check(config, B, n_objects_max, n_present + (size_t)t * B, n_edges + (size_t)t * B,
-                                     in_degree + (size_t)t * B, &S, &Z)) return rc;
-        if (Z.n_total > 0 && (!graph_send[t] || !graph_recv[t] || !edge2node[t] || !uniform[t]))
-            return fail(AETHER_EINVAL, "dyn_rollout_batched: a step's graph / uniform pointer is null");
-    }
-    const size_t need = aether_dyn_rollout_batched_workspace_bytes(config, B, n_objects_max, n_steps, n_present, n_edges, in_degree);
-    if (need == 0) return fail(AETHER_EINVAL, "dyn_rollout_batched: bad sizes");
-    if (workspace_bytes < need) return fail(AETHER_ESPACE, "dyn_rollout_batched: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>(align_up((size_t)workspace, 256));
-    float* state = reinterpret_cast<float*>(ws);
-    const size_t rows = (size_t)B * n_objects_max;
-    char* step_ws = ws + align_up(rows * 16, 256);
-    const size_t step_bytes = workspace_bytes - (size_t)(step_ws - (char*)workspace);
-    const size_t row = rows * 4;
-    for (int t = 0; t < n_steps; ++t) {
-        const float* last = t == 0 ? inputs : predictions + (size_t)(t - 1) * row;
-        float* pred = predictions + (size_t)t * row;
-        k_dyn_mix<<<dim3((unsigned)((row + 255) / 256)), dim3(256), 0, st>>>(inputs + (size_t)t * row, last,
-                                                                            burn_in_masks + (size_t)t * rows, (int)rows, state);
-        if (int rc = aether_dyn_step_batched(field_params, prior_params, decoder_params, config, B, n_objects_max,
-                                             n_present + (size_t)t * B, n_edges + (size_t)t * B, in_degree + (size_t)t * B, state,
-                                             masks + (size_t)t * rows, node_inds ? node_inds[t] : nullptr, graph_send[t],
-                                             graph_recv[t], edge2node[t], prior_h, prior_c, decoder_hidden, uniform[t], pred,
-                                             nullptr, step_ws, step_bytes, stream)) return rc;
-    }
-    return AETHER_OK;
+    return dyn_rollout_run(DynAetherModel{field_params, prior_params, decoder_params}, config, n_scenes, n_objects_max, n_steps,
+                           inputs, masks, burn_in_masks, n_present, n_edges, in_degree, node_inds, graph_send, graph_recv,
+                           edge2node, uniform, prior_h, prior_c, decoder_hidden, predictions, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------ one scene: n_scenes = 1 of the above

@@ -18,6 +18,7 @@ from ... import _lib
 from ..seq2seq.encoder import gumbel_softmax_hard
 from ..seq2seq.field import _CoordinateEmbedding
 from ._rollout import SceneRolloutMixin
+from ._scene import ScenePack, _DynStepConfig, cached_workspace, pack_scenes      # noqa: F401  (ScenePack, pack_scenes: re-exported)
 from .decoder import Decoder
 from .encoder import Encoder
 
@@ -26,86 +27,9 @@ class _DynFieldQueryParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("B", "ang_w", "ang_b", "w0", "b0", "w2", "b2", "w4", "b4")]
 
 
-class _DynStepConfig(C.Structure):                      # AetherDynStepConfig of include/aether_hip.h
-    _fields_ = [(n, C.c_int) for n in ("field_hidden", "encoder_hidden", "rnn_hidden", "prior_layers", "prior_hidden",
-                                       "num_edge_types", "decoder_hidden", "skip_first", "encoder_polar", "decoder_polar",
-                                       "knn_k")] + [("gumbel_tau", C.c_float)]
-
-
-class ScenePack:
-    """The per-frame graphs of B scenes, built on the device by ``pack_scenes`` (``aether_dyn_scene_pack``): what the
-    reference's data set keeps as Python lists per scene and per frame (experiments/ind/single_ind_data.py:70-89).
-    ``buf`` holds the arrays, ``view`` the device pointers and per-frame strides into it, ``n_present`` / ``n_edges`` /
-    ``in_degree`` the host arrays [n_frames][B] the rollout takes as they are."""
-
-    def __init__(self, buf, view, n_present, n_edges, in_degree, n_scenes, n_frames, n_objects_max, k):
-        self.buf, self.view, self.n_present, self.n_edges, self.in_degree = buf, view, n_present, n_edges, in_degree
-        self.n_scenes, self.n_frames, self.n_objects_max, self.k = n_scenes, n_frames, n_objects_max, k
-
-    def _frames(self, ptr, stride):
-        """[n_frames][stride] int64 view of one of the pack's arrays."""
-        lo = ptr - self.buf.data_ptr()
-        return self.buf[lo:lo + self.n_frames * stride * 8].view(torch.int64).view(self.n_frames, stride)
-
-    def arrays(self):
-        """(node_inds [n_frames][B Nmax], graph_send, graph_recv, edge2node [n_frames][B Nmax k]): views into the pack; of
-        frame t the first sum_b n_present[t][b] / sum_b n_edges[t][b] entries are meaningful."""
-        v = self.view
-        return (self._frames(v.node_inds, v.node_stride), self._frames(v.graph_send, v.edge_stride),
-                self._frames(v.graph_recv, v.edge_stride), self._frames(v.edge2node, v.edge_stride))
-
-    def counts(self):
-        """(n_present, n_edges, in_degree) as host int64 tensors [n_frames][B]."""
-        shape = (self.n_frames, self.n_scenes)
-        return tuple(torch.tensor(list(a), dtype=torch.int64).view(shape) for a in (self.n_present, self.n_edges,
-                                                                                     self.in_degree))
-
-    def as_lists(self):
-        """-> (node_inds[b][t], graph_info[b][t] = (send, recv, edge2node [n][in_degree])): views into the pack, in the form
-        ``predict_future`` takes (the compatibility path: this is per-(scene, frame) Python again)."""
-        ni, gs, gr, e2n = self.arrays()
-        n, e, d = (c.tolist() for c in self.counts())
-        B = self.n_scenes
-        node_inds, graph_info = [[] for _ in range(B)], [[] for _ in range(B)]
-        for t in range(self.n_frames):
-            no = eo = 0
-            for b in range(B):
-                nb, eb = n[t][b], e[t][b]
-                node_inds[b].append(ni[t, no:no + nb])
-                graph_info[b].append((gs[t, eo:eo + eb], gr[t, eo:eo + eb],
-                                      e2n[t, eo:eo + eb].view(nb, d[t][b]) if nb else e2n[t, eo:eo].view(0, 1)))
-                no += nb; eo += eb
-        return node_inds, graph_info
-
-
-@torch.no_grad()
-def pack_scenes(inputs, masks, k=10):
-    """inputs [B, T, Nmax, 4], masks [B, T, Nmax] (device) -> ``ScenePack`` of all T frames: present rows, kNN graph of the
-    ground-truth positions (``k`` neighbours) and edge2node per (scene, frame), in ONE library call with one
-    device-to-host copy (the counts).  Raises if a scene has exactly one present object in a frame."""
-    if not inputs.is_cuda:
-        raise _lib.AetherHipError("pack_scenes runs on an MI355X only; got a CPU tensor (there is no CPU fallback)")
-    lib = _lib.load()
-    dev = inputs.device
-    B, T, Nmax = int(inputs.size(0)), int(inputs.size(1)), int(inputs.size(2))
-    if inputs.size(-1) != 4 or tuple(masks.shape) != (B, T, Nmax):
-        raise ValueError("pack_scenes: inputs must be [B, T, Nmax, 4] and masks [B, T, Nmax]")
-    x = inputs.detach().to(torch.float32).transpose(0, 1).contiguous()                  # time-major, as the rollout takes it
-    m = masks.detach().to(device=dev, dtype=torch.float32).transpose(0, 1).contiguous()
-    need = lib.aether_dyn_scene_pack_bytes(B, Nmax, T, int(k))
-    if need == 0:
-        raise _lib.AetherHipError("aether_dyn_scene_pack_bytes: " + lib.aether_last_error().decode())
-    buf = torch.empty(need, dtype=torch.uint8, device=dev)
-    view = _lib.AetherDynScenePack()
-    n_present, n_edges, in_degree = (C.c_int64 * (T * B))(), (C.c_int64 * (T * B))(), (C.c_int * (T * B))()
-    st = lib.aether_dyn_scene_pack(x.data_ptr(), m.data_ptr(), B, Nmax, T, int(k), buf.data_ptr(), buf.numel(), C.byref(view),
-                                   n_present, n_edges, in_degree, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(st, "aether_dyn_scene_pack")
-    return ScenePack(buf, view, n_present, n_edges, in_degree, B, T, Nmax, int(k))
-
-
 class AetherDynamicVars(SceneRolloutMixin, nn.Module):
     one_call_step = True       # predict_future's steps go through aether_dyn_step (False: the three staged calls + torch glue)
+    _STEP_WS_CAPTURE_CHECK = "the step workspace must be reserved outside graph capture (reserve())"
 
     def __init__(self, params, device="cuda"):
         super().__init__()
@@ -125,12 +49,6 @@ class AetherDynamicVars(SceneRolloutMixin, nn.Module):
         self._ws = None
         if device is not None:
             self.to(device)
-
-    def save(self, path):
-        torch.save(self.state_dict(), path)                       # as the reference's save / load
-
-    def load(self, path):
-        self.load_state_dict(torch.load(path))
 
     def _field_struct(self):
         fn = self.field_net
@@ -166,10 +84,9 @@ class AetherDynamicVars(SceneRolloutMixin, nn.Module):
         h = self.field_hidden
         ps = self._field_struct()
         need = lib.aether_dyn_field_workspace_bytes(n, h)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        ws = cached_workspace(self, "_ws", need, x.device)
         out = torch.empty(n, 2, dtype=torch.float32, device=x.device)
-        st = lib.aether_dyn_field(C.byref(ps), h, n, xs.data_ptr(), self._ws.data_ptr(), self._ws.numel(), out.data_ptr(),
+        st = lib.aether_dyn_field(C.byref(ps), h, n, xs.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(),
                                   torch.cuda.current_stream(x.device).cuda_stream)
         _lib.check(st, "aether_dyn_field")
         if idx is None:
@@ -217,51 +134,14 @@ class AetherDynamicVars(SceneRolloutMixin, nn.Module):
                               1 if enc.pos_representation == "polar" else 0, 1 if dec.pos_representation == "polar" else 0,
                               10, float(self.gumbel_temp))
 
-    @torch.no_grad()
-    def _step_one_call(self, state, present, node_inds_t, gsend, grecv, e2n, prior_h, prior_c, dec_state, uniform_t,
-                       pass_node_inds=True, return_edge_types=False):
-        """``_step_core`` as ONE library call (``aether_dyn_step``): the same stage kernels, the index work between them in
-        seven small kernels of the library instead of ~60 torch launches; bit-identical to the staged path."""
-        lib = _lib.load()
-        dev = state.device
-        if self.encoder.training:
-            raise _lib.AetherHipError("the prior step uses BatchNorm running statistics: call .eval() first")
-        Nmax, n, E = int(state.shape[1]), int(node_inds_t.numel()), int(gsend.numel())
-        if grecv.numel() != E or e2n.ndim != 2 or e2n.shape[0] != n or uniform_t.numel() != E * self.num_edge_types:
-            raise ValueError("graph_info / uniform do not match the present objects")
-        i64 = lambda t: t.to(device=dev, dtype=torch.int64).contiguous()
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        state, present, uniform_t = f32(state), f32(present).reshape(-1), f32(uniform_t)
-        ni, gs, gr, e2n = i64(node_inds_t), i64(gsend), i64(grecv), i64(e2n)
-        if self.__dict__.get("_kernel_copies"):        # diagnostic (tools/dyn_graph_repro.py): copies as kernels, not memcpy nodes
-            new_h, new_c, new_dec = (torch.add(f32(t), 0.0) for t in (prior_h, prior_c, dec_state))
-        else:
-            new_h, new_c, new_dec = f32(prior_h).clone(), f32(prior_c).clone(), f32(dec_state).clone()
-        cfg = self._step_config()
-        need = lib.aether_dyn_step_workspace_bytes(C.byref(cfg), Nmax, n, E)
-        if need == 0:
-            raise _lib.AetherHipError("aether_dyn_step_workspace_bytes: " + lib.aether_last_error().decode())
-        ws = self.__dict__.get("_step_ws")
-        if ws is None or ws.numel() < need or ws.device != dev:
-            if torch.cuda.is_current_stream_capturing():
-                raise _lib.AetherHipError("the step workspace must be reserved outside graph capture (reserve())")
-            ws = self.__dict__["_step_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        pred = torch.empty(1, Nmax, 4, dtype=torch.float32, device=dev)
-        edge_types = torch.empty(E, self.num_edge_types, dtype=torch.float32, device=dev) if return_edge_types else None
-        fs = self._field_struct()
-        ps_e = self.encoder._param_struct()[0]
-        ps_d = self.decoder._param_struct()
-        # node_inds = None: the library takes the mask's non-zero rows (what the data set's node_inds are)
-        st = lib.aether_dyn_step(C.byref(fs), C.byref(ps_e), C.byref(ps_d), C.byref(cfg), Nmax, n, E, state.data_ptr(),
-                                 present.data_ptr(), ni.data_ptr() if pass_node_inds else None, gs.data_ptr(), gr.data_ptr(),
-                                 e2n.data_ptr(), int(e2n.shape[1]), new_h.data_ptr(), new_c.data_ptr(), new_dec.data_ptr(),
-                                 uniform_t.data_ptr(), pred.data_ptr(),
-                                 edge_types.data_ptr() if edge_types is not None else None, ws.data_ptr(), ws.numel(),
-                                 torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(st, "aether_dyn_step")
-        if return_edge_types:
-            return pred, new_h, new_c, new_dec, edge_types
-        return pred, new_h, new_c, new_dec
+    def _step_entries(self, lib):
+        """One step of one scene (``SceneRolloutMixin._step_one_call``): the single-scene ``aether_dyn_step``, which sizes for
+        the largest in_degree a step accepts and takes the actual one behind the graph."""
+        def step(cfg, Nmax, n, E, in_degree, state, mask, node_inds, send, recv, e2n, *rest):
+            head = (self._field_struct(), self.encoder._param_struct()[0], self.decoder._param_struct())
+            return lib.aether_dyn_step(*(C.byref(h) for h in head), cfg, Nmax, n, E, state, mask, node_inds, send, recv, e2n,
+                                       in_degree, *rest)
+        return (lambda cfg, Nmax, n, E, in_degree: lib.aether_dyn_step_workspace_bytes(cfg, Nmax, n, E)), step, "aether_dyn_step"
 
     @torch.no_grad()
     def _step_core(self, state, present, node_inds_t, gsend, grecv, e2n, prior_h, prior_c, dec_state, uniform_t):
@@ -298,16 +178,9 @@ class AetherDynamicVars(SceneRolloutMixin, nn.Module):
             for n in range(2, int(n_objects_max) + 1):
                 need_s = max(need_s, lib.aether_dyn_step_workspace_bytes(C.byref(cfg), int(n_objects_max), n,
                                                                          n * min(int(k), n - 1)))
-            ws = self.__dict__.get("_step_ws")
-            if ws is None or ws.numel() < need_s or ws.device != dev:
-                if torch.cuda.is_current_stream_capturing():
-                    raise _lib.AetherHipError("reserve() must run outside graph capture")
-                self.__dict__["_step_ws"] = torch.empty(need_s, dtype=torch.uint8, device=dev)
+            cached_workspace(self, "_step_ws", need_s, dev, capture_check="reserve() must run outside graph capture")
         for mod, need in ((self, need_f), (self.encoder, need_e), (self.decoder, need_d)):
-            if mod._ws is None or mod._ws.numel() < need or mod._ws.device != dev:
-                if torch.cuda.is_current_stream_capturing():
-                    raise _lib.AetherHipError("reserve() must run outside graph capture")
-                mod._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            cached_workspace(mod, "_ws", need, dev, capture_check="reserve() must run outside graph capture")
 
     def _captured_step(self, args):
         """``_step_core`` as a hipGraph replay, one graph per (present objects, edges, slots) signature.
@@ -347,8 +220,7 @@ class AetherDynamicVars(SceneRolloutMixin, nn.Module):
         # one replay in flight at a time: replays of a captured step enqueued behind a running one ended in a GPU memory
         # access fault while the decoder's all-types filter kernel was a graph node (bisected to that node
         # and the runtime's graph packet capture; the library no longer launches it) -- kept as a second line of defence
-        if not self.__dict__.get("_capture_one_call"):
-            torch.cuda.current_stream(static[0].device).synchronize()
+        torch.cuda.current_stream(static[0].device).synchronize()
         g.replay()
         # graphs share one memory pool: a later replay of another signature may reuse these buffers
         return tuple(o.clone() for o in outs)
@@ -359,79 +231,43 @@ class AetherDynamicVars(SceneRolloutMixin, nn.Module):
         present objects and their graph per time step.  ``uniform``: per-step Gumbel draws (list of [E_t, K]).
         With B > 1 scenes (inputs [B, T, Nmax, 4], node_inds[b][t], graph_info[b][t], uniform[t][b]) every time step is
         ONE batched call per stage (predict_future_batched) -- the reference raises on batch > 1 (:588-591).
-        One scene, default: the whole loop is ONE library call (``_predict_future_rollout``).  With ``one_call_step = False``
+        One scene, default: the whole loop is ONE library call (``_predict_future_rollout``: 52 launches per step, no host
+        round trip, nothing left for a captured graph to save -- measured 0.35 ms per step against 0.41 ms for replays of a
+        captured aether_dyn_step; ``graph=True`` is accepted and means the same thing there).  With ``one_call_step = False``
         (the staged calls + torch glue of rounds 1-2) ``graph=True`` replays a captured hipGraph per step signature
         (``_captured_step``); bit-identical to the eager loop either way."""
-        if inputs.size(0) > 1:
-            return self.predict_future_batched(inputs, masks, node_inds, graph_info, burn_in_masks, uniform)
-        n_steps = inputs.size(1) - 1
-        if self.one_call_step and n_steps > 0 and not (graph and self.__dict__.get("_capture_one_call")):
-            # ONE library call queues the whole loop (52 launches per step, no host round trip): nothing left for a
-            # captured graph to save -- measured 0.35 ms per step against 0.41 ms for replays of a captured
-            # aether_dyn_step.  ``graph=True`` is accepted and means the same thing here.  (DESIGN.md 4.11c: replays of a
-            # captured step in flight behind each other faulted while the decoder's all-types filter kernel was a graph
-            # node -- a runtime replay problem, bisected and avoided in the library.)
-            return self._predict_future_rollout(inputs, masks, node_inds, graph_info, burn_in_masks,
-                                                None if uniform is None else [[u] for u in uniform])
-        prior_state = self.encoder.get_initial_hidden(inputs)
-        dec_state = self.decoder.get_initial_hidden(inputs)
-        last = inputs[:, 0]
-        preds = []
-        dev = inputs.device
-        for t in range(n_steps):
-            present = masks[:, t]
-            observed = burn_in_masks[:, t].unsqueeze(-1).type(inputs.dtype)
-            # observed objects are fed their ground truth, the others the model's own last prediction (:264)
-            state = observed * inputs[:, t] + (1 - observed) * last
-            # the data set hands over the present objects of every step (node_inds, built from the masks): their number
-            # is known on the host, which spares the three stages their device round trips (mask -> index list)
-            ni_t = node_inds[0][t]
-            n_t = int(ni_t.numel())
-            if n_t >= 2:
-                gs, gr, e2n = (g.to(dev) for g in graph_info[0][t])
-                u_t = uniform[t] if uniform is not None else torch.rand(gs.numel(), self.num_edge_types, device=dev)
-                args = (state.to(torch.float32), present.to(dev).to(torch.float32), ni_t.to(dev), gs, gr, e2n,
-                        prior_state[0], prior_state[1], dec_state.to(torch.float32),
-                        u_t.to(dev).reshape(gs.numel(), self.num_edge_types).to(torch.float32))
-                last, new_h, new_c, dec_state = self._captured_step(args) if graph else self._step_core(*args)
-                prior_state = (new_h, new_c)
-            else:                                                  # nobody or one object: the stages' own early exits
-                field, _ = self.predict_field(state, present, n_present=n_t)
-                logits, prior_state = self.encoder.single_step_forward(state, present, ni_t, graph_info[0][t], prior_state,
-                                                                       field, n_present=n_t)
-                last, dec_state, _ = self.single_step_forward(state, present, graph_info[0][t], dec_state, logits, True, field,
-                                                              None if uniform is None else uniform[t], n_present=n_t)
-            preds.append(last)
-        return torch.stack(preds, dim=1)
+        return self._predict_future(inputs, masks, node_inds, graph_info, burn_in_masks, uniform, graph=graph)
+
+    def _staged_step(self, state, present, ni_t, gi_t, prior_state, dec_state, uniform_t, graph=False):
+        # the data set hands over the present objects of every step (node_inds, built from the masks): their number
+        # is known on the host, which spares the three stages their device round trips (mask -> index list)
+        dev = state.device
+        n_t = int(ni_t.numel())
+        if n_t >= 2:
+            gs, gr, e2n = (g.to(dev) for g in gi_t)
+            u_t = uniform_t if uniform_t is not None else torch.rand(gs.numel(), self.num_edge_types, device=dev)
+            args = (state.to(torch.float32), present.to(dev).to(torch.float32), ni_t.to(dev), gs, gr, e2n,
+                    prior_state[0], prior_state[1], dec_state.to(torch.float32),
+                    u_t.to(dev).reshape(gs.numel(), self.num_edge_types).to(torch.float32))
+            last, new_h, new_c, dec_state = self._captured_step(args) if graph else self._step_core(*args)
+            return last, (new_h, new_c), dec_state
+        # nobody or one object: the stages' own early exits
+        field, _ = self.predict_field(state, present, n_present=n_t)
+        logits, prior_state = self.encoder.single_step_forward(state, present, ni_t, gi_t, prior_state, field, n_present=n_t)
+        last, dec_state, _ = self.single_step_forward(state, present, gi_t, dec_state, logits, True, field, uniform_t,
+                                                      n_present=n_t)
+        return last, prior_state, dec_state
+
+    def _batched_staged_step(self, state, present, ni_t, gi_t, prior_state, dec_state, uniform_t):
+        """B scenes through the staged calls (``one_call_step = False``, or more than 256 scenes): one field query, one
+        kNN + prior step, one sampling pass and one decoder step over the present objects of ALL scenes."""
+        field, _ = self.predict_field(state, present)
+        logits, prior_state = self.encoder.single_step_forward_batched(state, present, ni_t, gi_t, prior_state, field)
+        last, dec_state, _ = self.single_step_forward(state, present, gi_t, dec_state, logits, True, field, uniform_t)
+        return last, prior_state, dec_state
 
     def _rollout_entries(self, lib):
         """The entries ``_predict_future_rollout`` / ``predict_future_packed`` (``_rollout.SceneRolloutMixin``) call."""
         head = (self._field_struct(), self.encoder._param_struct()[0], self.decoder._param_struct())
         return (lib.aether_dyn_rollout_batched_workspace_bytes, lib.aether_dyn_rollout_batched, "aether_dyn_rollout_batched",
                 tuple(C.byref(h) for h in head))
-
-    @torch.no_grad()
-    def predict_future_batched(self, inputs, masks, node_inds, graph_info, burn_in_masks, uniform=None):
-        """``predict_future`` for B scenes at once: per time step one field query, one kNN + prior step, one sampling pass
-        and one decoder step over the present objects of ALL scenes (BASELINE config 4: 64 scenes).  Default: the whole
-        loop is ONE library call (``aether_dyn_rollout_batched``, up to 256 scenes); ``one_call_step = False`` keeps the
-        staged calls with torch glue of round 2 (same stage kernels: bit-identical)."""
-        if self.one_call_step and inputs.size(1) > 1 and inputs.size(0) <= 256:
-            return self._predict_future_rollout(inputs, masks, node_inds, graph_info, burn_in_masks, uniform)
-        B, n_steps = inputs.size(0), inputs.size(1) - 1
-        prior_state = self.encoder.get_initial_hidden(inputs)
-        dec_state = self.decoder.get_initial_hidden(inputs)
-        last = inputs[:, 0]
-        preds = []
-        for t in range(n_steps):
-            present = masks[:, t]
-            observed = burn_in_masks[:, t].unsqueeze(-1).type(inputs.dtype)
-            state = observed * inputs[:, t] + (1 - observed) * last
-            field, _ = self.predict_field(state, present)
-            ni_t = [node_inds[b][t] for b in range(B)]
-            gi_t = [graph_info[b][t] for b in range(B)]
-            logits, prior_state = self.encoder.single_step_forward_batched(state, present, ni_t, gi_t, prior_state, field)
-            last, dec_state, _ = self.single_step_forward(state, present, gi_t, dec_state, logits, True, field,
-                                                          None if uniform is None else uniform[t])
-            preds.append(last)
-        return torch.stack(preds, dim=1)

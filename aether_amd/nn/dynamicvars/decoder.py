@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from ... import _lib
 from ..seq2seq.encoder import _AnisotropicEdgeFilter, filter_image
+from ._scene import cached_workspace, f32
 
 
 class _DynDecoderParams(C.Structure):
@@ -127,8 +128,7 @@ class Decoder(nn.Module):
         lib = _lib.load()
         dev = inputs.device
         h, K = self.msg_out_shape, self.edge_types
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        inputs, hidden, field = f32(inputs), f32(hidden), f32(predicted_field)
+        inputs, hidden, field = f32(inputs, dev), f32(hidden, dev), f32(predicted_field, dev)
         if n_present is None:
             node_inds = node_masks.reshape(-1).to(dev).nonzero()[:, -1]
         else:                       # the caller knows the number of present objects on the host: no device round trip
@@ -147,10 +147,9 @@ class Decoder(nn.Module):
         ext_full = torch.cat([inputs[0], field[0]], -1).contiguous()                  # indexed with compacted ids (:823)
         rowptr = torch.arange(nv + 1, device=dev, dtype=torch.int64) * e2n.shape[1]
         order = e2n.reshape(-1).contiguous()
-        ew = f32(edges)[0]
+        ew = f32(edges, dev)[0]
         need = lib.aether_dyn_decoder_workspace_bytes(h, nv, E)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = cached_workspace(self, "_ws", need, dev)
         out = torch.empty(nv, 4, dtype=torch.float32, device=dev)
         new_h = torch.empty(nv, h, dtype=torch.float32, device=dev)
         ps = self._param_struct()
@@ -158,7 +157,7 @@ class Decoder(nn.Module):
                                          1 if self.pos_representation == "polar" else 0, nv, E, cur_in.data_ptr(),
                                          cur_h.data_ptr(), ew.data_ptr(), cur_f.data_ptr(), ext_full.data_ptr(),
                                          send.data_ptr(), recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(),
-                                         float(nv - 1), self._ws.data_ptr(), self._ws.numel(), out.data_ptr(),
+                                         float(nv - 1), ws.data_ptr(), ws.numel(), out.data_ptr(),
                                          new_h.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(st, "aether_dyn_decoder_step")
         hidden = hidden.clone()
@@ -182,8 +181,7 @@ class Decoder(nn.Module):
         dev = inputs.device
         B, Nmax = inputs.size(0), inputs.size(1)
         h, K = self.msg_out_shape, self.edge_types
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        inputs, hidden, field = f32(inputs), f32(hidden), f32(predicted_field)
+        inputs, hidden, field = f32(inputs, dev), f32(hidden, dev), f32(predicted_field, dev)
         masks = node_masks.reshape(B, Nmax).to(dev) != 0
         counts = masks.sum(1)                                            # present objects per scene
         counts_h = counts.tolist()
@@ -200,7 +198,7 @@ class Decoder(nn.Module):
         # small tensor operations per scene made the 64-scene step host-bound: 3.9 ms for 0.7 ms of kernels).
         present = [b for b in range(B) if counts_h[b] > 0]
         gi = [tuple(t.to(device=dev, dtype=torch.int64) for t in graph_info[b]) for b in present]
-        ews = [f32(edges[b]).reshape(-1, K) for b in present]
+        ews = [f32(edges[b], dev).reshape(-1, K) for b in present]
         E_l = [g[0].numel() for g in gi]
         for b, g, ew_b, E_b in zip(present, gi, ews, E_l):
             if g[1].numel() != E_b or ew_b.shape[0] != E_b or g[2].ndim != 2 or g[2].shape[0] != counts_h[b]:
@@ -226,8 +224,7 @@ class Decoder(nn.Module):
         cur_in, cur_h, cur_f = x2[flat_idx].contiguous(), h2[flat_idx].contiguous(), f2[flat_idx].contiguous()
         ext_full = torch.cat([x2, f2], -1).contiguous()
         need = lib.aether_dyn_decoder_workspace_bytes(h, nv, E)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = cached_workspace(self, "_ws", need, dev)
         out = torch.empty(nv, 4, dtype=torch.float32, device=dev)
         new_h = torch.empty(nv, h, dtype=torch.float32, device=dev)
         ps = self._param_struct()
@@ -235,7 +232,7 @@ class Decoder(nn.Module):
             C.byref(ps), h, K, 1 if self.skip_first_edge_type else 0, 1 if self.pos_representation == "polar" else 0,
             nv, E, cur_in.data_ptr(), cur_h.data_ptr(), ew.data_ptr(), cur_f.data_ptr(), ext_full.data_ptr(),
             ssend.data_ptr(), srecv.data_ptr(), send.data_ptr(), recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(),
-            1.0, div_node.data_ptr(), self._ws.data_ptr(), self._ws.numel(), out.data_ptr(), new_h.data_ptr(),
+            1.0, div_node.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), new_h.data_ptr(),
             torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(st, "aether_dyn_decoder_step_batched")
         hidden = hidden.clone()

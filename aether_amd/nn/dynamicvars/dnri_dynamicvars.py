@@ -29,7 +29,7 @@ from ...knn import csr_by_receiver, knn_edges
 from ..seq2seq.dnri import _DnriDecoderParams, _DnriPriorParams
 from ..seq2seq.encoder import _RefNRIMLP, _mlp_out, gumbel_softmax_hard
 from ._rollout import SceneRolloutMixin
-from .aether_dynamicvars import _DynStepConfig
+from ._scene import _DynStepConfig, cached_workspace, f32
 
 _NOT_HERE = ("is not part of the prediction path of aether_amd's DNRIDynamicVars (single_step_forward, predict_future, "
              "predict_future_packed)")
@@ -146,8 +146,7 @@ class DNRI_DynamicVars_Encoder(nn.Module):
         if n == 1:
             raise _lib.AetherHipError(_ONE_OBJECT)
         Nmax, h, R, K = inputs.size(1), self.hidden_size, self.rnn_hidden_size, self.num_edges
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        x = f32(inputs)
+        x = f32(inputs, dev)
         mask = node_masks.reshape(-1).to(dev)
         # the encoder's own kNN graph of the present objects, from the current inputs (:408); n is known on the host
         send, recv, _ = knn_edges(x, mask.reshape(1, -1).to(torch.float32), k=_KNN_K, n_present=n)
@@ -164,19 +163,18 @@ class DNRI_DynamicVars_Encoder(nn.Module):
         if slot.numel() != E:
             raise ValueError("graph_info and the encoder's kNN graph list a different number of edges "
                              "(n_edges must be n_present * min(10, n_present - 1))")
-        h0, c0 = f32(forward_state[0])[0, slot].contiguous(), f32(forward_state[1])[0, slot].contiguous()
+        h0, c0 = f32(forward_state[0], dev)[0, slot].contiguous(), f32(forward_state[1], dev)[0, slot].contiguous()
         ps, n_layers, prior_hidden = self._param_struct()
         need = lib.aether_dyn_dnri_prior_workspace_bytes(h, R, prior_hidden, n, E)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = cached_workspace(self, "_ws", need, dev)
         logits = torch.empty(E, K, dtype=torch.float32, device=dev)
         h1, c1 = torch.empty_like(h0), torch.empty_like(c0)
         st = lib.aether_dyn_dnri_prior_step(C.byref(ps), h, R, n_layers, prior_hidden, K, 0, n, E, cur_in.data_ptr(),
                                             h0.data_ptr(), c0.data_ptr(), send.data_ptr(), recv.data_ptr(), order.data_ptr(),
-                                            rowptr.data_ptr(), self._ws.data_ptr(), self._ws.numel(), logits.data_ptr(),
+                                            rowptr.data_ptr(), ws.data_ptr(), ws.numel(), logits.data_ptr(),
                                             h1.data_ptr(), c1.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(st, "aether_dyn_dnri_prior_step")
-        new_h, new_c = f32(forward_state[0]).clone(), f32(forward_state[1]).clone()
+        new_h, new_c = f32(forward_state[0], dev).clone(), f32(forward_state[1], dev).clone()
         new_h[0, slot], new_c[0, slot] = h1, c1
         return logits.unsqueeze(0), (new_h, new_c)
 
@@ -253,8 +251,7 @@ class DNRI_DynamicVars_Decoder(nn.Module):
         lib = _lib.load()
         dev = inputs.device
         h, K = self.msg_out_shape, self.edge_types
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        inputs, hidden = f32(inputs), f32(hidden)
+        inputs, hidden = f32(inputs, dev), f32(hidden, dev)
         node_inds = node_masks.reshape(-1).to(dev).nonzero()[:, -1]
         nv = int(node_inds.numel())
         if nv == 0:                                                                    # :662-664
@@ -270,17 +267,16 @@ class DNRI_DynamicVars_Decoder(nn.Module):
         cur_in, cur_h = inputs[0, node_inds].contiguous(), hidden[0, node_inds].contiguous()
         rowptr = torch.arange(nv + 1, device=dev, dtype=torch.int64) * e2n.shape[1]
         order = e2n.reshape(-1).contiguous()
-        ew = f32(edges)[0]
+        ew = f32(edges, dev)[0]
         need = lib.aether_dyn_dnri_decoder_workspace_bytes(h, K, nv, E)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = cached_workspace(self, "_ws", need, dev)
         out = torch.empty(nv, 4, dtype=torch.float32, device=dev)
         new_h = torch.empty(nv, h, dtype=torch.float32, device=dev)
         ps = self._param_struct()
         st = lib.aether_dyn_dnri_decoder_step_batched(C.byref(ps), h, K, 1 if self.skip_first_edge_type else 0, 0, nv, E,
                                                       cur_in.data_ptr(), cur_h.data_ptr(), ew.data_ptr(), send.data_ptr(),
                                                       recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(), float(nv - 1), None,
-                                                      self._ws.data_ptr(), self._ws.numel(), out.data_ptr(), new_h.data_ptr(),
+                                                      ws.data_ptr(), ws.numel(), out.data_ptr(), new_h.data_ptr(),
                                                       torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(st, "aether_dyn_dnri_decoder_step_batched")
         hidden = hidden.clone()
@@ -303,12 +299,6 @@ class DNRIDynamicVars(SceneRolloutMixin, nn.Module):
         if device is not None:
             self.to(device)
 
-    def save(self, path):
-        torch.save(self.state_dict(), path)                       # as the reference's save / load
-
-    def load(self, path):
-        self.load_state_dict(torch.load(path))
-
     # -- not part of the prediction path ---------------------------------------------------------------------------------------
     def calculate_loss(self, *args, **kwargs):
         raise _lib.AetherHipError("DNRIDynamicVars.calculate_loss " + _NOT_HERE)
@@ -323,14 +313,11 @@ class DNRIDynamicVars(SceneRolloutMixin, nn.Module):
         raise _lib.AetherHipError("DNRIDynamicVars.get_edge_probs " + _NOT_HERE)
 
     # -- the prediction path ---------------------------------------------------------------------------------------------------
-    def _guard(self, inputs):
-        if not inputs.is_cuda:
-            raise _cpu_error("DNRIDynamicVars")
-        if self.training or self.encoder.training:
-            raise _lib.AetherHipError("training mode is not part of this path (the prior step uses BatchNorm running "
-                                      "statistics): call .eval() first")
+    _TRAINING_REFUSAL = ("training mode is not part of this path (the prior step uses BatchNorm running statistics): call "
+                         ".eval() first")
 
-    _rollout_guard = _guard                              # (SceneRolloutMixin: the same two refusals, by this model's names)
+    def _in_training(self):
+        return self.training or self.encoder.training
 
     @torch.no_grad()
     def single_step_forward(self, inputs, node_masks, graph_info, decoder_hidden, edge_logits, hard_sample, uniform=None):
@@ -359,44 +346,15 @@ class DNRIDynamicVars(SceneRolloutMixin, nn.Module):
         return (lib.aether_dyn_dnri_rollout_batched_workspace_bytes, lib.aether_dyn_dnri_rollout_batched,
                 "aether_dyn_dnri_rollout_batched", tuple(C.byref(h) for h in head))
 
-    @torch.no_grad()
-    def _step_one_call(self, state, present, node_inds_t, gsend, grecv, e2n, prior_h, prior_c, dec_state, uniform_t,
-                       return_edge_types=False):
-        """One step of one scene as ONE library call (``aether_dyn_dnri_step_batched`` with n_scenes = 1): the same stage
-        kernels as the staged calls, the index work between them in the library; bit-identical to the staged path.
-        state [1, Nmax, 4], present [1, Nmax], prior_h / prior_c [1, Nmax (Nmax - 1), R], dec_state [1, Nmax, hd]."""
-        self._guard(state)
-        lib = _lib.load()
-        dev = state.device
-        Nmax, n, E = int(state.shape[1]), int(node_inds_t.numel()), int(gsend.numel())
-        if grecv.numel() != E or e2n.ndim != 2 or e2n.shape[0] != n or uniform_t.numel() != E * self.num_edge_types:
-            raise ValueError("graph_info / uniform do not match the present objects")
-        i64 = lambda t: t.to(device=dev, dtype=torch.int64).contiguous()
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        state, present, uniform_t = f32(state), f32(present).reshape(-1), f32(uniform_t)
-        ni, gs, gr, e2n = i64(node_inds_t), i64(gsend), i64(grecv), i64(e2n)
-        new_h, new_c, new_dec = f32(prior_h).clone(), f32(prior_c).clone(), f32(dec_state).clone()
-        cfg = self._step_config()
-        n_arr, e_arr, d_arr = (C.c_int64 * 1)(n), (C.c_int64 * 1)(E), (C.c_int * 1)(int(e2n.shape[1]) if n else 0)
-        need = lib.aether_dyn_dnri_step_batched_workspace_bytes(C.byref(cfg), 1, Nmax, n_arr, e_arr, d_arr)
-        if need == 0:
-            raise _lib.AetherHipError("aether_dyn_dnri_step_batched_workspace_bytes: " + lib.aether_last_error().decode())
-        ws = self.__dict__.get("_step_ws")
-        if ws is None or ws.numel() < need or ws.device != dev:
-            ws = self.__dict__["_step_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        pred = torch.empty(1, Nmax, 4, dtype=torch.float32, device=dev)
-        edge_types = torch.empty(E, self.num_edge_types, dtype=torch.float32, device=dev) if return_edge_types else None
-        ps_e, ps_d = self.encoder._param_struct()[0], self.decoder._param_struct()
-        st = lib.aether_dyn_dnri_step_batched(C.byref(ps_e), C.byref(ps_d), C.byref(cfg), 1, Nmax, n_arr, e_arr, d_arr,
-                                              state.data_ptr(), present.data_ptr(), ni.data_ptr(), gs.data_ptr(), gr.data_ptr(),
-                                              e2n.data_ptr(), new_h.data_ptr(), new_c.data_ptr(), new_dec.data_ptr(),
-                                              uniform_t.data_ptr(), pred.data_ptr(),
-                                              edge_types.data_ptr() if edge_types is not None else None, ws.data_ptr(),
-                                              ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(st, "aether_dyn_dnri_step_batched")
-        if return_edge_types:
-            return pred, new_h, new_c, new_dec, edge_types
-        return pred, new_h, new_c, new_dec
+    def _step_entries(self, lib):
+        """One step of one scene (``SceneRolloutMixin._step_one_call``): ``aether_dyn_dnri_step_batched`` with n_scenes = 1."""
+        arrays = lambda n, E, in_degree: ((C.c_int64 * 1)(n), (C.c_int64 * 1)(E), (C.c_int * 1)(in_degree))
+
+        def step(cfg, Nmax, n, E, in_degree, *rest):
+            head = (self.encoder._param_struct()[0], self.decoder._param_struct())
+            return lib.aether_dyn_dnri_step_batched(*(C.byref(h) for h in head), cfg, 1, Nmax, *arrays(n, E, in_degree), *rest)
+        return (lambda cfg, Nmax, n, E, in_degree: lib.aether_dyn_dnri_step_batched_workspace_bytes(
+            cfg, 1, Nmax, *arrays(n, E, in_degree))), step, "aether_dyn_dnri_step_batched"
 
     @torch.no_grad()
     def predict_future(self, inputs, masks, node_inds, graph_info, burn_in_masks, uniform=None):
@@ -404,34 +362,9 @@ class DNRIDynamicVars(SceneRolloutMixin, nn.Module):
         objects and their graph per time step.  ``uniform``: per-step Gumbel draws (list of [E_t, K]).  With B > 1 scenes
         (node_inds[b][t], graph_info[b][t], uniform[t][b]) see ``predict_future_batched`` -- the reference raises there.
         Default: the whole loop is ONE library call; ``one_call_step = False`` runs the staged calls step by step."""
-        self._guard(inputs)
-        if inputs.size(0) > 1:
-            return self.predict_future_batched(inputs, masks, node_inds, graph_info, burn_in_masks, uniform)
-        n_steps = inputs.size(1) - 1
-        if self.one_call_step and n_steps > 0:
-            return self._predict_future_rollout(inputs, masks, node_inds, graph_info, burn_in_masks,
-                                                None if uniform is None else [[u] for u in uniform])
-        prior_state = self.encoder.get_initial_hidden(inputs)
-        dec_state = self.decoder.get_initial_hidden(inputs)
-        last = inputs[:, 0]
-        preds = []
-        for t in range(n_steps):
-            present = masks[:, t]
-            observed = burn_in_masks[:, t].unsqueeze(-1).type(inputs.dtype)
-            state = observed * inputs[:, t] + (1 - observed) * last                  # :171
-            ni_t, gi_t = node_inds[0][t], graph_info[0][t]
-            logits, prior_state = self.encoder.single_step_forward(state, present, ni_t, gi_t, prior_state)
-            last, dec_state, _ = self.single_step_forward(state, present, gi_t, dec_state, logits, True,
-                                                          None if uniform is None else uniform[t])
-            preds.append(last)
-        return torch.stack(preds, dim=1)
+        return self._predict_future(inputs, masks, node_inds, graph_info, burn_in_masks, uniform)
 
-    @torch.no_grad()
-    def predict_future_batched(self, inputs, masks, node_inds, graph_info, burn_in_masks, uniform=None):
-        """``predict_future`` for B scenes (1..256) at once -- what the reference cannot do (:464-465): per time step ONE
-        batched step over the present objects of all scenes, the whole loop ONE library call
-        (``aether_dyn_dnri_rollout_batched``)."""
-        self._guard(inputs)
-        if inputs.size(1) < 2 or inputs.size(0) > 256:
-            raise ValueError("predict_future_batched takes 1..256 scenes of at least two frames")
-        return self._predict_future_rollout(inputs, masks, node_inds, graph_info, burn_in_masks, uniform)
+    def _staged_step(self, state, present, ni_t, gi_t, prior_state, dec_state, uniform_t):
+        logits, prior_state = self.encoder.single_step_forward(state, present, ni_t, gi_t, prior_state)
+        last, dec_state, _ = self.single_step_forward(state, present, gi_t, dec_state, logits, True, uniform_t)
+        return last, prior_state, dec_state

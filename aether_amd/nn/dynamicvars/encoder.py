@@ -20,6 +20,7 @@ import torch.nn as nn
 from ... import _lib
 from ...knn import csr_by_receiver, knn_edges
 from ..seq2seq.encoder import _AnisotropicEdgeFilter, _RefNRIMLP, _mlp_out, filter_image
+from ._scene import cached_workspace, f32
 
 
 class _DynPriorParams(C.Structure):
@@ -129,8 +130,7 @@ class Encoder(nn.Module):
         if len(node_inds) <= 1:                                                      # :696-697
             return torch.empty(1, 0, self.num_edges, device=dev), forward_state
         Nmax, h, R, K = inputs.size(1), self.hidden_size, self.rnn_hidden_size, self.num_edges
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        x, field = f32(inputs), f32(predicted_field)
+        x, field = f32(inputs, dev), f32(predicted_field, dev)
         mask = node_masks.reshape(-1).to(dev)
         # the encoder's own kNN graph of the present objects, from the current inputs (:528)
         if n_present is None:
@@ -152,17 +152,16 @@ class Encoder(nn.Module):
         slot = gs * (Nmax - 1) + gr - (gr >= gs).long()
         if slot.numel() != E:
             raise ValueError("graph_info and the encoder's kNN graph list a different number of edges")
-        h0, c0 = f32(forward_state[0])[0, slot].contiguous(), f32(forward_state[1])[0, slot].contiguous()
+        h0, c0 = f32(forward_state[0], dev)[0, slot].contiguous(), f32(forward_state[1], dev)[0, slot].contiguous()
         ps, n_layers, prior_hidden = self._param_struct()
         need = lib.aether_dyn_prior_workspace_bytes(h, R, prior_hidden, n, E)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = cached_workspace(self, "_ws", need, dev)
         logits = torch.empty(E, K, dtype=torch.float32, device=dev)
         h1, c1 = torch.empty_like(h0), torch.empty_like(c0)
         st = lib.aether_dyn_prior_step(C.byref(ps), h, R, n_layers, prior_hidden, K,
                                        1 if self.pos_representation == "polar" else 0, n, E, cur_in.data_ptr(),
                                        cur_f.data_ptr(), h0.data_ptr(), c0.data_ptr(), send.data_ptr(), recv.data_ptr(),
-                                       order.data_ptr(), rowptr.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                       order.data_ptr(), rowptr.data_ptr(), ws.data_ptr(), ws.numel(),
                                        logits.data_ptr(), h1.data_ptr(), c1.data_ptr(),
                                        torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(st, "aether_dyn_prior_step")
@@ -186,8 +185,7 @@ class Encoder(nn.Module):
         lib = _lib.load()
         dev = inputs.device
         B, Nmax, h, R, K = inputs.size(0), inputs.size(1), self.hidden_size, self.rnn_hidden_size, self.num_edges
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        x, field = f32(inputs), f32(predicted_field)
+        x, field = f32(inputs, dev), f32(predicted_field, dev)
         mask = node_masks.reshape(B, Nmax).to(dev) != 0
         counts = mask.sum(1)
         counts_h = counts.tolist()
@@ -219,17 +217,16 @@ class Encoder(nn.Module):
         slot = meta[2][scene_e] + gs * (Nmax - 1) + gr - (gr >= gs).long()
         if slot.numel() != E:
             raise ValueError("graph_info and the encoder's kNN graphs list a different number of edges")
-        h0, c0 = f32(forward_state[0])[0, slot].contiguous(), f32(forward_state[1])[0, slot].contiguous()
+        h0, c0 = f32(forward_state[0], dev)[0, slot].contiguous(), f32(forward_state[1], dev)[0, slot].contiguous()
         ps, n_layers, prior_hidden = self._param_struct()
         need = lib.aether_dyn_prior_workspace_bytes(h, R, prior_hidden, n, E)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = cached_workspace(self, "_ws", need, dev)
         logits = torch.empty(E, K, dtype=torch.float32, device=dev)
         h1, c1 = torch.empty_like(h0), torch.empty_like(c0)
         st = lib.aether_dyn_prior_step(C.byref(ps), h, R, n_layers, prior_hidden, K,
                                        1 if self.pos_representation == "polar" else 0, n, E, cur_in.data_ptr(),
                                        cur_f.data_ptr(), h0.data_ptr(), c0.data_ptr(), send.data_ptr(), recv.data_ptr(),
-                                       order.data_ptr(), rowptr.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                       order.data_ptr(), rowptr.data_ptr(), ws.data_ptr(), ws.numel(),
                                        logits.data_ptr(), h1.data_ptr(), c1.data_ptr(),
                                        torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(st, "aether_dyn_prior_step")

@@ -231,6 +231,59 @@ def test_many_scenes_in_one_call():
         assert torch.equal(x, y)
 
 
+# -- the smallest scenes, an empty step among them ----------------------------------------------------------------------------------
+SMALLEST = [[2, 2, 0, 5, 3, 2], [3, 0, 2, 2, 5, 4]]
+
+
+def test_smallest_scenes_and_an_empty_step_on_one_path():
+    """Two scenes of 5 object rows over 6 steps (test_gpu_dynamicvars' smallest scenes): scene 0 has [2, 2, 0, 5, 3, 2] present
+    objects -- k = 1 with two edges and in_degree 1, a step with nobody anywhere when it runs alone (the step's all-empty
+    branch: zeros, states untouched), a full scene.  Scene 0 alone is exactly zero at step 2, equals the staged loop's bytes
+    and is within TOL of its fp64 restatement; as scene 0 of two it is within 2 * TOL of itself alone (the stage GEMMs see
+    other row counts then: the bar of the Aether test, for its reason), and the list path equals the device-built pack's
+    bytes.  Draws as in ``_many``: the first seed that leaves every Gumbel race of the fp64 restatement a margin of 1e-3."""
+    from aether_amd.nn.dynamicvars.aether_dynamicvars import pack_scenes
+    from test_gpu_dynamicvars import _scenes
+    model, _, _ = _model("N9")
+    rs = T.restatement(model, "N9", torch.float64)
+    K, N, B, Tn = 3, 5, len(SMALLEST), len(SMALLEST[0])
+    for seed in range(52, 92):
+        s = _scenes(SMALLEST, N, seed, K)
+        want, ok = [], True
+        for b in range(B):
+            u = [s["uniform"][t][b].double() for t in range(Tn - 1)]
+            p, _, lg = rs.predict_future(s["inputs"][b], s["masks"][b], s["node_inds"][b], s["graph_info"][b], s["burn"][b], u,
+                                         return_all=True)
+            ok = ok and all(MG.min_margin(lg[t], u[t], MG.TAU) > MARGIN for t in range(Tn - 1) if lg[t].numel())
+            want.append(p)
+        if ok:
+            break
+    else:
+        raise RuntimeError("no seed with unambiguous samples")
+    assert [gi[0].numel() for gi in s["graph_info"][0]] == [2, 2, 0, 20, 6, 2] and s["graph_info"][0][0][2].shape == (2, 1)
+    g = {k: _cu(v) for k, v in s.items()}
+    one = (g["inputs"][:1], g["masks"][:1], [g["node_inds"][0]], [g["graph_info"][0]], g["burn"][:1])
+    u0 = [g["uniform"][t][0] for t in range(Tn - 1)]
+    got = model.predict_future(*one, uniform=u0)
+    assert got.shape == (1, Tn - 1, N, 4) and float(got[0, 2].abs().max()) == 0.0
+    model.one_call_step = False
+    try:
+        staged = model.predict_future(*one, uniform=u0)
+    finally:
+        model.one_call_step = True
+    assert torch.equal(got, staged)
+    err = scale_rel_err(got[0].cpu(), want[0])
+    print(f"[dyn dnri smallest] seed {seed}, scene 0 alone vs its fp64 restatement: {err:.3g}")
+    assert err <= TOL
+    both = model.predict_future(g["inputs"], g["masks"], g["node_inds"], g["graph_info"], g["burn"], uniform=g["uniform"])
+    err2 = scale_rel_err(both[:1].cpu(), got.cpu())
+    print(f"[dyn dnri smallest] scene 0 of two vs alone: {err2:.3g}")
+    assert both.shape == (B, Tn - 1, N, 4) and err2 <= 2 * TOL
+    packed = model.predict_future_packed(g["inputs"], g["masks"], g["burn"], pack_scenes(g["inputs"], g["masks"]),
+                                         uniform=g["uniform"])
+    assert torch.equal(packed, both)
+
+
 # -- the predicted update ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("tag", ["N9", "N14"])
 def test_predicted_update_against_fp64(tag):
