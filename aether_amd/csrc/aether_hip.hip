@@ -1050,6 +1050,7 @@ extern "C" {
 const char* aether_version(void) { return "aether_hip 0.7 (gfx950; state2state fused + streamed + wide + fused backward, loss + AdamW, seq2seq fused step, variable-N steps, kNN, simulators; dense layers as split-fp16 matrix-core GEMMs)"; }
 const char* aether_last_error(void) { return g_err; }
 
+#include "host_nri_chain.inc"
 #include "host_seq2seq.inc"
 #include "host_s2s_step.inc"
 #include "host_s2s_markov.inc"

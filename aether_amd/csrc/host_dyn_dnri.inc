@@ -46,71 +46,39 @@ int dyn_dnri_prior_impl(const AetherDynDnriPriorParams* p, int h, int R, int pri
     if (prior_layers > 1 && (ph < 16 || ph % 16 != 0))
         return fail(AETHER_EINVAL, "dyn_dnri_prior: prior_hidden must be a multiple of 16");
     if (K < 1 || K > 4 || Nn <= 0 || E <= 0 || E > INT32_MAX / 64) return fail(AETHER_EINVAL, "dyn_dnri_prior: bad sizes");
-    const float* bns[4] = {nullptr, nullptr, nullptr, nullptr};
     const DynDnriPriorLayout L(h, R, ph, Nn, E);
     if (workspace_bytes < L.total) return fail(AETHER_ESPACE, "dyn_dnri_prior: workspace too small");
-    char* ws = (char*)workspace;
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    const NriMem m{(char*)workspace, nullptr};                 // (no plan: no weight has an image)
+    NriDnriPrior c{};                                          // (host_nri_chain.inc: plain receiver sum, BatchNorm where there is one)
+    c.send = send; c.recv = recv; c.order = order; c.rowptr = rowptr; c.mean_div = 0.0f;
+    c.X1a = m.wp(L.X1a); c.X1 = m.wp(L.X1); c.Ps = m.wp(L.Ps); c.Pr = m.wp(L.Pr); c.T2 = m.wp(L.T2); c.X2 = m.wp(L.X2);
+    c.X2n = m.wp(L.X2n); c.X3a = m.wp(L.X3a); c.X3 = m.wp(L.X3); c.T4 = m.wp(L.T4); c.out = m.wp(L.X4);
+    c.h = h; c.Nn = Nn; c.E = E;
     for (int l = 0; l < 4; ++l) {
         if (!p->mlp_w0[l] || !p->mlp_b0[l] || !p->mlp_w3[l] || !p->mlp_b3[l]) return fail(AETHER_EINVAL, "dyn_dnri_prior: null weight");
         if (!p->mlp_bn_w[l]) continue;                         // no_encoder_bn
         if (!p->mlp_bn_b[l] || !p->mlp_bn_mean[l] || !p->mlp_bn_var[l])
             return fail(AETHER_EINVAL, "dyn_dnri_prior: incomplete BatchNorm pointers");
-        bns[l] = wp(L.bn) + (size_t)2 * l * h;
+        c.bn_scale[l] = m.wp(L.bn) + (size_t)2 * l * h; c.bn_shift[l] = c.bn_scale[l] + h;
     }
     if (!p->lstm_w_ih || !p->lstm_w_hh || !p->lstm_b_ih || !p->lstm_b_hh) return fail(AETHER_EINVAL, "dyn_dnri_prior: null LSTM weight");
     for (int l = 0; l < prior_layers; ++l)
         if (!p->prior_w[l] || !p->prior_b[l]) return fail(AETHER_EINVAL, "dyn_dnri_prior: null prior_fc_out weight");
-    S2SJobs T;
-    auto one = [&](S2SJob J) { T.n = 0; T.j[T.n++] = J; return s2s_launch_jobs(T, st); };
-    auto bn_job = [&](S2SJob J, int l) { if (bns[l]) { J.post_scale = bns[l]; J.post_shift = bns[l] + h; } return J; };
     // ---- mlp1 on the raw 4 columns (:412): the first Linear in the node kernel (with the BatchNorm affines and the LSTM bias)
     {
         const int64_t work = std::max<int64_t>(std::max<int64_t>(Nn * (h / 4), (int64_t)4 * h), (int64_t)4 * R);
-        k_dyn_dnri_node_in<<<blocks(work), dim3(256), 0, st>>>(
-            inputs, p->mlp_w0[0], p->mlp_b0[0], wp(L.X1a), h, Nn, p->mlp_bn_w[0], p->mlp_bn_w[1], p->mlp_bn_w[2], p->mlp_bn_w[3],
+        k_dyn_dnri_node_in<<<nri_blocks(work), dim3(256), 0, st>>>(
+            inputs, p->mlp_w0[0], p->mlp_b0[0], c.X1a, h, Nn, p->mlp_bn_w[0], p->mlp_bn_w[1], p->mlp_bn_w[2], p->mlp_bn_w[3],
             p->mlp_bn_b[0], p->mlp_bn_b[1], p->mlp_bn_b[2], p->mlp_bn_b[3], p->mlp_bn_mean[0], p->mlp_bn_mean[1], p->mlp_bn_mean[2],
-            p->mlp_bn_mean[3], p->mlp_bn_var[0], p->mlp_bn_var[1], p->mlp_bn_var[2], p->mlp_bn_var[3], wp(L.bn), p->lstm_b_ih,
-            p->lstm_b_hh, wp(L.lb), R);
+            p->mlp_bn_mean[3], p->mlp_bn_var[0], p->mlp_bn_var[1], p->mlp_bn_var[2], p->mlp_bn_var[3], m.wp(L.bn), p->lstm_b_ih,
+            p->lstm_b_hh, m.wp(L.lb), R);
     }
-    if (int rc = one(bn_job(s2s_job(4, p->mlp_w3[0], h, p->mlp_b3[0], wp(L.X1a), h, wp(L.X1), h, h, h, Nn), 0))) return rc;
-    // ---- [x_send | x_recv] -> mlp2 (:413-415): the first Linear as the node products of its two halves, no [E, 2h] rows
-    T.n = 0;
-    T.j[T.n++] = s2s_job(0, p->mlp_w0[1], 2 * h, p->mlp_b0[1], wp(L.X1), h, wp(L.Ps), h, h, h, Nn);
-    T.j[T.n++] = s2s_job(0, p->mlp_w0[1] + h, 2 * h, nullptr, wp(L.X1), h, wp(L.Pr), h, h, h, Nn);
-    if (int rc = s2s_launch_jobs(T, st)) return rc;
-    k_s2s_dnri_pair_elu<<<blocks(E * (h / 4)), dim3(256), 0, st>>>(wp(L.Ps), wp(L.Pr), send, recv, wp(L.T2), h, E);
-    if (int rc = one(bn_job(s2s_job(4, p->mlp_w3[1], h, p->mlp_b3[1], wp(L.T2), h, wp(L.X2), h, h, h, E), 1))) return rc;
-    // ---- index_add_ over the receiver (:416-417): a sum; mlp3 (:418)
-    k_dyn_dnri_recv_sum<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(wp(L.X2), order, rowptr, wp(L.X2n), h);
-    if (int rc = one(s2s_job(4, p->mlp_w0[2], h, p->mlp_b0[2], wp(L.X2n), h, wp(L.X3a), h, h, h, Nn))) return rc;
-    if (int rc = one(bn_job(s2s_job(4, p->mlp_w3[2], h, p->mlp_b3[2], wp(L.X3a), h, wp(L.X3), h, h, h, Nn), 2))) return rc;
-    // ---- [x_send | x_recv | skip] -> mlp4 (:419-421): node halves in one launch, the skip third through the GEMM with the
-    // gathers in its epilogue -- no [E, 3h] rows
-    T.n = 0;
-    T.j[T.n++] = s2s_job(0, p->mlp_w0[3], 3 * h, p->mlp_b0[3], wp(L.X3), h, wp(L.Ps), h, h, h, Nn);
-    T.j[T.n++] = s2s_job(0, p->mlp_w0[3] + h, 3 * h, nullptr, wp(L.X3), h, wp(L.Pr), h, h, h, Nn);
-    if (int rc = s2s_launch_jobs(T, st)) return rc;
-    { S2SJob J = s2s_job(4, p->mlp_w0[3] + 2 * h, 3 * h, nullptr, wp(L.X2), h, wp(L.T4), h, h, h, E);
-      J.g1 = wp(L.Ps); J.i1 = send; J.g2 = wp(L.Pr); J.i2 = recv;
-      if (int rc = one(J)) return rc; }
-    if (int rc = one(bn_job(s2s_job(4, p->mlp_w3[3], h, p->mlp_b3[3], wp(L.T4), h, wp(L.X4), h, h, h, E), 3))) return rc;
-    // ---- one LSTM step per edge (:558-560): [W_ih | W_hh] . [x | h0] in one launch, then the cell; prior_fc_out (:566)
-    { S2SJob J = s2s_job(0, p->lstm_w_ih, h, wp(L.lb), wp(L.X4), h, wp(L.G), 4 * R, 4 * R, h, E);
-      J.W2 = p->lstm_w_hh; J.X2 = h0; J.K2 = R; J.ldw2 = R; J.ldx2 = R;
-      if (int rc = one(J)) return rc; }
-    k_s2s_lstm_cell<<<blocks(E * R), dim3(256), 0, st>>>(wp(L.G), c0, h1, c1, R, E);
-    const float* cur = h1;
-    int cur_k = R;
-    for (int l = 0; l < prior_layers; ++l) {
-        const bool last = l + 1 == prior_layers;
-        float* dst = last ? logits : wp(l % 2 == 0 ? L.Y1 : L.Y2);
-        const int M = last ? K : ph;
-        if (int rc = one(s2s_job(last ? 0 : 4, p->prior_w[l], cur_k, p->prior_b[l], cur, cur_k, dst, M, M, cur_k, E))) return rc;
-        cur = dst;
-        cur_k = M;
-    }
+    // ---- mlp1's second layer .. mlp4 (:412-421): node products instead of [E, 2h] / [E, 3h] rows, index_add_ over the receiver
+    if (int rc = nri_dnri_prior(p, c, [](S2SJobs&) { return (int)AETHER_OK; }, st)) return rc;
+    // ---- one LSTM step per edge (:558-560), prior_fc_out (:566): no images, so the fp32 job kernel with the summed bias, then the cell
+    if (int rc = nri_lstm_head(NriLstmHead{p->lstm_w_ih, p->lstm_w_hh, m.wp(L.lb), nullptr, nullptr, nullptr, p->prior_w, p->prior_b,
+                                           {nullptr, nullptr, nullptr, nullptr}, c.out, h0, c0, m.wp(L.G), h1, c1, m.wp(L.Y1),
+                                           m.wp(L.Y2), logits, h, R, prior_layers, ph, K, E}, st)) return rc;
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }
@@ -140,51 +108,27 @@ int dyn_dnri_decoder_impl(const AetherDynDnriDecoderParams* p, int h, int K, int
         return fail(AETHER_EINVAL, "dyn_dnri_decoder: null weight");
     const DynDnriDecLayout L(h, K, Nn, E);
     if (workspace_bytes < L.total) return fail(AETHER_ESPACE, "dyn_dnri_decoder: workspace too small");
-    char* ws = (char*)workspace;
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-    int* counts = reinterpret_cast<int*>(ws + L.counts);
-    int64_t* lists = reinterpret_cast<int64_t*>(ws + L.lists);
-    float* A = wp(L.A);
-    float* S = wp(L.S);
-    S2SJobs T;
+    const NriMem m{(char*)workspace, nullptr};
+    int* counts = reinterpret_cast<int*>(m.ws + L.counts);
+    int64_t* lists = reinterpret_cast<int64_t*>(m.ws + L.lists);
     if (!(sc && sc->counts_zeroed)) HIP_OK(hipMemsetAsync(counts, 0, 64 * sizeof(int), st));
-    // ---- per-type edge lists of the (one-hot) sample; the receiver | sender halves of msg_fc1 on the hidden state (:635-638, :652)
-    k_s2s_select_all<<<blocks(E), dim3(256), 0, st>>>(edge_w, K, k0, 1.0f, wp(L.ewn), lists, (size_t)E, counts, E);
-    T.n = 0;
-    for (int k = k0; k < K; ++k) {
-        T.j[T.n++] = s2s_job(0, p->msg_fc1_w[k], 2 * h, p->msg_fc1_b[k], hidden_in, h, A + (size_t)k * Nn * h, h, h, h, Nn);
-        T.j[T.n++] = s2s_job(0, p->msg_fc1_w[k] + h, 2 * h, nullptr, hidden_in, h, S + (size_t)k * Nn * h, h, h, h, Nn);
-    }
-    if (int rc = s2s_launch_jobs(T, st)) return rc;
-    k_s2s_dnri_pair<false><<<blocks(E * (h / 4)), dim3(256), 0, st>>>(A, S, Nn, send, recv, edge_w, K, k0, wp(L.Tm), wp(L.M), h, E);
-    // ---- second layer of every used type in one launch: rows through the type's list, times the sample's weight (:654-655)
-    T.n = 0;
-    for (int k = k0; k < K; ++k) {
-        S2SJob J = s2s_job(3, p->msg_fc2_w[k], h, p->msg_fc2_b[k], wp(L.Tm) + (size_t)k * E * h, h, wp(L.M), h, h, h, E);
-        J.xidx = lists + (size_t)k * E; J.yidx = lists + (size_t)k * E; J.n_dev = counts + k;
-        J.scale = wp(L.ewn) + k; J.sstride = K;
-        T.j[T.n++] = J;
-    }
-    if (int rc = s2s_launch_jobs(T, st)) return rc;
-    // ---- / norm, sum over the edge2node rows / (num_vars - 1) of the object's scene (:656-661)
-    k_dyn_dnri_aggregate<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(wp(L.M), agg_order, agg_rowptr, wp(L.agg), h, (float)(K - k0), agg_div,
-                                                                  agg_div_node);
-    // ---- GRU-style gate on the raw inputs (:669-675)
-    T.n = 0;
-    T.j[T.n++] = s2s_job(0, p->hidden_r_w, h, nullptr, wp(L.agg), h, wp(L.hr), h, h, h, Nn);
-    T.j[T.n++] = s2s_job(0, p->hidden_i_w, h, nullptr, wp(L.agg), h, wp(L.hi), h, h, h, Nn);
-    T.j[T.n++] = s2s_job(0, p->hidden_h_w, h, nullptr, wp(L.agg), h, wp(L.hh), h, h, h, Nn);
-    if (int rc = s2s_launch_jobs(T, st)) return rc;
-    k_s2s_dnri_gate<<<blocks(Nn * (h / 4)), dim3(256), 0, st>>>(inputs, 4, p->input_r_w, p->input_r_b, p->input_i_w, p->input_i_b,
-                                                               p->input_n_w, p->input_n_b, wp(L.hr), wp(L.hi), wp(L.hh), hidden_in,
-                                                               hidden_out, h, Nn);
-    // ---- output MLP, residual and (the step) the rows back to their objects (:678-686)
-    auto one = [&](S2SJob J) { T.n = 0; T.j[T.n++] = J; return s2s_launch_jobs(T, st); };
-    if (int rc = one(s2s_job(2, p->out1_w, h, p->out1_b, hidden_out, h, wp(L.o1), h, h, h, Nn))) return rc;
-    if (int rc = one(s2s_job(2, p->out2_w, h, p->out2_b, wp(L.o1), h, wp(L.o2), h, h, h, Nn))) return rc;
+    // ---- per-type edge lists of the (one-hot) sample (:635-638)
+    k_s2s_select_all<<<nri_blocks(E), dim3(256), 0, st>>>(edge_w, K, k0, 1.0f, m.wp(L.ewn), lists, (size_t)E, counts, E);
+    // ---- msg_fc1 .. out_fc2 (:652-680, host_nri_chain.inc): no images; / norm, sum over the edge2node rows / the scene's num_vars - 1
+    NriDnriDecoder d{};
+    d.x_in = inputs; d.dh_in = hidden_in; d.sample = edge_w; d.scale = m.wp(L.ewn);
+    d.lists = lists; d.send = send; d.recv = recv; d.counts = counts;
+    d.A = m.wp(L.A); d.S = m.wp(L.S); d.Tm = m.wp(L.Tm); d.M = m.wp(L.M); d.agg = m.wp(L.agg); d.hr = m.wp(L.hr); d.hi = m.wp(L.hi);
+    d.hh = m.wp(L.hh); d.o1 = m.wp(L.o1); d.o2 = m.wp(L.o2); d.dh_out = hidden_out;
+    d.ldx = 4; d.hd = h; d.K = K; d.k0 = k0; d.Nn = Nn; d.E = E; d.node_products = true;
+    auto aggregate = [&] {
+        k_dyn_dnri_aggregate<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(d.M, agg_order, agg_rowptr, d.agg, h, (float)(K - k0), agg_div,
+                                                                      agg_div_node);
+    };
+    if (int rc = nri_dnri_decoder(p, d, aggregate, st)) return rc;
+    // ---- last layer, residual and (the step) the rows back to their objects (:681-686)
     const int64_t rows = sc ? sc->n_rows : Nn;
-    k_dyn_dnri_out<<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st>>>(wp(L.o2), p->out3_w, p->out3_b, h, inputs, outputs, rows,
+    k_dyn_dnri_out<<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st>>>(d.o2, p->out3_w, p->out3_b, h, inputs, outputs, rows,
                                                                           sc ? sc->cidx : nullptr, sc ? sc->status : nullptr,
                                                                           hidden_out, sc ? sc->hidden : nullptr);
     HIP_OK(hipGetLastError());

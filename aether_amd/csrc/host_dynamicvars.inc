@@ -330,19 +330,10 @@ int aether_dyn_prior_step(const AetherDynPriorParams* p, int hidden, int rnn_hid
     if (s2s_linear(4, p->mlp4_w3, h, p->mlp4_b3, wp(L.T1), wp(L.X4), h, h, E, h, nullptr, 0, 0, st, nullptr, nullptr, nullptr,
                    bns[2][0], bns[2][1])) return AETHER_EINVAL;
     // ---- one LSTM step per edge, prior_fc_out (:688-696)
-    if (s2s_linear(0, p->lstm_w_ih, h, p->lstm_b_ih, wp(L.X4), wp(L.G), 4 * R, h, E, 4 * R, nullptr, 0, 0, st)) return AETHER_EINVAL;
-    if (s2s_linear(0, p->lstm_w_hh, R, p->lstm_b_hh, h0, wp(L.G), 4 * R, R, E, 4 * R, nullptr, 0, 1, st)) return AETHER_EINVAL;
-    k_s2s_lstm_cell<<<blocks(E * R), dim3(256), 0, st>>>(wp(L.G), c0, h1, c1, R, E);
-    const float* cur = h1;
-    int cur_k = R;
-    for (int l = 0; l < prior_layers; ++l) {
-        const bool last = l + 1 == prior_layers;
-        float* dst = last ? logits : wp(l % 2 == 0 ? L.Y1 : L.Y2);
-        const int M = last ? K : prior_hidden;
-        if (s2s_linear(last ? 0 : 4, p->prior_w[l], cur_k, p->prior_b[l], cur, dst, M, cur_k, E, M, nullptr, 0, 0, st)) return AETHER_EINVAL;
-        cur = dst;
-        cur_k = M;
-    }
+    if (int rc = nri_lstm_two_launch(p->lstm_w_ih, p->lstm_w_hh, p->lstm_b_ih, p->lstm_b_hh, h, R, E, wp(L.X4), h0, c0, wp(L.G), h1,
+                                     c1, st)) return rc;
+    if (int rc = nri_head_linear(p->prior_w, p->prior_b, prior_layers, R, prior_hidden, K, E, h1, wp(L.Y1), wp(L.Y2), logits, st))
+        return rc;
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }

@@ -120,109 +120,56 @@ extern "C++" DnriArgs s2s_dnri_args(const AetherS2SDnriPriorParams* pp, const Ae
 extern "C++" template <class FirstJobs>
 int s2s_dnri_front(const DnriArgs& a, char* ws, const float* x_in, const float* h0, const float* c0, const float* uniform,
                    float* h1, float* c1, float* edges, FirstJobs&& first_jobs, hipStream_t st) {
-    const int D = a.D, he = a.he, R = a.R, K = a.K, k0 = a.skip_first ? 1 : 0;
+    const int D = a.D, he = a.he, K = a.K, k0 = a.skip_first ? 1 : 0;
     const int64_t Nn = a.Nn, E = a.E;
     const DnriPlanLayout& P = a.P;
     const DnriStepLayout& L = a.L;
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto pl = [&](size_t off) { return reinterpret_cast<const float*>(a.plan + off); };
-    auto im = [&](size_t off) { return off ? reinterpret_cast<const void*>(a.plan + off) : nullptr; };
-    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    const NriMem m{ws, a.plan};
     const AetherS2SDnriPriorParams* p = a.pp;
     int* counts = reinterpret_cast<int*>(ws + L.counts);
     int64_t* lists = reinterpret_cast<int64_t*>(ws + L.lists);
-    S2SJobs T;
-    auto one = [&](S2SJob J) { T.n = 0; T.j[T.n++] = J; return s2s_launch_jobs(T, st); };
-    auto bns = [&](int l) { return pl(P.bn) + (size_t)2 * l * he; };
     // the step's edge counters; for the MLP decoder (when the step decodes) the raw state where out_fc1 reads it and the node
     // products of its first message layer
     {
-        const AetherS2SDnriMlpParams* m = edges != nullptr ? a.mp : nullptr;
+        const AetherS2SDnriMlpParams* mp = edges != nullptr ? a.mp : nullptr;
         const int per = a.hd / 4 > S2S_RFG ? a.hd / 4 : S2S_RFG;
         const float* none = nullptr;
-        k_s2s_dnri_node_prep<<<m ? blocks(Nn * per) : dim3(1), dim3(256), 0, st>>>(
-            x_in, 2 * D, m ? wp(L.agg) : nullptr, L.ldagg, counts, Nn, m ? m->msg_fc1_w[0] : none, m ? m->msg_fc1_w[1] : none,
-            m ? m->msg_fc1_w[2] : none, m ? m->msg_fc1_w[3] : none, m ? m->msg_fc1_b[0] : none, m ? m->msg_fc1_b[1] : none,
-            m ? m->msg_fc1_b[2] : none, m ? m->msg_fc1_b[3] : none, K, k0, wp(L.A), wp(L.S), a.hd, per);
+        k_s2s_dnri_node_prep<<<mp ? nri_blocks(Nn * per) : dim3(1), dim3(256), 0, st>>>(
+            x_in, 2 * D, mp ? m.wp(L.agg) : nullptr, L.ldagg, counts, Nn, mp ? mp->msg_fc1_w[0] : none, mp ? mp->msg_fc1_w[1] : none,
+            mp ? mp->msg_fc1_w[2] : none, mp ? mp->msg_fc1_w[3] : none, mp ? mp->msg_fc1_b[0] : none, mp ? mp->msg_fc1_b[1] : none,
+            mp ? mp->msg_fc1_b[2] : none, mp ? mp->msg_fc1_b[3] : none, K, k0, m.wp(L.A), m.wp(L.S), a.hd, per);
     }
     if (a.ext_logits == nullptr) {
         // mlp1 on the raw state (:405): its first Linear has 2D columns -- a narrow layer
         { NarrowLayers N1{};
-          N1.W[0] = p->mlp_w0[0]; N1.b[0] = p->mlp_b0[0]; N1.Y[0] = wp(L.X1a); N1.n = 1;
-          k_s2s_narrow_layers<<<blocks(Nn * (he / 4)), dim3(256), 0, st>>>(N1, x_in, 2 * D, 2 * D, he, 4, Nn); }
-        { S2SJob J = s2s_job(4, p->mlp_w3[0], he, p->mlp_b3[0], wp(L.X1a), he, wp(L.X1), he, he, he, Nn);
-          J.post_scale = bns(0); J.post_shift = bns(0) + he; J.Wimg = im(P.i_w3[0]);
-          T.n = 0; T.j[T.n++] = J;
-          if (int rc = first_jobs(T)) return rc;
-          if (int rc = s2s_launch_jobs(T, st)) return rc; }
-        // node2edge, mlp2 (:406-407): the first Linear on [x_send | x_recv] as its two halves' node products
-        float* Ps = wp(L.PsPr);
-        float* Pr = Ps + (size_t)Nn * he;
-        T.n = 0;
-        T.j[T.n++] = s2s_job(0, p->mlp_w0[1], 2 * he, p->mlp_b0[1], wp(L.X1), he, Ps, he, he, he, Nn);
-        T.j[T.n - 1].Wimg = im(P.i_m2s);
-        T.j[T.n++] = s2s_job(0, p->mlp_w0[1] + he, 2 * he, nullptr, wp(L.X1), he, Pr, he, he, he, Nn);
-        T.j[T.n - 1].Wimg = im(P.i_m2r);
-        if (int rc = s2s_launch_jobs(T, st)) return rc;
-        k_s2s_dnri_pair_elu<<<blocks(E * (he / 4)), dim3(256), 0, st>>>(Ps, Pr, a.send, a.recv, wp(L.T2), he, E);
-        { S2SJob J = s2s_job(4, p->mlp_w3[1], he, p->mlp_b3[1], wp(L.T2), he, wp(L.X2), he, he, he, E);
-          J.post_scale = bns(1); J.post_shift = bns(1) + he; J.Wimg = im(P.i_w3[1]);
-          if (int rc = one(J)) return rc; }
-        // edge2node (:344-351, :409): in-edge sum / (num_vars - 1); mlp3 (:410)
-        k_s2s_segment_mean<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(wp(L.X2), a.order, a.rowptr, wp(L.X2n), he,
-                                                                    (float)(a.num_vars - 1), nullptr);
-        { S2SJob J = s2s_job(4, p->mlp_w0[2], he, p->mlp_b0[2], wp(L.X2n), he, wp(L.X3a), he, he, he, Nn); J.Wimg = im(P.i_m3_0);
-          if (int rc = one(J)) return rc; }
-        { S2SJob J = s2s_job(4, p->mlp_w3[2], he, p->mlp_b3[2], wp(L.X3a), he, wp(L.X3), he, he, he, Nn);
-          J.post_scale = bns(2); J.post_shift = bns(2) + he; J.Wimg = im(P.i_w3[2]);
-          if (int rc = one(J)) return rc; }
-        // mlp4 on [x_send | x_recv | skip] (:411-413): node halves in one launch, the edge third with the gathers in its epilogue
-        T.n = 0;
-        T.j[T.n++] = s2s_job(0, p->mlp_w0[3], 3 * he, p->mlp_b0[3], wp(L.X3), he, Ps, he, he, he, Nn);
-        T.j[T.n - 1].Wimg = im(P.i_ps);
-        T.j[T.n++] = s2s_job(0, p->mlp_w0[3] + he, 3 * he, nullptr, wp(L.X3), he, Pr, he, he, he, Nn);
-        T.j[T.n - 1].Wimg = im(P.i_pr);
-        if (int rc = s2s_launch_jobs(T, st)) return rc;
-        { S2SJob J = s2s_job(4, p->mlp_w0[3] + 2 * he, 3 * he, nullptr, wp(L.X2), he, wp(L.T4), he, he, he, E);
-          J.Wimg = im(P.i_m4e); J.g1 = Ps; J.i1 = a.send; J.g2 = Pr; J.i2 = a.recv;
-          if (int rc = one(J)) return rc; }
-        { S2SJob J = s2s_job(4, p->mlp_w3[3], he, p->mlp_b3[3], wp(L.T4), he, a.features_out ? a.features_out : wp(L.X4), he, he,
-                             he, E);
-          J.post_scale = bns(3); J.post_shift = bns(3) + he; J.Wimg = im(P.i_w3[3]);
-          if (int rc = one(J)) return rc; }
+          N1.W[0] = p->mlp_w0[0]; N1.b[0] = p->mlp_b0[0]; N1.Y[0] = m.wp(L.X1a); N1.n = 1;
+          k_s2s_narrow_layers<<<nri_blocks(Nn * (he / 4)), dim3(256), 0, st>>>(N1, x_in, 2 * D, 2 * D, he, 4, Nn); }
+        // mlp1's second layer .. mlp4 (:405-413): in-edge sum / (num_vars - 1) between mlp2 and mlp3 (:344-351)
+        const float* bn = m.pl(P.bn);                          // scale | shift of mlp1 .. mlp4
+        float* Ps = m.wp(L.PsPr);
+        float* x4 = a.features_out ? a.features_out : m.wp(L.X4);
+        const NriDnriPrior c{{bn, bn + 2 * he, bn + 4 * he, bn + 6 * he}, {bn + he, bn + 3 * he, bn + 5 * he, bn + 7 * he},
+                             {m.im(P.i_w3[0]), m.im(P.i_w3[1]), m.im(P.i_w3[2]), m.im(P.i_w3[3])}, m.im(P.i_m2s), m.im(P.i_m2r),
+                             m.im(P.i_m3_0), m.im(P.i_ps), m.im(P.i_pr), m.im(P.i_m4e), a.send, a.recv, a.order, a.rowptr,
+                             (float)(a.num_vars - 1), m.wp(L.X1a), m.wp(L.X1), Ps, Ps + (size_t)Nn * he, m.wp(L.T2), m.wp(L.X2),
+                             m.wp(L.X2n), m.wp(L.X3a), m.wp(L.X3), m.wp(L.T4), x4, he, Nn, E};
+        if (int rc = nri_dnri_prior(p, c, first_jobs, st)) return rc;
         if (a.features_out) return AETHER_OK;
         // one LSTM step per edge (:415-421), prior_fc_out (:422)
-        { S2SJob J = s2s_job(0, p->lstm_w_ih, he, pl(P.lb), wp(L.X4), he, wp(L.G), 4 * R, 4 * R, he, E);      // [W_ih | W_hh] . [x | h0]
-          J.W2 = p->lstm_w_hh; J.X2 = h0; J.K2 = R; J.ldw2 = R; J.ldx2 = R; J.Wimg = im(P.i_ih); J.W2img = im(P.i_hh);
-          T.n = 0; T.j[T.n++] = J;
-          if (s2s_jobs_take_split(T)) {                        // the cell update is the split GEMM's epilogue (S2SJob act 5)
-              T.j[0].act = 5; T.j[0].bias = pl(P.lbp); T.j[0].cell_c0 = c0; T.j[0].cell_h1 = h1; T.j[0].cell_c1 = c1;
-              if (int rc = s2s_launch_jobs(T, st)) return rc;
-          } else {
-              T.j[0].Wimg = nullptr; T.j[0].W2img = nullptr;   // (the interleaved images fit the fused form only)
-              if (int rc = s2s_launch_jobs(T, st)) return rc;
-              k_s2s_lstm_cell<<<blocks(E * R), dim3(256), 0, st>>>(wp(L.G), c0, h1, c1, R, E);
-          } }
-        const float* cur = h1;
-        int cur_k = R;
-        for (int l = 0; l < a.prior_layers; ++l) {
-            const bool last = l + 1 == a.prior_layers;
-            float* dst = last ? wp(L.logits) : wp(l % 2 == 0 ? L.Y1 : L.Y2);
-            const int M = last ? K : a.ph;
-            S2SJob J = s2s_job(last ? 0 : 4, p->prior_w[l], cur_k, p->prior_b[l], cur, cur_k, dst, M, M, cur_k, E);
-            if (!last) J.Wimg = im(P.i_prior[l]);
-            if (int rc = one(J)) return rc;
-            cur = dst;
-            cur_k = M;
-        }
+        if (int rc = nri_lstm_head(NriLstmHead{p->lstm_w_ih, p->lstm_w_hh, m.pl(P.lb), m.pl(P.lbp), m.im(P.i_ih), m.im(P.i_hh),
+                                               p->prior_w, p->prior_b,
+                                               {m.im(P.i_prior[0]), m.im(P.i_prior[1]), m.im(P.i_prior[2]), m.im(P.i_prior[3])},
+                                               x4, h0, c0, m.wp(L.G), h1, c1, m.wp(L.Y1), m.wp(L.Y2), m.wp(L.logits), he, a.R,
+                                               a.prior_layers, a.ph, K, E}, st)) return rc;
     } else {                           // (given logits: what rides in mlp1's launch goes alone)
+        S2SJobs T;
         T.n = 0;
         if (int rc = first_jobs(T)) return rc;
         if (int rc = s2s_launch_jobs(T, st)) return rc;
     }
     if (edges != nullptr)
-        k_s2s_gumbel_select<<<blocks(E), dim3(256), 0, st>>>(a.ext_logits ? a.ext_logits : wp(L.logits), uniform, a.tau, K, k0, edges,
-                                                           lists, counts, E);
+        k_s2s_gumbel_select<<<nri_blocks(E), dim3(256), 0, st>>>(a.ext_logits ? a.ext_logits : m.wp(L.logits), uniform, a.tau, K, k0,
+                                                                edges, lists, counts, E);
     return AETHER_OK;
 }
 
@@ -235,79 +182,52 @@ int s2s_dnri_step_impl(const DnriArgs& a, char* ws, const float* x_in, const flo
     const int64_t Nn = a.Nn, E = a.E;
     const DnriPlanLayout& P = a.P;
     const DnriStepLayout& L = a.L;
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto pl = [&](size_t off) { return reinterpret_cast<const float*>(a.plan + off); };
-    auto im = [&](size_t off) { return off ? reinterpret_cast<const void*>(a.plan + off) : nullptr; };
-    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    const NriMem m{ws, a.plan};
     const AetherS2SDnriDecoderParams* q = a.dp;
-    const AetherS2SDnriMlpParams* m = a.mp;
-    int* counts = reinterpret_cast<int*>(ws + L.counts);
-    int64_t* lists = reinterpret_cast<int64_t*>(ws + L.lists);
-    float* edges = !decode ? nullptr : edges_out ? edges_out : wp(L.edges);
-    float* A = wp(L.A);
-    float* S = wp(L.S);
-    S2SJobs T;
+    const AetherS2SDnriMlpParams* mp = a.mp;
+    float* edges = !decode ? nullptr : edges_out ? edges_out : m.wp(L.edges);
+    // what either decoder's message layers and the recurrent decoder's chain (host_nri_chain.inc) use; the sample is its own scale
+    const NriDnriDecoder d{{m.im(P.i_a[0]), m.im(P.i_a[1]), m.im(P.i_a[2]), m.im(P.i_a[3])},
+                           {m.im(P.i_s[0]), m.im(P.i_s[1]), m.im(P.i_s[2]), m.im(P.i_s[3])},
+                           {m.im(P.i_msg2[0]), m.im(P.i_msg2[1]), m.im(P.i_msg2[2]), m.im(P.i_msg2[3])}, m.im(P.i_hr), m.im(P.i_hi),
+                           m.im(P.i_hh2), m.im(P.i_out1), m.im(P.i_out2), x_in, dh_in, edges, edges,
+                           reinterpret_cast<const int64_t*>(ws + L.lists), a.send, a.recv, reinterpret_cast<const int*>(ws + L.counts),
+                           m.wp(L.A), m.wp(L.S), m.wp(L.Tm), m.wp(L.M), m.wp(L.agg), m.wp(L.hr), m.wp(L.hi), m.wp(L.hh), m.wp(L.o1),
+                           m.wp(L.o2), dh_out, 2 * D, hd, K, k0, Nn, E, false};
     // the receiver | sender halves of msg_fc1 on the hidden state (:489-493, :508) ride in mlp1's launch
     auto first_jobs = [&](S2SJobs& F) {
         if (q == nullptr) return (int)AETHER_OK;
         for (int k = k0; k < K; ++k) {
             if (F.n > S2S_MAX_JOBS - 2) { if (int rc = s2s_launch_jobs(F, st)) return rc; F.n = 0; }
-            F.j[F.n++] = s2s_job(0, q->msg_fc1_w[k], 2 * hd, q->msg_fc1_b[k], dh_in, hd, A + (size_t)k * Nn * hd, hd, hd, hd, Nn);
-            F.j[F.n - 1].Wimg = im(P.i_a[k]);
-            F.j[F.n++] = s2s_job(0, q->msg_fc1_w[k] + hd, 2 * hd, nullptr, dh_in, hd, S + (size_t)k * Nn * hd, hd, hd, hd, Nn);
-            F.j[F.n - 1].Wimg = im(P.i_s[k]);
+            nri_dnri_msg1_pair(q, d, k, F);
         }
         return (int)AETHER_OK;
     };
     if (int rc = s2s_dnri_front(a, ws, x_in, h0, c0, uniform, h1, c1, edges, first_jobs, st)) return rc;
     if (!decode) return AETHER_OK;
-    // ---- first message layer of the sampled type, per edge, from its node products (rows of unsampled edges of M cleared)
-    if (q)
-        k_s2s_dnri_pair<false><<<blocks(E * (hd / 4)), dim3(256), 0, st>>>(A, S, Nn, a.send, a.recv, edges, K, k0, wp(L.Tm), wp(L.M), hd, E);
-    else
-        k_s2s_dnri_pair<true><<<blocks(E * (hd / 4)), dim3(256), 0, st>>>(A, S, Nn, a.send, a.recv, edges, K, k0, wp(L.Tm), wp(L.M), hd, E);
-    // ---- second layer of every used type in one launch: rows through the type's list, scaled by the sample's weight
-    {
-        T.n = 0;
-        for (int k = k0; k < K; ++k) {
-            S2SJob J = s2s_job(q ? 3 : 2, q ? q->msg_fc2_w[k] : m->msg_fc2_w[k], hd, q ? q->msg_fc2_b[k] : m->msg_fc2_b[k],
-                               wp(L.Tm) + (size_t)k * E * hd, hd, wp(L.M), hd, hd, hd, E);
-            J.xidx = lists + (size_t)k * E; J.yidx = lists + (size_t)k * E; J.n_dev = counts + k;
-            J.scale = edges + k; J.sstride = K; J.Wimg = im(P.i_msg2[k]);
-            T.j[T.n++] = J;
-        }
-        if (int rc = s2s_launch_jobs(T, st)) return rc;
-    }
-    const float* o_in;
     if (q) {
-        // / norm, sum per receiver / (N - 1) (:512-516); GRU gate on the raw inputs (:519-525)
-        k_s2s_dnri_aggregate<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(wp(L.M), a.order, a.rowptr, wp(L.agg), hd, hd, (float)(K - k0),
-                                                                      (float)(a.num_vars - 1));
-        T.n = 0;
-        T.j[T.n++] = s2s_job(0, q->hidden_r_w, hd, nullptr, wp(L.agg), hd, wp(L.hr), hd, hd, hd, Nn); T.j[T.n - 1].Wimg = im(P.i_hr);
-        T.j[T.n++] = s2s_job(0, q->hidden_i_w, hd, nullptr, wp(L.agg), hd, wp(L.hi), hd, hd, hd, Nn); T.j[T.n - 1].Wimg = im(P.i_hi);
-        T.j[T.n++] = s2s_job(0, q->hidden_h_w, hd, nullptr, wp(L.agg), hd, wp(L.hh), hd, hd, hd, Nn); T.j[T.n - 1].Wimg = im(P.i_hh2);
-        if (int rc = s2s_launch_jobs(T, st)) return rc;
-        k_s2s_dnri_gate<<<blocks(Nn * (hd / 4)), dim3(256), 0, st>>>(x_in, 2 * D, q->input_r_w, q->input_r_b, q->input_i_w,
-                                                                    q->input_i_b, q->input_n_w, q->input_n_b, wp(L.hr), wp(L.hi),
-                                                                    wp(L.hh), dh_in, dh_out, hd, Nn);
-        o_in = dh_out;
+        // / norm, sum per receiver / (N - 1) (:512-516) between the messages and the GRU gate (:519-525)
+        auto aggregate = [&] {
+            k_s2s_dnri_aggregate<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(d.M, a.order, a.rowptr, d.agg, hd, hd, (float)(K - k0),
+                                                                          (float)(a.num_vars - 1));
+        };
+        if (int rc = nri_dnri_decoder(q, d, aggregate, st)) return rc;
     } else {
-        // plain sum per receiver behind the staged inputs (:612-616): out_fc1 reads [inputs, 0 .. | agg]
-        k_s2s_dnri_aggregate<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(wp(L.M), a.order, a.rowptr, wp(L.agg) + S2S_RFG, L.ldagg, hd,
-                                                                      1.0f, 1.0f);
-        o_in = nullptr;
+        // ReLU pair, second layer without tanh, plain sum per receiver behind the staged inputs (:612-616): [inputs, 0 .. | agg]
+        k_s2s_dnri_pair<true><<<nri_blocks(E * (hd / 4)), dim3(256), 0, st>>>(d.A, d.S, Nn, a.send, a.recv, edges, K, k0, d.Tm, d.M,
+                                                                              hd, E);
+        if (int rc = nri_dnri_msg2(2, mp->msg_fc2_w, mp->msg_fc2_b, d, st)) return rc;
+        k_s2s_dnri_aggregate<<<dim3((unsigned)Nn), dim3(128), 0, st>>>(d.M, a.order, a.rowptr, d.agg + S2S_RFG, L.ldagg, hd, 1.0f,
+                                                                      1.0f);
+        if (int rc = nri_one(st, s2s_job(2, m.pl(P.o1p), P.ldo1, mp->out1_b, d.agg, L.ldagg, d.o1, hd, hd, P.ldo1, Nn), d.img_out1))
+            return rc;
+        if (int rc = nri_one(st, s2s_job(2, mp->out2_w, hd, mp->out2_b, d.o1, hd, d.o2, hd, hd, hd, Nn), d.img_out2)) return rc;
     }
-    // ---- output MLP and residual (:528-532, :619-624)
-    auto one = [&](S2SJob J, size_t image) { T.n = 1; T.j[0] = J; T.j[0].Wimg = im(image); return s2s_launch_jobs(T, st); };
-    if (q) { if (int rc = one(s2s_job(2, q->out1_w, hd, q->out1_b, o_in, hd, wp(L.o1), hd, hd, hd, Nn), P.i_out1)) return rc; }
-    else if (int rc = one(s2s_job(2, pl(P.o1p), P.ldo1, m->out1_b, wp(L.agg), L.ldagg, wp(L.o1), hd, hd, P.ldo1, Nn), P.i_out1)) return rc;
-    if (int rc = one(s2s_job(2, q ? q->out2_w : m->out2_w, hd, q ? q->out2_b : m->out2_b, wp(L.o1), hd, wp(L.o2), hd, hd, hd, Nn),
-                     P.i_out2)) return rc;
-    const float* w3 = q ? q->out3_w : m->out3_w;
-    const float* b3 = q ? q->out3_b : m->out3_b;
+    // ---- last layer of the output MLP and residual (:528-532, :619-624)
+    const float* w3 = q ? q->out3_w : mp->out3_w;
+    const float* b3 = q ? q->out3_b : mp->out3_b;
     dispatch_dim(D, [&](auto DD) {
-        k_s2s_dnri_out<decltype(DD)::value><<<dim3((unsigned)((Nn + 3) / 4)), dim3(256), 0, st>>>(wp(L.o2), w3, b3, hd, x_in, x_out, Nn);
+        k_s2s_dnri_out<decltype(DD)::value><<<dim3((unsigned)((Nn + 3) / 4)), dim3(256), 0, st>>>(d.o2, w3, b3, hd, x_in, x_out, Nn);
     });
     return AETHER_OK;
 }
@@ -438,35 +358,11 @@ int aether_s2s_dnri_rollout(const AetherS2SDnriPriorParams* pp, const AetherS2SD
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const DnriStepLayout& L = a.L;
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    const size_t dbytes = (size_t)a.Nn * a.hd * 4, rbytes = (size_t)a.E * a.R * 4;
-    const size_t ustep = (size_t)a.E * a.K, xstep = (size_t)a.Nn * 2 * a.D;
-    // state ping-pong inside the workspace (the decoder's only when it has a state)
-    float *dcur = dp ? wp(L.da) : nullptr, *dnext = dp ? wp(L.db) : nullptr;
-    float *hcur = wp(L.ha), *hnext = wp(L.hb), *ccur = wp(L.ca), *cnext = wp(L.cb);
-    if (dcur) HIP_OK(hipMemcpyAsync(dcur, decoder_state, dbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(hcur, h, rbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(ccur, c, rbytes, hipMemcpyDeviceToDevice, st));
-    const int total = burn_in_steps + steps;
-    const float* xcur = burn_in_steps > 0 ? burn_in : inputs;
-    for (int t = 0; t < total; ++t) {
-        // A burn-in step's prediction is discarded.  The recurrent decoder still needs the step for its state: the whole step,
-        // its output into L.xa.  The MLP decoder has no state: the prior only -- no sample, no decoder, no output.
-        const bool teacher = t < burn_in_steps, decode = !teacher || dp != nullptr;
-        float* xout = !teacher ? predictions + (size_t)(t - burn_in_steps) * xstep : decode ? wp(L.xa) : nullptr;
-        float* eout = (!teacher && edges_out) ? edges_out + (size_t)(t - burn_in_steps) * ustep : nullptr;
-        if (int rc = s2s_dnri_step_impl(a, ws, xcur, dcur, hcur, ccur, uniform + (size_t)t * ustep, xout, dnext, hnext, cnext, eout,
-                                        decode, st)) return rc;
-        std::swap(dcur, dnext); std::swap(hcur, hnext); std::swap(ccur, cnext);
-        if (t + 1 < burn_in_steps) xcur = burn_in + (size_t)(t + 1) * xstep;
-        else if (t + 1 == burn_in_steps) xcur = inputs;
-        else xcur = xout;
-    }
-    if (dcur) HIP_OK(hipMemcpyAsync(decoder_state, dcur, dbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(h, hcur, rbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(c, ccur, rbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipGetLastError());
-    return AETHER_OK;
+    auto step = [&](int, bool, const S2SStateIn& cur, const float* u, const S2SStateOut& next, float* eout, bool decode) {
+        return s2s_dnri_step_impl(a, ws, cur.x, cur.dh, cur.h, cur.c, u, next.x, next.dh, next.h, next.c, eout, decode, st);
+    };
+    return nri_rollout(ws, NriRolloutWs{L.xa, L.da, L.db, L.ha, L.hb, L.ca, L.cb, a.D, a.hd, a.R, a.K, a.Nn, a.E}, burn_in_steps,
+                       burn_in, steps, inputs, dp ? decoder_state : nullptr, h, c, uniform, predictions, edges_out, step, st);
 }
 
 int aether_s2s_dnri_encoder_features(const AetherS2SDnriPriorParams* pp, const AetherS2SDnriDecoderParams* dp,

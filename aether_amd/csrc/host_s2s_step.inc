@@ -297,11 +297,6 @@ struct S2SChargeArgs {
     float* ea;
 };
 
-// The state a step reads and the one it writes: x [Nn][2D], dh [Nn][hd] (null with the Markov decoder, which has none),
-// h / c [E][R]
-struct S2SStateIn { const float *x, *dh, *h, *c; };
-struct S2SStateOut { float *x, *dh, *h, *c; };
-
 extern "C++" {                 // (templates: the including block has C linkage)
 // f(std::integral_constant<int, D>) for the run-time num_dims (2 or 3): picks a kernel's template argument, e.g.
 //   dispatch_dim(D, [&](auto DD) { k<decltype(DD)::value><<<...>>>(...); })      (as dispatch_bools, host_gnn_common.inc)
@@ -429,7 +424,6 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
                                                                       wp(L.eaf), wp(L.X0), he, (float)(a.num_vars - 1));
     }
     const float *bn3s = pl(P.bn), *bn3b = pl(P.bn) + he, *bn4s = pl(P.bn) + 2 * he, *bn4b = pl(P.bn) + 3 * he;
-    auto one = [&](S2SJob J) { T.n = 0; T.j[T.n++] = J; return s2s_launch_jobs(T, st); };
     // + res1(rel_feat) (:395), mlp3 (RefNRIMLP, eval)
     { S2SJob J = s2s_job(0, pl(P.res1p), d.RFp, a.chg ? nullptr : p->res1_b, wp(L.relp), d.RFp, wp(L.X0), he, he, d.RFp, Nn);
       J.accumulate = 1;
@@ -437,55 +431,20 @@ int s2s_front_impl(const S2SStepArgs& a, const S2SStepLayout& L, const S2SPlanLa
       T.n = 0; T.j[T.n++] = J;
       if (int rc = res1_jobs(T)) return rc;
       if (int rc = s2s_launch_jobs(T, st)) return rc; }
-    { S2SJob J = s2s_job(4, p->mlp3_w0, he, p->mlp3_b0, wp(L.X0), he, wp(L.X1), he, he, he, Nn); J.Wimg = im(P.i_mlp3_0);
-      if (int rc = one(J)) return rc; }
-    { S2SJob J = s2s_job(4, p->mlp3_w3, he, p->mlp3_b3, wp(L.X1), he, wp(L.X3), he, he, he, Nn); J.post_scale = bn3s; J.post_shift = bn3b;
-      J.Wimg = im(P.i_mlp3_3);
-      if (int rc = one(J)) return rc; }
-    // mlp4 on [x_send | x_recv | edge] (:396-398): node halves in one launch, the edge third with the gathers in its epilogue
+    if (int rc = nri_one(st, s2s_job(4, p->mlp3_w0, he, p->mlp3_b0, wp(L.X0), he, wp(L.X1), he, he, he, Nn), im(P.i_mlp3_0))) return rc;
+    if (int rc = nri_one(st, s2s_job(4, p->mlp3_w3, he, p->mlp3_b3, wp(L.X1), he, wp(L.X3), he, he, he, Nn), im(P.i_mlp3_3), bn3s,
+                         bn3b)) return rc;
+    // mlp4 on [x_send | x_recv | edge] (:396-398), one LSTM step per edge (:400-407), prior_fc_out (:408): host_nri_chain.inc
     float* Ps = wp(L.PsPr);
-    float* Pr = Ps + (size_t)Nn * he;
-    T.n = 0;
-    T.j[T.n++] = s2s_job(0, p->mlp4_w0, 3 * he, p->mlp4_b0, wp(L.X3), he, Ps, he, he, he, Nn);
-    T.j[T.n - 1].Wimg = im(P.i_ps);
-    T.j[T.n++] = s2s_job(0, p->mlp4_w0 + he, 3 * he, nullptr, wp(L.X3), he, Pr, he, he, he, Nn);
-    T.j[T.n - 1].Wimg = im(P.i_pr);
-    if (int rc = s2s_launch_jobs(T, st)) return rc;
-    { S2SJob J = s2s_job(4, p->mlp4_w0 + 2 * he, 3 * he, nullptr, wp(L.eaf), he, wp(L.T1e), he, he, he, E);
-      J.Wimg = im(P.i_mlp4e); J.g1 = Ps; J.i1 = a.send; J.g2 = Pr; J.i2 = a.recv;
-      if (int rc = one(J)) return rc; }
-    { S2SJob J = s2s_job(4, p->mlp4_w3, he, p->mlp4_b3, wp(L.T1e), he, a.features_out ? a.features_out : wp(L.X4), he, he, he, E);
-      J.post_scale = bn4s; J.post_shift = bn4b;
-      J.Wimg = im(P.i_mlp4_3);
-      if (int rc = one(J)) return rc; }
+    float* x4 = a.features_out ? a.features_out : wp(L.X4);
+    if (int rc = nri_edge_mlp4(NriMlp4{p->mlp4_w0, p->mlp4_b0, p->mlp4_w3, p->mlp4_b3, bn4s, bn4b, im(P.i_ps), im(P.i_pr),
+                                       im(P.i_mlp4e), im(P.i_mlp4_3), wp(L.X3), wp(L.eaf), a.send, a.recv, Ps, Ps + (size_t)Nn * he,
+                                       wp(L.T1e), x4, he, Nn, E}, st)) return rc;
     if (a.features_out) return AETHER_OK;
-    // one LSTM step per edge (:400-407), prior_fc_out (:408)
-    { S2SJob J = s2s_job(0, p->lstm_w_ih, he, pl(P.lb), wp(L.X4), he, wp(L.G), 4 * R, 4 * R, he, E);      // [W_ih | W_hh] . [x | h0]
-      J.W2 = p->lstm_w_hh; J.X2 = h0; J.K2 = R; J.ldw2 = R; J.ldx2 = R; J.Wimg = im(P.i_ih); J.W2img = im(P.i_hh);
-      T.n = 0; T.j[T.n++] = J;
-      if (s2s_jobs_take_split(T)) {
-          // the images' rows are the gates interleaved by unit: the cell update is the GEMM's epilogue (one launch, no [E][4R] round trip)
-          T.j[0].act = 5; T.j[0].bias = pl(P.lbp); T.j[0].cell_c0 = c0; T.j[0].cell_h1 = h1; T.j[0].cell_c1 = c1;
-          if (int rc = s2s_launch_jobs(T, st)) return rc;
-      } else {
-          T.j[0].Wimg = nullptr; T.j[0].W2img = nullptr;       // (the interleaved images fit the fused form only)
-          if (int rc = s2s_launch_jobs(T, st)) return rc;
-          k_s2s_lstm_cell<<<blocks(E * R), dim3(256), 0, st>>>(wp(L.G), c0, h1, c1, R, E);
-      } }
-    {
-        const float* cur = h1;
-        int cur_k = R;
-        for (int l = 0; l < a.prior_layers; ++l) {
-            const bool last = l + 1 == a.prior_layers;
-            float* dst = last ? wp(L.logits) : wp(l % 2 == 0 ? L.Y1 : L.Y2);
-            const int M = last ? K : a.ph;
-            S2SJob J = s2s_job(last ? 0 : 4, p->prior_w[l], cur_k, p->prior_b[l], cur, cur_k, dst, M, M, cur_k, E);
-            if (!last) J.Wimg = im(P.i_prior[l]);
-            if (int rc = one(J)) return rc;
-            cur = dst;
-            cur_k = M;
-        }
-    }
+    if (int rc = nri_lstm_head(NriLstmHead{p->lstm_w_ih, p->lstm_w_hh, pl(P.lb), pl(P.lbp), im(P.i_ih), im(P.i_hh), p->prior_w,
+                                           p->prior_b, {im(P.i_prior[0]), im(P.i_prior[1]), im(P.i_prior[2]), im(P.i_prior[3])},
+                                           x4, h0, c0, wp(L.G), h1, c1, wp(L.Y1), wp(L.Y2), wp(L.logits), he, R, a.prior_layers,
+                                           a.ph, K, E}, st)) return rc;
     } else {                           // (given logits: what rides in the prior's res1 launch goes alone)
         T.n = 0;
         if (int rc = res1_jobs(T)) return rc;
@@ -504,19 +463,14 @@ int s2s_out_tail(const S2SStepArgs& a, char* ws, const DecoderParams* q, const f
                  hipStream_t st) {
     const int hd = a.hd;
     const int64_t Nn = a.Nn;
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto one = [&](S2SJob J, size_t image) {
-        S2SJobs T;
-        T.n = 1; T.j[0] = J; T.j[0].Wimg = image ? a.plan + image : nullptr;
-        return s2s_launch_jobs(T, st);
-    };
-    if (int rc = one(s2s_job(2, q->out0_w, hd, q->out0_b, in, hd, wp(a.L.o1), hd, hd, hd, Nn), a.P.i_out0)) return rc;
-    { S2SJob J = s2s_job(2, q->out3_w, hd, q->out3_b, wp(a.L.o1), hd, wp(a.L.o2), hd, hd, hd, Nn);
+    const NriMem m{ws, a.plan};
+    if (int rc = nri_one(st, s2s_job(2, q->out0_w, hd, q->out0_b, in, hd, m.wp(a.L.o1), hd, hd, hd, Nn), m.im(a.P.i_out0))) return rc;
+    { S2SJob J = s2s_job(2, q->out3_w, hd, q->out3_b, m.wp(a.L.o1), hd, m.wp(a.L.o2), hd, hd, hd, Nn);
       if (a.chg) { J.scale = a.chg->nscale; J.sstride = 1; }       // 1, or NaN for a node whose charge index was out of range
-      if (int rc = one(J, a.P.i_out3)) return rc; }
+      if (int rc = nri_one(st, J, m.im(a.P.i_out3))) return rc; }
     dispatch_dim(a.D, [&](auto DD) {
         k_s2s_out_globalize<decltype(DD)::value><<<dim3((unsigned)((Nn + 3) / 4)), dim3(256), 0, st>>>(
-            wp(a.L.o2), q->out6_w, q->out6_b, hd, x_in, wp(a.L.Rinv), x_out, Nn);
+            m.wp(a.L.o2), q->out6_w, q->out6_b, hd, x_in, m.wp(a.L.Rinv), x_out, Nn);
     });
     return AETHER_OK;
 }
@@ -685,36 +639,12 @@ int s2s_run_rollout(const char* what, const S2SStepArgs& a, void* workspace, siz
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const S2SStepLayout& L = a.L;
-    auto wp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    const size_t dbytes = (size_t)a.Nn * a.hd * 4, rbytes = (size_t)a.E * a.R * 4;
-    const size_t ustep = (size_t)a.E * a.K, xstep = (size_t)a.Nn * 2 * a.D;
-    // state ping-pong inside the workspace (the decoder's only when it has a state)
-    float *dcur = decoder_state ? wp(L.da) : nullptr, *dnext = decoder_state ? wp(L.db) : nullptr;
-    float *hcur = wp(L.ha), *hnext = wp(L.hb), *ccur = wp(L.ca), *cnext = wp(L.cb);
-    if (dcur) HIP_OK(hipMemcpyAsync(dcur, decoder_state, dbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(hcur, h, rbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(ccur, c, rbytes, hipMemcpyDeviceToDevice, st));
-    const int total = burn_in_steps + steps;
-    const float* xcur = burn_in_steps > 0 ? burn_in : inputs;
-    for (int t = 0; t < total; ++t) {
-        // A burn-in step's prediction is discarded.  The recurrent decoder still needs the step for its state: the whole
-        // step, its output into L.xa.  The Markov decoder has no state: the prior only -- no sample, no decoder, no output.
-        const bool teacher = t < burn_in_steps, decode = !teacher || !a.mp;
-        float* xout = !teacher ? predictions + (size_t)(t - burn_in_steps) * xstep : decode ? wp(L.xa) : nullptr;
-        float* eout = (!teacher && edges_out) ? edges_out + (size_t)(t - burn_in_steps) * ustep : nullptr;
+    auto step = [&](int t, bool teacher, const S2SStateIn& cur, const float* u, const S2SStateOut& next, float* eout, bool decode) {
         const float* ext = teacher && burn_in_field ? burn_in_field + (size_t)t * a.Nn * a.D : nullptr;
-        if (int rc = s2s_step(a, ws, {xcur, dcur, hcur, ccur}, ext, uniform + (size_t)t * ustep, {xout, dnext, hnext, cnext},
-                              eout, decode, st)) return rc;
-        std::swap(dcur, dnext); std::swap(hcur, hnext); std::swap(ccur, cnext);
-        if (t + 1 < burn_in_steps) xcur = burn_in + (size_t)(t + 1) * xstep;
-        else if (t + 1 == burn_in_steps) xcur = inputs;
-        else xcur = xout;
-    }
-    if (dcur) HIP_OK(hipMemcpyAsync(decoder_state, dcur, dbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(h, hcur, rbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(c, ccur, rbytes, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipGetLastError());
-    return AETHER_OK;
+        return s2s_step(a, ws, cur, ext, u, next, eout, decode, st);
+    };
+    return nri_rollout(ws, NriRolloutWs{L.xa, L.da, L.db, L.ha, L.hb, L.ca, L.cb, a.D, a.hd, a.R, a.K, a.Nn, a.E}, burn_in_steps,
+                       burn_in, steps, inputs, decoder_state, h, c, uniform, predictions, edges_out, step, st);
 }
 
 // Bytes of the plan of either decoder, 0 for sizes the fused step does not take.  markov_ku: the Markov decoder's count of

@@ -1,14 +1,6 @@
 // Host side of the C ABI: seq2seq steps (SURVEY 8a rows A8-A10) and the seq2seq dynamic-field variant (8f N3).  Included by aether_hip.hip inside its extern "C" block (one translation
 // unit: the kernels live in anonymous namespaces); not a stand-alone source file.
 
-namespace {
-int s2s_linear(int act, const float* W, int ldw, const float* b, const float* X, float* Y, int M, int K, int64_t N,
-               int ldy, const float* scale, int sstride, int accumulate, hipStream_t st,
-               const int64_t* xidx = nullptr, const int64_t* yidx = nullptr, const int* n_dev = nullptr,
-               const float* post_scale = nullptr, const float* post_shift = nullptr,
-               const float* film_gamma = nullptr, const float* film_beta = nullptr, int film_rows = 1);
-}  // namespace
-
 size_t aether_s2s_field_workspace_bytes(int64_t n_points, int hidden) {
     if (n_points <= 0 || hidden <= 0) return 0;
     return (size_t)3 * (size_t)n_points * (size_t)hidden * sizeof(float) + 768;
@@ -338,9 +330,7 @@ int s2s_prior_features(const AetherS2SPriorParams* p, int D, int h, int polar, i
     return AETHER_OK;
 }
 
-int s2s_prior_check(const char* who, const AetherS2SPriorParams* p, int num_dims, int hidden, int num_vars, int64_t n_nodes,
-                    int64_t n_edges) {
-    (void)who;
+int s2s_prior_check(const AetherS2SPriorParams* p, int num_dims, int hidden, int num_vars, int64_t n_nodes, int64_t n_edges) {
     if (!p) return fail(AETHER_EINVAL, "s2s_prior: null pointer");
     if (num_dims != 2 && num_dims != 3) return fail(AETHER_EINVAL, "s2s_prior: num_dims must be 2 or 3");
     if (hidden < 128 || hidden % 128 != 0) return fail(AETHER_EINVAL, "s2s_prior: hidden must be a multiple of 128");
@@ -355,7 +345,7 @@ int aether_s2s_encoder_features(const AetherS2SPriorParams* p, int num_dims, int
                                 void* workspace, size_t workspace_bytes, float* features, void* stream) {
     if (!inputs || !field || !send || !recv || !order || !rowptr || !workspace || !features)
         return fail(AETHER_EINVAL, "s2s_encoder_features: null pointer");
-    if (int rc = s2s_prior_check("s2s_encoder_features", p, num_dims, hidden, num_vars, n_nodes, n_edges)) return rc;
+    if (int rc = s2s_prior_check(p, num_dims, hidden, num_vars, n_nodes, n_edges)) return rc;
     S2SPriorLayout L(num_dims, hidden, 16, 0, n_nodes, n_edges);
     if (workspace_bytes < L.total) return fail(AETHER_ESPACE, "s2s_encoder_features: workspace too small");
     int rc = s2s_prior_features(p, num_dims, hidden, polar, num_vars, n_nodes, n_edges, inputs, field, send, recv, order, rowptr,
@@ -372,11 +362,8 @@ int aether_s2s_lstm_step(const float* w_ih, const float* w_hh, const float* b_ih
         return fail(AETHER_EINVAL, "s2s_lstm_step: null pointer");
     if (in_size < 16 || in_size % 16 != 0 || rnn_hidden < 16 || rnn_hidden % 16 != 0 || n_rows <= 0)
         return fail(AETHER_EINVAL, "s2s_lstm_step: sizes must be multiples of 16");
-    hipStream_t st = (hipStream_t)stream;
-    const int R = rnn_hidden;
-    if (s2s_linear(0, w_ih, in_size, b_ih, x, gates, 4 * R, in_size, n_rows, 4 * R, nullptr, 0, 0, st)) return AETHER_EINVAL;
-    if (s2s_linear(0, w_hh, R, b_hh, h0, gates, 4 * R, R, n_rows, 4 * R, nullptr, 0, 1, st)) return AETHER_EINVAL;
-    k_s2s_lstm_cell<<<dim3((unsigned)((n_rows * R + 255) / 256)), dim3(256), 0, st>>>(gates, c0, h1, c1, R, n_rows);
+    if (int rc = nri_lstm_two_launch(w_ih, w_hh, b_ih, b_hh, in_size, rnn_hidden, n_rows, x, h0, c0, gates, h1, c1,
+                                     (hipStream_t)stream)) return rc;
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }
@@ -386,18 +373,11 @@ int aether_s2s_mlp_head(const float* const* w, const float* const* b, int layers
     if (!w || !b || !x || !out || (layers > 1 && !scratch)) return fail(AETHER_EINVAL, "s2s_mlp_head: null pointer");
     if (layers < 1 || layers > 4 || in_size % 16 != 0 || (layers > 1 && hidden_size % 16 != 0) || out_size < 1 || n_rows <= 0)
         return fail(AETHER_EINVAL, "s2s_mlp_head: 1..4 layers, input / hidden sizes multiples of 16");
-    hipStream_t st = (hipStream_t)stream;
-    const float* cur = x;
-    int cur_k = in_size;
-    for (int l = 0; l < layers; ++l) {
+    for (int l = 0; l < layers; ++l)
         if (!w[l] || !b[l]) return fail(AETHER_EINVAL, "s2s_mlp_head: null layer pointer");
-        const bool last = l + 1 == layers;
-        float* dst = last ? out : scratch + (size_t)(l % 2) * n_rows * hidden_size;
-        const int M = last ? out_size : hidden_size;
-        if (s2s_linear(last ? 0 : 4, w[l], cur_k, b[l], cur, dst, M, cur_k, n_rows, M, nullptr, 0, 0, st)) return AETHER_EINVAL;
-        cur = dst;
-        cur_k = M;
-    }
+    float* second = layers > 2 ? scratch + (size_t)n_rows * hidden_size : nullptr;     // (three layers and more ping-pong)
+    if (int rc = nri_head_linear(w, b, layers, in_size, hidden_size, out_size, n_rows, x, scratch, second, out,
+                                 (hipStream_t)stream)) return rc;
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }
@@ -409,7 +389,7 @@ int aether_s2s_prior_step(const AetherS2SPriorParams* p, int num_dims, int hidde
                           void* workspace, size_t workspace_bytes, float* logits, float* h1, float* c1, void* stream) {
     if (!p || !inputs || !field || !h0 || !c0 || !send || !recv || !order || !rowptr || !workspace || !logits || !h1 || !c1)
         return fail(AETHER_EINVAL, "s2s_prior: null pointer");
-    if (int rc = s2s_prior_check("s2s_prior", p, num_dims, hidden, num_vars, n_nodes, n_edges)) return rc;
+    if (int rc = s2s_prior_check(p, num_dims, hidden, num_vars, n_nodes, n_edges)) return rc;
     if (rnn_hidden < 16 || rnn_hidden % 16 != 0) return fail(AETHER_EINVAL, "s2s_prior: rnn_hidden must be a multiple of 16");
     if (prior_layers < 1 || prior_layers > 4) return fail(AETHER_EINVAL, "s2s_prior: 1..4 prior layers");
     if (prior_layers > 1 && (prior_hidden < 16 || prior_hidden % 16 != 0))
@@ -425,21 +405,11 @@ int aether_s2s_prior_step(const AetherS2SPriorParams* p, int num_dims, int hidde
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     if (int rc = s2s_prior_features(p, D, h, polar, num_vars, n_nodes, n_edges, inputs, field, send, recv, order, rowptr, L, ws,
                                     wp(L.X4), stream)) return rc;
-    // ---- one LSTM step per edge (:400-407)
-    if (s2s_linear(0, p->lstm_w_ih, h, p->lstm_b_ih, wp(L.X4), wp(L.G), 4 * R, h, E, 4 * R, nullptr, 0, 0, st)) return AETHER_EINVAL;
-    if (s2s_linear(0, p->lstm_w_hh, R, p->lstm_b_hh, h0, wp(L.G), 4 * R, R, E, 4 * R, nullptr, 0, 1, st)) return AETHER_EINVAL;
-    k_s2s_lstm_cell<<<blocks(E * R), dim3(256), 0, st>>>(wp(L.G), c0, h1, c1, R, E);
-    // ---- prior_fc_out (:408)
-    const float* cur = h1;
-    int cur_k = R;
-    for (int l = 0; l < prior_layers; ++l) {
-        const bool last = l + 1 == prior_layers;
-        float* dst = last ? logits : wp(l % 2 == 0 ? L.Y1 : L.Y2);
-        const int M = last ? K : prior_hidden;
-        if (s2s_linear(last ? 0 : 4, p->prior_w[l], cur_k, p->prior_b[l], cur, dst, M, cur_k, E, M, nullptr, 0, 0, st)) return AETHER_EINVAL;
-        cur = dst;
-        cur_k = M;
-    }
+    // ---- one LSTM step per edge (:400-407), prior_fc_out (:408)
+    if (int rc = nri_lstm_two_launch(p->lstm_w_ih, p->lstm_w_hh, p->lstm_b_ih, p->lstm_b_hh, h, R, E, wp(L.X4), h0, c0, wp(L.G), h1,
+                                     c1, st)) return rc;
+    if (int rc = nri_head_linear(p->prior_w, p->prior_b, prior_layers, R, prior_hidden, K, E, h1, wp(L.Y1), wp(L.Y2), logits, st))
+        return rc;
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }
