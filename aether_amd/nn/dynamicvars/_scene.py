@@ -29,10 +29,7 @@ def cached_workspace(owner, attr, need, dev, capture_check=None):
     return ws
 
 
-class _DynStepConfig(C.Structure):                      # AetherDynStepConfig of include/aether_hip.h
-    _fields_ = [(n, C.c_int) for n in ("field_hidden", "encoder_hidden", "rnn_hidden", "prior_layers", "prior_hidden",
-                                       "num_edge_types", "decoder_hidden", "skip_first", "encoder_polar", "decoder_polar",
-                                       "knn_k")] + [("gumbel_tau", C.c_float)]
+_DynStepConfig = _lib.AetherDynStepConfig
 
 
 class ScenePack:

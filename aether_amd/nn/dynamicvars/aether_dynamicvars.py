@@ -23,8 +23,7 @@ from .decoder import Decoder
 from .encoder import Encoder
 
 
-class _DynFieldQueryParams(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("B", "ang_w", "ang_b", "w0", "b0", "w2", "b2", "w4", "b4")]
+_DynFieldQueryParams = _lib.AetherDynFieldQueryParams
 
 
 class AetherDynamicVars(SceneRolloutMixin, nn.Module):

@@ -20,13 +20,7 @@ from ..seq2seq.encoder import _AnisotropicEdgeFilter, filter_image
 from ._scene import cached_workspace, f32
 
 
-class _DynDecoderParams(C.Structure):
-    _fields_ = ([(n, C.c_void_p * 4) for n in ("msg_fc1_w", "msg_fc1_b", "msg_fc2_w", "msg_fc2_b")] +
-                [(n, C.c_void_p) for n in ("hidden_r_w", "hidden_i_w", "hidden_h_w", "input_r_w", "input_r_b", "input_i_w",
-                                           "input_i_b", "input_n_w", "input_n_b", "present_r_w", "present_r_b",
-                                           "present_i_w", "present_i_b", "present_n_w", "present_n_b", "out1_w", "out1_b",
-                                           "out2_w", "out2_b", "out3_w", "out3_b")] +
-                [(n, C.c_void_p * 4) for n in ("filt_w0", "filt_b0", "filt_w2", "filt_b2", "filt_image")])
+_DynDecoderParams = _lib.AetherDynDecoderParams
 
 
 class Decoder(nn.Module):

@@ -26,7 +26,6 @@ import torch.nn as nn
 
 from ... import _lib
 from ...knn import csr_by_receiver, knn_edges
-from ..seq2seq.dnri import _DnriDecoderParams, _DnriPriorParams
 from ..seq2seq.encoder import _RefNRIMLP, _mlp_out, gumbel_softmax_hard
 from ._rollout import SceneRolloutMixin
 from ._scene import _DynStepConfig, cached_workspace, f32
@@ -105,7 +104,7 @@ class DNRI_DynamicVars_Encoder(nn.Module):
     def _param_struct(self):
         """-> (pointer struct, prior layers, prior hidden)."""
         _check_params(self)
-        ps = _DnriPriorParams()
+        ps = _lib.AetherDynDnriPriorParams()
         ptr = lambda t: t.data_ptr()
         for l, name in enumerate(("mlp1", "mlp2", "mlp3", "mlp4")):
             m = getattr(self, name)
@@ -224,7 +223,7 @@ class DNRI_DynamicVars_Decoder(nn.Module):
 
     def _param_struct(self):
         _check_params(self)
-        ps = _DnriDecoderParams()
+        ps = _lib.AetherDynDnriDecoderParams()
         ptr = lambda t: t.data_ptr()
         for k in range(self.edge_types):
             ps.msg_fc1_w[k], ps.msg_fc1_b[k] = ptr(self.msg_fc1[k].weight), ptr(self.msg_fc1[k].bias)

@@ -23,12 +23,7 @@ from ..seq2seq.encoder import _AnisotropicEdgeFilter, _RefNRIMLP, _mlp_out, filt
 from ._scene import cached_workspace, f32
 
 
-class _DynPriorParams(C.Structure):
-    _fields_ = ([(f"{m}_{t}", C.c_void_p) for m in ("mlp1", "mlp3", "mlp4")
-                 for t in ("w0", "b0", "w3", "b3", "bn_w", "bn_b", "bn_mean", "bn_var")] +
-                [(n, C.c_void_p) for n in ("lstm_w_ih", "lstm_w_hh", "lstm_b_ih", "lstm_b_hh")] +
-                [("prior_w", C.c_void_p * 4), ("prior_b", C.c_void_p * 4)] +
-                [(n, C.c_void_p) for n in ("filt_w0", "filt_b0", "filt_w2", "filt_b2", "filt_image")])
+_DynPriorParams = _lib.AetherDynPriorParams
 
 
 class Encoder(nn.Module):

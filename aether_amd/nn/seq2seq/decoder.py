@@ -17,16 +17,7 @@ from ... import _lib
 from .localizer import AugmentedLocalizer, Localizer
 
 
-class _DecoderParams(C.Structure):
-    _fields_ = ([("msg_fc1_w", C.c_void_p * 4), ("msg_fc1_b", C.c_void_p * 4),
-                 ("msg_fc2_w", C.c_void_p * 4), ("msg_fc2_b", C.c_void_p * 4)] +
-                [(n, C.c_void_p) for n in ("hidden_r_w", "hidden_i_w", "hidden_h_w", "present_r_w", "present_r_b",
-                                           "present_i_w", "present_i_b", "present_n_w", "present_n_b",
-                                           "out0_w", "out0_b", "out3_w", "out3_b", "out6_w", "out6_b")] +
-                [("pmsg_fc1_w", C.c_void_p * 4), ("pmsg_fc1_b", C.c_void_p * 4),
-                 ("pmsg_fc2_w", C.c_void_p * 4), ("pmsg_fc2_b", C.c_void_p * 4)] +
-                [(n, C.c_void_p) for n in ("input_r_w", "input_r_b", "input_i_w", "input_i_b", "input_n_w",
-                                           "input_n_b")])
+_DecoderParams = _lib.AetherS2SDecoderParams
 
 
 class RecurrentDecoder(nn.Module):

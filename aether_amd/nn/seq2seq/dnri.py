@@ -34,25 +34,11 @@ _THROUGH_MODEL = ("of the seq2seq dNRI runs through the model (DNRI.single_step_
                   "aether_s2s_dnri_*), not as a call of the module")
 
 
-class _DnriPriorParams(C.Structure):
-    _fields_ = ([(n, C.c_void_p * 4) for n in ("mlp_w0", "mlp_b0", "mlp_w3", "mlp_b3", "mlp_bn_w", "mlp_bn_b", "mlp_bn_mean",
-                                               "mlp_bn_var")] +
-                [(n, C.c_void_p) for n in ("lstm_w_ih", "lstm_w_hh", "lstm_b_ih", "lstm_b_hh")] +
-                [("prior_w", C.c_void_p * 4), ("prior_b", C.c_void_p * 4)])
+_DnriPriorParams = _lib.AetherS2SDnriPriorParams
+_DnriDecoderParams = _lib.AetherS2SDnriDecoderParams
 
 
-class _DnriDecoderParams(C.Structure):
-    _fields_ = ([("msg_fc1_w", C.c_void_p * 4), ("msg_fc1_b", C.c_void_p * 4),
-                 ("msg_fc2_w", C.c_void_p * 4), ("msg_fc2_b", C.c_void_p * 4)] +
-                [(n, C.c_void_p) for n in ("hidden_r_w", "hidden_i_w", "hidden_h_w", "input_r_w", "input_r_b", "input_i_w",
-                                           "input_i_b", "input_n_w", "input_n_b", "out1_w", "out1_b", "out2_w", "out2_b",
-                                           "out3_w", "out3_b")])
-
-
-class _DnriMlpParams(C.Structure):
-    _fields_ = ([("msg_fc1_w", C.c_void_p * 4), ("msg_fc1_b", C.c_void_p * 4),
-                 ("msg_fc2_w", C.c_void_p * 4), ("msg_fc2_b", C.c_void_p * 4)] +
-                [(n, C.c_void_p) for n in ("out1_w", "out1_b", "out2_w", "out2_b", "out3_w", "out3_b")])
+_DnriMlpParams = _lib.AetherS2SDnriMlpParams
 
 
 def _edges(num_vars):

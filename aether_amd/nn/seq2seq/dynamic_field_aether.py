@@ -29,15 +29,8 @@ from .field import _CoordinateEmbedding
 from .markov import MarkovDecoder
 
 
-class _SummaryParams(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        "emb_w", "emb_b", "gru_w_ih", "gru_w_hh", "gru_b_ih", "gru_b_hh", "pe",
-        "gate_w0", "gate_b0", "gate_w2", "gate_b2", "nn_w0", "nn_b0", "nn_w2", "nn_b2")]
-
-
-class _FilmParams(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("B", "lin1_w", "lin1_b", "lin2_w", "lin2_b", "lin3_w", "lin3_b")] + \
-               [(n, C.c_void_p * 4) for n in ("mod_w0", "mod_b0", "mod_w2", "mod_b2")]
+_SummaryParams = _lib.AetherS2SGraphSummaryParams
+_FilmParams = _lib.AetherS2SFilmParams
 
 
 def _check(tensors, what):

@@ -21,13 +21,7 @@ from ... import _lib
 from .localizer import AugmentedLocalizer, Localizer
 
 
-class _PriorParams(C.Structure):
-    _fields_ = ([(n, C.c_void_p) for n in (
-        "mlp3_w0", "mlp3_b0", "mlp3_w3", "mlp3_b3", "mlp3_bn_w", "mlp3_bn_b", "mlp3_bn_mean", "mlp3_bn_var",
-        "mlp4_w0", "mlp4_b0", "mlp4_w3", "mlp4_b3", "mlp4_bn_w", "mlp4_bn_b", "mlp4_bn_mean", "mlp4_bn_var",
-        "lstm_w_ih", "lstm_w_hh", "lstm_b_ih", "lstm_b_hh")] +
-        [("prior_w", C.c_void_p * 4), ("prior_b", C.c_void_p * 4)] +
-        [(n, C.c_void_p) for n in ("res1_w", "res1_b", "filt_w0", "filt_b0", "filt_w2", "filt_b2", "filt_image")])
+_PriorParams = _lib.AetherS2SPriorParams
 
 
 def gumbel_softmax_hard(logits, uniform, tau):

@@ -18,8 +18,7 @@ import torch.nn as nn
 from ... import _lib
 
 
-class _S2SFieldParams(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("B", "w0", "b0", "w2", "b2", "w4", "b4")]
+_S2SFieldParams = _lib.AetherS2SFieldParams
 
 
 class _CoordinateEmbedding(nn.Module):

@@ -19,9 +19,7 @@ from .decoder import RecurrentDecoder
 from .localizer import AugmentedLocalizer, Localizer
 
 
-class _MarkovParams(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("lin1_w", "lin1_b", "lin2_w", "lin2_b", "res1_w", "res1_b", "out0_w", "out0_b",
-                                          "out3_w", "out3_b", "out6_w", "out6_b")]
+_MarkovParams = _lib.AetherS2SMarkovParams
 
 
 class MLPEdgeFilter(nn.Module):

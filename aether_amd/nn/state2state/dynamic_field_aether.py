@@ -64,12 +64,7 @@ class _LatentFieldNetwork(nn.Module):
         self.class_embedding = nn.Embedding(3, class_embedding_dim)
 
 
-class _DynFieldParams(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        "gate_w0", "gate_b0", "gate_w2", "gate_b2", "nn_w0", "nn_b0", "nn_w2", "nn_b2",
-        "lin1_w", "lin1_b", "lin2_w", "lin2_b", "lin3_w", "lin3_b",
-        "film1_w0", "film1_b0", "film1_w2", "film1_b2", "film1_w4", "film1_b4",
-        "film2_w0", "film2_b0", "film2_w2", "film2_b2", "film2_w4", "film2_b4", "emb")]
+_DynFieldParams = _lib.AetherDynFieldParams
 
 
 class _DynStep(torch.autograd.Function):

@@ -12,6 +12,11 @@
  * indices and to size the fused kernel's groups on the host).
  * All functions return 0 on success, a negative AETHER_E* code on error;
  * aether_last_error() returns a host string for the calling thread's last error.
+ *
+ * The Python binding (aether_amd/_lib.py) is generated from this file when it is imported: every integer #define, struct and
+ * prototype below becomes its ctypes counterpart, and a new entry needs no Python table edit.  The reader is a few regular
+ * expressions (aether_amd/_header.py), so the file stays inside the grammar of DESIGN.md section 1; a declaration outside it
+ * is an error at import, not a skipped entry.
  */
 #ifndef AETHER_HIP_H
 #define AETHER_HIP_H
