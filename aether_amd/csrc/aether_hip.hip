@@ -1709,6 +1709,8 @@ int aether_debug_fused_wave_role(int what, int wave) {
     if (wave < 0 || wave >= 12) return -1;
     if (what == 0) return wave >= FUSED_FRAME_WAVE0 && fused_frame_tile(wave) < FUSED_MAX_NODES / 16 ? fused_frame_tile(wave) : -1;
     if (what == 1) return wave >= FUSED_X0_WAVE0 && fused_x0_rowblock(wave) < FUSED_X0_WAVES ? fused_x0_rowblock(wave) : -1;
+    if (what == 3) return fused_product_step(wave);
+    if (what == 4) return wave == 0 ? (FUSED_WIMG / 2) * 4 : wave == 1 ? FUSED_MAX_NODES * LDW * 4 : -1;
     return -1;
 }
 

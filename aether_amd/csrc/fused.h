@@ -187,7 +187,58 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             }
         }
     };
-    dma_images(1);
+    // 12 waves (EARLY): the tiles of layers 2-4 never read wA -- their W_e e product ran under the previous node phase -- so
+    // wA is dead from the closing barrier of node phase l - 1 to the products of node phase l, and so is constants slot
+    // (l + 1) & 1.  W_e(l + 1) and constants block l + 1 are therefore copied a whole edge phase ahead (dma_ahead: 19
+    // fragments, dealt round-robin to `nslots` waves, this wave being number `slot` of them or none, slot < 0), and only
+    // W2(l + 1) is left for the node phase (dma_w2: 16 fragments on the four waves that are idle in step 2).  Layer 1's
+    // image A, which the tiles of layer 1 do read, goes to the P_s rows (L::W1A).
+    // The copy instruction stands in an asm statement: as a builtin inside the layer loop's edge phase it is, to the
+    // compiler's wait-count pass, an access that may return out of order with the LDS reads, and every counted lgkmcnt
+    // wait of the tiles behind it becomes an lgkmcnt(0) (29 waits instead of 54 in the tile code, + 2.1 us per step).
+    // Unseen, it only makes the compiler's counted vmcnt waits wait for more than they need: loads return in order.
+    // The waits for the copy itself are written by hand where its fragments are first read.
+    auto dma_frag = [&](int soff, int doff) {
+        const float* src = dbg.wimg + soff + lane * 4;
+        const unsigned dst = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + doff);
+        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(dst) : "memory", "m0");
+    };
+    auto dma_ahead = [&](int layer_, int slot, int nslots) {
+        const int g_img = fused_wimg_offset(layer_, 0), g_cb = fused_cblk_offset(layer_);
+        const int l_cb = L::CBLK + (layer_ & 1) * FUSED_CBLK;
+        constexpr int total = 16 + FUSED_CBLK / 256;
+#pragma unroll
+        for (int j = 0; j < (total + NW - 2) / (NW - 1); ++j) {
+            const int f = slot + nslots * j;
+            if (slot >= 0 && f < total) dma_frag(f < 16 ? g_img + f * 256 : g_cb + (f - 16) * 256, f < 16 ? L::WA + f * 256 : l_cb + (f - 16) * 256);
+        }
+    };
+    auto dma_w2 = [&](int layer_, int slot) {
+        const int g_img = fused_wimg_offset(layer_, 1);
+        constexpr int nw2 = NW > FUSED_W2DMA_WAVE0 ? NW - FUSED_W2DMA_WAVE0 : 1;
+        static_assert(16 % nw2 == 0, "every wave of step 2's idle ones issues the same number of fragments");
+#pragma unroll
+        for (int j = 0; j < 16 / nw2; ++j) {
+            const int f = slot + nw2 * j;
+            dma_frag(g_img + f * 256, L::WB + f * 256);
+        }
+    };
+    if constexpr (EARLY) {
+        const int wv = __builtin_amdgcn_readfirstlane(wave);
+        __builtin_assume(wv >= 0 && wv < NW);
+        constexpr int total = 8 + 16 + FUSED_CBLK / 256;      // W1 (half an image), W2(1), constants block 1 -> slot 1
+#pragma unroll
+        for (int j = 0; j < (total + NW - 1) / NW; ++j) {
+            const int f = wv + NW * j;
+            if (f < total)
+                dma_frag(f < 8 ? fused_wimg_offset(1, 0) + f * 256 : f < 24 ? fused_wimg_offset(1, 1) + (f - 8) * 256 : fused_cblk_offset(1) + (f - 24) * 256,
+                         f < 8 ? L::W1A + f * 256 : f < 24 ? L::WB + (f - 8) * 256 : L::CBLK + FUSED_CBLK + (f - 24) * 256);
+        }
+        // W_e(2) -> wA, block 2 -> slot 0: neither has been written yet in this launch
+        dma_ahead(2, wv, NW);
+    } else {
+        dma_images(1);
+    }
     FUSED_STAMP(1);
 
     // ---------------------------------------------------------------- edge indices of P2, requested during P1
@@ -873,7 +924,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb) acc[mb] = ld4(cb + CB_B1 + 16 * mb + 4 * q);
                 f32x4 bop[2] = {e[r][0], e[r][1]};
-                gemm_split<4, 1>(wA, bop, acc, lane);
+                gemm_split<4, 1>(EARLY ? smem + L::W1A : wA, bop, acc, lane);      // (EARLY: layer 1's image A lies in the P_s rows)
             } else {
                 f32x4 pr[4], st[4];          // st: what the product is added to, P_r + P_s or P_r alone
 #pragma unroll
@@ -1016,7 +1067,7 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
             asm volatile("" ::: "memory");
         };
         // 12 waves: g = W_e(layer + 1) e of the wave's tile, in place, under this layer's node phase (the image is in wA
-        // behind the "u complete" barrier).  gemm_split as the tile would run it: same k order, small terms first, same
+        // since the post-edge barrier: dma_ahead).  gemm_split as the tile would run it: same k order, small terms first, same
         // operand scale.  A wave without a tile has nothing to multiply.
         auto early_product = [&]() {
             if (n_tiles > wave) {
@@ -1090,6 +1141,21 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         };
         {
             const int nvalid = n_tiles > wave ? (n_tiles - wave + NW - 1) / NW : 0;    // wave-uniform
+            if constexpr (EARLY) {
+                // W_e(layer + 1) -> wA and constants block layer + 1 -> slot (layer + 1) & 1, a layer ahead (layer 1: with the
+                // prologue's DMA).  Safe without a second slot: every read of wA as W_e(layer) -- the products of node phase
+                // layer - 1 -- precedes that phase's closing barrier, and so does the last read of the slot, which held block
+                // layer - 1 (CB_B1N in step 4).  The receiving wave issues none: its sweep waits vmcnt(0) and would wait for
+                // the copy; the other eleven share the 19 fragments whether or not the view is split.  This wave's fragments are
+                // its oldest loads in flight: the node phase's prefetch, eight loads per wave, is issued behind them.
+                // (in front of the prefetch of a wave without a tile, too)
+                if (layer == 2 || layer == 3) {
+                    const int recv_wave = GRAN && na >= 16 ? 0 : NW - 1;          // (see below)
+                    const int wv = __builtin_amdgcn_readfirstlane(wave);
+                    dma_ahead(layer + 1, wv == recv_wave ? -1 : wv - (wv > recv_wave ? 1 : 0), NW - 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
             if (nvalid == 0) {
 #pragma unroll
                 for (int part = 1; part < 5; ++part) issue_loads(part);
@@ -1140,7 +1206,11 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         }
         FUSED_STAMP(4 + 8 * (layer - 1) + 2);
         // ------------------------------------------------------------ node phase (locs.py:240-241)
-        lds_barrier();       // all partial rows are published; wA / wB are idle
+        // EARLY: this wave's fragments of W_e(layer + 1) and constants block layer + 1 (dma_ahead, top of the edge phase) have
+        // landed: everything but the eight younger loads of the node phase's prefetch, which stay in flight (loads return
+        // in order).
+        if constexpr (EARLY) __builtin_amdgcn_s_waitcnt(0x0F78);       // vmcnt(8)
+        lds_barrier();       // all partial rows are published; wB is idle (12 waves: wA holds W_e(layer + 1) whole already)
         FUSED_STAMP(4 + 8 * (layer - 1) + 3);
         // step 1: n = x_prev + (sum of the node's partial rows, in tile order) / max(deg, 1)
         if (tid < FUSED_MAX_NODES * 16) {
@@ -1162,11 +1232,18 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         // The wave's W3 / W4 / W_s / W_r fragments have arrived: a wait the compiler's wait-count pass sees (simm16 of
         // vmcnt(0) alone), so that it places none of its own in steps 2-4 -- in particular none behind the LDS-DMA below.
         __builtin_amdgcn_s_waitcnt(0x0F70);
-        // next layer's images and constants: in flight under step 2 (12 waves with the early product: waited for in front
-        // of the "u complete" barrier) or steps 2-4 (waited for before step 4's barrier)
-        if (layer < 4) dma_images(layer + 1);
+        // next layer's images and constants: in flight under steps 2-4, waited for before step 4's barrier (12 waves: W_e and
+        // the constants came a layer ahead, W2 is issued in step 2)
+        if constexpr (!EARLY) {
+            if (layer < 4) dma_images(layer + 1);
+        }
         lds_barrier();       // n complete
         FUSED_STAMP(4 + 8 * (layer - 1) + 7);
+        if constexpr (EARLY) {
+            // W2(layer + 1) -> wB, which the tiles of this layer read up to the post-edge barrier: issued by the waves that have
+            // no row block in step 2, waited for in step 4 (granules) or in front of the closing barrier
+            if (layer < 4 && wave >= FUSED_W2DMA_WAVE0) dma_w2(layer + 1, __builtin_amdgcn_readfirstlane(wave) - FUSED_W2DMA_WAVE0);
+        }
         // step 2: u = SiLU(W3 n + b3): rows 16*mb2.. of u for both node tiles
         if (act3) {
             float* ubuf = smem + L::UBUF;
@@ -1191,17 +1268,12 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
                 }
             }
         }
-        if constexpr (EARLY) {
-            // the one vmcnt wait between step 1's barrier and step 4's closing barrier: this wave's fragments of the next
-            // layer's images have landed; behind the barrier wA holds W_e(layer + 1) whole
-            if (layer < 4) __builtin_amdgcn_s_waitcnt(0x0F70);
-        }
         lds_barrier();       // u complete
         FUSED_STAMP(4 + 8 * (layer - 1) + 4);
         if constexpr (EARLY) {
             // waves 0-7 have nothing to do in step 3: their tile's product for the next layer runs here, next to the four
             // waves (8-11) of step 3, and never between a barrier and node-phase work that somebody waits for
-            if (layer < 4 && wave < 8) {
+            if (layer < 4 && fused_product_step(wave) == 3) {
                 FUSED_WSTAMP(layer + 1, 0, 8);
                 early_product();
                 FUSED_WSTAMP(layer + 1, 0, 9);
@@ -1241,11 +1313,11 @@ k_fused(AetherParams P, const float* __restrict__ x, const float* __restrict__ v
         if (layer < 4) {
             // granules: the LDS-DMA of the next layer's images and constants (issued in step 1) is waited for HERE, where it
             // has long landed, and not in front of the closing barrier: the granule stores below stay in flight across it
-            // (with the early product it was waited for in front of the "u complete" barrier)
-            if constexpr (GRAN && !EARLY) __builtin_amdgcn_s_waitcnt(0x0F70);
+            // (12 waves: W2 alone, issued in step 2 by waves 8-11)
+            if constexpr (GRAN) __builtin_amdgcn_s_waitcnt(0x0F70);
             if constexpr (EARLY) {
                 // ... and waves 8-11, which ran step 3, have nothing to do in step 4
-                if (wave >= 8) {
+                if (fused_product_step(wave) == 4) {
                     FUSED_WSTAMP(layer + 1, 0, 8);
                     early_product();
                     FUSED_WSTAMP(layer + 1, 0, 9);

@@ -26,6 +26,14 @@ __device__ __host__ constexpr int fused_x0_rowblock(int wave) { return wave - FU
 static_assert(FUSED_FRAME_WAVE0 >= FUSED_MAX_NODES / 16 && FUSED_FRAME_WAVE0 + FUSED_MAX_NODES / 16 <= 12 && FUSED_X0_WAVE0 + FUSED_X0_WAVES <= 12 &&
               FUSED_X0_WAVES * 16 == H, "frame waves behind the field waves, one x0 wave per 16 of the H rows");
 
+// 12-wave kernels, node phase: the window in which a wave multiplies its tile by the next layer's W_e (early_product) --
+// step 3's for the waves that have no row block there (0-7), step 4's for the four that run step 3 (8-11).  Those four
+// have no row block in step 2 either: they issue the LDS-DMA of the next layer's W2 there.  (Products in step 1's window
+// -- waves 4-11 beside the node sums -- or step 2's -- waves 8-11 -- cost 2 us per step: HISTORY R31.)
+constexpr int FUSED_STEP3_WAVE0 = 8;
+__device__ __host__ constexpr int fused_product_step(int wave) { return wave < FUSED_STEP3_WAVE0 ? 3 : 4; }
+constexpr int FUSED_W2DMA_WAVE0 = FUSED_STEP3_WAVE0;
+
 // The edge MLP's two 64 x 64 contractions run as three fp16 MFMA terms on operands split into two fp16 pieces (common.h,
 // gemm_split); the weight images (2 x 8 KB each instead of 18 KB of padded fp32) fit every variant since the layer-1 features of the
 // 17-24 tile one are built two rounds at a time.
@@ -87,6 +95,10 @@ template <int NW, int ROUNDS> struct FusedLds {          // offsets in floats
     static constexpr int XPC = UPC + 2 * SPLIT_PIECES;
     static constexpr int OPC = XPC + SPLIT_PIECES;
     static constexpr int PFLAG = OPC + SPLIT_PIECES;                   // [5 operands][4 producing waves] range words (n, u half 0, u half 1, x, o1)
+    // 12 waves: layer 1's image A (W1 padded to K = 32, half an image) lies in the P_s rows, which nobody touches before
+    // step 4 of layer 1; wA holds W_e(2) from the prologue on.
+    static constexpr int W1A = PS;
+    static_assert(FUSED_WIMG / 2 <= FUSED_MAX_NODES * LDW && W1A % 256 == 0, "layer 1's image A fits the P_s rows, on a fragment boundary");
     static_assert(NW != 12 || (NPC >= OBUF2 + FUSED_MAX_NODES * LDW && NPC >= UBUF + FUSED_MAX_NODES * LDU && PFLAG + 5 * 4 <= TOTAL && NPC % 4 == 0), "operand pieces");
     static_assert(FIELD_END <= TOTAL, "field scratch");
     static_assert(UBUF + FUSED_MAX_NODES * LDU <= TOTAL, "ubuf");

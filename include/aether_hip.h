@@ -260,7 +260,10 @@ int aether_debug_fused_packed_edge(int wave, int lane);
 /*
  * Test hook of the 12-wave fused kernels' wave roles behind the field waves (csrc/fused_layout.h), wave in 0 .. 11:
  *   what 0  the visible node tile whose frames the wave builds (fused_frame_tile), or -1;
- *   what 1  the 16-row block of x0 the wave computes behind the prologue's barrier (fused_x0_rowblock), or -1.
+ *   what 1  the 16-row block of x0 the wave computes behind the prologue's barrier (fused_x0_rowblock), or -1;
+ *   what 3  the step of the node phase in whose window the wave multiplies its tile by the next layer's W_e
+ *           (fused_product_step): 3 or 4;
+ *   what 4  layout, not a role: bytes of layer 1's weight image A (wave 0) and of the P_s rows that hold it (wave 1).
  * Host only: needs no GPU.
  */
 int aether_debug_fused_wave_role(int what, int wave);

@@ -96,10 +96,20 @@ for w in range(12):            # 8 or 12 waves per workgroup (FUSED_WSTAMP: 24 s
         print(f"   {w:4d} {r:5d} {v[0]:8.0f} {d[0]:9.0f} {d[1]:12.0f} {d[2]:18.0f} {d[3]:6.0f}    | {v[5]-v[0]:6.0f}{late}")
 early = [(w, med[64 + w * 24 + 8], med[64 + w * 24 + 9]) for w in range(12)]     # FUSED_WSTAMP(2, 0, 8 / 9): 12-wave kernels only
 if any(t1 > 0 for _, _, t1 in early):
-    print("  layer 2's W_e e product under layer 1's node phase (waves 0-7: step 3's window, waves 8-11: step 4's), cycles since kernel entry:")
+    # the window a wave multiplies in, from the stamps themselves: thread 0's wall-clock stamps of layer 1's node phase
+    # (post-edge barrier, n complete, u complete, step 3's barrier, closing barrier) against the product's first cycle
+    b = 4
+    edges = [("step 1", med[b + 3], med[b + 7]), ("step 2", med[b + 7], med[b + 4]), ("step 3", med[b + 4], med[b + 5]),
+             ("step 4", med[b + 5], med[b + 6])]
+    print("  layer 2's W_e e product under layer 1's node phase, cycles since kernel entry (window: the step whose barriers enclose its start):")
+    groups = {}
     for w, t0, t1 in early:
         if t1 > 0:
-            print(f"   wave {w:2d}: {t0:8.0f} .. {t1:8.0f}  ({t1 - t0:5.0f})")
+            win = next((name for name, lo, hi in edges if lo * clk - 200 <= t0 < hi * clk - 200), "?")
+            groups.setdefault(win, []).append(t1 - t0)
+            print(f"   wave {w:2d}: {t0:8.0f} .. {t1:8.0f}  ({t1 - t0:5.0f})  {win}")
+    for win, cyc in sorted(groups.items()):
+        print(f"   {win}'s window: {len(cyc)} waves, product {min(cyc):.0f} .. {max(cyc):.0f} cycles (median {np.median(cyc):.0f})")
 for w in range(12):            # the wave that copies the partner's rows (split groups): slots 6, 7 of its first round
     v = med[64 + w * 24: 64 + w * 24 + 8]
     if v[6] > 0:
