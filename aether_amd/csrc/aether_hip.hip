@@ -48,6 +48,7 @@
 #include "knn.h"
 #include "dyn_step.h"
 #include "dyn_dnri.h"
+#include "dyn_loss.h"
 #include "sim.h"
 #include "train_step.h"
 #include "egnn.h"
@@ -1061,6 +1062,7 @@ const char* aether_last_error(void) { return g_err; }
 #include "host_dynamicvars.inc"
 #include "host_dyn_step.inc"
 #include "host_dyn_dnri.inc"
+#include "host_dyn_loss.inc"
 #include "host_sim.inc"
 #include "host_train.inc"
 #include "host_gnn_common.inc"

@@ -37,8 +37,10 @@ struct DynDnriDecLayout {
 int dyn_dnri_prior_impl(const AetherDynDnriPriorParams* p, int h, int R, int prior_layers, int ph, int K, int64_t Nn, int64_t E,
                         const float* inputs, const float* h0, const float* c0, const int64_t* send, const int64_t* recv,
                         const int64_t* order, const int64_t* rowptr, void* workspace, size_t workspace_bytes, float* logits,
-                        float* h1, float* c1, hipStream_t st) {
-    if (!p || !inputs || !h0 || !c0 || !send || !recv || !order || !rowptr || !workspace || !logits || !h1 || !c1)
+                        float* h1, float* c1, hipStream_t st, const NriSeqTail* seq = nullptr) {
+    // seq: null (one prior step from h0 / c0), or the sequence encoder's tail on the same rows -- the LSTM step from the zero
+    // state and both heads (host_nri_chain.inc 3b); h0, c0 and c1 are not read or written then.
+    if (!p || !inputs || !send || !recv || !order || !rowptr || !workspace || !logits || !h1 || (!seq && (!h0 || !c0 || !c1)))
         return fail(AETHER_EINVAL, "dyn_dnri_prior: null pointer");
     if (h < 128 || h % 128 != 0) return fail(AETHER_EINVAL, "dyn_dnri_prior: hidden must be a multiple of 128");
     if (R < 16 || R % 16 != 0) return fail(AETHER_EINVAL, "dyn_dnri_prior: rnn_hidden must be a multiple of 16");
@@ -75,6 +77,12 @@ int dyn_dnri_prior_impl(const AetherDynDnriPriorParams* p, int h, int R, int pri
     }
     // ---- mlp1's second layer .. mlp4 (:412-421): node products instead of [E, 2h] / [E, 3h] rows, index_add_ over the receiver
     if (int rc = nri_dnri_prior(p, c, [](S2SJobs&) { return (int)AETHER_OK; }, st)) return rc;
+    if (seq) {   // ---- every frame from the zero state, prior_fc_out and encoder_fc_out (:499-541)
+        if (int rc = nri_seq_tail(p->lstm_w_ih, p->lstm_b_ih, p->lstm_b_hh, p->prior_w, p->prior_b, prior_layers, ph, *seq, h, R, K,
+                                  E, c.out, h1, m.wp(L.Y1), m.wp(L.Y2), logits, st)) return rc;
+        HIP_OK(hipGetLastError());
+        return AETHER_OK;
+    }
     // ---- one LSTM step per edge (:558-560), prior_fc_out (:566): no images, so the fp32 job kernel with the summed bias, then the cell
     if (int rc = nri_lstm_head(NriLstmHead{p->lstm_w_ih, p->lstm_w_hh, m.wp(L.lb), nullptr, nullptr, nullptr, p->prior_w, p->prior_b,
                                            {nullptr, nullptr, nullptr, nullptr}, c.out, h0, c0, m.wp(L.G), h1, c1, m.wp(L.Y1),
@@ -183,13 +191,36 @@ struct DynDnriModel {
                                    X.ip(L.krowptr), X.ws + L.ws_prior, L.b_prior, X.fp(L.logits), X.fp(L.h1), X.fp(L.c1), X.st());
     }
     // decoder step on the callers' graphs (:618-688); its last kernel writes the rows back to their objects
-    int decode(const Ctx& X, const float* ew) const {
+    int decode(const Ctx& X, const float* ew, bool = true) const {      // (no frames: nothing of the prior step is read)
         const Layout& L = X.L;
         const AetherDynStepConfig& c = X.c;
         const DynDnriScatter sc{X.cidx(), X.status(), X.rows, X.decoder_hidden, true};
         return dyn_dnri_decoder_impl(decoder_params, c.decoder_hidden, c.num_edge_types, c.skip_first, X.n, X.E, X.fp(L.cur_in),
                                      X.fp(L.cur_h), ew, X.ip(L.send), X.ip(L.recv), X.ip(L.order), X.ip(L.rowptr_dec), 1.0f,
                                      X.fp(L.div_node), X.ws + L.ws_dec, L.b_dec, X.prediction, X.fp(L.new_h), X.st(), &sc);
+    }
+    // ---- the evaluation half of calculate_loss (host_dyn_loss.inc: dyn_seq_run, dyn_loss_run)
+    static constexpr const char* seq_name = "dyn_dnri_sequence_logits";
+    static constexpr const char* loss_name = "dyn_dnri_loss_rollout";
+    bool seq_params_ok() const { return prior_params != nullptr; }
+    bool loss_params_ok() const { return decoder_params != nullptr; }
+    static size_t seq_field_bytes(const AetherDynStepConfig&, const DynBatchSizes&) { return 0; }
+    static size_t seq_prior_bytes(const AetherDynStepConfig& c, const DynBatchSizes& Z) {
+        return DynDnriPriorLayout(c.encoder_hidden, c.rnn_hidden, c.prior_hidden, Z.n_total, Z.e_total).total;
+    }
+    int seq_field(const DynSeqCtx&) const { return AETHER_OK; }
+    int seq_prior(const DynSeqCtx& Q) const {
+        const AetherDynStepConfig& c = Q.c;
+        return dyn_dnri_prior_impl(prior_params, c.encoder_hidden, c.rnn_hidden, c.prior_layers, c.prior_hidden, c.num_edge_types,
+                                   Q.n, Q.E, Q.fp(Q.L.cur_in), nullptr, nullptr, Q.ip(Q.L.ksend), Q.ip(Q.L.krecv), Q.ip(Q.L.korder),
+                                   Q.ip(Q.L.krowptr), Q.ws + Q.L.ws_prior, Q.L.b_prior, Q.prior_logits, Q.fp(Q.L.h1), nullptr,
+                                   (hipStream_t)Q.stream, &Q.tail);
+    }
+    void loss_graph(const Ctx& X) const {
+        const Layout& L = X.L;
+        k_dyn_loss_graph<<<dyn_blocks(std::max<int64_t>(X.E, X.Z.o_total)), dim3(256), 0, X.st()>>>(
+            X.graph_send, X.graph_recv, X.edge2node, X.n, X.E, X.Z.o_total, X.S.n_max, X.ip(L.send), X.ip(L.recv), X.ip(L.order),
+            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, X.status());
     }
 };
 }  // namespace

@@ -65,6 +65,28 @@ struct DynBatchLayout : DynSceneLayout {
     }
 };
 
+// The sequence encoder's buffers: the scene bookkeeping of a step, the field at the present rows and the model's prior
+// workspace (sizes from the model), the posterior head's hidden rows and the decoder-count words k_dynb_present clears.
+struct DynSeqLayout : DynSceneLayout {
+    size_t field_c, ws_field, ws_prior, P1, P2, counts;
+    size_t b_field, b_prior;
+    DynSeqLayout(const AetherDynStepConfig& c, int F, int n_max, const DynBatchSizes& Z, size_t field_bytes, size_t prior_bytes,
+                 int post_hidden)
+        : DynSceneLayout(c, F, n_max, Z), b_field(field_bytes), b_prior(prior_bytes) {
+        const size_t nn = (size_t)Z.n_total, ee = (size_t)Z.e_total, ph = (size_t)(post_hidden > 0 ? post_hidden : 1);
+        field_c = take(nn * 8); ws_field = take(b_field); ws_prior = take(b_prior);
+        P1 = take(ee * ph * 4); P2 = take(ee * ph * 4); counts = take(64 * 4);
+    }
+};
+
+// (host_dyn_loss.inc) What a model's stages of the sequence encoder see
+struct DynSeqCtx {
+    const AetherDynStepConfig& c; const DynSeqLayout& L; char* ws; void* stream; int n; int64_t E;
+    const NriSeqTail& tail; float* prior_logits;
+    float* fp(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+    int64_t* ip(size_t off) const { return reinterpret_cast<int64_t*>(ws + off); }
+};
+
 // Every scene is empty (n = 0) or passes dyn_step_check; fills the by-value scene table and the totals.
 int dyn_batch_check(const AetherDynStepConfig* c, int B, int n_max, const int64_t* n_present, const int64_t* n_edges,
                     const int* in_degree, DynScenes* S, DynBatchSizes* Z) {
@@ -293,15 +315,17 @@ struct DynAetherModel {
                                      X.ip(L.ksend), X.ip(L.krecv), X.ip(L.korder), X.ip(L.krowptr), X.ws + L.ws_prior, L.b_prior,
                                      X.fp(L.logits), X.fp(L.h1), X.fp(L.c1), X.stream);
     }
-    // decoder step on the callers' graphs (:775-870), rows back to their objects
-    int decode(const Ctx& X, const float* ew) const {
+    // decoder step on the callers' graphs (:775-870), rows back to their objects.  prior_nodes: the prior step of the same
+    // call has the canonical states and frames of these rows in its workspace (false: the decoder computes its own)
+    int decode(const Ctx& X, const float* ew, bool prior_nodes = true) const {
         const Layout& L = X.L;
         const AetherDynStepConfig& c = X.c;
         const int hd = c.decoder_hidden;
         const DynPriorLayout PL(c.encoder_hidden, c.rnn_hidden, c.prior_hidden, X.n, X.E);
-        const DynSharedNodes shared{reinterpret_cast<const float*>(X.ws + L.ws_prior + PL.ext),
-                                    reinterpret_cast<const float*>(X.ws + L.ws_prior + PL.rel),
-                                    reinterpret_cast<const float*>(X.ws + L.ws_prior + PL.Rinv), true};
+        DynSharedNodes shared{reinterpret_cast<const float*>(X.ws + L.ws_prior + PL.ext),
+                              reinterpret_cast<const float*>(X.ws + L.ws_prior + PL.rel),
+                              reinterpret_cast<const float*>(X.ws + L.ws_prior + PL.Rinv), true};
+        if (!prior_nodes) shared.ext = shared.rel = shared.Rinv = nullptr;
         if (int rc = dyn_decoder_impl(decoder_params, hd, c.num_edge_types, c.skip_first, c.decoder_polar, X.n, X.E, X.fp(L.cur_in),
                                       X.fp(L.cur_h), ew, X.fp(L.field_c), X.fp(L.ext_full), X.ip(L.ssend), X.ip(L.srecv),
                                       X.ip(L.send), X.ip(L.recv), X.ip(L.order), X.ip(L.rowptr_dec), 1.0f, X.fp(L.div_node),
@@ -310,6 +334,37 @@ struct DynAetherModel {
         k_dynb_finish<<<dyn_blocks(work), dim3(256), 0, X.st()>>>(X.fp(L.out_c), X.fp(L.new_h), X.cidx(), X.ip(L.idx), X.status(),
                                                                  X.rows, X.n, hd, X.prediction, X.decoder_hidden);
         return AETHER_OK;
+    }
+    // ---- the evaluation half of calculate_loss (host_dyn_loss.inc: dyn_seq_run, dyn_loss_run)
+    static constexpr const char* seq_name = "dyn_sequence_logits";
+    static constexpr const char* loss_name = "dyn_loss_rollout";
+    bool seq_params_ok() const { return field_params && prior_params; }
+    bool loss_params_ok() const { return field_params && decoder_params; }
+    static size_t seq_field_bytes(const AetherDynStepConfig& c, const DynBatchSizes& Z) {
+        return aether_dyn_field_workspace_bytes(Z.n_total, c.field_hidden);
+    }
+    static size_t seq_prior_bytes(const AetherDynStepConfig& c, const DynBatchSizes& Z) {
+        return aether_dyn_prior_workspace_bytes(c.encoder_hidden, c.rnn_hidden, c.prior_hidden, Z.n_total, Z.e_total);
+    }
+    int seq_field(const DynSeqCtx& Q) const {
+        return aether_dyn_field(field_params, Q.c.field_hidden, Q.n, Q.fp(Q.L.cur_in), Q.ws + Q.L.ws_field, Q.L.b_field,
+                                Q.fp(Q.L.field_c), Q.stream);
+    }
+    int seq_prior(const DynSeqCtx& Q) const {
+        const AetherDynStepConfig& c = Q.c;
+        return dyn_prior_impl(prior_params, c.encoder_hidden, c.rnn_hidden, c.prior_layers, c.prior_hidden, c.num_edge_types,
+                              c.encoder_polar, Q.n, Q.E, Q.fp(Q.L.cur_in), Q.fp(Q.L.field_c), nullptr, nullptr, Q.ip(Q.L.ksend),
+                              Q.ip(Q.L.krecv), Q.ip(Q.L.korder), Q.ip(Q.L.krowptr), Q.ws + Q.L.ws_prior, Q.L.b_prior,
+                              Q.prior_logits, Q.fp(Q.L.h1), nullptr, Q.stream, &Q.tail);
+    }
+    // the data set's graph of a step of the loss loop as the decoder takes it, ext_full (:823)
+    void loss_graph(const Ctx& X) const {
+        const Layout& L = X.L;
+        const int64_t work = std::max<int64_t>(std::max<int64_t>(X.E, X.Z.o_total), X.rows * 6);
+        k_dyn_loss_graph<<<dyn_blocks(work), dim3(256), 0, X.st()>>>(X.graph_send, X.graph_recv, X.edge2node, X.n, X.E, X.Z.o_total,
+                                                                    X.S.n_max, X.ip(L.send), X.ip(L.recv), X.ip(L.order),
+                                                                    X.ip(L.ssend), X.ip(L.srecv), X.state, X.fp(L.field_c), X.cidx(),
+                                                                    X.fp(L.ext_full), X.status());
     }
 };
 }  // namespace

@@ -76,6 +76,7 @@ int aether_dyn_decoder_step(const AetherDynDecoderParams* p, int hidden, int num
 
 // Canonical state / frames of the present objects when another stage of the same step has them already (aether_dyn_step:
 // the prior step computes exactly these from the same rows): [n][6], [n][15], [n][4]
+// (ext == nullptr: the decoder computes its own, and only counts_zeroed is read)
 struct DynSharedNodes { const float* ext; const float* rel; const float* Rinv; bool counts_zeroed; };
 static int dyn_decoder_impl(const AetherDynDecoderParams* p, int hidden, int num_edge_types, int skip_first,
                             int polar, int64_t n_nodes, int64_t n_edges, const float* inputs,
@@ -130,7 +131,7 @@ static int dyn_decoder_impl(const AetherDynDecoderParams* p, int hidden, int num
     auto elist = [&](int k) { return reinterpret_cast<int64_t*>(ws + L.list[k]); };
     // ---- canonical state and frames of the present objects (:790)
     const float *n_ext = wp(L.ext), *n_rel = wp(L.rel), *n_Rinv = wp(L.Rinv);
-    if (shared) { n_ext = shared->ext; n_rel = shared->rel; n_Rinv = shared->Rinv; }
+    if (shared && shared->ext) { n_ext = shared->ext; n_rel = shared->rel; n_Rinv = shared->Rinv; }
     else k_s2s_aug_nodes<2><<<blocks(Nn), dim3(256), 0, st>>>(nullptr, wp(L.rel), wp(L.Rinv), Nn, inputs, field, wp(L.ext));
     S2SJobs T;
     if (E > 0) {
@@ -260,12 +261,28 @@ size_t aether_dyn_prior_workspace_bytes(int hidden, int rnn_hidden, int prior_hi
     return DynPriorLayout(hidden, rnn_hidden, prior_hidden, n_nodes, n_edges).total;
 }
 
+// seq: null (one prior step from h0 / c0), or the sequence encoder's tail on the same rows -- the LSTM step from the zero state
+// and both heads (host_nri_chain.inc 3b); h0, c0 and c1 are not read or written then.
+static int dyn_prior_impl(const AetherDynPriorParams* p, int hidden, int rnn_hidden, int prior_layers, int prior_hidden,
+                          int num_edge_types, int polar, int64_t n_nodes, int64_t n_edges, const float* inputs,
+                          const float* field, const float* h0, const float* c0, const int64_t* send, const int64_t* recv,
+                          const int64_t* order, const int64_t* rowptr, void* workspace, size_t workspace_bytes,
+                          float* logits, float* h1, float* c1, void* stream, const NriSeqTail* seq);
 int aether_dyn_prior_step(const AetherDynPriorParams* p, int hidden, int rnn_hidden, int prior_layers, int prior_hidden,
                           int num_edge_types, int polar, int64_t n_nodes, int64_t n_edges, const float* inputs,
                           const float* field, const float* h0, const float* c0, const int64_t* send, const int64_t* recv,
                           const int64_t* order, const int64_t* rowptr, void* workspace, size_t workspace_bytes,
                           float* logits, float* h1, float* c1, void* stream) {
-    if (!p || !inputs || !field || !h0 || !c0 || !send || !recv || !order || !rowptr || !workspace || !logits || !h1 || !c1)
+    return dyn_prior_impl(p, hidden, rnn_hidden, prior_layers, prior_hidden, num_edge_types, polar, n_nodes, n_edges, inputs, field,
+                          h0, c0, send, recv, order, rowptr, workspace, workspace_bytes, logits, h1, c1, stream, nullptr);
+}
+static int dyn_prior_impl(const AetherDynPriorParams* p, int hidden, int rnn_hidden, int prior_layers, int prior_hidden,
+                          int num_edge_types, int polar, int64_t n_nodes, int64_t n_edges, const float* inputs,
+                          const float* field, const float* h0, const float* c0, const int64_t* send, const int64_t* recv,
+                          const int64_t* order, const int64_t* rowptr, void* workspace, size_t workspace_bytes,
+                          float* logits, float* h1, float* c1, void* stream, const NriSeqTail* seq) {
+    if (!p || !inputs || !field || !send || !recv || !order || !rowptr || !workspace || !logits || !h1 ||
+        (!seq && (!h0 || !c0 || !c1)))
         return fail(AETHER_EINVAL, "dyn_prior: null pointer");
     if (hidden < 128 || hidden % 128 != 0) return fail(AETHER_EINVAL, "dyn_prior: hidden must be a multiple of 128");
     if (rnn_hidden < 16 || rnn_hidden % 16 != 0) return fail(AETHER_EINVAL, "dyn_prior: rnn_hidden must be a multiple of 16");
@@ -329,6 +346,12 @@ int aether_dyn_prior_step(const AetherDynPriorParams* p, int hidden, int rnn_hid
     k_s2s_edge_sum_elu<<<blocks(E * (h / 4)), dim3(256), 0, st>>>(wp(L.T1), wp(L.Ps), wp(L.Pr), send, recv, h, E);
     if (s2s_linear(4, p->mlp4_w3, h, p->mlp4_b3, wp(L.T1), wp(L.X4), h, h, E, h, nullptr, 0, 0, st, nullptr, nullptr, nullptr,
                    bns[2][0], bns[2][1])) return AETHER_EINVAL;
+    if (seq) {   // ---- every frame from the zero state, prior_fc_out and encoder_fc_out (:620-668)
+        if (int rc = nri_seq_tail(p->lstm_w_ih, p->lstm_b_ih, p->lstm_b_hh, p->prior_w, p->prior_b, prior_layers, prior_hidden, *seq,
+                                  h, R, K, E, wp(L.X4), h1, wp(L.Y1), wp(L.Y2), logits, st)) return rc;
+        HIP_OK(hipGetLastError());
+        return AETHER_OK;
+    }
     // ---- one LSTM step per edge, prior_fc_out (:688-696)
     if (int rc = nri_lstm_two_launch(p->lstm_w_ih, p->lstm_w_hh, p->lstm_b_ih, p->lstm_b_hh, h, R, E, wp(L.X4), h0, c0, wp(L.G), h1,
                                      c1, st)) return rc;

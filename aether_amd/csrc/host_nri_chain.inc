@@ -126,6 +126,46 @@ int nri_head_linear(const float* const* w, const float* const* b, int layers, in
     return AETHER_OK;
 }
 
+// ---- 3b. the tail of the variable-N sequence encoders (Encoder.forward, aether_dynamicvars.py:588-670, dnri_dynamicvars.py:
+// 463-542) on the mlp4 rows x [rows][h] of ALL frames: the LSTM step from the zero state (k_dyn_lstm_zero: the reference
+// never writes the forward state back, and never runs reverse_rnn), then prior_fc_out(h1) and encoder_fc_out([h1 | 0]) layer
+// by layer, the two heads' layers of the same depth in one launch.  The posterior head's first Linear reads the first R of its
+// 2R input columns: its weight goes in with a row stride of 2R, no zero-padded copy of h1 is made.
+struct NriSeqTail {
+    const float* const* post_w; const float* const* post_b;      // encoder_fc_out, 1 .. 4 layers
+    int post_layers, post_hidden;
+    float *P1, *P2, *posterior_logits;                           // [rows][post_hidden] x 2 (unused with one layer), [rows][K]
+    const int* status;                                           // k_dyn_lstm_zero's poison word, or null
+};
+int nri_seq_tail(const float* w_ih, const float* b_ih, const float* b_hh, const float* const* prior_w, const float* const* prior_b,
+                 int prior_layers, int ph, const NriSeqTail& q, int h, int R, int K, int64_t rows, const float* x, float* h1,
+                 float* Y1, float* Y2, float* prior_logits, hipStream_t st) {
+    k_dyn_lstm_zero<<<dim3((unsigned)((rows + 63) / 64), (unsigned)(R / 16)), dim3(256), 0, st>>>(x, w_ih, b_ih, b_hh, h, R, rows,
+                                                                                               q.status, h1);
+    const float *pc = h1, *qc = h1;
+    int pk = R, qk = R;
+    for (int l = 0; l < std::max(prior_layers, q.post_layers); ++l) {
+        S2SJobs T;
+        T.n = 0;
+        if (l < prior_layers) {
+            const bool last = l + 1 == prior_layers;
+            float* dst = last ? prior_logits : l % 2 == 0 ? Y1 : Y2;
+            const int M = last ? K : ph;
+            T.j[T.n++] = s2s_job(last ? 0 : 4, prior_w[l], pk, prior_b[l], pc, pk, dst, M, M, pk, rows);
+            pc = dst; pk = M;
+        }
+        if (l < q.post_layers) {
+            const bool last = l + 1 == q.post_layers;
+            float* dst = last ? q.posterior_logits : l % 2 == 0 ? q.P1 : q.P2;
+            const int M = last ? K : q.post_hidden;
+            T.j[T.n++] = s2s_job(last ? 0 : 4, q.post_w[l], l == 0 ? 2 * R : qk, q.post_b[l], qc, qk, dst, M, M, qk, rows);
+            qc = dst; qk = M;
+        }
+        if (int rc = s2s_launch_jobs(T, st)) return rc;
+    }
+    return AETHER_OK;
+}
+
 // ---- 4. the dNRI prior from mlp1's second layer (on X1a [Nn][h], the caller's node kernel's) to mlp4 -> out [E][h].
 // first_jobs(T) adds what rides in the first launch (and flushes T itself where it fills up).  Receiver reduction between mlp2
 // and mlp3: mean_div > 0 the in-edge sum / mean_div (k_s2s_segment_mean), 0 the plain sum (k_dyn_dnri_recv_sum)

@@ -4,8 +4,9 @@
 
 Sub-modules carry the reference's names (``encoder``, ``decoder``, ``field_net``, ``coordinate_embedding``,
 ``angular_embedding``) and are created in its order, so a seeded construction or ``load_state_dict`` of a reference
-checkpoint gives the same weights.  The training loss (``calculate_loss``) and the posterior encoder are not part
-of this path.  No CPU fallback.
+checkpoint gives the same weights.  ``calculate_loss(is_train=False)`` -- the runner's validation NLL / KL -- is two
+library calls (``_loss.SceneLossMixin``: the sequence encoder over all frames, the teacher-forced decoding loop); training
+(``is_train=True``) is not part of this path.  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -17,6 +18,7 @@ import torch.nn as nn
 from ... import _lib
 from ..seq2seq.encoder import gumbel_softmax_hard
 from ..seq2seq.field import _CoordinateEmbedding
+from ._loss import SceneLossMixin
 from ._rollout import SceneRolloutMixin
 from ._scene import ScenePack, _DynStepConfig, cached_workspace, pack_scenes      # noqa: F401  (ScenePack, pack_scenes: re-exported)
 from .decoder import Decoder
@@ -26,7 +28,7 @@ from .encoder import Encoder
 _DynFieldQueryParams = _lib.AetherDynFieldQueryParams
 
 
-class AetherDynamicVars(SceneRolloutMixin, nn.Module):
+class AetherDynamicVars(SceneLossMixin, SceneRolloutMixin, nn.Module):
     one_call_step = True       # predict_future's steps go through aether_dyn_step (False: the three staged calls + torch glue)
     _STEP_WS_CAPTURE_CHECK = "the step workspace must be reserved outside graph capture (reserve())"
 
@@ -37,6 +39,8 @@ class AetherDynamicVars(SceneRolloutMixin, nn.Module):
         self.num_edge_types = params.get("num_edge_types")
         self.gumbel_temp = params.get("gumbel_temp")
         self.kl_coef = params.get("kl_coef", 1.)                      # read by the training scripts
+        self._init_loss_config(params)
+        object.__setattr__(self.encoder, "_owner", self)              # Encoder.forward queries this model's field net
         self.num_dims = 2
         self.field_hidden = hidden_size = params["field_hidden"]
         if hidden_size % 32 != 0:
@@ -264,6 +268,19 @@ class AetherDynamicVars(SceneRolloutMixin, nn.Module):
         logits, prior_state = self.encoder.single_step_forward_batched(state, present, ni_t, gi_t, prior_state, field)
         last, dec_state, _ = self.single_step_forward(state, present, gi_t, dec_state, logits, True, field, uniform_t)
         return last, prior_state, dec_state
+
+    # -- calculate_loss(is_train=False): _loss.SceneLossMixin ------------------------------------------------------------------
+    def _encode_sequence(self, inputs, node_masks, node_inds, graph_info):
+        return self.encoder(inputs, node_masks, node_inds, graph_info)
+
+    def _loss_entries(self, lib):
+        head = (self._field_struct(), self.decoder._param_struct())
+        return (lib.aether_dyn_loss_rollout_workspace_bytes, lib.aether_dyn_loss_rollout, "aether_dyn_loss_rollout",
+                tuple(C.byref(h) for h in head))
+
+    def _loss_stage_step(self, state, mask, gi, decoder_hidden, logits, uniform_t, n_present):
+        field, _ = self.predict_field(state, mask, n_present=n_present)
+        return self.single_step_forward(state, mask, gi, decoder_hidden, logits, True, field, uniform_t, n_present=n_present)
 
     def _rollout_entries(self, lib):
         """The entries ``_predict_future_rollout`` / ``predict_future_packed`` (``_rollout.SceneRolloutMixin``) call."""

@@ -10,11 +10,12 @@ between hidden states on the caller's graph, sums them over ``edge2node_inds`` /
 ``input_r / _i / _n`` of the raw inputs.
 
 Sub-modules carry the reference's names and are created in its order, so a seeded construction or ``load_state_dict`` of a
-reference checkpoint gives the same weights (``encoder.reverse_rnn.*`` and ``encoder.encoder_fc_out.*`` are held and never
-read).  The computation runs in libaether_hip.so (``aether_dyn_dnri_*``, csrc/dyn_dnri.h) on the scene engine of
-``AetherDynamicVars``: the whole loop of 1 .. 256 scenes is ONE library call.  Not part of this path, each raising by name:
-``calculate_loss`` and the full-sequence ``encoder.forward`` (the posterior), ``predict_future_fixedwindow``,
-``get_prior_posterior``, ``get_edge_probs``, training mode, ``hard_sample=False``, CPU tensors.  A (scene, step) with exactly
+reference checkpoint gives the same weights (``encoder.reverse_rnn.*`` is held and never read: the reference's sequence encoder never calls it, :531-536).  The
+computation runs in libaether_hip.so (``aether_dyn_dnri_*``, csrc/dyn_dnri.h, csrc/dyn_loss.h) on the scene engine of
+``AetherDynamicVars``: the whole loop of 1 .. 256 scenes is ONE library call, and ``calculate_loss(is_train=False)`` -- the
+runner's validation NLL / KL -- is two (``_loss.SceneLossMixin``).  Not part of this path, each raising by name:
+``calculate_loss(is_train=True)``, ``predict_future_fixedwindow``, ``get_prior_posterior``, ``get_edge_probs``, training mode,
+``hard_sample=False``, CPU tensors.  A (scene, step) with exactly
 one present object is refused, as the engine refuses it for ``AetherDynamicVars``.
 """
 from __future__ import annotations
@@ -27,6 +28,7 @@ import torch.nn as nn
 from ... import _lib
 from ...knn import csr_by_receiver, knn_edges
 from ..seq2seq.encoder import _RefNRIMLP, _mlp_out, gumbel_softmax_hard
+from ._loss import SceneLossMixin, check_sequence_args, sequence_logits
 from ._rollout import SceneRolloutMixin
 from ._scene import _DynStepConfig, cached_workspace, f32
 
@@ -122,8 +124,29 @@ class DNRI_DynamicVars_Encoder(nn.Module):
             ps.prior_w[l], ps.prior_b[l] = ptr(lin.weight), ptr(lin.bias)
         return ps, len(layers), (layers[0].out_features if len(layers) > 1 else 0)
 
-    def forward(self, *args, **kwargs):
-        raise _lib.AetherHipError("DNRI_DynamicVars_Encoder.forward (the full-sequence posterior encoder) " + _NOT_HERE)
+    def _sequence_config(self):
+        """The configuration the sequence entry reads (the decoder's members are placeholders that pass its checks)."""
+        _, n_layers, prior_hidden = self._param_struct()
+        return _DynStepConfig(0, self.hidden_size, self.rnn_hidden_size, n_layers, prior_hidden, self.num_edges, 128, 0, 0, 0,
+                              _KNN_K, 1.0)
+
+    @torch.no_grad()
+    def forward(self, inputs, node_masks, all_node_inds, all_graph_info, normalized_inputs=None):
+        """dnri_dynamicvars.py:463-542 as ONE library call (``aether_dyn_dnri_sequence_logits``).  inputs [1, F, Nmax, 4],
+        node_masks [1, F, Nmax], all_node_inds[0][t]: the present objects of frame t (two or more) -> (prior_result,
+        encoder_result [1, sum_t E_t, K], forward_state).  The reference drops the forward LSTM state it computes (:506-509)
+        and never calls ``reverse_rnn`` (:531-536): every frame is an LSTM step from the zero state, the posterior head sees
+        [h | 0], and ``forward_state`` comes back as zeros.  ``reverse_rnn.*`` stays in the state_dict and is never read."""
+        if not inputs.is_cuda:
+            raise _cpu_error("DNRI_DynamicVars_Encoder.forward (the sequence encoder: prior and posterior logits)")
+        if self.training:
+            raise _lib.AetherHipError("the encoder uses BatchNorm running statistics (training mode is not part of this path): "
+                                      "call .eval() first")
+        check_sequence_args(inputs, normalized_inputs)
+        lib = _lib.load()
+        entries = (lib.aether_dyn_dnri_sequence_logits_workspace_bytes, lib.aether_dyn_dnri_sequence_logits,
+                   "aether_dyn_dnri_sequence_logits", (C.byref(self._param_struct()[0]),))
+        return sequence_logits(self, entries, self._sequence_config(), inputs, node_masks, all_node_inds)
 
     @torch.no_grad()
     def single_step_forward(self, inputs, node_masks, node_inds, all_graph_info, forward_state):
@@ -285,7 +308,7 @@ class DNRI_DynamicVars_Decoder(nn.Module):
         return pred_all, hidden
 
 
-class DNRIDynamicVars(SceneRolloutMixin, nn.Module):
+class DNRIDynamicVars(SceneLossMixin, SceneRolloutMixin, nn.Module):
     one_call_step = True       # predict_future is ONE library call (False: the staged calls + torch glue, step by step)
 
     def __init__(self, params, device="cuda"):
@@ -295,13 +318,11 @@ class DNRIDynamicVars(SceneRolloutMixin, nn.Module):
         self.num_edge_types = params.get("num_edge_types")
         self.gumbel_temp = params.get("gumbel_temp")
         self.kl_coef = params.get("kl_coef", 1.)                          # read by the training scripts
+        self._init_loss_config(params)
         if device is not None:
             self.to(device)
 
     # -- not part of the prediction path ---------------------------------------------------------------------------------------
-    def calculate_loss(self, *args, **kwargs):
-        raise _lib.AetherHipError("DNRIDynamicVars.calculate_loss " + _NOT_HERE)
-
     def predict_future_fixedwindow(self, *args, **kwargs):
         raise _lib.AetherHipError("DNRIDynamicVars.predict_future_fixedwindow " + _NOT_HERE)
 
@@ -362,6 +383,17 @@ class DNRIDynamicVars(SceneRolloutMixin, nn.Module):
         (node_inds[b][t], graph_info[b][t], uniform[t][b]) see ``predict_future_batched`` -- the reference raises there.
         Default: the whole loop is ONE library call; ``one_call_step = False`` runs the staged calls step by step."""
         return self._predict_future(inputs, masks, node_inds, graph_info, burn_in_masks, uniform)
+
+    # -- calculate_loss(is_train=False): _loss.SceneLossMixin ------------------------------------------------------------------
+    def _encode_sequence(self, inputs, node_masks, node_inds, graph_info):
+        return self.encoder(inputs, node_masks, node_inds, graph_info)
+
+    def _loss_entries(self, lib):
+        return (lib.aether_dyn_dnri_loss_rollout_workspace_bytes, lib.aether_dyn_dnri_loss_rollout, "aether_dyn_dnri_loss_rollout",
+                (C.byref(self.decoder._param_struct()),))
+
+    def _loss_stage_step(self, state, mask, gi, decoder_hidden, logits, uniform_t, n_present):
+        return self.single_step_forward(state, mask, gi, decoder_hidden, logits, True, uniform_t)
 
     def _staged_step(self, state, present, ni_t, gi_t, prior_state, dec_state, uniform_t):
         logits, prior_state = self.encoder.single_step_forward(state, present, ni_t, gi_t, prior_state)

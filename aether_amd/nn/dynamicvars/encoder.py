@@ -7,8 +7,8 @@ which this path does not use) and ``single_step_forward(inputs, node_masks, node
 forward_state, predicted_field) -> (prior_logits, forward_state)``.  The kNN graph of the present objects
 (``knn_edges``, :559-586), the feature transform (:505-557) and the LSTM / prior step run in libaether_hip.so
 (``aether_knn_edges``, ``aether_dyn_prior_step``); the state slots per fully connected pair (:684-694) are gathered
-and scattered here with torch indexing.  No CPU fallback; the full-sequence ``forward`` (posterior) is not part of
-this path.
+and scattered here with torch indexing.  ``forward`` (the sequence encoder of ``calculate_loss``, :588-670) is ONE library
+call over all frames (``aether_dyn_sequence_logits``).  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -20,7 +20,8 @@ import torch.nn as nn
 from ... import _lib
 from ...knn import csr_by_receiver, knn_edges
 from ..seq2seq.encoder import _AnisotropicEdgeFilter, _RefNRIMLP, _mlp_out, filter_image
-from ._scene import cached_workspace, f32
+from ._loss import check_sequence_args, sequence_logits
+from ._scene import _DynStepConfig, cached_workspace, f32
 
 
 _DynPriorParams = _lib.AetherDynPriorParams
@@ -108,6 +109,35 @@ class Encoder(nn.Module):
         # the filter image follows in-place updates by itself (version counter)
         ps.filt_image = filter_image(self.__dict__.setdefault("_img_cache", {}), "filt", w, 15, w.shape[1]).data_ptr()
         return ps, hit[3], hit[4]
+
+    @torch.no_grad()
+    def forward(self, inputs, node_masks, all_node_inds, all_graph_info, normalized_inputs=None, predicted_field=None):
+        """aether_dynamicvars.py:588-670 as ONE library call (``aether_dyn_sequence_logits``).  inputs [1, F, Nmax, 4],
+        node_masks [1, F, Nmax], all_node_inds[0][t]: the present objects of frame t (two or more) -> (prior_result,
+        encoder_result [1, sum_t E_t, K], forward_state).  The reference drops the forward LSTM state it computes (:632-635)
+        and never calls ``reverse_rnn`` (:657-662): every frame is an LSTM step from the zero state, the posterior head sees
+        [h | 0], and ``forward_state`` comes back as zeros.  ``reverse_rnn.*`` stays in the state_dict and is never read.
+        The field at the present rows is computed inside the call from the owning model's field net -- what
+        ``predict_field(inputs, node_masks)`` gives, which is all the reference ever passes (:160-165); ``predicted_field`` is
+        accepted for the signature and not read.  An encoder built outside an ``AetherDynamicVars`` has no field net and
+        raises."""
+        if not inputs.is_cuda:
+            raise _lib.AetherHipError("aether_amd Encoder runs on an MI355X only; got a CPU tensor "
+                                      "(there is no CPU fallback)")
+        if self.training:
+            raise _lib.AetherHipError("the encoder uses BatchNorm running statistics: call .eval() first")
+        check_sequence_args(inputs, normalized_inputs)
+        owner = self.__dict__.get("_owner")
+        if owner is None:
+            raise _lib.AetherHipError("Encoder.forward queries the field net of the AetherDynamicVars that owns the encoder; "
+                                      "this encoder has none")
+        lib = _lib.load()
+        ps, n_layers, prior_hidden = self._param_struct()
+        cfg = _DynStepConfig(owner.field_hidden, self.hidden_size, self.rnn_hidden_size, n_layers, prior_hidden, self.num_edges,
+                             128, 0, 1 if self.pos_representation == "polar" else 0, 0, 10, 1.0)   # (decoder members: placeholders)
+        entries = (lib.aether_dyn_sequence_logits_workspace_bytes, lib.aether_dyn_sequence_logits, "aether_dyn_sequence_logits",
+                   (C.byref(owner._field_struct()), C.byref(ps)))
+        return sequence_logits(self, entries, cfg, inputs, node_masks, all_node_inds)
 
     @torch.no_grad()
     def single_step_forward(self, inputs, node_masks, node_inds, all_graph_info, forward_state, predicted_field,

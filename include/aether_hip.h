@@ -1403,6 +1403,82 @@ int aether_dyn_dnri_rollout_batched(const AetherDynDnriPriorParams* prior_params
                                     void* stream);
 
 /*
+ * The evaluation half of calculate_loss of both variable-N models (aether_dynamicvars.py:152-207, dnri_dynamicvars.py:70-114),
+ * as the inD runner calls it for its validation NLL / KL (is_train=False): two calls per sequence.
+ *
+ * aether_dyn_sequence_logits / aether_dyn_dnri_sequence_logits replace Encoder.forward (aether_dynamicvars.py:588-670,
+ * dnri_dynamicvars.py:463-542) on the F = T - 1 frames of one sequence.  The reference never writes its forward LSTM state
+ * back (tmp_state0 / tmp_state1 are built and dropped, :632-635 / :506-509) and its reverse pass never calls reverse_rnn
+ * (:657-662 / :531-536), so for every frame t
+ *     h_t = LSTMcell(compute_feat_transform(frame t), (0, 0)),  prior = prior_fc_out(h_t),  posterior = encoder_fc_out([h_t | 0])
+ * and the frames are independent: they run as F scenes of ONE prior stage -- present rows, the field at them (Aether), the
+ * encoder's own kNN graphs and their receiver CSR, the feature transform (the kernels of the prior step), one LSTM kernel from
+ * the zero state (no W_hh product, no state loads, no slots) and the two heads, whose layers of equal depth share a launch; the
+ * posterior head's first Linear reads the first R of its 2R weight columns in place.
+ *   frames [F][n_objects_max][4], masks [F][n_objects_max]; HOST arrays n_present, n_edges [F] with n_edges[t] =
+ *   n_present[t] * min(knn_k, n_present[t] - 1);  prior_logits, posterior_logits [sum_t n_edges[t]][K]: frames in time order,
+ *   edges in the order of the encoder's kNN graph (aether_knn_edges) -- the layout calculate_loss slices by step (:181-188).
+ *   posterior_params: encoder_fc_out, posterior_layers (1..4) Linear layers with ELU between, hidden size posterior_hidden
+ *   (a multiple of 16; ignored with one layer); w[0] is [.][2 rnn_hidden].
+ * F <= 256 per call; a longer sequence is split by the caller, and the result does not depend on the split.  Refused before
+ * anything is queued (AETHER_EINVAL): null pointers, F outside 1..256, an n_edges that disagrees with n_present, and a frame
+ * with fewer than two present objects (the reference's encoder drops such a frame from the logits while its loss loop does
+ * not; the runner skips such sequences, experiments/ind/train_dynamicvars.py:166-174).  A mask that disagrees with n_present
+ * makes every logit NaN and the next call return AETHER_EHIP (async error word).
+ *
+ * aether_dyn_loss_rollout / aether_dyn_dnri_loss_rollout are the body of calculate_loss's loop (:171-193 / :83-100) for one
+ * sequence: for step t the state is inputs[t] when t == 0 or t is teacher-forced (teacher_forcing_steps: -1 = every step,
+ * otherwise the steps t < teacher_forcing_steps; teacher_forcing=False is 0), else predictions[t - 1] -- an object that first
+ * appears then enters with the all-zero row the reference feeds (:176, :866-868).  Per step: the present rows, the field at
+ * them (Aether), the hard Gumbel sample of logits[sum_{s<t} n_edges[s] ...] with uniform[t], and the decoder step on the data
+ * set's graph of the step, from a zero decoder state.  No prior stage, no LSTM slots, no kNN graph.
+ *   inputs [n_steps (+ 1)][n_objects_max][4], masks [n_steps][n_objects_max]; HOST arrays n_present, n_edges, in_degree
+ *   [n_steps] and per-step device pointers graph_send, graph_recv, edge2node, uniform as aether_dyn_rollout takes them;
+ *   logits [sum_t n_edges[t]][K]: the slice the caller decodes with (posterior or prior);
+ *   predictions [n_steps][n_objects_max][4], zero at absent rows;  edge_types [n_edges[n_steps - 1]][K]: the last step's
+ *   one-hot sample, or NULL.
+ * Everything is validated on the host before the first launch (the refusals above, plus the in_degree rule of
+ * aether_dyn_step_batched): a refused call has queued nothing and written nothing.  No host synchronisation.  The decoder
+ * stage is the one of aether_dyn_step (same kernels, same order), computing its own node frames.
+ */
+typedef struct AetherDynPosteriorParams {
+    const float* w[4]; const float* b[4];                      /* encoder_fc_out: [.][2R] first, [K][.] last */
+} AetherDynPosteriorParams;
+size_t aether_dyn_sequence_logits_workspace_bytes(const AetherDynStepConfig* config, int posterior_layers, int posterior_hidden,
+                                                  int n_frames, int n_objects_max, const int64_t* n_present,
+                                                  const int64_t* n_edges);
+int aether_dyn_sequence_logits(const AetherDynFieldQueryParams* field_params, const AetherDynPriorParams* prior_params,
+                               const AetherDynPosteriorParams* posterior_params, const AetherDynStepConfig* config,
+                               int posterior_layers, int posterior_hidden, int n_frames, int n_objects_max,
+                               const int64_t* n_present, const int64_t* n_edges, const float* frames, const float* masks,
+                               float* prior_logits, float* posterior_logits, void* workspace, size_t workspace_bytes,
+                               void* stream);
+size_t aether_dyn_dnri_sequence_logits_workspace_bytes(const AetherDynStepConfig* config, int posterior_layers,
+                                                       int posterior_hidden, int n_frames, int n_objects_max,
+                                                       const int64_t* n_present, const int64_t* n_edges);
+int aether_dyn_dnri_sequence_logits(const AetherDynDnriPriorParams* prior_params, const AetherDynPosteriorParams* posterior_params,
+                                    const AetherDynStepConfig* config, int posterior_layers, int posterior_hidden, int n_frames,
+                                    int n_objects_max, const int64_t* n_present, const int64_t* n_edges, const float* frames,
+                                    const float* masks, float* prior_logits, float* posterior_logits, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+size_t aether_dyn_loss_rollout_workspace_bytes(const AetherDynStepConfig* config, int n_objects_max, int n_steps,
+                                               const int64_t* n_present, const int64_t* n_edges, const int* in_degree);
+int aether_dyn_loss_rollout(const AetherDynFieldQueryParams* field_params, const AetherDynDecoderParams* decoder_params,
+                            const AetherDynStepConfig* config, int n_objects_max, int n_steps, int teacher_forcing_steps,
+                            const float* inputs, const float* masks, const int64_t* n_present, const int64_t* n_edges,
+                            const int* in_degree, const int64_t* const* graph_send, const int64_t* const* graph_recv,
+                            const int64_t* const* edge2node, const float* logits, const float* const* uniform,
+                            float* predictions, float* edge_types, void* workspace, size_t workspace_bytes, void* stream);
+size_t aether_dyn_dnri_loss_rollout_workspace_bytes(const AetherDynStepConfig* config, int n_objects_max, int n_steps,
+                                                    const int64_t* n_present, const int64_t* n_edges, const int* in_degree);
+int aether_dyn_dnri_loss_rollout(const AetherDynDnriDecoderParams* decoder_params, const AetherDynStepConfig* config,
+                                 int n_objects_max, int n_steps, int teacher_forcing_steps, const float* inputs,
+                                 const float* masks, const int64_t* n_present, const int64_t* n_edges, const int* in_degree,
+                                 const int64_t* const* graph_send, const int64_t* const* graph_recv,
+                                 const int64_t* const* edge2node, const float* logits, const float* const* uniform,
+                                 float* predictions, float* edge_types, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Scene pack: the data side of the variable-N family on the device.  Replaces, for B scenes and every frame at once, what
  * the reference's data set builds per scene and per frame on the host (experiments/ind/single_ind_data.py:70-89):
  * node_inds = mask[step].nonzero()[:, -1] (:82) and get_knn_graph_info (:186-217) -- the kNN graph of the frame's
