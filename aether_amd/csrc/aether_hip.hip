@@ -43,6 +43,7 @@
 #include "s2s_charges.h"
 #include "s2s_locs.h"
 #include "s2s_dnri.h"
+#include "s2s_dnri_aether.h"
 #include "dynfield.h"
 #include "s2s_dynfield.h"
 #include "knn.h"
@@ -1059,6 +1060,7 @@ const char* aether_last_error(void) { return g_err; }
 #include "host_s2s_dynfield.inc"
 #include "host_s2s_locs.inc"
 #include "host_s2s_dnri.inc"
+#include "host_s2s_dnri_aether.inc"
 #include "host_dynamicvars.inc"
 #include "host_dyn_step.inc"
 #include "host_dyn_dnri.inc"

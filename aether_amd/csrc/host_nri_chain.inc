@@ -252,15 +252,20 @@ int nri_dnri_decoder(const DecoderParams* q, const NriDnriDecoder& d, Aggregate&
                                                                            d.M, hd, E);
     if (int rc = nri_dnri_msg2(3, q->msg_fc2_w, q->msg_fc2_b, d, st)) return rc;
     aggregate();
-    // GRU-style gate on the raw inputs
+    // GRU-style gate on the raw inputs (ldx <= 6 columns), or on [inputs | field] of DNRIAether at D = 3 (9 columns)
     T.n = 0;
     T.j[T.n++] = nri_with(s2s_job(0, q->hidden_r_w, hd, nullptr, d.agg, hd, d.hr, hd, hd, hd, Nn), d.img_hr);
     T.j[T.n++] = nri_with(s2s_job(0, q->hidden_i_w, hd, nullptr, d.agg, hd, d.hi, hd, hd, hd, Nn), d.img_hi);
     T.j[T.n++] = nri_with(s2s_job(0, q->hidden_h_w, hd, nullptr, d.agg, hd, d.hh, hd, hd, hd, Nn), d.img_hh);
     if (int rc = s2s_launch_jobs(T, st)) return rc;
-    k_s2s_dnri_gate<<<nri_blocks(Nn * (hd / 4)), dim3(256), 0, st>>>(d.x_in, d.ldx, q->input_r_w, q->input_r_b, q->input_i_w,
-                                                                     q->input_i_b, q->input_n_w, q->input_n_b, d.hr, d.hi, d.hh,
-                                                                     d.dh_in, d.dh_out, hd, Nn);
+    if (d.ldx > 6)
+        k_s2s_dnria_gate<<<nri_blocks(Nn * (hd / 4)), dim3(256), 0, st>>>(d.x_in, d.ldx, q->input_r_w, q->input_r_b, q->input_i_w,
+                                                                          q->input_i_b, q->input_n_w, q->input_n_b, d.hr, d.hi, d.hh,
+                                                                          d.dh_in, d.dh_out, hd, Nn);
+    else
+        k_s2s_dnri_gate<<<nri_blocks(Nn * (hd / 4)), dim3(256), 0, st>>>(d.x_in, d.ldx, q->input_r_w, q->input_r_b, q->input_i_w,
+                                                                         q->input_i_b, q->input_n_w, q->input_n_b, d.hr, d.hi, d.hh,
+                                                                         d.dh_in, d.dh_out, hd, Nn);
     if (int rc = nri_one(st, s2s_job(2, q->out1_w, hd, q->out1_b, d.dh_out, hd, d.o1, hd, hd, hd, Nn), d.img_out1)) return rc;
     return nri_one(st, s2s_job(2, q->out2_w, hd, q->out2_b, d.o1, hd, d.o2, hd, hd, hd, Nn), d.img_out2);
 }

@@ -67,6 +67,13 @@ struct DnriStepLayout {
     }
 };
 
+// The field of the ablation DNRIAether (host_s2s_dnri_aether.inc): its parameters, the images of field_net.0 / .2 in the plan
+// and the field query's rows in the workspace (byte offsets behind DnriPlanLayout / DnriStepLayout)
+struct DnriFieldArgs {
+    const AetherS2SFieldParams* fp;
+    size_t i_f0, i_f2, gamma, fh1, fh2, field, ext;
+};
+
 struct DnriArgs : DnriSizes {
     const AetherS2SDnriPriorParams* pp; const AetherS2SDnriDecoderParams* dp; const AetherS2SDnriMlpParams* mp;
     const char* plan;
@@ -75,7 +82,15 @@ struct DnriArgs : DnriSizes {
     DnriStepLayout L;
     const float* ext_logits = nullptr;          // the decoder on given logits: the prior is skipped
     float* features_out = nullptr;              // the prior stops behind mlp4 and leaves its rows there
+    // DNRIAether (null: dNRI): every layer on the raw state reads ext = [inputs | field] (3D columns) instead.  ext_field
+    // [Nn][D] (or null: the step queries the field) and field_out (or null) are those of the step at hand
+    const DnriFieldArgs* fld = nullptr;
+    const float* ext_field = nullptr;
+    float* field_out = nullptr;
 };
+
+// The node side of a DNRIAether step (host_s2s_dnri_aether.inc): field query, ext, edge counters, the MLP decoder's node rows
+int s2s_dnria_node_side(const DnriArgs& a, char* ws, const float* x_in, const AetherS2SDnriMlpParams* mp, hipStream_t st);
 
 // Used edge types of the MLP decoder (-1: the recurrent decoder; 0: no decoder, both, or no used type)
 int s2s_dnri_ku(const void* dp, const void* mp, int K, int skip_first) {
@@ -130,7 +145,9 @@ int s2s_dnri_front(const DnriArgs& a, char* ws, const float* x_in, const float* 
     int64_t* lists = reinterpret_cast<int64_t*>(ws + L.lists);
     // the step's edge counters; for the MLP decoder (when the step decodes) the raw state where out_fc1 reads it and the node
     // products of its first message layer
-    {
+    if (a.fld) {
+        if (int rc = s2s_dnria_node_side(a, ws, x_in, edges != nullptr ? a.mp : nullptr, st)) return rc;
+    } else {
         const AetherS2SDnriMlpParams* mp = edges != nullptr ? a.mp : nullptr;
         const int per = a.hd / 4 > S2S_RFG ? a.hd / 4 : S2S_RFG;
         const float* none = nullptr;
@@ -140,7 +157,11 @@ int s2s_dnri_front(const DnriArgs& a, char* ws, const float* x_in, const float* 
             mp ? mp->msg_fc1_b[2] : none, mp ? mp->msg_fc1_b[3] : none, K, k0, m.wp(L.A), m.wp(L.S), a.hd, per);
     }
     if (a.ext_logits == nullptr) {
-        // mlp1 on the raw state (:405): its first Linear has 2D columns -- a narrow layer
+        // mlp1 on the raw state (:405): its first Linear has 2D columns -- a narrow layer (DNRIAether: 3D columns of ext)
+        if (a.fld)
+            k_s2s_dnria_narrow_elu<<<nri_blocks(Nn * (he / 4)), dim3(256), 0, st>>>(p->mlp_w0[0], p->mlp_b0[0], m.wp(a.fld->ext), 3 * D,
+                                                                                    m.wp(L.X1a), he, Nn);
+        else
         { NarrowLayers N1{};
           N1.W[0] = p->mlp_w0[0]; N1.b[0] = p->mlp_b0[0]; N1.Y[0] = m.wp(L.X1a); N1.n = 1;
           k_s2s_narrow_layers<<<nri_blocks(Nn * (he / 4)), dim3(256), 0, st>>>(N1, x_in, 2 * D, 2 * D, he, 4, Nn); }
@@ -190,10 +211,10 @@ int s2s_dnri_step_impl(const DnriArgs& a, char* ws, const float* x_in, const flo
     const NriDnriDecoder d{{m.im(P.i_a[0]), m.im(P.i_a[1]), m.im(P.i_a[2]), m.im(P.i_a[3])},
                            {m.im(P.i_s[0]), m.im(P.i_s[1]), m.im(P.i_s[2]), m.im(P.i_s[3])},
                            {m.im(P.i_msg2[0]), m.im(P.i_msg2[1]), m.im(P.i_msg2[2]), m.im(P.i_msg2[3])}, m.im(P.i_hr), m.im(P.i_hi),
-                           m.im(P.i_hh2), m.im(P.i_out1), m.im(P.i_out2), x_in, dh_in, edges, edges,
+                           m.im(P.i_hh2), m.im(P.i_out1), m.im(P.i_out2), a.fld ? m.wp(a.fld->ext) : x_in, dh_in, edges, edges,
                            reinterpret_cast<const int64_t*>(ws + L.lists), a.send, a.recv, reinterpret_cast<const int*>(ws + L.counts),
                            m.wp(L.A), m.wp(L.S), m.wp(L.Tm), m.wp(L.M), m.wp(L.agg), m.wp(L.hr), m.wp(L.hi), m.wp(L.hh), m.wp(L.o1),
-                           m.wp(L.o2), dh_out, 2 * D, hd, K, k0, Nn, E, false};
+                           m.wp(L.o2), dh_out, a.fld ? 3 * D : 2 * D, hd, K, k0, Nn, E, false};
     // the receiver | sender halves of msg_fc1 on the hidden state (:489-493, :508) ride in mlp1's launch
     auto first_jobs = [&](S2SJobs& F) {
         if (q == nullptr) return (int)AETHER_OK;
@@ -248,19 +269,13 @@ size_t aether_s2s_dnri_plan_bytes(const AetherS2SDnriDecoderParams* dp, const Ae
     return DnriPlanLayout(encoder_hidden, decoder_hidden, num_edge_types, rnn_hidden, prior_layers, prior_hidden, ku).total;
 }
 
-int aether_s2s_dnri_plan_build(const AetherS2SDnriPriorParams* pp, const AetherS2SDnriDecoderParams* dp,
-                               const AetherS2SDnriMlpParams* mp, int num_dims, int encoder_hidden, int decoder_hidden,
-                               int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, int skip_first, void* plan,
-                               size_t plan_bytes, void* stream) {
-    const char* what = "s2s_dnri_plan_build";
-    if (!pp || !plan) return s2s_fail(AETHER_EINVAL, what, "null pointer");
-    if ((dp != nullptr) == (mp != nullptr)) return s2s_fail(AETHER_EINVAL, what, "exactly one of the two decoders must be given");
-    const int D = num_dims, he = encoder_hidden, hd = decoder_hidden, K = num_edge_types, R = rnn_hidden;
-    const size_t need = aether_s2s_dnri_plan_bytes(dp, mp, D, he, hd, R, prior_layers, prior_hidden, K, skip_first);
-    if (int rc = s2s_plan_buffer_check(what, need, plan, plan_bytes)) return rc;
+namespace {
+// The plan's contents (after the entry's checks).  xcols: the columns of out_fc1 in front of the aggregated messages -- 2D, or
+// the 3D of DNRIAether's [inputs | field]
+int s2s_dnri_plan_fill(const AetherS2SDnriPriorParams* pp, const AetherS2SDnriDecoderParams* dp, const AetherS2SDnriMlpParams* mp,
+                       int xcols, int he, int hd, int R, int prior_layers, int prior_hidden, int K, int skip_first, char* base,
+                       hipStream_t st) {
     const DnriPlanLayout P(he, hd, K, R, prior_layers, prior_hidden, s2s_dnri_ku(dp, mp, K, skip_first));
-    hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)plan;
     auto fl = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     for (int l = 0; l < 4; ++l) {
@@ -293,10 +308,26 @@ int aether_s2s_dnri_plan_build(const AetherS2SDnriPriorParams* pp, const AetherS
         s2s_image(base, st, P.i_out2, dp->out2_w, hd, hd, hd);
     } else {
         for (int k = skip_first ? 1 : 0; k < K; ++k) s2s_image(base, st, P.i_msg2[k], mp->msg_fc2_w[k], hd, hd, hd);
-        k_s2s_dnri_pad_front<<<blocks((int64_t)hd * P.ldo1), dim3(256), 0, st>>>(mp->out1_w, 2 * D, S2S_RFG, hd, fl(P.o1p), hd);
+        k_s2s_dnri_pad_front<<<blocks((int64_t)hd * P.ldo1), dim3(256), 0, st>>>(mp->out1_w, xcols, S2S_RFG, hd, fl(P.o1p), hd);
         s2s_image(base, st, P.i_out1, fl(P.o1p), hd, P.ldo1, P.ldo1);
         s2s_image(base, st, P.i_out2, mp->out2_w, hd, hd, hd);
     }
+    return AETHER_OK;
+}
+}  // namespace
+
+int aether_s2s_dnri_plan_build(const AetherS2SDnriPriorParams* pp, const AetherS2SDnriDecoderParams* dp,
+                               const AetherS2SDnriMlpParams* mp, int num_dims, int encoder_hidden, int decoder_hidden,
+                               int rnn_hidden, int prior_layers, int prior_hidden, int num_edge_types, int skip_first, void* plan,
+                               size_t plan_bytes, void* stream) {
+    const char* what = "s2s_dnri_plan_build";
+    if (!pp || !plan) return s2s_fail(AETHER_EINVAL, what, "null pointer");
+    if ((dp != nullptr) == (mp != nullptr)) return s2s_fail(AETHER_EINVAL, what, "exactly one of the two decoders must be given");
+    const size_t need = aether_s2s_dnri_plan_bytes(dp, mp, num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers,
+                                                   prior_hidden, num_edge_types, skip_first);
+    if (int rc = s2s_plan_buffer_check(what, need, plan, plan_bytes)) return rc;
+    if (int rc = s2s_dnri_plan_fill(pp, dp, mp, 2 * num_dims, encoder_hidden, decoder_hidden, rnn_hidden, prior_layers, prior_hidden,
+                                    num_edge_types, skip_first, (char*)plan, (hipStream_t)stream)) return rc;
     HIP_OK(hipGetLastError());
     return AETHER_OK;
 }

@@ -59,6 +59,12 @@ def _num_dims(params):
     return params["input_size"] // 2
 
 
+def _no_field_cols(params):
+    """Columns a layer on the raw state reads besides the state itself: none in dNRI; the field's D in the sub-modules of
+    ``ablations.dnri_aether.DNRIAether``, which override ``_field_cols``."""
+    return 0
+
+
 class DNRI_Encoder(nn.Module):
     """Parameter holder of ``DNRI_Encoder`` (dnri.py:262-332), same creation / init order.  ``forward(inputs)`` is the
     full-sequence encoder in evaluation mode once the module belongs to a ``DNRI`` (the library's entries take the model's
@@ -83,7 +89,7 @@ class DNRI_Encoder(nn.Module):
         inp_size = params["input_size"]
         self.num_dims = _num_dims(params)
         self.hidden_size, self.rnn_hidden_size = hidden_size, rnn_hidden_size
-        self.mlp1 = _RefNRIMLP(inp_size, hidden_size, hidden_size)
+        self.mlp1 = _RefNRIMLP(inp_size + self._field_cols(params), hidden_size, hidden_size)
         self.mlp2 = _RefNRIMLP(hidden_size * 2, hidden_size, hidden_size)
         self.mlp3 = _RefNRIMLP(hidden_size, hidden_size, hidden_size)
         self.mlp4 = _RefNRIMLP(hidden_size * 3, hidden_size, hidden_size)
@@ -102,6 +108,7 @@ class DNRI_Encoder(nn.Module):
         if device is not None:
             self.to(device)
 
+    _field_cols = staticmethod(_no_field_cols)
     _graph = Encoder._graph
     _head = Encoder._head
     _sequence_heads = Encoder._sequence_heads
@@ -164,9 +171,10 @@ class DNRI_Decoder(nn.Module):
         self.hidden_r = nn.Linear(n_hid, n_hid, bias=False)
         self.hidden_i = nn.Linear(n_hid, n_hid, bias=False)
         self.hidden_h = nn.Linear(n_hid, n_hid, bias=False)
-        self.input_r = nn.Linear(input_size, n_hid, bias=True)
-        self.input_i = nn.Linear(input_size, n_hid, bias=True)
-        self.input_n = nn.Linear(input_size, n_hid, bias=True)
+        gate_in = input_size + self._field_cols(params)
+        self.input_r = nn.Linear(gate_in, n_hid, bias=True)
+        self.input_i = nn.Linear(gate_in, n_hid, bias=True)
+        self.input_n = nn.Linear(gate_in, n_hid, bias=True)
         self.out_fc1 = nn.Linear(n_hid, n_hid)
         self.out_fc2 = nn.Linear(n_hid, n_hid)
         self.out_fc3 = nn.Linear(n_hid, out_size)
@@ -177,6 +185,7 @@ class DNRI_Decoder(nn.Module):
             self.to(device)
 
     _has_state = True
+    _field_cols = staticmethod(_no_field_cols)
     _graph = RecurrentDecoder._graph
 
     def get_initial_hidden(self, inputs):
@@ -219,11 +228,12 @@ class DNRI_MLP_Decoder(nn.Module):
         if edge_types - (1 if params["skip_first"] else 0) < 1:
             raise ValueError("the decoder needs at least one used edge type (num_edge_types - skip_first >= 1)")
         self.edge_types = edge_types
-        self.msg_fc1 = nn.ModuleList([nn.Linear(2 * in_size, msg_hid) for _ in range(edge_types)])
+        ext_size = in_size + self._field_cols(params)
+        self.msg_fc1 = nn.ModuleList([nn.Linear(2 * ext_size, msg_hid) for _ in range(edge_types)])
         self.msg_fc2 = nn.ModuleList([nn.Linear(msg_hid, msg_out) for _ in range(edge_types)])
         self.msg_out_shape = msg_out
         self.skip_first_edge_type = params["skip_first"]
-        self.out_fc1 = nn.Linear(in_size + msg_out, n_hid)
+        self.out_fc1 = nn.Linear(ext_size + msg_out, n_hid)
         self.out_fc2 = nn.Linear(n_hid, n_hid)
         self.out_fc3 = nn.Linear(n_hid, in_size)
         self.num_vars = num_vars
@@ -234,6 +244,7 @@ class DNRI_MLP_Decoder(nn.Module):
             self.to(device)
 
     _has_state = False
+    _field_cols = staticmethod(_no_field_cols)
     _graph = RecurrentDecoder._graph
 
     def get_initial_hidden(self, inputs):
@@ -255,12 +266,15 @@ class DNRI_MLP_Decoder(nn.Module):
 
 
 class DNRI(_StepLoop, _EvalLoss, nn.Module):
+    _encoder_class, _decoder_classes = DNRI_Encoder, (DNRI_Decoder, DNRI_MLP_Decoder)
+    _features_entry = "aether_s2s_dnri_encoder_features"
+
     def __init__(self, params, device="cuda"):
         super().__init__()
         self.num_vars = params["num_vars"]
-        self.encoder = DNRI_Encoder(params)                                # creation order of dnri.py:14-19
+        self.encoder = self._encoder_class(params)                         # creation order of dnri.py:14-19
         self._markov = params.get("decoder_type", None) == "ref_mlp"
-        self.decoder = (DNRI_MLP_Decoder if self._markov else DNRI_Decoder)(params)
+        self.decoder = self._decoder_classes[1 if self._markov else 0](params)
         self.num_edge_types = params.get("num_edge_types")
         # training parameters the runner's scripts read or set (dnri.py:23-38); only evaluation runs here
         self.gumbel_temp = params.get("gumbel_temp")
@@ -309,11 +323,12 @@ class DNRI(_StepLoop, _EvalLoss, nn.Module):
         return out, dh_out, edges
 
     @torch.no_grad()
-    def _encoder_forward(self, inputs, max_edges_per_call=400_000):
+    def _encoder_forward(self, inputs, max_edges_per_call=400_000, field=None):
         """The full-sequence encoder (DNRI_Encoder.forward, dnri.py:371-401) in evaluation mode: inputs [B, T, N, 2D] ->
         (prior_logits, posterior_logits [B, T, E, K], prior_state).  The per-time-step features come from
         ``aether_s2s_dnri_encoder_features`` over chunks of T x B graphs, the recurrent half is the shared one
-        (``Encoder._sequence_heads``)."""
+        (``Encoder._sequence_heads``).  ``field`` [T, B, N, D] (DNRIAether only, whose entry takes it behind the inputs): the
+        field of the frames."""
         enc = self.encoder
         if enc.training:
             raise _lib.AetherHipError("the encoder uses BatchNorm running statistics: call .eval() first")
@@ -338,15 +353,16 @@ class DNRI(_StepLoop, _EvalLoss, nn.Module):
             t1 = min(T, t0 + chunk)
             G = (t1 - t0) * B
             send, recv, order, rowptr = enc._graph(G, N, dev)
-            need = lib.aether_s2s_dnri_workspace_bytes(D, he, hd, R, prior_hidden, K, G * N, G * E1)
+            need = getattr(lib, self._entries(hook)[2])(D, he, hd, R, prior_hidden, K, G * N, G * E1)
             ws = enc._cache.get("ws_dnri")
             if ws is None or ws.numel() < need or ws.device != dev:
                 ws = enc._cache["ws_dnri"] = torch.empty(need, dtype=torch.uint8, device=dev)
-            st = lib.aether_s2s_dnri_encoder_features(
-                C.byref(pe), *hook.decoders(self.decoder, pd), plan.data_ptr(), D, he, hd, R, n_layers, prior_hidden, K,
-                *hook.plan_tail, 0, N, G * N, G * E1, send.data_ptr(), recv.data_ptr(), order.data_ptr(), rowptr.data_ptr(),
-                x[t0:t1].data_ptr(), ws.data_ptr(), ws.numel(), feats[t0:t1].data_ptr(), stream)
-            _lib.check(st, "aether_s2s_dnri_encoder_features")
+            st = getattr(lib, self._features_entry)(
+                *hook.field(), C.byref(pe), *hook.decoders(self.decoder, pd), plan.data_ptr(), D, he, hd, R, n_layers,
+                prior_hidden, K, *hook.plan_tail, 0, N, G * N, G * E1, send.data_ptr(), recv.data_ptr(), order.data_ptr(),
+                rowptr.data_ptr(), x[t0:t1].data_ptr(), *(() if field is None else (field[t0:t1].data_ptr(),)), ws.data_ptr(),
+                ws.numel(), feats[t0:t1].data_ptr(), stream)
+            _lib.check(st, self._features_entry)
         return enc._sequence_heads(feats, B)
 
     def _sequence_logits(self, inputs):

@@ -1058,6 +1058,66 @@ int aether_s2s_dnri_encoder_features(const AetherS2SDnriPriorParams* prior, cons
                                      void* workspace, size_t workspace_bytes, float* features, void* stream);
 
 /*
+ * The seq2seq ablation DNRIAether of nn/seq2seq/ablations/dnri_aether.py (--model_type nn.seq2seq.ablations.dnri_aether.
+ * DNRIAether): dNRI whose encoder and decoders also read the field the model discovers, without local frames.  The field is
+ * Aether's: predict_field (:81-85) = field_net(RFF(position)), AetherS2SFieldParams.  ext = [inputs | field] (3D columns) takes
+ * the place of the raw state in mlp1's first Linear (:320, :416, :446), in input_r / _i / _n of DNRI_Decoder (:498-500, :564-569)
+ * and in msg_fc1[k] / out_fc1 of DNRI_MLP_Decoder (:601, :608, :632-636, :669); both decoders return inputs + prediction on the
+ * 2D-wide state (:580, :677).  The entries are aether_s2s_dnri_*'s with `field` in front and the arguments named below; the
+ * three parameter structs are dNRI's with the wider first-layer tensors: mlp_w0[0] [he][3D], input_*_w [hd][3D], the MLP
+ * decoder's msg_fc1_w[k] [hd][6D] and out1_w [hd][3D + hd].
+ *   aether_s2s_dnri_aether_plan_bytes / _plan_build : dNRI's plan (out_fc1 padded from 3D + hd columns) and the fp16 x 2 images of
+ *                                              field_net.0 / .2
+ *   aether_s2s_dnri_aether_workspace_bytes   : dNRI's workspace and the field query's rows (RFF, two hidden layers, field, ext);
+ *                                              nothing of a frame
+ *   aether_s2s_dnri_aether_step              : predict_field, DNRI_Encoder.single_step_forward (:443-467), the hard Gumbel sample
+ *                                              and the decoder (single_step_forward :87-94) as one call.  ext_field [n_nodes][D]
+ *                                              != NULL: the field is handed in and no field launch is made (`field` may then be
+ *                                              NULL); ext_logits as for dNRI (with both it is single_step_forward itself, as
+ *                                              calculate_loss :119-122 calls it); field_out (or NULL) [n_nodes][D]: the field the
+ *                                              step used
+ *   aether_s2s_dnri_aether_rollout           : the loops of predict_future (:142-172).  burn_in_field (NULL or [burn_in_steps]
+ *                                              [n_nodes][D]): the field of the burn-in frames, known before the loop (:148-149);
+ *                                              the predicted steps query theirs from their own predictions (:161)
+ *   aether_s2s_dnri_aether_encoder_features  : the per-time-step half of DNRI_Encoder.forward (:409-425) on a flattened batch of
+ *                                              (time, graph) items; field_in (NULL: queried) [n_nodes][D] the field of those frames
+ * Sizes, status codes and stream order as aether_s2s_dnri_*; AETHER_EINVAL also when `field` is NULL and a step has to query.
+ */
+size_t aether_s2s_dnri_aether_plan_bytes(const AetherS2SDnriDecoderParams* decoder, const AetherS2SDnriMlpParams* mlp, int num_dims,
+                                         int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden,
+                                         int num_edge_types, int skip_first);
+int aether_s2s_dnri_aether_plan_build(const AetherS2SFieldParams* field, const AetherS2SDnriPriorParams* prior,
+                                      const AetherS2SDnriDecoderParams* decoder, const AetherS2SDnriMlpParams* mlp, int num_dims,
+                                      int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers, int prior_hidden,
+                                      int num_edge_types, int skip_first, void* plan, size_t plan_bytes, void* stream);
+size_t aether_s2s_dnri_aether_workspace_bytes(int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_hidden,
+                                              int num_edge_types, int64_t n_nodes, int64_t n_edges);
+int aether_s2s_dnri_aether_step(const AetherS2SFieldParams* field, const AetherS2SDnriPriorParams* prior,
+                                const AetherS2SDnriDecoderParams* decoder, const AetherS2SDnriMlpParams* mlp, const void* plan,
+                                int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
+                                int prior_hidden, int num_edge_types, int skip_first, int polar, int num_vars, float tau,
+                                int64_t n_nodes, int64_t n_edges, const int64_t* send, const int64_t* recv, const int64_t* order,
+                                const int64_t* rowptr, const float* inputs, const float* ext_field, const float* ext_logits,
+                                const float* decoder_hidden_in, const float* h0, const float* c0, const float* uniform,
+                                void* workspace, size_t workspace_bytes, float* outputs, float* decoder_hidden_out, float* h1,
+                                float* c1, float* edges_out, float* logits_out, float* field_out, void* stream);
+int aether_s2s_dnri_aether_rollout(const AetherS2SFieldParams* field, const AetherS2SDnriPriorParams* prior,
+                                   const AetherS2SDnriDecoderParams* decoder, const AetherS2SDnriMlpParams* mlp, const void* plan,
+                                   int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
+                                   int prior_hidden, int num_edge_types, int skip_first, int polar, int num_vars, float tau,
+                                   int64_t n_nodes, int64_t n_edges, const int64_t* send, const int64_t* recv, const int64_t* order,
+                                   const int64_t* rowptr, int burn_in_steps, const float* burn_in, const float* burn_in_field,
+                                   int steps, const float* inputs, float* decoder_state, float* h, float* c, const float* uniform,
+                                   void* workspace, size_t workspace_bytes, float* predictions, float* edges_out, void* stream);
+int aether_s2s_dnri_aether_encoder_features(const AetherS2SFieldParams* field, const AetherS2SDnriPriorParams* prior,
+                                            const AetherS2SDnriDecoderParams* decoder, const AetherS2SDnriMlpParams* mlp, const void* plan,
+                                            int num_dims, int encoder_hidden, int decoder_hidden, int rnn_hidden, int prior_layers,
+                                            int prior_hidden, int num_edge_types, int skip_first, int polar, int num_vars,
+                                            int64_t n_nodes, int64_t n_edges, const int64_t* send, const int64_t* recv,
+                                            const int64_t* order, const int64_t* rowptr, const float* inputs, const float* field_in,
+                                            void* workspace, size_t workspace_bytes, float* features, void* stream);
+
+/*
  * k-nearest-neighbour edge builder for variable-N scenes: replaces Encoder.knn_edges
  * (nn/dynamicvars/aether_dynamicvars.py:559-586; the same method in the other *_dynamicvars.py) and the send /
  * recv half of get_knn_graph_info (experiments/ind/single_ind_data.py:186-217).

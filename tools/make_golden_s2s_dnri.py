@@ -114,8 +114,13 @@ def one_step(model, x0, B, N, E, z, dtype):
     return res, logits
 
 
-def fixture(out, D, dec, decoder_type):
-    import s2s_dnri_restatement as RS
+def fixture(out, D, dec, decoder_type, reference=reference, build_model=build_model, one_step=one_step, RS=None,
+            shared_encoder=True):
+    """The cases of one decoder into ``out``.  The keyword arguments are the model's own pieces: the generator of a model built
+    on dNRI (tools/make_golden_s2s_dnri_aether.py) passes its reference import, constructor, step and restatement;
+    ``shared_encoder``: both decoders' models compute the same prior step, which is stored once."""
+    if RS is None:
+        import s2s_dnri_restatement as RS
     from oracle import seq2seq_oracle as S
     with reference() as L:
         for ci, (tag, (B, N, skip)) in enumerate(CASES.items()):
@@ -164,7 +169,7 @@ def fixture(out, D, dec, decoder_type):
             # once (rec.).  The prior state [B, E, R] is the largest entry: its fp64 copy is left out (file size) -- the fp64
             # prior logits, a function of it, are kept
             front = ("prior_logits", "prior_h", "prior_c")
-            skip_keys = front if dec != "rec" else ()
+            skip_keys = front if dec != "rec" and shared_encoder else ()
             for k, v in s32.items():
                 if k not in skip_keys:
                     out[f"{pre}.ref.{k}"] = v.detach().numpy()
@@ -179,11 +184,12 @@ def fixture(out, D, dec, decoder_type):
             print(f"D={D} {dec} {tag}: noise seed {8000 + noise_seed}, margin {m:.3g}")
 
 
-def loss_fixture(out, D, dec, decoder_type):
+def loss_fixture(out, D, dec, decoder_type, reference=reference, build_model=build_model, RS=None):
     """calculate_loss(is_train=False, return_logits=True) for the two LOSS_CONFIGS of make_golden_seq2seq.py on the B2N5 case's
     model (T = 5: with val_teacher_forcing_steps 2 the last two steps run on the model's own predictions), fp32 and after
-    .double(); under <dec>.loss.<config>."""
-    import s2s_dnri_restatement as RS
+    .double(); under <dec>.loss.<config>.  Keyword arguments as ``fixture``."""
+    if RS is None:
+        import s2s_dnri_restatement as RS
     B, N, skip = CASES["B2N5"]
     E, TL = N * (N - 1), 5
     g = torch.Generator().manual_seed(7500 + D)
